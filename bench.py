@@ -222,6 +222,14 @@ def timed_region(fn, dist):
     return elapsed, out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 or float64), written after the timed region."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def call_site_rate(timeout_s=120):
     """The reference's UNCHANGED per-candidate call site (src/Tracking.cc:1886-1894: one blocking
     CUDAF::NMIWithCuda_noMask per candidate, here through host/cudaf_shim.hpp) measured by the C++ program
@@ -592,9 +600,16 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16, help="cap on oracle threads for the cpu_baseline leg")
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the ranks, have each report its rendezvous and the device it would select, touch no GPU, exit")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="c2 / c3 / c4: after the timed steps, write what the last timed step returned (the winner's index and score) "
+                         "as DIR/<name>.npy, to compare two builds output for output (the inputs are seeded: identical run to run)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config in ("stream", "e2e"):
+        ap.error("--dump-outputs covers the search configs c2 / c3 / c4")
     if args.gpus > 1 and "RANK" not in os.environ:  # plain `python3 bench.py --gpus N`: we are the launcher
         sys.exit(self_launch(args, sys.argv[1:]))
     if args.dry_launch:
@@ -685,6 +700,7 @@ def main():
     # one blocking nmi_search_grid call per step: the arguments are converted to C once (NmiContext.bind_search), the timed loop
     # makes the call and compares the winner -- the interpreter's per-call checks and conversions are harness, not library
     bound_search = ctx.bind_search(rs, ws) if dist is None else None
+    region = {}  # "winner": (index, score) of the last step run, read back by --dump-outputs
 
     def run_blocking(n):
         res = None
@@ -697,8 +713,8 @@ def main():
                 res = nmi.key_unpack(int(key.item()))
             if res[0] != planted_global:
                 sys.exit(f"rank {rank}: wrong winner {res} (expected index {planted_global})")
-
-    region = {}
+        if res is not None:
+            region["winner"] = res
 
     bucket = max(1, args.allreduce_bucket)
 
@@ -735,6 +751,8 @@ def main():
         bad = got[idx != planted_global]
         if bad.size:
             sys.exit(f"rank {rank}: {bad.size} wrong winners, e.g. {nmi.key_unpack(int(bad[0]))} (expected index {planted_global})")
+        if n:
+            region["winner"] = nmi.key_unpack(int(got[-1]))
 
     run = run_blocking if blocking_mode else run_async
 
@@ -762,6 +780,7 @@ def main():
     run(args.steps)
     sync_all()
     elapsed = time.perf_counter() - t0
+    last_winner = region["winner"]  # the measurements below run more steps: keep the timed region's last one
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -859,6 +878,9 @@ def main():
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_budget, args.cpu_threads)
         if world == 1 and not args.no_call_site and args.config == "c2":
             out["call_site"] = call_site_rate()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"best_index": np.array([last_winner[0]], np.float64),
+                                             "best_score": np.array([last_winner[1]], np.float32)})
         print(json.dumps(out))
     for c in ctxs:
         c.close()

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -40,6 +41,21 @@ def test_default_line_is_the_contracts_blocking_metric_with_throughput_beside_it
     assert d["collective_ranks"] == 1 and d["rccl"] is False
     rf = d["roofline"]
     assert rf["bound"] == "hbm" and rf["kernel"] == "nmi_grid_kernel" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
+
+
+def test_dump_outputs_hold_the_last_steps_winner_in_either_step_mode(tmp_path):
+    """--dump-outputs writes what the last timed step returned; the inputs are seeded, and the blocking call and the
+    back-to-back steps return the same winner to the bit."""
+    got = {}
+    for mode in ("blocking", "throughput"):
+        d = bench(*QUICK, f"--{mode}", "--dump-outputs", str(tmp_path / mode))
+        assert d["steps"] == 5 and d["ms_per_step"] > 0
+        got[mode] = {n: np.load(tmp_path / mode / f"{n}.npy") for n in ("best_index", "best_score")}
+        assert sorted(os.listdir(tmp_path / mode)) == ["best_index.npy", "best_score.npy"]
+    for g in got.values():
+        assert g["best_index"].dtype == np.float64 and g["best_score"].dtype == np.float32
+        assert g["best_index"].tolist() == [13 * 27 + 13] and 0 < g["best_score"][0] <= 1   # the planted centre cell
+    assert (got["blocking"]["best_score"].view(np.uint32) == got["throughput"]["best_score"].view(np.uint32)).all()
 
 
 def test_rccl_branch_with_one_rank():

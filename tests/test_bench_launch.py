@@ -65,6 +65,13 @@ def test_children_exit_code_is_relayed():
     assert p.returncode != 0 and "needs a HIP device" in (p.stderr + p.stdout)
 
 
+def test_refuses_no_timed_steps_and_dump_outputs_outside_the_search_configs():
+    p = run("--steps", "0")
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr and p.stdout.strip() == ""
+    p = run("--config", "stream", "--dump-outputs", "unused")
+    assert p.returncode == 2 and "--dump-outputs covers" in p.stderr
+
+
 def test_started_by_a_launcher_with_the_wrong_world_is_refused():
     p = run("--gpus", "4", "--dry-launch", env={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "2"})
     assert p.returncode != 0 and "WORLD_SIZE 2 does not match --gpus 4" in p.stderr

@@ -79,11 +79,11 @@ def test_cpp_class_replays_the_reference_driver(ref, tmp_path):
 
 
 def test_fixture_is_what_the_reference_build_prints(ref):
-    """In the build container (where /root/reference and oracle/_ref exist) the committed fixture must be reproducible
-    from the reference binary; on the GPU box the binary is absent and the fixture stands alone."""
+    """Where build() made oracle/_ref/ref_search_kernel (the reference's sources were at hand, oracle/Makefile) the committed
+    fixture must be reproducible from that binary; without it the fixture stands alone."""
     exe = os.path.join(ROOT, "oracle", "_ref", "ref_search_kernel")
-    if not (os.path.exists(exe) and os.path.exists("/root/reference/Thirdparty/Localization/nmiSearchKernel.cpp")):
-        pytest.skip("reference build not present (expected outside the build container)")
+    if not os.access(exe, os.X_OK):
+        pytest.skip("oracle/_ref/ref_search_kernel not built (the reference's sources were not available to build())")
     _, _, g = ref
     out = subprocess.run([exe], input=g["inputs"].tobytes(), capture_output=True, check=True, timeout=120).stdout
     assert out == g["outputs"].tobytes()
