@@ -32,7 +32,8 @@ extern "C" {
 
 #define NMI_HIP_ABI_VERSION 2 /* 2 (round 4): + nmi_pix_status, NMI_OPT_SPLIT 1; round 3 had added nmi_split_status,
                                  nmi_level_create_block, nmi_level_create_mesh_block, nmi_level_run_rccl, nmi_stream_submit_block and
-                                 changed NMI_OPT_TILE_QUEUE from queue items to entries per tile bin without a bump */
+                                 changed NMI_OPT_TILE_QUEUE from queue items to entries per tile bin without a bump; still 2 after
+                                 the purely additive nmi_warp_stack_masked, nmi_search_grid_masked, nmi_last_mask_counts */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -171,6 +172,44 @@ int nmi_search_grid_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_l
 int nmi_warp_homographies(const double K[9], const int32_t num_warp_xyz[3], const float step_rad_xyz[3],
                           double *h_forward /*[Wn][9]*/);
 int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward, int32_t Wn, uint8_t *d_warp_stack);
+
+/*
+ * Masked search: which pixels of the camera frame take part in the score.  The reference's entry point is
+ * CUDAF::NMIWithCuda_noMask (Thirdparty/CUDA_Functions/kernel.cuh:35-37, under "no masks:"); these are its masked siblings
+ * for the whole grid (new).
+ *
+ * A warp mask is uint8 [Wn][H][W] in the coordinates of the warp stack (top-down rows of the camera frame); nonzero = the
+ * pixel takes part, 0 = excluded.  For candidate (warp w, render s) pixel pos enters the joint histogram iff
+ *   mask[w][pos] != 0, and the background rule passes (use_bg = 0: both RAW intensities nonzero, before the >> shift);
+ * its render pixel is the one nmi_search_grid pairs with it (flipped when render_bottom_up).  len_w = popcount(mask[w])
+ * replaces W*H in the per-bin term fl32(p * fl32(log2(p))), p = fl32(c / len_w); like W*H it is not reduced by the
+ * background rule.  Trees, SUC / ENMI, the all-zero guard, the rating layout [Wn][S] and the arg-max rule are those of
+ * nmi_search_grid, so an all-ones mask gives nmi_search_grid's bits, and an empty mask (len_w = 0) scores 0.0 for every
+ * render of its warp.
+ *
+ * nmi_warp_stack_masked: nmi_warp_stack (the warp stack is byte-identical) plus the masks of the warps.  Pixel (x, y) of
+ * warp w is valid (1, else 0) when its fp32 source coordinate (xs, ys) -- computed as the warp computes it -- passes the
+ * warp's source test -2 < xs < W+1, -2 < ys < H+1, when every bilinear tap with nonzero weight lies inside the frame
+ * (x1 = floor(xs) >= 0, x1 + (xs != x1) <= W-1, the same for rows), and, given d_frame_mask (uint8 [H][W], nullable = all
+ * valid), when every such tap is nonzero in it.  The identity homography gives an all-ones mask and warp == frame.
+ * Enqueued on the context's stream, like nmi_warp_stack.
+ *
+ * nmi_search_grid_masked: nmi_search_grid with the masks; len_w is counted on the device from warp_masks (the source of
+ * truth: the masks need not come from nmi_warp_stack_masked).  A NULL warp_masks is NMI_ERR_INVALID_ARGUMENT.  Blocking
+ * exactly like nmi_search_grid.  Options that choose among nmi_search_grid's kernels (NMI_OPT_SPLIT*,
+ * NMI_OPT_CONTENT_PATH) do not apply: the masked search has one kernel, and its results do not depend on them.
+ *
+ * nmi_last_mask_counts: len_w of the latest masked search's first n warps (n <= its Wn) to host memory.  Blocking.
+ *
+ * Not masked (yet): captured levels, streams, shard / block / RCCL forms, the CUDAF shim, and render-side masks (those
+ * make len per candidate instead of per warp).
+ */
+int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask /* nullable: all valid */,
+                          const double *h_forward, int32_t Wn, uint8_t *d_warp_stack, uint8_t *d_warp_masks);
+int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S, const uint8_t *warp_stack,
+                           const uint8_t *warp_masks, int32_t Wn, float *ratings /* nullable */,
+                           int64_t *best_linear_idx, float *best_score);
+int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU

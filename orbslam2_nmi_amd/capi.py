@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "nmi_rccl_unique_id", "nmi_rccl_comm_init", "nmi_rccl_comm_destroy", "nmi_set_profiling", "nmi_last_kernel_ms",
     "nmi_set_option", "nmi_copy_term_table", "nmi_abi_version", "nmi_error_string", "nmi_last_error_detail", "nmi_get_info", "nmi_last_content", "nmi_sort_points", "nmi_sort_triangles",
     "nmi_split_status", "nmi_pix_status", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
+    "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts",
 )
 
 
@@ -84,6 +85,9 @@ def load_library(build_if_missing=False):
     lib.nmi_search_grid_block.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, u64p]
     lib.nmi_warp_homographies.argtypes = [C.POINTER(C.c_double), C.POINTER(i32), f32p, C.POINTER(C.c_double)]
     lib.nmi_warp_stack.argtypes = [vp, vp, C.POINTER(C.c_double), i32, vp]
+    lib.nmi_warp_stack_masked.argtypes = [vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp]
+    lib.nmi_search_grid_masked.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64p, f32p]
+    lib.nmi_last_mask_counts.argtypes = [vp, C.POINTER(i32), i32]
     lib.nmi_render_mvp.argtypes = [C.POINTER(RenderParams), f32p, f32p, f32p, f32p, f32p]
     lib.nmi_render_points.argtypes = [vp, vp, vp, C.c_int64, f32p, i32, C.c_float, vp]
     lib.nmi_texture_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
@@ -166,6 +170,16 @@ def render_mvp(rp, cam_pos, cam_look_at, cam_up, translation):
     if rc != NMI_OK:
         raise NmiError(rc, "nmi_render_mvp")
     return np.array(out, np.float32)
+
+
+def _dev_mask(t, ndim, what):
+    """A device mask tensor: uint8 or bool (the same bytes: nonzero = the pixel takes part), contiguous."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"{what} must be a device (HIP) torch tensor; the NMI path has no CPU implementation")
+    if t.dtype not in (torch.uint8, torch.bool) or t.dim() != ndim or not t.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous uint8 or bool tensor with {ndim} dims, got {t.dtype} {tuple(t.shape)}")
+    return t
 
 
 def _dev_u8(t, ndim, what):
@@ -387,6 +401,63 @@ class NmiContext:
                                              o.data_ptr()), "nmi_warp_stack")
         if sync:
             self.synchronize()
+        return out
+
+    def warp_stack_masked(self, frame, homographies, frame_mask=None, out=None, out_masks=None, sync=True):
+        """warp_stack plus the masks of its valid pixels (nmi_warp_stack_masked) -> (warps [Wn,H,W] u8, masks [Wn,H,W]).
+
+        frame_mask: optional device [H,W] uint8 / bool, nonzero = usable frame pixel.  out_masks may be uint8 or bool (default
+        uint8); mask bytes are 1 for a valid pixel, 0 otherwise.  The warps are byte-identical to warp_stack's."""
+        import torch
+        f = self._img(frame, "frame")
+        m = np.ascontiguousarray(homographies, np.float64).reshape(-1, 9)
+        wn = m.shape[0]
+        fm = None
+        if frame_mask is not None:
+            fm = _dev_mask(frame_mask, 2, "frame_mask")
+            if tuple(fm.shape) != (self.height, self.width):
+                raise ValueError(f"frame_mask is {tuple(fm.shape)}, context is {(self.height, self.width)}")
+        if out is None:
+            out = torch.empty((wn, self.height, self.width), dtype=torch.uint8, device=self.device)
+        if out_masks is None:
+            out_masks = torch.empty((wn, self.height, self.width), dtype=torch.uint8, device=self.device)
+        o, om = self._stack(out, "out"), self._mask_stack(out_masks, "out_masks")
+        if o.shape[0] != wn or om.shape[0] != wn:
+            raise ValueError("out / out_masks have the wrong number of warps")
+        self._order_after_torch()
+        self._check(self._lib.nmi_warp_stack_masked(self._h, f.data_ptr(), fm.data_ptr() if fm is not None else None,
+                                                    m.ctypes.data_as(C.POINTER(C.c_double)), wn, o.data_ptr(), om.data_ptr()),
+                    "nmi_warp_stack_masked")
+        if sync:
+            self.synchronize()
+        return out, out_masks
+
+    def _mask_stack(self, t, what):
+        t = _dev_mask(t, 3, what)
+        if tuple(t.shape[1:]) != (self.height, self.width):
+            raise ValueError(f"{what} is {tuple(t.shape)}, context images are {(self.height, self.width)}")
+        return t
+
+    def search_grid_masked(self, render_stack, warp_stack, warp_masks, ratings=None):
+        """search_grid with per-warp pixel masks (nmi_search_grid_masked) -> (best linear index w*S+s, best score).
+
+        warp_masks: device [Wn,H,W] uint8 or bool, nonzero = the pixel takes part; ratings as for search_grid."""
+        rs, ws = self._stack(render_stack, "render_stack"), self._stack(warp_stack, "warp_stack")
+        wm = self._mask_stack(warp_masks, "warp_masks")
+        S, Wn = rs.shape[0], ws.shape[0]
+        if wm.shape[0] != Wn:
+            raise ValueError(f"warp_masks has {wm.shape[0]} warps, warp_stack {Wn}")
+        rp = self._ratings_ptr(ratings, Wn, S)
+        idx, sc = C.c_int64(0), C.c_float(0)
+        self._order_after_torch()
+        self._check(self._lib.nmi_search_grid_masked(self._h, rs.data_ptr(), S, ws.data_ptr(), wm.data_ptr(), Wn, rp, C.byref(idx),
+                                                     C.byref(sc)), "nmi_search_grid_masked")
+        return int(idx.value), np.float32(sc.value)
+
+    def mask_counts(self, n):
+        """len_w (pixels taking part) of the first n warps of the latest masked search -> numpy int32 [n]."""
+        out = np.zeros(int(n), np.int32)
+        self._check(self._lib.nmi_last_mask_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)), "nmi_last_mask_counts")
         return out
 
     def render_points(self, xyz, red, mvps, point_size, out=None, sync=True):

@@ -670,6 +670,10 @@ int nmi_destroy(nmi_ctx *ctx)
     if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
     if (ctx->d_pair_rating) (void)hipFree(ctx->d_pair_rating);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_mask_counts) (void)hipFree(ctx->d_mask_counts);
+    if (ctx->d_mask_tables) (void)hipFree(ctx->d_mask_tables);
+    if (ctx->d_mask_redo) (void)hipFree(ctx->d_mask_redo);
+    if (ctx->d_mask_redo_state) (void)hipFree(ctx->d_mask_redo_state);
     if (ctx->d_zbuf) (void)hipFree(ctx->d_zbuf);
     mesh_work_free(&ctx->mesh);
     for (int i = 0; i < StagingRing::kSlots; ++i) {

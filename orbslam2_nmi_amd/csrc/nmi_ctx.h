@@ -121,6 +121,15 @@ struct nmi_ctx {
     hipEvent_t warp_ev[kWarpRing] = {};
     int warp_coeffs_cap = 0;
     unsigned warp_uses = 0;
+    // Masked search (nmi_capi_masked.cpp): per-warp mask counts and term tables, the redo list of its optimistic launch.
+    // Allocated on first use, grown on demand, freed by nmi_destroy.
+    int32_t *d_mask_counts = nullptr;     // [mask_warps_cap] len_w of the latest masked search
+    float *d_mask_tables = nullptr;       // [mask_warps_cap][npix + 1]
+    int mask_warps_cap = 0;
+    int mask_count_n = 0;                 // warps counted by the latest masked search
+    int32_t *d_mask_redo = nullptr;       // [mask_redo_cap] candidates to score again exactly
+    uint32_t *d_mask_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
+    int64_t mask_redo_cap = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     int hist_variant = 3;
     int phase_mask = 3;
