@@ -158,19 +158,24 @@ static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, co
 
 int main(int argc, char **argv)
 {
-    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--write-files DIR | --files DIR]
+    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--write-files DIR | --files DIR]
     //   --mesh: nmi_prop_RENDER 1, the reference's default render mode: the same surface as NX x NY quads = 2 NX NY textured
     //           triangles, default 300x200 = 120,000;  --density: points per pixel of a view along each axis (cloud; default 0.9)
+    //   --masked: the frame's bottom sixth is a "hood" (a flat grey band over the scene); a frame mask excludes it and the levels
+    //           are masked ones (nmi_level_set_masks: border masks of the rotated warps + the hood mask)
     //   --write-files DIR: write the map and a settings file into DIR and stop (no GPU needed)
     //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names
     //           (nmi_config_load, nmi_map_load_obj / _bmp / _xyz) instead of building them in memory
     int keyframes = 200, mesh_nx = 0, mesh_ny = 0;
     float density = 0.9f;
     const char *write_dir = nullptr, *read_dir = nullptr;
+    bool masked = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mesh")) {
             mesh_nx = 300, mesh_ny = 200;
             if (i + 1 < argc && sscanf(argv[i + 1], "%dx%d", &mesh_nx, &mesh_ny) == 2) ++i;
+        } else if (!strcmp(argv[i], "--masked")) {
+            masked = true;
         } else if (!strcmp(argv[i], "--density") && i + 1 < argc) {
             density = (float)atof(argv[++i]);
         } else if (!strcmp(argv[i], "--write-files") && i + 1 < argc) {
@@ -275,7 +280,7 @@ int main(int argc, char **argv)
     if (mesh) CHECK_NMI(nmi_texture_create(ctx, rgb.data(), tw, th, &tex));
     const int64_t n_prims = mesh ? (int64_t)(xyz.size() / 9) : (int64_t)red.size();
     float *d_xyz = nullptr, *d_red = nullptr;
-    uint8_t *d_frame = nullptr, *d_tmp = nullptr;
+    uint8_t *d_frame = nullptr, *d_tmp = nullptr, *d_hood = nullptr;
     CHECK_HIP(hipMalloc((void **)&d_xyz, xyz.size() * sizeof(float)));
     CHECK_HIP(hipMalloc((void **)&d_red, red.size() * sizeof(float)));
     CHECK_HIP(hipMalloc((void **)&d_frame, (size_t)W * H));
@@ -316,12 +321,23 @@ int main(int argc, char **argv)
                 const float val = (float)img[(size_t)(H - 1 - y) * W + x] + 16.0f * acc;
                 frame[(size_t)y * W + x] = (uint8_t)lrintf(fminf(fmaxf(val, 0.0f), 255.0f));
             }
+        if (masked) {
+            // the hood: a flat grey band over the bottom sixth of the frame, and the frame mask that excludes it
+            const int hood = H - H / 6;
+            std::vector<uint8_t> usable((size_t)W * H, 1);
+            for (int y = hood; y < H; ++y)
+                for (int x = 0; x < W; ++x) frame[(size_t)y * W + x] = 60, usable[(size_t)y * W + x] = 0;
+            CHECK_HIP(hipMalloc((void **)&d_hood, usable.size()));
+            CHECK_HIP(hipMemcpy(d_hood, usable.data(), usable.size(), hipMemcpyHostToDevice));
+            printf("masked levels: rows %d..%d of the frame are a hood, excluded by the frame mask\n", hood, H - 1);
+        }
         CHECK_HIP(hipMemcpy(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice));
     }
     if (mesh)
         CHECK_NMI(nmi_level_create_mesh(ctx, d_xyz, d_red, n_prims, tex, d_frame, 27, 27, &p.level));
     else
         CHECK_NMI(nmi_level_create(ctx, d_xyz, d_red, n_prims, d_frame, 27, 27, p.rp.point_size, &p.level));
+    if (masked) CHECK_NMI(nmi_level_set_masks(p.level, 1, d_hood));  // every replay: warp masks, counts, masked search
 
     // 3^6 grid with the steps of ETH_small.yaml:83-88
     NmiSearchKernel initial(3, 3, 3, 3, 3, 3, 0.2f, 0.2f, 0.5f, 0.02f, 0.02f, 0.05f);
@@ -379,6 +395,7 @@ int main(int argc, char **argv)
     (void)hipFree(d_red);
     (void)hipFree(d_frame);
     (void)hipFree(d_tmp);
+    if (d_hood) (void)hipFree(d_hood);
     nmi_destroy(ctx);
     printf("%s\n", ok ? "PIPELINE OK" : "PIPELINE FAILED");
     return ok ? 0 : 1;

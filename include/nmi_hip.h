@@ -33,7 +33,8 @@ extern "C" {
 #define NMI_HIP_ABI_VERSION 2 /* 2 (round 4): + nmi_pix_status, NMI_OPT_SPLIT 1; round 3 had added nmi_split_status,
                                  nmi_level_create_block, nmi_level_create_mesh_block, nmi_level_run_rccl, nmi_stream_submit_block and
                                  changed NMI_OPT_TILE_QUEUE from queue items to entries per tile bin without a bump; still 2 after
-                                 the purely additive nmi_warp_stack_masked, nmi_search_grid_masked, nmi_last_mask_counts */
+                                 the purely additive nmi_warp_stack_masked, nmi_search_grid_masked, nmi_last_mask_counts,
+                                 nmi_level_set_masks, nmi_level_copy_masks */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -311,6 +312,27 @@ int nmi_level_run_rccl(nmi_level *lv, const float *h_mvps, const double *h_forwa
  * table [Wn][S] (any pointer may be NULL).  Blocking; for tests and debugging (the reference's orb_prop_log dumps,
  * src/Tracking.cc:1911-1948, serve the same purpose). */
 int nmi_level_copy_outputs(nmi_level *lv, uint8_t *h_renders, uint8_t *h_warps, float *h_ratings);
+/*
+ * Masked levels.  nmi_level_set_masks turns masks on (enabled = 1) or off (0) for a level made by any of the four
+ * nmi_level_create* calls.  It captures the level's graph again and waits for a replay in flight.  Masked, every replay also
+ * computes the warps' masks, exactly as nmi_warp_stack_masked does for the same homographies and d_frame_mask, and their
+ * counts len_w, and scores with nmi_search_grid_masked's arithmetic (nmi_masked_grid_kernel, or the masked pixel-range
+ * kernel for mid-size grids): same renders, same masks, same ratings, winner and score bits as those calls made one after
+ * the other.  Blocks score their local warps with their own len_w and report global indices; empty blocks still take
+ * part in the RCCL exchange.
+ * d_frame_mask: uint8 [H][W], nonzero = usable, or NULL = border masks only.  Kept like d_frame: it must stay valid in
+ * place; its CONTENTS may change between runs.  enabled = 0 restores the unmasked graph (d_frame_mask must then be NULL)
+ * and frees the mask buffers.
+ * Memory: a masked level owns its masks (Wn x H x W bytes), its counts and its per-warp term tables, Wn x (H x W + 1)
+ * floats -- 44 MB for 27 warps at 848 x 480; both grow with Wn.  The tables are rebuilt only for the warps whose len_w
+ * changed since the previous replay (within a strategy level the warps, hence the counts, repeat), and are never shared
+ * with the standalone masked calls or with other levels.
+ * nmi_level_run, nmi_level_run_rccl, nmi_level_copy_outputs keep their meaning on a masked level.
+ */
+int nmi_level_set_masks(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask);
+/* Host copies of the latest replay's warp masks [Wn][H][W] and counts [Wn] (either pointer may be NULL).  Blocking.
+ * NMI_ERR_INVALID_ARGUMENT on a level without masks. */
+int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts);
 int nmi_level_destroy(nmi_level *lv);
 
 /*

@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "nmi_rccl_unique_id", "nmi_rccl_comm_init", "nmi_rccl_comm_destroy", "nmi_set_profiling", "nmi_last_kernel_ms",
     "nmi_set_option", "nmi_copy_term_table", "nmi_abi_version", "nmi_error_string", "nmi_last_error_detail", "nmi_get_info", "nmi_last_content", "nmi_sort_points", "nmi_sort_triangles",
     "nmi_split_status", "nmi_pix_status", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
-    "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts",
+    "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts", "nmi_level_set_masks", "nmi_level_copy_masks",
 )
 
 
@@ -101,6 +101,8 @@ def load_library(build_if_missing=False):
     lib.nmi_level_run_rccl.argtypes = [vp, f32p, C.POINTER(C.c_double), vp, i64p, f32p]
     lib.nmi_stream_submit_block.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(C.c_double), i32, i32, i32, vp, i64p]
     lib.nmi_level_copy_outputs.argtypes = [vp, vp, vp, vp]
+    lib.nmi_level_set_masks.argtypes = [vp, i32, vp]
+    lib.nmi_level_copy_masks.argtypes = [vp, vp, C.POINTER(i32)]
     lib.nmi_level_destroy.argtypes = [vp]
     lib.nmi_stream_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     lib.nmi_stream_destroy.argtypes = [vp]
@@ -678,6 +680,30 @@ class NmiLevel:
         t = np.empty((self.Wn, self.S), np.float32)
         self.ctx._check(self._lib.nmi_level_copy_outputs(self._h, r.ctypes.data, v.ctypes.data, t.ctypes.data), "nmi_level_copy_outputs")
         return r, v, t
+
+    def set_masks(self, enabled=True, frame_mask=None):
+        """Masked level (nmi_level_set_masks): every replay also computes the warps' masks (border masks, and frame_mask where
+        given) and scores with the masked search's arithmetic.  frame_mask: device [H,W] uint8 / bool, nonzero = usable, or None;
+        the level reads it in place on every replay (its contents may change between runs) and keeps it alive.
+        enabled=False restores the unmasked level."""
+        fm = None
+        if frame_mask is not None:
+            if not enabled:
+                raise ValueError("set_masks(enabled=False) takes no frame_mask")
+            fm = _dev_mask(frame_mask, 2, "frame_mask")
+            if tuple(fm.shape) != (self.ctx.height, self.ctx.width):
+                raise ValueError(f"frame_mask is {tuple(fm.shape)}, context is {(self.ctx.height, self.ctx.width)}")
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_masks(self._h, int(bool(enabled)), fm.data_ptr() if fm is not None else None),
+                        "nmi_level_set_masks")
+        self._frame_mask = fm  # the graph holds its device address
+
+    def masks(self):
+        """-> (warp masks [Wn,H,W] u8, counts [Wn] int32) of the latest run of a masked level, as numpy (host copies)."""
+        m = np.empty((self.Wn, self.ctx.height, self.ctx.width), np.uint8)
+        n = np.empty(self.Wn, np.int32)
+        self.ctx._check(self._lib.nmi_level_copy_masks(self._h, m.ctypes.data, n.ctypes.data_as(C.POINTER(C.c_int32))), "nmi_level_copy_masks")
+        return m, n
 
     def close(self):
         if self._h and self._h.value:

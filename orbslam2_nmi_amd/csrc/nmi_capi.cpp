@@ -181,7 +181,7 @@ static int ensure_slabs(nmi_ctx *ctx, int n)
 
 // nmi_pix_kernel's hand-off blocks: a buffer of their own -- the row-split kernel tags its granules with 16 bits in the top of
 // an 8-byte word, which a packed counter of the other kernel's layout can equal.
-static int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes)
+int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->pix_blocks_bytes) return NMI_OK;
     if (ctx->d_pix_blocks) {

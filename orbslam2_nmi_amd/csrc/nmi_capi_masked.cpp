@@ -1,5 +1,5 @@
 // nmi_capi_masked.cpp -- the masked entry points of include/nmi_hip.h: nmi_warp_stack_masked, nmi_search_grid_masked,
-// nmi_last_mask_counts.  Kernels: nmi_masked_producer.hip, nmi_masked_kernel.hip.
+// nmi_last_mask_counts.  Kernels: nmi_masked_producer.hip, nmi_masked_kernel.hip, nmi_masked_pix_kernel.hip (mid-size grids).
 #include "nmi_ctx.h"
 #include "nmi_masked.h"
 
@@ -110,22 +110,34 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
     m.redo = ctx->d_mask_redo;
     m.redo_n = ctx->d_mask_redo_state;
     m.redo_done = ctx->d_mask_redo_state + 1;
-    if (ctx->xcd_tiling && total <= (1ll << 24)) {
+    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
+    const int workgroups = (int)(total < cap ? total : cap);
+    // mid-size grids: pixel ranges (nmi_masked_pix_kernel.hip), by nmi_search_grid's rules and controls (choose_pix)
+    const int pix = choose_pix(ctx, a, total, cap);
+    if (pix) {
+        rc = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
+        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
+        if (rc == NMI_OK) rc = ensure_pix_timeouts(ctx);
+        if (rc != NMI_OK) return rc;
+        a.blocks = ctx->d_pix_blocks;
+        a.phase_mask = 3 | (ctx->phase_mask & 512);  // (bit 9: the helpers' hand-off test hook, as for nmi_pix_kernel)
+    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {
         rc = ensure_order(ctx, S, Wn, &a.order);
         if (rc != NMI_OK) return rc;
     }
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
-    const int workgroups = (int)(total < cap ? total : cap);
     // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid -- not the counts and tables before them
     if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    NMI_HIP_TRY(ctx, nmi::launch_grid_masked(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
+    if (pix)
+        NMI_HIP_TRY(ctx, nmi::launch_pix_masked(m, pix, pix_owner_share(ctx, pix), p.use_bg != 0, nullptr, ctx->d_pix_timeouts, ctx->stream));
+    else
+        NMI_HIP_TRY(ctx, nmi::launch_grid_masked(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
     // accepted: commit the protocol state (enqueue_grid's bookkeeping)
     if (post) ++ctx->seq;
     ctx->posted = post;
     ctx->last_slot = ctx->slot;
     ctx->slot ^= 1;
     ctx->last_parts = 0;
-    ctx->last_pix = 0;
+    ctx->last_pix = pix;
     ctx->last_epoch = 0;
     ctx->last_few = 0;
     if (ctx->profiling) {

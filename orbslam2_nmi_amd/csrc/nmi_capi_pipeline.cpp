@@ -1,6 +1,7 @@
 // nmi_capi_pipeline.cpp -- C ABI of the composed forms: one search level as a captured HIP graph (nmi_level_*) and the
 // double-buffered streaming pipeline (nmi_stream_*).  Declared in include/nmi_hip.h.
 #include "nmi_ctx.h"
+#include "nmi_masked.h"
 
 using namespace nmi_internal;
 
@@ -46,6 +47,24 @@ struct nmi_level {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
+    // What the graph is captured from (level_capture), kept so that nmi_level_set_masks can capture it again.
+    const float *d_xyz = nullptr, *d_attr = nullptr;
+    int64_t n_points = 0;
+    const nmi_texture *tex = nullptr;
+    const uint8_t *d_frame = nullptr;
+    nmi::GridArgs args{};                       // the search's arguments (unmasked form)
+    float *hd_mvps = nullptr, *hd_coeffs = nullptr;
+    int workgroups = 0;
+    size_t pix_blocks_bytes = 0;
+    // Masks (nmi_level_set_masks): the warps' masks and counts of the latest replay, the counts of the replay before (tables are
+    // rebuilt only for the warps whose count changed), the per-warp term tables, the redo list of the masked grid kernel.
+    bool masked = false;
+    const uint8_t *d_frame_mask = nullptr;
+    uint8_t *d_masks = nullptr;                 // [Wn][H][W]
+    int32_t *d_counts = nullptr;                // [3][Wn]: counts, previous counts, changed flags
+    float *d_tables = nullptr;                  // [Wn][npix + 1]
+    int32_t *d_redo = nullptr;                  // [S * Wn]
+    uint32_t *d_redo_state = nullptr;           // [2], zero between replays
 };
 
 extern "C" {
@@ -57,7 +76,8 @@ int nmi_level_destroy(nmi_level *lv)
     (void)hipStreamSynchronize(lv->ctx->stream);
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
-    void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks};
+    void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks,
+                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state};
     for (void *q : dev)
         if (q) (void)hipFree(q);
     void *host[] = {lv->h_mvps, lv->h_coeffs, lv->h_key};
@@ -72,6 +92,122 @@ int nmi_level_destroy(nmi_level *lv)
 }
 
 }  // extern "C"
+
+// Captures the level's graph (unmasked, or masked when lv->masked) and instantiates it, replacing the previous one only on
+// success.  The caller has waited for the stream.
+static int level_capture(nmi_level *lv)
+{
+    nmi_ctx *ctx = lv->ctx;
+    const nmi_params &p = ctx->params;
+    const int S = lv->S, Wn = lv->Wn;
+    const int64_t total = (int64_t)S * Wn;
+    const nmi_texture *tex = lv->tex;
+    const float *d_xyz = lv->d_xyz, *d_attr = lv->d_attr, *d_red = lv->d_attr;
+    const int64_t n_points = lv->n_points;
+    const uint8_t *d_frame = lv->d_frame;
+    float *hd_mvps = lv->hd_mvps, *hd_coeffs = lv->hd_coeffs;
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) {
+        if (e == hipSuccess) e = r;
+        return r == hipSuccess;
+    };
+    nmi::GridArgs a = lv->args;
+    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
+    // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
+    // (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the
+    // prep kernel keeps; the level keeps one epoch for all its captures (the replay count only grows, so tags never repeat).
+    lv->pix = choose_pix(ctx, a, total, cap);
+    if (lv->pix) {
+        const size_t bytes = nmi::pix_block_bytes((int)total, lv->pix);
+        if (bytes > lv->pix_blocks_bytes) {
+            if (lv->d_pix_blocks) ok(hipFree(lv->d_pix_blocks));
+            lv->d_pix_blocks = nullptr;
+            lv->pix_blocks_bytes = 0;
+            ok(hipMalloc((void **)&lv->d_pix_blocks, bytes));
+            if (e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
+            if (e == hipSuccess) lv->pix_blocks_bytes = bytes;
+        }
+        if (e == hipSuccess && lv->args.epoch == 0 && next_split_epoch(ctx, &lv->args.epoch) != NMI_OK) e = hipErrorOutOfMemory;
+        if (e == hipSuccess && ensure_pix_timeouts(ctx) != NMI_OK) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
+        a.epoch = lv->args.epoch;
+        a.blocks = lv->d_pix_blocks;
+        a.order = nullptr;
+    }
+    const int workgroups = lv->workgroups;
+    const bool masked = lv->masked;
+    nmi::MaskedGridArgs m{};
+    if (masked) {
+        m.g = a;
+        m.g.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;  // (bit 9: the pixel-range kernel's hand-off test hook)
+        m.warp_masks = lv->d_masks;
+        m.tables = lv->d_tables;
+        m.counts = lv->d_counts;
+        m.vec_ok = a.vec_ok && ((uintptr_t)lv->d_masks % 16) == 0;
+        m.redo = lv->d_redo;
+        m.redo_n = lv->d_redo_state;
+        m.redo_done = lv->d_redo_state + 1;
+    }
+    int32_t *d_prev = lv->d_counts + Wn, *d_changed = lv->d_counts + 2 * Wn;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipStream_t st = ctx->stream;
+    if (e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
+        // (mesh: nothing to clear -- the renderer leaves its work area clean)
+        ok(nmi::launch_level_prep(hd_mvps, lv->d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, lv->d_coeffs, Wn * 9, lv->d_key, lv->d_zbuf,
+                                  (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
+                                  lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
+                                  lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
+        // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
+        // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
+        const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
+        // Masked: the masks, their counts and the changed warps' tables on that branch too (they need the inverse maps only),
+        // beside the render.
+        if (!fused || masked) {
+            ok(hipEventRecord(lv->ev_fork, st));
+            ok(hipStreamWaitEvent(lv->side, lv->ev_fork, 0));
+            if (!fused) ok(nmi::launch_warp(d_frame, lv->d_coeffs, lv->d_warps, p.width, p.height, Wn, lv->side));
+            if (masked) {
+                ok(nmi::launch_warp_masks(lv->d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
+                ok(nmi::launch_level_mask_counts(lv->d_masks, Wn, ctx->npix, lv->d_counts, d_prev, d_changed, lv->side));
+                ok(nmi::launch_level_mask_tables(lv->d_counts, d_changed, Wn, ctx->npix, lv->d_tables, lv->side));
+            }
+            ok(hipEventRecord(lv->ev_join, lv->side));
+        }
+        if (tex)
+            ok(nmi::launch_render_mesh(d_xyz, d_attr, n_points, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, lv->d_mvps, S, lv->mesh, S,
+                                       (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
+                                       p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn));
+        else if (fused)
+            ok(nmi::launch_level_front_points(lv->d_packed, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_epoch, lv->d_renders, p.width, p.height,
+                                              lv->size, d_frame, lv->d_coeffs, lv->d_warps, Wn, st, lv->d_kept, lv->d_kept_count, ctx->compute_units));
+        else
+            ok(nmi::launch_render_points(d_xyz, d_red, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_renders, p.width, p.height, lv->size, st,
+                                         /*clear_first=*/false));
+        if (!fused || masked) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
+        if (masked && lv->pix)
+            ok(nmi::launch_pix_masked(m, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
+        else if (masked)
+            ok(nmi::launch_grid_masked(m, workgroups, true, false, st));
+        else if (lv->pix)
+            ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
+        else
+            ok(nmi::launch_grid(a, workgroups, true, st));
+        hipError_t ec = hipStreamEndCapture(st, &graph);
+        ok(ec);
+    }
+    if (e == hipSuccess) ok(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    if (e != hipSuccess) {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        return hip_fail(ctx, e, "nmi_level (graph capture)");
+    }
+    if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
+    if (lv->graph) (void)hipGraphDestroy(lv->graph);
+    lv->graph = graph;
+    lv->exec = exec;
+    return NMI_OK;
+}
 
 // Common part of nmi_level_create (tex == nullptr: coloured points, d_attr = red) and nmi_level_create_mesh (tex: textured
 // triangles, d_attr = uv, n = triangles).
@@ -209,56 +345,25 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     a.phase_mask = 3;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     const int workgroups = (int)(total < cap ? total : cap);
-    // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
-    // (nmi_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the prep kernel keeps.
-    lv->pix = e == hipSuccess ? choose_pix(ctx, a, total, cap) : 0;
-    if (lv->pix) {
-        const size_t bytes = nmi::pix_block_bytes((int)total, lv->pix);
-        ok(hipMalloc((void **)&lv->d_pix_blocks, bytes));
-        if (e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
-        if (e == hipSuccess && (next_split_epoch(ctx, &a.epoch) != NMI_OK || ensure_pix_timeouts(ctx) != NMI_OK)) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
-        a.blocks = lv->d_pix_blocks;
-        a.order = nullptr;
-    }
-
-    hipStream_t st = ctx->stream;
-    if (e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
-        // (mesh: nothing to clear -- the renderer leaves its work area clean)
-        ok(nmi::launch_level_prep(hd_mvps, lv->d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, lv->d_coeffs, Wn * 9, lv->d_key, lv->d_zbuf,
-                                  (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
-                                  lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
-                                  lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
-        // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
-        // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
-        const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
-        if (!fused) {
-            ok(hipEventRecord(lv->ev_fork, st));
-            ok(hipStreamWaitEvent(lv->side, lv->ev_fork, 0));
-            ok(nmi::launch_warp(d_frame, lv->d_coeffs, lv->d_warps, p.width, p.height, Wn, lv->side));
-            ok(hipEventRecord(lv->ev_join, lv->side));
+    // the graph (level_capture) is made from these; nmi_level_set_masks captures it again from them
+    lv->d_xyz = d_xyz;
+    lv->d_attr = d_attr;
+    lv->n_points = n_points;
+    lv->tex = tex;
+    lv->d_frame = d_frame;
+    lv->args = a;
+    lv->hd_mvps = hd_mvps;
+    lv->hd_coeffs = hd_coeffs;
+    lv->workgroups = workgroups;
+    if (e == hipSuccess) {
+        const int rc = level_capture(lv);
+        if (rc != NMI_OK) {
+            nmi_level_destroy(lv);
+            return rc;
         }
-        if (tex)
-            ok(nmi::launch_render_mesh(d_xyz, d_attr, n_points, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, lv->d_mvps, S, lv->mesh, S,
-                                       (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
-                                       p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn));
-        else if (fused)
-            ok(nmi::launch_level_front_points(lv->d_packed, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_epoch, lv->d_renders, p.width, p.height,
-                                              lv->size, d_frame, lv->d_coeffs, lv->d_warps, Wn, st, lv->d_kept, lv->d_kept_count, ctx->compute_units));
-        else
-            ok(nmi::launch_render_points(d_xyz, d_red, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_renders, p.width, p.height, lv->size, st,
-                                         /*clear_first=*/false));
-        if (!fused) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
-        if (lv->pix)
-            ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
-        else
-            ok(nmi::launch_grid(a, workgroups, true, st));
-        hipError_t ec = hipStreamEndCapture(st, &lv->graph);
-        ok(ec);
     }
-    if (e == hipSuccess) ok(hipGraphInstantiate(&lv->exec, lv->graph, nullptr, nullptr, 0));
     if (e != hipSuccess) {
-        const int rc = hip_fail(ctx, e, "nmi_level_create (graph capture)");
+        const int rc = hip_fail(ctx, e, "nmi_level_create");
         nmi_level_destroy(lv);
         return rc;
     }
@@ -387,6 +492,79 @@ int nmi_level_copy_outputs(nmi_level *lv, uint8_t *h_renders, uint8_t *h_warps, 
     if (h_renders) NMI_HIP_TRY(ctx, hipMemcpy(h_renders, lv->d_renders, npix * lv->S, hipMemcpyDeviceToHost));
     if (h_warps) NMI_HIP_TRY(ctx, hipMemcpy(h_warps, lv->d_warps, npix * lv->Wn, hipMemcpyDeviceToHost));
     if (h_ratings) NMI_HIP_TRY(ctx, hipMemcpy(h_ratings, lv->d_ratings, (size_t)lv->S * lv->Wn * sizeof(float), hipMemcpyDeviceToHost));
+    return NMI_OK;
+}
+
+static void level_free_masks(nmi_level *lv)
+{
+    void *dev[] = {lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state};
+    for (void *q : dev)
+        if (q) (void)hipFree(q);
+    lv->d_masks = nullptr;
+    lv->d_counts = nullptr;
+    lv->d_tables = nullptr;
+    lv->d_redo = nullptr;
+    lv->d_redo_state = nullptr;
+}
+
+int nmi_level_set_masks(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask)
+{
+    if (!lv || (enabled != 0 && enabled != 1) || (!enabled && d_frame_mask)) return NMI_ERR_INVALID_ARGUMENT;
+    nmi_ctx *ctx = lv->ctx;
+    ctx->detail.clear();
+    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
+        lv->masked = enabled != 0;
+        lv->d_frame_mask = d_frame_mask;
+        return NMI_OK;
+    }
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
+    const size_t npix = (size_t)ctx->npix, Wn = (size_t)lv->Wn;
+    if (enabled) {
+        if (!lv->d_masks) {
+            hipError_t e = hipSuccess;
+            auto ok = [&](hipError_t r) {
+                if (e == hipSuccess) e = r;
+            };
+            ok(hipMalloc((void **)&lv->d_masks, npix * Wn));
+            ok(hipMalloc((void **)&lv->d_counts, 3 * Wn * sizeof(int32_t)));
+            ok(hipMalloc((void **)&lv->d_tables, Wn * (npix + 1) * sizeof(float)));
+            ok(hipMalloc((void **)&lv->d_redo, (size_t)lv->S * Wn * sizeof(int32_t)));
+            ok(hipMalloc((void **)&lv->d_redo_state, 2 * sizeof(uint32_t)));
+            if (e == hipSuccess) ok(hipMemset(lv->d_masks, 0, npix * Wn));
+            if (e == hipSuccess) ok(hipMemset(lv->d_counts, 0, Wn * sizeof(int32_t)));
+            if (e == hipSuccess) ok(hipMemset(lv->d_redo_state, 0, 2 * sizeof(uint32_t)));
+            if (e != hipSuccess) {
+                level_free_masks(lv);
+                return hip_fail(ctx, e, "nmi_level_set_masks");
+            }
+        }
+        // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
+        NMI_HIP_TRY(ctx, hipMemset(lv->d_counts + Wn, 0xFF, Wn * sizeof(int32_t)));
+    }
+    const bool was = lv->masked;
+    const uint8_t *was_mask = lv->d_frame_mask;
+    lv->masked = enabled != 0;
+    lv->d_frame_mask = d_frame_mask;
+    const int rc = level_capture(lv);
+    if (rc != NMI_OK) {
+        lv->masked = was;
+        lv->d_frame_mask = was_mask;
+        return rc;
+    }
+    if (!enabled) level_free_masks(lv);
+    return NMI_OK;
+}
+
+int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts)
+{
+    if (!lv || !lv->masked) return NMI_ERR_INVALID_ARGUMENT;
+    if (lv->S == 0 || lv->Wn == 0) return NMI_OK;  // empty block: nothing was produced
+    nmi_ctx *ctx = lv->ctx;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks, (size_t)ctx->npix * lv->Wn, hipMemcpyDeviceToHost));
+    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_counts, (size_t)lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 

@@ -169,6 +169,7 @@ int choose_pix(const nmi_ctx *ctx, const nmi::GridArgs &a, int64_t total, int ca
 double pix_owner_share(const nmi_ctx *ctx, int pix);
 int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch);
 int ensure_pix_timeouts(nmi_ctx *ctx);
+int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes);  // the context's hand-off blocks of the pixel-range kernels (grown on demand)
 int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack, int Wn,
                  float *d_ratings, unsigned long long *out_key, bool post, uint32_t *dbg_joint, uint32_t *dbg_h1, uint32_t *dbg_h2,
                  float *dbg_sums, int w_offset = 0, bool post_score = false);

@@ -32,6 +32,17 @@ hipError_t launch_mask_tables(const int32_t *counts, int Wn, int npix, float *ta
 // fewer than 256 bins, and NMI_OPT_HIST_VARIANT 1); otherwise an optimistic launch and an exact launch for the candidates
 // whose count test failed (m.redo must be set).  Either way the last launch posts the winner (m.g.mailbox / out_key).
 hipError_t launch_grid_masked(const MaskedGridArgs &m, int workgroups, bool use_bg, bool exact, hipStream_t stream);
+// A masked level's count and table nodes (nmi_masked_level.hip).  counts[w] = nonzero bytes of masks[w]; changed[w] = counts[w]
+// differs from prev[w], which then takes the new count (prev = -1: every warp changed).  The table launch rebuilds
+// launch_mask_tables' entries for the changed warps only.
+hipError_t launch_level_mask_counts(const uint8_t *masks, int Wn, int npix, int32_t *counts, int32_t *prev, int32_t *changed, hipStream_t stream);
+hipError_t launch_level_mask_tables(const int32_t *counts, const int32_t *changed, int Wn, int npix, float *tables, hipStream_t stream);
+// Mid-size grids (nmi_masked_pix_kernel.hip): pix_parts workgroups per candidate over dealt pixel ranges, nmi_pix_kernel's
+// hand-off through m.g.blocks (pix_block_bytes, zero when allocated; tag from m.g.epoch + *replay).  Candidates that wrap a
+// counter or whose helper does not arrive in time are scored exactly by their owner inside the launch and counted in *healed.
+// Needs m.g.order == nullptr, m.g.epoch != 0, width >= 32; m.redo is not used.  Posts the winner like launch_grid_masked.
+hipError_t launch_pix_masked(const MaskedGridArgs &m, int pix_parts, double owner_share, bool use_bg, const uint32_t *replay, uint32_t *healed,
+                             hipStream_t stream);
 // out_masks[w][y][x] = 1 if warp w's pixel (x, y) interpolates from inside the frame (and from nonzero frame_mask taps when
 // frame_mask is given), else 0.  coeffs: [Wn][9] inverse maps, as launch_warp.
 hipError_t launch_warp_masks(const uint8_t *frame_mask, const float *coeffs, uint8_t *out_masks, int width, int height, int Wn,

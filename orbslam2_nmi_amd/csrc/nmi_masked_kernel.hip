@@ -28,8 +28,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// nmi_masked_pix_kernel.hip includes this file for its device functions only (NMI_MASKED_DEVICE_ONLY), after nmi_kernels.hip.
+#ifndef NMI_MASKED_DEVICE_ONLY
 #define NMI_KERNELS_DEVICE_ONLY 1
 #include "nmi_kernels.hip"  // Lds, add_chunk, add_pixel, decode_phase, final_phase, finish_search, candidate_at
+#endif
 #include "nmi_masked.h"
 
 namespace nmi {
@@ -157,6 +160,7 @@ __device__ __forceinline__ void masked_histogram_phase(Lds &lds, int par, const 
 
 }  // namespace
 
+#ifndef NMI_MASKED_DEVICE_ONLY
 // One workgroup per candidate, grid-stride over the candidates in the visiting order -- nmi_grid_kernel's structure: B1
 // histogram -> decode, B2 decode -> (wavefront 0: final trees + score + arg-max) || (the others: next candidate's pixels),
 // per-candidate state double-buffered by parity.
@@ -349,5 +353,6 @@ hipError_t launch_grid_masked(const MaskedGridArgs &m, int workgroups, bool use_
     }
     return hipGetLastError();
 }
+#endif  // !NMI_MASKED_DEVICE_ONLY
 
 }  // namespace nmi

@@ -334,6 +334,8 @@ __device__ __forceinline__ void final_phase_owner(Lds &lds, const GridArgs &a, i
 
 }  // namespace
 
+// nmi_masked_pix_kernel.hip includes this file for its device functions only (NMI_PIX_DEVICE_ONLY).
+#ifndef NMI_PIX_DEVICE_ONLY
 size_t pix_block_bytes(int candidates, int pix_parts) { return (size_t)candidates * (size_t)(pix_parts - 1) * kPixBlockBytes; }
 int pix_max_ranges() { return kMaxRanges; }
 
@@ -550,5 +552,6 @@ hipError_t launch_pix(const GridArgs &a, int pix_parts, double owner_share, bool
         hipLaunchKernelGGL((nmi_pix_kernel<true, false>), grid, block, 0, stream, a, pix_parts, g, replay, timeouts);
     return hipGetLastError();
 }
+#endif  // !NMI_PIX_DEVICE_ONLY
 
 }  // namespace nmi
