@@ -169,6 +169,10 @@ int nmi_search_grid_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_l
  *   d_frame     device uint8 [H][W]; d_warp_stack device uint8 [Wn][H][W], w = (wZ*nWy + wY)*nWx + wX.
  * Enqueued on the context's stream (no synchronisation).  OpenCV is not part of the reference tree: parity of the
  * interpolation arithmetic is unpinned (see the kernel comment).
+ * A matrix with a non-finite entry, or singular (det == 0 after it is scaled to a largest |entry| in [1, 2)), makes the
+ * call return NMI_ERR_INVALID_ARGUMENT before anything is enqueued.  Any other scale is accepted: M and c M (c != 0)
+ * give the same warp, and for c a power of two the same bytes.  The same rule holds for nmi_warp_stack_masked,
+ * nmi_level_run and nmi_level_run_rccl (a rejected level run leaves the level as it was).
  */
 int nmi_warp_homographies(const double K[9], const int32_t num_warp_xyz[3], const float step_rad_xyz[3],
                           double *h_forward /*[Wn][9]*/);
@@ -193,7 +197,7 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
  * warp's source test -2 < xs < W+1, -2 < ys < H+1, when every bilinear tap with nonzero weight lies inside the frame
  * (x1 = floor(xs) >= 0, x1 + (xs != x1) <= W-1, the same for rows), and, given d_frame_mask (uint8 [H][W], nullable = all
  * valid), when every such tap is nonzero in it.  The identity homography gives an all-ones mask and warp == frame.
- * Enqueued on the context's stream, like nmi_warp_stack.
+ * Enqueued on the context's stream, like nmi_warp_stack; non-finite or singular matrices are rejected as there.
  *
  * nmi_search_grid_masked: nmi_search_grid with the masks; len_w is counted on the device from warp_masks (the source of
  * truth: the masks need not come from nmi_warp_stack_masked).  A NULL warp_masks is NMI_ERR_INVALID_ARGUMENT.  Blocking

@@ -410,21 +410,17 @@ int nmi_level_create_mesh_block(nmi_ctx *ctx, const float *d_xyz, const float *d
 static int level_launch(nmi_level *lv, const float *h_mvps, const double *h_forward)
 {
     nmi_ctx *ctx = lv->ctx;
+    // every homography is checked before anything of the replay is touched: a rejected call leaves the level as it was
+    std::vector<float> coeffs((size_t)lv->Wn * 9);
+    for (int w = 0; w < lv->Wn; ++w)
+        if (warp_inverse_coeffs(h_forward + (size_t)w * 9, coeffs.data() + (size_t)w * 9) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     memcpy(lv->h_mvps, h_mvps, (size_t)lv->S * 16 * sizeof(float));
     nmi::level_views_bound(h_mvps, lv->S, lv->h_mvps + (size_t)lv->S * 16);  // for the front kernel's first test: all views at once
     static const bool no_bound = getenv("NMI_LEVEL_NO_BOUND") != nullptr;      // measurement switch: six zero planes cull nothing
     if (no_bound) memset(lv->h_mvps + (size_t)lv->S * 16, 0, 24 * sizeof(float));
     const uint32_t parity = ++lv->replay & 1u;  // which of its two counters the prep kernel's cull counts under (it zeroes the other one)
     memcpy(lv->h_mvps + (size_t)lv->S * 16 + 24, &parity, sizeof parity);
-    for (int w = 0; w < lv->Wn; ++w) {
-        const double *m = h_forward + (size_t)w * 9;
-        const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        if (det == 0.0) return NMI_ERR_INVALID_ARGUMENT;
-        const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
-                               (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
-                               (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
-        for (int k = 0; k < 9; ++k) lv->h_coeffs[w * 9 + k] = (float)inv[k];
-    }
+    memcpy(lv->h_coeffs, coeffs.data(), coeffs.size() * sizeof(float));
     constexpr unsigned long long kPending = ~0ull;
     __atomic_store_n(lv->h_key, kPending, __ATOMIC_RELEASE);
     const hipError_t le = hipGraphLaunch(lv->exec, ctx->stream);

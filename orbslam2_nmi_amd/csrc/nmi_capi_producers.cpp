@@ -67,6 +67,41 @@ int ensure_mesh_work(nmi_ctx *ctx, int S)
     return NMI_OK;
 }
 
+// warpPerspective inverts the forward matrix on the host in double and hands 9 floats to the device.  A homography is
+// defined up to scale, but the floats are not: cast as they come, the inverse of 1e-38 M overflows to inf and that of 1e39 M
+// is subnormal, and the determinant of a matrix with entries near 1e-110 underflows to 0.  So M is brought to its largest
+// |entry| in [1, 2) before the inversion, and the inverse likewise before the cast.  Both scalings are powers of two: every
+// coefficient of a well-scaled matrix keeps its bits up to one common power of two, which the kernels' arithmetic
+// (1 / den times a numerator, both linear in the coefficients) cancels exactly -- warps and masks keep their bits.
+static void scale_to_unit(double *a)
+{
+    double mx = 0.0;
+    for (int i = 0; i < 9; ++i) mx = fmax(mx, fabs(a[i]));
+    int e = 0;
+    frexp(mx, &e);  // mx = f 2^e, f in [0.5, 1)
+    for (int i = 0; i < 9; ++i) a[i] = ldexp(a[i], 1 - e);
+}
+
+int warp_inverse_coeffs(const double *forward, float *coeffs)
+{
+    double m[9];
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(forward[i])) return NMI_ERR_INVALID_ARGUMENT;
+        m[i] = forward[i];
+    }
+    scale_to_unit(m);  // (all zero stays all zero: det == 0 below)
+    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+    if (det == 0.0) return NMI_ERR_INVALID_ARGUMENT;
+    double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
+                     (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
+                     (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(inv[i])) return NMI_ERR_INVALID_ARGUMENT;  // a subnormal determinant: singular to working precision
+    scale_to_unit(inv);
+    for (int i = 0; i < 9; ++i) coeffs[i] = (float)inv[i];
+    return NMI_OK;
+}
+
 }  // namespace nmi_internal
 
 extern "C" {
@@ -130,16 +165,8 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
     // this ring entry was last used kWarpRing submissions ago; normally long finished
     NMI_HIP_TRY(ctx, hipEventSynchronize(ctx->warp_ev[ring]));
     float *h_coeffs = ctx->h_warp_coeffs[ring], *d_coeffs = ctx->d_warp_coeffs[ring];
-    // warpPerspective inverts the forward matrix on the host in double and hands 9 floats to the device
-    for (int w = 0; w < Wn; ++w) {
-        const double *m = h_forward + (size_t)w * 9;
-        const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        if (det == 0.0) return NMI_ERR_INVALID_ARGUMENT;
-        const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
-                               (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
-                               (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
-        for (int e = 0; e < 9; ++e) h_coeffs[w * 9 + e] = (float)inv[e];
-    }
+    for (int w = 0; w < Wn; ++w)
+        if (warp_inverse_coeffs(h_forward + (size_t)w * 9, h_coeffs + (size_t)w * 9) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     NMI_HIP_TRY(ctx, hipMemcpyAsync(d_coeffs, h_coeffs, (size_t)Wn * 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_warp(d_frame, d_coeffs, d_warp_stack, ctx->params.width, ctx->params.height, Wn, ctx->stream));
     NMI_HIP_TRY(ctx, hipEventRecord(ctx->warp_ev[ring], ctx->stream));

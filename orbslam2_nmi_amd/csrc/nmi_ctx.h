@@ -155,6 +155,9 @@ int mesh_work_alloc(nmi_ctx *ctx, int S, nmi::MeshWork *w);
 void mesh_work_free(nmi::MeshWork *w);
 int ensure_mesh_work(nmi_ctx *ctx, int S);  // the context's own, grown on demand
 int ensure_mesh_pairs(nmi_ctx *ctx, nmi::MeshWork *w, long long n_triangles);  // the pair list of the two-kernel binning pass
+// The 9 floats the warp kernels take for one forward homography (nmi_capi_producers.cpp): NMI_ERR_INVALID_ARGUMENT for a
+// non-finite or singular matrix.  Shared by nmi_warp_stack, nmi_warp_stack_masked and the level replays.
+int warp_inverse_coeffs(const double *forward /*[9]*/, float *coeffs /*[9]*/);
 int level_enqueue(nmi_level *lv, const float *h_mvps, const double *h_forward, const unsigned long long **d_key);
 nmi_ctx *level_ctx(nmi_level *lv);
 // ncclAllReduce(ncclMax, ncclUint64) of one 8-byte key on the context's stream, out of place (nmi_capi_rccl.cpp)

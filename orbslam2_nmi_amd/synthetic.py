@@ -101,6 +101,11 @@ def warp_homographies(K, counts, steps):
 def warp_perspective(img, M):
     """dst(x, y) = bilinear src at M^-1 (x, y, 1), constant border 0 -- the semantics of
     cv::cuda::warpPerspective as called at image.cpp:123 (forward matrix, INTER_LINEAR, BORDER_CONSTANT)."""
+    return np.clip(np.rint(warp_perspective_value(img, M)), 0, 255).astype(np.uint8)
+
+
+def warp_perspective_value(img, M):
+    """warp_perspective before the rounding: the float64 bilinear value of every pixel (NaN where the source is undefined)."""
     h, w = img.shape
     Mi = np.linalg.inv(M)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
@@ -115,9 +120,8 @@ def warp_perspective(img, M):
         ok = (xi >= -1) & (xi <= w) & (yi >= -1) & (yi <= h)
         return np.where(ok, src[np.clip(yi, -1, h) + 1, np.clip(xi, -1, w) + 1], 0.0)
 
-    val = ((1 - fx) * (1 - fy) * at(y0, x0) + fx * (1 - fy) * at(y0, x0 + 1)
-           + (1 - fx) * fy * at(y0 + 1, x0) + fx * fy * at(y0 + 1, x0 + 1))
-    return np.clip(np.rint(val), 0, 255).astype(np.uint8)
+    return ((1 - fx) * (1 - fy) * at(y0, x0) + fx * (1 - fy) * at(y0, x0 + 1)
+            + (1 - fx) * fy * at(y0 + 1, x0) + fx * fy * at(y0 + 1, x0 + 1))
 
 
 def warp_stack(frame_u8, counts, steps=(0.02, 0.02, 0.05)):

@@ -10,7 +10,7 @@ the product's bits.
 import numpy as np
 
 from oracle import binding as oc
-from oracle.warp_oracle_np import inverse_coeffs_adjugate
+from oracle.warp_oracle_np import device_coeffs
 
 f32 = np.float32
 
@@ -24,7 +24,7 @@ def warp_masks(shape, homographies, frame_mask=None):
     fm = None if frame_mask is None else (np.asarray(frame_mask) != 0)
     out = np.zeros((len(homographies), h, w), np.uint8)
     for i, M in enumerate(homographies):
-        c = inverse_coeffs_adjugate(M)
+        c = device_coeffs(M)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             coeff = f32(1.0) / ((c[6] * fx + c[7] * fy) + c[8])
             xs = coeff * ((c[0] * fx + c[1] * fy) + c[2])
