@@ -206,8 +206,8 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
  *
  * nmi_last_mask_counts: len_w of the latest masked search's first n warps (n <= its Wn) to host memory.  Blocking.
  *
- * Not masked (yet): captured levels, streams, shard / block / RCCL forms, the CUDAF shim, and render-side masks (those
- * make len per candidate instead of per warp).
+ * Render-side masks: see nmi_search_grid_covered below.  Not masked (yet): captured levels, streams, shard / block / RCCL
+ * forms, the CUDAF shim.
  */
 int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask /* nullable: all valid */,
                           const double *h_forward, int32_t Wn, uint8_t *d_warp_stack, uint8_t *d_warp_masks);
@@ -215,6 +215,36 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
                            const uint8_t *warp_masks, int32_t Wn, float *ratings /* nullable */,
                            int64_t *best_linear_idx, float *best_score);
 int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
+
+/*
+ * Covered search: masks on both sides.  The map side's mask is the coverage of a render: both renderers clear to 255
+ * (glClearColor(1,1,1), rendering.hpp:533) and the background rule drops only raw zeros, so without it every pixel the map
+ * does not cover enters the joint histogram as a solid 255.
+ *
+ * A render mask is uint8 [S][H][W] in the render's own layout (bottom-up rows, like the render stack); nonzero = covered.
+ * Candidate (warp w, render s) counts pixel pos of the warp iff
+ *   warp_masks[w][pos] != 0, render_masks[s][rpos] != 0 (rpos: the render pixel nmi_search_grid pairs with pos, row-flipped
+ *   when render_bottom_up), and the background rule passes on the raw intensities.
+ * len[w][s] = the number of pos where both masks are nonzero (like W*H, not reduced by the background rule) replaces W*H in
+ * the term fl32(p * fl32(log2_f64(p))), p = fl32(c / len[w][s]); len = 0 scores 0.0.  Everything else is
+ * nmi_search_grid_masked's: trees, SUC / ENMI, the all-zero guard, the [Wn][S] layout, the arg-max and key rule, blocking
+ * behaviour; NMI_OPT_SPLIT* and NMI_OPT_CONTENT_PATH do not apply.  So all-ones render masks give nmi_search_grid_masked's
+ * bits, and all-ones masks on both sides nmi_search_grid's.  Masks mean "nonzero" (bytes 1 and 2 both count).
+ * NULL masks, S < 1 or Wn < 1 are NMI_ERR_INVALID_ARGUMENT.
+ *
+ * nmi_last_cover_counts: the first n entries of len[w][s] (layout [Wn][S]) of the latest covered search.  Blocking.
+ *
+ * nmi_render_points_masked / nmi_render_mesh_masked: nmi_render_points / nmi_render_mesh (d_render_stack byte-identical)
+ * plus d_render_masks uint8 [S][H][W], render layout: 1 where a fragment won the pixel, 0 where it kept the clear colour --
+ * exactly where the same call renders 0 with every red 0 (points) or an all-black texture (mesh), and 255 otherwise.
+ * Enqueued on the context's stream; a NULL d_render_masks is NMI_ERR_INVALID_ARGUMENT.
+ *
+ * Not covered (yet): captured levels, streams, shard / block / RCCL forms, the CUDAF shim.
+ */
+int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int32_t S,
+                            const uint8_t *warp_stack, const uint8_t *warp_masks, int32_t Wn, float *ratings /* nullable */,
+                            int64_t *best_linear_idx, float *best_score);
+int nmi_last_cover_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
@@ -257,6 +287,11 @@ int nmi_texture_create(nmi_ctx *ctx, const uint8_t *h_rgb, int32_t tex_width, in
 int nmi_texture_destroy(nmi_texture *tex);
 int nmi_render_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                     const float *h_mvps, int32_t S, uint8_t *d_render_stack);
+/* coverage forms (see nmi_search_grid_covered above) */
+int nmi_render_points_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
+                             float point_size, uint8_t *d_render_stack, uint8_t *d_render_masks);
+int nmi_render_mesh_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
+                           const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks);
 
 /*
  * Map order.  What the renderers draw does not depend on the order of the points / triangles (the depth test is a

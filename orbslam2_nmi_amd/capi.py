@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "nmi_set_option", "nmi_copy_term_table", "nmi_abi_version", "nmi_error_string", "nmi_last_error_detail", "nmi_get_info", "nmi_last_content", "nmi_sort_points", "nmi_sort_triangles",
     "nmi_split_status", "nmi_pix_status", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
     "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts", "nmi_level_set_masks", "nmi_level_copy_masks",
+    "nmi_render_points_masked", "nmi_render_mesh_masked", "nmi_search_grid_covered", "nmi_last_cover_counts",
 )
 
 
@@ -88,6 +89,10 @@ def load_library(build_if_missing=False):
     lib.nmi_warp_stack_masked.argtypes = [vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp]
     lib.nmi_search_grid_masked.argtypes = [vp, vp, i32, vp, vp, i32, vp, i64p, f32p]
     lib.nmi_last_mask_counts.argtypes = [vp, C.POINTER(i32), i32]
+    lib.nmi_render_points_masked.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_float), i32, C.c_float, vp, vp]
+    lib.nmi_render_mesh_masked.argtypes = [vp, vp, vp, C.c_int64, vp, C.POINTER(C.c_float), i32, vp, vp]
+    lib.nmi_search_grid_covered.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i64p, f32p]
+    lib.nmi_last_cover_counts.argtypes = [vp, C.POINTER(i32), i32]
     lib.nmi_render_mvp.argtypes = [C.POINTER(RenderParams), f32p, f32p, f32p, f32p, f32p]
     lib.nmi_render_points.argtypes = [vp, vp, vp, C.c_int64, f32p, i32, C.c_float, vp]
     lib.nmi_texture_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
@@ -462,9 +467,72 @@ class NmiContext:
         self._check(self._lib.nmi_last_mask_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)), "nmi_last_mask_counts")
         return out
 
+    def search_grid_covered(self, render_stack, render_masks, warp_stack, warp_masks, ratings=None):
+        """search_grid with masks on both sides (nmi_search_grid_covered) -> (best linear index w*S+s, best score).
+
+        render_masks: device [S,H,W] uint8 or bool in the render's own layout (bottom-up rows like the render stack), nonzero =
+        the map covers the pixel; warp_masks as for search_grid_masked; ratings as for search_grid."""
+        rs, ws = self._stack(render_stack, "render_stack"), self._stack(warp_stack, "warp_stack")
+        rm, wm = self._mask_stack(render_masks, "render_masks"), self._mask_stack(warp_masks, "warp_masks")
+        S, Wn = rs.shape[0], ws.shape[0]
+        if rm.shape[0] != S:
+            raise ValueError(f"render_masks has {rm.shape[0]} renders, render_stack {S}")
+        if wm.shape[0] != Wn:
+            raise ValueError(f"warp_masks has {wm.shape[0]} warps, warp_stack {Wn}")
+        rp = self._ratings_ptr(ratings, Wn, S)
+        idx, sc = C.c_int64(0), C.c_float(0)
+        self._order_after_torch()
+        self._check(self._lib.nmi_search_grid_covered(self._h, rs.data_ptr(), rm.data_ptr(), S, ws.data_ptr(), wm.data_ptr(), Wn, rp,
+                                                      C.byref(idx), C.byref(sc)), "nmi_search_grid_covered")
+        return int(idx.value), np.float32(sc.value)
+
+    def cover_counts(self, n):
+        """len[w][s] (pixels where both masks are nonzero) of the first n candidates of the latest covered search, layout
+        [Wn][S] flattened -> numpy int32 [n]."""
+        out = np.zeros(int(n), np.int32)
+        self._check(self._lib.nmi_last_cover_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)), "nmi_last_cover_counts")
+        return out
+
+    def render_points_masked(self, xyz, red, mvps, point_size, out=None, out_masks=None, sync=True):
+        """render_points plus its coverage (nmi_render_points_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
+        where a point won the pixel, 0 where it kept the background; bottom-up rows like the renders, which are
+        byte-identical to render_points'.  out_masks may be uint8 or bool (default uint8)."""
+        import torch
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        if out_masks is None:
+            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
+        om = self._mask_stack(out_masks, "out_masks")
+        if om.shape[0] != m.shape[0]:
+            raise ValueError("out_masks has the wrong number of views")
+        out = self._render_points(xyz, red, m, point_size, out, om)
+        if sync:
+            self.synchronize()
+        return out, out_masks
+
+    def render_mesh_masked(self, xyz, uv, texture, mvps, out=None, out_masks=None, sync=True):
+        """render_mesh plus its coverage (nmi_render_mesh_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
+        where a triangle won the pixel, 0 where it kept the background; the renders are byte-identical to render_mesh's."""
+        import torch
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        if out_masks is None:
+            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
+        om = self._mask_stack(out_masks, "out_masks")
+        if om.shape[0] != m.shape[0]:
+            raise ValueError("out_masks has the wrong number of views")
+        out = self._render_mesh(xyz, uv, texture, m, out, om)
+        if sync:
+            self.synchronize()
+        return out, out_masks
+
     def render_points(self, xyz, red, mvps, point_size, out=None, sync=True):
         """Rendering<4>::renderToTextureOnGPU without OpenGL: device float32 xyz [N,3] + red [N], host MVPs [S,16]
         (render_mvp) -> render stack [S,H,W] u8 on the device, bottom-up rows, background 255."""
+        out = self._render_points(xyz, red, mvps, point_size, out, None)
+        if sync:
+            self.synchronize()
+        return out
+
+    def _render_points(self, xyz, red, mvps, point_size, out, masks):
         import torch
         for t, shape in ((xyz, 2), (red, 1)):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != shape:
@@ -475,16 +543,25 @@ class NmiContext:
             out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
         o = self._stack(out, "out")
         self._order_after_torch()
-        self._check(self._lib.nmi_render_points(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0],
-                                                m.ctypes.data_as(C.POINTER(C.c_float)), S, float(point_size), o.data_ptr()),
-                    "nmi_render_points")
-        if sync:
-            self.synchronize()
+        if masks is None:
+            self._check(self._lib.nmi_render_points(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0],
+                                                    m.ctypes.data_as(C.POINTER(C.c_float)), S, float(point_size), o.data_ptr()),
+                        "nmi_render_points")
+        else:
+            self._check(self._lib.nmi_render_points_masked(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0],
+                                                           m.ctypes.data_as(C.POINTER(C.c_float)), S, float(point_size), o.data_ptr(),
+                                                           masks.data_ptr()), "nmi_render_points_masked")
         return out
 
     def render_mesh(self, xyz, uv, texture, mvps, out=None, sync=True):
         """Rendering<1>::renderToTextureOnGPU without OpenGL: device float32 corner arrays xyz [3T,3], uv [3T,2], an
         NmiTexture, host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
+        out = self._render_mesh(xyz, uv, texture, mvps, out, None)
+        if sync:
+            self.synchronize()
+        return out
+
+    def _render_mesh(self, xyz, uv, texture, mvps, out, masks):
         import torch
         for t, cols in ((xyz, 3), (uv, 2)):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols:
@@ -497,10 +574,13 @@ class NmiContext:
             out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
         o = self._stack(out, "out")
         self._order_after_torch()
-        self._check(self._lib.nmi_render_mesh(self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h,
-                                              m.ctypes.data_as(C.POINTER(C.c_float)), S, o.data_ptr()), "nmi_render_mesh")
-        if sync:
-            self.synchronize()
+        if masks is None:
+            self._check(self._lib.nmi_render_mesh(self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h,
+                                                  m.ctypes.data_as(C.POINTER(C.c_float)), S, o.data_ptr()), "nmi_render_mesh")
+        else:
+            self._check(self._lib.nmi_render_mesh_masked(self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h,
+                                                         m.ctypes.data_as(C.POINTER(C.c_float)), S, o.data_ptr(), masks.data_ptr()),
+                        "nmi_render_mesh_masked")
         return out
 
     def search_grid(self, render_stack, warp_stack, ratings=None):

@@ -213,6 +213,16 @@ int nmi_render_mvp(const nmi_render_params *rp, const float cam_pos[3], const fl
 int nmi_render_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
                       float point_size, uint8_t *d_render_stack)
 {
+    return render_points_impl(ctx, d_xyz, d_red, n_points, h_mvps, S, point_size, d_render_stack, nullptr);
+}
+
+}  // extern "C"
+
+namespace nmi_internal {
+
+int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
+                       float point_size, uint8_t *d_render_stack, uint8_t *cover)
+{
     if (!ctx || !h_mvps || !d_render_stack || S <= 0 || n_points < 0 || (n_points > 0 && (!d_xyz || !d_red)))
         return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
@@ -234,9 +244,13 @@ int nmi_render_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int6
     const int src = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (src != NMI_OK) return src;
     NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, ctx->d_zbuf, d_render_stack, ctx->params.width,
-                                               ctx->params.height, size, ctx->stream));
+                                               ctx->params.height, size, ctx->stream, true, cover));
     return NMI_OK;
 }
+
+}  // namespace nmi_internal
+
+extern "C" {
 
 // ---------------------------------------------------------------------------------------------------------
 // Textured-mesh renderer: texture object (mip chain -> per-level luma on the device) and the draw call.
@@ -316,6 +330,16 @@ int nmi_texture_create(nmi_ctx *ctx, const uint8_t *h_rgb, int32_t tw, int32_t t
 int nmi_render_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                     const float *h_mvps, int32_t S, uint8_t *d_render_stack)
 {
+    return render_mesh_impl(ctx, d_xyz, d_uv, n_triangles, tex, h_mvps, S, d_render_stack, nullptr);
+}
+
+}  // extern "C"
+
+namespace nmi_internal {
+
+int render_mesh_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex, const float *h_mvps,
+                     int32_t S, uint8_t *d_render_stack, uint8_t *cover)
+{
     if (!ctx || !tex || tex->ctx != ctx || !h_mvps || !d_render_stack || S <= 0 || n_triangles < 0 ||
         (n_triangles > 0 && (!d_xyz || !d_uv)))
         return NMI_ERR_INVALID_ARGUMENT;
@@ -331,13 +355,18 @@ int nmi_render_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t
     if (rc != NMI_OK) return rc;
     const hipError_t e = nmi::launch_render_mesh(d_xyz, d_uv, n_triangles, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, d_mvps, S, ctx->mesh,
                                                  ctx->mesh_views, (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit,
-                                                 d_render_stack, ctx->params.width, ctx->params.height, ctx->stream);
+                                                 d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr, nullptr,
+                                                 nullptr, 0, cover);
     if (e != hipSuccess) {
         ctx->mesh_views = 0;  // whatever state the buffers are in: allocate and clear afresh next time
         return hip_fail(ctx, e, "launch_render_mesh");
     }
     return NMI_OK;
 }
+
+}  // namespace nmi_internal
+
+extern "C" {
 
 int nmi_sort_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, float *d_xyz_out, float *d_red_out)
 {

@@ -130,6 +130,12 @@ struct nmi_ctx {
     int32_t *d_mask_redo = nullptr;       // [mask_redo_cap] candidates to score again exactly
     uint32_t *d_mask_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
     int64_t mask_redo_cap = 0;
+    // Covered search (nmi_capi_covered.cpp): per-candidate pixel counts and the redo list of its optimistic launch.
+    int32_t *d_cover_counts = nullptr;    // [cover_cap] len[w][s] of the latest covered search, layout [Wn][S]
+    int32_t *d_cover_redo = nullptr;      // [cover_cap] candidates to score again exactly
+    uint32_t *d_cover_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
+    int64_t cover_cap = 0;
+    int64_t cover_count_n = 0;            // candidates counted by the latest covered search
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     int hist_variant = 3;
     int phase_mask = 3;
@@ -187,6 +193,11 @@ bool split_launch_failed(nmi_ctx *ctx, int parts, uint32_t epoch);      // ... t
 int search_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_local, int32_t s_offset, int32_t S_total, const uint8_t *warp_stack,
                  int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float *d_ratings, uint64_t *d_key, uint64_t *h_key,
                  bool caller_checks);
+// nmi_render_points / nmi_render_mesh and their masked forms (nmi_capi_producers.cpp): cover = null, or the coverage masks
+int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
+                       float point_size, uint8_t *d_render_stack, uint8_t *cover);
+int render_mesh_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex, const float *h_mvps,
+                     int32_t S, uint8_t *d_render_stack, uint8_t *cover);
 int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
                     int Wn);
 

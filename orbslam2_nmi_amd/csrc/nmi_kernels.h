@@ -179,14 +179,16 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
                               unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
                               // a captured level: the Wn warps of `warp_frame` are made by extra workgroups of the first kernel
                               // (level_front_eligible must hold; needs at least one triangle and S <= 64)
-                              const uint8_t *warp_frame = nullptr, const float *warp_coeffs = nullptr, uint8_t *warp_out = nullptr, int Wn = 0);
+                              const uint8_t *warp_frame = nullptr, const float *warp_coeffs = nullptr, uint8_t *warp_out = nullptr, int Wn = 0,
+                              // coverage masks [S][H][W] (1 where a fragment won the pixel, 0 where it kept the clear colour), or null
+                              uint8_t *cover = nullptr);
 // Words between rows of the renderers' anchor / depth buffer: the padded width, rounded so that the resolve pass can
 // read 8 consecutive anchors of any output quad with two aligned 16-byte loads (point sizes > 1); width for size 1.
 inline int zbuf_stride(int width, int size) { return size > 1 ? ((width + size - 1 + 3) & ~3) + 4 : width; }
 size_t render_zbuf_words(int S, int width, int height, int size);
 hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps /*[S][16] column-major*/,
                                 int S, uint32_t *zbuf /*[render_zbuf_words]*/, uint8_t *out, int width, int height, int size, hipStream_t stream,
-                                bool clear_first = true);
+                                bool clear_first = true, uint8_t *cover = nullptr /* [S][H][W]: 1 where a point won the pixel, or null */);
 // nmi_sort.hip: records (na floats each in `a`, the first 3 * verts being vertices; nb floats each in `b`, may be null) into
 // Morton order of their positions.  Drains the stream.
 hipError_t sort_records_morton(const float *a, int na, int verts, const float *b, int nb, long long n, float *a_out, float *b_out,

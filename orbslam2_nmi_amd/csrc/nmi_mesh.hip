@@ -775,10 +775,12 @@ __device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
 
 }  // namespace
 
-template <int BINMAX>
+// COVER (nmi_render_mesh_masked): also writes cover[s][y][x] = 1 where a fragment won the pixel (its grey comes from a triangle,
+// from the LDS records or through the memory buffer), 0 where it kept the clear colour; same layout as `out`.
+template <int BINMAX, bool COVER = false>
 __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, const float *__restrict__ uv,
                                                                      const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                     int height, MeshTexture tex, BinGrid g)
+                                                                     int height, MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover = nullptr)
 {
     __shared__ TileLds<BINMAX> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -813,6 +815,13 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 *reinterpret_cast<uint32_t *>(dst) = 0xFFFFFFFFu;
             else
                 for (int k = 0; k < 4 && ox + k < width; ++k) dst[k] = 255;
+            if (COVER) {
+                uint8_t *cdst = cover + (dst - out);
+                if (dword_ok && (((uintptr_t)cover & 3) == 0))
+                    *reinterpret_cast<uint32_t *>(cdst) = 0u;
+                else
+                    for (int k = 0; k < 4 && ox + k < width; ++k) cdst[k] = 0;
+            }
         }
         return;
     }
@@ -982,6 +991,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
         }
         // ---- shade every pixel once, by the triangle that won it ------------------------------------------------------------
         uint32_t packed = 0xFFFFFFFFu;
+        uint32_t covered = 0;  // (COVER) 1 in byte k: pixel k's grey came from a fragment
         // Pixels won through the memory buffer have no record in LDS: their triangle is set up here, on the fly.  One copy of
         // that code, outside the unrolled loop below (for a mesh of pixel-sized triangles this IS the shading loop).
         if (from_memory) {
@@ -998,6 +1008,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                     Planes P;
                     tri_planes(t, su, sv, P);
                     grey = shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                    if (COVER) covered |= 1u << (8 * k);
                 }
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
                 keys[3] = kEmptyKey;  // done
@@ -1012,6 +1023,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
                 const uint32_t grey = shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, (float)(ox + k) + 0.5f, (float)y + 0.5f);
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
+                if (COVER) covered |= 1u << (8 * k);
             }
         }
         uint8_t *dst = out + ((size_t)s * height + y) * width + ox;
@@ -1019,6 +1031,13 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
             *reinterpret_cast<uint32_t *>(dst) = packed;
         else
             for (int k = 0; k < 4 && ox + k < width; ++k) dst[k] = (uint8_t)(packed >> (8 * k));
+        if (COVER) {
+            uint8_t *cdst = cover + (dst - out);
+            if (dword_ok && (((uintptr_t)cover & 3) == 0))
+                *reinterpret_cast<uint32_t *>(cdst) = covered;
+            else
+                for (int k = 0; k < 4 && ox + k < width; ++k) cdst[k] = (uint8_t)(covered >> (8 * k));
+        }
     }
 }
 
@@ -1041,6 +1060,21 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6,
     MeshTexture tex, BinGrid g)
 {
     mesh_tile_body<kBinSmall>(xyz, uv, mvps, out, width, height, tex, g);
+}
+
+// The coverage forms of the two builds (nmi_render_mesh_masked): the same bodies, plus the mask stack.
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ uv,
+                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
+                                                                           int height, MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
+{
+    mesh_tile_body<kBinMax, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
+}
+
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void nmi_mesh_tile_small_cover_kernel(
+    const float *__restrict__ xyz, const float *__restrict__ uv, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width, int height,
+    MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
+{
+    mesh_tile_body<kBinSmall, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
 }
 
 
@@ -1094,7 +1128,7 @@ size_t mesh_pairs_entries(long long ntri) { return (size_t)((ntri + 255) / 256) 
 hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri, const float *luma, int levels, const int *lw,
                               const int *lh, const long long *loff, const float *mvps, int S, const MeshWork &w, int layout_views,
                               int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
-                              const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn)
+                              const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover)
 {
     if (S > layout_views) return hipErrorInvalidValue;
     WarpFuse wf{warp_frame, warp_coeffs, warp_out, 0};
@@ -1158,7 +1192,13 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
             hipLaunchKernelGGL(nmi_mesh_clip_kernel, dim3(64), dim3(256), 0, stream, xyz, uv, ntri, mvps + (size_t)s0 * 16, views, width,
                                height, g, clipq, w.clip_state, clip_cap, w.pair_state);
         }
-        if (small_tiles)
+        if (cover && small_tiles)
+            hipLaunchKernelGGL(nmi_mesh_tile_small_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
+                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g, cover + (size_t)s0 * width * height);
+        else if (cover)
+            hipLaunchKernelGGL(nmi_mesh_tile_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
+                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g, cover + (size_t)s0 * width * height);
+        else if (small_tiles)
             hipLaunchKernelGGL(nmi_mesh_tile_small_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
                                mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g);
         else

@@ -433,6 +433,114 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *_
     }
 }
 
+// The coverage forms of the two resolve kernels above (nmi_render_points_masked): the same code, which also writes
+// cover[s][y][x] = 1 where the pixel's resolved key is not empty (a point won it), 0 where it kept the clear colour.  Copies
+// rather than a template parameter of the kernels above, whose code stays as it is.
+template <int SIZE>
+__global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
+                                                                          uint8_t *__restrict__ cover, int views, int width, int height, int stride)
+{
+    // requires width % 4 == 0, SIZE <= 5, stride % 4 == 0, (SIZE == 1 or stride >= width + 4) and cover 4-byte aligned
+    const int hp = height + SIZE - 1;
+    const int quads = width >> 2, strips = (height + kResolveRows - 1) / kResolveRows;
+    const size_t n = (size_t)views * strips * quads;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % quads), st = (int)((i / quads) % strips), s = (int)(i / ((size_t)quads * strips));
+        const int py0 = st * kResolveRows;
+        const uint32_t *base = zbuf + ((size_t)s * hp + py0) * stride + q * 4;
+        uint8_t *dst = out + ((size_t)s * height + py0) * width + q * 4;
+        uint32_t h[SIZE][4];  // horizontal minima of the last SIZE anchor rows (ring, indices static after unrolling)
+        auto fetch = [&](int row, uint32_t (&m)[4]) {
+            const uint4 lo = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride);
+            uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+            if (SIZE > 1) {
+                const uint4 hi = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride + 4);
+                v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                m[k] = v[k];
+#pragma unroll
+                for (int d = 1; d < SIZE; ++d) m[k] = min(m[k], v[k + d]);
+            }
+        };
+#pragma unroll
+        for (int r = 0; r < SIZE - 1; ++r) fetch(r, h[r]);  // (anchor rows py0 .. py0 + SIZE - 2 exist: hp = height + SIZE - 1)
+#pragma unroll
+        for (int r = 0; r < kResolveRows; ++r) {
+            if (py0 + r >= height) break;
+            fetch(r + SIZE - 1, h[(r + SIZE - 1) % SIZE]);
+            uint32_t best[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                best[k] = h[0][k];
+#pragma unroll
+                for (int j = 1; j < SIZE; ++j) best[k] = min(best[k], h[j][k]);
+            }
+            *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
+            uint32_t bits = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bits |= (best[k] != 0xFFFFFFFFu ? 1u : 0u) << (8 * k);
+            *reinterpret_cast<uint32_t *>(cover + (dst - out) + (size_t)r * width) = bits;
+        }
+    }
+}
+
+// Any size / width (coverage form).
+__global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
+                                                                     uint8_t *__restrict__ cover, int views, int width, int height, int size, int stride)
+{
+    const int wp = width + size - 1, hp = height + size - 1;
+    const int quads = (width + 3) / 4;
+    const size_t n = (size_t)views * height * quads;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % quads), py = (int)((i / quads) % height), s = (int)(i / ((size_t)quads * height));
+        const int px = q * 4;
+        const uint32_t *base = zbuf + ((size_t)s * hp + py) * stride + px;
+        uint32_t best[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        for (int dy = 0; dy < size; ++dy) {
+            const uint32_t *row = base + (size_t)dy * stride;
+            for (int dx = 0; dx < size + 3; ++dx) {
+                if (px + dx >= wp) break;
+                const uint32_t v = row[dx];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (dx >= k && dx - k < size) best[k] = min(best[k], v);
+            }
+        }
+        uint8_t *dst = out + ((size_t)s * height + py) * width + px;
+        if (px + 3 < width && (width & 3) == 0) {
+            *reinterpret_cast<uint32_t *>(dst) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
+        } else {
+            for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(best[k] & 0xFFu);  // untouched pixels keep 255
+        }
+        uint8_t *cdst = cover + (dst - out);  // (byte stores: the mask stack has no alignment requirement here)
+        for (int k = 0; k < 4 && px + k < width; ++k) cdst[k] = best[k] != 0xFFFFFFFFu ? 1 : 0;
+    }
+}
+
+// The coverage forms of launch_resolve's kernels (nmi_render_points_masked): the same choice of form, the render bytes the same.
+static void launch_resolve_cover(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, int S, int width, int height, int size, hipStream_t stream)
+{
+    const int stride = zbuf_stride(width, size);
+    const size_t nq = (size_t)S * height * ((width + 3) / 4);
+    dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
+    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && (((uintptr_t)cover & 3) == 0);
+    if (!fast) {
+        hipLaunchKernelGGL(nmi_zbuf_resolve_cover_kernel, grid, block, 0, stream, zbuf, out, cover, S, width, height, size, stride);
+        return;
+    }
+    const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
+    grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
+    switch (size) {
+    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<1>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<2>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<3>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<4>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    default: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<5>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    }
+}
+
 static void launch_resolve(const uint32_t *zbuf, uint8_t *out, int S, int width, int height, int size, hipStream_t stream,
                            const uint32_t *epoch = nullptr, size_t pair_words = 0)
 {
@@ -458,7 +566,7 @@ static void launch_resolve(const uint32_t *zbuf, uint8_t *out, int S, int width,
 size_t render_zbuf_words(int S, int width, int height, int size) { return (size_t)S * zbuf_stride(width, size) * (height + size - 1); }
 
 hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps, int S, uint32_t *zbuf,
-                                uint8_t *out, int width, int height, int size, hipStream_t stream, bool clear_first)
+                                uint8_t *out, int width, int height, int size, hipStream_t stream, bool clear_first, uint8_t *cover)
 {
     const size_t nz = render_zbuf_words(S, width, height, size);
     const size_t n = (size_t)S * width * height;
@@ -473,7 +581,10 @@ hipError_t launch_render_points(const float *xyz, const float *red, long long np
                                mvps + (size_t)s0 * 16, views, zbuf + (size_t)s0 * per_view, width, height, size, stride);
         }
     }
-    launch_resolve(zbuf, out, S, width, height, size, stream);
+    if (cover)
+        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream);
+    else
+        launch_resolve(zbuf, out, S, width, height, size, stream);
     (void)n;
     return hipGetLastError();
 }
