@@ -10,6 +10,7 @@
 // Exit code 0 iff the planted camera offset is recovered (lateral offset as seen in the image within 8 cm, depth within 20 cm).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -158,24 +159,28 @@ static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, co
 
 int main(int argc, char **argv)
 {
-    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--write-files DIR | --files DIR]
+    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered] [--write-files DIR | --files DIR]
     //   --mesh: nmi_prop_RENDER 1, the reference's default render mode: the same surface as NX x NY quads = 2 NX NY textured
     //           triangles, default 300x200 = 120,000;  --density: points per pixel of a view along each axis (cloud; default 0.9)
     //   --masked: the frame's bottom sixth is a "hood" (a flat grey band over the scene); a frame mask excludes it and the levels
     //           are masked ones (nmi_level_set_masks: border masks of the rotated warps + the hood mask)
+    //   --covered: the map has a hole where the frame does not (part of every view is left uncovered); the levels are covered
+    //           ones (nmi_level_set_coverage: the renders' coverage masks + the warps' border masks, + the hood mask with --masked)
     //   --write-files DIR: write the map and a settings file into DIR and stop (no GPU needed)
     //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names
     //           (nmi_config_load, nmi_map_load_obj / _bmp / _xyz) instead of building them in memory
     int keyframes = 200, mesh_nx = 0, mesh_ny = 0;
     float density = 0.9f;
     const char *write_dir = nullptr, *read_dir = nullptr;
-    bool masked = false;
+    bool masked = false, covered = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mesh")) {
             mesh_nx = 300, mesh_ny = 200;
             if (i + 1 < argc && sscanf(argv[i + 1], "%dx%d", &mesh_nx, &mesh_ny) == 2) ++i;
         } else if (!strcmp(argv[i], "--masked")) {
             masked = true;
+        } else if (!strcmp(argv[i], "--covered")) {
+            covered = true;
         } else if (!strcmp(argv[i], "--density") && i + 1 < argc) {
             density = (float)atof(argv[++i]);
         } else if (!strcmp(argv[i], "--write-files") && i + 1 < argc) {
@@ -278,7 +283,7 @@ int main(int argc, char **argv)
     CHECK_NMI(nmi_create(&prm, &ctx));
     nmi_texture *tex = nullptr;
     if (mesh) CHECK_NMI(nmi_texture_create(ctx, rgb.data(), tw, th, &tex));
-    const int64_t n_prims = mesh ? (int64_t)(xyz.size() / 9) : (int64_t)red.size();
+    int64_t n_prims = mesh ? (int64_t)(xyz.size() / 9) : (int64_t)red.size();
     float *d_xyz = nullptr, *d_red = nullptr;
     uint8_t *d_frame = nullptr, *d_tmp = nullptr, *d_hood = nullptr;
     CHECK_HIP(hipMalloc((void **)&d_xyz, xyz.size() * sizeof(float)));
@@ -333,11 +338,34 @@ int main(int argc, char **argv)
         }
         CHECK_HIP(hipMemcpy(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice));
     }
+    if (covered) {
+        // The frame saw the whole surface; the map the levels render has a hole: the points / triangles whose (first) vertex
+        // projects into a rectangle of the tracker's view are dropped, so that part of every render keeps the clear colour.
+        const int per = mesh ? 9 : 3, per_attr = mesh ? 6 : 1;
+        const float u0 = 0.55f * W, u1 = 0.85f * W, v0 = 0.20f * H, v1 = 0.70f * H;
+        size_t kept = 0;
+        for (int64_t k = 0; k < n_prims; ++k) {
+            const float *q = &xyz[(size_t)k * per];
+            const float u = q[0] / q[2] * (float)FX + (float)CX, v = q[1] / q[2] * (float)FY + (float)CY;
+            if (u >= u0 && u < u1 && v >= v0 && v < v1) continue;
+            std::copy(q, q + per, &xyz[kept * per]);
+            std::copy(&red[(size_t)k * per_attr], &red[(size_t)k * per_attr] + per_attr, &red[kept * per_attr]);
+            ++kept;
+        }
+        printf("covered levels: the map leaves x %d..%d, y %d..%d of the tracker's view uncovered (%lld of %lld %s kept)\n", (int)u0,
+               (int)u1 - 1, (int)v0, (int)v1 - 1, (long long)kept, (long long)n_prims, mesh ? "triangles" : "points");
+        n_prims = (int64_t)kept;
+        CHECK_HIP(hipMemcpy(d_xyz, xyz.data(), kept * per * sizeof(float), hipMemcpyHostToDevice));
+        CHECK_HIP(hipMemcpy(d_red, red.data(), kept * per_attr * sizeof(float), hipMemcpyHostToDevice));
+    }
     if (mesh)
         CHECK_NMI(nmi_level_create_mesh(ctx, d_xyz, d_red, n_prims, tex, d_frame, 27, 27, &p.level));
     else
         CHECK_NMI(nmi_level_create(ctx, d_xyz, d_red, n_prims, d_frame, 27, 27, p.rp.point_size, &p.level));
-    if (masked) CHECK_NMI(nmi_level_set_masks(p.level, 1, d_hood));  // every replay: warp masks, counts, masked search
+    if (covered)
+        CHECK_NMI(nmi_level_set_coverage(p.level, 1, d_hood));  // every replay: coverage + warp masks, covered search
+    else if (masked)
+        CHECK_NMI(nmi_level_set_masks(p.level, 1, d_hood));  // every replay: warp masks, counts, masked search
 
     // 3^6 grid with the steps of ETH_small.yaml:83-88
     NmiSearchKernel initial(3, 3, 3, 3, 3, 3, 0.2f, 0.2f, 0.5f, 0.02f, 0.02f, 0.05f);

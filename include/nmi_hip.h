@@ -34,7 +34,8 @@ extern "C" {
                                  nmi_level_create_block, nmi_level_create_mesh_block, nmi_level_run_rccl, nmi_stream_submit_block and
                                  changed NMI_OPT_TILE_QUEUE from queue items to entries per tile bin without a bump; still 2 after
                                  the purely additive nmi_warp_stack_masked, nmi_search_grid_masked, nmi_last_mask_counts,
-                                 nmi_level_set_masks, nmi_level_copy_masks */
+                                 nmi_level_set_masks, nmi_level_copy_masks, and after nmi_level_set_coverage,
+                                 nmi_level_copy_coverage */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -201,13 +202,14 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
  *
  * nmi_search_grid_masked: nmi_search_grid with the masks; len_w is counted on the device from warp_masks (the source of
  * truth: the masks need not come from nmi_warp_stack_masked).  A NULL warp_masks is NMI_ERR_INVALID_ARGUMENT.  Blocking
- * exactly like nmi_search_grid.  Options that choose among nmi_search_grid's kernels (NMI_OPT_SPLIT*,
- * NMI_OPT_CONTENT_PATH) do not apply: the masked search has one kernel, and its results do not depend on them.
+ * exactly like nmi_search_grid.  NMI_OPT_SPLIT* choose the kernel, never the result: mid-size grids take the masked
+ * pixel-range kernel where choose_pix's rules for nmi_search_grid pick pixel ranges (NMI_OPT_SPLIT 0 keeps the masked grid
+ * kernel, NMI_OPT_SPLIT 1 + NMI_OPT_SPLIT_PIXELS P forces P ranges wherever they fit); NMI_OPT_CONTENT_PATH does not apply.
  *
  * nmi_last_mask_counts: len_w of the latest masked search's first n warps (n <= its Wn) to host memory.  Blocking.
  *
- * Render-side masks: see nmi_search_grid_covered below.  Not masked (yet): captured levels, streams, shard / block / RCCL
- * forms, the CUDAF shim.
+ * Render-side masks: see nmi_search_grid_covered below.  Captured levels: nmi_level_set_masks.  Not masked (yet): streams,
+ * shard / block / RCCL forms of the search, the CUDAF shim.
  */
 int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask /* nullable: all valid */,
                           const double *h_forward, int32_t Wn, uint8_t *d_warp_stack, uint8_t *d_warp_masks);
@@ -228,7 +230,9 @@ int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
  * len[w][s] = the number of pos where both masks are nonzero (like W*H, not reduced by the background rule) replaces W*H in
  * the term fl32(p * fl32(log2_f64(p))), p = fl32(c / len[w][s]); len = 0 scores 0.0.  Everything else is
  * nmi_search_grid_masked's: trees, SUC / ENMI, the all-zero guard, the [Wn][S] layout, the arg-max and key rule, blocking
- * behaviour; NMI_OPT_SPLIT* and NMI_OPT_CONTENT_PATH do not apply.  So all-ones render masks give nmi_search_grid_masked's
+ * behaviour.  NMI_OPT_SPLIT* choose the kernel, never the result: mid-size grids take the covered pixel-range kernel by the
+ * masked search's rules (NMI_OPT_SPLIT 0 keeps the covered grid kernel, NMI_OPT_SPLIT 1 + NMI_OPT_SPLIT_PIXELS P forces P
+ * ranges wherever they fit); NMI_OPT_CONTENT_PATH does not apply.  So all-ones render masks give nmi_search_grid_masked's
  * bits, and all-ones masks on both sides nmi_search_grid's.  Masks mean "nonzero" (bytes 1 and 2 both count).
  * NULL masks, S < 1 or Wn < 1 are NMI_ERR_INVALID_ARGUMENT.
  *
@@ -239,7 +243,8 @@ int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
  * exactly where the same call renders 0 with every red 0 (points) or an all-black texture (mesh), and 255 otherwise.
  * Enqueued on the context's stream; a NULL d_render_masks is NMI_ERR_INVALID_ARGUMENT.
  *
- * Not covered (yet): captured levels, streams, shard / block / RCCL forms, the CUDAF shim.
+ * Captured levels: nmi_level_set_coverage.  Not covered (yet): streams, shard / block / RCCL forms of the search, the CUDAF
+ * shim.
  */
 int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int32_t S,
                             const uint8_t *warp_stack, const uint8_t *warp_masks, int32_t Wn, float *ratings /* nullable */,
@@ -372,6 +377,31 @@ int nmi_level_set_masks(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_m
 /* Host copies of the latest replay's warp masks [Wn][H][W] and counts [Wn] (either pointer may be NULL).  Blocking.
  * NMI_ERR_INVALID_ARGUMENT on a level without masks. */
 int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts);
+/*
+ * Covered levels.  nmi_level_set_coverage turns coverage on (enabled = 1) or off (0) for a level made by any of the four
+ * nmi_level_create* calls.  It captures the level's graph again and waits for a replay in flight, as nmi_level_set_masks
+ * does.  Covered, every replay renders with coverage on the level's own render path (the renders stay byte-identical to the
+ * unmasked level's; the masks are nmi_render_points_masked's / nmi_render_mesh_masked's), computes the warps' masks exactly
+ * as nmi_warp_stack_masked does for the same homographies and d_frame_mask (NULL = border masks only), and scores with
+ * nmi_search_grid_covered's arithmetic (the covered grid kernel, or the covered pixel-range kernel for mid-size grids):
+ * ratings, winner index and score bits equal those of nmi_render_*_masked -> nmi_warp_stack_masked ->
+ * nmi_search_grid_covered on the same inputs.  Blocks score their local candidates with their own len[w][s] and report
+ * global indices; empty blocks still take part in the RCCL exchange.  d_frame_mask is kept like d_frame: it must stay valid
+ * in place; its contents may change between runs.  enabled = 0 restores the unmasked graph (d_frame_mask must then be NULL)
+ * and frees the coverage buffers.
+ * A level is unmasked, masked or covered, never two at once: nmi_level_set_coverage on a masked level and
+ * nmi_level_set_masks on a covered level return NMI_ERR_INVALID_ARGUMENT (for either value of enabled) and leave the level
+ * as it was; nmi_level_copy_masks returns NMI_ERR_INVALID_ARGUMENT on a covered level.  A NULL level, enabled outside
+ * {0, 1} or a mask passed with enabled = 0 are NMI_ERR_INVALID_ARGUMENT.
+ * Memory: a covered level owns its render masks (S x H x W bytes), its warp masks (Wn x H x W bytes), len[w][s] (Wn x S
+ * int32) and a redo list (Wn x S int32) -- no term tables: 22 MB for 27 + 27 at 848 x 480.  Never shared with the
+ * standalone covered calls or with other levels.
+ * nmi_level_run, nmi_level_run_rccl, nmi_level_copy_outputs keep their meaning on a covered level.
+ */
+int nmi_level_set_coverage(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask);
+/* Host copies of the latest replay's render masks [S][H][W], warp masks [Wn][H][W] and len [Wn][S] (any pointer may be
+ * NULL).  Blocking.  NMI_ERR_INVALID_ARGUMENT on a level without coverage. */
+int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_warp_masks, int32_t *h_counts);
 int nmi_level_destroy(nmi_level *lv);
 
 /*

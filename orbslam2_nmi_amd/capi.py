@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "nmi_split_status", "nmi_pix_status", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
     "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts", "nmi_level_set_masks", "nmi_level_copy_masks",
     "nmi_render_points_masked", "nmi_render_mesh_masked", "nmi_search_grid_covered", "nmi_last_cover_counts",
+    "nmi_level_set_coverage", "nmi_level_copy_coverage",
 )
 
 
@@ -108,6 +109,8 @@ def load_library(build_if_missing=False):
     lib.nmi_level_copy_outputs.argtypes = [vp, vp, vp, vp]
     lib.nmi_level_set_masks.argtypes = [vp, i32, vp]
     lib.nmi_level_copy_masks.argtypes = [vp, vp, C.POINTER(i32)]
+    lib.nmi_level_set_coverage.argtypes = [vp, i32, vp]
+    lib.nmi_level_copy_coverage.argtypes = [vp, vp, vp, C.POINTER(i32)]
     lib.nmi_level_destroy.argtypes = [vp]
     lib.nmi_stream_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     lib.nmi_stream_destroy.argtypes = [vp]
@@ -784,6 +787,34 @@ class NmiLevel:
         n = np.empty(self.Wn, np.int32)
         self.ctx._check(self._lib.nmi_level_copy_masks(self._h, m.ctypes.data, n.ctypes.data_as(C.POINTER(C.c_int32))), "nmi_level_copy_masks")
         return m, n
+
+    def set_coverage(self, enabled=True, frame_mask=None):
+        """Covered level (nmi_level_set_coverage): every replay also writes the renders' coverage masks and the warps' masks
+        (border masks, and frame_mask where given) and scores with the covered search's arithmetic (masks on both sides).
+        frame_mask: device [H,W] uint8 / bool, nonzero = usable, or None; read in place on every replay and kept alive.
+        enabled=False restores the unmasked level.  A masked level cannot be covered (set_masks(False) first), nor the reverse."""
+        fm = None
+        if frame_mask is not None:
+            if not enabled:
+                raise ValueError("set_coverage(enabled=False) takes no frame_mask")
+            fm = _dev_mask(frame_mask, 2, "frame_mask")
+            if tuple(fm.shape) != (self.ctx.height, self.ctx.width):
+                raise ValueError(f"frame_mask is {tuple(fm.shape)}, context is {(self.ctx.height, self.ctx.width)}")
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_coverage(self._h, int(bool(enabled)), fm.data_ptr() if fm is not None else None),
+                        "nmi_level_set_coverage")
+        self._frame_mask = fm  # the graph holds its device address
+
+    def coverage(self):
+        """-> (render masks [S,H,W] u8, warp masks [Wn,H,W] u8, counts len [Wn,S] int32) of the latest run of a covered level, as
+        numpy (host copies)."""
+        h, w = self.ctx.height, self.ctx.width
+        r = np.empty((self.S, h, w), np.uint8)
+        m = np.empty((self.Wn, h, w), np.uint8)
+        n = np.empty((self.Wn, self.S), np.int32)
+        self.ctx._check(self._lib.nmi_level_copy_coverage(self._h, r.ctypes.data, m.ctypes.data, n.ctypes.data_as(C.POINTER(C.c_int32))),
+                        "nmi_level_copy_coverage")
+        return r, m, n
 
     def close(self):
         if self._h and self._h.value:

@@ -1,6 +1,6 @@
 // nmi_capi_covered.cpp -- the covered entry points of include/nmi_hip.h: nmi_search_grid_covered, nmi_last_cover_counts,
-// nmi_render_points_masked, nmi_render_mesh_masked.  Kernels: nmi_covered_kernel.hip (search), nmi_producers.hip and
-// nmi_mesh.hip (the coverage forms of the renderers' last pass).
+// nmi_render_points_masked, nmi_render_mesh_masked.  Kernels: nmi_covered_kernel.hip and nmi_covered_pix_kernel.hip (mid-size
+// grids) for the search, nmi_producers.hip and nmi_mesh.hip (the coverage forms of the renderers' last pass).
 #include "nmi_covered.h"
 #include "nmi_ctx.h"
 
@@ -79,20 +79,32 @@ int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uin
     m.redo_done = ctx->d_cover_redo_state + 1;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     const int workgroups = (int)(total < cap ? total : cap);
-    if (ctx->xcd_tiling && total <= (1ll << 24)) {
+    // mid-size grids: pixel ranges (nmi_covered_pix_kernel.hip), by nmi_search_grid's rules and controls (choose_pix)
+    const int pix = choose_pix(ctx, a, total, cap);
+    if (pix) {
+        rc = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
+        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
+        if (rc == NMI_OK) rc = ensure_pix_timeouts(ctx);
+        if (rc != NMI_OK) return rc;
+        a.blocks = ctx->d_pix_blocks;
+        a.phase_mask = 3 | (ctx->phase_mask & 512);  // (bit 9: the helpers' hand-off test hook, as for nmi_pix_kernel)
+    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {
         rc = ensure_order(ctx, S, Wn, &a.order);
         if (rc != NMI_OK) return rc;
     }
     // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid
     if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    NMI_HIP_TRY(ctx, nmi::launch_grid_covered(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
+    if (pix)
+        NMI_HIP_TRY(ctx, nmi::launch_pix_covered(m, pix, pix_owner_share(ctx, pix), p.use_bg != 0, nullptr, ctx->d_pix_timeouts, ctx->stream));
+    else
+        NMI_HIP_TRY(ctx, nmi::launch_grid_covered(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
     // accepted: commit the protocol state (enqueue_grid's bookkeeping)
     if (post) ++ctx->seq;
     ctx->posted = post;
     ctx->last_slot = ctx->slot;
     ctx->slot ^= 1;
     ctx->last_parts = 0;
-    ctx->last_pix = 0;
+    ctx->last_pix = pix;
     ctx->last_epoch = 0;
     ctx->last_few = 0;
     ctx->cover_count_n = total;

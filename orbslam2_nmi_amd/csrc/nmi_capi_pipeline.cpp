@@ -1,5 +1,6 @@
 // nmi_capi_pipeline.cpp -- C ABI of the composed forms: one search level as a captured HIP graph (nmi_level_*) and the
 // double-buffered streaming pipeline (nmi_stream_*).  Declared in include/nmi_hip.h.
+#include "nmi_covered.h"
 #include "nmi_ctx.h"
 #include "nmi_masked.h"
 
@@ -65,6 +66,11 @@ struct nmi_level {
     float *d_tables = nullptr;                  // [Wn][npix + 1]
     int32_t *d_redo = nullptr;                  // [S * Wn]
     uint32_t *d_redo_state = nullptr;           // [2], zero between replays
+    // Coverage (nmi_level_set_coverage): the renders' coverage masks and len[w][s] of the latest replay; the warps' masks, the
+    // frame mask and the redo list are the masked level's fields above (a level is never masked and covered at once).
+    bool covered = false;
+    uint8_t *d_rmasks = nullptr;                // [S][H][W], render layout
+    int32_t *d_cover_counts = nullptr;          // [Wn][S]
 };
 
 extern "C" {
@@ -77,7 +83,7 @@ int nmi_level_destroy(nmi_level *lv)
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
     void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks,
-                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state};
+                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts};
     for (void *q : dev)
         if (q) (void)hipFree(q);
     void *host[] = {lv->h_mvps, lv->h_coeffs, lv->h_key};
@@ -93,7 +99,7 @@ int nmi_level_destroy(nmi_level *lv)
 
 }  // extern "C"
 
-// Captures the level's graph (unmasked, or masked when lv->masked) and instantiates it, replacing the previous one only on
+// Captures the level's graph (unmasked, masked when lv->masked, covered when lv->covered) and instantiates it, replacing the previous one only on
 // success.  The caller has waited for the stream.
 static int level_capture(nmi_level *lv)
 {
@@ -114,7 +120,7 @@ static int level_capture(nmi_level *lv)
     nmi::GridArgs a = lv->args;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
-    // (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the
+    // (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip, nmi_covered_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the
     // prep kernel keeps; the level keeps one epoch for all its captures (the replay count only grows, so tags never repeat).
     lv->pix = choose_pix(ctx, a, total, cap);
     if (lv->pix) {
@@ -148,6 +154,20 @@ static int level_capture(nmi_level *lv)
         m.redo_n = lv->d_redo_state;
         m.redo_done = lv->d_redo_state + 1;
     }
+    const bool covered = lv->covered;
+    nmi::CoveredGridArgs cm{};
+    if (covered) {
+        cm.g = a;
+        cm.g.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;
+        cm.warp_masks = lv->d_masks;
+        cm.render_masks = lv->d_rmasks;
+        cm.counts = lv->d_cover_counts;
+        cm.vec_ok = a.vec_ok && (((uintptr_t)lv->d_masks | (uintptr_t)lv->d_rmasks) % 16) == 0;
+        cm.redo = lv->d_redo;
+        cm.redo_n = lv->d_redo_state;
+        cm.redo_done = lv->d_redo_state + 1;
+    }
+    uint8_t *cover = covered ? lv->d_rmasks : nullptr;  // the renderers' coverage masks
     int32_t *d_prev = lv->d_counts + Wn, *d_changed = lv->d_counts + 2 * Wn;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
@@ -162,8 +182,8 @@ static int level_capture(nmi_level *lv)
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
         // Masked: the masks, their counts and the changed warps' tables on that branch too (they need the inverse maps only),
-        // beside the render.
-        if (!fused || masked) {
+        // beside the render.  Covered: the masks alone (no counts, no tables: len[w][s] is counted by the search).
+        if (!fused || masked || covered) {
             ok(hipEventRecord(lv->ev_fork, st));
             ok(hipStreamWaitEvent(lv->side, lv->ev_fork, 0));
             if (!fused) ok(nmi::launch_warp(d_frame, lv->d_coeffs, lv->d_warps, p.width, p.height, Wn, lv->side));
@@ -172,20 +192,26 @@ static int level_capture(nmi_level *lv)
                 ok(nmi::launch_level_mask_counts(lv->d_masks, Wn, ctx->npix, lv->d_counts, d_prev, d_changed, lv->side));
                 ok(nmi::launch_level_mask_tables(lv->d_counts, d_changed, Wn, ctx->npix, lv->d_tables, lv->side));
             }
+            if (covered) ok(nmi::launch_warp_masks(lv->d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
         if (tex)
             ok(nmi::launch_render_mesh(d_xyz, d_attr, n_points, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, lv->d_mvps, S, lv->mesh, S,
                                        (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
-                                       p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn));
+                                       p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
         else if (fused)
             ok(nmi::launch_level_front_points(lv->d_packed, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_epoch, lv->d_renders, p.width, p.height,
-                                              lv->size, d_frame, lv->d_coeffs, lv->d_warps, Wn, st, lv->d_kept, lv->d_kept_count, ctx->compute_units));
+                                              lv->size, d_frame, lv->d_coeffs, lv->d_warps, Wn, st, lv->d_kept, lv->d_kept_count, ctx->compute_units,
+                                              cover));
         else
             ok(nmi::launch_render_points(d_xyz, d_red, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_renders, p.width, p.height, lv->size, st,
-                                         /*clear_first=*/false));
-        if (!fused || masked) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
-        if (masked && lv->pix)
+                                         /*clear_first=*/false, cover));
+        if (!fused || masked || covered) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
+        if (covered && lv->pix)
+            ok(nmi::launch_pix_covered(cm, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
+        else if (covered)
+            ok(nmi::launch_grid_covered(cm, workgroups, true, false, st));
+        else if (masked && lv->pix)
             ok(nmi::launch_pix_masked(m, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
         else if (masked)
             ok(nmi::launch_grid_masked(m, workgroups, true, false, st));
@@ -493,9 +519,11 @@ int nmi_level_copy_outputs(nmi_level *lv, uint8_t *h_renders, uint8_t *h_warps, 
 
 static void level_free_masks(nmi_level *lv)
 {
-    void *dev[] = {lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state};
+    void *dev[] = {lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts};
     for (void *q : dev)
         if (q) (void)hipFree(q);
+    lv->d_rmasks = nullptr;
+    lv->d_cover_counts = nullptr;
     lv->d_masks = nullptr;
     lv->d_counts = nullptr;
     lv->d_tables = nullptr;
@@ -506,6 +534,7 @@ static void level_free_masks(nmi_level *lv)
 int nmi_level_set_masks(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask)
 {
     if (!lv || (enabled != 0 && enabled != 1) || (!enabled && d_frame_mask)) return NMI_ERR_INVALID_ARGUMENT;
+    if (lv->covered) return NMI_ERR_INVALID_ARGUMENT;  // a covered level turns coverage off first (nmi_level_set_coverage)
     nmi_ctx *ctx = lv->ctx;
     ctx->detail.clear();
     if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
@@ -561,6 +590,73 @@ int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks, (size_t)ctx->npix * lv->Wn, hipMemcpyDeviceToHost));
     if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_counts, (size_t)lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NMI_OK;
+}
+
+int nmi_level_set_coverage(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask)
+{
+    if (!lv || (enabled != 0 && enabled != 1) || (!enabled && d_frame_mask)) return NMI_ERR_INVALID_ARGUMENT;
+    if (lv->masked) return NMI_ERR_INVALID_ARGUMENT;  // a masked level turns its masks off first (nmi_level_set_masks)
+    nmi_ctx *ctx = lv->ctx;
+    ctx->detail.clear();
+    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
+        lv->covered = enabled != 0;
+        lv->d_frame_mask = d_frame_mask;
+        return NMI_OK;
+    }
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
+    const size_t npix = (size_t)ctx->npix, S = (size_t)lv->S, Wn = (size_t)lv->Wn;
+    // Turning coverage on for a level that is not covered: what a failed nmi_level_set_masks may have left behind is freed
+    // first, and what this call allocates is freed again if its capture fails -- so a level that is neither masked nor covered
+    // never holds mode buffers another mode's call would take for its own.
+    const bool fresh = enabled && !lv->covered;
+    if (fresh) {
+        level_free_masks(lv);
+        hipError_t e = hipSuccess;
+        auto ok = [&](hipError_t r) {
+            if (e == hipSuccess) e = r;
+        };
+        ok(hipMalloc((void **)&lv->d_masks, npix * Wn));
+        ok(hipMalloc((void **)&lv->d_rmasks, npix * S));
+        ok(hipMalloc((void **)&lv->d_cover_counts, S * Wn * sizeof(int32_t)));
+        ok(hipMalloc((void **)&lv->d_redo, S * Wn * sizeof(int32_t)));
+        ok(hipMalloc((void **)&lv->d_redo_state, 2 * sizeof(uint32_t)));
+        if (e == hipSuccess) ok(hipMemset(lv->d_masks, 0, npix * Wn));
+        if (e == hipSuccess) ok(hipMemset(lv->d_rmasks, 0, npix * S));
+        if (e == hipSuccess) ok(hipMemset(lv->d_cover_counts, 0, S * Wn * sizeof(int32_t)));
+        if (e == hipSuccess) ok(hipMemset(lv->d_redo_state, 0, 2 * sizeof(uint32_t)));
+        if (e != hipSuccess) {
+            level_free_masks(lv);
+            return hip_fail(ctx, e, "nmi_level_set_coverage");
+        }
+    }
+    const bool was = lv->covered;
+    const uint8_t *was_mask = lv->d_frame_mask;
+    lv->covered = enabled != 0;
+    lv->d_frame_mask = d_frame_mask;
+    const int rc = level_capture(lv);
+    if (rc != NMI_OK) {
+        lv->covered = was;
+        lv->d_frame_mask = was_mask;
+        if (fresh) level_free_masks(lv);
+        return rc;
+    }
+    if (!enabled) level_free_masks(lv);
+    return NMI_OK;
+}
+
+int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_warp_masks, int32_t *h_counts)
+{
+    if (!lv || !lv->covered) return NMI_ERR_INVALID_ARGUMENT;
+    if (lv->S == 0 || lv->Wn == 0) return NMI_OK;  // empty block: nothing was produced
+    nmi_ctx *ctx = lv->ctx;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t npix = (size_t)ctx->npix;
+    if (h_render_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_render_masks, lv->d_rmasks, npix * lv->S, hipMemcpyDeviceToHost));
+    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks, npix * lv->Wn, hipMemcpyDeviceToHost));
+    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_cover_counts, (size_t)lv->S * lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 

@@ -26,5 +26,13 @@ struct CoveredGridArgs {
 // than 256 bins); otherwise an optimistic launch and an exact launch for the candidates whose count test failed (m.redo must
 // be set).  Either way the last launch posts the winner (m.g.mailbox / out_key).
 hipError_t launch_grid_covered(const CoveredGridArgs &m, int workgroups, bool use_bg, bool exact, hipStream_t stream);
+// Mid-size grids (nmi_covered_pix_kernel.hip): pix_parts workgroups per candidate over dealt pixel ranges, nmi_pix_kernel's
+// hand-off through m.g.blocks (pix_block_bytes, zero when allocated; tag from m.g.epoch + *replay); len[w][s] is the sum of the
+// ranges' counts.  Candidates that wrap a counter or whose helper does not arrive in time are scored exactly by their owner
+// inside the launch and counted in *healed.  Needs m.g.order == nullptr, m.g.epoch != 0, width >= 32, and every covered
+// pixel added (the background rule on, or off at 256 bins); m.redo is not used.  Writes m.counts and posts the winner like
+// launch_grid_covered.
+hipError_t launch_pix_covered(const CoveredGridArgs &m, int pix_parts, double owner_share, bool use_bg, const uint32_t *replay, uint32_t *healed,
+                              hipStream_t stream);
 
 }  // namespace nmi

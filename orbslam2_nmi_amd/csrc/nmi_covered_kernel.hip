@@ -19,14 +19,19 @@
 //     the bytes are tested, never ANDed raw (0x01 & 0x02 == 0).
 //   * Wrap detector and redo: nmi_masked_grid_kernel's rules with the expected total taken from the in-kernel len.
 //   * Shapes.  Whole aligned 16-byte chunks (width % 16 == 0, width >= 32, both stacks and both masks 16-byte aligned) take the
-//     16-byte path; every other shape takes a byte path.  One kernel for every grid size: no split, pixel-range or few-levels form.
+//     16-byte path; every other shape takes a byte path.  No split or few-levels form; mid-size grids
+//     take the pixel-range form of nmi_covered_pix_kernel.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// nmi_covered_pix_kernel.hip includes this file for its device functions only (NMI_COVERED_DEVICE_ONLY), after nmi_kernels.hip
+// and nmi_masked_kernel.hip.
+#ifndef NMI_COVERED_DEVICE_ONLY
 #define NMI_KERNELS_DEVICE_ONLY 1
 #include "nmi_kernels.hip"  // Lds, add_chunk, apply_wraps, the trees, commit_score, finish_search, candidate_at
 #define NMI_MASKED_DEVICE_ONLY 1
 #include "nmi_masked_kernel.hip"  // masked_add_chunk, nonzero_byte_bits
+#endif
 #include "nmi_covered.h"
 
 namespace nmi {
@@ -234,6 +239,7 @@ __device__ __forceinline__ void covered_final_phase(Lds &lds, const GridArgs &a,
 
 }  // namespace
 
+#ifndef NMI_COVERED_DEVICE_ONLY
 // One workgroup per candidate, grid-stride over the candidates in the visiting order -- nmi_masked_grid_kernel's structure
 // with one more barrier: B1 histogram -> terms, B1b terms -> decode, B2 decode -> (wavefront 0: final trees + score + arg-max)
 // || (the others: next candidate's pixels).  lds.table holds the candidate's terms from B1b until wavefront 0 has finished
@@ -358,5 +364,6 @@ hipError_t launch_grid_covered(const CoveredGridArgs &m, int workgroups, bool us
     }
     return hipGetLastError();
 }
+#endif  // !NMI_COVERED_DEVICE_ONLY
 
 }  // namespace nmi

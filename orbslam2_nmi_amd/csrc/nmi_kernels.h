@@ -206,7 +206,8 @@ hipError_t launch_level_front_points(const void *packed, long long npoints, cons
                                      const uint32_t *epoch, uint8_t *out, int width, int height, int size, const uint8_t *frame,
                                      const float *coeffs, uint8_t *warps, int Wn, hipStream_t stream,
                                      const uint32_t *kept /* [ceil(n / 64)]: wavefronts in reach of a view, made by the prep kernel */,
-                                     const uint32_t *kept_count /* [2], by replay parity */, int compute_units);
+                                     const uint32_t *kept_count /* [2], by replay parity */, int compute_units,
+                                     uint8_t *cover = nullptr /* [S][H][W] coverage masks (4-byte aligned), as launch_render_points */);
 hipError_t launch_level_prep(const float *h_mvps, float *d_mvps, int n_mvps, const float *h_coeffs, float *d_coeffs, int n_coeffs,
                              unsigned long long *key, uint32_t *zbuf, size_t nz, hipStream_t stream, uint32_t *epoch = nullptr,
                              const void *packed = nullptr, long long npoints = 0, const float *h_bound /* pinned: 24 floats + parity word */ = nullptr,

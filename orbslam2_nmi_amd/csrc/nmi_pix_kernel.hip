@@ -185,6 +185,7 @@ __device__ __forceinline__ int unit_offset(int wave, int kk, int lane) { return 
 // The owner's decode: decode_phase (ComputeEntropyKernel + AddvectorParwiseMidKernel, NMI.cu:230-287) over its own packed
 // counters PLUS the helpers' (acc: their units of this lane, already summed field by field), with two differences: counters
 // are not cleared (the workgroup scores one candidate) and there are no wrap events to replay (nobody used returning atomics).
+// TWIN: covered_decode_merged (nmi_covered_pix_kernel.hip) is a copy with per-candidate terms -- a fix here belongs there too.
 template <bool ZERO0>
 __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int wave, int lane, const u32x4 (&acc)[kUnitsPerLane])
 {
