@@ -240,7 +240,8 @@ int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
  *
  * nmi_render_points_masked / nmi_render_mesh_masked: nmi_render_points / nmi_render_mesh (d_render_stack byte-identical)
  * plus d_render_masks uint8 [S][H][W], render layout: 1 where a fragment won the pixel, 0 where it kept the clear colour --
- * exactly where the same call renders 0 with every red 0 (points) or an all-black texture (mesh), and 255 otherwise.
+ * exactly where the same call renders 0 with every red 0 (points) or an all-black texture (mesh), and 255 otherwise -- apart
+ * from points at the far plane with colour 255, whose key is the background's (nmi_render_points).
  * Enqueued on the context's stream; a NULL d_render_masks is NMI_ERR_INVALID_ARGUMENT.
  *
  * Captured levels: nmi_level_set_coverage.  Not covered (yet): streams, shard / block / RCCL forms of the search, the CUDAF
@@ -258,6 +259,17 @@ int nmi_last_cover_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
  * rendering.hpp:196-202,547-553 (column-major float[16] like glm); nmi_render_points draws the cloud into
  * d_render_stack [S][H][W] (uint8, bottom-up rows like the GL texture, background 255).  d_xyz: float [N][3] vertices
  * (loadXYZ output, objloader.cpp:257-260), d_red: float [N] red colour component (objloader.cpp:261: file value / 256).
+ * Point rule: a point is drawn iff its clip coordinate w is a positive normal float and |x|, |y|, |z| <= w (a NaN coordinate
+ * is not drawn); odd sizes are centred on floor(xw) + 0.5, even sizes on floor(xw + 0.5); depth = min(round(zw * (2^24 - 1)),
+ * 2^24 - 1), so a point at the far plane has the largest depth and loses to anything nearer; colour = round(clamp(red, 0, 1)
+ * * 255), a NaN red giving 0.  Each pixel keeps the smallest depth << 8 | colour: among equal 24-bit depths the SMALLER red
+ * wins, where GL_LESS would keep the point drawn first (a deliberate deviation: one atomicMin per point and view).  A second
+ * deliberate deviation: the reference clears depth to 1.0 and tests GL_LESS (rendering.hpp:294-297), so it draws no point at
+ * the far plane; here such a point is drawn at depth 2^24 - 1, behind everything nearer, and covered -- except with colour
+ * 255, whose key is the background's: it leaves 255 and is not covered (nmi_render_points_masked).
+ * point_size: NaN is NMI_ERR_INVALID_ARGUMENT; otherwise the size is rounded to nearest, floor(point_size + 0.5) in float,
+ * and clamped to [1, 64] before any conversion to int, so 1e10 and inf draw 64 x 64 sprites.  The same rule holds for
+ * nmi_level_create / nmi_level_create_block.
  * Enqueued on the context's stream.  Parity with an OpenGL driver's rasteriser is unpinned (kernel comment).
  */
 typedef struct nmi_render_params {

@@ -253,6 +253,8 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
         return NMI_ERR_INVALID_ARGUMENT;
     if ((int64_t)blk.S_total * blk.Wn_total >= 0x7FFFFFFFll) return NMI_ERR_UNSUPPORTED;  // index lives in 32 bits of the key
     if (tex && tex->ctx != ctx) return NMI_ERR_INVALID_ARGUMENT;
+    int size = 1;  // (a mesh level has no point size)
+    if (!tex && point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     if (!ctx->params.use_bg) return NMI_ERR_UNSUPPORTED;
     *out = nullptr;
     ctx->detail.clear();
@@ -279,8 +281,7 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
         *out = lv;
         return NMI_OK;
     }
-    int size = (int)floorf(point_size + 0.5f);
-    lv->size = size < 1 ? 1 : (size > 64 ? 64 : size);
+    lv->size = size;
     const nmi_params &p = ctx->params;
     const size_t npix = (size_t)ctx->npix;
     const int64_t total = (int64_t)S * Wn;

@@ -220,6 +220,16 @@ int nmi_render_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int6
 
 namespace nmi_internal {
 
+// glPointSize: non-antialiased points use the size rounded to the nearest integer, at least 1 (OpenGL 3.3, 3.4.1), and at most
+// the largest supported size (64 here).  The clamp is done in float: converting 1e10, inf or NaN to int is undefined.
+int point_sprite_size(float point_size, int *size)
+{
+    if (std::isnan(point_size)) return NMI_ERR_INVALID_ARGUMENT;
+    const float s = floorf(point_size + 0.5f);
+    *size = s < 1.0f ? 1 : (s > 64.0f ? 64 : (int)s);
+    return NMI_OK;
+}
+
 int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
                        float point_size, uint8_t *d_render_stack, uint8_t *cover)
 {
@@ -227,10 +237,8 @@ int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int
         return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    // glPointSize: non-antialiased points use the size rounded to the nearest integer, at least 1 (OpenGL 3.3, 3.4.1)
-    int size = (int)floorf(point_size + 0.5f);
-    if (size < 1) size = 1;
-    if (size > 64) size = 64;
+    int size = 1;
+    if (point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     const int64_t need = (int64_t)nmi::render_zbuf_words(S, ctx->params.width, ctx->params.height, size);
     if (need > ctx->zbuf_cap) {
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

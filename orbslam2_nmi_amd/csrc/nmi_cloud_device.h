@@ -26,7 +26,7 @@ namespace {
 // Returns false for a clipped point or an anchor outside the padded buffer.
 // The view loops are bound by vector-instruction issue, so this is written for instruction count: components in pairs through
 // the packed fp32 instructions ((cx, cy) and (cz, cw) -- the matrix is column-major, so each pair's coefficients are adjacent
-// floats; IEEE results per element, never fused: -ffp-contract=off), the six clip comparisons as one maximum of magnitudes, and
+// floats; IEEE results per element, never fused: -ffp-contract=off), the six clip comparisons as three on magnitudes, and
 // the reciprocal by warp_rcp (nmi_warp_device.h: bit-identical to the division, checked for every float).  Values are those of
 // the plain expressions in the comments, bit for bit (the fp32 twin oracle/render_oracle_np.py checks them).
 template <typename M>
@@ -38,16 +38,19 @@ __device__ __forceinline__ bool splat_anchor(const M &m, float x, float y, float
     const v2f cxy = (v2f{m[0], m[1]} * X + v2f{m[4], m[5]} * Y) + (v2f{m[8], m[9]} * Z + v2f{m[12], m[13]});
     const v2f czw = (v2f{m[2], m[3]} * X + v2f{m[6], m[7]} * Y) + (v2f{m[10], m[11]} * Z + v2f{m[14], m[15]});
     const float cw = czw.y;
-    // point clipping:  !(cw > 0) || cx < -cw || cx > cw || cy < -cw || cy > cw || cz < -cw || cz > cw.  The six comparisons are
-    // "the largest magnitude exceeds cw" (fmaxf passes over a NaN operand, and a comparison with NaN is false, exactly as there)
-    if (!(cw > 0.0f)) return false;
-    if (fmaxf(fmaxf(fabsf(cxy.x), fabsf(cxy.y)), fabsf(czw.x)) > cw) return false;
+    // point clipping:  keep iff cw is a positive normal float and |cx|, |cy|, |cz| <= cw -- the six comparisons
+    // -cw <= c <= cw as three on magnitudes, each written so that a NaN fails it (fmaxf would pass over a NaN operand and keep a
+    // point whose cx alone is NaN).  cw in [FLT_MIN, FLT_MAX] (one class test) keeps the reciprocal finite and every window
+    // coordinate below finite: a positive subnormal cw (1 / cw overflows; 0 * inf is NaN) or an infinite one (inf * 0) could
+    // otherwise reach the float -> int conversions with a NaN.
+    if (!__builtin_isfpclass(cw, __FPCLASS_POSNORMAL)) return false;
+    if (!(fabsf(cxy.x) <= cw) | !(fabsf(cxy.y) <= cw) | !(fabsf(czw.x) <= cw)) return false;
     // the perspective divide as one (correctly rounded) reciprocal and three products:
     //   xw = (cx * iw * 0.5f + 0.5f) * width, yw likewise with height, zw = cz * iw * 0.5f + 0.5f
     const float iw = warp_rcp(cw);
     const v2f win = ((cxy * iw) * 0.5f + 0.5f) * v2f{(float)width, (float)height};
     const float zw = czw.x * iw * 0.5f + 0.5f;
-    const uint32_t depth = (uint32_t)(zw * 16777215.0f + 0.5f);
+    const uint32_t depth = min((uint32_t)(zw * 16777215.0f + 0.5f), 0xFFFFFFu);  // (at zw = 1 the fp32 sum rounds up to 2^24: the far plane is the largest depth)
     frag = (depth << 8) | colour;
     // odd sizes are centred on floor(xw) + 0.5, even sizes on floor(xw + 0.5); the anchor is the sprite's lowest-left pixel in the
     // buffer padded by size - 1:  x0 + size - 1

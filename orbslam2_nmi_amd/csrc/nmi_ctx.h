@@ -164,6 +164,10 @@ int ensure_mesh_pairs(nmi_ctx *ctx, nmi::MeshWork *w, long long n_triangles);  /
 // The 9 floats the warp kernels take for one forward homography (nmi_capi_producers.cpp): NMI_ERR_INVALID_ARGUMENT for a
 // non-finite or singular matrix.  Shared by nmi_warp_stack, nmi_warp_stack_masked and the level replays.
 int warp_inverse_coeffs(const double *forward /*[9]*/, float *coeffs /*[9]*/);
+// The sprite side for a point size (include/nmi_hip.h, nmi_render_points): NMI_ERR_INVALID_ARGUMENT for NaN, else the size
+// rounded to nearest and clamped to [1, 64] in float before the conversion to int.  Shared by render_points_impl and
+// nmi_level_create.
+int point_sprite_size(float point_size, int *size);
 int level_enqueue(nmi_level *lv, const float *h_mvps, const double *h_forward, const unsigned long long **d_key);
 nmi_ctx *level_ctx(nmi_level *lv);
 // ncclAllReduce(ncclMax, ncclUint64) of one 8-byte key on the context's stream, out of place (nmi_capi_rccl.cpp)

@@ -111,7 +111,7 @@ hipError_t launch_warp(const uint8_t *frame, const float *coeffs, uint8_t *out, 
 // non-antialiased points (centre clipped against the view volume; size rounded to an integer >= 1; odd sizes centred on
 // floor(x)+0.5, even sizes on floor(x+0.5); 24-bit depth) evaluated in fp32 -- parity with a GL driver is unpinned.
 // Depth test + colour write are one 32-bit atomicMin on (depth24 << 8 | red8); equal depths resolve to the darker
-// fragment (GL: the first drawn).  Rows are written bottom-up like a GL texture (what NMI.cu:82 flips back).
+// fragment (GL: the first drawn -- a deliberate deviation, include/nmi_hip.h).  Rows are written bottom-up like a GL texture (what NMI.cu:82 flips back).
 __global__ __launch_bounds__(256) void nmi_zbuf_clear_kernel(uint32_t *zbuf, size_t n)
 {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) zbuf[i] = 0xFFFFFFFFu;
