@@ -34,8 +34,10 @@ extern "C" {
                                  nmi_level_create_block, nmi_level_create_mesh_block, nmi_level_run_rccl, nmi_stream_submit_block and
                                  changed NMI_OPT_TILE_QUEUE from queue items to entries per tile bin without a bump; still 2 after
                                  the purely additive nmi_warp_stack_masked, nmi_search_grid_masked, nmi_last_mask_counts,
-                                 nmi_level_set_masks, nmi_level_copy_masks, and after nmi_level_set_coverage,
-                                 nmi_level_copy_coverage */
+                                 nmi_level_set_masks, nmi_level_copy_masks, after nmi_level_set_coverage,
+                                 nmi_level_copy_coverage, and after nmi_pack_mask_bits, nmi_stream_submit_masked,
+                                 nmi_stream_submit_masked_block, nmi_stream_submit_covered, nmi_stream_submit_covered_block,
+                                 nmi_stream_copy_counts */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -208,8 +210,8 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
  *
  * nmi_last_mask_counts: len_w of the latest masked search's first n warps (n <= its Wn) to host memory.  Blocking.
  *
- * Render-side masks: see nmi_search_grid_covered below.  Captured levels: nmi_level_set_masks.  Not masked (yet): streams,
- * shard / block / RCCL forms of the search, the CUDAF shim.
+ * Render-side masks: see nmi_search_grid_covered below.  Captured levels: nmi_level_set_masks.  Streams:
+ * nmi_stream_submit_masked.  Not masked (yet): shard / block / RCCL forms of the standalone search, the CUDAF shim.
  */
 int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask /* nullable: all valid */,
                           const double *h_forward, int32_t Wn, uint8_t *d_warp_stack, uint8_t *d_warp_masks);
@@ -244,13 +246,20 @@ int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
  * from points at the far plane with colour 255, whose key is the background's (nmi_render_points).
  * Enqueued on the context's stream; a NULL d_render_masks is NMI_ERR_INVALID_ARGUMENT.
  *
- * Captured levels: nmi_level_set_coverage.  Not covered (yet): streams, shard / block / RCCL forms of the search, the CUDAF
- * shim.
+ * Captured levels: nmi_level_set_coverage.  Streams: nmi_stream_submit_covered.  Not covered (yet): shard / block / RCCL forms
+ * of the standalone search, the CUDAF shim.
+ *
+ * nmi_pack_mask_bits: bit-packed masks, the form in which a covered stream ticket carries its render masks over PCIe (1/8 of
+ * the render stack's bytes).  Image i of n occupies ceil(H*W/8) bytes; pixel p (row-major, in the image's own layout) is bit
+ * p % 8 (LSB first) of byte p / 8; bits past H*W in the last byte are 0 when packed here and ignored when read
+ * == np.packbits(masks.reshape(n, -1) != 0, axis=1, bitorder="little").  Enqueued on the context's stream.  For a producer
+ * that renders coverage on a GPU (nmi_render_*_masked), packs it there and copies only the bits to host memory.
  */
 int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int32_t S,
                             const uint8_t *warp_stack, const uint8_t *warp_masks, int32_t Wn, float *ratings /* nullable */,
                             int64_t *best_linear_idx, float *best_score);
 int nmi_last_cover_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
+int nmi_pack_mask_bits(nmi_ctx *ctx, const uint8_t *d_masks /*[n][H][W]*/, int32_t n, uint8_t *d_bits /*[n][ceil(H*W/8)]*/);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
@@ -450,6 +459,45 @@ int nmi_stream_wait(nmi_stream *st, int64_t ticket, int64_t *h_best_index, float
  * slot is submitted to again. */
 int nmi_stream_keep_ratings(nmi_stream *st, int32_t enabled);
 int nmi_stream_copy_ratings(nmi_stream *st, int64_t ticket, float *h_ratings, int64_t n);
+/*
+ * Masked and covered tickets: the stream's forms of nmi_search_grid_masked and nmi_search_grid_covered.  A ticket's winner
+ * index, score bits, rating table (nmi_stream_keep_ratings) and counts are those of the standalone calls on the same inputs:
+ *   masked   nmi_warp_stack_masked(frame, frame_mask, forward) followed by nmi_search_grid_masked;
+ *   covered  the same warps and warp masks, the render masks unpacked from h_render_mask_bits (nmi_pack_mask_bits' layout,
+ *            [S][ceil(H*W/8)], render layout), and nmi_search_grid_covered.
+ * The _block forms report global indices exactly as nmi_stream_submit_block does, their cells equal the whole grid's cells,
+ * and with nccl_comm the key is MAX-all-reduced right behind the search; empty blocks (S_local == 0) still take part.
+ *   h_frame_mask  uint8 [H][W], nonzero = usable, uploaded with the frame on the copy stream; NULL = border masks only.  A
+ *                 frame mask without a frame is NMI_ERR_INVALID_ARGUMENT.
+ *   h_frame NULL  reuses the warps AND warp masks of the most recent frame submission; when that was a plain nmi_stream_submit*
+ *                 (which makes no masks) the call is NMI_ERR_INVALID_ARGUMENT.  A plain frame-less ticket after a masked or
+ *                 covered frame is fine (the warp stack is byte-identical).
+ *   h_render_mask_bits  must stay valid until the ticket completes, like h_render_stack; NULL with S > 0 is
+ *                 NMI_ERR_INVALID_ARGUMENT.  The bits cross PCIe (+12.5 % on the render stack) and are unpacked on the device.
+ * One stream carries any mix of plain, masked and covered tickets; they complete in submission order.  Masked and covered
+ * tickets never use the split kernel, so nmi_stream_wait never returns NMI_ERR_NOT_READY for them; mid-size grids take the
+ * masked / covered pixel-range kernel by the standalone calls' rules (those heal inside the launch).  They leave
+ * nmi_last_mask_counts / nmi_last_cover_counts reporting the latest standalone search.
+ * Memory, allocated on the stream's first masked or covered submission (never for a plain-only stream): 2 x H*W (frame masks)
+ * + 2 x max_Wn x H*W (warp masks) + (depth + 1) x max_S x max_Wn x 4 bytes (counts, redo list); on the first masked one also
+ * 2 x max_Wn x (H*W + 1) x 4 bytes (term tables: 88 MB at 27 warps and 848 x 480) + 2 x max_Wn x 4; on the first covered one
+ * depth x max_S x ceil(H*W/8) (bits) + max_S x H*W (one unpacked render-mask buffer shared by all slots).
+ * nmi_stream_copy_counts: len_w [Wn] of a masked ticket, len[w][s] [Wn][S] of a covered ticket (n must be exactly that);
+ * valid from nmi_stream_wait until the slot is reused.  NMI_ERR_INVALID_ARGUMENT on a plain ticket.
+ */
+int nmi_stream_submit_masked(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, const uint8_t *h_frame,
+                             const uint8_t *h_frame_mask /* nullable */, const double *h_forward, int32_t Wn, int64_t *ticket);
+int nmi_stream_submit_masked_block(nmi_stream *st, const uint8_t *h_render_stack, int32_t S_local, int32_t s_offset, int32_t S_total,
+                                   const uint8_t *h_frame, const uint8_t *h_frame_mask /* nullable */, const double *h_forward,
+                                   int32_t Wn_local, int32_t w_offset, int32_t Wn_total, void *nccl_comm, int64_t *ticket);
+int nmi_stream_submit_covered(nmi_stream *st, const uint8_t *h_render_stack, const uint8_t *h_render_mask_bits, int32_t S,
+                              const uint8_t *h_frame, const uint8_t *h_frame_mask /* nullable */, const double *h_forward,
+                              int32_t Wn, int64_t *ticket);
+int nmi_stream_submit_covered_block(nmi_stream *st, const uint8_t *h_render_stack, const uint8_t *h_render_mask_bits, int32_t S_local,
+                                    int32_t s_offset, int32_t S_total, const uint8_t *h_frame, const uint8_t *h_frame_mask /* nullable */,
+                                    const double *h_forward, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, void *nccl_comm,
+                                    int64_t *ticket);
+int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, int64_t n);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

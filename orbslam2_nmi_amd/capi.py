@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = (
     "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts", "nmi_level_set_masks", "nmi_level_copy_masks",
     "nmi_render_points_masked", "nmi_render_mesh_masked", "nmi_search_grid_covered", "nmi_last_cover_counts",
     "nmi_level_set_coverage", "nmi_level_copy_coverage",
+    "nmi_pack_mask_bits", "nmi_stream_submit_masked", "nmi_stream_submit_masked_block", "nmi_stream_submit_covered",
+    "nmi_stream_submit_covered_block", "nmi_stream_copy_counts",
 )
 
 
@@ -118,6 +120,12 @@ def load_library(build_if_missing=False):
     lib.nmi_stream_wait.argtypes = [vp, C.c_int64, i64p, f32p]
     lib.nmi_stream_keep_ratings.argtypes = [vp, i32]
     lib.nmi_stream_copy_ratings.argtypes = [vp, C.c_int64, f32p, C.c_int64]
+    lib.nmi_pack_mask_bits.argtypes = [vp, vp, i32, vp]
+    lib.nmi_stream_submit_masked.argtypes = [vp, vp, i32, vp, vp, C.POINTER(C.c_double), i32, i64p]
+    lib.nmi_stream_submit_masked_block.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double), i32, i32, i32, vp, i64p]
+    lib.nmi_stream_submit_covered.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(C.c_double), i32, i64p]
+    lib.nmi_stream_submit_covered_block.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double), i32, i32, i32, vp, i64p]
+    lib.nmi_stream_copy_counts.argtypes = [vp, C.c_int64, C.POINTER(i32), C.c_int64]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -496,6 +504,24 @@ class NmiContext:
         self._check(self._lib.nmi_last_cover_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)), "nmi_last_cover_counts")
         return out
 
+    def pack_mask_bits(self, masks, out=None, sync=True):
+        """Bit-pack device masks [n,H,W] (uint8 / bool, nonzero = set) -> device uint8 [n, ceil(H*W/8)] (nmi_pack_mask_bits):
+        pixel p of image i is bit p % 8 (LSB first) of byte p // 8 of row i, as np.packbits(..., bitorder="little").  The form in
+        which NmiStream.submit_covered takes render masks."""
+        import torch
+        m = self._mask_stack(masks, "masks")
+        n, nb = m.shape[0], (self.width * self.height + 7) // 8
+        if out is None:
+            out = torch.empty((n, nb), dtype=torch.uint8, device=self.device)
+        o = _dev_u8(out, 2, "out")
+        if tuple(o.shape) != (n, nb):
+            raise ValueError(f"out is {tuple(o.shape)}, bits need {(n, nb)}")
+        self._order_after_torch()
+        self._check(self._lib.nmi_pack_mask_bits(self._h, m.data_ptr(), n, o.data_ptr()), "nmi_pack_mask_bits")
+        if sync:
+            self.synchronize()
+        return out
+
     def render_points_masked(self, xyz, red, mvps, point_size, out=None, out_masks=None, sync=True):
         """render_points plus its coverage (nmi_render_points_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
         where a point won the pixel, 0 where it kept the background; bottom-up rows like the renders, which are
@@ -864,6 +890,70 @@ class NmiStream:
                                                               wn, wo, wt, comm, C.byref(t)), "nmi_stream_submit_block")
         self._keep[t.value] = (rs, frame_host, m)  # keep host buffers alive until the ticket completes
         return int(t.value)
+
+    def _host_u8(self, t, what, nbytes):
+        if t.is_cuda or str(t.dtype) != "torch.uint8" or not t.is_contiguous() or t.numel() != nbytes:
+            raise TypeError(f"{what} must be a contiguous CPU uint8 tensor of {nbytes} bytes (pinned for overlap)")
+        return t.data_ptr() if nbytes else None
+
+    def _submit_masked(self, kind, render_stack_host, bits_host, frame_host, frame_mask_host, homographies, block, comm):
+        rs = render_stack_host
+        if rs.is_cuda or str(rs.dtype) != "torch.uint8" or not rs.is_contiguous():
+            raise TypeError("render_stack_host must be a contiguous CPU uint8 tensor (pinned for overlap)")
+        S, npix = rs.shape[0], self.ctx.width * self.ctx.height
+        bp = None
+        if kind == "covered":
+            if bits_host is None:
+                raise ValueError("submit_covered needs the render masks' bits (NmiContext.pack_mask_bits / np.packbits little)")
+            bp = self._host_u8(bits_host, "render_mask_bits_host", S * ((npix + 7) // 8))
+        fp, fmp, mp, wn, m = None, None, None, 0, None
+        if frame_host is not None:
+            m = np.ascontiguousarray(homographies, np.float64).reshape(-1, 9)
+            fp, mp, wn = self._host_u8(frame_host, "frame_host", npix), m.ctypes.data_as(C.POINTER(C.c_double)), m.shape[0]
+        if frame_mask_host is not None:
+            if frame_host is None:
+                raise ValueError("frame_mask_host goes with a frame_host")
+            fmp = self._host_u8(frame_mask_host, "frame_mask_host", npix)
+        t = C.c_int64(-1)
+        rp = rs.data_ptr() if S else None
+        if block is None and comm is None:
+            if kind == "covered":
+                rc = self._lib.nmi_stream_submit_covered(self._h, rp, bp, S, fp, fmp, mp, wn, C.byref(t))
+            else:
+                rc = self._lib.nmi_stream_submit_masked(self._h, rp, S, fp, fmp, mp, wn, C.byref(t))
+        else:
+            if block is None:
+                raise ValueError(f"NmiStream.submit_{kind}(comm=...) needs block=(s_offset, S_total, w_offset, Wn_total)")
+            so, st, wo, wt = (int(v) for v in block)
+            if kind == "covered":
+                rc = self._lib.nmi_stream_submit_covered_block(self._h, rp, bp, S, so, st, fp, fmp, mp, wn, wo, wt, comm, C.byref(t))
+            else:
+                rc = self._lib.nmi_stream_submit_masked_block(self._h, rp, S, so, st, fp, fmp, mp, wn, wo, wt, comm, C.byref(t))
+        self.ctx._check(rc, f"nmi_stream_submit_{kind}")
+        self._keep[t.value] = (rs, bits_host, frame_host, frame_mask_host, m)  # host buffers stay alive until the ticket completes
+        return int(t.value)
+
+    def submit_masked(self, render_stack_host, frame_host=None, frame_mask_host=None, homographies=None, block=None, comm=None):
+        """submit with warp masks (nmi_stream_submit_masked[_block]): the ticket equals nmi_warp_stack_masked + search_grid_masked.
+        frame_mask_host: optional pinned CPU uint8 [H,W], nonzero = usable, only with a frame.  Without a frame the warps and warp
+        masks of the most recent (masked or covered) frame are reused.  block / comm as for submit."""
+        return self._submit_masked("masked", render_stack_host, None, frame_host, frame_mask_host, homographies, block, comm)
+
+    def submit_covered(self, render_stack_host, render_mask_bits_host, frame_host=None, frame_mask_host=None, homographies=None,
+                       block=None, comm=None):
+        """submit with masks on both sides (nmi_stream_submit_covered[_block]): the ticket equals search_grid_covered on the
+        render masks the bits came from.  render_mask_bits_host: pinned CPU uint8 [S, ceil(H*W/8)] (NmiContext.pack_mask_bits,
+        or np.packbits(masks.reshape(S, -1) != 0, axis=1, bitorder="little")), render layout.  The rest as for submit_masked."""
+        return self._submit_masked("covered", render_stack_host, render_mask_bits_host, frame_host, frame_mask_host, homographies,
+                                   block, comm)
+
+    def counts(self, ticket, n):
+        """len_w [n = Wn] of a masked ticket or len[w][s] [n = Wn * S, layout [Wn][S]] of a covered ticket that has been waited
+        for -> numpy int32 [n]."""
+        out = np.zeros(int(n), np.int32)
+        self.ctx._check(self._lib.nmi_stream_copy_counts(self._h, int(ticket), out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)),
+                        "nmi_stream_copy_counts")
+        return out
 
     def keep_ratings(self, on=True):
         self.ctx._check(self._lib.nmi_stream_keep_ratings(self._h, int(bool(on))), "nmi_stream_keep_ratings")

@@ -40,6 +40,85 @@ int ensure_mask_work(nmi_ctx *ctx, int Wn, int64_t total)
 
 }  // namespace
 
+// nmi_search_grid_masked's launches without its blocking tail (it also serves masked stream tickets).  counts / tables hold the
+// Wn warps' len_w and term tables already; redo has room for S_local * Wn candidates and redo_state [2] is zero.  out_key:
+// optional device word that receives the packed key; post: the caller polls the mailbox (the blocking call).  Commits
+// enqueue_grid's protocol bookkeeping once the launches are accepted.  S_local * Wn > 0.
+int nmi_internal::enqueue_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
+                                      const uint8_t *warp_masks, int Wn, int w_offset, const int32_t *counts, const float *tables, int32_t *redo,
+                                      uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post)
+{
+    const nmi_params &p = ctx->params;
+    const int64_t total = (int64_t)S_local * Wn;
+    int rc = NMI_OK;
+    nmi::MaskedGridArgs m{};
+    nmi::GridArgs &a = m.g;
+    a.render_stack = render_stack;
+    a.warp_stack = warp_stack;
+    a.S_local = S_local;
+    a.Wn = Wn;
+    a.s_offset = s_offset;
+    a.S_total = S_total;
+    a.w_offset = w_offset;
+    nmi::set_geometry(a, p.width, p.height, render_stack, warp_stack, p.render_bottom_up != 0);
+    a.shift = ctx->shift;
+    a.mode = p.mode;
+    a.table = nullptr;
+    a.plan = nullptr;
+    a.ratings = d_ratings;
+    a.key = ctx->d_keys + ctx->slot;
+    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
+    a.out_key = out_key;
+    a.done = ctx->d_done;
+    post = post && ctx->result_path == 1;
+    a.mailbox = post ? ctx->mailbox : nullptr;
+    a.seq = post ? ctx->seq + 1 : 0;
+    a.hist_variant = ctx->hist_variant;
+    a.phase_mask = 3;
+    m.warp_masks = warp_masks;
+    m.tables = tables;
+    m.counts = counts;
+    m.vec_ok = a.vec_ok && ((uintptr_t)warp_masks % 16) == 0;
+    m.redo = redo;
+    m.redo_n = redo_state;
+    m.redo_done = redo_state + 1;
+    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
+    const int workgroups = (int)(total < cap ? total : cap);
+    // mid-size grids: pixel ranges (nmi_masked_pix_kernel.hip), by nmi_search_grid's rules and controls (choose_pix)
+    const int pix = choose_pix(ctx, a, total, cap);
+    if (pix) {
+        rc = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
+        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
+        if (rc == NMI_OK) rc = ensure_pix_timeouts(ctx);
+        if (rc != NMI_OK) return rc;
+        a.blocks = ctx->d_pix_blocks;
+        a.phase_mask = 3 | (ctx->phase_mask & 512);  // (bit 9: the helpers' hand-off test hook, as for nmi_pix_kernel)
+    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {
+        rc = ensure_order(ctx, S_local, Wn, &a.order);
+        if (rc != NMI_OK) return rc;
+    }
+    // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid -- not the counts and tables before them
+    if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (pix)
+        NMI_HIP_TRY(ctx, nmi::launch_pix_masked(m, pix, pix_owner_share(ctx, pix), p.use_bg != 0, nullptr, ctx->d_pix_timeouts, ctx->stream));
+    else
+        NMI_HIP_TRY(ctx, nmi::launch_grid_masked(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
+    // accepted: commit the protocol state (enqueue_grid's bookkeeping)
+    if (post) ++ctx->seq;
+    ctx->posted = post;
+    ctx->last_slot = ctx->slot;
+    ctx->slot ^= 1;
+    ctx->last_parts = 0;
+    ctx->last_pix = pix;
+    ctx->last_epoch = 0;
+    ctx->last_few = 0;
+    if (ctx->profiling) {
+        NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+        ctx->have_timing = true;
+    }
+    return NMI_OK;
+}
+
 extern "C" {
 
 int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask, const double *h_forward, int32_t Wn,
@@ -64,7 +143,6 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
     if (rc != NMI_OK) return rc;
     if (!warp_masks) return NMI_ERR_INVALID_ARGUMENT;  // never the unmasked search in disguise
     DeviceGuard guard(ctx->device);
-    const nmi_params &p = ctx->params;
     const int64_t total = (int64_t)S * Wn;
     if (Wn > 0) {
         rc = ensure_mask_work(ctx, Wn, total);
@@ -80,70 +158,9 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
         return nmi_key_unpack(0, h_best_index, h_best_score);
     }
 
-    nmi::MaskedGridArgs m{};
-    nmi::GridArgs &a = m.g;
-    a.render_stack = render_stack;
-    a.warp_stack = warp_stack;
-    a.S_local = S;
-    a.Wn = Wn;
-    a.s_offset = 0;
-    a.S_total = S;
-    a.w_offset = 0;
-    nmi::set_geometry(a, p.width, p.height, render_stack, warp_stack, p.render_bottom_up != 0);
-    a.shift = ctx->shift;
-    a.mode = p.mode;
-    a.table = nullptr;
-    a.plan = nullptr;
-    a.ratings = d_ratings;
-    a.key = ctx->d_keys + ctx->slot;
-    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
-    a.done = ctx->d_done;
-    const bool post = ctx->result_path == 1;
-    a.mailbox = post ? ctx->mailbox : nullptr;
-    a.seq = post ? ctx->seq + 1 : 0;
-    a.hist_variant = ctx->hist_variant;
-    a.phase_mask = 3;
-    m.warp_masks = warp_masks;
-    m.tables = ctx->d_mask_tables;
-    m.counts = ctx->d_mask_counts;
-    m.vec_ok = a.vec_ok && ((uintptr_t)warp_masks % 16) == 0;
-    m.redo = ctx->d_mask_redo;
-    m.redo_n = ctx->d_mask_redo_state;
-    m.redo_done = ctx->d_mask_redo_state + 1;
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
-    const int workgroups = (int)(total < cap ? total : cap);
-    // mid-size grids: pixel ranges (nmi_masked_pix_kernel.hip), by nmi_search_grid's rules and controls (choose_pix)
-    const int pix = choose_pix(ctx, a, total, cap);
-    if (pix) {
-        rc = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
-        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
-        if (rc == NMI_OK) rc = ensure_pix_timeouts(ctx);
-        if (rc != NMI_OK) return rc;
-        a.blocks = ctx->d_pix_blocks;
-        a.phase_mask = 3 | (ctx->phase_mask & 512);  // (bit 9: the helpers' hand-off test hook, as for nmi_pix_kernel)
-    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {
-        rc = ensure_order(ctx, S, Wn, &a.order);
-        if (rc != NMI_OK) return rc;
-    }
-    // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid -- not the counts and tables before them
-    if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    if (pix)
-        NMI_HIP_TRY(ctx, nmi::launch_pix_masked(m, pix, pix_owner_share(ctx, pix), p.use_bg != 0, nullptr, ctx->d_pix_timeouts, ctx->stream));
-    else
-        NMI_HIP_TRY(ctx, nmi::launch_grid_masked(m, workgroups, p.use_bg != 0, ctx->hist_variant == 1, ctx->stream));
-    // accepted: commit the protocol state (enqueue_grid's bookkeeping)
-    if (post) ++ctx->seq;
-    ctx->posted = post;
-    ctx->last_slot = ctx->slot;
-    ctx->slot ^= 1;
-    ctx->last_parts = 0;
-    ctx->last_pix = pix;
-    ctx->last_epoch = 0;
-    ctx->last_few = 0;
-    if (ctx->profiling) {
-        NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-        ctx->have_timing = true;
-    }
+    rc = enqueue_grid_masked(ctx, render_stack, S, 0, S, warp_stack, warp_masks, Wn, 0, ctx->d_mask_counts, ctx->d_mask_tables, ctx->d_mask_redo,
+                             ctx->d_mask_redo_state, d_ratings, nullptr, /*post=*/true);
+    if (rc != NMI_OK) return rc;
     unsigned long long key = 0;
     rc = fetch_key(ctx, &key);
     if (rc != NMI_OK) return rc;

@@ -2,6 +2,7 @@
 // double-buffered streaming pipeline (nmi_stream_*).  Declared in include/nmi_hip.h.
 #include "nmi_covered.h"
 #include "nmi_ctx.h"
+#include "nmi_mask_bits.h"
 #include "nmi_masked.h"
 
 using namespace nmi_internal;
@@ -685,6 +686,11 @@ struct nmi_stream {
         int s_offset = 0, S_total = 0, w_offset = 0;  // position of the slot's block in its level
         int warp_buf = 0;            // warp buffer the search read, and that buffer's generation at submission
         uint64_t warp_gen = 0;
+        // masked / covered tickets (allocated on the stream's first such submission, see nmi_stream_submit_masked)
+        int kind = 0;                // kPlain, kMasked, kCovered
+        int64_t n_counts = 0;        // entries of d_counts the ticket wrote: len_w [Wn] (masked), len [Wn][S] (covered)
+        int32_t *d_counts = nullptr;  // [max_Wn * max_S]
+        uint8_t *d_bits = nullptr;   // [max_S][ceil(npix / 8)]: the render-mask bits, uploaded beside the render stack (covered)
     };
     Slot *slots = nullptr;
     uint8_t *d_frame[2] = {nullptr, nullptr};  // frames alternate so an upload never overwrites one still being warped
@@ -696,7 +702,59 @@ struct nmi_stream {
     bool have_warps = false;
     bool keep_ratings = false;
     int64_t next_ticket = 0;
+    // Masks, beside the warp buffers: the frame mask and the warp masks of each buffer's frame, and -- for masked tickets --
+    // len_w and the per-warp term tables, built once per frame submission (a frame-less ticket reuses them).
+    uint8_t *d_fmask[2] = {nullptr, nullptr};     // [H][W]
+    uint8_t *d_wmasks[2] = {nullptr, nullptr};    // [max_Wn][H][W]
+    int32_t *d_wcounts[2] = {nullptr, nullptr};   // [max_Wn]
+    float *d_wtables[2] = {nullptr, nullptr};     // [max_Wn][npix + 1]
+    bool masks_ok[2] = {false, false};            // the buffer's frame was submitted masked or covered: its warp masks exist
+    bool tables_ok[2] = {false, false};           // ... and its len_w / tables have been built
+    // Unpacked render masks of the covered ticket being searched.  ONE buffer for all slots: the unpack and the search that
+    // reads it both run on the context's compute stream, so ticket i + 1's unpack cannot start before ticket i's search ended.
+    uint8_t *d_rmasks = nullptr;                  // [max_S][H][W]
+    int32_t *d_redo = nullptr;                    // [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
+    uint32_t *d_redo_state = nullptr;             // [2], zero between searches
 };
+
+namespace {
+
+enum { kPlain = 0, kMasked = 1, kCovered = 2 };
+
+// Buffers of masked / covered tickets, allocated on the stream's first such submission (a plain-only stream never has them).
+// Each pointer is allocated once; after a failure the next submission allocates what is still missing.
+int stream_alloc_masks(nmi_stream *st, int kind)
+{
+    nmi_ctx *ctx = st->ctx;
+    const size_t npix = (size_t)ctx->npix, cells = (size_t)st->max_S * st->max_Wn;
+    auto alloc = [](void *p, size_t bytes) {
+        void **pp = (void **)p;
+        return *pp ? hipSuccess : hipMalloc(pp, bytes);
+    };
+    for (int b = 0; b < 2; ++b) {
+        NMI_HIP_TRY(ctx, alloc(&st->d_fmask[b], npix));
+        NMI_HIP_TRY(ctx, alloc(&st->d_wmasks[b], npix * st->max_Wn));
+    }
+    for (int i = 0; i < st->depth; ++i) NMI_HIP_TRY(ctx, alloc(&st->slots[i].d_counts, cells * sizeof(int32_t)));
+    NMI_HIP_TRY(ctx, alloc(&st->d_redo, cells * sizeof(int32_t)));
+    if (!st->d_redo_state) {
+        NMI_HIP_TRY(ctx, alloc(&st->d_redo_state, 2 * sizeof(uint32_t)));
+        NMI_HIP_TRY(ctx, hipMemsetAsync(st->d_redo_state, 0, 2 * sizeof(uint32_t), ctx->stream));
+    }
+    if (kind == kMasked) {
+        for (int b = 0; b < 2; ++b) {
+            NMI_HIP_TRY(ctx, alloc(&st->d_wcounts[b], (size_t)st->max_Wn * sizeof(int32_t)));
+            NMI_HIP_TRY(ctx, alloc(&st->d_wtables[b], (size_t)st->max_Wn * (npix + 1) * sizeof(float)));
+        }
+    }
+    if (kind == kCovered) {
+        for (int i = 0; i < st->depth; ++i) NMI_HIP_TRY(ctx, alloc(&st->slots[i].d_bits, nmi::mask_bit_bytes(ctx->npix) * st->max_S));
+        NMI_HIP_TRY(ctx, alloc(&st->d_rmasks, npix * st->max_S));
+    }
+    return NMI_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -714,13 +772,22 @@ int nmi_stream_destroy(nmi_stream *st)
         if (s.h_key) (void)hipHostFree(s.h_key);
         if (s.copied) (void)hipEventDestroy(s.copied);
         if (s.done) (void)hipEventDestroy(s.done);
+        if (s.d_counts) (void)hipFree(s.d_counts);
+        if (s.d_bits) (void)hipFree(s.d_bits);
     }
     delete[] st->slots;
     for (int b = 0; b < 2; ++b) {
         if (st->d_frame[b]) (void)hipFree(st->d_frame[b]);
         if (st->d_warps[b]) (void)hipFree(st->d_warps[b]);
         if (st->warps_free[b]) (void)hipEventDestroy(st->warps_free[b]);
+        if (st->d_fmask[b]) (void)hipFree(st->d_fmask[b]);
+        if (st->d_wmasks[b]) (void)hipFree(st->d_wmasks[b]);
+        if (st->d_wcounts[b]) (void)hipFree(st->d_wcounts[b]);
+        if (st->d_wtables[b]) (void)hipFree(st->d_wtables[b]);
     }
+    if (st->d_rmasks) (void)hipFree(st->d_rmasks);
+    if (st->d_redo) (void)hipFree(st->d_redo);
+    if (st->d_redo_state) (void)hipFree(st->d_redo_state);
     if (st->frame_copied) (void)hipEventDestroy(st->frame_copied);
     if (st->copy) (void)hipStreamDestroy(st->copy);
     delete st;
@@ -776,13 +843,21 @@ int nmi_stream_submit(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, 
     return nmi_stream_submit_block(st, h_render_stack, S, 0, S, h_frame, h_forward, Wn, 0, h_frame ? Wn : (st ? st->cur_Wn : 0), nullptr, ticket);
 }
 
-int nmi_stream_submit_block(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, int32_t s_offset, int32_t S_total,
-                            const uint8_t *h_frame, const double *h_forward, int32_t Wn, int32_t w_offset, int32_t Wn_total,
-                            void *nccl_comm, int64_t *ticket)
+}  // extern "C"
+
+// Every submission form.  kind kPlain is nmi_stream_submit_block as it always was; kMasked / kCovered add the masks and take the
+// masked / covered search (never the split kernel: parts stays 0, so nmi_stream_wait never redoes them).
+static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack, const uint8_t *h_bits, int32_t S, int32_t s_offset,
+                         int32_t S_total, const uint8_t *h_frame, const uint8_t *h_frame_mask, const double *h_forward, int32_t Wn,
+                         int32_t w_offset, int32_t Wn_total, void *nccl_comm, int64_t *ticket)
 {
     if (!st || !ticket || S < 0 || S > st->max_S || (S > 0 && !h_render_stack)) return NMI_ERR_INVALID_ARGUMENT;
     if (h_frame && (!h_forward || Wn <= 0 || Wn > st->max_Wn)) return NMI_ERR_INVALID_ARGUMENT;
     if (!h_frame && !st->have_warps && !(S == 0 && nccl_comm)) return NMI_ERR_INVALID_ARGUMENT;
+    if (h_frame_mask && !h_frame) return NMI_ERR_INVALID_ARGUMENT;                      // a frame mask goes with its frame
+    if (kind == kCovered && S > 0 && !h_bits) return NMI_ERR_INVALID_ARGUMENT;         // never the masked search in disguise
+    // frame-less masked / covered: the most recent frame must have been submitted with masks (a plain one made none)
+    if (kind != kPlain && !h_frame && st->have_warps && !st->masks_ok[st->warp_buf]) return NMI_ERR_INVALID_ARGUMENT;
     const int32_t Wn_block = h_frame ? Wn : st->cur_Wn;
     if (s_offset < 0 || w_offset < 0 || s_offset + S > S_total || w_offset + Wn_block > Wn_total) return NMI_ERR_INVALID_ARGUMENT;
     if ((int64_t)S_total * Wn_total >= 0x7FFFFFFFll) return NMI_ERR_UNSUPPORTED;
@@ -793,23 +868,41 @@ int nmi_stream_submit_block(nmi_stream *st, const uint8_t *h_render_stack, int32
     nmi_stream::Slot &s = st->slots[t % st->depth];
     if (!s.waited) return NMI_ERR_NOT_READY;  // the ticket that used this slot has not been collected yet
     const size_t npix = (size_t)ctx->npix;
+    if (kind != kPlain) {
+        const int rc = stream_alloc_masks(st, kind);
+        if (rc != NMI_OK) return rc;
+    }
 
     // copy stream: render stack of this level into the slot (the slot's previous search finished: it was waited for)
     if (S > 0) NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_renders, h_render_stack, npix * S, hipMemcpyHostToDevice, st->copy));
+    if (kind == kCovered && S > 0)  // its coverage as bits: 1/8 of the render stack's bytes on the wire
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_bits, h_bits, nmi::mask_bit_bytes(ctx->npix) * S, hipMemcpyHostToDevice, st->copy));
     if (h_frame) {
         const int nb = st->have_warps ? st->warp_buf ^ 1 : 0;
         // the buffer being refilled was last read by searches submitted before the previous frame switch
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(st->copy, st->warps_free[nb], 0));
         NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
+        if (h_frame_mask) NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_fmask[nb], h_frame_mask, npix, hipMemcpyHostToDevice, st->copy));
         NMI_HIP_TRY(ctx, hipEventRecord(st->frame_copied, st->copy));
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
         if (st->have_warps) NMI_HIP_TRY(ctx, hipEventRecord(st->warps_free[st->warp_buf], ctx->stream));
-        int rc = nmi_warp_stack(ctx, st->d_frame[nb], h_forward, Wn, st->d_warps[nb]);
+        int rc = kind == kPlain ? nmi_warp_stack(ctx, st->d_frame[nb], h_forward, Wn, st->d_warps[nb])
+                                : nmi_warp_stack_masked(ctx, st->d_frame[nb], h_frame_mask ? st->d_fmask[nb] : nullptr, h_forward, Wn,
+                                                        st->d_warps[nb], st->d_wmasks[nb]);
         if (rc != NMI_OK) return rc;
         st->warp_buf = nb;
         ++st->warp_gen[nb];
         st->cur_Wn = Wn;
         st->have_warps = true;
+        st->masks_ok[nb] = kind != kPlain;
+        st->tables_ok[nb] = false;
+    }
+    const int wb = st->warp_buf;
+    if (kind == kMasked && st->have_warps && !st->tables_ok[wb]) {
+        // len_w and the per-warp term tables of this buffer's warp masks: once per frame (nmi_search_grid_masked's kernels)
+        NMI_HIP_TRY(ctx, nmi::launch_mask_counts(st->d_wmasks[wb], st->cur_Wn, ctx->npix, st->d_wcounts[wb], ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_mask_tables(st->d_wcounts[wb], st->cur_Wn, ctx->npix, st->d_wtables[wb], ctx->stream));
+        st->tables_ok[wb] = true;
     }
     NMI_HIP_TRY(ctx, hipEventRecord(s.copied, st->copy));
 
@@ -819,20 +912,37 @@ int nmi_stream_submit_block(nmi_stream *st, const uint8_t *h_render_stack, int32
         NMI_HIP_TRY(ctx, hipMalloc((void **)&s.d_ratings, (size_t)st->max_S * st->max_Wn * sizeof(float)));
     s.S = S;
     s.Wn = st->cur_Wn;
-    // nmi_stream_wait checks this very launch for a split-kernel timeout (parts, epoch below) and redoes it -- which it cannot do
-    // once the key has gone into a collective, so submissions with a communicator keep to the one-workgroup kernel
-    ctx->allow_unchecked_split = nccl_comm == nullptr;
     s.s_offset = s_offset;
     s.S_total = S_total;
     s.w_offset = w_offset;
-    int rc = enqueue_grid(ctx, s.d_renders, S, s_offset, S_total, st->d_warps[st->warp_buf], st->cur_Wn, st->keep_ratings ? s.d_ratings : nullptr,
-                          s.d_key, false, nullptr, nullptr, nullptr, nullptr, w_offset);
-    ctx->allow_unchecked_split = false;
+    float *ratings = st->keep_ratings ? s.d_ratings : nullptr;
+    int rc = NMI_OK;
+    if (kind == kPlain || (int64_t)S * st->cur_Wn == 0) {
+        // nmi_stream_wait checks this very launch for a split-kernel timeout (parts, epoch below) and redoes it -- which it cannot
+        // do once the key has gone into a collective, so submissions with a communicator keep to the one-workgroup kernel.
+        // (An empty masked / covered block comes here too: nothing is scored, the key is "none".)
+        ctx->allow_unchecked_split = nccl_comm == nullptr && kind == kPlain;
+        rc = enqueue_grid(ctx, s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->cur_Wn, ratings, s.d_key, false, nullptr, nullptr,
+                          nullptr, nullptr, w_offset);
+        ctx->allow_unchecked_split = false;
+    } else if (kind == kMasked) {
+        rc = enqueue_grid_masked(ctx, s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn, w_offset,
+                                 st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+    } else {
+        NMI_HIP_TRY(ctx, nmi::launch_unpack_mask_bits(s.d_bits, S, ctx->npix, st->d_rmasks, ctx->stream));
+        rc = enqueue_grid_covered(ctx, s.d_renders, st->d_rmasks, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn,
+                                  w_offset, s.d_counts, st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+    }
     if (rc != NMI_OK) return rc;
+    s.kind = kind;
+    s.n_counts = kind == kMasked ? st->cur_Wn : kind == kCovered ? (int64_t)S * st->cur_Wn : 0;
+    if (kind == kMasked && s.n_counts > 0)  // len_w into the slot: the buffer's own may be rebuilt by a later frame
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_counts, st->d_wcounts[wb], (size_t)s.n_counts * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                        ctx->stream));
     s.parts = ctx->last_parts;
     s.epoch = ctx->last_epoch;
-    s.warp_buf = st->warp_buf;
-    s.warp_gen = st->warp_gen[st->warp_buf];
+    s.warp_buf = wb;
+    s.warp_gen = st->warp_gen[wb];
     const unsigned long long *result = s.d_key;
     if (nccl_comm) {
         // the level's only exchange: 8-byte MAX all-reduce of the packed keys, issued in submission order on every rank
@@ -847,6 +957,62 @@ int nmi_stream_submit_block(nmi_stream *st, const uint8_t *h_render_stack, int32
     s.failed = false;
     *ticket = t;
     ++st->next_ticket;
+    return NMI_OK;
+}
+
+extern "C" {
+
+int nmi_stream_submit_block(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, int32_t s_offset, int32_t S_total,
+                            const uint8_t *h_frame, const double *h_forward, int32_t Wn, int32_t w_offset, int32_t Wn_total,
+                            void *nccl_comm, int64_t *ticket)
+{
+    return stream_submit(st, kPlain, h_render_stack, nullptr, S, s_offset, S_total, h_frame, nullptr, h_forward, Wn, w_offset, Wn_total,
+                         nccl_comm, ticket);
+}
+
+int nmi_stream_submit_masked(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, const uint8_t *h_frame, const uint8_t *h_frame_mask,
+                             const double *h_forward, int32_t Wn, int64_t *ticket)
+{
+    if (S <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    return stream_submit(st, kMasked, h_render_stack, nullptr, S, 0, S, h_frame, h_frame_mask, h_forward, Wn, 0,
+                         h_frame ? Wn : (st ? st->cur_Wn : 0), nullptr, ticket);
+}
+
+int nmi_stream_submit_masked_block(nmi_stream *st, const uint8_t *h_render_stack, int32_t S_local, int32_t s_offset, int32_t S_total,
+                                   const uint8_t *h_frame, const uint8_t *h_frame_mask, const double *h_forward, int32_t Wn_local,
+                                   int32_t w_offset, int32_t Wn_total, void *nccl_comm, int64_t *ticket)
+{
+    return stream_submit(st, kMasked, h_render_stack, nullptr, S_local, s_offset, S_total, h_frame, h_frame_mask, h_forward, Wn_local,
+                         w_offset, Wn_total, nccl_comm, ticket);
+}
+
+int nmi_stream_submit_covered(nmi_stream *st, const uint8_t *h_render_stack, const uint8_t *h_render_mask_bits, int32_t S,
+                              const uint8_t *h_frame, const uint8_t *h_frame_mask, const double *h_forward, int32_t Wn, int64_t *ticket)
+{
+    if (S <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    return stream_submit(st, kCovered, h_render_stack, h_render_mask_bits, S, 0, S, h_frame, h_frame_mask, h_forward, Wn, 0,
+                         h_frame ? Wn : (st ? st->cur_Wn : 0), nullptr, ticket);
+}
+
+int nmi_stream_submit_covered_block(nmi_stream *st, const uint8_t *h_render_stack, const uint8_t *h_render_mask_bits, int32_t S_local,
+                                    int32_t s_offset, int32_t S_total, const uint8_t *h_frame, const uint8_t *h_frame_mask,
+                                    const double *h_forward, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, void *nccl_comm,
+                                    int64_t *ticket)
+{
+    return stream_submit(st, kCovered, h_render_stack, h_render_mask_bits, S_local, s_offset, S_total, h_frame, h_frame_mask, h_forward,
+                         Wn_local, w_offset, Wn_total, nccl_comm, ticket);
+}
+
+int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, int64_t n)
+{
+    if (!st || (!h_counts && n != 0) || ticket < 0 || ticket >= st->next_ticket) return NMI_ERR_INVALID_ARGUMENT;
+    nmi_stream::Slot &s = st->slots[ticket % st->depth];
+    // valid from nmi_stream_wait(ticket) until the slot is submitted to again; plain tickets have none
+    if (s.ticket != ticket || !s.waited || s.failed || s.kind == kPlain || n != s.n_counts) return NMI_ERR_INVALID_ARGUMENT;
+    if (n == 0) return NMI_OK;
+    nmi_ctx *ctx = st->ctx;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipMemcpy(h_counts, s.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 

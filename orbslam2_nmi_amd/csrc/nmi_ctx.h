@@ -186,6 +186,14 @@ int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes);  // the context's hand-off bl
 int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack, int Wn,
                  float *d_ratings, unsigned long long *out_key, bool post, uint32_t *dbg_joint, uint32_t *dbg_h1, uint32_t *dbg_h2,
                  float *dbg_sums, int w_offset = 0, bool post_score = false);
+// The masked / covered searches' launches without their blocking tails (nmi_capi_masked.cpp, nmi_capi_covered.cpp): serve
+// nmi_search_grid_masked / _covered and the masked / covered stream tickets.  S_local * Wn > 0; see the definitions.
+int enqueue_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
+                        const uint8_t *warp_masks, int Wn, int w_offset, const int32_t *counts, const float *tables, int32_t *redo,
+                        uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
+int enqueue_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int S_local, int s_offset, int S_total,
+                         const uint8_t *warp_stack, const uint8_t *warp_masks, int Wn, int w_offset, int32_t *counts, int32_t *redo,
+                         uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
 int wait_word(nmi_ctx *ctx, const volatile unsigned long long *word, unsigned long long mask, unsigned long long want,
               unsigned long long *out);
 int stage_floats(nmi_ctx *ctx, StagingRing &ring, const float *h_src, size_t n, float **d_out);
