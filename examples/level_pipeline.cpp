@@ -366,6 +366,16 @@ int main(int argc, char **argv)
         CHECK_NMI(nmi_level_set_coverage(p.level, 1, d_hood));  // every replay: coverage + warp masks, covered search
     else if (masked)
         CHECK_NMI(nmi_level_set_masks(p.level, 1, d_hood));  // every replay: warp masks, counts, masked search
+    if (read_dir) {
+        // the lens of the settings file (Camera.k1 k2 p1 p2 k3): a distorted camera's frame is undistorted by every replay
+        float dist[5];
+        CHECK_NMI(nmi_config_load_distortion((std::string(read_dir) + "/settings.yaml").c_str(), dist));
+        if (dist[0] != 0.0f || dist[1] != 0.0f || dist[2] != 0.0f || dist[3] != 0.0f || dist[4] != 0.0f) {
+            const double Kc[9] = {cfg.fx, 0, cfg.cx, 0, cfg.fy, cfg.cy, 0, 0, 1};
+            CHECK_NMI(nmi_level_set_distortion(p.level, Kc, dist));
+            printf("distorted lens: k1 %g k2 %g p1 %g p2 %g k3 %g\n", dist[0], dist[1], dist[2], dist[3], dist[4]);
+        }
+    }
 
     // 3^6 grid with the steps of ETH_small.yaml:83-88
     NmiSearchKernel initial(3, 3, 3, 3, 3, 3, 0.2f, 0.2f, 0.5f, 0.02f, 0.02f, 0.05f);

@@ -37,7 +37,8 @@ extern "C" {
                                  nmi_level_set_masks, nmi_level_copy_masks, after nmi_level_set_coverage,
                                  nmi_level_copy_coverage, and after nmi_pack_mask_bits, nmi_stream_submit_masked,
                                  nmi_stream_submit_masked_block, nmi_stream_submit_covered, nmi_stream_submit_covered_block,
-                                 nmi_stream_copy_counts */
+                                 nmi_stream_copy_counts, and after nmi_undistort_frame,
+                                 nmi_level_set_distortion, nmi_stream_set_distortion */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -262,6 +263,35 @@ int nmi_last_cover_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n);
 int nmi_pack_mask_bits(nmi_ctx *ctx, const uint8_t *d_masks /*[n][H][W]*/, int32_t n, uint8_t *d_bits /*[n][ceil(H*W/8)]*/);
 
 /*
+ * Lens distortion (new): the camera frame resampled onto the pinhole camera K the renders and the warps use.  The reference's
+ * tracker reads the radial-tangential coefficients Camera.k1 k2 p1 p2 [k3] into mDistCoef (src/Tracking.cc:133-144) but its
+ * NMI path scores the raw mImGray (src/Tracking.cc:1871); on a rectified camera (every Camera.k* of the reference's settings
+ * files is 0) the two agree.  nmi_undistort_frame maps the raw frame d_raw [H][W] (and optionally its mask d_raw_mask,
+ * nonzero = usable) to the undistorted frame d_frame [H][W] and its validity mask d_frame_mask; the new camera matrix is K,
+ * as in cv::undistort's default.  One resampling per frame; the warp paths then run unchanged on the result.
+ *   Host: fx, fy, cx, cy = fl32(K[0], K[4], K[2], K[5]); ifx = fl32(1.0 / K[0]), ify = fl32(1.0 / K[4]) in double; the
+ *   five coefficients as given (fp32).  Per output pixel (u, v), fp32 in this order:
+ *     x = (u - cx) * ifx;  y = (v - cy) * ify;  x2 = x*x;  y2 = y*y;  xy = x*y;  r2 = x2 + y2
+ *     rad = r2 * (k1 + r2 * (k2 + r2 * k3))
+ *     dx = ((x*rad) + ((2*p1)*xy)) + (p2*(r2 + 2*x2));  dy = ((y*rad) + (p1*(r2 + 2*y2))) + ((2*p2)*xy)
+ *     xs = u + fx*dx;  ys = v + fy*dy
+ *   (u_d = fx x_d + cx written as a displacement: all-zero coefficients give xs = u, ys = v exactly, i.e. a byte copy and an
+ *   all-ones mask).  The value at (xs, ys) is the warp stack's (reach test -2 < xs < W+1, -2 < ys < H+1, bilinear taps with
+ *   a border of 0, round to nearest even, clamp to [0, 255]); the mask byte is 1 exactly where nmi_warp_stack_masked's rule
+ *   holds at (xs, ys) -- the reach test, every tap with nonzero weight inside the frame and, given d_raw_mask, nonzero in
+ *   it -- else 0.  Where the polynomial folds over (strong coefficients far from the centre) the result is whatever the
+ *   formula gives.  Parity with cv::undistort unpinned (OpenCV is not part of the reference tree, as for the warp).
+ * Enqueued on the context's stream.  NMI_ERR_INVALID_ARGUMENT, before anything is enqueued: a NULL ctx, K, dist, d_raw or
+ * d_frame; K not [fx 0 cx; 0 fy cy; 0 0 1] with finite fx, fy > 0 and finite cx, cy; a non-finite coefficient;
+ * d_raw == d_frame, or an output mask that aliases an input or the frame.  d_raw_mask and d_frame_mask may be NULL (no mask
+ * written).
+ * Captured levels: nmi_level_set_distortion.  Streams: nmi_stream_set_distortion.  Settings: nmi_config_parse_distortion
+ * (include/nmi_host.h).
+ */
+int nmi_undistort_frame(nmi_ctx *ctx, const double K[9], const float dist[5] /* k1 k2 p1 p2 k3 */, const uint8_t *d_raw,
+                        const uint8_t *d_raw_mask /* nullable */, uint8_t *d_frame, uint8_t *d_frame_mask /* nullable: no mask written */);
+
+/*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
  * (Thirdparty/Localization/rendering.hpp:530-630, nmi_prop_RENDER 4, shaders/ShadingWithColor.*) for S camera
  * translations of one pose -- no OpenGL.  nmi_render_mvp builds Projection * glm::lookAt for one view exactly as
@@ -423,6 +453,21 @@ int nmi_level_set_coverage(nmi_level *lv, int32_t enabled, const uint8_t *d_fram
 /* Host copies of the latest replay's render masks [S][H][W], warp masks [Wn][H][W] and len [Wn][S] (any pointer may be
  * NULL).  Blocking.  NMI_ERR_INVALID_ARGUMENT on a level without coverage. */
 int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_warp_masks, int32_t *h_counts);
+/*
+ * Distorted lenses.  nmi_level_set_distortion(lv, K, dist) turns undistortion on for a level made by any of the four
+ * nmi_level_create* calls: d_frame is then the RAW frame, and so is a d_frame_mask given to nmi_level_set_masks /
+ * nmi_level_set_coverage.  Every replay runs one nmi_undistort_frame node after the prep node, into a frame (and, when the
+ * level is masked or covered, a mask) the level owns; the warps, their masks and the search read those.  Ratings, winner
+ * index and score bits equal the standalone chain's: nmi_undistort_frame(raw, NULL) -> nmi_warp_stack -> render ->
+ * nmi_search_grid (plain); nmi_undistort_frame(raw, raw_mask) -> nmi_warp_stack_masked(ud, ud_mask) ->
+ * nmi_search_grid_masked (masked), or the covered chain; nmi_level_copy_outputs' warps are those of the undistorted frame.
+ * The call captures the graph again and waits for a replay in flight, as nmi_level_set_masks does; set and clear it in any
+ * order with the masks and coverage, which keep it.  dist = NULL or five zero coefficients turn it off: the graph is again
+ * the never-distorted level's, and the level frees its buffers (H x W bytes, and H x W more while masked or covered).  Empty blocks
+ * take the setting and have no node.  NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, K or dist as for
+ * nmi_undistort_frame (K is not read when dist is NULL).
+ */
+int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[5] /* NULL = off */);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -498,6 +543,16 @@ int nmi_stream_submit_covered_block(nmi_stream *st, const uint8_t *h_render_stac
                                     const double *h_forward, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, void *nccl_comm,
                                     int64_t *ticket);
 int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, int64_t n);
+/*
+ * Distorted lenses on a stream: after nmi_stream_set_distortion(st, K, dist) every frame submission, of every kind (plain,
+ * masked, covered and their _block forms), takes h_frame and h_frame_mask as RAW: the frame is undistorted on the compute
+ * stream before its warps (nmi_undistort_frame, into a pair of frames -- and, for masked and covered frames, masks -- beside
+ * the uploaded ones), and a ticket equals the chain nmi_level_set_distortion names.  Tickets submitted before the call are
+ * not affected; frame-less tickets reuse the most recent warps as always.  dist = NULL or five zero coefficients turn it off:
+ * later tickets are those of a stream that never had it.  NMI_ERR_INVALID_ARGUMENT as for nmi_level_set_distortion (the
+ * stream left as it was).  Memory: 2 x H*W bytes on the first distorted frame, 2 x H*W more on the first masked or covered one.
+ */
+int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5] /* NULL = off */);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

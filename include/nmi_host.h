@@ -120,6 +120,12 @@ typedef struct nmi_config {
 } nmi_config;
 int nmi_config_parse(const char *text, size_t len, nmi_config *out);
 int nmi_config_load(const char *yaml_path, nmi_config *out);
+/* The lens model of the same file (src/Tracking.cc:133-144): dist = fl32 of Camera.k1, k2, p1, p2, k3; a key the file lacks
+ * (k3 in most of them) reads as 0, as cv::FileNode's conversion gives it.  nmi_config keeps its layout: these are calls of their
+ * own.  Input of nmi_undistort_frame / nmi_level_set_distortion / nmi_stream_set_distortion (include/nmi_hip.h) with K from
+ * Camera.fx..cy.  Returns 0, or <0: -1 NULL argument, -2 syntax, -5 file not readable. */
+int nmi_config_parse_distortion(const char *text, size_t len, float dist[5]);
+int nmi_config_load_distortion(const char *yaml_path, float dist[5]);
 
 /*
  * Map files (the paths of nmi_config.render_object / render_texture / render_cloud / render_offset), read with the grammar and

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "nmi_level_set_coverage", "nmi_level_copy_coverage",
     "nmi_pack_mask_bits", "nmi_stream_submit_masked", "nmi_stream_submit_masked_block", "nmi_stream_submit_covered",
     "nmi_stream_submit_covered_block", "nmi_stream_copy_counts",
+    "nmi_undistort_frame", "nmi_level_set_distortion", "nmi_stream_set_distortion",
 )
 
 
@@ -126,6 +127,9 @@ def load_library(build_if_missing=False):
     lib.nmi_stream_submit_covered.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(C.c_double), i32, i64p]
     lib.nmi_stream_submit_covered_block.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double), i32, i32, i32, vp, i64p]
     lib.nmi_stream_copy_counts.argtypes = [vp, C.c_int64, C.POINTER(i32), C.c_int64]
+    lib.nmi_undistort_frame.argtypes = [vp, C.POINTER(C.c_double), f32p, vp, vp, vp, vp]
+    lib.nmi_level_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
+    lib.nmi_stream_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -188,6 +192,21 @@ def render_mvp(rp, cam_pos, cam_look_at, cam_up, translation):
     if rc != NMI_OK:
         raise NmiError(rc, "nmi_render_mvp")
     return np.array(out, np.float32)
+
+
+def _lens(K, dist):
+    """(K [3,3] or [9] float64, dist [5] float32 or None) -> numpy copies and the pointers the C ABI takes (dist None -> NULL)."""
+    if K is None and dist is None:
+        return None, None, None, None
+    k = np.ascontiguousarray(K, np.float64).reshape(-1)
+    if k.size != 9:
+        raise ValueError("K must have 9 entries")
+    if dist is None:
+        return k, None, k.ctypes.data_as(C.POINTER(C.c_double)), None
+    d = np.ascontiguousarray(dist, np.float32).reshape(-1)
+    if d.size != 5:
+        raise ValueError("dist must be k1 k2 p1 p2 k3 (5 entries; pad k3 = 0)")
+    return k, d, k.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def _dev_mask(t, ndim, what):
@@ -449,6 +468,38 @@ class NmiContext:
         if sync:
             self.synchronize()
         return out, out_masks
+
+    def undistort_frame(self, raw, K, dist, raw_mask=None, out=None, out_mask=None, sync=True):
+        """nmi_undistort_frame: the raw camera frame [H,W] u8 (device) resampled onto the pinhole camera K ([3,3] float64) for the
+        lens coefficients dist = (k1, k2, p1, p2, k3) -> (frame [H,W] u8, mask [H,W] u8 or None).  raw_mask: optional device
+        [H,W] uint8 / bool, nonzero = usable raw pixel.  out_mask=False: no mask is written (None is returned in its place);
+        otherwise a new uint8 tensor when None.  Enqueued on the context's stream."""
+        import torch
+        r = self._img(raw, "raw")
+        rm = None
+        if raw_mask is not None:
+            rm = _dev_mask(raw_mask, 2, "raw_mask")
+            if tuple(rm.shape) != (self.height, self.width):
+                raise ValueError(f"raw_mask is {tuple(rm.shape)}, context is {(self.height, self.width)}")
+        k, d, kp, dp = _lens(K, dist)
+        if d is None:
+            raise ValueError("undistort_frame needs the five coefficients")
+        if out is None:
+            out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        o = self._img(out, "out")
+        om = None
+        if out_mask is None:
+            out_mask = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        if out_mask is not False:
+            om = _dev_mask(out_mask, 2, "out_mask")
+            if tuple(om.shape) != (self.height, self.width):
+                raise ValueError(f"out_mask is {tuple(om.shape)}, context is {(self.height, self.width)}")
+        self._order_after_torch()
+        self._check(self._lib.nmi_undistort_frame(self._h, kp, dp, r.data_ptr(), rm.data_ptr() if rm is not None else None, o.data_ptr(),
+                                                  om.data_ptr() if om is not None else None), "nmi_undistort_frame")
+        if sync:
+            self.synchronize()
+        return out, om
 
     def _mask_stack(self, t, what):
         t = _dev_mask(t, 3, what)
@@ -842,6 +893,14 @@ class NmiLevel:
                         "nmi_level_copy_coverage")
         return r, m, n
 
+    def set_distortion(self, K, dist):
+        """Distorted lens (nmi_level_set_distortion): the level's frame, and a frame mask given to set_masks / set_coverage, are
+        then the RAW camera frame; every replay undistorts them for K ([3,3] float64) and dist = (k1, k2, p1, p2, k3) before the
+        warps.  dist=None or all zeros turns it off."""
+        k, d, kp, dp = _lens(K, dist)
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_distortion(self._h, kp, dp), "nmi_level_set_distortion")
+
     def close(self):
         if self._h and self._h.value:
             self._lib.nmi_level_destroy(self._h)
@@ -954,6 +1013,13 @@ class NmiStream:
         self.ctx._check(self._lib.nmi_stream_copy_counts(self._h, int(ticket), out.ctypes.data_as(C.POINTER(C.c_int32)), int(n)),
                         "nmi_stream_copy_counts")
         return out
+
+    def set_distortion(self, K, dist):
+        """Distorted lens (nmi_stream_set_distortion): frames (and frame masks) of later submissions, of every kind, are RAW and
+        undistorted on the device for K ([3,3] float64) and dist = (k1, k2, p1, p2, k3) before their warps.  dist=None or all
+        zeros turns it off."""
+        k, d, kp, dp = _lens(K, dist)
+        self.ctx._check(self._lib.nmi_stream_set_distortion(self._h, kp, dp), "nmi_stream_set_distortion")
 
     def keep_ratings(self, on=True):
         self.ctx._check(self._lib.nmi_stream_keep_ratings(self._h, int(bool(on))), "nmi_stream_keep_ratings")

@@ -4,6 +4,7 @@
 #include "nmi_ctx.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
+#include "nmi_undistort.h"
 
 using namespace nmi_internal;
 
@@ -72,6 +73,11 @@ struct nmi_level {
     bool covered = false;
     uint8_t *d_rmasks = nullptr;                // [S][H][W], render layout
     int32_t *d_cover_counts = nullptr;          // [Wn][S]
+    // Lens distortion (nmi_level_set_distortion): d_frame (and d_frame_mask) are the raw frame; every replay undistorts it into
+    // d_ud (and, masked or covered, its mask into d_ud_mask), which the warps and their masks read instead.
+    bool distorted = false;
+    nmi::UndistortParams ud{};
+    uint8_t *d_ud = nullptr, *d_ud_mask = nullptr;  // [H][W] each, allocated by level_capture when first needed
 };
 
 extern "C" {
@@ -84,7 +90,7 @@ int nmi_level_destroy(nmi_level *lv)
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
     void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks,
-                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts};
+                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts, lv->d_ud, lv->d_ud_mask};
     for (void *q : dev)
         if (q) (void)hipFree(q);
     void *host[] = {lv->h_mvps, lv->h_coeffs, lv->h_key};
@@ -111,13 +117,19 @@ static int level_capture(nmi_level *lv)
     const nmi_texture *tex = lv->tex;
     const float *d_xyz = lv->d_xyz, *d_attr = lv->d_attr, *d_red = lv->d_attr;
     const int64_t n_points = lv->n_points;
-    const uint8_t *d_frame = lv->d_frame;
     float *hd_mvps = lv->hd_mvps, *hd_coeffs = lv->hd_coeffs;
     hipError_t e = hipSuccess;
     auto ok = [&](hipError_t r) {
         if (e == hipSuccess) e = r;
         return r == hipSuccess;
     };
+    // Distorted: the chain reads the level's undistorted frame (16-byte aligned: the fused front kernels stay eligible) and, masked
+    // or covered, its mask.
+    const bool distorted = lv->distorted, want_ud_mask = distorted && (lv->masked || lv->covered);
+    if (distorted && !lv->d_ud) ok(hipMalloc((void **)&lv->d_ud, (size_t)ctx->npix));
+    if (want_ud_mask && !lv->d_ud_mask && e == hipSuccess) ok(hipMalloc((void **)&lv->d_ud_mask, (size_t)ctx->npix));
+    const uint8_t *d_frame = distorted ? lv->d_ud : lv->d_frame;
+    const uint8_t *d_frame_mask = distorted ? (want_ud_mask ? lv->d_ud_mask : nullptr) : lv->d_frame_mask;
     nmi::GridArgs a = lv->args;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
@@ -179,6 +191,9 @@ static int level_capture(nmi_level *lv)
                                   (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
+        if (distorted)
+            ok(nmi::launch_undistort(lv->ud, lv->d_frame, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud, want_ud_mask ? lv->d_ud_mask : nullptr,
+                                     p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
@@ -189,11 +204,11 @@ static int level_capture(nmi_level *lv)
             ok(hipStreamWaitEvent(lv->side, lv->ev_fork, 0));
             if (!fused) ok(nmi::launch_warp(d_frame, lv->d_coeffs, lv->d_warps, p.width, p.height, Wn, lv->side));
             if (masked) {
-                ok(nmi::launch_warp_masks(lv->d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
+                ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
                 ok(nmi::launch_level_mask_counts(lv->d_masks, Wn, ctx->npix, lv->d_counts, d_prev, d_changed, lv->side));
                 ok(nmi::launch_level_mask_tables(lv->d_counts, d_changed, Wn, ctx->npix, lv->d_tables, lv->side));
             }
-            if (covered) ok(nmi::launch_warp_masks(lv->d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
+            if (covered) ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
         if (tex)
@@ -233,6 +248,10 @@ static int level_capture(nmi_level *lv)
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
     lv->graph = graph;
     lv->exec = exec;
+    if (!want_ud_mask && lv->d_ud_mask) {  // masks / coverage off (or distortion off): no graph reads the undistorted mask now
+        (void)hipFree(lv->d_ud_mask);
+        lv->d_ud_mask = nullptr;
+    }
     return NMI_OK;
 }
 
@@ -662,6 +681,40 @@ int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_w
     return NMI_OK;
 }
 
+int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[5])
+{
+    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
+    nmi::UndistortParams ud{};
+    bool identity = true;
+    if (dist && undistort_params(K, dist, &ud, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = dist && !identity;  // five zero coefficients: the never-distorted graph
+    nmi_ctx *ctx = lv->ctx;
+    ctx->detail.clear();
+    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph
+        lv->distorted = on;
+        lv->ud = ud;
+        return NMI_OK;
+    }
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
+    const bool was = lv->distorted;
+    const nmi::UndistortParams was_ud = lv->ud;
+    lv->distorted = on;
+    lv->ud = ud;
+    const int rc = level_capture(lv);
+    if (rc != NMI_OK) {
+        lv->distorted = was;
+        lv->ud = was_ud;
+        return rc;
+    }
+    if (!on) {
+        if (lv->d_ud) (void)hipFree(lv->d_ud);
+        if (lv->d_ud_mask) (void)hipFree(lv->d_ud_mask);
+        lv->d_ud = lv->d_ud_mask = nullptr;
+    }
+    return NMI_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Streaming pipeline (config 5): double-buffered render stacks, copy stream beside the compute stream.
 // ---------------------------------------------------------------------------------------------------------
@@ -715,6 +768,12 @@ struct nmi_stream {
     uint8_t *d_rmasks = nullptr;                  // [max_S][H][W]
     int32_t *d_redo = nullptr;                    // [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
     uint32_t *d_redo_state = nullptr;             // [2], zero between searches
+    // Lens distortion (nmi_stream_set_distortion): frames submitted while it is on are undistorted on the compute stream into
+    // d_ud[b] (masked / covered: their masks into d_ud_mask[b]), and the warps are made from those.
+    bool distorted = false;
+    nmi::UndistortParams ud{};
+    uint8_t *d_ud[2] = {nullptr, nullptr};        // [H][W], allocated on the first distorted frame
+    uint8_t *d_ud_mask[2] = {nullptr, nullptr};   // [H][W], allocated on the first distorted masked / covered frame
 };
 
 namespace {
@@ -784,6 +843,8 @@ int nmi_stream_destroy(nmi_stream *st)
         if (st->d_wmasks[b]) (void)hipFree(st->d_wmasks[b]);
         if (st->d_wcounts[b]) (void)hipFree(st->d_wcounts[b]);
         if (st->d_wtables[b]) (void)hipFree(st->d_wtables[b]);
+        if (st->d_ud[b]) (void)hipFree(st->d_ud[b]);
+        if (st->d_ud_mask[b]) (void)hipFree(st->d_ud_mask[b]);
     }
     if (st->d_rmasks) (void)hipFree(st->d_rmasks);
     if (st->d_redo) (void)hipFree(st->d_redo);
@@ -872,6 +933,11 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const int rc = stream_alloc_masks(st, kind);
         if (rc != NMI_OK) return rc;
     }
+    const bool undistort = h_frame && st->distorted;
+    for (int b = 0; undistort && b < 2; ++b) {
+        if (!st->d_ud[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud[b], npix));
+        if (kind != kPlain && !st->d_ud_mask[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud_mask[b], npix));
+    }
 
     // copy stream: render stack of this level into the slot (the slot's previous search finished: it was waited for)
     if (S > 0) NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_renders, h_render_stack, npix * S, hipMemcpyHostToDevice, st->copy));
@@ -886,9 +952,16 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         NMI_HIP_TRY(ctx, hipEventRecord(st->frame_copied, st->copy));
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
         if (st->have_warps) NMI_HIP_TRY(ctx, hipEventRecord(st->warps_free[st->warp_buf], ctx->stream));
-        int rc = kind == kPlain ? nmi_warp_stack(ctx, st->d_frame[nb], h_forward, Wn, st->d_warps[nb])
-                                : nmi_warp_stack_masked(ctx, st->d_frame[nb], h_frame_mask ? st->d_fmask[nb] : nullptr, h_forward, Wn,
-                                                        st->d_warps[nb], st->d_wmasks[nb]);
+        const uint8_t *frame = st->d_frame[nb], *frame_mask = h_frame_mask ? st->d_fmask[nb] : nullptr;
+        if (undistort) {  // the raw frame (and mask) -> the undistorted ones, on the compute stream: the warps read them next
+            uint8_t *ud_mask = kind != kPlain ? st->d_ud_mask[nb] : nullptr;
+            NMI_HIP_TRY(ctx, nmi::launch_undistort(st->ud, frame, frame_mask, st->d_ud[nb], ud_mask, ctx->params.width, ctx->params.height,
+                                                   ctx->stream));
+            frame = st->d_ud[nb];
+            frame_mask = ud_mask;
+        }
+        int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, st->d_warps[nb])
+                                : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, st->d_warps[nb], st->d_wmasks[nb]);
         if (rc != NMI_OK) return rc;
         st->warp_buf = nb;
         ++st->warp_gen[nb];
@@ -1013,6 +1086,18 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
     nmi_ctx *ctx = st->ctx;
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipMemcpy(h_counts, s.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NMI_OK;
+}
+
+int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5])
+{
+    if (!st) return NMI_ERR_INVALID_ARGUMENT;
+    nmi::UndistortParams ud{};
+    bool identity = true;
+    if (dist && undistort_params(K, dist, &ud, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    // later frame submissions take the map by value at their launch: tickets already submitted are not affected
+    st->distorted = dist && !identity;
+    st->ud = ud;
     return NMI_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "nmi_masked.h"
+#include "nmi_warp_device.h"
 
 namespace nmi {
 
@@ -27,15 +28,7 @@ __device__ __forceinline__ uint8_t warp_pixel_valid(const uint8_t *__restrict__ 
     const float coeff = 1.0f / (c[6] * fx + c[7] * fy + c[8]);
     const float xs = coeff * (c[0] * fx + c[1] * fy + c[2]);
     const float ys = coeff * (c[3] * fx + c[4] * fy + c[5]);
-    if (!(xs > -2.0f && xs < (float)(width + 1) && ys > -2.0f && ys < (float)(height + 1))) return 0;  // also NaN
-    const int x1 = (int)floorf(xs), y1 = (int)floorf(ys);
-    const int x2 = x1 + (xs != (float)x1 ? 1 : 0), y2 = y1 + (ys != (float)y1 ? 1 : 0);  // last tap with nonzero weight
-    if (x1 < 0 || y1 < 0 || x2 > width - 1 || y2 > height - 1) return 0;
-    if (frame_mask) {
-        const uint8_t *r1 = frame_mask + (size_t)y1 * width, *r2 = frame_mask + (size_t)y2 * width;
-        if (r1[x1] == 0 || r1[x2] == 0 || r2[x1] == 0 || r2[x2] == 0) return 0;
-    }
-    return 1;
+    return warp_source_valid(frame_mask, width, height, xs, ys);
 }
 
 }  // namespace

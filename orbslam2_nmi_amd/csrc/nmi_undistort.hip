@@ -1,0 +1,79 @@
+// nmi_undistort.hip -- lens undistortion of a camera frame (nmi_undistort_frame, include/nmi_hip.h): the radial-tangential
+// model of OpenCV / ORB-SLAM2 (Tracking.cc:133-144 reads k1 k2 p1 p2 [k3]), resampled once per frame onto the pinhole camera
+// K the renders use (the new camera matrix is K, as in cv::undistort's default).  Per output pixel (u, v), fp32, in this
+// order (the file is built with -ffp-contract=off, so tests/helpers/undistort_np.py reproduces it byte for byte):
+//   x = (u - cx) * ifx;  y = (v - cy) * ify;  x2 = x x;  y2 = y y;  xy = x y;  r2 = x2 + y2
+//   rad = r2 (k1 + r2 (k2 + r2 k3))
+//   dx = ((x rad) + ((2 p1) xy)) + (p2 (r2 + 2 x2));  dy = ((y rad) + (p1 (r2 + 2 y2))) + ((2 p2) xy)
+//   xs = u + fx dx;  ys = v + fy dy
+// -- the textbook u_d = fx x_d + cx written as a displacement, so that zero coefficients give xs = u, ys = v exactly: the
+// frame is copied and every mask byte is 1.  The value at (xs, ys) is warp_sample_global's (nmi_warp_device.h), the mask
+// warp_source_valid's: the rules of the warp stack and its masks.  No special case where the polynomial folds over.
+// Taps are gathered from global memory (a frame is well under 1 MB and stays in L2); no LDS staging.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "nmi_undistort.h"
+#include "nmi_warp_device.h"
+
+namespace nmi {
+
+namespace {
+
+constexpr int kUndistortQuads = 64;  // lanes per block row: 4 x 64 = 256 pixels; 4 block rows
+
+__device__ __forceinline__ void undistort_source(const UndistortParams &p, float u, float v, float *xs, float *ys)
+{
+    const float x = (u - p.cx) * p.ifx, y = (v - p.cy) * p.ify;
+    const float x2 = x * x, y2 = y * y, xy = x * y, r2 = x2 + y2;
+    const float rad = r2 * (p.k1 + r2 * (p.k2 + r2 * p.k3));
+    const float dx = ((x * rad) + ((2.0f * p.p1) * xy)) + (p.p2 * (r2 + 2.0f * x2));
+    const float dy = ((y * rad) + (p.p1 * (r2 + 2.0f * y2))) + ((2.0f * p.p2) * xy);
+    *xs = u + p.fx * dx;
+    *ys = v + p.fy * dy;
+}
+
+}  // namespace
+
+// A lane makes 4 adjacent pixels of one row (and their mask bytes): one dword store each where every row starts on a 4-byte
+// boundary (aligned), byte stores otherwise.
+__global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, const uint8_t *__restrict__ raw, const uint8_t *__restrict__ raw_mask,
+                                                            uint8_t *__restrict__ frame, uint8_t *__restrict__ frame_mask, int width, int height,
+                                                            int aligned)
+{
+    const int q = blockIdx.x * kUndistortQuads + (int)threadIdx.x;
+    const int y = blockIdx.y * 4 + (int)threadIdx.y;
+    const int x0 = q * 4;
+    if (x0 >= width || y >= height) return;
+    const int n = min(4, width - x0);
+    uint32_t packed = 0, mpacked = 0;
+    const float v = (float)y;
+    for (int k = 0; k < n; ++k) {
+        float xs, ys;
+        undistort_source(p, (float)(x0 + k), v, &xs, &ys);
+        packed |= warp_sample_global(raw, width, height, xs, ys) << (8 * k);
+        if (frame_mask) mpacked |= (uint32_t)warp_source_valid(raw_mask, width, height, xs, ys) << (8 * k);
+    }
+    const size_t o = (size_t)y * width + x0;
+    if (aligned) {  // (width % 4 == 0: the quad lies wholly inside the row)
+        *reinterpret_cast<uint32_t *>(frame + o) = packed;
+        if (frame_mask) *reinterpret_cast<uint32_t *>(frame_mask + o) = mpacked;
+    } else {
+        for (int k = 0; k < n; ++k) frame[o + k] = (uint8_t)(packed >> (8 * k));
+        if (frame_mask)
+            for (int k = 0; k < n; ++k) frame_mask[o + k] = (uint8_t)(mpacked >> (8 * k));
+    }
+}
+
+hipError_t launch_undistort(const UndistortParams &p, const uint8_t *raw, const uint8_t *raw_mask, uint8_t *frame, uint8_t *frame_mask,
+                            int width, int height, hipStream_t stream)
+{
+    const int quads = (width + 3) / 4;
+    const int aligned = (width % 4) == 0 && ((uintptr_t)frame % 4) == 0 && ((uintptr_t)frame_mask % 4) == 0;
+    hipLaunchKernelGGL(nmi_undistort_kernel, dim3((quads + kUndistortQuads - 1) / kUndistortQuads, (height + 3) / 4), dim3(kUndistortQuads, 4), 0,
+                       stream, p, raw, raw_mask, frame, frame_mask, width, height, aligned);
+    return hipGetLastError();
+}
+
+}  // namespace nmi

@@ -29,15 +29,10 @@ __device__ __forceinline__ float warp_tap(const uint8_t *__restrict__ src, int w
     return (x >= 0 && x < w && y >= 0 && y < h) ? (float)src[y * w + x] : 0.0f;  // BORDER_CONSTANT, value 0
 }
 
-// One output pixel with its taps taken from global memory (the arithmetic of nmi_warp_kernel, shared with the fallback of
-// the staged kernel below).
-__device__ __forceinline__ uint32_t warp_pixel_global(const uint8_t *__restrict__ frame, const float *__restrict__ c, int width, int height,
-                                                      int x, int y)
+// The value at source coordinate (xs, ys) with its taps taken from global memory: the reach test, the bilinear taps with a
+// border of 0, saturate_cast<uchar>.  Shared by warp_pixel_global and the undistortion kernel (nmi_undistort.hip).
+__device__ __forceinline__ uint32_t warp_sample_global(const uint8_t *__restrict__ frame, int width, int height, float xs, float ys)
 {
-    const float fx = (float)x, fy = (float)y;
-    const float coeff = 1.0f / (c[6] * fx + c[7] * fy + c[8]);
-    const float xs = coeff * (c[0] * fx + c[1] * fy + c[2]);
-    const float ys = coeff * (c[3] * fx + c[4] * fy + c[5]);
     float acc = 0.0f;
     if (xs > -2.0f && xs < (float)(width + 1) && ys > -2.0f && ys < (float)(height + 1)) {
         const int x1 = (int)floorf(xs), y1 = (int)floorf(ys);
@@ -51,6 +46,34 @@ __device__ __forceinline__ uint32_t warp_pixel_global(const uint8_t *__restrict_
     }
     const float r = rintf(acc);
     return r <= 0.0f ? 0u : (r >= 255.0f ? 255u : (uint32_t)r);
+}
+
+// One output pixel with its taps taken from global memory (the arithmetic of nmi_warp_kernel, shared with the fallback of
+// the staged kernel below).
+__device__ __forceinline__ uint32_t warp_pixel_global(const uint8_t *__restrict__ frame, const float *__restrict__ c, int width, int height,
+                                                      int x, int y)
+{
+    const float fx = (float)x, fy = (float)y;
+    const float coeff = 1.0f / (c[6] * fx + c[7] * fy + c[8]);
+    const float xs = coeff * (c[0] * fx + c[1] * fy + c[2]);
+    const float ys = coeff * (c[3] * fx + c[4] * fy + c[5]);
+    return warp_sample_global(frame, width, height, xs, ys);
+}
+
+// The validity rule of the warp masks (nmi_masked_producer.hip) at source coordinate (xs, ys): 1 iff the reach test passes,
+// every bilinear tap with nonzero weight lies inside the frame (tap x1 + 1 has weight xs - x1, zero exactly when xs is an
+// integer) and, given a frame mask, every such tap is nonzero in it.  Shared with the undistortion kernel.
+__device__ __forceinline__ uint8_t warp_source_valid(const uint8_t *__restrict__ frame_mask, int width, int height, float xs, float ys)
+{
+    if (!(xs > -2.0f && xs < (float)(width + 1) && ys > -2.0f && ys < (float)(height + 1))) return 0;  // also NaN
+    const int x1 = (int)floorf(xs), y1 = (int)floorf(ys);
+    const int x2 = x1 + (xs != (float)x1 ? 1 : 0), y2 = y1 + (ys != (float)y1 ? 1 : 0);  // last tap with nonzero weight
+    if (x1 < 0 || y1 < 0 || x2 > width - 1 || y2 > height - 1) return 0;
+    if (frame_mask) {
+        const uint8_t *r1 = frame_mask + (size_t)y1 * width, *r2 = frame_mask + (size_t)y2 * width;
+        if (r1[x1] == 0 || r1[x2] == 0 || r2[x1] == 0 || r2[x2] == 0) return 0;
+    }
+    return 1;
 }
 
 // The same warp with the source patch of each block staged in LDS.  nmi_warp_kernel spends its time on scattered tap

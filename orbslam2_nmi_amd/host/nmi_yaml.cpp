@@ -191,17 +191,46 @@ int nmi_config_parse(const char *text, size_t len, nmi_config *out)
     return 0;
 }
 
-int nmi_config_load(const char *yaml_path, nmi_config *out)
+static int read_file(const char *path, std::string &text)
 {
-    if (!yaml_path || !out) return -1;
-    FILE *f = fopen(yaml_path, "rb");
+    FILE *f = fopen(path, "rb");
     if (!f) return -5;
-    std::string text;
     char buf[4096];
     size_t n;
     while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
     fclose(f);
+    return 0;
+}
+
+int nmi_config_load(const char *yaml_path, nmi_config *out)
+{
+    if (!yaml_path || !out) return -1;
+    std::string text;
+    if (read_file(yaml_path, text) != 0) return -5;
     return nmi_config_parse(text.data(), text.size(), out);
+}
+
+// Tracking.cc:133-144: DistCoef = (Camera.k1, k2, p1, p2) and k3 when it is nonzero.  A key the file lacks reads as 0 there
+// (cv::FileNode's conversion of an empty node), and here.
+int nmi_config_parse_distortion(const char *text, size_t len, float dist[5])
+{
+    if (!text || !dist) return -1;
+    std::map<std::string, Node> m;
+    if (!parse(text, len, m)) return -2;
+    static const char *keys[5] = {"Camera.k1", "Camera.k2", "Camera.p1", "Camera.p2", "Camera.k3"};
+    for (int i = 0; i < 5; ++i) {
+        double v = 0.0;
+        dist[i] = number(m, keys[i], v) ? (float)v : 0.0f;
+    }
+    return 0;
+}
+
+int nmi_config_load_distortion(const char *yaml_path, float dist[5])
+{
+    if (!yaml_path || !dist) return -1;
+    std::string text;
+    if (read_file(yaml_path, text) != 0) return -5;
+    return nmi_config_parse_distortion(text.data(), text.size(), dist);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ EXPORTED_SYMBOLS = (
     "nmi_sk_format", "nmi_sk_linear_index", "nmi_sk_set_best_from_index", "nmi_find_max_elements",
     "nmi_calculate_translation", "nmi_calculate_relocalization", "nmi_mat4_inverse", "nmi_relocalize_with_strategy",
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
+    "nmi_config_parse_distortion", "nmi_config_load_distortion",
 )
 
 
@@ -99,6 +100,8 @@ def _lib():
                                                      C.c_void_p, C.POINTER(StrategyOutput)]
         lib.nmi_config_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Config)]
         lib.nmi_config_load.argtypes = [C.c_char_p, C.POINTER(Config)]
+        lib.nmi_config_parse_distortion.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_float)]
+        lib.nmi_config_load_distortion.argtypes = [C.c_char_p, C.POINTER(C.c_float)]
         fpp, i64p = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)
         lib.nmi_map_load_obj.argtypes = [C.c_char_p, fpp, fpp, i64p]
         lib.nmi_map_load_xyz.argtypes = [C.c_char_p, C.c_char_p, fpp, fpp, fpp, i64p]
@@ -195,6 +198,24 @@ def config_load(path):
     if rc != 0:
         raise ValueError(f"nmi_config_load({path}) failed: {rc}")
     return cfg
+
+
+def config_parse_distortion(text):
+    """Camera.k1 k2 p1 p2 k3 of a settings file (Tracking.cc:133-144; a missing key reads as 0) -> float32 [5]; raises on errors."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    out = np.zeros(5, np.float32)
+    rc = _lib().nmi_config_parse_distortion(raw, len(raw), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError(f"nmi_config_parse_distortion failed: {rc}")
+    return out
+
+
+def config_load_distortion(path):
+    out = np.zeros(5, np.float32)
+    rc = _lib().nmi_config_load_distortion(str(path).encode(), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError(f"nmi_config_load_distortion({path}) failed: {rc}")
+    return out
 
 
 def _take(ptr, shape, dtype):
