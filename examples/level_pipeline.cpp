@@ -159,13 +159,17 @@ static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, co
 
 int main(int argc, char **argv)
 {
-    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered] [--write-files DIR | --files DIR]
+    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered] [--color rgb|bgr|rgba|bgra]
+    //                       [--write-files DIR | --files DIR]
     //   --mesh: nmi_prop_RENDER 1, the reference's default render mode: the same surface as NX x NY quads = 2 NX NY textured
     //           triangles, default 300x200 = 120,000;  --density: points per pixel of a view along each axis (cloud; default 0.9)
     //   --masked: the frame's bottom sixth is a "hood" (a flat grey band over the scene); a frame mask excludes it and the levels
     //           are masked ones (nmi_level_set_masks: border masks of the rotated warps + the hood mask)
     //   --covered: the map has a hole where the frame does not (part of every view is left uncovered); the levels are covered
     //           ones (nmi_level_set_coverage: the renders' coverage masks + the warps' border masks, + the hood mask with --masked)
+    //   --color FMT: the camera frame is a colour image in that format (a smooth chroma pattern over its grey values, so that the
+    //           channel order matters), in rows padded to 256 bytes; the levels read it raw and turn it grey on the device
+    //           (nmi_level_set_frame_format).  With --files the order (RGB or BGR) is the settings file's Camera.RGB.
     //   --write-files DIR: write the map and a settings file into DIR and stop (no GPU needed)
     //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names
     //           (nmi_config_load, nmi_map_load_obj / _bmp / _xyz) instead of building them in memory
@@ -173,6 +177,7 @@ int main(int argc, char **argv)
     float density = 0.9f;
     const char *write_dir = nullptr, *read_dir = nullptr;
     bool masked = false, covered = false;
+    int color_bpp = 0, color_rgb = 0;  // --color: 3 or 4 bytes per pixel, RGB (1) or BGR (0) order
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mesh")) {
             mesh_nx = 300, mesh_ny = 200;
@@ -181,6 +186,14 @@ int main(int argc, char **argv)
             masked = true;
         } else if (!strcmp(argv[i], "--covered")) {
             covered = true;
+        } else if (!strcmp(argv[i], "--color") && i + 1 < argc) {
+            const char *c = argv[++i];
+            color_bpp = !strcmp(c, "rgb") || !strcmp(c, "bgr") ? 3 : !strcmp(c, "rgba") || !strcmp(c, "bgra") ? 4 : 0;
+            color_rgb = c[0] == 'r';
+            if (!color_bpp) {
+                fprintf(stderr, "--color takes rgb, bgr, rgba or bgra\n");
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--density") && i + 1 < argc) {
             density = (float)atof(argv[++i]);
         } else if (!strcmp(argv[i], "--write-files") && i + 1 < argc) {
@@ -285,7 +298,9 @@ int main(int argc, char **argv)
     if (mesh) CHECK_NMI(nmi_texture_create(ctx, rgb.data(), tw, th, &tex));
     int64_t n_prims = mesh ? (int64_t)(xyz.size() / 9) : (int64_t)red.size();
     float *d_xyz = nullptr, *d_red = nullptr;
-    uint8_t *d_frame = nullptr, *d_tmp = nullptr, *d_hood = nullptr;
+    uint8_t *d_frame = nullptr, *d_tmp = nullptr, *d_hood = nullptr, *d_color = nullptr;
+    int32_t color_format = NMI_FRAME_GRAY;
+    int64_t color_pitch = 0;
     CHECK_HIP(hipMalloc((void **)&d_xyz, xyz.size() * sizeof(float)));
     CHECK_HIP(hipMalloc((void **)&d_red, red.size() * sizeof(float)));
     CHECK_HIP(hipMalloc((void **)&d_frame, (size_t)W * H));
@@ -337,6 +352,30 @@ int main(int argc, char **argv)
             printf("masked levels: rows %d..%d of the frame are a hood, excluded by the frame mask\n", hood, H - 1);
         }
         CHECK_HIP(hipMemcpy(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice));
+        if (color_bpp) {
+            // The camera's colour frame: R and B swing +-50 around the grey value (slowly across and down the frame), G makes up the
+            // rest, so that the rule of nmi_gray_frame gives about the grey frame back -- and a wrong channel order does not.
+            if (read_dir) CHECK_NMI(nmi_config_load_color_order((std::string(read_dir) + "/settings.yaml").c_str(), &color_rgb));
+            color_format = color_bpp == 3 ? (color_rgb ? NMI_FRAME_RGB : NMI_FRAME_BGR) : (color_rgb ? NMI_FRAME_RGBA : NMI_FRAME_BGRA);
+            color_pitch = ((int64_t)W * color_bpp + 255) / 256 * 256;  // a driver's padded rows
+            std::vector<uint8_t> col((size_t)H * color_pitch, 0);
+            const int ri = color_rgb ? 0 : 2;
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    const double g = frame[(size_t)y * W + x];
+                    const double r = std::min(255.0, std::max(0.0, std::round(g + 50.0 * std::sin(6.2832 * 1.5 * x / W))));
+                    const double b = std::min(255.0, std::max(0.0, std::round(g - 50.0 * std::sin(6.2832 * 1.2 * y / H + 1.0))));
+                    const double gg = std::min(255.0, std::max(0.0, std::round((g * 16384.0 - 4899.0 * r - 1868.0 * b) / 9617.0)));
+                    uint8_t *px = &col[(size_t)y * color_pitch + (size_t)x * color_bpp];
+                    px[ri] = (uint8_t)r, px[1] = (uint8_t)gg, px[2 - ri] = (uint8_t)b;
+                    if (color_bpp == 4) px[3] = 255;
+                }
+            CHECK_HIP(hipMalloc((void **)&d_color, col.size()));
+            CHECK_HIP(hipMemcpy(d_color, col.data(), col.size(), hipMemcpyHostToDevice));
+            static const char *names[] = {"GRAY", "BGR", "RGB", "BGRA", "RGBA"};
+            printf("colour frame: %s, %d x %d in rows of %lld bytes, turned grey on the device by every replay\n", names[color_format], W, H,
+                   (long long)color_pitch);
+        }
     }
     if (covered) {
         // The frame saw the whole surface; the map the levels render has a hole: the points / triangles whose (first) vertex
@@ -358,10 +397,12 @@ int main(int argc, char **argv)
         CHECK_HIP(hipMemcpy(d_xyz, xyz.data(), kept * per * sizeof(float), hipMemcpyHostToDevice));
         CHECK_HIP(hipMemcpy(d_red, red.data(), kept * per_attr * sizeof(float), hipMemcpyHostToDevice));
     }
+    const uint8_t *d_camera = d_color ? d_color : d_frame;  // what the levels read: the colour frame, raw, when there is one
     if (mesh)
-        CHECK_NMI(nmi_level_create_mesh(ctx, d_xyz, d_red, n_prims, tex, d_frame, 27, 27, &p.level));
+        CHECK_NMI(nmi_level_create_mesh(ctx, d_xyz, d_red, n_prims, tex, d_camera, 27, 27, &p.level));
     else
-        CHECK_NMI(nmi_level_create(ctx, d_xyz, d_red, n_prims, d_frame, 27, 27, p.rp.point_size, &p.level));
+        CHECK_NMI(nmi_level_create(ctx, d_xyz, d_red, n_prims, d_camera, 27, 27, p.rp.point_size, &p.level));
+    if (d_color) CHECK_NMI(nmi_level_set_frame_format(p.level, color_format, color_pitch));  // every replay: colour -> grey node
     if (covered)
         CHECK_NMI(nmi_level_set_coverage(p.level, 1, d_hood));  // every replay: coverage + warp masks, covered search
     else if (masked)
@@ -434,6 +475,7 @@ int main(int argc, char **argv)
     (void)hipFree(d_frame);
     (void)hipFree(d_tmp);
     if (d_hood) (void)hipFree(d_hood);
+    if (d_color) (void)hipFree(d_color);
     nmi_destroy(ctx);
     printf("%s\n", ok ? "PIPELINE OK" : "PIPELINE FAILED");
     return ok ? 0 : 1;

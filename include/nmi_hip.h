@@ -11,6 +11,8 @@
  * Data conventions:
  *   image           uint8 [height][width], contiguous, row stride = width
  *                   (cv::cuda::createContinuous CV_8UC1, Thirdparty/Localization/image.cpp:67).
+ *                   The camera frame alone may also come in colour or with a row stride: nmi_gray_frame,
+ *                   nmi_level_set_frame_format, nmi_stream_set_frame_format (NMI_FRAME_*).
  *   render          same shape; stored bottom-up when nmi_params.render_bottom_up = 1, which is how
  *                   the reference samples the GL texture (NMI.cu:82).
  *   render_stack    uint8 [S][height][width],  s = (sZ*nSy + sY)*nSx + sX
@@ -38,7 +40,8 @@ extern "C" {
                                  nmi_level_copy_coverage, and after nmi_pack_mask_bits, nmi_stream_submit_masked,
                                  nmi_stream_submit_masked_block, nmi_stream_submit_covered, nmi_stream_submit_covered_block,
                                  nmi_stream_copy_counts, and after nmi_undistort_frame,
-                                 nmi_level_set_distortion, nmi_stream_set_distortion */
+                                 nmi_level_set_distortion, nmi_stream_set_distortion, and after nmi_gray_frame,
+                                 nmi_level_set_frame_format, nmi_stream_set_frame_format */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -292,6 +295,31 @@ int nmi_undistort_frame(nmi_ctx *ctx, const double K[9], const float dist[5] /* 
                         const uint8_t *d_raw_mask /* nullable */, uint8_t *d_frame, uint8_t *d_frame_mask /* nullable: no mask written */);
 
 /*
+ * Colour and pitched camera frames (new).  The reference's tracker turns each camera frame into the grey mImGray its NMI path
+ * scores with cv::cvtColor, RGB or BGR by Camera.RGB, 3 or 4 channels (src/Tracking.cc:179-183, 316-341).  A frame in one of
+ * these formats is H rows of pitch bytes, row y at src + y * pitch; pitch = 0 means dense, W * bytes per pixel:
+ *   NMI_FRAME_GRAY  1 byte per pixel (with a pitch: the rows are copied)
+ *   NMI_FRAME_BGR, NMI_FRAME_RGB    3 bytes per pixel in that order
+ *   NMI_FRAME_BGRA, NMI_FRAME_RGBA  4 bytes per pixel, the alpha byte ignored
+ * Camera.RGB = 0 is BGR(A), 1 is RGB(A), as Tracking.cc chooses (nmi_config_parse_color_order, include/nmi_host.h).  The grey
+ * value is OpenCV's 8-bit fixed-point rule for COLOR_{RGB,BGR,RGBA,BGRA}2GRAY, in integers:
+ *   gray = (4899 R + 9617 G + 1868 B + 8192) >> 14
+ * The coefficients sum to 2^14, so R = G = B = g gives g exactly.  Parity with any particular OpenCV build is unpinned (OpenCV is
+ * not part of the reference tree, as for the warp and the undistortion).
+ * nmi_gray_frame writes the dense grey frame d_gray [H][W] of d_src; H and W are the context's.  Enqueued on the context's
+ * stream.  NMI_ERR_INVALID_ARGUMENT, before anything is enqueued: a NULL pointer, an unknown format, pitch < 0 or
+ * 0 < pitch < W * bytes per pixel, d_gray overlapping the source's bytes (rows 0 .. H-1 of W * bytes per pixel each, and the
+ * bytes between them).
+ * Captured levels: nmi_level_set_frame_format.  Streams: nmi_stream_set_frame_format.
+ */
+#define NMI_FRAME_GRAY 0
+#define NMI_FRAME_BGR 1
+#define NMI_FRAME_RGB 2
+#define NMI_FRAME_BGRA 3
+#define NMI_FRAME_RGBA 4
+int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, uint8_t *d_gray /* [H][W] */);
+
+/*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
  * (Thirdparty/Localization/rendering.hpp:530-630, nmi_prop_RENDER 4, shaders/ShadingWithColor.*) for S camera
  * translations of one pose -- no OpenGL.  nmi_render_mvp builds Projection * glm::lookAt for one view exactly as
@@ -468,6 +496,19 @@ int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_w
  * nmi_undistort_frame (K is not read when dist is NULL).
  */
 int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[5] /* NULL = off */);
+/*
+ * Colour and pitched frames.  nmi_level_set_frame_format(lv, format, pitch) makes a level of any of the four nmi_level_create*
+ * forms (and its RCCL runs) read d_frame -- d_frame alone; a frame mask stays dense uint8 [H][W] in raw coordinates -- in place
+ * on every replay as H rows of pitch bytes in format (pitch 0: dense).  The replay gains one node after the prep node, which
+ * writes a grey frame the level owns (H x W bytes, 16-byte aligned: the fused front kernels stay eligible); with distortion on
+ * it is the single node that converts and undistorts at once, with the bytes of the chain.  Ratings, winner index, score bits,
+ * warps, masks and coverage equal the standalone chain's: nmi_gray_frame -> [nmi_undistort_frame] -> the level's chain on the
+ * grey frame.  The call captures the graph again and waits for a replay in flight, as nmi_level_set_distortion does; set it in
+ * any order with masks, coverage and distortion, which keep it.  (NMI_FRAME_GRAY, 0) or (NMI_FRAME_GRAY, W) turns it off: the
+ * graph is again the never-formatted level's, and the level frees its grey frame.  Empty blocks take the setting and have no
+ * node.  NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, format or pitch as for nmi_gray_frame.
+ */
+int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -553,6 +594,17 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
  * stream left as it was).  Memory: 2 x H*W bytes on the first distorted frame, 2 x H*W more on the first masked or covered one.
  */
 int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5] /* NULL = off */);
+/*
+ * Colour and pitched frames on a stream: after nmi_stream_set_frame_format(st, format, pitch) every frame submission, of every
+ * kind (plain, masked, covered and their _block forms), reads h_frame as H rows of pitch bytes in format (pitch 0: dense).  The
+ * frame crosses to the device with hipMemcpy2DAsync into a dense colour slot (a pair: frames alternate) and is converted on the
+ * compute stream before its warps -- in one node with the undistortion when that is on -- and a ticket equals a grey ticket on
+ * nmi_gray_frame's frame.  Frame masks (h_frame_mask) stay dense [H][W].  Tickets submitted before the call are not affected;
+ * frame-less tickets reuse the most recent warps as always.  (NMI_FRAME_GRAY, 0) or (NMI_FRAME_GRAY, W) turns it off.
+ * NMI_ERR_INVALID_ARGUMENT as for nmi_level_set_frame_format (the stream left as it was).  Memory: 2 x H*W*bytes per pixel on the
+ * first formatted frame, and 2 x H*W for the grey frames unless undistortion already holds them.
+ */
+int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

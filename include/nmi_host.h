@@ -126,6 +126,12 @@ int nmi_config_load(const char *yaml_path, nmi_config *out);
  * Camera.fx..cy.  Returns 0, or <0: -1 NULL argument, -2 syntax, -5 file not readable. */
 int nmi_config_parse_distortion(const char *text, size_t len, float dist[5]);
 int nmi_config_load_distortion(const char *yaml_path, float dist[5]);
+/* The channel order of the same file's camera frames (src/Tracking.cc:179-183): *rgb = Camera.RGB as an int, 1 for RGB(A) and 0 for
+ * BGR(A) -- NMI_FRAME_RGB / NMI_FRAME_BGR (or their 4-channel forms) of nmi_gray_frame, nmi_level_set_frame_format and
+ * nmi_stream_set_frame_format (include/nmi_hip.h).  A missing key reads as 0, as cv::FileNode's int conversion gives it to
+ * Tracking.cc.  nmi_config keeps its layout.  Returns as the distortion pair does. */
+int nmi_config_parse_color_order(const char *text, size_t len, int32_t *rgb);
+int nmi_config_load_color_order(const char *yaml_path, int32_t *rgb);
 
 /*
  * Map files (the paths of nmi_config.render_object / render_texture / render_cloud / render_offset), read with the grammar and

@@ -20,6 +20,14 @@ ERR_UNSUPPORTED = -2
 ERR_NO_DEVICE = -3
 ERR_NOT_READY = -4
 
+# Camera frame formats (include/nmi_hip.h, nmi_gray_frame): bytes per pixel 1, 3, 3, 4, 4; Camera.RGB 0 -> BGR(A), 1 -> RGB(A).
+FRAME_GRAY = 0
+FRAME_BGR = 1
+FRAME_RGB = 2
+FRAME_BGRA = 3
+FRAME_RGBA = 4
+FRAME_BYTES_PER_PIXEL = {FRAME_GRAY: 1, FRAME_BGR: 3, FRAME_RGB: 3, FRAME_BGRA: 4, FRAME_RGBA: 4}
+
 # Every symbol include/nmi_hip.h declares; tests check that the library exports all of them.
 EXPORTED_SYMBOLS = (
     "nmi_params_default", "nmi_create", "nmi_destroy", "nmi_set_stream", "nmi_synchronize", "nmi_eval_pair", "nmi_eval_pairs", "nmi_eval_pair_debug",
@@ -35,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "nmi_pack_mask_bits", "nmi_stream_submit_masked", "nmi_stream_submit_masked_block", "nmi_stream_submit_covered",
     "nmi_stream_submit_covered_block", "nmi_stream_copy_counts",
     "nmi_undistort_frame", "nmi_level_set_distortion", "nmi_stream_set_distortion",
+    "nmi_gray_frame", "nmi_level_set_frame_format", "nmi_stream_set_frame_format",
 )
 
 
@@ -130,6 +139,9 @@ def load_library(build_if_missing=False):
     lib.nmi_undistort_frame.argtypes = [vp, C.POINTER(C.c_double), f32p, vp, vp, vp, vp]
     lib.nmi_level_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
     lib.nmi_stream_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
+    lib.nmi_gray_frame.argtypes = [vp, vp, i32, C.c_int64, vp]
+    lib.nmi_level_set_frame_format.argtypes = [vp, i32, C.c_int64]
+    lib.nmi_stream_set_frame_format.argtypes = [vp, i32, C.c_int64]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -500,6 +512,29 @@ class NmiContext:
         if sync:
             self.synchronize()
         return out, om
+
+    def gray_frame(self, src, fmt, pitch=0, out=None, sync=True):
+        """nmi_gray_frame: the camera frame src (device uint8 tensor holding H rows of `pitch` bytes in format fmt, FRAME_*; pitch 0
+        = dense, W * bytes per pixel) -> its dense grey frame [H,W] u8 (a new tensor when out is None).  src may be any uint8 tensor
+        (a view whose first element is the frame's first byte) with at least (H - 1) * pitch + W * bytes per pixel bytes from there
+        on.  Enqueued on the context's stream."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        bpp = FRAME_BYTES_PER_PIXEL.get(int(fmt))
+        if bpp is not None and int(pitch) >= 0:
+            need = (self.height - 1) * (int(pitch) or self.width * bpp) + self.width * bpp
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        if out is None:
+            out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        o = self._img(out, "out")
+        self._order_after_torch()
+        self._check(self._lib.nmi_gray_frame(self._h, src.data_ptr(), int(fmt), int(pitch), o.data_ptr()), "nmi_gray_frame")
+        if sync:
+            self.synchronize()
+        return out
 
     def _mask_stack(self, t, what):
         t = _dev_mask(t, 3, what)
@@ -901,6 +936,13 @@ class NmiLevel:
         self.ctx._order_after_torch()
         self.ctx._check(self._lib.nmi_level_set_distortion(self._h, kp, dp), "nmi_level_set_distortion")
 
+    def set_frame_format(self, fmt, pitch=0):
+        """Colour or pitched frame (nmi_level_set_frame_format): every replay reads the level's frame in place as H rows of `pitch`
+        bytes (0: dense) in format fmt (FRAME_*) and converts it to grey on the device (undistorting it in the same node when
+        set_distortion is on).  Frame masks stay dense [H,W].  (FRAME_GRAY, 0) or (FRAME_GRAY, W) turns it off."""
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_level_set_frame_format")
+
     def close(self):
         if self._h and self._h.value:
             self._lib.nmi_level_destroy(self._h)
@@ -934,7 +976,8 @@ class NmiStream:
         fp, mp, wn, m = None, None, 0, None
         if frame_host is not None:
             m = np.ascontiguousarray(homographies, np.float64).reshape(-1, 9)
-            fp, mp, wn = frame_host.data_ptr(), m.ctypes.data_as(C.POINTER(C.c_double)), m.shape[0]
+            fp = self._frame_ptr(frame_host) if hasattr(self, "_frame_bytes") else frame_host.data_ptr()
+            mp, wn = m.ctypes.data_as(C.POINTER(C.c_double)), m.shape[0]
         t = C.c_int64(-1)
         if block is None and comm is None:
             self.ctx._check(self._lib.nmi_stream_submit(self._h, rs.data_ptr(), rs.shape[0], fp, mp, wn, C.byref(t)),
@@ -968,7 +1011,7 @@ class NmiStream:
         fp, fmp, mp, wn, m = None, None, None, 0, None
         if frame_host is not None:
             m = np.ascontiguousarray(homographies, np.float64).reshape(-1, 9)
-            fp, mp, wn = self._host_u8(frame_host, "frame_host", npix), m.ctypes.data_as(C.POINTER(C.c_double)), m.shape[0]
+            fp, mp, wn = self._frame_ptr(frame_host), m.ctypes.data_as(C.POINTER(C.c_double)), m.shape[0]
         if frame_mask_host is not None:
             if frame_host is None:
                 raise ValueError("frame_mask_host goes with a frame_host")
@@ -1020,6 +1063,24 @@ class NmiStream:
         zeros turns it off."""
         k, d, kp, dp = _lens(K, dist)
         self.ctx._check(self._lib.nmi_stream_set_distortion(self._h, kp, dp), "nmi_stream_set_distortion")
+
+    def set_frame_format(self, fmt, pitch=0):
+        """Colour or pitched host frames (nmi_stream_set_frame_format): frames of later submissions, of every kind, are H rows of
+        `pitch` bytes (0: dense) in format fmt (FRAME_*), converted to grey on the device before their warps.  Frame masks stay
+        dense [H,W].  (FRAME_GRAY, 0) or (FRAME_GRAY, W) turns it off."""
+        self.ctx._check(self._lib.nmi_stream_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_stream_set_frame_format")
+        bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
+        w, h = self.ctx.width, self.ctx.height
+        self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
+
+    def _frame_ptr(self, frame_host):
+        """A host frame's pointer, its size checked against the frame format (dense grey: exactly H x W bytes)."""
+        need = getattr(self, "_frame_bytes", self.ctx.width * self.ctx.height)
+        if need == self.ctx.width * self.ctx.height:
+            return self._host_u8(frame_host, "frame_host", need)
+        if frame_host.is_cuda or str(frame_host.dtype) != "torch.uint8" or not frame_host.is_contiguous() or frame_host.numel() < need:
+            raise TypeError(f"frame_host must be a contiguous CPU uint8 tensor of at least {need} bytes (pinned for overlap)")
+        return frame_host.data_ptr()
 
     def keep_ratings(self, on=True):
         self.ctx._check(self._lib.nmi_stream_keep_ratings(self._h, int(bool(on))), "nmi_stream_keep_ratings")

@@ -1,0 +1,50 @@
+// nmi_capi_color.cpp -- nmi_gray_frame (include/nmi_hip.h) and the host side of the frame formats the captured levels and streams
+// share (nmi_capi_pipeline.cpp: nmi_level_set_frame_format, nmi_stream_set_frame_format).  Kernels: nmi_color.hip, and the colour
+// instantiation of the undistortion kernel in nmi_undistort.hip.
+#include "nmi_color.h"
+#include "nmi_ctx.h"
+
+using namespace nmi_internal;
+
+int nmi_internal::frame_bytes_per_pixel(int32_t format)
+{
+    switch (format) {
+    case NMI_FRAME_GRAY: return 1;
+    case NMI_FRAME_BGR:
+    case NMI_FRAME_RGB: return 3;
+    case NMI_FRAME_BGRA:
+    case NMI_FRAME_RGBA: return 4;
+    default: return 0;
+    }
+}
+
+int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, int64_t *row_bytes, bool *identity)
+{
+    const int bpp = frame_bytes_per_pixel(format);
+    if (bpp == 0 || pitch < 0 || width <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t dense = (int64_t)width * bpp;
+    if (pitch != 0 && pitch < dense) return NMI_ERR_INVALID_ARGUMENT;
+    if (row_bytes) *row_bytes = pitch ? pitch : dense;
+    if (identity) *identity = format == NMI_FRAME_GRAY && (pitch == 0 || pitch == dense);
+    return NMI_OK;
+}
+
+extern "C" {
+
+int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch, uint8_t *d_gray)
+{
+    if (!ctx || !d_src || !d_gray) return NMI_ERR_INVALID_ARGUMENT;
+    const int W = ctx->params.width, H = ctx->params.height;
+    int64_t rb = 0;
+    if (frame_format_check(format, pitch, W, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    // the source's bytes run from d_src to the end of its last row's pixels; the grey frame's H x W bytes may not meet them
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + (int64_t)W * frame_bytes_per_pixel(format));
+    const uintptr_t g0 = (uintptr_t)d_gray, g1 = g0 + (uintptr_t)ctx->npix;
+    if (g0 < s1 && s0 < g1) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
+    return NMI_OK;
+}
+
+}  // extern "C"

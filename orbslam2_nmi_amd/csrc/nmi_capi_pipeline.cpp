@@ -1,6 +1,7 @@
 // nmi_capi_pipeline.cpp -- C ABI of the composed forms: one search level as a captured HIP graph (nmi_level_*) and the
 // double-buffered streaming pipeline (nmi_stream_*).  Declared in include/nmi_hip.h.
 #include "nmi_covered.h"
+#include "nmi_color.h"
 #include "nmi_ctx.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
@@ -78,6 +79,11 @@ struct nmi_level {
     bool distorted = false;
     nmi::UndistortParams ud{};
     uint8_t *d_ud = nullptr, *d_ud_mask = nullptr;  // [H][W] each, allocated by level_capture when first needed
+    // Frame format (nmi_level_set_frame_format): d_frame is H rows of frame_pitch bytes in frame_format; every replay converts it
+    // into d_ud (the level's grey frame; undistorted too when distorted, in the same node).
+    bool colored = false;
+    int32_t frame_format = NMI_FRAME_GRAY;
+    int64_t frame_pitch = 0;                    // row bytes (never 0 while colored)
 };
 
 extern "C" {
@@ -123,12 +129,13 @@ static int level_capture(nmi_level *lv)
         if (e == hipSuccess) e = r;
         return r == hipSuccess;
     };
-    // Distorted: the chain reads the level's undistorted frame (16-byte aligned: the fused front kernels stay eligible) and, masked
-    // or covered, its mask.
+    // Distorted or coloured: the chain reads the level's own grey (undistorted) frame (16-byte aligned: the fused front kernels
+    // stay eligible) and, distorted and masked or covered, its mask.  A frame mask is dense [H][W] in every format.
     const bool distorted = lv->distorted, want_ud_mask = distorted && (lv->masked || lv->covered);
-    if (distorted && !lv->d_ud) ok(hipMalloc((void **)&lv->d_ud, (size_t)ctx->npix));
+    const bool colored = lv->colored, own_frame = distorted || colored;
+    if (own_frame && !lv->d_ud) ok(hipMalloc((void **)&lv->d_ud, (size_t)ctx->npix));
     if (want_ud_mask && !lv->d_ud_mask && e == hipSuccess) ok(hipMalloc((void **)&lv->d_ud_mask, (size_t)ctx->npix));
-    const uint8_t *d_frame = distorted ? lv->d_ud : lv->d_frame;
+    const uint8_t *d_frame = own_frame ? lv->d_ud : lv->d_frame;
     const uint8_t *d_frame_mask = distorted ? (want_ud_mask ? lv->d_ud_mask : nullptr) : lv->d_frame_mask;
     nmi::GridArgs a = lv->args;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
@@ -191,9 +198,14 @@ static int level_capture(nmi_level *lv)
                                   (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
-        if (distorted)
+        if (distorted && colored)  // one node: each tap converted to grey, then the undistortion's arithmetic
+            ok(nmi::launch_undistort_color(lv->ud, lv->d_frame, lv->frame_format, lv->frame_pitch, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud,
+                                           want_ud_mask ? lv->d_ud_mask : nullptr, p.width, p.height, st));
+        else if (distorted)
             ok(nmi::launch_undistort(lv->ud, lv->d_frame, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud, want_ud_mask ? lv->d_ud_mask : nullptr,
                                      p.width, p.height, st));
+        else if (colored)
+            ok(nmi::launch_gray(lv->d_frame, lv->frame_format, lv->frame_pitch, lv->d_ud, p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
@@ -708,9 +720,49 @@ int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[
         return rc;
     }
     if (!on) {
-        if (lv->d_ud) (void)hipFree(lv->d_ud);
+        if (lv->d_ud && !lv->colored) {  // (a coloured level still converts into it)
+            (void)hipFree(lv->d_ud);
+            lv->d_ud = nullptr;
+        }
         if (lv->d_ud_mask) (void)hipFree(lv->d_ud_mask);
-        lv->d_ud = lv->d_ud_mask = nullptr;
+        lv->d_ud_mask = nullptr;
+    }
+    return NMI_OK;
+}
+
+int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch)
+{
+    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
+    nmi_ctx *ctx = lv->ctx;
+    int64_t row_bytes = 0;
+    bool identity = true;
+    if (frame_format_check(format, pitch, ctx->params.width, &row_bytes, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = !identity;  // dense grey: the never-formatted graph
+    ctx->detail.clear();
+    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph
+        lv->colored = on;
+        lv->frame_format = on ? format : NMI_FRAME_GRAY;
+        lv->frame_pitch = on ? row_bytes : 0;
+        return NMI_OK;
+    }
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
+    const bool was = lv->colored;
+    const int32_t was_format = lv->frame_format;
+    const int64_t was_pitch = lv->frame_pitch;
+    lv->colored = on;
+    lv->frame_format = on ? format : NMI_FRAME_GRAY;
+    lv->frame_pitch = on ? row_bytes : 0;
+    const int rc = level_capture(lv);
+    if (rc != NMI_OK) {
+        lv->colored = was;
+        lv->frame_format = was_format;
+        lv->frame_pitch = was_pitch;
+        return rc;
+    }
+    if (!on && !lv->distorted && lv->d_ud) {  // no graph reads the level's own frame now
+        (void)hipFree(lv->d_ud);
+        lv->d_ud = nullptr;
     }
     return NMI_OK;
 }
@@ -772,8 +824,16 @@ struct nmi_stream {
     // d_ud[b] (masked / covered: their masks into d_ud_mask[b]), and the warps are made from those.
     bool distorted = false;
     nmi::UndistortParams ud{};
-    uint8_t *d_ud[2] = {nullptr, nullptr};        // [H][W], allocated on the first distorted frame
+    uint8_t *d_ud[2] = {nullptr, nullptr};        // [H][W], allocated on the first distorted (or coloured) frame
     uint8_t *d_ud_mask[2] = {nullptr, nullptr};   // [H][W], allocated on the first distorted masked / covered frame
+    // Frame format (nmi_stream_set_frame_format): frames submitted while it is set cross as H rows of frame_pitch bytes into the
+    // dense colour slot d_color[b] and are converted on the compute stream into d_ud[b] (undistorted too, in the same node, when
+    // distorted); the warps are made from those.
+    bool colored = false;
+    int32_t frame_format = NMI_FRAME_GRAY;
+    int64_t frame_pitch = 0;                      // host row bytes (never 0 while colored)
+    uint8_t *d_color[2] = {nullptr, nullptr};     // [H][W * bytes per pixel], allocated on the first coloured frame
+    size_t color_bytes = 0;                       // their size
 };
 
 namespace {
@@ -845,6 +905,7 @@ int nmi_stream_destroy(nmi_stream *st)
         if (st->d_wtables[b]) (void)hipFree(st->d_wtables[b]);
         if (st->d_ud[b]) (void)hipFree(st->d_ud[b]);
         if (st->d_ud_mask[b]) (void)hipFree(st->d_ud_mask[b]);
+        if (st->d_color[b]) (void)hipFree(st->d_color[b]);
     }
     if (st->d_rmasks) (void)hipFree(st->d_rmasks);
     if (st->d_redo) (void)hipFree(st->d_redo);
@@ -933,10 +994,23 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const int rc = stream_alloc_masks(st, kind);
         if (rc != NMI_OK) return rc;
     }
-    const bool undistort = h_frame && st->distorted;
-    for (int b = 0; undistort && b < 2; ++b) {
+    const bool undistort = h_frame && st->distorted, colored = h_frame && st->colored;
+    const int32_t format = st->frame_format;
+    const int64_t dense_row = (int64_t)ctx->params.width * frame_bytes_per_pixel(format);
+    for (int b = 0; (undistort || colored) && b < 2; ++b) {
         if (!st->d_ud[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud[b], npix));
-        if (kind != kPlain && !st->d_ud_mask[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud_mask[b], npix));
+        if (undistort && kind != kPlain && !st->d_ud_mask[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud_mask[b], npix));
+    }
+    if (colored && st->color_bytes < (size_t)dense_row * ctx->params.height) {  // (a wider format than the slots were made for)
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(st->copy));        // nothing in flight reads or fills the old slots
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        st->color_bytes = 0;
+        for (int b = 0; b < 2; ++b) {
+            if (st->d_color[b]) (void)hipFree(st->d_color[b]);
+            st->d_color[b] = nullptr;
+        }
+        for (int b = 0; b < 2; ++b) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_color[b], (size_t)dense_row * ctx->params.height));
+        st->color_bytes = (size_t)dense_row * ctx->params.height;
     }
 
     // copy stream: render stack of this level into the slot (the slot's previous search finished: it was waited for)
@@ -947,7 +1021,11 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const int nb = st->have_warps ? st->warp_buf ^ 1 : 0;
         // the buffer being refilled was last read by searches submitted before the previous frame switch
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(st->copy, st->warps_free[nb], 0));
-        NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
+        if (colored)  // H rows of the host's pitch into the dense colour slot
+            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)st->frame_pitch, (size_t)dense_row,
+                                              (size_t)ctx->params.height, hipMemcpyHostToDevice, st->copy));
+        else
+            NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
         if (h_frame_mask) NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_fmask[nb], h_frame_mask, npix, hipMemcpyHostToDevice, st->copy));
         NMI_HIP_TRY(ctx, hipEventRecord(st->frame_copied, st->copy));
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
@@ -955,10 +1033,17 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const uint8_t *frame = st->d_frame[nb], *frame_mask = h_frame_mask ? st->d_fmask[nb] : nullptr;
         if (undistort) {  // the raw frame (and mask) -> the undistorted ones, on the compute stream: the warps read them next
             uint8_t *ud_mask = kind != kPlain ? st->d_ud_mask[nb] : nullptr;
-            NMI_HIP_TRY(ctx, nmi::launch_undistort(st->ud, frame, frame_mask, st->d_ud[nb], ud_mask, ctx->params.width, ctx->params.height,
-                                                   ctx->stream));
+            if (colored)  // converted and undistorted in one node
+                NMI_HIP_TRY(ctx, nmi::launch_undistort_color(st->ud, st->d_color[nb], format, dense_row, frame_mask, st->d_ud[nb], ud_mask,
+                                                             ctx->params.width, ctx->params.height, ctx->stream));
+            else
+                NMI_HIP_TRY(ctx, nmi::launch_undistort(st->ud, frame, frame_mask, st->d_ud[nb], ud_mask, ctx->params.width, ctx->params.height,
+                                                       ctx->stream));
             frame = st->d_ud[nb];
             frame_mask = ud_mask;
+        } else if (colored) {  // the colour frame -> grey, on the compute stream; a frame mask is dense already
+            NMI_HIP_TRY(ctx, nmi::launch_gray(st->d_color[nb], format, dense_row, st->d_ud[nb], ctx->params.width, ctx->params.height, ctx->stream));
+            frame = st->d_ud[nb];
         }
         int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, st->d_warps[nb])
                                 : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, st->d_warps[nb], st->d_wmasks[nb]);
@@ -1098,6 +1183,19 @@ int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dis
     // later frame submissions take the map by value at their launch: tickets already submitted are not affected
     st->distorted = dist && !identity;
     st->ud = ud;
+    return NMI_OK;
+}
+
+int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch)
+{
+    if (!st) return NMI_ERR_INVALID_ARGUMENT;
+    int64_t row_bytes = 0;
+    bool identity = true;
+    if (frame_format_check(format, pitch, st->ctx->params.width, &row_bytes, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    // later frame submissions read the format at their upload: tickets already submitted are not affected
+    st->colored = !identity;
+    st->frame_format = identity ? NMI_FRAME_GRAY : format;
+    st->frame_pitch = identity ? 0 : row_bytes;
     return NMI_OK;
 }
 

@@ -1,0 +1,32 @@
+// nmi_color.h -- internal interface of the colour and pitched camera frames (nmi_color.hip, and the colour instantiation of the
+// undistortion kernel in nmi_undistort.hip), used by nmi_capi_color.cpp (nmi_gray_frame) and by the captured levels and streams
+// of nmi_capi_pipeline.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nmi_undistort.h"
+
+namespace nmi {
+
+// gray[y][x] = the grey value (include/nmi_hip.h, nmi_gray_frame) of pixel (x, y) of the height rows of pitch bytes at src in
+// format (an NMI_FRAME_* value; pitch > 0, the rows' bytes).  gray is dense [height][width] and does not overlap the source.
+hipError_t launch_gray(const uint8_t *src, int format, int64_t pitch, uint8_t *gray, int width, int height, hipStream_t stream);
+
+// launch_undistort on the grey values of a colour or pitched raw frame, in one kernel: equal to launch_gray into a dense frame
+// followed by launch_undistort on it.  raw_mask and frame_mask are dense [height][width], as there.
+hipError_t launch_undistort_color(const UndistortParams &p, const uint8_t *src, int format, int64_t pitch, const uint8_t *raw_mask,
+                                  uint8_t *frame, uint8_t *frame_mask, int width, int height, hipStream_t stream);
+
+}  // namespace nmi
+
+namespace nmi_internal {
+
+// Bytes per pixel of an NMI_FRAME_* format, 0 for an unknown one.
+int frame_bytes_per_pixel(int32_t format);
+
+// format known, pitch 0 (dense) or >= width * bytes per pixel -> NMI_OK, *row_bytes = the rows' pitch (width * bytes per pixel
+// for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion); else NMI_ERR_INVALID_ARGUMENT.
+int frame_format_check(int32_t format, int64_t pitch, int width, int64_t *row_bytes, bool *identity);
+
+}  // namespace nmi_internal

@@ -9,11 +9,15 @@
 // -- the textbook u_d = fx x_d + cx written as a displacement, so that zero coefficients give xs = u, ys = v exactly: the
 // frame is copied and every mask byte is 1.  The value at (xs, ys) is warp_sample_global's (nmi_warp_device.h), the mask
 // warp_source_valid's: the rules of the warp stack and its masks.  No special case where the polynomial folds over.
-// Taps are gathered from global memory (a frame is well under 1 MB and stays in L2); no LDS staging.
+// Taps are gathered from global memory (a frame is well under 1 MB and stays in L2); no LDS staging.  The colour instantiation
+// (launch_undistort_color) takes its taps from a colour or pitched frame, converted to grey (nmi_color_device.h) one by one.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "nmi_hip.h"
+#include "nmi_color.h"
+#include "nmi_color_device.h"
 #include "nmi_undistort.h"
 #include "nmi_warp_device.h"
 
@@ -37,8 +41,12 @@ __device__ __forceinline__ void undistort_source(const UndistortParams &p, float
 }  // namespace
 
 // A lane makes 4 adjacent pixels of one row (and their mask bytes): one dword store each where every row starts on a 4-byte
-// boundary (aligned), byte stores otherwise.
-__global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, const uint8_t *__restrict__ raw, const uint8_t *__restrict__ raw_mask,
+// boundary (aligned), byte stores otherwise.  raw fetches the raw frame's grey taps (warp_sample_taps): GrayTaps
+// (nmi_warp_device.h) for a dense grey frame (launch_undistort), ColorTaps (nmi_color_device.h) for a colour or pitched one
+// (launch_undistort_color: one node instead of launch_gray followed by this kernel, with the same bytes, each tap being the grey
+// value launch_gray would have stored).
+template <class Taps>
+__global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, const Taps raw, const uint8_t *__restrict__ raw_mask,
                                                             uint8_t *__restrict__ frame, uint8_t *__restrict__ frame_mask, int width, int height,
                                                             int aligned)
 {
@@ -52,7 +60,7 @@ __global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, c
     for (int k = 0; k < n; ++k) {
         float xs, ys;
         undistort_source(p, (float)(x0 + k), v, &xs, &ys);
-        packed |= warp_sample_global(raw, width, height, xs, ys) << (8 * k);
+        packed |= warp_sample_taps(raw, width, height, xs, ys) << (8 * k);
         if (frame_mask) mpacked |= (uint32_t)warp_source_valid(raw_mask, width, height, xs, ys) << (8 * k);
     }
     const size_t o = (size_t)y * width + x0;
@@ -66,13 +74,46 @@ __global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, c
     }
 }
 
+static dim3 undistort_grid(int width, int height)
+{
+    const int quads = (width + 3) / 4;
+    return dim3((quads + kUndistortQuads - 1) / kUndistortQuads, (height + 3) / 4);
+}
+
 hipError_t launch_undistort(const UndistortParams &p, const uint8_t *raw, const uint8_t *raw_mask, uint8_t *frame, uint8_t *frame_mask,
                             int width, int height, hipStream_t stream)
 {
-    const int quads = (width + 3) / 4;
     const int aligned = (width % 4) == 0 && ((uintptr_t)frame % 4) == 0 && ((uintptr_t)frame_mask % 4) == 0;
-    hipLaunchKernelGGL(nmi_undistort_kernel, dim3((quads + kUndistortQuads - 1) / kUndistortQuads, (height + 3) / 4), dim3(kUndistortQuads, 4), 0,
-                       stream, p, raw, raw_mask, frame, frame_mask, width, height, aligned);
+    hipLaunchKernelGGL(nmi_undistort_kernel<GrayTaps>, undistort_grid(width, height), dim3(kUndistortQuads, 4), 0, stream, p, GrayTaps{raw}, raw_mask,
+                       frame, frame_mask, width, height, aligned);
+    return hipGetLastError();
+}
+
+hipError_t launch_undistort_color(const UndistortParams &p, const uint8_t *src, int format, int64_t pitch, const uint8_t *raw_mask,
+                                  uint8_t *frame, uint8_t *frame_mask, int width, int height, hipStream_t stream)
+{
+    const int aligned = (width % 4) == 0 && ((uintptr_t)frame % 4) == 0 && ((uintptr_t)frame_mask % 4) == 0;
+    const dim3 grid = undistort_grid(width, height), block(kUndistortQuads, 4);
+    const size_t pb = (size_t)pitch;
+    switch (format) {
+    case NMI_FRAME_GRAY:
+        hipLaunchKernelGGL((nmi_undistort_kernel<ColorTaps<1, 0>>), grid, block, 0, stream, p, ColorTaps<1, 0>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned);
+        break;
+    case NMI_FRAME_BGR:
+        hipLaunchKernelGGL((nmi_undistort_kernel<ColorTaps<3, 2>>), grid, block, 0, stream, p, ColorTaps<3, 2>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned);
+        break;
+    case NMI_FRAME_RGB:
+        hipLaunchKernelGGL((nmi_undistort_kernel<ColorTaps<3, 0>>), grid, block, 0, stream, p, ColorTaps<3, 0>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned);
+        break;
+    case NMI_FRAME_BGRA:
+        hipLaunchKernelGGL((nmi_undistort_kernel<ColorTaps<4, 2>>), grid, block, 0, stream, p, ColorTaps<4, 2>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned);
+        break;
+    case NMI_FRAME_RGBA:
+        hipLaunchKernelGGL((nmi_undistort_kernel<ColorTaps<4, 0>>), grid, block, 0, stream, p, ColorTaps<4, 0>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned);
+        break;
+    default:
+        return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -29,16 +29,25 @@ __device__ __forceinline__ float warp_tap(const uint8_t *__restrict__ src, int w
     return (x >= 0 && x < w && y >= 0 && y < h) ? (float)src[y * w + x] : 0.0f;  // BORDER_CONSTANT, value 0
 }
 
-// The value at source coordinate (xs, ys) with its taps taken from global memory: the reach test, the bilinear taps with a
-// border of 0, saturate_cast<uchar>.  Shared by warp_pixel_global and the undistortion kernel (nmi_undistort.hip).
-__device__ __forceinline__ uint32_t warp_sample_global(const uint8_t *__restrict__ frame, int width, int height, float xs, float ys)
+// The grey frame's tap fetch: the byte at (x, y), 0 outside (warp_tap).  warp_sample_taps takes any fetch of this shape; the
+// colour frames' (nmi_color_device.h) converts each tap to grey first.
+struct GrayTaps {
+    const uint8_t *__restrict__ frame;
+    __device__ __forceinline__ float operator()(int w, int h, int x, int y) const { return warp_tap(frame, w, h, x, y); }
+};
+
+// The value at source coordinate (xs, ys) with its taps taken from global memory through taps(w, h, x, y): the reach test, the
+// bilinear taps with a border of 0, saturate_cast<uchar>.  Shared by warp_pixel_global and the undistortion kernel
+// (nmi_undistort.hip).
+template <class Taps>
+__device__ __forceinline__ uint32_t warp_sample_taps(const Taps &taps, int width, int height, float xs, float ys)
 {
     float acc = 0.0f;
     if (xs > -2.0f && xs < (float)(width + 1) && ys > -2.0f && ys < (float)(height + 1)) {
         const int x1 = (int)floorf(xs), y1 = (int)floorf(ys);
         const int x2 = x1 + 1, y2 = y1 + 1;
-        const float t11 = warp_tap(frame, width, height, x1, y1), t21 = warp_tap(frame, width, height, x2, y1);
-        const float t12 = warp_tap(frame, width, height, x1, y2), t22 = warp_tap(frame, width, height, x2, y2);
+        const float t11 = taps(width, height, x1, y1), t21 = taps(width, height, x2, y1);
+        const float t12 = taps(width, height, x1, y2), t22 = taps(width, height, x2, y2);
         acc = acc + t11 * (((float)x2 - xs) * ((float)y2 - ys));
         acc = acc + t21 * ((xs - (float)x1) * ((float)y2 - ys));
         acc = acc + t12 * (((float)x2 - xs) * (ys - (float)y1));
@@ -46,6 +55,11 @@ __device__ __forceinline__ uint32_t warp_sample_global(const uint8_t *__restrict
     }
     const float r = rintf(acc);
     return r <= 0.0f ? 0u : (r >= 255.0f ? 255u : (uint32_t)r);
+}
+
+__device__ __forceinline__ uint32_t warp_sample_global(const uint8_t *__restrict__ frame, int width, int height, float xs, float ys)
+{
+    return warp_sample_taps(GrayTaps{frame}, width, height, xs, ys);
 }
 
 // One output pixel with its taps taken from global memory (the arithmetic of nmi_warp_kernel, shared with the fallback of

@@ -6,6 +6,7 @@
 // (the reference files also contain `key:value` without a blank, which OpenCV accepts), quoted strings, and
 // `!!opencv-matrix` nodes with rows / cols / dt / data (data may span lines).
 #include <ctype.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -231,6 +232,30 @@ int nmi_config_load_distortion(const char *yaml_path, float dist[5])
     std::string text;
     if (read_file(yaml_path, text) != 0) return -5;
     return nmi_config_parse_distortion(text.data(), text.size(), dist);
+}
+
+// Tracking.cc:179-183: int nRGB = fSettings["Camera.RGB"]; mbRGB = nRGB.  A missing key reads as 0 there (cv::FileNode's int
+// conversion of an empty node), and here; a real value is rounded to the nearest int (half to even), as that conversion's cvRound
+// does, and one out of int range is a syntax error.
+int nmi_config_parse_color_order(const char *text, size_t len, int32_t *rgb)
+{
+    if (!text || !rgb) return -1;
+    std::map<std::string, Node> m;
+    if (!parse(text, len, m)) return -2;
+    double v = 0.0;
+    if (!number(m, "Camera.RGB", v)) v = 0.0;
+    v = nearbyint(v);
+    if (!(v >= -2147483648.0 && v <= 2147483647.0)) return -2;
+    *rgb = (int32_t)v;
+    return 0;
+}
+
+int nmi_config_load_color_order(const char *yaml_path, int32_t *rgb)
+{
+    if (!yaml_path || !rgb) return -1;
+    std::string text;
+    if (read_file(yaml_path, text) != 0) return -5;
+    return nmi_config_parse_color_order(text.data(), text.size(), rgb);
 }
 
 }  // extern "C"

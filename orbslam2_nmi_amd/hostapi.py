@@ -16,6 +16,7 @@ EXPORTED_SYMBOLS = (
     "nmi_calculate_translation", "nmi_calculate_relocalization", "nmi_mat4_inverse", "nmi_relocalize_with_strategy",
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
     "nmi_config_parse_distortion", "nmi_config_load_distortion",
+    "nmi_config_parse_color_order", "nmi_config_load_color_order",
 )
 
 
@@ -102,6 +103,8 @@ def _lib():
         lib.nmi_config_load.argtypes = [C.c_char_p, C.POINTER(Config)]
         lib.nmi_config_parse_distortion.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_float)]
         lib.nmi_config_load_distortion.argtypes = [C.c_char_p, C.POINTER(C.c_float)]
+        lib.nmi_config_parse_color_order.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.nmi_config_load_color_order.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
         fpp, i64p = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)
         lib.nmi_map_load_obj.argtypes = [C.c_char_p, fpp, fpp, i64p]
         lib.nmi_map_load_xyz.argtypes = [C.c_char_p, C.c_char_p, fpp, fpp, fpp, i64p]
@@ -216,6 +219,24 @@ def config_load_distortion(path):
     if rc != 0:
         raise ValueError(f"nmi_config_load_distortion({path}) failed: {rc}")
     return out
+
+
+def config_parse_color_order(text):
+    """Camera.RGB of a settings file (Tracking.cc:179-183; a missing key reads as 0) -> int: 1 = RGB(A), 0 = BGR(A); raises on errors."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    out = C.c_int32(-1)
+    rc = _lib().nmi_config_parse_color_order(raw, len(raw), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"nmi_config_parse_color_order failed: {rc}")
+    return int(out.value)
+
+
+def config_load_color_order(path):
+    out = C.c_int32(-1)
+    rc = _lib().nmi_config_load_color_order(str(path).encode(), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"nmi_config_load_color_order({path}) failed: {rc}")
+    return int(out.value)
 
 
 def _take(ptr, shape, dtype):
