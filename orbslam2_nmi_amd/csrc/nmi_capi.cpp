@@ -675,8 +675,6 @@ int nmi_destroy(nmi_ctx *ctx)
     if (ctx->d_mask_redo) (void)hipFree(ctx->d_mask_redo);
     if (ctx->d_mask_redo_state) (void)hipFree(ctx->d_mask_redo_state);
     if (ctx->d_cover_counts) (void)hipFree(ctx->d_cover_counts);
-    if (ctx->d_cover_redo) (void)hipFree(ctx->d_cover_redo);
-    if (ctx->d_cover_redo_state) (void)hipFree(ctx->d_cover_redo_state);
     if (ctx->d_zbuf) (void)hipFree(ctx->d_zbuf);
     mesh_work_free(&ctx->mesh);
     for (int i = 0; i < StagingRing::kSlots; ++i) {

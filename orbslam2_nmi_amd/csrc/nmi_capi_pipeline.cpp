@@ -161,32 +161,11 @@ static int level_capture(nmi_level *lv)
         a.order = nullptr;
     }
     const int workgroups = lv->workgroups;
-    const bool masked = lv->masked;
-    nmi::MaskedGridArgs m{};
-    if (masked) {
-        m.g = a;
-        m.g.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;  // (bit 9: the pixel-range kernel's hand-off test hook)
-        m.warp_masks = lv->d_masks;
-        m.tables = lv->d_tables;
-        m.counts = lv->d_counts;
-        m.vec_ok = a.vec_ok && ((uintptr_t)lv->d_masks % 16) == 0;
-        m.redo = lv->d_redo;
-        m.redo_n = lv->d_redo_state;
-        m.redo_done = lv->d_redo_state + 1;
-    }
-    const bool covered = lv->covered;
-    nmi::CoveredGridArgs cm{};
-    if (covered) {
-        cm.g = a;
-        cm.g.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;
-        cm.warp_masks = lv->d_masks;
-        cm.render_masks = lv->d_rmasks;
-        cm.counts = lv->d_cover_counts;
-        cm.vec_ok = a.vec_ok && (((uintptr_t)lv->d_masks | (uintptr_t)lv->d_rmasks) % 16) == 0;
-        cm.redo = lv->d_redo;
-        cm.redo_n = lv->d_redo_state;
-        cm.redo_done = lv->d_redo_state + 1;
-    }
+    const bool masked = lv->masked, covered = lv->covered;
+    nmi::GridArgs ma = a;
+    ma.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;  // (bit 9: the pixel-range kernel's hand-off test hook)
+    const MaskSearch ms = mask_search_args(ma, lv->d_masks, covered ? lv->d_rmasks : nullptr, covered ? lv->d_cover_counts : lv->d_counts,
+                                           lv->d_tables, lv->d_redo, lv->d_redo_state);
     uint8_t *cover = covered ? lv->d_rmasks : nullptr;  // the renderers' coverage masks
     int32_t *d_prev = lv->d_counts + Wn, *d_changed = lv->d_counts + 2 * Wn;
     hipGraph_t graph = nullptr;
@@ -235,14 +214,9 @@ static int level_capture(nmi_level *lv)
             ok(nmi::launch_render_points(d_xyz, d_red, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_renders, p.width, p.height, lv->size, st,
                                          /*clear_first=*/false, cover));
         if (!fused || masked || covered) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
-        if (covered && lv->pix)
-            ok(nmi::launch_pix_covered(cm, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
-        else if (covered)
-            ok(nmi::launch_grid_covered(cm, workgroups, true, false, st));
-        else if (masked && lv->pix)
-            ok(nmi::launch_pix_masked(m, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
-        else if (masked)
-            ok(nmi::launch_grid_masked(m, workgroups, true, false, st));
+        if (masked || covered)
+            ok(launch_mask_search(ms, lv->pix, lv->pix ? pix_owner_share(ctx, lv->pix) : 0.0, workgroups, true, false, lv->d_epoch,
+                                  ctx->d_pix_timeouts, st));
         else if (lv->pix)
             ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
         else
@@ -1084,12 +1058,12 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
                           nullptr, nullptr, w_offset);
         ctx->allow_unchecked_split = false;
     } else if (kind == kMasked) {
-        rc = enqueue_grid_masked(ctx, s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn, w_offset,
-                                 st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+        rc = enqueue_grid_mask(ctx, s.d_renders, nullptr, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn, w_offset,
+                               st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state, ratings, s.d_key, false);
     } else {
         NMI_HIP_TRY(ctx, nmi::launch_unpack_mask_bits(s.d_bits, S, ctx->npix, st->d_rmasks, ctx->stream));
-        rc = enqueue_grid_covered(ctx, s.d_renders, st->d_rmasks, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn,
-                                  w_offset, s.d_counts, st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+        rc = enqueue_grid_mask(ctx, s.d_renders, st->d_rmasks, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn,
+                               w_offset, s.d_counts, nullptr, st->d_redo, st->d_redo_state, ratings, s.d_key, false);
     }
     if (rc != NMI_OK) return rc;
     s.kind = kind;

@@ -4,12 +4,11 @@
 // per-candidate len.  nmi_covered_grid_kernel gives a candidate to one workgroup, so 81 candidates fill 81 of the 256 CUs;
 // here they fill 243.
 //
-// One function is restated -- covered_decode_merged, decode_merged with the candidate's terms (see TWIN there).  Everything
-// else is reused: the dealing (make_deal), the hand-off blocks (PixHeader, unit layout, tagged mask
-// granules) come from nmi_pix_kernel.hip; masked_add_chunk from nmi_masked_kernel.hip; the mask fold (both_nonzero), the
-// term expression (cover_term), the exact path (covered_histogram_phase, covered_decode_phase) and the final trees
-// (covered_final_phase) from nmi_covered_kernel.hip.  All three files are included for their device functions only, so no
-// existing kernel changes.  Results are bit-identical to nmi_covered_grid_kernel's: the decoded counters are the same sums,
+// Restated: covered_decode_merged, decode_merged with the candidate's terms (see TWIN there), and the hand-off (a TWIN of
+// nmi_pix_kernel's).  Reused: the dealing (make_deal, pix_dealing) and the hand-off blocks (PixHeader, unit layout, tagged
+// mask granules) from nmi_pix_device.h; masked_add_chunk, the mask fold (both_nonzero), the term expression (cover_term), the
+// exact path (covered_histogram_phase, covered_decode_phase) and the final trees (covered_final_phase) from
+// nmi_mask_device.h.  Results are bit-identical to nmi_covered_grid_kernel's: the decoded counters are the same sums,
 // the trees the same code, the terms the same expression of the same len.
 //
 // What differs from nmi_masked_pix_kernel, and why:
@@ -34,13 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define NMI_PIX_DEVICE_ONLY 1
-#include "nmi_pix_kernel.hip"  // (includes nmi_kernels.hip) Deal, make_deal, PixHeader, decode_word, unit_offset
-#define NMI_MASKED_DEVICE_ONLY 1
-#include "nmi_masked_kernel.hip"  // masked_add_chunk, nonzero_byte_bits
-#define NMI_COVERED_DEVICE_ONLY 1
-#include "nmi_covered_kernel.hip"  // cover_term, both_nonzero, popc4, covered_histogram_phase, covered_decode_phase, covered_final_phase
-#include "nmi_covered.h"
+#include "nmi_mask_device.h"  // masked_add_chunk, cover_term, both_nonzero, popc4, covered_histogram_phase, covered_decode_phase, covered_final_phase
+#include "nmi_pix_device.h"   // Deal, make_deal, PixHeader, decode_word, unit_offset
 
 namespace nmi {
 
@@ -246,6 +240,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_pix_kernel(Cove
     char *const blocks = reinterpret_cast<char *>(a.blocks) + (size_t)p * (size_t)(P - 1) * kPixBlockBytes;
     if (!owner) {
         // ---- helper: nmi_pix_kernel's hand-off, plus the count of pixels added (header word pad[0]) ----
+        // TWIN: nmi_pix_kernel's helper part and owner's wait and merge, written out (see there) -- a fix there belongs here too.
         __syncthreads();
         char *const blk = blocks + (size_t)(q - 1) * kPixBlockBytes;
         PixHeader *const hdr = reinterpret_cast<PixHeader *>(blk);
@@ -367,28 +362,9 @@ hipError_t launch_pix_covered(const CoveredGridArgs &m, int pix_parts, double ow
                               hipStream_t stream)
 {
     const GridArgs &a = m.g;
+    if (!pix_launch_ok(a, pix_parts, use_bg) || a.plan || !m.counts || !m.warp_masks || !m.render_masks) return hipErrorInvalidValue;
     const long long total = (long long)a.S_local * a.Wn;
-    if (pix_parts < 2 || pix_parts > kMaxRanges || total <= 0 || total * pix_parts > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    if (a.width < 32 || !a.blocks || a.hist_variant != 3 || (a.shift != 0 && !use_bg) || a.order || a.plan || !m.counts || !m.warp_masks ||
-        !m.render_masks)
-        return hipErrorInvalidValue;
-    // the dealing pattern: launch_pix's choice (nmi_pix_kernel.hip), restated on the host
-    int own = 1, hlp = 1;
-    {
-        const double f = owner_share < 0.02 ? 0.02 : (owner_share > 0.98 ? 0.98 : owner_share);
-        double best = 2.0;
-        for (int b = 1; b <= 12; ++b) {
-            int o = (int)(f / (1.0 - f) * (pix_parts - 1) * b + 0.5);
-            o = o < 1 ? 1 : o;
-            if (o + (pix_parts - 1) * b > 48) break;
-            const double err = fabs((double)o / (o + (pix_parts - 1) * b) - f);
-            constexpr double kCloser = 0.03;
-            if (err < best - kCloser) best = err, own = o, hlp = b;
-        }
-    }
-    auto magic = [](int d) { return d > 1 ? (uint32_t)((0x100000000ull + (uint32_t)d - 1) / (uint32_t)d) : 0u; };
-    const int pieces = (a.height * a.chunks_per_row + 63) >> 6, L = own + (pix_parts - 1) * hlp;
-    const DealArgs g{own, hlp, magic(own), magic(hlp), pieces / L, pieces % L, magic((int)total)};
+    const DealArgs g = pix_dealing(a, pix_parts, owner_share);
     const dim3 grid((unsigned)(total * pix_parts)), block(kBlock);
     if (a.shift != 0)
         hipLaunchKernelGGL((nmi_covered_pix_kernel<false, true>), grid, block, 0, stream, m, pix_parts, g, replay, healed);

@@ -12,7 +12,9 @@
 #include <vector>
 
 #include "nmi_hip.h"
+#include "nmi_covered.h"
 #include "nmi_kernels.h"
+#include "nmi_masked.h"
 
 // Small host->device parameter uploads (warp coefficients, view matrices) go through a ring of pinned staging buffers so
 // that back-to-back submissions never have to wait for the stream: entry i is reused only after the copy that read it.
@@ -121,19 +123,19 @@ struct nmi_ctx {
     hipEvent_t warp_ev[kWarpRing] = {};
     int warp_coeffs_cap = 0;
     unsigned warp_uses = 0;
-    // Masked search (nmi_capi_masked.cpp): per-warp mask counts and term tables, the redo list of its optimistic launch.
-    // Allocated on first use, grown on demand, freed by nmi_destroy.
+    // Masked search (nmi_capi_masked.cpp): per-warp mask counts and term tables.  Allocated on first use, grown on demand,
+    // freed by nmi_destroy.
     int32_t *d_mask_counts = nullptr;     // [mask_warps_cap] len_w of the latest masked search
     float *d_mask_tables = nullptr;       // [mask_warps_cap][npix + 1]
     int mask_warps_cap = 0;
     int mask_count_n = 0;                 // warps counted by the latest masked search
+    // The redo list of the masked and the covered searches' optimistic launches: one for both, as in a level or a stream (the
+    // searches are serialised on the context's stream, and each leaves the list empty).
     int32_t *d_mask_redo = nullptr;       // [mask_redo_cap] candidates to score again exactly
     uint32_t *d_mask_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
     int64_t mask_redo_cap = 0;
-    // Covered search (nmi_capi_covered.cpp): per-candidate pixel counts and the redo list of its optimistic launch.
+    // Covered search (nmi_capi_covered.cpp): per-candidate pixel counts.
     int32_t *d_cover_counts = nullptr;    // [cover_cap] len[w][s] of the latest covered search, layout [Wn][S]
-    int32_t *d_cover_redo = nullptr;      // [cover_cap] candidates to score again exactly
-    uint32_t *d_cover_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
     int64_t cover_cap = 0;
     int64_t cover_count_n = 0;            // candidates counted by the latest covered search
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
@@ -186,14 +188,25 @@ int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes);  // the context's hand-off bl
 int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack, int Wn,
                  float *d_ratings, unsigned long long *out_key, bool post, uint32_t *dbg_joint, uint32_t *dbg_h1, uint32_t *dbg_h2,
                  float *dbg_sums, int w_offset = 0, bool post_score = false);
-// The masked / covered searches' launches without their blocking tails (nmi_capi_masked.cpp, nmi_capi_covered.cpp): serve
-// nmi_search_grid_masked / _covered and the masked / covered stream tickets.  S_local * Wn > 0; see the definitions.
-int enqueue_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
-                        const uint8_t *warp_masks, int Wn, int w_offset, const int32_t *counts, const float *tables, int32_t *redo,
-                        uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
-int enqueue_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int S_local, int s_offset, int S_total,
-                         const uint8_t *warp_stack, const uint8_t *warp_masks, int Wn, int w_offset, int32_t *counts, int32_t *redo,
-                         uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
+// The masked and covered searches' kernel arguments around the grid arguments a (nmi_capi_masked.cpp): the covered search
+// when render_masks is set (counts receives len[w][s], [Wn][S_local]), else the masked one (counts: len_w [Wn], tables: the
+// warps' term tables).  redo has room for S_local * Wn candidates; redo_state [2] is zero.
+struct MaskSearch {
+    bool covered;
+    nmi::MaskedGridArgs masked;
+    nmi::CoveredGridArgs cover;
+};
+MaskSearch mask_search_args(const nmi::GridArgs &a, const uint8_t *warp_masks, const uint8_t *render_masks, int32_t *counts,
+                            const float *tables, int32_t *redo, uint32_t *redo_state);
+// Its launches: the pixel-range form when pix > 0 (replay, healed: as launch_pix_masked / _covered), else the grid form.
+hipError_t launch_mask_search(const MaskSearch &ms, int pix, double owner_share, int workgroups, bool use_bg, bool exact,
+                              const uint32_t *replay, uint32_t *healed, hipStream_t stream);
+int ensure_mask_redo(nmi_ctx *ctx, int64_t total);  // the context's redo list, room for `total` candidates
+// The masked / covered search's launches without its blocking tail (nmi_capi_masked.cpp): serves nmi_search_grid_masked,
+// nmi_search_grid_covered and the masked / covered stream tickets.  S_local * Wn > 0; see the definition.
+int enqueue_grid_mask(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int S_local, int s_offset, int S_total,
+                      const uint8_t *warp_stack, const uint8_t *warp_masks, int Wn, int w_offset, int32_t *counts, const float *tables,
+                      int32_t *redo, uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
 int wait_word(nmi_ctx *ctx, const volatile unsigned long long *word, unsigned long long mask, unsigned long long want,
               unsigned long long *out);
 int stage_floats(nmi_ctx *ctx, StagingRing &ring, const float *h_src, size_t n, float **d_out);

@@ -141,7 +141,8 @@ inline size_t split_block_bytes_per_candidate(int pix_parts) { return (size_t)pi
 // Pixel-range form for mid-size grids (nmi_pix_kernel.hip): pix_parts workgroups per candidate, each adding a range of the
 // pair's pixels into a whole packed joint histogram; the helpers' histograms travel to the candidate's owner through
 // a.blocks (pix_block_bytes, zero when allocated; tag from a.epoch + *replay).  *timeouts counts candidates whose owner
-// gave up waiting and scored them alone (the launch heals itself).  Needs a.vec_ok, a.order == nullptr, a.epoch != 0.
+// gave up waiting and scored them alone (the launch heals itself).  Needs width >= 32 (rows need not be whole aligned
+// chunks), a.order == nullptr, a.epoch != 0.
 // owner_share: fraction of the pair's pixels the owner adds itself (the helpers share the rest equally).
 hipError_t launch_pix(const GridArgs &a, int pix_parts, double owner_share, bool use_bg, const uint32_t *replay, uint32_t *timeouts, hipStream_t stream);
 size_t pix_block_bytes(int candidates, int pix_parts);

@@ -3,8 +3,7 @@
 // A candidate (warp w, render s) counts pixel pos iff mask[w][pos] != 0 and the background rule passes (NMI.cu:85, on the
 // raw intensities, before the shift); the entropy terms use len_w = popcount(mask[w]) in place of W*H (NMI.cu:245), so each
 // warp has its own per-count table.  Everything else -- the trees, SUC / ENMI, the all-zero guard, the rating table and the
-// arg-max -- is nmi_grid_kernel's own code (nmi_kernels.hip, included below for its device functions only; the existing
-// kernels' translation units are untouched).
+// arg-max -- is nmi_grid_kernel's own code (nmi_grid_device.h; the masked forms are in nmi_mask_device.h).
 //
 // What changes against nmi_grid_kernel, and why:
 //   * Pixel loop.  A wavefront whose 16-byte mask chunks are all nonzero runs nmi_grid_kernel's add_chunk unchanged; one with
@@ -28,139 +27,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// nmi_masked_pix_kernel.hip includes this file for its device functions only (NMI_MASKED_DEVICE_ONLY), after nmi_kernels.hip.
-#ifndef NMI_MASKED_DEVICE_ONLY
-#define NMI_KERNELS_DEVICE_ONLY 1
-#include "nmi_kernels.hip"  // Lds, add_chunk, add_pixel, decode_phase, final_phase, finish_search, candidate_at
-#endif
-#include "nmi_masked.h"
+#include "nmi_mask_device.h"
 
 namespace nmi {
 
-namespace {
-
-// number of nonzero bytes of a dword (bit 7 of each byte of the sum is set iff the byte is nonzero)
-__device__ __forceinline__ uint32_t nonzero_byte_bits(uint32_t v) { return (((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u; }
-
-// 16 pixels of one lane with their 16 mask bytes.  HIST 2: non-returning atomics (optimistic pass); a wavefront whose mask
-// bytes are all nonzero runs add_chunk (nmi_kernels.hip) unchanged.  The choice is per wavefront, not per lane: an LDS atomic
-// costs its issue whatever the number of active lanes, so a wavefront that ran both forms for its lanes would issue 32 atomic
-// instructions per 16 pixels (measured: 1.4x the kernel time with the border masks of a rotation grid).  HIST 1: returning
-// atomics + wrap bookkeeping (exact path), in batches of 4 pixels -- 4 returned words in flight instead of add_chunk's 16
-// keep this cold path inside the register budget.
-template <bool BG, bool SHIFTED, int HIST>
-__device__ __forceinline__ void masked_add_chunk(Lds &lds, int par, const uint4 &rv, const uint4 &wv, const uint4 &mv, int shift)
-{
-    if (HIST == 2 &&
-        __all((nonzero_byte_bits(mv.x) & nonzero_byte_bits(mv.y) & nonzero_byte_bits(mv.z) & nonzero_byte_bits(mv.w)) == 0x80808080u)) {
-        add_chunk<BG, SHIFTED, HIST, false>(lds, par, rv, wv, shift, false);  // every pixel takes part
-        return;
-    }
-    const uint32_t r[4] = {rv.x, rv.y, rv.z, rv.w};
-    const uint32_t w[4] = {wv.x, wv.y, wv.z, wv.w};
-    const uint32_t m[4] = {mv.x, mv.y, mv.z, mv.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t old[4], any = 0;  // any: 0xFFFFFFFF iff some counter wrapped (a pixel that was not added has old = 0)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t d1 = (r[q] >> (8 * j)) & 0xFFu, d2 = (w[q] >> (8 * j)) & 0xFFu;
-            const bool take = ((m[q] >> (8 * j)) & 0xFFu) != 0u && (BG || (d1 != 0 && d2 != 0));  // NMI.cu:85 on the raw values
-            if (SHIFTED) {
-                d1 >>= shift;
-                d2 >>= shift;
-            }
-            const uint32_t word = joint_word(d1, d2), val = joint_inc(d2);
-            if (HIST == 2) {
-                if (take) (void)__hip_atomic_fetch_add(&lds.joint[word], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {
-                old[j] = 0;
-                if (take) old[j] = __hip_atomic_fetch_add(&lds.joint[word], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-        if (HIST == 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t d2 = (w[q] >> (8 * j)) & 0xFFu;
-                if (SHIFTED) d2 >>= shift;
-                const uint32_t t = old[j] | ((d2 & 128u) ? 0x0000FFFFu : 0xFFFF0000u);
-                any = t > any ? t : any;
-            }
-            if (__builtin_expect(any == 0xFFFFFFFFu, 0)) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t d1 = (r[q] >> (8 * j)) & 0xFFu, d2 = (w[q] >> (8 * j)) & 0xFFu;
-                    const bool take = ((m[q] >> (8 * j)) & 0xFFu) != 0u && (BG || (d1 != 0 && d2 != 0));
-                    if (SHIFTED) {
-                        d1 >>= shift;
-                        d2 >>= shift;
-                    }
-                    const uint32_t val = joint_inc(d2), field = val * 0xFFFFu;
-                    if (take && (old[j] & field) == field) record_wrap(lds, par, joint_word(d1, d2), val, old[j]);
-                }
-            }
-        }
-    }
-}
-
-// Histogram phase of one candidate over all its pixels (NMI.cu:79-87 with the mask), all 1024 lanes.
-template <bool BG, bool SHIFTED, int HIST>
-__device__ __forceinline__ void masked_histogram_phase(Lds &lds, int par, const MaskedGridArgs &m, const uint8_t *__restrict__ render,
-                                                       const uint8_t *__restrict__ warped, const uint8_t *__restrict__ mask, int tid)
-{
-    const GridArgs &a = m.g;
-    if (m.vec_ok) {
-        const int nchunks = a.npix >> 4, last = nchunks - 1;
-        auto ld = [&](const uint8_t *base, int c) { return *reinterpret_cast<const uint4 *>(base + ((uint32_t)c << 4)); };
-        // NMI.cu:82: row y of the frame meets row H-1-y of a bottom-up render (flip_base / flip_row, as histogram_phase)
-        auto ldr = [&](int c) {
-            const int y = (int)__umulhi((uint32_t)c, a.cpr_magic);
-            return *reinterpret_cast<const uint4 *>(render + ((uint32_t)(__mul24(y, a.flip_row) + c + a.flip_base) << 4));
-        };
-        if (HIST == 1) {
-            // exact path (cold): no prefetch -- the 16 returned words of a chunk already hold 16 registers
-#pragma unroll 1
-            for (int ch = tid; ch < nchunks; ch += kBlock) masked_add_chunk<BG, SHIFTED, HIST>(lds, par, ldr(ch), ld(warped, ch), ld(mask, ch), a.shift);
-            return;
-        }
-        // one chunk of prefetch; loads clamped to the last chunk (a valid address), only the adds are predicated
-        int c = min(tid, last);
-        uint4 wc = ld(warped, c), mc = ld(mask, c), rc = ldr(c);
-#pragma unroll 1
-        for (int ch = tid; ch < nchunks; ch += kBlock) {
-            const int cn = min(ch + kBlock, last);
-            const uint4 wn = ld(warped, cn), mn = ld(mask, cn), rn = ldr(cn);
-            masked_add_chunk<BG, SHIFTED, HIST>(lds, par, rc, wc, mc, a.shift);
-            wc = wn;
-            mc = mn;
-            rc = rn;
-        }
-    } else {
-        // any width / alignment: byte loads, positions as in NMI.cu:79-83
-        for (int pos = tid; pos < a.npix; pos += kBlock) {
-            if (mask[pos] == 0) continue;
-            const int y = pos / a.width;
-            const int x = pos - y * a.width;
-            const int ry = a.flip ? (a.height - 1 - y) : y;
-            uint32_t d1 = render[ry * a.width + x], d2 = warped[pos];
-            if (HIST == 2) {
-                if (BG || (d1 != 0 && d2 != 0)) {
-                    if (SHIFTED) {
-                        d1 >>= a.shift;
-                        d2 >>= a.shift;
-                    }
-                    (void)__hip_atomic_fetch_add(&lds.joint[joint_word(d1, d2)], joint_inc(d2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            } else {
-                add_pixel<BG, SHIFTED>(lds, par, d1, d2, a.shift);
-            }
-        }
-    }
-}
-
-}  // namespace
-
-#ifndef NMI_MASKED_DEVICE_ONLY
 // One workgroup per candidate, grid-stride over the candidates in the visiting order -- nmi_grid_kernel's structure: B1
 // histogram -> decode, B2 decode -> (wavefront 0: final trees + score + arg-max) || (the others: next candidate's pixels),
 // per-candidate state double-buffered by parity.
@@ -353,6 +223,5 @@ hipError_t launch_grid_masked(const MaskedGridArgs &m, int workgroups, bool use_
     }
     return hipGetLastError();
 }
-#endif  // !NMI_MASKED_DEVICE_ONLY
 
 }  // namespace nmi

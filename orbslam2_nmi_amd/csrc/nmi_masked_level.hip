@@ -8,11 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define NMI_KERNELS_DEVICE_ONLY 1
-#include "nmi_kernels.hip"  // kLdsTable
-#define NMI_MASKED_DEVICE_ONLY 1
-#include "nmi_masked_kernel.hip"  // nonzero_byte_bits
-#include "nmi_masked.h"
+#include "nmi_mask_device.h"  // kLdsTable, nonzero_byte_bits
 
 namespace nmi {
 
