@@ -364,6 +364,8 @@ int nmi_render_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int6
  *                       GL_LINEAR / GL_LINEAR_MIPMAP_LINEAR.  Triangles are clipped against the near plane in clip space
  *                       (a ground plane passing under the camera keeps its visible part).  Among fragments of equal 24-bit
  *                       depth the triangle drawn first (lowest index) wins, as GL_LESS leaves it.  At most 2^30 - 1 triangles.
+ *                       GL_REPEAT is exact while |u w_l - 0.5| < 2^24 - w_l on every sampled level l (v, h_l likewise);
+ *                       beyond that, and for non-finite uv, a sample reads some texel inside the level, not the repeated one.
  * Enqueued on the context's stream.  Parity with an OpenGL driver is unpinned (kernel comment).
  */
 typedef struct nmi_texture nmi_texture;

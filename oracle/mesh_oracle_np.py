@@ -12,10 +12,50 @@ implied by glEnable(GL_DEPTH_TEST) / glDrawArrays(GL_TRIANGLES), rendering.hpp:2
 z_clip >= -w_clip, new corners interpolated from the inside corner towards the outside one.
 "PARITY UNPINNED": an OpenGL driver rasterises in fixed point and may approximate the LOD; nothing to compare against.
 Slow (python loop over triangles): small test meshes only.
+
+The rule is written once, in stages, over a float type F: clip_coords -> _clip_near -> setup -> cover -> shade -> resolve
+(render_staged).  F = float32 is the twin of csrc/nmi_mesh.hip (same operations in the same order, the device's conversions:
+float -> int saturates and NaN converts to 0, fminf / fmaxf drop a NaN operand, GL_REPEAT by the kernel's fp32 wrap_index);
+F = float64 is the MODEL (render_mesh_f64): every operation in float64 on the fp32 inputs, log2 in float64, GL_REPEAT by an
+exact modulo.  render_mesh / render_stack return the twin's bytes.
 """
 import numpy as np
 
 f32 = np.float32
+DEPTH_MAX = 0xFFFFFF
+EMPTY_DEPTH = 1 << 24      # the depth of a pixel no fragment reached
+SETUP_STATUS = ("kept", "cw", "plane", "area", "box")   # kept, or the first test that dropped the piece (tri_setup's order)
+
+
+def sat_int(x):
+    """float -> int32 as the device converts: towards zero, saturating, NaN -> 0 (numpy's astype is undefined there)."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        y = np.where(np.isnan(x), 0.0, np.clip(np.trunc(x), -2.0 ** 31, 2.0 ** 31 - 1))
+    return y.astype(np.int64)
+
+
+def sat_uint(x):
+    """float -> uint32 likewise: negative and NaN -> 0, saturating at 2^32 - 1."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        y = np.where(np.isnan(x), 0.0, np.clip(np.trunc(x), 0.0, 2.0 ** 32 - 1))
+    return y.astype(np.int64)
+
+
+def wrap_index(x, n, bounded=True):
+    """wrap_index of nmi_mesh.hip in fp32: x mod n for an integer-valued x, exact for |x| < 2^24 - n; beyond that clamped into
+    [0, n - 1] (bounded=False: the rule before the clamp, kept for the test that shows what it did)."""
+    x = np.asarray(x, f32)
+    n = f32(n)
+    inv = f32(1.0) / n
+    with np.errstate(all="ignore"):
+        r = x - np.floor(x * inv) * n
+        r = np.where(r < 0, r + n, r)
+        r = np.where(r >= n, r - n, r)
+        if bounded:
+            r = np.fmin(np.fmax(r, f32(0.0)), n - f32(1.0))
+    return sat_int(r)
 
 
 def mip_luma(rgb):
@@ -38,118 +78,132 @@ def mip_luma(rgb):
     return levels
 
 
-def _bilinear(level, u, v):
+def _repeat(xf, n, F):
+    if F is f32:
+        return wrap_index(xf, n)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(xf), np.mod(xf, F(n)), 0.0).astype(np.int64)   # (fmod is exact)
+
+
+def _bilinear(level, u, v, F=f32):
     h, w = level.shape
-    x = u * f32(w) - f32(0.5)
-    y = v * f32(h) - f32(0.5)
-    xf, yf = np.floor(x), np.floor(y)
-    fx, fy = x - xf, y - yf
-    i0 = np.mod(xf.astype(np.int64), w)
-    j0 = np.mod(yf.astype(np.int64), h)
-    i1 = np.where(i0 + 1 == w, 0, i0 + 1)
-    j1 = np.where(j0 + 1 == h, 0, j0 + 1)
-    t00, t10, t01, t11 = level[j0, i0], level[j0, i1], level[j1, i0], level[j1, i1]
-    a = t00 + (t10 - t00) * fx
-    b = t01 + (t11 - t01) * fx
-    return a + (b - a) * fy
+    with np.errstate(all="ignore"):
+        x = u * F(w) - F(0.5)
+        y = v * F(h) - F(0.5)
+        xf, yf = np.floor(x), np.floor(y)
+        fx, fy = x - xf, y - yf
+        i0, j0 = _repeat(xf, w, F), _repeat(yf, h, F)
+        i1 = np.where(i0 + 1 == w, 0, i0 + 1)
+        j1 = np.where(j0 + 1 == h, 0, j0 + 1)
+        lv = level if F is f32 else level.astype(F)
+        t00, t10, t01, t11 = lv[j0, i0], lv[j0, i1], lv[j1, i0], lv[j1, i1]
+        a = t00 + (t10 - t00) * fx
+        b = t01 + (t11 - t01) * fx
+        return a + (b - a) * fy
 
 
-def render_mesh(xyz, uv, levels, mvp_colmajor, width, height):
-    """One view -> uint8 [H, W], bottom-up rows, background 255."""
-    m = np.asarray(mvp_colmajor, f32)
-    P = np.asarray(xyz, f32).reshape(-1, 3, 3)
-    T = np.asarray(uv, f32).reshape(-1, 3, 2)
-    zbuf = np.full((height, width), 0xFFFFFFFFFF, np.uint64)   # depth << 8 | grey; empty: a depth no fragment reaches, grey 255
-    for tri in range(P.shape[0]):
-        x, y, z = P[tri, :, 0], P[tri, :, 1], P[tri, :, 2]
-        cx = (m[0] * x + m[4] * y) + (m[8] * z + m[12])
-        cy = (m[1] * x + m[5] * y) + (m[9] * z + m[13])
-        cz = (m[2] * x + m[6] * y) + (m[10] * z + m[14])
-        cw = (m[3] * x + m[7] * y) + (m[11] * z + m[15])
-        tu, tv = T[tri, :, 0], T[tri, :, 1]
-        for sub in _clip_near(cx, cy, cz, cw, tu, tv):
-            _raster(zbuf, levels, width, height, *sub)
-    return (zbuf & np.uint64(0xFF)).astype(np.uint8)
+def clip_coords(xyz, mvp_colmajor, F=f32):
+    """-> cx, cy, cz, cw [T, 3]: glm mat4 * vec4 per corner, (m0 x + m1 y) + (m2 z + m3)."""
+    m = np.asarray(mvp_colmajor, f32).astype(F)
+    P = np.asarray(xyz, f32).reshape(-1, 3, 3).astype(F)
+    x, y, z = P[..., 0], P[..., 1], P[..., 2]
+    with np.errstate(all="ignore"):
+        return tuple((m[r] * x + m[4 + r] * y) + (m[8 + r] * z + m[12 + r]) for r in range(4))
 
 
 def _clip_near(cx, cy, cz, cw, tu, tv):
     """Near-plane clipping of one triangle in clip space -> list of 0, 1 or 2 triangles, each (cx, cy, cz, cw, tu, tv) of 3."""
-    d = cz + cw
-    inside = d >= 0
-    n_in = int(inside.sum())
-    if n_in == 0:
-        return []
-    if n_in == 3:
-        return [(cx, cy, cz, cw, tu, tv)]
-    poly = []
-    for k in range(3):
-        b = (k + 1) % 3
-        if inside[k]:
-            poly.append((cx[k], cy[k], cz[k], cw[k], tu[k], tv[k]))
-        if inside[k] != inside[b]:
-            i, o = (k, b) if inside[k] else (b, k)   # from the inside corner towards the outside one
-            t = d[i] / (d[i] - d[o])
-            w = cw[i] + (cw[o] - cw[i]) * t
-            poly.append((cx[i] + (cx[o] - cx[i]) * t, cy[i] + (cy[o] - cy[i]) * t, -w, w, tu[i] + (tu[o] - tu[i]) * t,
-                         tv[i] + (tv[o] - tv[i]) * t))
+    F = cx.dtype.type
+    with np.errstate(all="ignore"):
+        d = cz + cw
+        inside = d >= 0
+        n_in = int(inside.sum())
+        if n_in == 0:
+            return []
+        if n_in == 3:
+            return [(cx, cy, cz, cw, tu, tv)]
+        poly = []
+        for k in range(3):
+            b = (k + 1) % 3
+            if inside[k]:
+                poly.append((cx[k], cy[k], cz[k], cw[k], tu[k], tv[k]))
+            if inside[k] != inside[b]:
+                i, o = (k, b) if inside[k] else (b, k)   # from the inside corner towards the outside one
+                t = d[i] / (d[i] - d[o])
+                w = cw[i] + (cw[o] - cw[i]) * t
+                poly.append((cx[i] + (cx[o] - cx[i]) * t, cy[i] + (cy[o] - cy[i]) * t, -w, w, tu[i] + (tu[o] - tu[i]) * t,
+                             tv[i] + (tv[o] - tv[i]) * t))
     out = []
     for a_, b_, c_ in ((0, 1, 2), (0, 2, 3))[:len(poly) - 2]:
-        out.append(tuple(np.array([poly[a_][j], poly[b_][j], poly[c_][j]], f32) for j in range(6)))
+        out.append(tuple(np.array([poly[a_][j], poly[b_][j], poly[c_][j]], F) for j in range(6)))
     return out
 
 
-def _raster(zbuf, levels, width, height, cx, cy, cz, cw, tu, tv):
-    tw, th = f32(levels[0].shape[1]), f32(levels[0].shape[0])
-    nlev = len(levels)
-    if True:
+def setup(width, height, cx, cy, cz, cw):
+    """tri_setup for one piece -> dict with status (SETUP_STATUS) and, when kept, the window corners xw / yw / zw, iw = 1 / cw, area,
+    inv_area, the edges ex / ey (edge k opposite corner k) with their ownership, and the pixel box x_lo .. y_hi."""
+    F = cx.dtype.type
+    with np.errstate(all="ignore"):
         if not (cw > 0).all():
-            return
+            return {"status": "cw"}
         if ((cx < -cw).all() or (cx > cw).all() or (cy < -cw).all() or (cy > cw).all() or (cz < -cw).all() or (cz > cw).all()):
-            return
-        xw = (cx / cw * f32(0.5) + f32(0.5)) * f32(width)
-        yw = (cy / cw * f32(0.5) + f32(0.5)) * f32(height)
-        zw = cz / cw * f32(0.5) + f32(0.5)
-        iw = f32(1.0) / cw
+            return {"status": "plane"}
+        xw = (cx / cw * F(0.5) + F(0.5)) * F(width)
+        yw = (cy / cw * F(0.5) + F(0.5)) * F(height)
+        zw = cz / cw * F(0.5) + F(0.5)
+        iw = F(1.0) / cw
         area = (xw[1] - xw[0]) * (yw[2] - yw[0]) - (xw[2] - xw[0]) * (yw[1] - yw[0])
+        t = {"status": "area", "xw": xw, "yw": yw, "zw": zw, "iw": iw, "area": area}
         if not area > 0:
-            return
-        x_lo = max(0, int(np.ceil(xw.min() - f32(0.5))))
-        x_hi = min(width - 1, int(np.floor(xw.max() - f32(0.5))))
-        y_lo = max(0, int(np.ceil(yw.min() - f32(0.5))))
-        y_hi = min(height - 1, int(np.floor(yw.max() - f32(0.5))))
+            return t
+        # (fminf / fmaxf: a NaN operand is dropped; no corner is NaN here, the area would be)
+        x_lo = max(0, int(sat_int(np.ceil(np.fmin.reduce(xw) - F(0.5)))))
+        x_hi = min(width - 1, int(sat_int(np.floor(np.fmax.reduce(xw) - F(0.5)))))
+        y_lo = max(0, int(sat_int(np.ceil(np.fmin.reduce(yw) - F(0.5)))))
+        y_hi = min(height - 1, int(sat_int(np.floor(np.fmax.reduce(yw) - F(0.5)))))
+        t.update(status="box", x_lo=x_lo, x_hi=x_hi, y_lo=y_lo, y_hi=y_hi)
         if x_lo > x_hi or y_lo > y_hi:
-            return
-        inv_area = f32(1.0) / area
-        ex = np.array([xw[(k + 2) % 3] - xw[(k + 1) % 3] for k in range(3)], f32)
-        ey = np.array([yw[(k + 2) % 3] - yw[(k + 1) % 3] for k in range(3)], f32)
+            return t
+        ex = np.array([xw[(k + 2) % 3] - xw[(k + 1) % 3] for k in range(3)], F)
+        ey = np.array([yw[(k + 2) % 3] - yw[(k + 1) % 3] for k in range(3)], F)
         own = [bool(ey[k] < 0 or (ey[k] == 0 and ex[k] < 0)) for k in range(3)]
-        yy, xx = np.mgrid[y_lo:y_hi + 1, x_lo:x_hi + 1]
-        fxp = xx.astype(f32) + f32(0.5)
-        fyp = yy.astype(f32) + f32(0.5)
+        t.update(status="kept", ex=ex, ey=ey, own=own, inv_area=F(1.0) / area)
+    return t
 
-        def weights(px, py):
-            return [(ex[k] * (py - yw[(k + 1) % 3]) - ey[k] * (px - xw[(k + 1) % 3])) * inv_area for k in range(3)]
 
-        # coverage and depth: barycentric weights per pixel (tri_cover, nmi_mesh.hip)
-        b = weights(fxp, fyp)
+def _weights(t, px, py):
+    xw, yw, ex, ey, inv_area = t["xw"], t["yw"], t["ex"], t["ey"], t["inv_area"]
+    with np.errstate(all="ignore"):
+        return [(ex[k] * (py - yw[(k + 1) % 3]) - ey[k] * (px - xw[(k + 1) % 3])) * inv_area for k in range(3)]
+
+
+def cover(t, region=None):
+    """tri_cover over the piece's box, or over region = (x_lo, x_hi, y_lo, y_hi) (pixels outside the piece's own box are not
+    inside) -> dict: xx, yy, the three edge values b (barycentric weights), inside, z, depth (24 bits)."""
+    F = t["xw"].dtype.type
+    x_lo, x_hi, y_lo, y_hi = region if region is not None else (t["x_lo"], t["x_hi"], t["y_lo"], t["y_hi"])
+    yy, xx = np.mgrid[y_lo:y_hi + 1, x_lo:x_hi + 1]
+    fxp = xx.astype(F) + F(0.5)
+    fyp = yy.astype(F) + F(0.5)
+    b = _weights(t, fxp, fyp)
+    zw = t["zw"]
+    with np.errstate(all="ignore"):
         zz = (b[0] * zw[0] + b[1] * zw[1]) + b[2] * zw[2]
-        inside = np.ones(fxp.shape, bool)
+        inside = (xx >= t["x_lo"]) & (xx <= t["x_hi"]) & (yy >= t["y_lo"]) & (yy <= t["y_hi"])
         for k in range(3):
-            inside &= (b[k] > 0) | ((b[k] == 0) & own[k])
+            inside &= (b[k] > 0) | ((b[k] == 0) & t["own"][k])
         inside &= (zz >= 0) & (zz <= 1)
-        if not inside.any():
-            return
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            depth = np.minimum((zz * f32(16777215.0) + f32(0.5)).astype(np.uint32), np.uint32(0xFFFFFF))
-        # Visibility: GL_LESS keeps the fragment drawn first among equal depths, and triangles arrive here in draw order, so
-        # a fragment wins only with a strictly smaller depth (the key depth << 40 | triangle << 10 | ... of nmi_mesh.hip).
-        sub = zbuf[y_lo:y_hi + 1, x_lo:x_hi + 1]
-        win = inside & (depth.astype(np.uint64) < (sub >> np.uint64(8)))
-        if not win.any():
-            return
-        # attributes: u/w, v/w and 1/w as planes about the centre of the box's first pixel (tri_planes / shade_pixel)
-        xr, yr = f32(x_lo) + f32(0.5), f32(y_lo) + f32(0.5)
-        b0 = weights(xr, yr)
+        depth = np.minimum(sat_uint(zz * F(16777215.0) + F(0.5)), DEPTH_MAX)
+    return {"xx": xx, "yy": yy, "b": b, "inside": inside, "z": zz, "depth": depth}
+
+
+def planes(t, tu, tv):
+    """tri_planes: S = u/w, R = v/w, Q = 1/w as (value at the centre of the box's first pixel, d/dx, d/dy)."""
+    F = t["xw"].dtype.type
+    ex, ey, inv_area, iw = t["ex"], t["ey"], t["inv_area"], t["iw"]
+    xr, yr = F(t["x_lo"]) + F(0.5), F(t["y_lo"]) + F(0.5)
+    with np.errstate(all="ignore"):
+        b0 = _weights(t, xr, yr)
         bx = [(-ey[k]) * inv_area for k in range(3)]
         by = [ex[k] * inv_area for k in range(3)]
         sc = [tu[k] * iw[k] for k in range(3)]
@@ -159,34 +213,134 @@ def _raster(zbuf, levels, width, height, cx, cy, cz, cw, tu, tv):
             return ((b0[0] * g[0] + b0[1] * g[1]) + b0[2] * g[2], (bx[0] * g[0] + bx[1] * g[1]) + bx[2] * g[2],
                     (by[0] * g[0] + by[1] * g[1]) + by[2] * g[2])
 
-        (s0, sx, sy), (r0, rx, ry), (q0, qx, qy) = plane(sc), plane(rc), plane(iw)
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            dx, dy = fxp - xr, fyp - yr
-            S = (s0 + sx * dx) + sy * dy
-            R = (r0 + rx * dx) + ry * dy
-            Q = (q0 + qx * dx) + qy * dy
-            iq, iqx, iqy = f32(1.0) / Q, f32(1.0) / (Q + qx), f32(1.0) / (Q + qy)
-            u, v = S * iq, R * iq
-            ux, vx = (S + sx) * iqx, (R + rx) * iqx
-            uy, vy = (S + sy) * iqy, (R + ry) * iqy
-            dudx, dvdx, dudy, dvdy = (ux - u) * tw, (vx - v) * th, (uy - u) * tw, (vy - v) * th
-            rho2 = np.maximum(dudx * dudx + dvdx * dvdx, dudy * dudy + dvdy * dvdy)
-            lam = f32(0.5) * np.log2(rho2).astype(f32)      # log2 of the longer footprint axis = half the log2 of its square
-            luma = _bilinear(levels[0], u, v)
-            mini = lam > 0
-            if mini.any():
-                lc = np.minimum(lam, f32(nlev - 1))
-                l0 = np.floor(lc).astype(np.int64)
-                fr = lc - l0.astype(f32)
-                for L in np.unique(l0[mini & win]):
-                    sel = mini & (l0 == L)
-                    L1 = min(int(L) + 1, nlev - 1)
-                    s0_ = _bilinear(levels[int(L)], u, v)
-                    s1_ = _bilinear(levels[L1], u, v)
-                    luma = np.where(sel, s0_ + (s1_ - s0_) * fr, luma)
-            colour = (np.clip(luma, 0, 1) * f32(255.0) + f32(0.5)).astype(np.uint32)
-        frag = (depth.astype(np.uint64) << np.uint64(8)) | colour.astype(np.uint64)
-        sub[win] = frag[win]
+        return xr, yr, plane(sc), plane(rc), plane(iw)
+
+
+def shade(t, tu, tv, levels, xx, yy):
+    """shade_pixel at the pixels (xx, yy) of a kept piece -> dict: u, v, Q, Qx, Qy, rho2, lam (lambda; meaningful where rho2 > 1),
+    l0, l1 (the level pair; 0, 0 when magnified), s0, s1 (the two levels' samples) and f (the blend), luma = s0 + (s1 - s0) f (before
+    clamping and rounding), grey."""
+    F = t["xw"].dtype.type
+    tw, th = F(levels[0].shape[1]), F(levels[0].shape[0])
+    nlev = len(levels)
+    xr, yr, (s0, sx, sy), (r0, rx, ry), (q0, qx, qy) = planes(t, tu, tv)
+    fxp = np.asarray(xx).astype(F) + F(0.5)
+    fyp = np.asarray(yy).astype(F) + F(0.5)
+    with np.errstate(all="ignore"):
+        dx, dy = fxp - xr, fyp - yr
+        S = (s0 + sx * dx) + sy * dy
+        R = (r0 + rx * dx) + ry * dy
+        Q = (q0 + qx * dx) + qy * dy
+        Qx, Qy = Q + qx, Q + qy
+        iq, iqx, iqy = F(1.0) / Q, F(1.0) / Qx, F(1.0) / Qy     # (warp_rcp_fast gives the division's bits)
+        u, v = S * iq, R * iq
+        ux, vx = (S + sx) * iqx, (R + rx) * iqx
+        uy, vy = (S + sy) * iqy, (R + ry) * iqy
+        dudx, dvdx, dudy, dvdy = (ux - u) * tw, (vx - v) * th, (uy - u) * tw, (vy - v) * th
+        rho2 = np.fmax(dudx * dudx + dvdx * dvdx, dudy * dudy + dvdy * dvdy)   # fmaxf: a NaN operand is dropped
+        mini = rho2 > 1                                     # false for NaN: the magnification branch
+        lam = F(0.5) * np.log2(np.where(mini, rho2, F(1.0))).astype(F)   # log2 of the longer footprint axis = half the log2 of its square
+        luma = _bilinear(levels[0], u, v, F)
+        l0 = np.zeros(np.shape(luma), np.int64)
+        l1 = l0.copy()
+        s0_, s1_, fr = luma, luma, np.zeros(np.shape(luma), F)
+        if mini.any():
+            lc = np.fmin(np.fmax(lam, F(0.0)), F(nlev - 1))
+            l0 = np.where(mini, sat_int(np.floor(lc)), 0)
+            l1 = np.where(mini, np.minimum(l0 + 1, nlev - 1), 0)
+            fr = lc - l0.astype(F)
+            for L in np.unique(l0[mini]):
+                sel = mini & (l0 == L)
+                a = _bilinear(levels[int(L)], u, v, F)
+                b = _bilinear(levels[min(int(L) + 1, nlev - 1)], u, v, F)
+                luma = np.where(sel, a + (b - a) * fr, luma)
+                s0_, s1_ = np.where(sel, a, s0_), np.where(sel, b, s1_)
+            fr = np.where(mini, fr, F(0.0))
+        grey = sat_uint(np.fmin(np.fmax(luma, F(0.0)), F(1.0)) * F(255.0) + F(0.5))   # fminf(fmaxf(NaN, 0), 1) = 0
+    return {"u": u, "v": v, "Q": Q, "Qx": Qx, "Qy": Qy, "rho2": rho2, "lam": lam, "l0": l0, "l1": l1, "s0": s0_, "s1": s1_, "f": fr,
+            "luma": luma, "grey": grey}
+
+
+def pieces(xyz, uv, mvp_colmajor, width, height, F=f32):
+    """Every (triangle, piece) of one view in draw order -> list of dicts: tri, piece, tu, tv, d (the triangle's near-plane
+    distances), n_in, and the set-up result (setup)."""
+    cx, cy, cz, cw = clip_coords(xyz, mvp_colmajor, F)
+    T = np.asarray(uv, f32).reshape(-1, 3, 2).astype(F)
+    out = []
+    for tri in range(cx.shape[0]):
+        with np.errstate(all="ignore"):
+            d = cz[tri] + cw[tri]
+        n_in = int((d >= 0).sum())
+        for sub, c in enumerate(_clip_near(cx[tri], cy[tri], cz[tri], cw[tri], T[tri, :, 0], T[tri, :, 1])):
+            t = setup(width, height, *c[:4])
+            out.append({"tri": tri, "piece": sub, "tu": c[4], "tv": c[5], "clip": c[:4], "d": d, "n_in": n_in, "t": t})
+    return out
+
+
+def render_staged(xyz, uv, levels, mvp_colmajor, width, height, F=f32, keep_cover=False):
+    """One view, every stage kept -> dict: pieces (see pieces(); with keep_cover each kept piece's cover() as "cover"), and per
+    pixel [H, W]: nfrag (fragments that passed coverage and the depth clip), tri / piece (the winner; -1: none), depth
+    (EMPTY_DEPTH: none), and the winner's u, v, rho2, lam, l0, l1, s0, s1, f, luma, grey (255 where no fragment won)."""
+    ps = pieces(xyz, uv, mvp_colmajor, width, height, F)
+    depth = np.full((height, width), EMPTY_DEPTH, np.int64)
+    tri = np.full((height, width), -1, np.int64)
+    piece = np.full((height, width), -1, np.int64)
+    nfrag = np.zeros((height, width), np.int64)
+    for i, p in enumerate(ps):
+        t = p["t"]
+        if t["status"] != "kept":
+            continue
+        c = cover(t)
+        if keep_cover:
+            p["cover"] = c
+        if not c["inside"].any():
+            continue
+        box = (slice(t["y_lo"], t["y_hi"] + 1), slice(t["x_lo"], t["x_hi"] + 1))
+        nfrag[box] += c["inside"]
+        # GL_LESS keeps the fragment drawn first among equal depths, and pieces arrive in draw order: a fragment wins only with
+        # a strictly smaller depth (the key depth << 40 | triangle << 10 | piece << 9 | slot of nmi_mesh.hip)
+        win = c["inside"] & (c["depth"] < depth[box])
+        depth[box] = np.where(win, c["depth"], depth[box])
+        tri[box] = np.where(win, p["tri"], tri[box])
+        piece[box] = np.where(win, i, piece[box])      # (index into ps for now)
+    out = {k: np.full((height, width), np.nan, F) for k in ("u", "v", "rho2", "lam", "luma", "s0", "s1", "f")}
+    out.update({k: np.zeros((height, width), np.int64) for k in ("l0", "l1")})
+    grey = np.full((height, width), 255, np.int64)
+    for i in np.unique(piece[piece >= 0]):
+        p = ps[int(i)]
+        yy, xx = np.nonzero(piece == i)
+        s = shade(p["t"], p["tu"], p["tv"], levels, xx, yy)
+        for k in out:
+            out[k][yy, xx] = s[k]
+        grey[yy, xx] = s["grey"]
+    sub = np.array([p["piece"] for p in ps] + [-1], np.int64)
+    out.update(pieces=ps, nfrag=nfrag, tri=tri, piece=sub[piece], piece_index=piece, depth=depth, grey=grey.astype(np.uint8),
+               covered=tri >= 0)
+    return out
+
+
+def render_mesh_f64(xyz, uv, levels, mvp_colmajor, width, height, keep_cover=False):
+    """The float64 model of the same rule: render_staged with every operation in float64 on the fp32 inputs."""
+    return render_staged(xyz, uv, levels, mvp_colmajor, width, height, np.float64, keep_cover)
+
+
+def render_mesh(xyz, uv, levels, mvp_colmajor, width, height):
+    """One view -> uint8 [H, W], bottom-up rows, background 255."""
+    return render_staged(xyz, uv, levels, mvp_colmajor, width, height)["grey"]
+
+
+def _raster(zbuf, levels, width, height, cx, cy, cz, cw, tu, tv):
+    """One piece into zbuf (uint64 [H, W]: depth << 8 | grey; empty 0xFFFFFFFFFF), as render_staged resolves it."""
+    t = setup(width, height, cx, cy, cz, cw)
+    if t["status"] != "kept":
+        return
+    c = cover(t)
+    sub = zbuf[t["y_lo"]:t["y_hi"] + 1, t["x_lo"]:t["x_hi"] + 1]
+    win = c["inside"] & (c["depth"].astype(np.uint64) < (sub >> np.uint64(8)))
+    if not win.any():
+        return
+    grey = shade(t, tu, tv, levels, c["xx"][win], c["yy"][win])["grey"]
+    sub[win] = (c["depth"][win].astype(np.uint64) << np.uint64(8)) | grey.astype(np.uint64)
 
 
 def render_stack(xyz, uv, levels, mvps, width, height):

@@ -63,14 +63,18 @@ struct MeshTexture {
     long long off[16];
 };
 
-// x mod n for an integer-valued x (|x| < 2^24) and 0 < n < 2^24, all in fp32: the quotient estimate may be one off, the
+// x mod n for an integer-valued x with |x| < 2^24 - n and 0 < n < 2^24, all in fp32: the quotient estimate may be one off, the
 // two corrections make the result the true remainder in [0, n) -- what an integer modulo (20+ instructions, four per
-// texture sample) would give.
+// texture sample) would give.  Beyond that domain (a finite uv of tens of millions of texture widths, inf, NaN)
+// the quotient's rounding error exceeds what two corrections mend, so the result is CLAMPED to [0, n - 1]: there it is some
+// texel of the level, no longer the remainder, and never an index outside the level.  In the domain r is already an integer
+// in [0, n - 1] and the clamp changes no bit; fmaxf(NaN, 0) is 0.
 __device__ __forceinline__ int wrap_index(float x, float n, float inv_n)
 {
     float r = x - floorf(x * inv_n) * n;
     r = r < 0.0f ? r + n : r;
     r = r >= n ? r - n : r;
+    r = fminf(fmaxf(r, 0.0f), n - 1.0f);
     return (int)r;
 }
 
