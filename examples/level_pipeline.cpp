@@ -99,16 +99,17 @@ static float surface_grey(float u, float v, float n)
 // --write-files DIR: the synthetic map as the files the reference's loaders read (OBJ + BMP, or XYZ + offset) and a settings file
 // in the reference's YAML format that names them.  Numbers are printed with enough digits to come back bit for bit.
 static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, const std::vector<float> &xyz, const std::vector<float> &attr,
-                        const std::vector<uint8_t> &rgb, int tw, int th)
+                        const std::vector<uint8_t> &rgb, int tw, int th, int factor)
 {
     const std::string d = std::string(dir) + "/";
     FILE *y = fopen((d + "settings.yaml").c_str(), "w");
     if (!y) return false;
-    fprintf(y, "%%YAML:1.0\n\nCamera.fx: %.17g\nCamera.fy: %.17g\nCamera.cx: %.17g\nCamera.cy: %.17g\nCamera.Width: %d\nCamera.Height: %d\n\n", FX, FY, CX,
-            CY, W, H);
+    // (factor > 1, --reduce: the full-size camera's settings, which nmi_config_reduce brings back to these)
+    fprintf(y, "%%YAML:1.0\n\nCamera.fx: %.17g\nCamera.fy: %.17g\nCamera.cx: %.17g\nCamera.cy: %.17g\nCamera.Width: %d\nCamera.Height: %d\n\n", FX * factor,
+            FY * factor, factor > 1 ? factor * (CX + 0.5) - 0.5 : CX, factor > 1 ? factor * (CY + 0.5) - 0.5 : CY, W * factor, H * factor);
     fprintf(y, "NMI.Treshold: 0.05\nNMI.SynthNumX: 3\nNMI.SynthNumY: 3\nNMI.SynthNumZ: 3\nNMI.WarpNumX: 3\nNMI.WarpNumY: 3\nNMI.WarpNumZ: 3\n");
     fprintf(y, "NMI.SynthStepX: 0.2\nNMI.SynthStepY: 0.2\nNMI.SynthStepZ: 0.5\nNMI.WarpStepX: 0.02\nNMI.WarpStepY: 0.02\nNMI.WarpStepZ: 0.05\n\n");
-    fprintf(y, "NMI.Render.PointSize: 3.0\nNMI.Render.NearPlane: 5.0\nNMI.Render.FarPlane: 30.0\n");
+    fprintf(y, "NMI.Render.PointSize: %.1f\nNMI.Render.NearPlane: 5.0\nNMI.Render.FarPlane: 30.0\n", 3.0 * factor);
     if (mesh)
         fprintf(y, "NMI.Render.Object: \"map.obj\"\nNMI.Render.Texture: \"map.bmp\"\n");
     else
@@ -160,7 +161,7 @@ static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, co
 int main(int argc, char **argv)
 {
     // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered] [--color rgb|bgr|rgba|bgra]
-    //                       [--write-files DIR | --files DIR]
+    //                       [--reduce F] [--write-files DIR | --files DIR]
     //   --mesh: nmi_prop_RENDER 1, the reference's default render mode: the same surface as NX x NY quads = 2 NX NY textured
     //           triangles, default 300x200 = 120,000;  --density: points per pixel of a view along each axis (cloud; default 0.9)
     //   --masked: the frame's bottom sixth is a "hood" (a flat grey band over the scene); a frame mask excludes it and the levels
@@ -170,6 +171,10 @@ int main(int argc, char **argv)
     //   --color FMT: the camera frame is a colour image in that format (a smooth chroma pattern over its grey values, so that the
     //           channel order matters), in rows padded to 256 bytes; the levels read it raw and turn it grey on the device
     //           (nmi_level_set_frame_format).  With --files the order (RGB or BGR) is the settings file's Camera.RGB.
+    //   --reduce F: the camera is F (2..4) times the search size in each direction: its frame is rendered at F * 848 x F * 480 (in
+    //           colour with --color) and the levels reduce it to the search size on the device (nmi_level_set_frame_reduction).
+    //           With --write-files the settings file describes that full-size camera; with --files it is read as such and brought
+    //           to the search size by nmi_config_reduce.
     //   --write-files DIR: write the map and a settings file into DIR and stop (no GPU needed)
     //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names
     //           (nmi_config_load, nmi_map_load_obj / _bmp / _xyz) instead of building them in memory
@@ -178,6 +183,7 @@ int main(int argc, char **argv)
     const char *write_dir = nullptr, *read_dir = nullptr;
     bool masked = false, covered = false;
     int color_bpp = 0, color_rgb = 0;  // --color: 3 or 4 bytes per pixel, RGB (1) or BGR (0) order
+    int reduce = 1;                    // --reduce: the camera frame is this many times the search size
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mesh")) {
             mesh_nx = 300, mesh_ny = 200;
@@ -192,6 +198,12 @@ int main(int argc, char **argv)
             color_rgb = c[0] == 'r';
             if (!color_bpp) {
                 fprintf(stderr, "--color takes rgb, bgr, rgba or bgra\n");
+                return 2;
+            }
+        } else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) {
+            reduce = atoi(argv[++i]);
+            if (reduce < 2 || reduce > 4) {
+                fprintf(stderr, "--reduce takes 2, 3 or 4\n");
                 return 2;
             }
         } else if (!strcmp(argv[i], "--density") && i + 1 < argc) {
@@ -218,7 +230,8 @@ int main(int argc, char **argv)
     unsigned s = 2468u;
     if (read_dir) {
         const std::string d = std::string(read_dir) + "/";
-        const int rc = nmi_config_load((d + "settings.yaml").c_str(), &cfg);
+        int rc = nmi_config_load((d + "settings.yaml").c_str(), &cfg);
+        if (rc == 0 && reduce > 1) rc = nmi_config_reduce(&cfg, reduce);  // the file describes the full-size camera
         if (rc != 0 || cfg.width != W || cfg.height != H) {
             fprintf(stderr, "settings.yaml: rc %d, %d x %d (this program is built for %d x %d)\n", rc, cfg.width, cfg.height, W, H);
             return 1;
@@ -286,7 +299,7 @@ int main(int argc, char **argv)
             }
     }
     if (write_dir) {
-        const bool ok = write_files(write_dir, mesh, mesh_nx, mesh_ny, xyz, red, rgb, tw, th);
+        const bool ok = write_files(write_dir, mesh, mesh_nx, mesh_ny, xyz, red, rgb, tw, th, reduce);
         printf("%s\n", ok ? "FILES WRITTEN" : "FILES FAILED");
         return ok ? 0 : 1;
     }
@@ -322,14 +335,37 @@ int main(int argc, char **argv)
         const float up[3] = {Twc0[1], Twc0[5], Twc0[9]};
         const float zero[3] = {0, 0, 0};
         float mvp[16];
-        CHECK_NMI(nmi_render_mvp(&p.rp, pos, look, up, zero, mvp));
+        // The camera's frame is CW x CH: the search size, or (--reduce) F times it, rendered by a context of that size through the
+        // full-size camera model -- the inverse of nmi_config_reduce: fx, fy and the point size times F, cx = F (cx' + 0.5) - 0.5.
+        const int F = reduce, CW = F * W, CH = F * H;
+        nmi_render_params crp = p.rp;
+        nmi_ctx *cctx = ctx;
+        nmi_texture *ctex = tex;
+        uint8_t *d_shot = d_tmp;
+        if (F > 1) {
+            crp.fx *= F, crp.fy *= F, crp.point_size *= F;
+            crp.cx = F * (crp.cx + 0.5) - 0.5, crp.cy = F * (crp.cy + 0.5) - 0.5;
+            nmi_params cprm;
+            CHECK_NMI(nmi_params_default(&cprm, CW, CH));
+            CHECK_NMI(nmi_create(&cprm, &cctx));
+            if (mesh) CHECK_NMI(nmi_texture_create(cctx, rgb.data(), tw, th, &ctex));
+            CHECK_HIP(hipMalloc((void **)&d_shot, (size_t)CW * CH));
+        }
+        CHECK_NMI(nmi_render_mvp(&crp, pos, look, up, zero, mvp));
         if (mesh)
-            CHECK_NMI(nmi_render_mesh(ctx, d_xyz, d_red, n_prims, tex, mvp, 1, d_tmp));
+            CHECK_NMI(nmi_render_mesh(cctx, d_xyz, d_red, n_prims, ctex, mvp, 1, d_shot));
         else
-            CHECK_NMI(nmi_render_points(ctx, d_xyz, d_red, n_prims, mvp, 1, p.rp.point_size, d_tmp));
-        CHECK_NMI(nmi_synchronize(ctx));
-        std::vector<uint8_t> img((size_t)W * H), frame((size_t)W * H);
-        CHECK_HIP(hipMemcpy(img.data(), d_tmp, img.size(), hipMemcpyDeviceToHost));
+            CHECK_NMI(nmi_render_points(cctx, d_xyz, d_red, n_prims, mvp, 1, crp.point_size, d_shot));
+        CHECK_NMI(nmi_synchronize(cctx));
+        std::vector<uint8_t> img((size_t)CW * CH), frame((size_t)CW * CH);
+        CHECK_HIP(hipMemcpy(img.data(), d_shot, img.size(), hipMemcpyDeviceToHost));
+        if (F > 1) {
+            (void)hipFree(d_shot);
+            if (mesh) nmi_texture_destroy(ctex);
+            nmi_destroy(cctx);
+        }
+        // (from here on W and H are the camera frame's; the search size is SW x SH)
+        const int SW = ::W, SH = ::H, W = CW, H = CH;
         unsigned q = 97531u;
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
@@ -343,15 +379,24 @@ int main(int argc, char **argv)
             }
         if (masked) {
             // the hood: a flat grey band over the bottom sixth of the frame, and the frame mask that excludes it
-            const int hood = H - H / 6;
-            std::vector<uint8_t> usable((size_t)W * H, 1);
-            for (int y = hood; y < H; ++y)
-                for (int x = 0; x < W; ++x) frame[(size_t)y * W + x] = 60, usable[(size_t)y * W + x] = 0;
+            // (the frame mask is always of the search size; a full-size frame's hood covers the same rows, F source rows each)
+            const int hood = SH - SH / 6;
+            std::vector<uint8_t> usable((size_t)SW * SH, 1);
+            for (int y = hood; y < SH; ++y)
+                for (int x = 0; x < SW; ++x) usable[(size_t)y * SW + x] = 0;
+            for (int y = hood * F; y < H; ++y)
+                for (int x = 0; x < W; ++x) frame[(size_t)y * W + x] = 60;
             CHECK_HIP(hipMalloc((void **)&d_hood, usable.size()));
             CHECK_HIP(hipMemcpy(d_hood, usable.data(), usable.size(), hipMemcpyHostToDevice));
-            printf("masked levels: rows %d..%d of the frame are a hood, excluded by the frame mask\n", hood, H - 1);
+            printf("masked levels: rows %d..%d of the frame are a hood, excluded by the frame mask\n", hood, SH - 1);
         }
-        CHECK_HIP(hipMemcpy(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice));
+        if (F > 1 && !color_bpp) {  // the full-size grey frame is what the levels read
+            CHECK_HIP(hipMalloc((void **)&d_color, frame.size()));
+            CHECK_HIP(hipMemcpy(d_color, frame.data(), frame.size(), hipMemcpyHostToDevice));
+            printf("full-size frame: GRAY, %d x %d, reduced %dx to %d x %d on the device by every replay\n", W, H, F, SW, SH);
+        } else if (F == 1) {
+            CHECK_HIP(hipMemcpy(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice));
+        }
         if (color_bpp) {
             // The camera's colour frame: R and B swing +-50 around the grey value (slowly across and down the frame), G makes up the
             // rest, so that the rule of nmi_gray_frame gives about the grey frame back -- and a wrong channel order does not.
@@ -373,8 +418,12 @@ int main(int argc, char **argv)
             CHECK_HIP(hipMalloc((void **)&d_color, col.size()));
             CHECK_HIP(hipMemcpy(d_color, col.data(), col.size(), hipMemcpyHostToDevice));
             static const char *names[] = {"GRAY", "BGR", "RGB", "BGRA", "RGBA"};
-            printf("colour frame: %s, %d x %d in rows of %lld bytes, turned grey on the device by every replay\n", names[color_format], W, H,
-                   (long long)color_pitch);
+            if (F > 1)
+                printf("full-size colour frame: %s, %d x %d in rows of %lld bytes, turned grey and reduced %dx to %d x %d on the device by every replay\n",
+                       names[color_format], W, H, (long long)color_pitch, F, SW, SH);
+            else
+                printf("colour frame: %s, %d x %d in rows of %lld bytes, turned grey on the device by every replay\n", names[color_format], W, H,
+                       (long long)color_pitch);
         }
     }
     if (covered) {
@@ -397,12 +446,15 @@ int main(int argc, char **argv)
         CHECK_HIP(hipMemcpy(d_xyz, xyz.data(), kept * per * sizeof(float), hipMemcpyHostToDevice));
         CHECK_HIP(hipMemcpy(d_red, red.data(), kept * per_attr * sizeof(float), hipMemcpyHostToDevice));
     }
-    const uint8_t *d_camera = d_color ? d_color : d_frame;  // what the levels read: the colour frame, raw, when there is one
+    const uint8_t *d_camera = d_color ? d_color : d_frame;  // what the levels read: the colour or full-size frame, raw, when there is one
     if (mesh)
         CHECK_NMI(nmi_level_create_mesh(ctx, d_xyz, d_red, n_prims, tex, d_camera, 27, 27, &p.level));
     else
         CHECK_NMI(nmi_level_create(ctx, d_xyz, d_red, n_prims, d_camera, 27, 27, p.rp.point_size, &p.level));
-    if (d_color) CHECK_NMI(nmi_level_set_frame_format(p.level, color_format, color_pitch));  // every replay: colour -> grey node
+    if (d_color && reduce > 1)  // every replay: full-size (colour) frame -> grey frame of the search size, one node
+        CHECK_NMI(nmi_level_set_frame_reduction(p.level, reduce, color_format, color_pitch));
+    else if (d_color)
+        CHECK_NMI(nmi_level_set_frame_format(p.level, color_format, color_pitch));  // every replay: colour -> grey node
     if (covered)
         CHECK_NMI(nmi_level_set_coverage(p.level, 1, d_hood));  // every replay: coverage + warp masks, covered search
     else if (masked)

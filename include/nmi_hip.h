@@ -12,7 +12,8 @@
  *   image           uint8 [height][width], contiguous, row stride = width
  *                   (cv::cuda::createContinuous CV_8UC1, Thirdparty/Localization/image.cpp:67).
  *                   The camera frame alone may also come in colour or with a row stride: nmi_gray_frame,
- *                   nmi_level_set_frame_format, nmi_stream_set_frame_format (NMI_FRAME_*).
+ *                   nmi_level_set_frame_format, nmi_stream_set_frame_format (NMI_FRAME_*); and at 2, 3 or 4 times the
+ *                   context's size: nmi_reduce_frame, nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction.
  *   render          same shape; stored bottom-up when nmi_params.render_bottom_up = 1, which is how
  *                   the reference samples the GL texture (NMI.cu:82).
  *   render_stack    uint8 [S][height][width],  s = (sZ*nSy + sY)*nSx + sX
@@ -41,7 +42,8 @@ extern "C" {
                                  nmi_stream_submit_masked_block, nmi_stream_submit_covered, nmi_stream_submit_covered_block,
                                  nmi_stream_copy_counts, and after nmi_undistort_frame,
                                  nmi_level_set_distortion, nmi_stream_set_distortion, and after nmi_gray_frame,
-                                 nmi_level_set_frame_format, nmi_stream_set_frame_format */
+                                 nmi_level_set_frame_format, nmi_stream_set_frame_format, and after nmi_reduce_frame,
+                                 nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -320,6 +322,37 @@ int nmi_undistort_frame(nmi_ctx *ctx, const double K[9], const float dist[5] /* 
 int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, uint8_t *d_gray /* [H][W] */);
 
 /*
+ * Full-size camera frames (new).  The reference searches at a fraction of the camera's size: "ZU-MAV 1920x1080 frame
+ * downsampled to 960x540" (BASELINE.json configs[2]; Examples/Monocular/ETH_small.yaml:23-24).  nmi_reduce_frame makes the grey
+ * frame d_gray [H][W] of the search size -- H and W are the context's -- from a source of f * H rows of f * W pixels in an
+ * NMI_FRAME_* format, f = factor = 1 .. 4.  Row y is at d_src + y * pitch; pitch = 0 means dense, f * W * bytes per pixel.  A
+ * source with spare columns or rows is cropped by passing its real pitch: 1241x376 at f = 2 gives 620x188.
+ * Each source pixel is first turned grey by nmi_gray_frame's rule (GRAY: the byte itself); output pixel (x, y) is then the box
+ * average of the f x f grey values at (f x .., f y ..), rounded from their integer sum s:
+ *   f = 1   s (the call is nmi_gray_frame)
+ *   f = 2   (s + 2) >> 2
+ *   f = 3   (s + 4) / 9
+ *   f = 4   q + (r > 8 || (r == 8 && (q & 1))),  q = s >> 4, r = s & 15    (round half to even)
+ * each within 0.5 of the exact mean.  They are the integer forms of what cv::resize(INTER_AREA) is understood to compute at
+ * integer scales: its 2x2 fast path for f = 2 (halves round up), rint(fl32(s) * fl32(1 / f^2)) for f = 3 and 4, which they
+ * equal for every possible s.  Parity with any particular OpenCV build is unpinned, as for the warp, the undistortion and the
+ * colour rule.
+ * Mask: d_mask[y][x] = 1 where all f x f bytes of d_src_mask (dense uint8 [f*H][f*W]) are nonzero, else 0; written only when
+ * both mask pointers are given.
+ * Enqueued on the context's stream.  NMI_ERR_INVALID_ARGUMENT, before anything is enqueued and with the outputs untouched: a NULL
+ * ctx, d_src or d_gray, an unknown format, a factor outside 1 .. 4, pitch < 0 or 0 < pitch < f * W * bytes per pixel, exactly
+ * one of the two mask pointers given, an output overlapping the source's bytes (rows 0 .. f*H-1 and the bytes between them),
+ * the source mask or the other output.
+ * Captured levels: nmi_level_set_frame_reduction.  Streams: nmi_stream_set_frame_reduction.  The search-size camera model of a
+ * full-size settings file: nmi_config_reduce (include/nmi_host.h).
+ * Not covered: non-integer scales, factors above 4, a fused reduce + undistort node, resolution pyramids inside
+ * nmi_relocalize_with_strategy.
+ */
+int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */,
+                     int32_t factor /* 1..4 */, const uint8_t *d_src_mask /* nullable, dense [f*H][f*W] */,
+                     uint8_t *d_gray /* [H][W] */, uint8_t *d_mask /* nullable, [H][W] */);
+
+/*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
  * (Thirdparty/Localization/rendering.hpp:530-630, nmi_prop_RENDER 4, shaders/ShadingWithColor.*) for S camera
  * translations of one pose -- no OpenGL.  nmi_render_mvp builds Projection * glm::lookAt for one view exactly as
@@ -511,6 +544,19 @@ int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[
  * node.  NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, format or pitch as for nmi_gray_frame.
  */
 int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch /* bytes, 0 = dense */);
+/*
+ * Full-size frames.  nmi_level_set_frame_reduction(lv, factor, format, pitch) is nmi_level_set_frame_format with a factor: the
+ * level (any of the four nmi_level_create* forms; plain, masked or covered) reads d_frame in place on every replay as f * H rows
+ * of pitch bytes holding f * W pixels in format.  Factor 1 is that call exactly; of the two calls the later one wins, and
+ * (1, NMI_FRAME_GRAY, 0) turns both off.  A frame mask (nmi_level_set_masks / _set_coverage) stays dense [H][W] at the search
+ * size; with distortion set, K and the mask are those of the reduced frame (nmi_config_reduce gives that K).  Each replay equals
+ * the standalone chain nmi_reduce_frame -> [nmi_undistort_frame] -> the level's chain on the grey frame: winner index and score
+ * bits ==, warps, masks and counts byte-equal.  The graph takes one node that converts and reduces; with distortion a second
+ * one, the undistortion node, reads the reduced frame from a buffer of the level's own (H x W bytes more).  Captures again and
+ * waits for a replay in flight, as the other setters do; set it in any order with masks, coverage and distortion, which keep
+ * it.  NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, factor, format or pitch as for nmi_reduce_frame.
+ */
+int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -607,6 +653,17 @@ int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dis
  * first formatted frame, and 2 x H*W for the grey frames unless undistortion already holds them.
  */
 int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch /* bytes, 0 = dense */);
+/*
+ * Full-size host frames on a stream: nmi_stream_set_frame_reduction is nmi_stream_set_frame_format with a factor (factor 1 is
+ * that call; the later of the two wins; (1, NMI_FRAME_GRAY, 0) turns both off).  After it every frame submission of every kind
+ * reads h_frame as f * H rows of pitch bytes holding f * W pixels in format.  The frame crosses with hipMemcpy2DAsync into a
+ * dense full-size slot (a pair) and is reduced on the compute stream before the warps (and before the undistortion when that is
+ * on: two nodes); a ticket equals a grey ticket on nmi_reduce_frame's frame.  Frame masks stay [H][W].  Tickets submitted before
+ * the call are not affected.  NMI_ERR_INVALID_ARGUMENT as for nmi_level_set_frame_reduction (the stream left as it was).
+ * Memory: 2 x f^2 * W*H * bytes per pixel on the first such frame, and 2 x H*W for the grey frames unless undistortion already
+ * holds them.
+ */
+int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

@@ -132,6 +132,13 @@ int nmi_config_load_distortion(const char *yaml_path, float dist[5]);
  * Tracking.cc.  nmi_config keeps its layout.  Returns as the distortion pair does. */
 int nmi_config_parse_color_order(const char *text, size_t len, int32_t *rgb);
 int nmi_config_load_color_order(const char *yaml_path, int32_t *rgb);
+/* The search-size settings of a full-size camera's (nmi_reduce_frame, nmi_level_set_frame_reduction,
+ * nmi_stream_set_frame_reduction, include/nmi_hip.h; Examples/Monocular/ETH_small.yaml:23-24 searches at 960x540 on a 1920x1080
+ * camera): width and height divided by factor (integer division: spare columns and rows are cropped), fx and fy divided by it,
+ * cx' = (cx + 0.5) / factor - 0.5 and the same for cy -- output pixel i is centred on source coordinate factor * i +
+ * (factor - 1) / 2 -- and render_point_size divided by it.  Everything else, and the layout, unchanged.  Returns 0, or -1 for a
+ * NULL cfg or a factor outside 1 .. 4 (cfg untouched). */
+int nmi_config_reduce(nmi_config *cfg, int32_t factor);
 
 /*
  * Map files (the paths of nmi_config.render_object / render_texture / render_cloud / render_offset), read with the grammar and

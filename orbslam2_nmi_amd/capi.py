@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "nmi_stream_submit_covered_block", "nmi_stream_copy_counts",
     "nmi_undistort_frame", "nmi_level_set_distortion", "nmi_stream_set_distortion",
     "nmi_gray_frame", "nmi_level_set_frame_format", "nmi_stream_set_frame_format",
+    "nmi_reduce_frame", "nmi_level_set_frame_reduction", "nmi_stream_set_frame_reduction",
 )
 
 
@@ -142,6 +143,9 @@ def load_library(build_if_missing=False):
     lib.nmi_gray_frame.argtypes = [vp, vp, i32, C.c_int64, vp]
     lib.nmi_level_set_frame_format.argtypes = [vp, i32, C.c_int64]
     lib.nmi_stream_set_frame_format.argtypes = [vp, i32, C.c_int64]
+    lib.nmi_reduce_frame.argtypes = [vp, vp, i32, C.c_int64, i32, vp, vp, vp]
+    lib.nmi_level_set_frame_reduction.argtypes = [vp, i32, i32, C.c_int64]
+    lib.nmi_stream_set_frame_reduction.argtypes = [vp, i32, i32, C.c_int64]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -535,6 +539,43 @@ class NmiContext:
         if sync:
             self.synchronize()
         return out
+
+    def reduce_frame(self, src, fmt, factor, pitch=0, src_mask=None, out=None, out_mask=None, sync=True):
+        """nmi_reduce_frame: the full-size camera frame src (device uint8 tensor holding factor * H rows of `pitch` bytes, each
+        factor * W pixels in format fmt, FRAME_*; pitch 0 = dense) -> its grey frame at the context's size [H,W] u8: every pixel
+        the rounded box average of factor x factor grey values.  src as for gray_frame, with at least (factor * H - 1) * pitch +
+        factor * W * bytes per pixel bytes.  src_mask: optional device [factor*H, factor*W] uint8 / bool, nonzero = usable; then
+        (frame, mask [H,W] u8: 1 where the whole block is usable) is returned, else the frame alone.  New tensors when out /
+        out_mask are None.  Enqueued on the context's stream."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        f = int(factor)
+        bpp = FRAME_BYTES_PER_PIXEL.get(int(fmt))
+        if bpp is not None and int(pitch) >= 0 and 1 <= f <= 4:
+            need = (f * self.height - 1) * (int(pitch) or f * self.width * bpp) + f * self.width * bpp
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        sm = om = None
+        if src_mask is not None:
+            sm = _dev_mask(src_mask, 2, "src_mask")
+            if 1 <= f <= 4 and tuple(sm.shape) != (f * self.height, f * self.width):
+                raise ValueError(f"src_mask is {tuple(sm.shape)}, the full-size frame is {(f * self.height, f * self.width)}")
+            if out_mask is None:
+                out_mask = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+            om = self._img(out_mask, "out_mask")
+        elif out_mask is not None:
+            raise ValueError("out_mask goes with a src_mask")
+        if out is None:
+            out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        o = self._img(out, "out")
+        self._order_after_torch()
+        self._check(self._lib.nmi_reduce_frame(self._h, src.data_ptr(), int(fmt), int(pitch), f, sm.data_ptr() if sm is not None else None,
+                                               o.data_ptr(), om.data_ptr() if om is not None else None), "nmi_reduce_frame")
+        if sync:
+            self.synchronize()
+        return out if sm is None else (out, out_mask)
 
     def _mask_stack(self, t, what):
         t = _dev_mask(t, 3, what)
@@ -943,6 +984,14 @@ class NmiLevel:
         self.ctx._order_after_torch()
         self.ctx._check(self._lib.nmi_level_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_level_set_frame_format")
 
+    def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
+        """Full-size frame (nmi_level_set_frame_reduction): every replay reads the level's frame in place as factor * H rows of
+        `pitch` bytes (0: dense), each factor * W pixels in format fmt (FRAME_*), and reduces it to the grey frame of the search
+        size on the device (reduce_frame's arithmetic), before the undistortion when set_distortion is on.  Frame masks stay
+        [H,W].  set_frame_format with a factor: the later of the two calls wins; (1, FRAME_GRAY, 0) turns both off."""
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_frame_reduction(self._h, int(factor), int(fmt), int(pitch)), "nmi_level_set_frame_reduction")
+
     def close(self):
         if self._h and self._h.value:
             self._lib.nmi_level_destroy(self._h)
@@ -1071,6 +1120,16 @@ class NmiStream:
         self.ctx._check(self._lib.nmi_stream_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_stream_set_frame_format")
         bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
         w, h = self.ctx.width, self.ctx.height
+        self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
+
+    def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
+        """Full-size host frames (nmi_stream_set_frame_reduction): frames of later submissions, of every kind, are factor * H rows
+        of `pitch` bytes (0: dense), each factor * W pixels in format fmt (FRAME_*), reduced to the grey frame of the search size
+        on the device before their warps.  Frame masks stay [H,W].  set_frame_format with a factor: the later call wins;
+        (1, FRAME_GRAY, 0) turns both off."""
+        self.ctx._check(self._lib.nmi_stream_set_frame_reduction(self._h, int(factor), int(fmt), int(pitch)), "nmi_stream_set_frame_reduction")
+        bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
+        w, h = int(factor) * self.ctx.width, int(factor) * self.ctx.height
         self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
 
     def _frame_ptr(self, frame_host):

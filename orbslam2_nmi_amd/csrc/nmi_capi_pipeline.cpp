@@ -5,6 +5,7 @@
 #include "nmi_ctx.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
+#include "nmi_reduce.h"
 #include "nmi_undistort.h"
 
 using namespace nmi_internal;
@@ -84,6 +85,11 @@ struct nmi_level {
     bool colored = false;
     int32_t frame_format = NMI_FRAME_GRAY;
     int64_t frame_pitch = 0;                    // row bytes (never 0 while colored)
+    // Frame reduction (nmi_level_set_frame_reduction): with frame_factor f > 1 (colored is then set) d_frame is f H rows of
+    // frame_pitch bytes holding f W pixels each, and the conversion node reduces it too: into d_ud, or, distorted, into d_small,
+    // which the undistortion node reads in d_frame's place.
+    int32_t frame_factor = 1;
+    uint8_t *d_small = nullptr;                 // [H][W], allocated by level_capture for a reduced and distorted level
 };
 
 extern "C" {
@@ -96,7 +102,7 @@ int nmi_level_destroy(nmi_level *lv)
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
     void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks,
-                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts, lv->d_ud, lv->d_ud_mask};
+                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts, lv->d_ud, lv->d_ud_mask, lv->d_small};
     for (void *q : dev)
         if (q) (void)hipFree(q);
     void *host[] = {lv->h_mvps, lv->h_coeffs, lv->h_key};
@@ -133,7 +139,9 @@ static int level_capture(nmi_level *lv)
     // stay eligible) and, distorted and masked or covered, its mask.  A frame mask is dense [H][W] in every format.
     const bool distorted = lv->distorted, want_ud_mask = distorted && (lv->masked || lv->covered);
     const bool colored = lv->colored, own_frame = distorted || colored;
+    const bool reduced = lv->frame_factor > 1;  // (colored too)
     if (own_frame && !lv->d_ud) ok(hipMalloc((void **)&lv->d_ud, (size_t)ctx->npix));
+    if (reduced && distorted && !lv->d_small && e == hipSuccess) ok(hipMalloc((void **)&lv->d_small, (size_t)ctx->npix));
     if (want_ud_mask && !lv->d_ud_mask && e == hipSuccess) ok(hipMalloc((void **)&lv->d_ud_mask, (size_t)ctx->npix));
     const uint8_t *d_frame = own_frame ? lv->d_ud : lv->d_frame;
     const uint8_t *d_frame_mask = distorted ? (want_ud_mask ? lv->d_ud_mask : nullptr) : lv->d_frame_mask;
@@ -177,7 +185,13 @@ static int level_capture(nmi_level *lv)
                                   (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
-        if (distorted && colored)  // one node: each tap converted to grey, then the undistortion's arithmetic
+        if (reduced) {  // one node converts and reduces; distorted: the undistortion node reads the level's reduced frame
+            ok(nmi::launch_reduce(lv->d_frame, lv->frame_format, lv->frame_pitch, lv->frame_factor, distorted ? lv->d_small : lv->d_ud, p.width,
+                                  p.height, st));
+            if (distorted)
+                ok(nmi::launch_undistort(lv->ud, lv->d_small, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud,
+                                         want_ud_mask ? lv->d_ud_mask : nullptr, p.width, p.height, st));
+        } else if (distorted && colored)  // one node: each tap converted to grey, then the undistortion's arithmetic
             ok(nmi::launch_undistort_color(lv->ud, lv->d_frame, lv->frame_format, lv->frame_pitch, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud,
                                            want_ud_mask ? lv->d_ud_mask : nullptr, p.width, p.height, st));
         else if (distorted)
@@ -700,46 +714,66 @@ int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[
         }
         if (lv->d_ud_mask) (void)hipFree(lv->d_ud_mask);
         lv->d_ud_mask = nullptr;
+        if (lv->d_small) (void)hipFree(lv->d_small);  // (a reduced level now reduces into d_ud)
+        lv->d_small = nullptr;
     }
     return NMI_OK;
 }
 
-int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch)
+}  // extern "C"
+
+// nmi_level_set_frame_format (factor 1) and nmi_level_set_frame_reduction: one setting, the later call wins.
+static int level_set_frame(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch)
 {
-    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
+    if (!lv || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
     nmi_ctx *ctx = lv->ctx;
     int64_t row_bytes = 0;
     bool identity = true;
-    if (frame_format_check(format, pitch, ctx->params.width, &row_bytes, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    const bool on = !identity;  // dense grey: the never-formatted graph
+    const int64_t full_width = (int64_t)factor * ctx->params.width;
+    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
+        return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = !identity || factor > 1;  // dense grey of the search size: the never-formatted graph
     ctx->detail.clear();
     if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph
         lv->colored = on;
         lv->frame_format = on ? format : NMI_FRAME_GRAY;
         lv->frame_pitch = on ? row_bytes : 0;
+        lv->frame_factor = factor;
         return NMI_OK;
     }
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
     const bool was = lv->colored;
-    const int32_t was_format = lv->frame_format;
+    const int32_t was_format = lv->frame_format, was_factor = lv->frame_factor;
     const int64_t was_pitch = lv->frame_pitch;
     lv->colored = on;
     lv->frame_format = on ? format : NMI_FRAME_GRAY;
     lv->frame_pitch = on ? row_bytes : 0;
+    lv->frame_factor = factor;
     const int rc = level_capture(lv);
     if (rc != NMI_OK) {
         lv->colored = was;
         lv->frame_format = was_format;
         lv->frame_pitch = was_pitch;
+        lv->frame_factor = was_factor;
         return rc;
     }
     if (!on && !lv->distorted && lv->d_ud) {  // no graph reads the level's own frame now
         (void)hipFree(lv->d_ud);
         lv->d_ud = nullptr;
     }
+    if (factor == 1 && lv->d_small) {
+        (void)hipFree(lv->d_small);
+        lv->d_small = nullptr;
+    }
     return NMI_OK;
 }
+
+extern "C" {
+
+int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return level_set_frame(lv, 1, format, pitch); }
+
+int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch) { return level_set_frame(lv, factor, format, pitch); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Streaming pipeline (config 5): double-buffered render stacks, copy stream beside the compute stream.
@@ -808,6 +842,10 @@ struct nmi_stream {
     int64_t frame_pitch = 0;                      // host row bytes (never 0 while colored)
     uint8_t *d_color[2] = {nullptr, nullptr};     // [H][W * bytes per pixel], allocated on the first coloured frame
     size_t color_bytes = 0;                       // their size
+    // Frame reduction (nmi_stream_set_frame_reduction): with frame_factor f > 1 (colored is then set) a host frame is f H rows of
+    // frame_pitch bytes holding f W pixels each; the colour slots hold it dense and full-size, and it is reduced on the compute
+    // stream into d_ud[b], or, distorted, into d_frame[b] (idle meanwhile), which the undistortion reads as a grey frame.
+    int32_t frame_factor = 1;
 };
 
 namespace {
@@ -970,12 +1008,15 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
     }
     const bool undistort = h_frame && st->distorted, colored = h_frame && st->colored;
     const int32_t format = st->frame_format;
-    const int64_t dense_row = (int64_t)ctx->params.width * frame_bytes_per_pixel(format);
+    const int32_t factor = st->frame_factor;
+    const bool reduced = colored && factor > 1;
+    const int64_t dense_row = (int64_t)factor * ctx->params.width * frame_bytes_per_pixel(format);
+    const size_t color_rows = (size_t)factor * ctx->params.height, color_need = (size_t)dense_row * color_rows;
     for (int b = 0; (undistort || colored) && b < 2; ++b) {
         if (!st->d_ud[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud[b], npix));
         if (undistort && kind != kPlain && !st->d_ud_mask[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud_mask[b], npix));
     }
-    if (colored && st->color_bytes < (size_t)dense_row * ctx->params.height) {  // (a wider format than the slots were made for)
+    if (colored && st->color_bytes < color_need) {  // (a wider format or a larger frame than the slots were made for)
         NMI_HIP_TRY(ctx, hipStreamSynchronize(st->copy));        // nothing in flight reads or fills the old slots
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         st->color_bytes = 0;
@@ -983,8 +1024,8 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
             if (st->d_color[b]) (void)hipFree(st->d_color[b]);
             st->d_color[b] = nullptr;
         }
-        for (int b = 0; b < 2; ++b) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_color[b], (size_t)dense_row * ctx->params.height));
-        st->color_bytes = (size_t)dense_row * ctx->params.height;
+        for (int b = 0; b < 2; ++b) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_color[b], color_need));
+        st->color_bytes = color_need;
     }
 
     // copy stream: render stack of this level into the slot (the slot's previous search finished: it was waited for)
@@ -995,9 +1036,9 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const int nb = st->have_warps ? st->warp_buf ^ 1 : 0;
         // the buffer being refilled was last read by searches submitted before the previous frame switch
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(st->copy, st->warps_free[nb], 0));
-        if (colored)  // H rows of the host's pitch into the dense colour slot
-            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)st->frame_pitch, (size_t)dense_row,
-                                              (size_t)ctx->params.height, hipMemcpyHostToDevice, st->copy));
+        if (colored)  // the rows of the host's pitch (H of them, or f H) into the dense colour slot
+            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)st->frame_pitch, (size_t)dense_row, color_rows,
+                                              hipMemcpyHostToDevice, st->copy));
         else
             NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
         if (h_frame_mask) NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_fmask[nb], h_frame_mask, npix, hipMemcpyHostToDevice, st->copy));
@@ -1005,9 +1046,12 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
         if (st->have_warps) NMI_HIP_TRY(ctx, hipEventRecord(st->warps_free[st->warp_buf], ctx->stream));
         const uint8_t *frame = st->d_frame[nb], *frame_mask = h_frame_mask ? st->d_fmask[nb] : nullptr;
+        if (reduced)  // the full-size frame -> grey at the search size, on the compute stream; a frame mask is that size already
+            NMI_HIP_TRY(ctx, nmi::launch_reduce(st->d_color[nb], format, dense_row, factor, undistort ? st->d_frame[nb] : st->d_ud[nb],
+                                                ctx->params.width, ctx->params.height, ctx->stream));
         if (undistort) {  // the raw frame (and mask) -> the undistorted ones, on the compute stream: the warps read them next
             uint8_t *ud_mask = kind != kPlain ? st->d_ud_mask[nb] : nullptr;
-            if (colored)  // converted and undistorted in one node
+            if (colored && !reduced)  // converted and undistorted in one node
                 NMI_HIP_TRY(ctx, nmi::launch_undistort_color(st->ud, st->d_color[nb], format, dense_row, frame_mask, st->d_ud[nb], ud_mask,
                                                              ctx->params.width, ctx->params.height, ctx->stream));
             else
@@ -1016,7 +1060,8 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
             frame = st->d_ud[nb];
             frame_mask = ud_mask;
         } else if (colored) {  // the colour frame -> grey, on the compute stream; a frame mask is dense already
-            NMI_HIP_TRY(ctx, nmi::launch_gray(st->d_color[nb], format, dense_row, st->d_ud[nb], ctx->params.width, ctx->params.height, ctx->stream));
+            if (!reduced)
+                NMI_HIP_TRY(ctx, nmi::launch_gray(st->d_color[nb], format, dense_row, st->d_ud[nb], ctx->params.width, ctx->params.height, ctx->stream));
             frame = st->d_ud[nb];
         }
         int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, st->d_warps[nb])
@@ -1160,18 +1205,24 @@ int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dis
     return NMI_OK;
 }
 
-int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch)
+int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t format, int64_t pitch)
 {
-    if (!st) return NMI_ERR_INVALID_ARGUMENT;
+    if (!st || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
     int64_t row_bytes = 0;
     bool identity = true;
-    if (frame_format_check(format, pitch, st->ctx->params.width, &row_bytes, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    // later frame submissions read the format at their upload: tickets already submitted are not affected
-    st->colored = !identity;
-    st->frame_format = identity ? NMI_FRAME_GRAY : format;
-    st->frame_pitch = identity ? 0 : row_bytes;
+    const int64_t full_width = (int64_t)factor * st->ctx->params.width;
+    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
+        return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = !identity || factor > 1;
+    // later frame submissions read the setting at their upload: tickets already submitted are not affected
+    st->colored = on;
+    st->frame_format = on ? format : NMI_FRAME_GRAY;
+    st->frame_pitch = on ? row_bytes : 0;
+    st->frame_factor = factor;
     return NMI_OK;
 }
+
+int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) { return nmi_stream_set_frame_reduction(st, 1, format, pitch); }
 
 int nmi_stream_keep_ratings(nmi_stream *st, int32_t enabled)
 {

@@ -258,4 +258,18 @@ int nmi_config_load_color_order(const char *yaml_path, int32_t *rgb)
     return nmi_config_parse_color_order(text.data(), text.size(), rgb);
 }
 
+int nmi_config_reduce(nmi_config *cfg, int32_t factor)
+{
+    if (!cfg || factor < 1 || factor > 4) return -1;
+    const double f = (double)factor;
+    cfg->width /= factor;
+    cfg->height /= factor;
+    cfg->fx /= f;
+    cfg->fy /= f;
+    cfg->cx = (cfg->cx + 0.5) / f - 0.5;  // output pixel i is centred on source coordinate f i + (f - 1) / 2
+    cfg->cy = (cfg->cy + 0.5) / f - 0.5;
+    cfg->render_point_size /= (float)factor;
+    return 0;
+}
+
 }  // extern "C"

@@ -16,7 +16,7 @@ EXPORTED_SYMBOLS = (
     "nmi_calculate_translation", "nmi_calculate_relocalization", "nmi_mat4_inverse", "nmi_relocalize_with_strategy",
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
     "nmi_config_parse_distortion", "nmi_config_load_distortion",
-    "nmi_config_parse_color_order", "nmi_config_load_color_order",
+    "nmi_config_parse_color_order", "nmi_config_load_color_order", "nmi_config_reduce",
 )
 
 
@@ -105,6 +105,7 @@ def _lib():
         lib.nmi_config_load_distortion.argtypes = [C.c_char_p, C.POINTER(C.c_float)]
         lib.nmi_config_parse_color_order.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.nmi_config_load_color_order.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
+        lib.nmi_config_reduce.argtypes = [C.POINTER(Config), C.c_int32]
         fpp, i64p = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)
         lib.nmi_map_load_obj.argtypes = [C.c_char_p, fpp, fpp, i64p]
         lib.nmi_map_load_xyz.argtypes = [C.c_char_p, C.c_char_p, fpp, fpp, fpp, i64p]
@@ -237,6 +238,17 @@ def config_load_color_order(path):
     if rc != 0:
         raise ValueError(f"nmi_config_load_color_order({path}) failed: {rc}")
     return int(out.value)
+
+
+def config_reduce(cfg, factor):
+    """nmi_config_reduce: the settings of a full-size camera -> those of the search size, factor (1 .. 4) times smaller: width,
+    height (integer division), fx, fy and render_point_size divided by it, cx' = (cx + 0.5) / factor - 0.5 and cy likewise.
+    Returns a new Config; raises on errors."""
+    out = Config.from_buffer_copy(cfg)
+    rc = _lib().nmi_config_reduce(C.byref(out), int(factor))
+    if rc != 0:
+        raise ValueError(f"nmi_config_reduce failed: {rc}")
+    return out
 
 
 def _take(ptr, shape, dtype):
