@@ -135,17 +135,17 @@ template <bool ZERO0>
 __device__ __forceinline__ void covered_decode_merged(Lds &lds, uint32_t len, int wave, int lane, const u32x4 (&acc)[kUnitsPerLane])
 {
     uint32_t wave_total = 0;
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) col_lo[k] = col_hi[k] = 0;
 #pragma unroll
     for (int pass = 0; pass < kRowsPerWave / 4; ++pass) {
-        const int d1 = wave * kRowsPerWave + pass * 4 + r;
+        const int d1 = decode_row(wave, pass, r);
         uint32_t lo[8], hi[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint32_t wd = lds.joint[decode_word(d1, i, o, k)];
+            const uint32_t wd = lds.joint[decode_word(d1, i, k)];
             const uint32_t ad = acc[pass * 2 + (k >> 2)][k & 3];
             lo[k] = (wd & 0xFFFFu) + (ad & 0xFFFFu);
             hi[k] = (wd >> 16) + (ad >> 16);
@@ -156,7 +156,7 @@ __device__ __forceinline__ void covered_decode_merged(Lds &lds, uint32_t len, in
 #pragma unroll
             for (int k = 0; k < 8; ++k) raw += lo[k] + hi[k];
             wave_total += row_sum_16(raw);
-            if (i == 0) lo[o ? 7 : 0] = 0;  // the bin d2 = 0 of this row
+            if (i == 0) lo[0] = 0;  // the bin d2 = 0 of this row
             if (d1 == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) lo[k] = hi[k] = 0;
@@ -189,7 +189,7 @@ __device__ __forceinline__ void covered_decode_merged(Lds &lds, uint32_t len, in
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int q = (i + 16 * (k + o)) & 127;
+        const int q = i + 16 * k;
         atomicAdd(&lds.hist_warped[q], col_lo[k]);
         atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
     }
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_pix_kernel(Cove
     {
         uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
         const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
     }
     if (tid < kBins) lds.hist_warped[tid] = 0;
     if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;  // total[0]: decoded counters, total[1]: len (pixels added by all ranges)
@@ -247,13 +247,13 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_pix_kernel(Cove
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)kPixBlockBytes, 0x00020000);
         unsigned long long bits[kUnitsPerLane];
         {
-            const int i = lane & 15, r = lane >> 4, o = r & 1;
+            const int i = lane & 15, r = lane >> 4;
 #pragma unroll
             for (int kk = 0; kk < kUnitsPerLane; ++kk) {
-                const int d1 = wave * kRowsPerWave + (kk >> 1) * 4 + r;
+                const int d1 = decode_row(wave, kk >> 1, r);
                 u32x4 v;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, o, (kk & 1) * 4 + j)];
+                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, (kk & 1) * 4 + j)];
                 const bool on = (v.x | v.y | v.z | v.w) != 0u;
                 bits[kk] = __ballot(on);
                 if (on) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_pix_kernel(Cove
         {
             uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
             const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
         }
         if (tid < kBins) lds.hist_warped[tid] = 0;
         if (tid < 2) lds.total[tid] = lds.ovf_n[tid] = 0;

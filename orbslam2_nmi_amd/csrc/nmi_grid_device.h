@@ -17,26 +17,31 @@ constexpr int kBlock = NMI_BLOCK_THREADS;  // 1024 lanes = 16 wavefronts, one wo
 constexpr int kWaves = kBlock / 64;
 constexpr int kBins = 256;
 constexpr int kWords = kBins * kBins / 2;  // two 16-bit counters per LDS word
+constexpr int kRowStride = 129;            // LDS words from one joint row to the next: 128 counter words + 1 unused (see joint_word)
+constexpr int kJointWords = kBins * kRowStride;  // the LDS array: the kWords counter words and the 256 gap words (always zero)
 constexpr int kOvfCap = 1024;              // >= 2 * floor(2^24 / 65536) + 1 wrap events per candidate
 constexpr int kRowsPerWave = kBins / kWaves;
 constexpr int kLdsTable = 4096;            // per-count entropy terms kept in LDS for counts below this
 constexpr int kSide = 8;                   // side counters for bins fed by flat image regions (see fold_flat_chunk)
 
 // LDS word of joint bin (d1 = render intensity, d2 = warped-frame intensity):
-//   word = d1 * 128 + (d2 & 127), low half for d2 < 128, high half for d2 >= 128.
+//   word = d1 * kRowStride + (d2 & 127), low half for d2 < 128, high half for d2 >= 128.
 // Each word thus holds the pair (d2, d2 + 128) -- the two operands of the first tree step a[t] += a[t+128]
 // (NMI.cu:276-284) -- and a lane that owns the words i, i+16, ..., i+112 of a row owns all operands of the steps
-// n = 128, 64, 32, 16 (decode_phase).  The LDS bank of a bin is (d2 & 31): the render intensity does not enter it.
+// n = 128, 64, 32, 16 (decode_phase).  A row is 129 words long, not 128: row d1 occupies [129 d1, 129 d1 + 127], the word
+// after it is never touched, nothing wraps inside a row -- and the LDS bank of a bin is (d1 + d2) & 31.  With 128 it was
+// d2 & 31 alone, and the zero border of a warped frame (3-4.5 % of the pixels of a search's warps) put every lane that
+// met it on bank 0, in a different word per render intensity.
 
 struct Lds {
-    uint32_t joint[kWords];    // 128 KiB
+    uint32_t joint[kJointWords];  // 129 KiB
     uint32_t hist_render[kBins];
     uint32_t hist_warped[kBins];
     float joint_row_sums[kBins];  // d_JointEntropyShort, kernel.cu:60,90
     uint32_t ovf[2][kOvfCap];     // wrap events: (word << 1) | field; double-buffered by candidate parity
     uint32_t ovf_n[2];
     uint32_t total[2];            // sum of all decoded counters of the candidate (wrap detector), by parity
-    uint32_t side_key[2][kSide];  // flat-region side counters: ((word << 1) | field) + 1, 0 = free; by candidate parity
+    uint32_t side_key[2][kSide];  // flat-region side counters: the bin ((d1 << 8) | d2) + 1, 0 = free; by candidate parity
     uint32_t side_cnt[2][kSide];  // their 32-bit counts (added to the decoded counters in decode_phase)
     float table[kLdsTable];       // table[c] for c < kLdsTable (16 KiB); larger counts read the global table
     uint32_t fallback;            // pipelined kernel: a candidate wrapped, finish sequentially on the exact path
@@ -59,7 +64,7 @@ __device__ __forceinline__ int candidate_at(const GridArgs &a, int ordinal) { re
 // high field then counts d2>=128 hits plus low wraps), a high-field wrap is seen either by a high
 // add (old high == 0xFFFF) or by the carrying low add (old word == 0xFFFFFFFF).  Events are rare
 // (at most about 2 * W*H / 65536 per candidate) and are replayed when the counters are decoded.
-__device__ __forceinline__ uint32_t joint_word(uint32_t d1, uint32_t d2) { return (d1 << 7) | (d2 & 127u); }
+__device__ __forceinline__ uint32_t joint_word(uint32_t d1, uint32_t d2) { return d1 * (uint32_t)kRowStride + (d2 & 127u); }
 __device__ __forceinline__ uint32_t joint_inc(uint32_t d2) { return (d2 & 128u) ? 0x10000u : 1u; }
 
 __device__ __forceinline__ void record_wrap(Lds &lds, int par, uint32_t word, uint32_t val, uint32_t old)
@@ -93,9 +98,9 @@ __device__ __forceinline__ void add_pixel(Lds &lds, int par, uint32_t d1, uint32
 // into a 32-bit side counter (kSide per candidate, replayed in decode_phase): a large flat region then neither
 // serialises the LDS nor wraps a 16-bit field, so such frames stay on the one-pass optimistic path.
 // Returns false (nothing done) when some active lane is not flat.
-__device__ __forceinline__ bool side_add(Lds &lds, int par, uint32_t word, uint32_t high, uint32_t weight)
+__device__ __forceinline__ bool side_add(Lds &lds, int par, uint32_t d1, uint32_t d2, uint32_t weight)
 {
-    const uint32_t key1 = ((word << 1) | high) + 1u;
+    const uint32_t key1 = ((d1 << 8) | d2) + 1u;
     for (int e = 0; e < kSide; ++e) {
         const uint32_t old = atomicCAS(&lds.side_key[par][e], 0u, key1);
         if (old == 0u || old == key1) {
@@ -129,7 +134,7 @@ __device__ __forceinline__ bool fold_flat_chunk(Lds &lds, int par, const uint32_
         const unsigned long long active = __ballot(1);
         weight = 16u * (uint32_t)__popcll(active);
         issue = issue && (__lane_id() == (uint32_t)__ffsll((long long)active) - 1u);
-        if (issue && side_add(lds, par, word, high, weight)) issue = false;
+        if (issue && side_add(lds, par, d1, d2, weight)) issue = false;
     }
     if (issue) {
         const uint32_t inc = high ? weight << 16 : weight;
@@ -170,28 +175,28 @@ __device__ __forceinline__ void add_chunk(Lds &lds, int par, const uint4 &rv, co
         }
     }
     if (HIST == 2 && BG && !SHIFTED) {
-        // The hot case, written so that each pixel costs 5 VALU + 1 DS: byte address = d1 * 512 + (d2 & 127) * 4 from one
-        // byte-select shift of the render dword and one shift + and-or of the frame dword; increment 1 + 0xFFFF * bit7(d2).
-        // hipcc re-derives 7 instructions from the plain C expressions (mask + compare + select for the increment, a
-        // separate mask for the render byte), so the five are spelled out: SDWA byte-select shift, shift, and-or, bit-field
-        // extract, 24-bit multiply-add.
+        // The hot case, written so that each pixel costs 5 VALU + 1 DS: byte address = d1 * 516 + (d2 & 127) * 4 from one
+        // byte-select 24-bit multiply of the render dword (the row's byte address), one bit-field extract of the frame dword
+        // and one shift-add; increment 1 + 0xFFFF * bit7(d2) from a second extract and a 24-bit multiply-add.  hipcc derives
+        // more from the plain C expressions (a separate mask for the render byte; mask + compare + select for the
+        // increment), so the SDWA multiply and the multiply-add are spelled out.
         char *const base = reinterpret_cast<char *>(lds.joint);
-        const uint32_t nine = 9, mask_1fc = 0x1FCu, k_ffff = 0xFFFFu;
+        const uint32_t row_bytes = kRowStride * 4, k_ffff = 0xFFFFu;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                uint32_t a1, a2, addr, hi, val;
+                uint32_t a1, c, addr, hi, val;
                 if (j == 0)
-                    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(a1) : "v"(nine), "v"(r[q]));
+                    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(a1) : "v"(r[q]), "s"(row_bytes));
                 else if (j == 1)
-                    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(a1) : "v"(nine), "v"(r[q]));
+                    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(a1) : "v"(r[q]), "s"(row_bytes));
                 else if (j == 2)
-                    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(a1) : "v"(nine), "v"(r[q]));
+                    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(a1) : "v"(r[q]), "s"(row_bytes));
                 else
-                    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(a1) : "v"(nine), "v"(r[q]));
-                a2 = j == 0 ? (w[q] << 2) : (w[q] >> (8 * j - 2));
-                asm("v_and_or_b32 %0, %1, %3, %2" : "=v"(addr) : "v"(a2), "v"(a1), "s"(mask_1fc));  // VOP3: no literals on gfx9
+                    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(a1) : "v"(r[q]), "s"(row_bytes));
+                c = __builtin_amdgcn_ubfe(w[q], 8 * j, 7);
+                asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(addr) : "v"(c), "v"(a1));
                 hi = __builtin_amdgcn_ubfe(w[q], 8 * j + 7, 1);
                 asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(val) : "v"(hi), "s"(k_ffff));
                 (void)__hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + addr), val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -387,6 +392,17 @@ __device__ __forceinline__ float term_lds(const Lds &lds, const float *__restric
     return t;
 }
 
+// Who decodes what: wavefront `wave` takes the 4 joint rows wave + 64 pass + 16 r of its pass `pass`, one per 16-lane DPP row
+// r, and lane i of a DPP row the words i + 16 k (k = 0..7) of its row.  Every kernel that reads packed counters in decode
+// order (decode_phase, the pixel-range hand-off units, the masked and covered forms, the ablation drain) goes through these.
+static_assert(kWaves == 16 && (kWaves * kRowStride) % 32 == 16, "rows kWaves apart must fall on opposite halves of the 32 banks");
+__device__ __forceinline__ int decode_row(int wave, int pass, int r) { return wave + 4 * kWaves * pass + kWaves * r; }
+__device__ __forceinline__ bool in_decode_pass(uint32_t d1, int wave, int pass)
+{
+    return (d1 % (uint32_t)kWaves) == (uint32_t)wave && (d1 / (uint32_t)(4 * kWaves)) == (uint32_t)pass;
+}
+__device__ __forceinline__ uint32_t decode_word(int d1, int i, int k) { return (uint32_t)(d1 * kRowStride + i + 16 * k); }
+
 // Replays the wrap events of one LDS word onto its two decoded counters.
 __device__ __forceinline__ void apply_wraps(const Lds &lds, int par, uint32_t novf, uint32_t word, uint32_t &lo,
                                             uint32_t &hi)
@@ -409,7 +425,8 @@ __device__ __forceinline__ void apply_wraps(const Lds &lds, int par, uint32_t no
 // d2 = i + 16*j (j = 0..15): words i + 16*k (k = 0..7) hold the pairs (d2, d2 + 128).  Every tree step
 // n >= 16 of NMI.cu:276-284 then pairs two values of the same lane and the steps n = 8..1 are DPP
 // shifts inside the 16-lane row: no LDS traffic besides reading (and clearing) the counters.
-// Odd DPP rows start at k = 1 so that the two rows of a 32-lane LDS access group hit disjoint banks.
+// The rows of a pass are 16 apart (decode_row): 16 rows of 129 words shift the bank by 16, so the two rows of a 32-lane LDS
+// access group hit disjoint halves of the banks, and a lane's eight words are constant offsets 16 k from one base.
 // ZERO0 (background rule off, NMI.cu:85: a pixel counts only if both intensities are non-zero): the histogram phase
 // has counted every pixel -- the skipped ones are exactly row 0 and column 0 of the joint histogram, which are cleared
 // here, after they have entered the wrap detector's total.
@@ -419,18 +436,18 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
     const uint32_t novf = lds.ovf_n[par] < (uint32_t)kOvfCap ? lds.ovf_n[par] : (uint32_t)kOvfCap;
     const bool side_any = lds.side_key[par][0] != 0u;
     uint32_t wave_total = 0;
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) col_lo[k] = col_hi[k] = 0;
 #pragma unroll 1
     for (int pass = 0; pass < kRowsPerWave / 4; ++pass) {
-        const int d1 = wave * kRowsPerWave + pass * 4 + r;
-        const uint32_t a0 = d1 * 128 + i + 16 * o;
+        const int d1 = decode_row(wave, pass, r);
+        const uint32_t a0 = decode_word(d1, i, 0);
         uint32_t lo[8], hi[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint32_t idx = k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o;
+            const uint32_t idx = a0 + 16 * k;
             const uint32_t wd = lds.joint[idx];
             lds.joint[idx] = 0;  // ready for the next candidate
             lo[k] = wd & 0xFFFFu;
@@ -438,20 +455,21 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
         }
         if (__builtin_expect(novf != 0, 0)) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) apply_wraps(lds, par, novf, k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o, lo[k], hi[k]);
+            for (int k = 0; k < 8; ++k) apply_wraps(lds, par, novf, a0 + 16 * k, lo[k], hi[k]);
         }
         if (__builtin_expect(side_any, 0)) {
             // side counters of flat regions (fold_flat_chunk): entries fill in order, a free one ends the list
             for (int e = 0; e < kSide; ++e) {
                 const uint32_t key1 = __builtin_amdgcn_readfirstlane(lds.side_key[par][e]);
                 if (key1 == 0u) break;
-                const uint32_t sword = (key1 - 1u) >> 1;
-                if ((sword >> 9) != (uint32_t)((wave * kRowsPerWave + pass * 4) >> 2)) continue;  // not among this pass's 4 rows
+                const uint32_t sd1 = (key1 - 1u) >> 8, sd2 = (key1 - 1u) & 0xFFu;
+                if (!in_decode_pass(sd1, wave, pass)) continue;  // not among this pass's 4 rows
+                const uint32_t sword = joint_word(sd1, sd2);
                 const uint32_t cnt = lds.side_cnt[par][e];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    if ((k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o) == sword) {
-                        if ((key1 - 1u) & 1u)
+                    if (a0 + 16 * k == sword) {
+                        if (sd2 & 128u)
                             hi[k] += cnt;
                         else
                             lo[k] += cnt;
@@ -465,7 +483,7 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
 #pragma unroll
             for (int k = 0; k < 8; ++k) raw += lo[k] + hi[k];
             wave_total += row_sum_16(raw);
-            if (i == 0) lo[o ? 7 : 0] = 0;  // the bin d2 = 0 of this row
+            if (i == 0) lo[0] = 0;  // the bin d2 = 0 of this row
             if (d1 == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) lo[k] = hi[k] = 0;
@@ -500,7 +518,7 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
             uint32_t *row = a.dbg_joint + d1 * kBins;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const int q = (i + 16 * (k + o)) & 127;
+                const int q = i + 16 * k;
                 row[q] = lo[k];
                 row[q + 128] = hi[k];
             }
@@ -508,7 +526,7 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int q = (i + 16 * (k + o)) & 127;
+        const int q = i + 16 * k;
         atomicAdd(&lds.hist_warped[q], col_lo[k]);
         atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
     }

@@ -7,7 +7,7 @@
 //   Thirdparty/CUDA_Functions/NMI.cu:342-362  SUC / ENMI score with the all-zero guard
 //   Thirdparty/Localization/helperFunctions.cpp:50-103  arg-max (strict '>' from 0, lowest index on ties)
 // How it is computed is new: one 1024-lane workgroup per pose candidate owns the whole
-// 256x256 joint histogram in LDS as packed 16-bit counters (128 KiB of the CU's 160 KiB); counts above 65535
+// 256x256 joint histogram in LDS as packed 16-bit counters (129 KiB of the CU's 160 KiB: rows 129 words apart); counts above 65535
 // are caught by a pixel-count test and redone with exact wrap bookkeeping; the entropy terms come from a
 // per-context table indexed by count; the trees are evaluated in registers / DPP in the reference's order; the
 // score, the rating-table store and the arg-max (one 64-bit atomicMax per candidate) are fused into the
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
     {
         uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
         const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
     }
     if (tid < kBins) lds.hist_warped[tid] = 0;
     if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;
@@ -258,23 +258,26 @@ constexpr int kDWaves = kWaves / 2;             // 8 decode wavefronts
 constexpr int kDRows = kBins / kDWaves;         // 32 joint rows per decode wavefront
 constexpr int kDPasses = kDRows / 4;            // 8 passes of 4 rows (one per 16-lane DPP row)
 
+// Joint row of DPP row r in pass `pass` of decode wavefront `dwave`: the two rows of a 32-lane LDS access group are 16 apart
+// (opposite halves of the banks under the 129-word row stride, nmi_grid_device.h).
+__device__ __forceinline__ int ws_row(int dwave, int pass, int r) { return dwave * kDRows + (r & 1) * 16 + pass * 2 + (r >> 1); }
+
 // Drain, all 16 wavefronts: packed counters LDS -> this workgroup's scratch slab in global memory (it stays in L2),
 // clearing the LDS words.  The slab is written in the order the decode wavefronts read it -- [dwave][pass][k][lane],
 // 256 contiguous bytes per wavefront instruction -- with the word ownership of decode_phase (lane i of a 16-lane row
-// owns words i + 16*k of its joint row).
+// owns words i + 16*k of its joint row) and the rows of ws_row.
 __device__ __forceinline__ void drain_to_scratch(Lds &lds, uint32_t *__restrict__ slab, int wave, int lane)
 {
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     const int dwave = wave >> 1, pass0 = (wave & 1) * (kDPasses / 2);
 #pragma unroll
     for (int pp = 0; pp < kDPasses / 2; ++pp) {
         const int pass = pass0 + pp;
-        const int d1 = dwave * kDRows + pass * 4 + r;
-        const uint32_t a0 = d1 * 128 + i + 16 * o;
+        const int d1 = ws_row(dwave, pass, r);
         uint32_t wd[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint32_t idx = k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o;
+            const uint32_t idx = decode_word(d1, i, k);
             wd[k] = lds.joint[idx];
             lds.joint[idx] = 0;
         }
@@ -328,7 +331,7 @@ __device__ __forceinline__ void decode_pass(Lds &lds, const GridArgs &a, int d1,
 __device__ __forceinline__ void decode_from_scratch(Lds &lds, const GridArgs &a, const uint32_t *__restrict__ slab, int dwave,
                                                     int lane)
 {
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8], wave_total = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) col_lo[k] = col_hi[k] = 0;
@@ -338,13 +341,13 @@ __device__ __forceinline__ void decode_from_scratch(Lds &lds, const GridArgs &a,
 #pragma unroll 1
     for (int pass = 0; pass < kDPasses; pass += 2) {
         load_pass(src + (pass + 1) * 8 * 64, wb);
-        decode_pass(lds, a, dwave * kDRows + pass * 4 + r, i, wa, col_lo, col_hi, wave_total);
+        decode_pass(lds, a, ws_row(dwave, pass, r), i, wa, col_lo, col_hi, wave_total);
         if (pass + 2 < kDPasses) load_pass(src + (pass + 2) * 8 * 64, wa);
-        decode_pass(lds, a, dwave * kDRows + (pass + 1) * 4 + r, i, wb, col_lo, col_hi, wave_total);
+        decode_pass(lds, a, ws_row(dwave, pass + 1, r), i, wb, col_lo, col_hi, wave_total);
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int q = (i + 16 * (k + o)) & 127;
+        const int q = i + 16 * k;
         atomicAdd(&lds.hist_warped[q], col_lo[k]);
         atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
     }
@@ -367,7 +370,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_grid_kernel_ws(GridArgs
     {
         uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
         const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
     }
     for (int c = tid; c < kLdsTable; c += kBlock) lds.table[c] = a.table[c <= a.npix ? c : 0];
     if (tid < kBins) lds.hist_warped[tid] = 0;

@@ -154,18 +154,18 @@ __device__ __forceinline__ void covered_decode_phase(Lds &lds, int par, uint32_t
 {
     const uint32_t novf = lds.ovf_n[par] < (uint32_t)kOvfCap ? lds.ovf_n[par] : (uint32_t)kOvfCap;
     uint32_t wave_total = 0;
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) col_lo[k] = col_hi[k] = 0;
 #pragma unroll 1
     for (int pass = 0; pass < kRowsPerWave / 4; ++pass) {
-        const int d1 = wave * kRowsPerWave + pass * 4 + r;
-        const uint32_t a0 = d1 * 128 + i + 16 * o;
+        const int d1 = decode_row(wave, pass, r);
+        const uint32_t a0 = decode_word(d1, i, 0);
         uint32_t lo[8], hi[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint32_t idx = k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o;
+            const uint32_t idx = a0 + 16 * k;
             const uint32_t wd = lds.joint[idx];
             lds.joint[idx] = 0;  // ready for the next candidate
             lo[k] = wd & 0xFFFFu;
@@ -173,7 +173,7 @@ __device__ __forceinline__ void covered_decode_phase(Lds &lds, int par, uint32_t
         }
         if (__builtin_expect(novf != 0, 0)) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) apply_wraps(lds, par, novf, k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o, lo[k], hi[k]);
+            for (int k = 0; k < 8; ++k) apply_wraps(lds, par, novf, a0 + 16 * k, lo[k], hi[k]);
         }
         uint32_t rsum = 0, cmax = 0;
         if (ZERO0) {
@@ -181,7 +181,7 @@ __device__ __forceinline__ void covered_decode_phase(Lds &lds, int par, uint32_t
 #pragma unroll
             for (int k = 0; k < 8; ++k) raw += lo[k] + hi[k];
             wave_total += row_sum_16(raw);
-            if (i == 0) lo[o ? 7 : 0] = 0;  // the bin d2 = 0 of this row
+            if (i == 0) lo[0] = 0;  // the bin d2 = 0 of this row
             if (d1 == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) lo[k] = hi[k] = 0;
@@ -214,7 +214,7 @@ __device__ __forceinline__ void covered_decode_phase(Lds &lds, int par, uint32_t
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int q = (i + 16 * (k + o)) & 127;
+        const int q = i + 16 * k;
         atomicAdd(&lds.hist_warped[q], col_lo[k]);
         atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
     }

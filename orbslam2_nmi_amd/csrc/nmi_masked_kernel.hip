@@ -64,7 +64,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_grid_kernel(Mask
         {
             uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
             const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
         }
         if (tid < kBins) lds.hist_warped[tid] = 0;
         if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;

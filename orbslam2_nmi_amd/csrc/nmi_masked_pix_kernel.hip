@@ -152,7 +152,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
     {
         uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
         const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
     }
     if (tid < kBins) lds.hist_warped[tid] = 0;
     if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;  // total[0]: decoded counters, total[1]: pixels added by all ranges
@@ -172,13 +172,13 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)kPixBlockBytes, 0x00020000);
         unsigned long long bits[kUnitsPerLane];
         {
-            const int i = lane & 15, r = lane >> 4, o = r & 1;
+            const int i = lane & 15, r = lane >> 4;
 #pragma unroll
             for (int kk = 0; kk < kUnitsPerLane; ++kk) {
-                const int d1 = wave * kRowsPerWave + (kk >> 1) * 4 + r;
+                const int d1 = decode_row(wave, kk >> 1, r);
                 u32x4 v;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, o, (kk & 1) * 4 + j)];
+                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, (kk & 1) * 4 + j)];
                 const bool on = (v.x | v.y | v.z | v.w) != 0u;
                 bits[kk] = __ballot(on);
                 if (on) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
         {
             uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
             const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
         }
         if (tid < kBins) lds.hist_warped[tid] = 0;
         if (tid < 2) lds.total[tid] = lds.ovf_n[tid] = 0;

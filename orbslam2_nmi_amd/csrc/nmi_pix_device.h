@@ -17,7 +17,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // a natural pair's joint histogram is empty, and the launch's hand-offs together (20 MB at 81 candidates x 3 ranges) otherwise
 // run at the rate the memory system takes write-through stores.  A unit is what ONE LANE OF THE OWNER'S DECODE needs at once:
 // unit (wave, pass, half) of lane l = the four packed words k = 4 half .. 4 half + 3 that decode_phase's lane l of that
-// wave reads in that pass (nmi_kernels.hip: rows 16 wave + 4 pass + l / 16, words i + 16 k of the row), so the owner never
+// wave reads in that pass (decode_row / decode_word, nmi_grid_device.h: row wave + 64 pass + 16 (l / 16), words i + 16 k of the row), so the owner never
 // reshuffles anything.  Which units came is said by 64-bit masks, one per (wave, k = 2 pass + half), and the masks double as
 // the flags: each travels as two 8-byte granules {half of the mask, launch tag}, stored after the drain and the barrier, so
 // a wave of the owner that finds the tag in its 16 granules has its masks AND knows the units are in memory.
@@ -147,12 +147,6 @@ __device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, con
     }
 }
 
-// LDS word k (0..7) of decode lane (i, r = DPP row, o = r & 1) in joint row d1: decode_phase's ownership (nmi_kernels.hip)
-__device__ __forceinline__ uint32_t decode_word(int d1, int i, int o, int k)
-{
-    const uint32_t a0 = d1 * 128 + i + 16 * o;
-    return k < 7 ? a0 + 16 * k : a0 + 112 - 128 * o;
-}
 __device__ __forceinline__ int unit_offset(int wave, int kk, int lane) { return (int)sizeof(PixHeader) + ((wave * kUnitsPerLane + kk) * 64 + lane) * 16; }
 
 // The dealing pattern of a launch (host): own : hlp pieces per period, the closest to owner_share among periods of at most 48
@@ -194,17 +188,17 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
 {
     const bool side_any = lds.side_key[0][0] != 0u;
     uint32_t wave_total = 0;
-    const int i = lane & 15, r = lane >> 4, o = r & 1;
+    const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) col_lo[k] = col_hi[k] = 0;
 #pragma unroll
     for (int pass = 0; pass < kRowsPerWave / 4; ++pass) {
-        const int d1 = wave * kRowsPerWave + pass * 4 + r;
+        const int d1 = decode_row(wave, pass, r);
         uint32_t lo[8], hi[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint32_t wd = lds.joint[decode_word(d1, i, o, k)];
+            const uint32_t wd = lds.joint[decode_word(d1, i, k)];
             const uint32_t ad = acc[pass * 2 + (k >> 2)][k & 3];
             lo[k] = (wd & 0xFFFFu) + (ad & 0xFFFFu);
             hi[k] = (wd >> 16) + (ad >> 16);
@@ -214,13 +208,14 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
             for (int e = 0; e < kSide; ++e) {
                 const uint32_t key1 = __builtin_amdgcn_readfirstlane(lds.side_key[0][e]);
                 if (key1 == 0u) break;
-                const uint32_t sword = (key1 - 1u) >> 1;
-                if ((sword >> 9) != (uint32_t)((wave * kRowsPerWave + pass * 4) >> 2)) continue;  // not among this pass's 4 rows
+                const uint32_t sd1 = (key1 - 1u) >> 8, sd2 = (key1 - 1u) & 0xFFu;
+                if (!in_decode_pass(sd1, wave, pass)) continue;  // not among this pass's 4 rows
+                const uint32_t sword = joint_word(sd1, sd2);
                 const uint32_t cnt = lds.side_cnt[0][e];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    if (decode_word(d1, i, o, k) == sword) {
-                        if ((key1 - 1u) & 1u)
+                    if (decode_word(d1, i, k) == sword) {
+                        if (sd2 & 128u)
                             hi[k] += cnt;
                         else
                             lo[k] += cnt;
@@ -234,7 +229,7 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
 #pragma unroll
             for (int k = 0; k < 8; ++k) raw += lo[k] + hi[k];
             wave_total += row_sum_16(raw);
-            if (i == 0) lo[o ? 7 : 0] = 0;  // the bin d2 = 0 of this row
+            if (i == 0) lo[0] = 0;  // the bin d2 = 0 of this row
             if (d1 == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) lo[k] = hi[k] = 0;
@@ -268,7 +263,7 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
             uint32_t *row = a.dbg_joint + d1 * kBins;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const int q = (i + 16 * (k + o)) & 127;
+                const int q = i + 16 * k;
                 row[q] = lo[k];
                 row[q + 128] = hi[k];
             }
@@ -276,7 +271,7 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int q = (i + 16 * (k + o)) & 127;
+        const int q = i + 16 * k;
         atomicAdd(&lds.hist_warped[q], col_lo[k]);
         atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
     }

@@ -9,7 +9,7 @@
 // however few of its lanes own them, and the time of nmi_grid_kernel's histogram phase is its LDS atomic instructions.
 //
 // How: workgroup (candidate p, range q) runs nmi_grid_kernel's own histogram phase (NMI.cu:79-87; nmi_kernels.hip:
-// packed 16-bit counters, 128 KiB of LDS, one non-returning atomic per pixel, flat regions folded) over chunks
+// packed 16-bit counters, 129 KiB of LDS, one non-returning atomic per pixel, flat regions folded) over chunks
 // of its own.  Range 0 is the candidate's OWNER; ranges 1 .. P-1 are HELPERS: a helper writes the 16-byte units of its packed
 // histogram that hold a count (+ its flat-region side counters) to its block in memory with write-through stores, every wave
 // drains its stores, and after the workgroup's barrier the launch's tag goes out with the masks that say which units came
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, 
     {
         uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
         const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
     }
     if (tid < kBins) lds.hist_warped[tid] = 0;
     if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;
@@ -104,13 +104,13 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, 
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)kPixBlockBytes, 0x00020000);
         unsigned long long mask[kUnitsPerLane];
         {
-            const int i = lane & 15, r = lane >> 4, o = r & 1;
+            const int i = lane & 15, r = lane >> 4;
 #pragma unroll
             for (int kk = 0; kk < kUnitsPerLane; ++kk) {
-                const int d1 = wave * kRowsPerWave + (kk >> 1) * 4 + r;
+                const int d1 = decode_row(wave, kk >> 1, r);
                 u32x4 v;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, o, (kk & 1) * 4 + j)];
+                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, (kk & 1) * 4 + j)];
                 const bool on = (v.x | v.y | v.z | v.w) != 0u;
                 mask[kk] = __ballot(on);
                 if (on) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, 
                 const uint32_t skey = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, side_key) + lane * 4, 0, kAuxSc1);
                 const uint32_t scnt = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, side_cnt) + lane * 4, 0, kAuxSc1);
                 if (skey != 0u) {
-                    const uint32_t word = (skey - 1u) >> 1, high = (skey - 1u) & 1u;
-                    if (!side_add(lds, 0, word, high, scnt)) atomicAdd(&lds.joint[word], high ? scnt << 16 : scnt);
+                    const uint32_t sd1 = (skey - 1u) >> 8, sd2 = (skey - 1u) & 0xFFu;
+                    if (!side_add(lds, 0, sd1, sd2, scnt)) atomicAdd(&lds.joint[joint_word(sd1, sd2)], (sd2 & 128u) ? scnt << 16 : scnt);
                 }
             }
 #pragma unroll
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, 
         {
             uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
             const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kWords / 4; i += kBlock) j4[i] = z;
+            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
         }
         if (tid < kBins) lds.hist_warped[tid] = 0;
         if (tid < 2) lds.total[tid] = lds.ovf_n[tid] = 0;
