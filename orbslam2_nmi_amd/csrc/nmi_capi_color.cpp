@@ -1,6 +1,6 @@
 // nmi_capi_color.cpp -- nmi_gray_frame (include/nmi_hip.h) and the host side of the frame formats the captured levels and streams
-// share (nmi_capi_pipeline.cpp: nmi_level_set_frame_format, nmi_stream_set_frame_format).  Kernels: nmi_color.hip, and the colour
-// instantiation of the undistortion kernel in nmi_undistort.hip.
+// share (nmi_level_set_frame_format, nmi_stream_set_frame_format: both through nmi_capi_intake.cpp's intake_set_frame and
+// launch_intake).  Kernels: nmi_color.hip, and the colour instantiation of the undistortion kernel in nmi_undistort.hip.
 #include "nmi_color.h"
 #include "nmi_ctx.h"
 

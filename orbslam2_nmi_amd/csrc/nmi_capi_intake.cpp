@@ -1,0 +1,53 @@
+// nmi_capi_intake.cpp -- the frame intake the captured levels and the streams share (nmi_intake.h): its two settings, checked
+// and normalised, and its kernel launches.
+#include "nmi_intake.h"
+
+#include "nmi_color.h"
+#include "nmi_reduce.h"
+
+namespace nmi_internal {
+
+int intake_set_distortion(FrameIntake *in, const double K[9], const float dist[5])
+{
+    nmi::UndistortParams ud{};
+    bool identity = true;
+    if (dist && undistort_params(K, dist, &ud, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    in->distorted = dist && !identity;  // five zero coefficients: as never distorted
+    in->ud = ud;
+    return NMI_OK;
+}
+
+int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch)
+{
+    if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    int64_t row_bytes = 0;
+    bool identity = true;
+    const int64_t full_width = (int64_t)factor * width;
+    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
+        return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = !identity || factor > 1;  // dense grey of the search size: as never formatted
+    in->colored = on;
+    in->frame_format = on ? format : NMI_FRAME_GRAY;
+    in->frame_pitch = on ? row_bytes : 0;
+    in->frame_factor = factor;
+    return NMI_OK;
+}
+
+hipError_t launch_intake(const FrameIntake &in, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask, uint8_t *scratch,
+                         uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream)
+{
+    const uint8_t *raw_mask = mask_out ? src_mask : nullptr;
+    if (in.reduced()) {  // one node converts and reduces; distorted: the undistortion node reads the reduced frame
+        const hipError_t e = nmi::launch_reduce(src, in.frame_format, src_row_bytes, in.frame_factor, in.distorted ? scratch : gray_out, width,
+                                                height, stream);
+        if (e != hipSuccess || !in.distorted) return e;
+        return nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
+    }
+    if (in.distorted && in.colored)
+        return nmi::launch_undistort_color(in.ud, src, in.frame_format, src_row_bytes, raw_mask, gray_out, mask_out, width, height, stream);
+    if (in.distorted) return nmi::launch_undistort(in.ud, src, raw_mask, gray_out, mask_out, width, height, stream);
+    if (in.colored) return nmi::launch_gray(src, in.frame_format, src_row_bytes, gray_out, width, height, stream);
+    return hipSuccess;
+}
+
+}  // namespace nmi_internal

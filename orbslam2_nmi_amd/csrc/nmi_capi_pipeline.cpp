@@ -3,6 +3,7 @@
 #include "nmi_covered.h"
 #include "nmi_color.h"
 #include "nmi_ctx.h"
+#include "nmi_intake.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
 #include "nmi_reduce.h"
@@ -26,6 +27,13 @@ extern "C" {
 // polls the winner word.
 // ---------------------------------------------------------------------------------------------------------
 }  // extern "C"
+
+// What a level's setters change.  A refused or failed call leaves the whole value as it was.
+struct LevelSettings {
+    bool masked = false, covered = false;
+    const uint8_t *d_frame_mask = nullptr;      // the caller's, read in place on every replay
+    FrameIntake intake;
+};
 
 struct nmi_level {
     nmi_ctx *ctx = nullptr;
@@ -52,7 +60,7 @@ struct nmi_level {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    // What the graph is captured from (level_capture), kept so that nmi_level_set_masks can capture it again.
+    // What the graph is captured from (level_capture), kept so that level_apply can capture it again.
     const float *d_xyz = nullptr, *d_attr = nullptr;
     int64_t n_points = 0;
     const nmi_texture *tex = nullptr;
@@ -61,35 +69,25 @@ struct nmi_level {
     float *hd_mvps = nullptr, *hd_coeffs = nullptr;
     int workgroups = 0;
     size_t pix_blocks_bytes = 0;
-    // Masks (nmi_level_set_masks): the warps' masks and counts of the latest replay, the counts of the replay before (tables are
-    // rebuilt only for the warps whose count changed), the per-warp term tables, the redo list of the masked grid kernel.
-    bool masked = false;
-    const uint8_t *d_frame_mask = nullptr;
+    // What the setters change, as one value (level_apply): masks (nmi_level_set_masks) or coverage (nmi_level_set_coverage, never
+    // both at once), their frame mask, and the frame's way in (nmi_level_set_distortion, _set_frame_format, _set_frame_reduction).
+    LevelSettings set;
+    // The buffers that go with the settings: level_buffers says which of them a setting needs, level_apply allocates and frees.
+    // Masked: the warps' masks and counts of the latest replay, the counts of the replay before (tables are rebuilt only for the
+    // warps whose count changed), the per-warp term tables, the redo list of the masked grid kernel.
     uint8_t *d_masks = nullptr;                 // [Wn][H][W]
     int32_t *d_counts = nullptr;                // [3][Wn]: counts, previous counts, changed flags
     float *d_tables = nullptr;                  // [Wn][npix + 1]
     int32_t *d_redo = nullptr;                  // [S * Wn]
     uint32_t *d_redo_state = nullptr;           // [2], zero between replays
-    // Coverage (nmi_level_set_coverage): the renders' coverage masks and len[w][s] of the latest replay; the warps' masks, the
-    // frame mask and the redo list are the masked level's fields above (a level is never masked and covered at once).
-    bool covered = false;
+    // Covered: the renders' coverage masks and len[w][s] of the latest replay; the warps' masks and the redo list are the masked
+    // level's fields above.
     uint8_t *d_rmasks = nullptr;                // [S][H][W], render layout
     int32_t *d_cover_counts = nullptr;          // [Wn][S]
-    // Lens distortion (nmi_level_set_distortion): d_frame (and d_frame_mask) are the raw frame; every replay undistorts it into
-    // d_ud (and, masked or covered, its mask into d_ud_mask), which the warps and their masks read instead.
-    bool distorted = false;
-    nmi::UndistortParams ud{};
-    uint8_t *d_ud = nullptr, *d_ud_mask = nullptr;  // [H][W] each, allocated by level_capture when first needed
-    // Frame format (nmi_level_set_frame_format): d_frame is H rows of frame_pitch bytes in frame_format; every replay converts it
-    // into d_ud (the level's grey frame; undistorted too when distorted, in the same node).
-    bool colored = false;
-    int32_t frame_format = NMI_FRAME_GRAY;
-    int64_t frame_pitch = 0;                    // row bytes (never 0 while colored)
-    // Frame reduction (nmi_level_set_frame_reduction): with frame_factor f > 1 (colored is then set) d_frame is f H rows of
-    // frame_pitch bytes holding f W pixels each, and the conversion node reduces it too: into d_ud, or, distorted, into d_small,
-    // which the undistortion node reads in d_frame's place.
-    int32_t frame_factor = 1;
-    uint8_t *d_small = nullptr;                 // [H][W], allocated by level_capture for a reduced and distorted level
+    // Distorted, coloured or reduced: d_frame (and d_frame_mask) are the camera's frame; every replay brings it into d_ud, the
+    // level's own grey frame (and, distorted and masked or covered, its mask into d_ud_mask), which the warps and their masks read
+    // instead.  Reduced and distorted: reduced into d_small, which the undistortion node reads in d_frame's place.
+    uint8_t *d_ud = nullptr, *d_ud_mask = nullptr, *d_small = nullptr;  // [H][W] each
 };
 
 extern "C" {
@@ -118,8 +116,47 @@ int nmi_level_destroy(nmi_level *lv)
 
 }  // extern "C"
 
-// Captures the level's graph (unmasked, masked when lv->masked, covered when lv->covered) and instantiates it, replacing the previous one only on
-// success.  The caller has waited for the stream.
+// Which of the level's setting buffers (struct nmi_level) a setting needs.  This is the one place that says so: level_apply
+// allocates and frees by it, level_capture reads by it.
+struct LevelNeeds {
+    bool mode;     // masked or covered: d_masks, d_redo, d_redo_state
+    bool masks;    // masked: d_counts, d_tables
+    bool cover;    // covered: d_rmasks, d_cover_counts
+    bool ud;       // the level's own grey frame
+    bool ud_mask;  // ... and its mask: undistorted, for the warps' masks
+    bool small;    // the reduced frame the undistortion node reads
+};
+
+static LevelNeeds level_needs(const LevelSettings &s)
+{
+    const bool mode = s.masked || s.covered;
+    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.reduced() && s.intake.distorted};
+}
+
+struct LevelBuffer {
+    void **slot;
+    size_t bytes, zeroed;  // its size, and how much of it starts as zero
+    bool needed;
+};
+
+static std::vector<LevelBuffer> level_buffers(nmi_level *lv, const LevelSettings &s)
+{
+    const LevelNeeds n = level_needs(s);
+    const size_t npix = (size_t)lv->ctx->npix, S = (size_t)lv->S, Wn = (size_t)lv->Wn, cells = S * Wn * sizeof(int32_t);
+    return {{(void **)&lv->d_masks, npix * Wn, npix * Wn, n.mode},
+            {(void **)&lv->d_redo, cells, 0, n.mode},
+            {(void **)&lv->d_redo_state, 2 * sizeof(uint32_t), 2 * sizeof(uint32_t), n.mode},
+            {(void **)&lv->d_counts, 3 * Wn * sizeof(int32_t), Wn * sizeof(int32_t), n.masks},
+            {(void **)&lv->d_tables, Wn * (npix + 1) * sizeof(float), 0, n.masks},
+            {(void **)&lv->d_rmasks, npix * S, npix * S, n.cover},
+            {(void **)&lv->d_cover_counts, cells, cells, n.cover},
+            {(void **)&lv->d_ud, npix, 0, n.ud},
+            {(void **)&lv->d_ud_mask, npix, 0, n.ud_mask},
+            {(void **)&lv->d_small, npix, 0, n.small}};
+}
+
+// Captures the level's graph for lv->set and instantiates it, replacing the previous one only on success.  The caller has waited
+// for the stream and holds the buffers lv->set needs (level_apply; a level as created needs none).
 static int level_capture(nmi_level *lv)
 {
     nmi_ctx *ctx = lv->ctx;
@@ -130,21 +167,15 @@ static int level_capture(nmi_level *lv)
     const float *d_xyz = lv->d_xyz, *d_attr = lv->d_attr, *d_red = lv->d_attr;
     const int64_t n_points = lv->n_points;
     float *hd_mvps = lv->hd_mvps, *hd_coeffs = lv->hd_coeffs;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) {
-        if (e == hipSuccess) e = r;
-        return r == hipSuccess;
-    };
+    FirstError ok;
     // Distorted or coloured: the chain reads the level's own grey (undistorted) frame (16-byte aligned: the fused front kernels
     // stay eligible) and, distorted and masked or covered, its mask.  A frame mask is dense [H][W] in every format.
-    const bool distorted = lv->distorted, want_ud_mask = distorted && (lv->masked || lv->covered);
-    const bool colored = lv->colored, own_frame = distorted || colored;
-    const bool reduced = lv->frame_factor > 1;  // (colored too)
-    if (own_frame && !lv->d_ud) ok(hipMalloc((void **)&lv->d_ud, (size_t)ctx->npix));
-    if (reduced && distorted && !lv->d_small && e == hipSuccess) ok(hipMalloc((void **)&lv->d_small, (size_t)ctx->npix));
-    if (want_ud_mask && !lv->d_ud_mask && e == hipSuccess) ok(hipMalloc((void **)&lv->d_ud_mask, (size_t)ctx->npix));
-    const uint8_t *d_frame = own_frame ? lv->d_ud : lv->d_frame;
-    const uint8_t *d_frame_mask = distorted ? (want_ud_mask ? lv->d_ud_mask : nullptr) : lv->d_frame_mask;
+    const LevelSettings &set = lv->set;
+    const FrameIntake &in = set.intake;
+    const bool masked = set.masked, covered = set.covered;
+    uint8_t *ud_mask = level_needs(set).ud_mask ? lv->d_ud_mask : nullptr;
+    const uint8_t *d_frame = in.own_frame() ? lv->d_ud : lv->d_frame;
+    const uint8_t *d_frame_mask = in.distorted ? ud_mask : set.d_frame_mask;
     nmi::GridArgs a = lv->args;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
@@ -158,18 +189,17 @@ static int level_capture(nmi_level *lv)
             lv->d_pix_blocks = nullptr;
             lv->pix_blocks_bytes = 0;
             ok(hipMalloc((void **)&lv->d_pix_blocks, bytes));
-            if (e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
-            if (e == hipSuccess) lv->pix_blocks_bytes = bytes;
+            if (ok.e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
+            if (ok.e == hipSuccess) lv->pix_blocks_bytes = bytes;
         }
-        if (e == hipSuccess && lv->args.epoch == 0 && next_split_epoch(ctx, &lv->args.epoch) != NMI_OK) e = hipErrorOutOfMemory;
-        if (e == hipSuccess && ensure_pix_timeouts(ctx) != NMI_OK) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
+        if (ok.e == hipSuccess && lv->args.epoch == 0 && next_split_epoch(ctx, &lv->args.epoch) != NMI_OK) ok.e = hipErrorOutOfMemory;
+        if (ok.e == hipSuccess && ensure_pix_timeouts(ctx) != NMI_OK) ok.e = hipErrorOutOfMemory;
+        if (ok.e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
         a.epoch = lv->args.epoch;
         a.blocks = lv->d_pix_blocks;
         a.order = nullptr;
     }
     const int workgroups = lv->workgroups;
-    const bool masked = lv->masked, covered = lv->covered;
     nmi::GridArgs ma = a;
     ma.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;  // (bit 9: the pixel-range kernel's hand-off test hook)
     const MaskSearch ms = mask_search_args(ma, lv->d_masks, covered ? lv->d_rmasks : nullptr, covered ? lv->d_cover_counts : lv->d_counts,
@@ -179,26 +209,13 @@ static int level_capture(nmi_level *lv)
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipStream_t st = ctx->stream;
-    if (e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
+    if (ok.e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
         // (mesh: nothing to clear -- the renderer leaves its work area clean)
         ok(nmi::launch_level_prep(hd_mvps, lv->d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, lv->d_coeffs, Wn * 9, lv->d_key, lv->d_zbuf,
                                   (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
-        if (reduced) {  // one node converts and reduces; distorted: the undistortion node reads the level's reduced frame
-            ok(nmi::launch_reduce(lv->d_frame, lv->frame_format, lv->frame_pitch, lv->frame_factor, distorted ? lv->d_small : lv->d_ud, p.width,
-                                  p.height, st));
-            if (distorted)
-                ok(nmi::launch_undistort(lv->ud, lv->d_small, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud,
-                                         want_ud_mask ? lv->d_ud_mask : nullptr, p.width, p.height, st));
-        } else if (distorted && colored)  // one node: each tap converted to grey, then the undistortion's arithmetic
-            ok(nmi::launch_undistort_color(lv->ud, lv->d_frame, lv->frame_format, lv->frame_pitch, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud,
-                                           want_ud_mask ? lv->d_ud_mask : nullptr, p.width, p.height, st));
-        else if (distorted)
-            ok(nmi::launch_undistort(lv->ud, lv->d_frame, want_ud_mask ? lv->d_frame_mask : nullptr, lv->d_ud, want_ud_mask ? lv->d_ud_mask : nullptr,
-                                     p.width, p.height, st));
-        else if (colored)
-            ok(nmi::launch_gray(lv->d_frame, lv->frame_format, lv->frame_pitch, lv->d_ud, p.width, p.height, st));
+        ok(launch_intake(in, lv->d_frame, in.frame_pitch, set.d_frame_mask, lv->d_small, lv->d_ud, ud_mask, p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
@@ -238,20 +255,59 @@ static int level_capture(nmi_level *lv)
         hipError_t ec = hipStreamEndCapture(st, &graph);
         ok(ec);
     }
-    if (e == hipSuccess) ok(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    if (e != hipSuccess) {
+    if (ok.e == hipSuccess) ok(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    if (ok.e != hipSuccess) {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
-        return hip_fail(ctx, e, "nmi_level (graph capture)");
+        return hip_fail(ctx, ok.e, "nmi_level (graph capture)");
     }
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
     lv->graph = graph;
     lv->exec = exec;
-    if (!want_ud_mask && lv->d_ud_mask) {  // masks / coverage off (or distortion off): no graph reads the undistorted mask now
-        (void)hipFree(lv->d_ud_mask);
-        lv->d_ud_mask = nullptr;
+    return NMI_OK;
+}
+
+// Every setter's transaction: the level takes the settings `next` and captures its graph again, or stays exactly as it was.
+// all_tables (nmi_level_set_masks, enabling): the new graph's first replay builds every warp's term table.
+static int level_apply(nmi_level *lv, const LevelSettings &next, const char *what, bool all_tables = false)
+{
+    nmi_ctx *ctx = lv->ctx;
+    ctx->detail.clear();
+    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
+        lv->set = next;
+        return NMI_OK;
     }
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
+    FirstError ok;
+    std::vector<void **> fresh;  // allocated by this call
+    for (const LevelBuffer &b : level_buffers(lv, next)) {
+        if (!b.needed || *b.slot || ok.e != hipSuccess) continue;
+        if (ok(hipMalloc(b.slot, b.bytes))) fresh.push_back(b.slot);
+        if (ok.e == hipSuccess && b.zeroed) ok(hipMemset(*b.slot, 0, b.zeroed));
+    }
+    // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
+    if (ok.e == hipSuccess && all_tables) ok(hipMemset(lv->d_counts + lv->Wn, 0xFF, (size_t)lv->Wn * sizeof(int32_t)));
+    int rc = ok.e == hipSuccess ? NMI_OK : hip_fail(ctx, ok.e, what);
+    const LevelSettings was = lv->set;
+    if (rc == NMI_OK) {
+        lv->set = next;
+        rc = level_capture(lv);
+    }
+    if (rc != NMI_OK) {
+        lv->set = was;
+        for (void **slot : fresh) {
+            (void)hipFree(*slot);
+            *slot = nullptr;
+        }
+        return rc;
+    }
+    for (const LevelBuffer &b : level_buffers(lv, lv->set))  // no graph reads these any more
+        if (!b.needed && *b.slot) {
+            (void)hipFree(*b.slot);
+            *b.slot = nullptr;
+        }
     return NMI_OK;
 }
 
@@ -305,19 +361,15 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     const nmi_params &p = ctx->params;
     const size_t npix = (size_t)ctx->npix;
     const int64_t total = (int64_t)S * Wn;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) {
-        if (e == hipSuccess) e = r;
-        return r == hipSuccess;
-    };
+    FirstError ok;
     ok(hipMalloc((void **)&lv->d_renders, npix * S));
     ok(hipMalloc((void **)&lv->d_warps, npix * Wn));
     lv->is_mesh = tex != nullptr;
     if (tex) {
-        if (mesh_work_alloc(ctx, S, &lv->mesh) != NMI_OK) e = hipErrorOutOfMemory;
-        if (e == hipSuccess && ensure_mesh_pairs(ctx, &lv->mesh, n_points) != NMI_OK) e = hipErrorOutOfMemory;
+        if (mesh_work_alloc(ctx, S, &lv->mesh) != NMI_OK) ok.e = hipErrorOutOfMemory;
+        if (ok.e == hipSuccess && ensure_mesh_pairs(ctx, &lv->mesh, n_points) != NMI_OK) ok.e = hipErrorOutOfMemory;
         ok(hipMalloc((void **)&lv->d_epoch, sizeof(uint32_t)));
-        if (e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
     } else {
         // Anchors: two buffers when the level runs as one chain of kernels (the front kernel of replay k clears the buffer of
         // replay k + 1); the classic form keeps one and clears it in its prep node.
@@ -327,13 +379,13 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
         ok(hipMalloc((void **)&lv->d_zbuf, words * sizeof(uint32_t)));
         ok(hipMalloc((void **)&lv->d_epoch, sizeof(uint32_t)));
         ok(hipMalloc(&lv->d_packed, nmi::cloud_pack_bytes(n_points, nullptr) + 16));
-        if (e == hipSuccess) ok(hipMemsetAsync(lv->d_zbuf, 0xFF, words * sizeof(uint32_t), ctx->stream));
-        if (e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
-        if (e == hipSuccess) ok(nmi::launch_cloud_pack(d_xyz, d_red, n_points, lv->d_packed, ctx->stream));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_zbuf, 0xFF, words * sizeof(uint32_t), ctx->stream));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
+        if (ok.e == hipSuccess) ok(nmi::launch_cloud_pack(d_xyz, d_red, n_points, lv->d_packed, ctx->stream));
         if (lv->fused_points) {
             ok(hipMalloc((void **)&lv->d_kept, (size_t)(2 * ((n_points + 63) / 64) + 1) * sizeof(uint32_t)));   // (twice the most one replay lists)
             ok(hipMalloc((void **)&lv->d_kept_count, 2 * sizeof(uint32_t)));
-            if (e == hipSuccess) ok(hipMemsetAsync(lv->d_kept_count, 0, 2 * sizeof(uint32_t), ctx->stream));
+            if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_kept_count, 0, 2 * sizeof(uint32_t), ctx->stream));
         }
     }
     ok(hipMalloc((void **)&lv->d_mvps, ((size_t)S * 16 + nmi::kLevelMvpExtra) * sizeof(float)));
@@ -349,9 +401,9 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     ok(hipStreamCreateWithFlags(&lv->side, hipStreamNonBlocking));
     ok(hipEventCreateWithFlags(&lv->ev_fork, hipEventDisableTiming));
     ok(hipEventCreateWithFlags(&lv->ev_join, hipEventDisableTiming));
-    int *order = e == hipSuccess ? new (std::nothrow) int[(size_t)total] : nullptr;
-    if (e != hipSuccess || !order) {
-        const int rc = e != hipSuccess ? hip_fail(ctx, e, "nmi_level_create") : NMI_ERR_INVALID_ARGUMENT;
+    int *order = ok.e == hipSuccess ? new (std::nothrow) int[(size_t)total] : nullptr;
+    if (ok.e != hipSuccess || !order) {
+        const int rc = ok.e != hipSuccess ? hip_fail(ctx, ok.e, "nmi_level_create") : NMI_ERR_INVALID_ARGUMENT;
         nmi_level_destroy(lv);
         return rc;
     }
@@ -382,7 +434,7 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     a.done = lv->d_done;
     float *hd_mvps = nullptr, *hd_coeffs = nullptr;
     unsigned long long *hd_key = nullptr;
-    if (e == hipSuccess) {
+    if (ok.e == hipSuccess) {
         ok(hipHostGetDevicePointer((void **)&hd_mvps, lv->h_mvps, 0));
         ok(hipHostGetDevicePointer((void **)&hd_coeffs, lv->h_coeffs, 0));
         ok(hipHostGetDevicePointer((void **)&hd_key, lv->h_key, 0));
@@ -392,7 +444,7 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     a.phase_mask = 3;
     const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     const int workgroups = (int)(total < cap ? total : cap);
-    // the graph (level_capture) is made from these; nmi_level_set_masks captures it again from them
+    // the graph (level_capture) is made from these; level_apply captures it again from them
     lv->d_xyz = d_xyz;
     lv->d_attr = d_attr;
     lv->n_points = n_points;
@@ -402,15 +454,15 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     lv->hd_mvps = hd_mvps;
     lv->hd_coeffs = hd_coeffs;
     lv->workgroups = workgroups;
-    if (e == hipSuccess) {
+    if (ok.e == hipSuccess) {
         const int rc = level_capture(lv);
         if (rc != NMI_OK) {
             nmi_level_destroy(lv);
             return rc;
         }
     }
-    if (e != hipSuccess) {
-        const int rc = hip_fail(ctx, e, "nmi_level_create");
+    if (ok.e != hipSuccess) {
+        const int rc = hip_fail(ctx, ok.e, "nmi_level_create");
         nmi_level_destroy(lv);
         return rc;
     }
@@ -538,73 +590,19 @@ int nmi_level_copy_outputs(nmi_level *lv, uint8_t *h_renders, uint8_t *h_warps, 
     return NMI_OK;
 }
 
-static void level_free_masks(nmi_level *lv)
-{
-    void *dev[] = {lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts};
-    for (void *q : dev)
-        if (q) (void)hipFree(q);
-    lv->d_rmasks = nullptr;
-    lv->d_cover_counts = nullptr;
-    lv->d_masks = nullptr;
-    lv->d_counts = nullptr;
-    lv->d_tables = nullptr;
-    lv->d_redo = nullptr;
-    lv->d_redo_state = nullptr;
-}
-
 int nmi_level_set_masks(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask)
 {
     if (!lv || (enabled != 0 && enabled != 1) || (!enabled && d_frame_mask)) return NMI_ERR_INVALID_ARGUMENT;
-    if (lv->covered) return NMI_ERR_INVALID_ARGUMENT;  // a covered level turns coverage off first (nmi_level_set_coverage)
-    nmi_ctx *ctx = lv->ctx;
-    ctx->detail.clear();
-    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
-        lv->masked = enabled != 0;
-        lv->d_frame_mask = d_frame_mask;
-        return NMI_OK;
-    }
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
-    const size_t npix = (size_t)ctx->npix, Wn = (size_t)lv->Wn;
-    if (enabled) {
-        if (!lv->d_masks) {
-            hipError_t e = hipSuccess;
-            auto ok = [&](hipError_t r) {
-                if (e == hipSuccess) e = r;
-            };
-            ok(hipMalloc((void **)&lv->d_masks, npix * Wn));
-            ok(hipMalloc((void **)&lv->d_counts, 3 * Wn * sizeof(int32_t)));
-            ok(hipMalloc((void **)&lv->d_tables, Wn * (npix + 1) * sizeof(float)));
-            ok(hipMalloc((void **)&lv->d_redo, (size_t)lv->S * Wn * sizeof(int32_t)));
-            ok(hipMalloc((void **)&lv->d_redo_state, 2 * sizeof(uint32_t)));
-            if (e == hipSuccess) ok(hipMemset(lv->d_masks, 0, npix * Wn));
-            if (e == hipSuccess) ok(hipMemset(lv->d_counts, 0, Wn * sizeof(int32_t)));
-            if (e == hipSuccess) ok(hipMemset(lv->d_redo_state, 0, 2 * sizeof(uint32_t)));
-            if (e != hipSuccess) {
-                level_free_masks(lv);
-                return hip_fail(ctx, e, "nmi_level_set_masks");
-            }
-        }
-        // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
-        NMI_HIP_TRY(ctx, hipMemset(lv->d_counts + Wn, 0xFF, Wn * sizeof(int32_t)));
-    }
-    const bool was = lv->masked;
-    const uint8_t *was_mask = lv->d_frame_mask;
-    lv->masked = enabled != 0;
-    lv->d_frame_mask = d_frame_mask;
-    const int rc = level_capture(lv);
-    if (rc != NMI_OK) {
-        lv->masked = was;
-        lv->d_frame_mask = was_mask;
-        return rc;
-    }
-    if (!enabled) level_free_masks(lv);
-    return NMI_OK;
+    if (lv->set.covered) return NMI_ERR_INVALID_ARGUMENT;  // a covered level turns coverage off first (nmi_level_set_coverage)
+    LevelSettings next = lv->set;
+    next.masked = enabled != 0;
+    next.d_frame_mask = d_frame_mask;
+    return level_apply(lv, next, "nmi_level_set_masks", next.masked);
 }
 
 int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts)
 {
-    if (!lv || !lv->masked) return NMI_ERR_INVALID_ARGUMENT;
+    if (!lv || !lv->set.masked) return NMI_ERR_INVALID_ARGUMENT;
     if (lv->S == 0 || lv->Wn == 0) return NMI_OK;  // empty block: nothing was produced
     nmi_ctx *ctx = lv->ctx;
     DeviceGuard guard(ctx->device);
@@ -617,59 +615,16 @@ int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts
 int nmi_level_set_coverage(nmi_level *lv, int32_t enabled, const uint8_t *d_frame_mask)
 {
     if (!lv || (enabled != 0 && enabled != 1) || (!enabled && d_frame_mask)) return NMI_ERR_INVALID_ARGUMENT;
-    if (lv->masked) return NMI_ERR_INVALID_ARGUMENT;  // a masked level turns its masks off first (nmi_level_set_masks)
-    nmi_ctx *ctx = lv->ctx;
-    ctx->detail.clear();
-    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph; it only takes part in the exchange
-        lv->covered = enabled != 0;
-        lv->d_frame_mask = d_frame_mask;
-        return NMI_OK;
-    }
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
-    const size_t npix = (size_t)ctx->npix, S = (size_t)lv->S, Wn = (size_t)lv->Wn;
-    // Turning coverage on for a level that is not covered: what a failed nmi_level_set_masks may have left behind is freed
-    // first, and what this call allocates is freed again if its capture fails -- so a level that is neither masked nor covered
-    // never holds mode buffers another mode's call would take for its own.
-    const bool fresh = enabled && !lv->covered;
-    if (fresh) {
-        level_free_masks(lv);
-        hipError_t e = hipSuccess;
-        auto ok = [&](hipError_t r) {
-            if (e == hipSuccess) e = r;
-        };
-        ok(hipMalloc((void **)&lv->d_masks, npix * Wn));
-        ok(hipMalloc((void **)&lv->d_rmasks, npix * S));
-        ok(hipMalloc((void **)&lv->d_cover_counts, S * Wn * sizeof(int32_t)));
-        ok(hipMalloc((void **)&lv->d_redo, S * Wn * sizeof(int32_t)));
-        ok(hipMalloc((void **)&lv->d_redo_state, 2 * sizeof(uint32_t)));
-        if (e == hipSuccess) ok(hipMemset(lv->d_masks, 0, npix * Wn));
-        if (e == hipSuccess) ok(hipMemset(lv->d_rmasks, 0, npix * S));
-        if (e == hipSuccess) ok(hipMemset(lv->d_cover_counts, 0, S * Wn * sizeof(int32_t)));
-        if (e == hipSuccess) ok(hipMemset(lv->d_redo_state, 0, 2 * sizeof(uint32_t)));
-        if (e != hipSuccess) {
-            level_free_masks(lv);
-            return hip_fail(ctx, e, "nmi_level_set_coverage");
-        }
-    }
-    const bool was = lv->covered;
-    const uint8_t *was_mask = lv->d_frame_mask;
-    lv->covered = enabled != 0;
-    lv->d_frame_mask = d_frame_mask;
-    const int rc = level_capture(lv);
-    if (rc != NMI_OK) {
-        lv->covered = was;
-        lv->d_frame_mask = was_mask;
-        if (fresh) level_free_masks(lv);
-        return rc;
-    }
-    if (!enabled) level_free_masks(lv);
-    return NMI_OK;
+    if (lv->set.masked) return NMI_ERR_INVALID_ARGUMENT;  // a masked level turns its masks off first (nmi_level_set_masks)
+    LevelSettings next = lv->set;
+    next.covered = enabled != 0;
+    next.d_frame_mask = d_frame_mask;
+    return level_apply(lv, next, "nmi_level_set_coverage");
 }
 
 int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_warp_masks, int32_t *h_counts)
 {
-    if (!lv || !lv->covered) return NMI_ERR_INVALID_ARGUMENT;
+    if (!lv || !lv->set.covered) return NMI_ERR_INVALID_ARGUMENT;
     if (lv->S == 0 || lv->Wn == 0) return NMI_OK;  // empty block: nothing was produced
     nmi_ctx *ctx = lv->ctx;
     DeviceGuard guard(ctx->device);
@@ -683,97 +638,25 @@ int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_w
 
 int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[5])
 {
-    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
-    nmi::UndistortParams ud{};
-    bool identity = true;
-    if (dist && undistort_params(K, dist, &ud, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    const bool on = dist && !identity;  // five zero coefficients: the never-distorted graph
-    nmi_ctx *ctx = lv->ctx;
-    ctx->detail.clear();
-    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph
-        lv->distorted = on;
-        lv->ud = ud;
-        return NMI_OK;
-    }
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
-    const bool was = lv->distorted;
-    const nmi::UndistortParams was_ud = lv->ud;
-    lv->distorted = on;
-    lv->ud = ud;
-    const int rc = level_capture(lv);
-    if (rc != NMI_OK) {
-        lv->distorted = was;
-        lv->ud = was_ud;
-        return rc;
-    }
-    if (!on) {
-        if (lv->d_ud && !lv->colored) {  // (a coloured level still converts into it)
-            (void)hipFree(lv->d_ud);
-            lv->d_ud = nullptr;
-        }
-        if (lv->d_ud_mask) (void)hipFree(lv->d_ud_mask);
-        lv->d_ud_mask = nullptr;
-        if (lv->d_small) (void)hipFree(lv->d_small);  // (a reduced level now reduces into d_ud)
-        lv->d_small = nullptr;
-    }
-    return NMI_OK;
+    // A bad K or dist is refused without reading *lv, as by nmi_stream_set_distortion (tests/test_undistort_api.py calls both
+    // with a handle that is not a level's): checked on a value of its own first, then set on the copy of the level's settings.
+    FrameIntake probe;
+    if (!lv || intake_set_distortion(&probe, K, dist) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    (void)intake_set_distortion(&next.intake, K, dist);
+    return level_apply(lv, next, "nmi_level_set_distortion");
 }
 
-}  // extern "C"
-
-// nmi_level_set_frame_format (factor 1) and nmi_level_set_frame_reduction: one setting, the later call wins.
-static int level_set_frame(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch)
+// nmi_level_set_frame_format is nmi_level_set_frame_reduction with factor 1: one setting, the later call wins.
+int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch)
 {
-    if (!lv || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
-    nmi_ctx *ctx = lv->ctx;
-    int64_t row_bytes = 0;
-    bool identity = true;
-    const int64_t full_width = (int64_t)factor * ctx->params.width;
-    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
-        return NMI_ERR_INVALID_ARGUMENT;
-    const bool on = !identity || factor > 1;  // dense grey of the search size: the never-formatted graph
-    ctx->detail.clear();
-    if (lv->S == 0 || lv->Wn == 0) {  // empty block: no graph
-        lv->colored = on;
-        lv->frame_format = on ? format : NMI_FRAME_GRAY;
-        lv->frame_pitch = on ? row_bytes : 0;
-        lv->frame_factor = factor;
-        return NMI_OK;
-    }
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
-    const bool was = lv->colored;
-    const int32_t was_format = lv->frame_format, was_factor = lv->frame_factor;
-    const int64_t was_pitch = lv->frame_pitch;
-    lv->colored = on;
-    lv->frame_format = on ? format : NMI_FRAME_GRAY;
-    lv->frame_pitch = on ? row_bytes : 0;
-    lv->frame_factor = factor;
-    const int rc = level_capture(lv);
-    if (rc != NMI_OK) {
-        lv->colored = was;
-        lv->frame_format = was_format;
-        lv->frame_pitch = was_pitch;
-        lv->frame_factor = was_factor;
-        return rc;
-    }
-    if (!on && !lv->distorted && lv->d_ud) {  // no graph reads the level's own frame now
-        (void)hipFree(lv->d_ud);
-        lv->d_ud = nullptr;
-    }
-    if (factor == 1 && lv->d_small) {
-        (void)hipFree(lv->d_small);
-        lv->d_small = nullptr;
-    }
-    return NMI_OK;
+    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    if (intake_set_frame(&next.intake, lv->ctx->params.width, factor, format, pitch) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    return level_apply(lv, next, "nmi_level_set_frame_reduction");
 }
 
-extern "C" {
-
-int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return level_set_frame(lv, 1, format, pitch); }
-
-int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch) { return level_set_frame(lv, factor, format, pitch); }
+int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return nmi_level_set_frame_reduction(lv, 1, format, pitch); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Streaming pipeline (config 5): double-buffered render stacks, copy stream beside the compute stream.
@@ -828,24 +711,16 @@ struct nmi_stream {
     uint8_t *d_rmasks = nullptr;                  // [max_S][H][W]
     int32_t *d_redo = nullptr;                    // [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
     uint32_t *d_redo_state = nullptr;             // [2], zero between searches
-    // Lens distortion (nmi_stream_set_distortion): frames submitted while it is on are undistorted on the compute stream into
-    // d_ud[b] (masked / covered: their masks into d_ud_mask[b]), and the warps are made from those.
-    bool distorted = false;
-    nmi::UndistortParams ud{};
+    // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction): frames submitted while one of them
+    // is set are brought on the compute stream into d_ud[b] (distorted, masked / covered: their masks into d_ud_mask[b]), and the
+    // warps are made from those.  A coloured, pitched or full-size host frame (intake.colored) crosses as its rows of
+    // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced and distorted, it is reduced into d_frame[b] (idle
+    // meanwhile), which the undistortion reads as a grey frame.
+    FrameIntake intake;
     uint8_t *d_ud[2] = {nullptr, nullptr};        // [H][W], allocated on the first distorted (or coloured) frame
     uint8_t *d_ud_mask[2] = {nullptr, nullptr};   // [H][W], allocated on the first distorted masked / covered frame
-    // Frame format (nmi_stream_set_frame_format): frames submitted while it is set cross as H rows of frame_pitch bytes into the
-    // dense colour slot d_color[b] and are converted on the compute stream into d_ud[b] (undistorted too, in the same node, when
-    // distorted); the warps are made from those.
-    bool colored = false;
-    int32_t frame_format = NMI_FRAME_GRAY;
-    int64_t frame_pitch = 0;                      // host row bytes (never 0 while colored)
-    uint8_t *d_color[2] = {nullptr, nullptr};     // [H][W * bytes per pixel], allocated on the first coloured frame
+    uint8_t *d_color[2] = {nullptr, nullptr};     // [f H][f W * bytes per pixel], allocated on the first coloured frame
     size_t color_bytes = 0;                       // their size
-    // Frame reduction (nmi_stream_set_frame_reduction): with frame_factor f > 1 (colored is then set) a host frame is f H rows of
-    // frame_pitch bytes holding f W pixels each; the colour slots hold it dense and full-size, and it is reduced on the compute
-    // stream into d_ud[b], or, distorted, into d_frame[b] (idle meanwhile), which the undistortion reads as a grey frame.
-    int32_t frame_factor = 1;
 };
 
 namespace {
@@ -941,13 +816,9 @@ int nmi_stream_create(nmi_ctx *ctx, int32_t max_S, int32_t max_Wn, int32_t depth
     st->max_Wn = max_Wn;
     st->slots = new (std::nothrow) nmi_stream::Slot[depth];
     const size_t npix = (size_t)ctx->npix;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) {
-        if (e == hipSuccess) e = r;
-        return r == hipSuccess;
-    };
+    FirstError ok;
     ok(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
-    for (int i = 0; st->slots && i < depth && e == hipSuccess; ++i) {
+    for (int i = 0; st->slots && i < depth && ok.e == hipSuccess; ++i) {
         nmi_stream::Slot &s = st->slots[i];
         ok(hipMalloc((void **)&s.d_renders, npix * max_S));
         ok(hipMalloc((void **)&s.d_key, 2 * sizeof(unsigned long long)));
@@ -955,14 +826,14 @@ int nmi_stream_create(nmi_ctx *ctx, int32_t max_S, int32_t max_Wn, int32_t depth
         ok(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
         ok(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
-    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+    for (int b = 0; b < 2 && ok.e == hipSuccess; ++b) {
         ok(hipMalloc((void **)&st->d_frame[b], npix));
         ok(hipMalloc((void **)&st->d_warps[b], npix * max_Wn));
         ok(hipEventCreateWithFlags(&st->warps_free[b], hipEventDisableTiming));
     }
     ok(hipEventCreateWithFlags(&st->frame_copied, hipEventDisableTiming));
-    if (!st->slots || e != hipSuccess) {
-        const int rc = st->slots ? hip_fail(ctx, e, "nmi_stream_create") : NMI_ERR_INVALID_ARGUMENT;
+    if (!st->slots || ok.e != hipSuccess) {
+        const int rc = st->slots ? hip_fail(ctx, ok.e, "nmi_stream_create") : NMI_ERR_INVALID_ARGUMENT;
         nmi_stream_destroy(st);
         return rc;
     }
@@ -1006,11 +877,10 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const int rc = stream_alloc_masks(st, kind);
         if (rc != NMI_OK) return rc;
     }
-    const bool undistort = h_frame && st->distorted, colored = h_frame && st->colored;
-    const int32_t format = st->frame_format;
-    const int32_t factor = st->frame_factor;
-    const bool reduced = colored && factor > 1;
-    const int64_t dense_row = (int64_t)factor * ctx->params.width * frame_bytes_per_pixel(format);
+    const FrameIntake in = st->intake;  // (this submission's: a later setter call does not reach it)
+    const bool undistort = h_frame && in.distorted, colored = h_frame && in.colored;
+    const int32_t factor = in.frame_factor;
+    const int64_t dense_row = (int64_t)factor * ctx->params.width * frame_bytes_per_pixel(in.frame_format);
     const size_t color_rows = (size_t)factor * ctx->params.height, color_need = (size_t)dense_row * color_rows;
     for (int b = 0; (undistort || colored) && b < 2; ++b) {
         if (!st->d_ud[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud[b], npix));
@@ -1037,7 +907,7 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         // the buffer being refilled was last read by searches submitted before the previous frame switch
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(st->copy, st->warps_free[nb], 0));
         if (colored)  // the rows of the host's pitch (H of them, or f H) into the dense colour slot
-            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)st->frame_pitch, (size_t)dense_row, color_rows,
+            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)in.frame_pitch, (size_t)dense_row, color_rows,
                                               hipMemcpyHostToDevice, st->copy));
         else
             NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
@@ -1046,24 +916,12 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
         if (st->have_warps) NMI_HIP_TRY(ctx, hipEventRecord(st->warps_free[st->warp_buf], ctx->stream));
         const uint8_t *frame = st->d_frame[nb], *frame_mask = h_frame_mask ? st->d_fmask[nb] : nullptr;
-        if (reduced)  // the full-size frame -> grey at the search size, on the compute stream; a frame mask is that size already
-            NMI_HIP_TRY(ctx, nmi::launch_reduce(st->d_color[nb], format, dense_row, factor, undistort ? st->d_frame[nb] : st->d_ud[nb],
-                                                ctx->params.width, ctx->params.height, ctx->stream));
-        if (undistort) {  // the raw frame (and mask) -> the undistorted ones, on the compute stream: the warps read them next
-            uint8_t *ud_mask = kind != kPlain ? st->d_ud_mask[nb] : nullptr;
-            if (colored && !reduced)  // converted and undistorted in one node
-                NMI_HIP_TRY(ctx, nmi::launch_undistort_color(st->ud, st->d_color[nb], format, dense_row, frame_mask, st->d_ud[nb], ud_mask,
-                                                             ctx->params.width, ctx->params.height, ctx->stream));
-            else
-                NMI_HIP_TRY(ctx, nmi::launch_undistort(st->ud, frame, frame_mask, st->d_ud[nb], ud_mask, ctx->params.width, ctx->params.height,
-                                                       ctx->stream));
-            frame = st->d_ud[nb];
-            frame_mask = ud_mask;
-        } else if (colored) {  // the colour frame -> grey, on the compute stream; a frame mask is dense already
-            if (!reduced)
-                NMI_HIP_TRY(ctx, nmi::launch_gray(st->d_color[nb], format, dense_row, st->d_ud[nb], ctx->params.width, ctx->params.height, ctx->stream));
-            frame = st->d_ud[nb];
-        }
+        // the camera's frame (and mask) -> the grey, undistorted ones, on the compute stream: the warps read them next
+        uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb] : nullptr;
+        NMI_HIP_TRY(ctx, launch_intake(in, colored ? st->d_color[nb] : st->d_frame[nb], dense_row, frame_mask, st->d_frame[nb], st->d_ud[nb],
+                                       ud_mask, ctx->params.width, ctx->params.height, ctx->stream));
+        if (in.own_frame()) frame = st->d_ud[nb];
+        if (undistort) frame_mask = ud_mask;
         int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, st->d_warps[nb])
                                 : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, st->d_warps[nb], st->d_wmasks[nb]);
         if (rc != NMI_OK) return rc;
@@ -1193,33 +1051,15 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
     return NMI_OK;
 }
 
+// The three frame settings: later frame submissions read them at their upload; tickets already submitted are not affected.
 int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5])
 {
-    if (!st) return NMI_ERR_INVALID_ARGUMENT;
-    nmi::UndistortParams ud{};
-    bool identity = true;
-    if (dist && undistort_params(K, dist, &ud, &identity) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    // later frame submissions take the map by value at their launch: tickets already submitted are not affected
-    st->distorted = dist && !identity;
-    st->ud = ud;
-    return NMI_OK;
+    return st ? intake_set_distortion(&st->intake, K, dist) : NMI_ERR_INVALID_ARGUMENT;
 }
 
 int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t format, int64_t pitch)
 {
-    if (!st || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
-    int64_t row_bytes = 0;
-    bool identity = true;
-    const int64_t full_width = (int64_t)factor * st->ctx->params.width;
-    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
-        return NMI_ERR_INVALID_ARGUMENT;
-    const bool on = !identity || factor > 1;
-    // later frame submissions read the setting at their upload: tickets already submitted are not affected
-    st->colored = on;
-    st->frame_format = on ? format : NMI_FRAME_GRAY;
-    st->frame_pitch = on ? row_bytes : 0;
-    st->frame_factor = factor;
-    return NMI_OK;
+    return st ? intake_set_frame(&st->intake, st->ctx->params.width, factor, format, pitch) : NMI_ERR_INVALID_ARGUMENT;
 }
 
 int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) { return nmi_stream_set_frame_reduction(st, 1, format, pitch); }

@@ -1,6 +1,7 @@
 // nmi_capi_reduce.cpp -- nmi_reduce_frame (include/nmi_hip.h): a full-size camera frame to the grey frame of the search size.
-// The captured levels and streams use the same kernels (nmi_capi_pipeline.cpp: nmi_level_set_frame_reduction,
-// nmi_stream_set_frame_reduction).  Kernels: nmi_reduce.hip; factor 1 is nmi_color.hip's conversion.
+// The captured levels and streams use the same kernels (nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction: both
+// through nmi_capi_intake.cpp's intake_set_frame and launch_intake).  Kernels: nmi_reduce.hip; factor 1 is nmi_color.hip's
+// conversion.
 #include "nmi_color.h"
 #include "nmi_ctx.h"
 #include "nmi_reduce.h"

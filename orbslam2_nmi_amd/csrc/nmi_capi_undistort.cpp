@@ -1,5 +1,6 @@
 // nmi_capi_undistort.cpp -- nmi_undistort_frame (include/nmi_hip.h) and the host side of the lens model the captured levels and
-// streams share (nmi_capi_pipeline.cpp: nmi_level_set_distortion, nmi_stream_set_distortion).  Kernel: nmi_undistort.hip.
+// streams share (nmi_level_set_distortion, nmi_stream_set_distortion: both through nmi_capi_intake.cpp's intake_set_distortion
+// and launch_intake).  Kernel: nmi_undistort.hip.
 #include "nmi_ctx.h"
 #include "nmi_undistort.h"
 

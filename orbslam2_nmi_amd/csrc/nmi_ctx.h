@@ -1,6 +1,6 @@
 // nmi_ctx.h -- internal: the context object behind include/nmi_hip.h and the helpers its translation units share
 // (nmi_capi.cpp: context + search; nmi_capi_producers.cpp: warp / render producers; nmi_capi_pipeline.cpp: captured level
-// and streaming pipeline; nmi_capi_rccl.cpp: the RCCL entry points).
+// and streaming pipeline; nmi_capi_intake.cpp: the frame's way into both; nmi_capi_rccl.cpp: the RCCL entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -231,6 +231,16 @@ int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int 
         hipError_t e_ = (call);                                 \
         if (e_ != hipSuccess) return nmi_internal::hip_fail((ctx), e_, #call); \
     } while (0)
+
+// The first error of a run of HIP calls: ok(call) keeps it in ok.e and says whether this call succeeded.
+struct FirstError {
+    hipError_t e = hipSuccess;
+    bool operator()(hipError_t r)
+    {
+        if (e == hipSuccess) e = r;
+        return r == hipSuccess;
+    }
+};
 
 struct DeviceGuard {
     int prev = -1;

@@ -1,0 +1,43 @@
+// nmi_intake.h -- internal: a camera frame's way into a captured level or a stream (nmi_capi_pipeline.cpp).  The frame may be
+// full-size (reduced to the search size), colour or pitched (converted to grey) and distorted (undistorted); FrameIntake is that
+// setting as one value, and launch_intake the one place that knows which of the steps share a kernel.  Definitions:
+// nmi_capi_intake.cpp.  The standalone calls (nmi_gray_frame, nmi_reduce_frame, nmi_undistort_frame) take explicit buffers and
+// launch the same kernels themselves.
+#pragma once
+#include "nmi_hip.h"
+#include "nmi_undistort.h"
+
+namespace nmi_internal {
+
+struct FrameIntake {
+    // Lens distortion (nmi_*_set_distortion): the source (and its mask) are the raw frame, undistorted into gray_out (mask_out).
+    bool distorted = false;
+    nmi::UndistortParams ud{};
+    // Frame format and reduction (nmi_*_set_frame_format, nmi_*_set_frame_reduction: one setting, the later call wins): the
+    // source is frame_factor * H rows of frame_pitch bytes, each frame_factor * W pixels in frame_format.
+    bool colored = false;                    // set: not a dense grey frame of the search size (always so with frame_factor > 1)
+    int32_t frame_format = NMI_FRAME_GRAY;
+    int64_t frame_pitch = 0;                 // row bytes (never 0 while colored)
+    int32_t frame_factor = 1;
+
+    bool reduced() const { return frame_factor > 1; }
+    bool own_frame() const { return distorted || colored; }  // the warps read gray_out, not the source
+};
+
+// dist == nullptr, or five zero coefficients: off.  A bad K or dist: NMI_ERR_INVALID_ARGUMENT, *in untouched.
+int intake_set_distortion(FrameIntake *in, const double K[9], const float dist[5]);
+// factor 1 .. 4, format and pitch checked on the full width factor * width (frame_format_check).  Dense grey of the search
+// size: off (NMI_FRAME_GRAY, pitch 0).  A bad argument: NMI_ERR_INVALID_ARGUMENT, *in untouched.
+int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch);
+
+// Enqueues the intake's kernels: src (rows of src_row_bytes) -> the dense grey [H][W] gray_out; nothing when !in.own_frame().
+//   reduced               launch_reduce, into scratch when distorted; then launch_undistort from scratch
+//   coloured, distorted   launch_undistort_color alone: each tap converted to grey, then the undistortion's arithmetic
+//   distorted             launch_undistort
+//   coloured              launch_gray
+// mask_out (may be null; only written when distorted) = the undistorted src_mask (dense [H][W], may be null: border only).
+// scratch is [H][W] and needed only when reduced and distorted.
+hipError_t launch_intake(const FrameIntake &in, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask, uint8_t *scratch,
+                         uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream);
+
+}  // namespace nmi_internal
