@@ -747,6 +747,12 @@ int nmi_last_kernel_ms(nmi_ctx *ctx, float *h_ms);
                                   phase); a matter of speed only */
 #define NMI_OPT_STAMPS 9       /* profiling tools only: value = device pointer to uint64 [workgroups][8]; workgroups of the
                                   split kernel store wall-clock stamps (100 MHz) at their phase boundaries there; 0 = off */
+#define NMI_OPT_STAMP_CANDIDATE 15 /* profiling tools only: the stamped nmi_grid_kernel (NMI_OPT_STAMPS on a grid search) stamps
+                                  every workgroup's k-th candidate, k = value (default 0: its first).  Waits for the stream. */
+#define NMI_OPT_WAVE_SHARES 16 /* profiling tools only: value = host pointer to uint32 [2][17], the cumulative shares (x 65536; 0
+                                  first, 65536 last, never falling) of a candidate's pixels that the 16 wavefronts of the stamped
+                                  nmi_grid_kernel take -- row 0 for a workgroup's first candidate, row 1 for its later ones.  The
+                                  product's kernels keep their built-in shares (csrc/nmi_grid_device.h).  Waits for the stream. */
 int nmi_set_option(nmi_ctx *ctx, int32_t option, int64_t value);
 
 /* Split-kernel liveness (see nmi_create): *timeouts = hand-off timeouts so far, *cooldown_calls_left = small-grid launches

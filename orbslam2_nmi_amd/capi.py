@@ -320,6 +320,7 @@ class NmiContext:
     OPT_HIST_VARIANT, OPT_PHASE_MASK, OPT_WORKGROUPS, OPT_RESULT_PATH, OPT_XCD_TILING, OPT_TILE_QUEUE = 1, 2, 3, 4, 5, 6
     OPT_SPLIT, OPT_WAIT_MODE, OPT_STAMPS, OPT_SPLIT_PIXELS, OPT_CLIP_QUEUE = 7, 8, 9, 10, 11
     OPT_PIX_OWNER_BIAS = 14
+    OPT_STAMP_CANDIDATE, OPT_WAVE_SHARES = 15, 16
     OPT_CONTENT_PATH, OPT_FEWLEVELS_BINS = 12, 13
 
     def set_option(self, option, value):

@@ -738,6 +738,16 @@ int nmi_set_option(nmi_ctx *ctx, int32_t option, int64_t value)
     case NMI_OPT_STAMPS:
         ctx->dbg_stamps = (unsigned long long *)(uintptr_t)value;
         return NMI_OK;
+    case NMI_OPT_STAMP_CANDIDATE:
+    case NMI_OPT_WAVE_SHARES:
+        if (option == NMI_OPT_STAMP_CANDIDATE ? (value < 0 || value > 65535) : value == 0) return NMI_ERR_INVALID_ARGUMENT;
+        {
+            DeviceGuard guard(ctx->device);
+            NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (option == NMI_OPT_STAMP_CANDIDATE) ctx->stamp_candidate = (int)value;
+            NMI_HIP_TRY(ctx, nmi::set_stamped_experiment(ctx->stamp_candidate, option == NMI_OPT_WAVE_SHARES ? (const uint32_t *)(uintptr_t)value : nullptr));
+        }
+        return NMI_OK;
     case NMI_OPT_WAIT_MODE:
         if (value < 0 || value > 1) return NMI_ERR_INVALID_ARGUMENT;
         ctx->wait_mode = (int)value;

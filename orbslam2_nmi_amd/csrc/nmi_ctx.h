@@ -105,6 +105,7 @@ struct nmi_ctx {
     size_t rank_bytes = 0;
     int last_few = 0;                     // the most recent launch went down the few-levels path (it may have fallen back)
     unsigned long long *dbg_stamps = nullptr;  // NMI_OPT_STAMPS
+    int stamp_candidate = 0;                   // NMI_OPT_STAMP_CANDIDATE
     int split_mode = -1;                  // NMI_OPT_SPLIT: -1 automatic, 0 never, 2 / 4 / 8 row parts whenever the grid fits, 1: pixel ranges only
     uint32_t *d_zbuf = nullptr;           // depth|colour anchor buffers of the point-cloud renderer (padded, per view)
     int64_t zbuf_cap = 0;

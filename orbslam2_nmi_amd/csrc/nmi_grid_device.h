@@ -263,10 +263,29 @@ __device__ __forceinline__ void add_chunk(Lds &lds, int par, const uint4 &rv, co
 // ry * width + 16 j of the render (unaligned 16-byte loads); the width % 16 pixels left at the end of every row are added one
 // by one after the loop.  c_end is then height * (width / 16).  (Through the byte path below such frames took 4.1x the time per
 // pixel: profiles/r04_a/odd_width_time.txt.)
-template <bool BG, bool SHIFTED, int HIST, int NT, bool FOLD = true, bool ROWS = false>
+//
+// SLABS (nmi_grid_kernel's hot loop only): shares of the chunks by wavefront age.  A SIMD serves its oldest wavefront first, so
+// with equal shares (chunk = c_first + tid + it * NT) wavefronts 0-3 were done at 12.4 us of a 21.7 us phase, 4-7 at 14.2, 8-11 at
+// 19.1, and the LDS unit spent the last 9 us fed by 12, 8, 4 wavefronts (profiles/r04_c/grid_stamps_27x27_clock.txt).  Instead
+// [c_first, c_end) is cut into 16 contiguous slabs, wavefront v walks slab v 64 chunks at a time (chunk = base[v] + it * 64 + lane),
+// and the slabs' lengths follow the rates the wavefronts really run at, so that all 16 end together.  Slab v is
+// [n * cum[v] >> 16, n * cum[v + 1] >> 16) of the n chunks: one scalar multiply and shift each, the end of one slab is the base
+// of the next, every chunk is covered once at any n.  Two rows of cumulative Q16 shares: a workgroup's first candidate, and its
+// later ones, where wavefront 0 scores the previous candidate (final_phase, ~2.5 us) before it adds its first pixel.
+// Calibrated on MI355X with tools/grid_stamps.py (profiles/NOTES.md, "Pixel shares by wavefront age"); a matter of speed only.
+#ifndef NMI_SLAB_SHARES_QUALIFIER
+#define NMI_SLAB_SHARES_QUALIFIER __constant__ const
+#endif
+NMI_SLAB_SHARES_QUALIFIER uint32_t slab_cum[2][kWaves + 1] = {
+    {0, 7048, 14096, 21145, 28193, 34369, 40546, 46722, 52899, 55010, 57120, 59231, 61342, 62390, 63439, 64487, 65536},
+    {0, 5934, 12896, 19858, 26820, 33147, 39384, 45621, 51859, 54448, 56633, 58818, 61003, 62222, 63327, 64431, 65536},
+};
+
+template <bool BG, bool SHIFTED, int HIST, int NT, bool FOLD = true, bool ROWS = false, bool SLABS = false>
 __device__ __forceinline__ void histogram_phase(Lds &lds, int par, const GridArgs &a, const uint8_t *__restrict__ render,
-                                                const uint8_t *__restrict__ warped, int tid, int c_first, int c_end)
+                                                const uint8_t *__restrict__ warped, int tid, int c_first, int c_end, bool later = false)
 {
+    static_assert(!SLABS || NT == kBlock, "slabs are per wavefront of a whole workgroup");
     if (ROWS || a.vec_ok) {
         // 16 pixels per lane per step: one 16-byte load from each image (1 KiB per wavefront instruction),
         // the next step's loads issued before this step's atomics.
@@ -296,31 +315,41 @@ __device__ __forceinline__ void histogram_phase(Lds &lds, int par, const GridArg
         // candidate (everything the fold needs inside this loop cost 5-11 % of the whole kernel).
         constexpr bool kHint = FOLD && HIST != 0;
         const bool try_flat = kHint && !(a.phase_mask & 4);  // bit 2: ablation switch (careful loop entered, nothing folded)
-        const int last = nchunks - 1;
-        const int iters = (nchunks - c_first + NT - 1) / NT;  // workgroup-uniform
-        int resume = (HIST == 1 && kHint) ? c_first + tid : -1;  // the exact path is cold anyway: careful from the start
+        // This lane walks the chunks first, first + kStep, ... below `stop`; prefetch indices are clamped to `last`.
+        constexpr int kStep = SLABS ? 64 : NT;
+        int base = c_first, stop = nchunks, first = c_first + tid;
+        if (SLABS) {  // this wavefront's slab [base, stop): wavefront-uniform (scalar)
+            const uint32_t v = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6), n = (uint32_t)(nchunks - c_first);
+            const uint32_t *cum = slab_cum[later ? 1 : 0];
+            base = c_first + (int)(((unsigned long long)n * cum[v]) >> 16);
+            stop = c_first + (int)(((unsigned long long)n * cum[v + 1]) >> 16);
+            first = base + (tid & 63);
+        }
+        const int last = SLABS ? max(stop, c_first + 1) - 1 : nchunks - 1;  // (an empty slab: still an address inside the images)
+        const int iters = (stop - base + kStep - 1) / kStep;  // wavefront-uniform
+        int resume = (HIST == 1 && kHint) ? first : -1;  // the exact path is cold anyway: careful from the start
         if (resume < 0) {
-            int ch = c_first + tid;
+            int ch = first;
             int c0 = min(ch, last);
             uint4 wa = ldw(c0), ra = ldr(c0), wb, rb;
             for (int it = 0; it < iters; it += 2) {
-                const int c1 = min(ch + NT, last);
+                const int c1 = min(ch + kStep, last);
                 wb = ldw(c1);
                 rb = ldr(c1);
                 if (kHint && __builtin_expect(flat_hint(ra, wa), 0)) {
                     resume = ch;
                     break;
                 }
-                if (ch < nchunks) add_chunk<BG, SHIFTED, HIST, false>(lds, par, ra, wa, a.shift, false);
-                const int c2 = min(ch + 2 * NT, last);
+                if (ch < stop) add_chunk<BG, SHIFTED, HIST, false>(lds, par, ra, wa, a.shift, false);
+                const int c2 = min(ch + 2 * kStep, last);
                 wa = ldw(c2);
                 ra = ldr(c2);
                 if (kHint && __builtin_expect(flat_hint(rb, wb), 0)) {
-                    resume = ch + NT;
+                    resume = ch + kStep;
                     break;
                 }
-                if (ch + NT < nchunks) add_chunk<BG, SHIFTED, HIST, false>(lds, par, rb, wb, a.shift, false);
-                ch += 2 * NT;
+                if (ch + kStep < stop) add_chunk<BG, SHIFTED, HIST, false>(lds, par, rb, wb, a.shift, false);
+                ch += 2 * kStep;
             }
         }
         if (resume >= 0) {
@@ -328,8 +357,8 @@ __device__ __forceinline__ void histogram_phase(Lds &lds, int par, const GridArg
             int c = min(resume, last);
             uint4 wc = ldw(c), rc = ldr(c);
 #pragma unroll 1
-            for (int ch = resume; ch < nchunks; ch += NT) {
-                const int cn = min(ch + NT, last);
+            for (int ch = resume; ch < stop; ch += kStep) {
+                const int cn = min(ch + kStep, last);
                 const uint4 wn = ldw(cn), rn = ldr(cn);
                 add_chunk<BG, SHIFTED, HIST, true>(lds, par, rc, wc, a.shift, try_flat);
                 wc = wn;

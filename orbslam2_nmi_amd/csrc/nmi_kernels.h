@@ -113,6 +113,9 @@ hipError_t launch_grid_gated(const GridArgs &a, int workgroups, bool use_bg, hip
 hipError_t launch_grid_rows(const GridArgs &a, int workgroups, bool use_bg, hipStream_t stream);
 // tools only (NMI_OPT_STAMPS): nmi_grid_kernel with wall-clock stamps at its phase boundaries (nmi_kernels_stamped.hip)
 hipError_t launch_grid_stamped(const GridArgs &a, int workgroups, hipStream_t stream);
+// ... which of a workgroup's candidates it stamps (its k-th), and, if cum != nullptr, the wavefronts' pixel shares it runs with:
+// [2][17] cumulative Q16 shares in place of slab_cum (nmi_grid_device.h).  The stamped kernel on the current device only.
+hipError_t set_stamped_experiment(int k, const uint32_t *cum);
 
 // Few-levels path (nmi_fewlevels_kernel.hip).  launch_levels probes the stacks (16-byte aligned, npix % 16 == 0) and
 // writes *plan (use = commit && nr * nw <= max_joint) and, if given, the pinned word *post = seq << 32 | nr << 16 | nw.

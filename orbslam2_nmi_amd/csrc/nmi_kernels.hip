@@ -38,7 +38,9 @@ namespace nmi {
 // this kernel sits at its register cap: the mere presence of more instantiations in this unit changed its allocation.
 //
 // nmi_kernels_stamped.hip compiles it a third time (NMI_GRID_KERNEL_STAMPED) as nmi_grid_kernel_stamped: the same code plus
-// wall-clock stamps of every workgroup's first candidate at the phase boundaries (NMI_OPT_STAMPS, tools/grid_stamps.py).
+// wall-clock stamps of one candidate of every workgroup -- its k-th, k = stamp_params.k, 0 by default -- at the phase
+// boundaries (NMI_OPT_STAMPS, NMI_OPT_STAMP_CANDIDATE, tools/grid_stamps.py).  In that unit the wavefronts' pixel shares
+// (slab_cum, nmi_grid_device.h) are a device variable that NMI_OPT_WAVE_SHARES overwrites: the calibration runs.
 #if defined(NMI_GRID_KERNEL_GATED)
 #define NMI_GRID_KERNEL_NAME nmi_grid_kernel_gated
 #elif defined(NMI_GRID_KERNEL_STAMPED)
@@ -51,12 +53,20 @@ namespace nmi {
 #ifdef NMI_GRID_KERNEL_STAMPED
 #define NMI_GRID_STAMP(k)                                                                                         \
     do {                                                                                                          \
-        if (a.dbg_stamps && tid == 0 && stamp_on) a.dbg_stamps[blockIdx.x * 8 + (k)] = wall_clock64();            \
+        if (a.dbg_stamps && tid == ((k) == 7 ? 64 : 0) && stamp_on) a.dbg_stamps[blockIdx.x * 8 + (k)] = wall_clock64(); \
     } while (0)
 #else
 #define NMI_GRID_STAMP(k) \
     do {                  \
     } while (0)
+#endif
+#ifndef NMI_WAVE_SLABS
+#define NMI_WAVE_SLABS 1  // 0: equal pixel shares for all wavefronts, as before the slabs (timing comparisons only)
+#endif
+#ifdef NMI_GRID_KERNEL_STAMPED
+namespace {
+__device__ uint32_t stamp_candidate = 0;  // which candidate of every workgroup is stamped (its k-th)
+}
 #endif
 template <bool BG, bool SHIFTED, int HIST>
 __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridArgs a)
@@ -69,7 +79,8 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
     const int lane = tid & 63;
     const int wave = tid >> 6;
 #ifdef NMI_GRID_KERNEL_STAMPED
-    bool stamp_on = true;  // first candidate of this workgroup only
+    bool stamp_on = true;  // inside the loop: the workgroup's k-th candidate only
+    const int stamp_ordinal = slot_in_round(blockIdx.x, gridDim.x) + (int)stamp_candidate * (int)gridDim.x;
 #endif
     NMI_GRID_STAMP(0);
     constexpr bool kOptimistic = HIST == 3;
@@ -87,6 +98,9 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
     // intensities 1 .. 2^shift - 1 (launch_grid sends BG off + shift to the exact path, HIST = 1).
     constexpr bool kZero0 = !BG && kOptimistic && !SHIFTED;
     constexpr bool kCountAll = BG || kZero0;
+    // Pixel shares by wavefront age (histogram_phase) where the fast loop runs; the exact-only instantiations (HIST = 1: careful
+    // loop from the first chunk, cold) keep equal shares, like exact_candidate -- the slabs cost them up to 60 bytes of scratch.
+    constexpr bool kSlabs = NMI_WAVE_SLABS != 0 && kFirst == 2;
 
     if (blockIdx.x == 0 && tid == 0 && a.reset_key) *a.reset_key = 0ull;  // next launch's slot; idle during this one
     // The LDS copy of the term table is first needed by the first decode phase: fetch it now, park it in
@@ -121,12 +135,16 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
         const int s = p - w * a.S_local;
         const uint8_t *render = a.render_stack + (size_t)s * a.npix;
         const uint8_t *warped = a.warp_stack + (size_t)w * a.npix;
+#ifdef NMI_GRID_KERNEL_STAMPED
+        stamp_on = ordinal == stamp_ordinal;
+#endif
+        NMI_GRID_STAMP(7);  // wavefront 1 starts on this candidate's pixels (wavefront 0 may have had the previous one to score)
 
         if (a.phase_mask & 1) {
             if (a.phase_mask & 8) {  // ablation: only half of the wavefronts take part in the histogram phase
                 if (wave < kWaves / 2) histogram_phase<kCountAll, SHIFTED, kFirst, kBlock / 2, true, kRows>(lds, par, a, render, warped, tid, 0, NMI_ALL_CHUNKS);
             } else
-                histogram_phase<kCountAll, SHIFTED, kFirst, kBlock, true, kRows>(lds, par, a, render, warped, tid, 0, NMI_ALL_CHUNKS);
+                histogram_phase<kCountAll, SHIFTED, kFirst, kBlock, true, kRows, kSlabs>(lds, par, a, render, warped, tid, 0, NMI_ALL_CHUNKS, ordinal != slot);
         }
         if (table_pending) {
 #pragma unroll
@@ -163,9 +181,6 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
             }
         }
         NMI_GRID_STAMP(5);  // score committed (wavefront 0)
-#ifdef NMI_GRID_KERNEL_STAMPED
-        stamp_on = false;
-#endif
     }
 
     if (kOptimistic && exact_from >= 0) {
@@ -211,6 +226,23 @@ hipError_t launch_grid_rows(const GridArgs &a, int workgroups, bool use_bg, hipS
 }
 #elif defined(NMI_GRID_KERNEL_STAMPED)
 // tools only: 256 bins, background rule on, default histogram variant
+// NMI_OPT_STAMP_CANDIDATE / NMI_OPT_WAVE_SHARES: k, and (or nullptr) the two rows of 17 cumulative Q16 shares that replace slab_cum
+// in this unit's kernel, for the current device.  Blocking.
+hipError_t set_stamped_experiment(int k, const uint32_t *cum)
+{
+    const uint32_t kk = (uint32_t)k;
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(stamp_candidate), &kk, sizeof kk);
+    if (e == hipSuccess && cum) {
+        for (int r = 0; r < 2; ++r)
+            for (int v = 0; v <= kWaves; ++v) {
+                const uint32_t c = cum[r * (kWaves + 1) + v];
+                if (c > 65536u || (v == 0 && c != 0u) || (v == kWaves && c != 65536u) || (v > 0 && c < cum[r * (kWaves + 1) + v - 1])) return hipErrorInvalidValue;
+            }
+        e = hipMemcpyToSymbol(HIP_SYMBOL(slab_cum), cum, 2 * (kWaves + 1) * sizeof(uint32_t));
+    }
+    return e;
+}
+
 hipError_t launch_grid_stamped(const GridArgs &a, int workgroups, hipStream_t stream)
 {
     if (a.hist_variant != 3 || a.shift != 0) return hipErrorInvalidValue;
