@@ -413,6 +413,29 @@ int nmi_render_mesh_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, 
                            const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks);
 
 /*
+ * Render-stack producer for vertex-coloured meshes (new): a triangle mesh with one colour per corner and no texture -- what
+ * Poisson / TSDF reconstructions and MeshLab, CloudCompare or Open3D exports ("v x y z r g b") hand out.  It stands for the draw
+ * the reference's Rendering<>::renderToTextureOnGPU (rendering.hpp:175,530-630) would make of such a mesh with
+ * shaders/ShadingWithColor.* -- the interpolated vertex colour passed straight through -- read back by glReadPixels(GL_RED)
+ * (rendering.hpp:520); the reference itself ships that shader for points only (allProperties.hpp:40: "other rendering options can
+ * be added").  No OpenGL.
+ *   nmi_render_mesh_colored  d_xyz float [3*T][3] as for nmi_render_mesh; d_red float [3*T]: the red component of each corner, in
+ *                            the order of d_xyz (nmi_map_load_obj_colored, include/nmi_host.h).  Everything in front of the
+ *                            fragment shader is nmi_render_mesh's: culling, near-plane clipping (the colour is cut as uv is),
+ *                            top-left fill rule, 24-bit depth with the triangle drawn first winning ties, background 255, at
+ *                            most 2^30 - 1 triangles.  Per pixel the colour is interpolated perspective-correctly,
+ *                            c = (red / w) / (1 / w) over the window as nmi_render_mesh interpolates u, and the grey level is
+ *                            the point renderer's colour rule: round(clamp(c, 0, 1) * 255), a NaN giving 0.
+ *   nmi_render_mesh_colored_masked   the same plus d_render_masks (see nmi_search_grid_covered above): 1 where a fragment won.
+ * Enqueued on the context's stream.  NMI_ERR_INVALID_ARGUMENT as for nmi_render_mesh (a NULL d_xyz or d_red with triangles to
+ * draw, S < 1, NULL outputs).  Parity with an OpenGL driver is unpinned (kernel comment, nmi_mesh.hip).
+ */
+int nmi_render_mesh_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const float *h_mvps, int32_t S,
+                            uint8_t *d_render_stack);
+int nmi_render_mesh_colored_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const float *h_mvps,
+                                   int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks);
+
+/*
  * Map order.  What the renderers draw does not depend on the order of the points / triangles (the depth test is a
  * minimum); how fast they draw does: neighbours in memory are culled together and their fragments share cache lines of the
  * depth buffer (3 M points into 27 views: 96 us in scan order, 406 us shuffled, 116 us after nmi_sort_points).  These two
@@ -424,6 +447,9 @@ int nmi_sort_points(nmi_ctx *ctx, const float *d_xyz /*[N][3]*/, const float *d_
                     float *d_red_out);
 int nmi_sort_triangles(nmi_ctx *ctx, const float *d_xyz /*[3*T][3]*/, const float *d_uv /*[3*T][2]*/, int64_t n_triangles,
                        float *d_xyz_out, float *d_uv_out);
+/* nmi_sort_triangles for a vertex-coloured mesh: the three colours of a triangle travel with its corners. */
+int nmi_sort_triangles_colored(nmi_ctx *ctx, const float *d_xyz /*[3*T][3]*/, const float *d_red /*[3*T]*/, int64_t n_triangles,
+                               float *d_xyz_out, float *d_red_out);
 
 /*
  * One whole search level on the device as a captured HIP graph: S renders of the cloud (nmi_render_points), Wn warps of the
@@ -444,6 +470,11 @@ int nmi_level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64
 /* The same with the textured mesh as the map (nmi_prop_RENDER 1): d_xyz / d_uv / tex as for nmi_render_mesh. */
 int nmi_level_create_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                           const uint8_t *d_frame, int32_t S, int32_t Wn, nmi_level **out);
+/* The same with a vertex-coloured mesh as the map: d_xyz / d_red as for nmi_render_mesh_colored, read in place (they must stay
+ * valid and unchanged).  A mesh level in every other respect: the same graph (prep -> binning + warp workgroups -> clip ->
+ * tiles -> search), and every nmi_level_* call below applies to it as to a textured one. */
+int nmi_level_create_mesh_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const uint8_t *d_frame,
+                                  int32_t S, int32_t Wn, nmi_level **out);
 int nmi_level_run(nmi_level *lv, const float *h_mvps, const double *h_forward, int64_t *h_best_index, float *h_best_score);
 /*
  * Level sharded over ranks (new; SURVEY.md 8e applied to the device-side level -- the LATENCY form of BASELINE.json configs[4]:
@@ -464,6 +495,9 @@ int nmi_level_create_block(nmi_ctx *ctx, const float *d_xyz, const float *d_red,
 int nmi_level_create_mesh_block(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                                 const uint8_t *d_frame, int32_t S_local, int32_t s_offset, int32_t S_total, int32_t Wn_local,
                                 int32_t w_offset, int32_t Wn_total, nmi_level **out);
+int nmi_level_create_mesh_colored_block(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const uint8_t *d_frame,
+                                        int32_t S_local, int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset,
+                                        int32_t Wn_total, nmi_level **out);
 int nmi_level_run_rccl(nmi_level *lv, const float *h_mvps, const double *h_forward, void *nccl_comm, int64_t *h_best_index,
                        float *h_best_score);
 /* Host copies of what the latest nmi_level_run produced: the S renders [S][H][W], the Wn warps [Wn][H][W] and the rating

@@ -151,11 +151,19 @@ int nmi_config_reduce(nmi_config *cfg, int32_t factor);
  *                     rgb (may be NULL) float [n][3], the whole scaled colour
  *   nmi_map_load_bmp  loadBMP_custom, texture.cpp:31-86: 24-bit uncompressed BMP -> uint8 [height][width][3] in file order
  *                     (row 0 = v 0) -- nmi_texture_create
+ *   nmi_map_load_obj_colored  (new; no loader of the reference reads this) an OBJ whose vertex lines carry a colour,
+ *                     "v x y z r g b" with r, g, b floats in [0, 1] as MeshLab, CloudCompare and Open3D write them, and
+ *                     triangular faces "f a b c" with corners in any of the forms a, a/b, a//c, a/b/c (only the position
+ *                     index a is used) -> one vertex per face corner: xyz float [n_vertices][3], red float [n_vertices] (the
+ *                     r column) -- nmi_render_mesh_colored; rgb (may be NULL) float [n_vertices][3], the whole colour, for a
+ *                     caller who wants a grey of their own in `red`'s place
  * Buffers are malloc'ed; release each with nmi_map_free.  Returns 0, or <0: -1 argument, -2 not in the format (an OBJ face
- * that is not three position/texcoord pairs, a point with fewer than six numbers, a BMP that is not 24-bit uncompressed or is
- * shorter than its header says), -3 OBJ index outside the file's lists, -5 file not readable, -6 out of memory.
+ * that is not three position/texcoord pairs -- coloured: not three corners --, a coloured OBJ's vertex line without its
+ * colour, a point with fewer than six numbers, a BMP that is not 24-bit uncompressed or is shorter than its header says),
+ * -3 OBJ index outside the file's lists, -5 file not readable, -6 out of memory.
  */
 int nmi_map_load_obj(const char *path, float **xyz, float **uv, int64_t *n_vertices);
+int nmi_map_load_obj_colored(const char *path, float **xyz, float **red, float **rgb, int64_t *n_vertices);
 int nmi_map_load_xyz(const char *path, const char *offset_path, float **xyz, float **red, float **rgb, int64_t *n_points);
 int nmi_map_load_bmp(const char *path, uint8_t **rgb, int32_t *width, int32_t *height);
 void nmi_map_free(void *p);

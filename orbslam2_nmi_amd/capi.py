@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "nmi_undistort_frame", "nmi_level_set_distortion", "nmi_stream_set_distortion",
     "nmi_gray_frame", "nmi_level_set_frame_format", "nmi_stream_set_frame_format",
     "nmi_reduce_frame", "nmi_level_set_frame_reduction", "nmi_stream_set_frame_reduction",
+    "nmi_render_mesh_colored", "nmi_render_mesh_colored_masked", "nmi_sort_triangles_colored", "nmi_level_create_mesh_colored",
+    "nmi_level_create_mesh_colored_block",
 )
 
 
@@ -117,6 +119,11 @@ def load_library(build_if_missing=False):
     lib.nmi_level_run.argtypes = [vp, f32p, C.POINTER(C.c_double), i64p, f32p]
     lib.nmi_level_create_block.argtypes = [vp, vp, vp, C.c_int64, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.POINTER(vp)]
     lib.nmi_level_create_mesh_block.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    lib.nmi_render_mesh_colored.argtypes = [vp, vp, vp, C.c_int64, f32p, i32, vp]
+    lib.nmi_render_mesh_colored_masked.argtypes = [vp, vp, vp, C.c_int64, f32p, i32, vp, vp]
+    lib.nmi_sort_triangles_colored.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
+    lib.nmi_level_create_mesh_colored.argtypes = [vp, vp, vp, C.c_int64, vp, i32, i32, C.POINTER(vp)]
+    lib.nmi_level_create_mesh_colored_block.argtypes = [vp, vp, vp, C.c_int64, vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     lib.nmi_level_run_rccl.argtypes = [vp, f32p, C.POINTER(C.c_double), vp, i64p, f32p]
     lib.nmi_stream_submit_block.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(C.c_double), i32, i32, i32, vp, i64p]
     lib.nmi_level_copy_outputs.argtypes = [vp, vp, vp, vp]
@@ -438,6 +445,20 @@ class NmiContext:
         self._check(self._lib.nmi_sort_triangles(self._h, xyz.data_ptr(), uv.data_ptr(), t, xo.data_ptr(), uo.data_ptr()), "nmi_sort_triangles")
         return xo, uo
 
+    def sort_triangles_colored(self, xyz, red):
+        """sort_triangles for a vertex-coloured mesh (device float32 [3T,3] corners, [3T] colours) -> copies in Morton order of the
+        centroids; a triangle's three colours travel with its corners."""
+        import torch
+        assert xyz.is_cuda and red.is_cuda and xyz.dtype == torch.float32 and red.dtype == torch.float32
+        xyz, red = xyz.contiguous(), red.contiguous()
+        t = xyz.shape[0] // 3
+        assert tuple(xyz.shape) == (3 * t, 3) and tuple(red.shape) == (3 * t,)
+        xo, ro = torch.empty_like(xyz), torch.empty_like(red)
+        self._order_after_torch()
+        self._check(self._lib.nmi_sort_triangles_colored(self._h, xyz.data_ptr(), red.data_ptr(), t, xo.data_ptr(), ro.data_ptr()),
+                    "nmi_sort_triangles_colored")
+        return xo, ro
+
     def warp_stack(self, frame, homographies, out=None, sync=True):
         """Image::calculateWarping (image.cpp:115-128) on the device: frame [H,W] u8 + forward homographies [Wn,3,3]
         (float64, host) -> warp stack [Wn,H,W] u8 (device).  Enqueued on the context's stream."""
@@ -740,6 +761,51 @@ class NmiContext:
                         "nmi_render_mesh_masked")
         return out
 
+    def render_mesh_colored(self, xyz, red, mvps, out=None, sync=True):
+        """A vertex-coloured mesh (nmi_render_mesh_colored): device float32 corner arrays xyz [3T,3] and red [3T] (one colour per
+        corner, no texture), host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
+        out = self._render_mesh_colored(xyz, red, mvps, out, None)
+        if sync:
+            self.synchronize()
+        return out
+
+    def render_mesh_colored_masked(self, xyz, red, mvps, out=None, out_masks=None, sync=True):
+        """render_mesh_colored plus its coverage (nmi_render_mesh_colored_masked) -> (renders [S,H,W] u8, masks [S,H,W]), as
+        render_mesh_masked."""
+        import torch
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        if out_masks is None:
+            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
+        om = self._mask_stack(out_masks, "out_masks")
+        if om.shape[0] != m.shape[0]:
+            raise ValueError("out_masks has the wrong number of views")
+        out = self._render_mesh_colored(xyz, red, m, out, om)
+        if sync:
+            self.synchronize()
+        return out, out_masks
+
+    def _render_mesh_colored(self, xyz, red, mvps, out, masks):
+        import torch
+        for t, dims in ((xyz, 2), (red, 1)):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != dims or (dims == 2 and t.shape[1] != 3):
+                raise TypeError("xyz / red must be contiguous float32 device tensors [3T,3] / [3T]")
+        if xyz.shape[0] != red.shape[0] or xyz.shape[0] % 3:
+            raise ValueError("xyz and red must hold three corners per triangle")
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        S = m.shape[0]
+        if out is None:
+            out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
+        o = self._stack(out, "out")
+        self._order_after_torch()
+        mp = m.ctypes.data_as(C.POINTER(C.c_float))
+        if masks is None:
+            self._check(self._lib.nmi_render_mesh_colored(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S, o.data_ptr()),
+                        "nmi_render_mesh_colored")
+        else:
+            self._check(self._lib.nmi_render_mesh_colored_masked(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S,
+                                                                 o.data_ptr(), masks.data_ptr()), "nmi_render_mesh_colored_masked")
+        return out
+
     def search_grid(self, render_stack, warp_stack, ratings=None):
         """Candidate loop + arg-max (Tracking.cc:1879-1905,1952).  -> (best linear index w*S+s, best score).
 
@@ -852,9 +918,10 @@ class NmiTexture:
 class NmiLevel:
     """nmi_level wrapper: cloud + frame -> renders, warps, search, winner as one captured HIP graph."""
 
-    def __init__(self, ctx, xyz, red, frame, S, Wn, point_size, texture=None, block=None):
+    def __init__(self, ctx, xyz, red, frame, S, Wn, point_size, texture=None, block=None, colors=False):
         """Point cloud: xyz [N,3], red [N], point_size.  Textured mesh: pass texture=NmiTexture, xyz [3T,3] corner
-        positions and `red` = uv [3T,2] (point_size is ignored).
+        positions and `red` = uv [3T,2] (point_size is ignored).  Vertex-coloured mesh: colors=True, xyz [3T,3] and red [3T],
+        no texture (point_size is ignored).
         block = (s_offset, S_total, w_offset, Wn_total): this level is one rank's block (S views x Wn warps, either may be 0)
         of a level sharded over ranks (nmi_level_create_block); winners then carry global indices."""
         self.ctx, self._lib = ctx, ctx._lib
@@ -865,7 +932,13 @@ class NmiLevel:
         if block is None:
             block = (0, self.S, 0, self.Wn)
         so, st, wo, wt = (int(v) for v in block)
-        if texture is None:
+        if colors:
+            if texture is not None:
+                raise ValueError("a vertex-coloured mesh level takes no texture")
+            ctx._check(self._lib.nmi_level_create_mesh_colored_block(ctx._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3,
+                                                                     frame.data_ptr(), self.S, so, st, self.Wn, wo, wt, C.byref(self._h)),
+                       "nmi_level_create_mesh_colored_block")
+        elif texture is None:
             ctx._check(self._lib.nmi_level_create_block(ctx._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0], frame.data_ptr(), self.S, so,
                                                         st, self.Wn, wo, wt, float(point_size), C.byref(self._h)), "nmi_level_create_block")
         else:

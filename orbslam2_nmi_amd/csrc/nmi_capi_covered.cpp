@@ -73,7 +73,7 @@ int nmi_render_mesh_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, 
                            const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks)
 {
     if (!ctx || !d_render_masks) return NMI_ERR_INVALID_ARGUMENT;
-    return render_mesh_impl(ctx, d_xyz, d_uv, n_triangles, tex, h_mvps, S, d_render_stack, d_render_masks);
+    return render_mesh_impl(ctx, MapKind::textured_mesh, d_xyz, d_uv, n_triangles, tex, h_mvps, S, d_render_stack, d_render_masks);
 }
 
 int nmi_pack_mask_bits(nmi_ctx *ctx, const uint8_t *d_masks, int32_t n, uint8_t *d_bits)

@@ -6,6 +6,7 @@
 #include "nmi_intake.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
+#include "nmi_mesh_color.h"
 #include "nmi_reduce.h"
 #include "nmi_undistort.h"
 
@@ -22,7 +23,7 @@ extern "C" {
 //           anchor buffer
 //   resolve sprites from anchors
 //   search  whose last workgroup stores the winner into pinned host memory.
-// (Textured mesh: prep -> binning + warp workgroups -> clip -> tiles -> search.  Where the warp cannot ride along -- frame rows
+// (Textured or vertex-coloured mesh: prep -> binning + warp workgroups -> clip -> tiles -> search.  Where the warp cannot ride along -- frame rows
 // not 16-byte aligned -- it runs on a forked branch.)  Only the pinned parameter buffers change between replays; the caller
 // polls the winner word.
 // ---------------------------------------------------------------------------------------------------------
@@ -42,8 +43,8 @@ struct nmi_level {
     uint8_t *d_renders = nullptr, *d_warps = nullptr;
     uint32_t *d_zbuf = nullptr;                 // point cloud: anchor buffer
     void *d_packed = nullptr;                   // point cloud: the level's own packed copy of the cloud (16-byte records + wavefront boxes)
-    nmi::MeshWork mesh;                         // textured mesh: the renderer's work area (kept clean by the renderer itself)
-    bool is_mesh = false;
+    nmi::MeshWork mesh;                         // either mesh kind: the renderer's work area (kept clean by the renderer itself)
+    MapKind kind = MapKind::points;             // what the level draws; d_attr below is red [N], uv [3T][2] or red [3T] accordingly
     bool fused_points = false;                  // point cloud, one chain of kernels, double-buffered anchors
     uint32_t *d_kept = nullptr, *d_kept_count = nullptr;  // ... and the wavefronts in reach of a view, listed by the prep kernel per replay
     uint32_t replay = 0;                        // parity of the counters the prep kernel counts under
@@ -164,6 +165,7 @@ static int level_capture(nmi_level *lv)
     const int S = lv->S, Wn = lv->Wn;
     const int64_t total = (int64_t)S * Wn;
     const nmi_texture *tex = lv->tex;
+    const bool mesh = lv->kind != MapKind::points;
     const float *d_xyz = lv->d_xyz, *d_attr = lv->d_attr, *d_red = lv->d_attr;
     const int64_t n_points = lv->n_points;
     float *hd_mvps = lv->hd_mvps, *hd_coeffs = lv->hd_coeffs;
@@ -212,13 +214,13 @@ static int level_capture(nmi_level *lv)
     if (ok.e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
         // (mesh: nothing to clear -- the renderer leaves its work area clean)
         ok(nmi::launch_level_prep(hd_mvps, lv->d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, lv->d_coeffs, Wn * 9, lv->d_key, lv->d_zbuf,
-                                  (tex || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
+                                  (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
         ok(launch_intake(in, lv->d_frame, in.frame_pitch, set.d_frame_mask, lv->d_small, lv->d_ud, ud_mask, p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
-        const bool fused = tex ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
+        const bool fused = mesh ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
         // Masked: the masks, their counts and the changed warps' tables on that branch too (they need the inverse maps only),
         // beside the render.  Covered: the masks alone (no counts, no tables: len[w][s] is counted by the search).
         if (!fused || masked || covered) {
@@ -233,7 +235,11 @@ static int level_capture(nmi_level *lv)
             if (covered) ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
-        if (tex)
+        if (lv->kind == MapKind::colored_mesh)
+            ok(nmi::launch_render_mesh_colored(d_xyz, d_attr, n_points, lv->d_mvps, S, lv->mesh, S,
+                                               (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit,
+                                               lv->d_renders, p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
+        else if (mesh)
             ok(nmi::launch_render_mesh(d_xyz, d_attr, n_points, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, lv->d_mvps, S, lv->mesh, S,
                                        (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
                                        p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
@@ -311,15 +317,16 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     return NMI_OK;
 }
 
-// Common part of nmi_level_create (tex == nullptr: coloured points, d_attr = red) and nmi_level_create_mesh (tex: textured
-// triangles, d_attr = uv, n = triangles).
+// Common part of nmi_level_create (kind points: d_attr = red), nmi_level_create_mesh (textured_mesh: d_attr = uv, tex, n =
+// triangles) and nmi_level_create_mesh_colored (colored_mesh: d_attr = red per corner, no texture, n = triangles).
 struct LevelBlock {
     int32_t S, s_offset, S_total, Wn, w_offset, Wn_total;
 };
 
-static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, int64_t n_points, const nmi_texture *tex,
+static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_points, const nmi_texture *tex,
                         const uint8_t *d_frame, const LevelBlock &blk, float point_size, nmi_level **out)
 {
+    const bool mesh = kind != MapKind::points;
     const float *d_red = d_attr;
     const int32_t S = blk.S, Wn = blk.Wn;
     if (!ctx || !out || !d_frame || S < 0 || Wn < 0 || n_points < 0 || (n_points > 0 && (!d_xyz || !d_attr)))
@@ -328,9 +335,9 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
         blk.w_offset + Wn > blk.Wn_total)
         return NMI_ERR_INVALID_ARGUMENT;
     if ((int64_t)blk.S_total * blk.Wn_total >= 0x7FFFFFFFll) return NMI_ERR_UNSUPPORTED;  // index lives in 32 bits of the key
-    if (tex && tex->ctx != ctx) return NMI_ERR_INVALID_ARGUMENT;
+    if (kind == MapKind::textured_mesh ? (!tex || tex->ctx != ctx) : tex != nullptr) return NMI_ERR_INVALID_ARGUMENT;
     int size = 1;  // (a mesh level has no point size)
-    if (!tex && point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (!mesh && point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     if (!ctx->params.use_bg) return NMI_ERR_UNSUPPORTED;
     *out = nullptr;
     ctx->detail.clear();
@@ -338,6 +345,7 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     nmi_level *lv = new (std::nothrow) nmi_level;
     if (!lv) return NMI_ERR_INVALID_ARGUMENT;
     lv->ctx = ctx;
+    lv->kind = kind;
     lv->S = S;
     lv->Wn = Wn;
     lv->s_offset = blk.s_offset;
@@ -364,8 +372,7 @@ static int level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_attr, i
     FirstError ok;
     ok(hipMalloc((void **)&lv->d_renders, npix * S));
     ok(hipMalloc((void **)&lv->d_warps, npix * Wn));
-    lv->is_mesh = tex != nullptr;
-    if (tex) {
+    if (mesh) {
         if (mesh_work_alloc(ctx, S, &lv->mesh) != NMI_OK) ok.e = hipErrorOutOfMemory;
         if (ok.e == hipSuccess && ensure_mesh_pairs(ctx, &lv->mesh, n_points) != NMI_OK) ok.e = hipErrorOutOfMemory;
         ok(hipMalloc((void **)&lv->d_epoch, sizeof(uint32_t)));
@@ -476,22 +483,29 @@ int nmi_level_create(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64
                      int32_t Wn, float point_size, nmi_level **out)
 {
     if (S <= 0 || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
-    return level_create(ctx, d_xyz, d_red, n_points, nullptr, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, point_size, out);
+    return level_create(ctx, MapKind::points, d_xyz, d_red, n_points, nullptr, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, point_size, out);
 }
 
 int nmi_level_create_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                           const uint8_t *d_frame, int32_t S, int32_t Wn, nmi_level **out)
 {
     if (!tex || S <= 0 || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
-    return level_create(ctx, d_xyz, d_uv, n_triangles, tex, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, 1.0f, out);
+    return level_create(ctx, MapKind::textured_mesh, d_xyz, d_uv, n_triangles, tex, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, 1.0f, out);
+}
+
+int nmi_level_create_mesh_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const uint8_t *d_frame, int32_t S,
+                                  int32_t Wn, nmi_level **out)
+{
+    if (S <= 0 || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    return level_create(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, 1.0f, out);
 }
 
 int nmi_level_create_block(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const uint8_t *d_frame, int32_t S_local,
                            int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float point_size,
                            nmi_level **out)
 {
-    return level_create(ctx, d_xyz, d_red, n_points, nullptr, d_frame, LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total},
-                        point_size, out);
+    return level_create(ctx, MapKind::points, d_xyz, d_red, n_points, nullptr, d_frame,
+                        LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total}, point_size, out);
 }
 
 int nmi_level_create_mesh_block(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
@@ -499,8 +513,16 @@ int nmi_level_create_mesh_block(nmi_ctx *ctx, const float *d_xyz, const float *d
                                 int32_t w_offset, int32_t Wn_total, nmi_level **out)
 {
     if (!tex) return NMI_ERR_INVALID_ARGUMENT;
-    return level_create(ctx, d_xyz, d_uv, n_triangles, tex, d_frame, LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total},
-                        1.0f, out);
+    return level_create(ctx, MapKind::textured_mesh, d_xyz, d_uv, n_triangles, tex, d_frame,
+                        LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total}, 1.0f, out);
+}
+
+int nmi_level_create_mesh_colored_block(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const uint8_t *d_frame,
+                                        int32_t S_local, int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset,
+                                        int32_t Wn_total, nmi_level **out)
+{
+    return level_create(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, d_frame,
+                        LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total}, 1.0f, out);
 }
 
 }  // extern "C"

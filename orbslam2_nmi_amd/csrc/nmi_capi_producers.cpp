@@ -1,6 +1,7 @@
 // nmi_capi_producers.cpp -- C ABI of the stack producers: warp stack, point-cloud and textured-mesh
-// render stacks.  Declared in include/nmi_hip.h.
+// render stacks, vertex-coloured-mesh render stacks.  Declared in include/nmi_hip.h.
 #include "nmi_ctx.h"
+#include "nmi_mesh_color.h"
 
 using namespace nmi_internal;
 
@@ -338,18 +339,32 @@ int nmi_texture_create(nmi_ctx *ctx, const uint8_t *h_rgb, int32_t tw, int32_t t
 int nmi_render_mesh(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex,
                     const float *h_mvps, int32_t S, uint8_t *d_render_stack)
 {
-    return render_mesh_impl(ctx, d_xyz, d_uv, n_triangles, tex, h_mvps, S, d_render_stack, nullptr);
+    return render_mesh_impl(ctx, MapKind::textured_mesh, d_xyz, d_uv, n_triangles, tex, h_mvps, S, d_render_stack, nullptr);
+}
+
+int nmi_render_mesh_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const float *h_mvps, int32_t S,
+                            uint8_t *d_render_stack)
+{
+    return render_mesh_impl(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, h_mvps, S, d_render_stack, nullptr);
+}
+
+int nmi_render_mesh_colored_masked(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, const float *h_mvps,
+                                   int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks)
+{
+    if (!ctx || !d_render_masks) return NMI_ERR_INVALID_ARGUMENT;
+    return render_mesh_impl(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, h_mvps, S, d_render_stack, d_render_masks);
 }
 
 }  // extern "C"
 
 namespace nmi_internal {
 
-int render_mesh_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex, const float *h_mvps,
-                     int32_t S, uint8_t *d_render_stack, uint8_t *cover)
+int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_triangles, const nmi_texture *tex,
+                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover)
 {
-    if (!ctx || !tex || tex->ctx != ctx || !h_mvps || !d_render_stack || S <= 0 || n_triangles < 0 ||
-        (n_triangles > 0 && (!d_xyz || !d_uv)))
+    const bool textured = kind == MapKind::textured_mesh;
+    if (!ctx || (textured ? (!tex || tex->ctx != ctx) : tex != nullptr) || !h_mvps || !d_render_stack || S <= 0 || n_triangles < 0 ||
+        (n_triangles > 0 && (!d_xyz || !d_attr)))
         return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
@@ -361,13 +376,16 @@ int render_mesh_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_
     float *d_mvps = nullptr;
     int rc = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (rc != NMI_OK) return rc;
-    const hipError_t e = nmi::launch_render_mesh(d_xyz, d_uv, n_triangles, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, d_mvps, S, ctx->mesh,
-                                                 ctx->mesh_views, (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit,
-                                                 d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr, nullptr,
-                                                 nullptr, 0, cover);
+    const int bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
+    const hipError_t e =
+        textured ? nmi::launch_render_mesh(d_xyz, d_attr, n_triangles, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, d_mvps, S, ctx->mesh, ctx->mesh_views,
+                                      bin_cap, ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
+                                      nullptr, nullptr, 0, cover)
+            : nmi::launch_render_mesh_colored(d_xyz, d_attr, n_triangles, d_mvps, S, ctx->mesh, ctx->mesh_views, bin_cap, ctx->clip_queue_limit,
+                                              d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr, nullptr, nullptr, 0, cover);
     if (e != hipSuccess) {
         ctx->mesh_views = 0;  // whatever state the buffers are in: allocate and clear afresh next time
-        return hip_fail(ctx, e, "launch_render_mesh");
+        return hip_fail(ctx, e, textured ? "launch_render_mesh" : "launch_render_mesh_colored");
     }
     return NMI_OK;
 }
@@ -393,6 +411,16 @@ int nmi_sort_triangles(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int6
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, nmi::sort_records_morton(d_xyz, 9, 3, d_uv, 6, n_triangles, d_xyz_out, d_uv_out, ctx->stream));
+    return NMI_OK;
+}
+
+int nmi_sort_triangles_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, float *d_xyz_out, float *d_red_out)
+{
+    if (!ctx || n_triangles < 0 || n_triangles >= (1ll << 32)) return NMI_ERR_INVALID_ARGUMENT;
+    if (n_triangles > 0 && (!d_xyz || !d_red || !d_xyz_out || !d_red_out || d_xyz == d_xyz_out || d_red == d_red_out)) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, nmi::sort_records_morton(d_xyz, 9, 3, d_red, 3, n_triangles, d_xyz_out, d_red_out, ctx->stream));
     return NMI_OK;
 }
 

@@ -219,11 +219,16 @@ bool split_launch_failed(nmi_ctx *ctx, int parts, uint32_t epoch);      // ... t
 int search_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_local, int32_t s_offset, int32_t S_total, const uint8_t *warp_stack,
                  int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float *d_ratings, uint64_t *d_key, uint64_t *h_key,
                  bool caller_checks);
-// nmi_render_points / nmi_render_mesh and their masked forms (nmi_capi_producers.cpp): cover = null, or the coverage masks
+// What a renderer or a level draws: a coloured point cloud (attribute: red [N]), a textured mesh (uv [3T][2] + texture) or a
+// vertex-coloured mesh (red [3T], no texture).
+enum class MapKind { points, textured_mesh, colored_mesh };
+// nmi_render_points / nmi_render_mesh / nmi_render_mesh_colored and their masked forms (nmi_capi_producers.cpp): cover = null,
+// or the coverage masks.  render_mesh_impl: kind is one of the two mesh kinds, d_attr its attribute array, tex the texture
+// (textured_mesh) or null (colored_mesh).
 int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
                        float point_size, uint8_t *d_render_stack, uint8_t *cover);
-int render_mesh_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, const nmi_texture *tex, const float *h_mvps,
-                     int32_t S, uint8_t *d_render_stack, uint8_t *cover);
+int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_triangles, const nmi_texture *tex,
+                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover);
 int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
                     int Wn);
 

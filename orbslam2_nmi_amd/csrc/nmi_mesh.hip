@@ -36,12 +36,26 @@
 // atomics.  Pixels won through the memory buffer (small triangles, bin overflow) carry slot 0x1FF and set their triangle up
 // on the fly.  The memory buffer and the bin counters are left clean by the tile kernel (it re-clears what it read), so a
 // render has no clear pass; tiles without small triangles never touch the buffer.
+//
+// NMI_MESH_COLOR (nmi_mesh_color.hip includes this file with it set): the same rasteriser for a mesh with one colour per corner
+// instead of a texture, as kernels of their own (nmi_mesh_*_color_kernel) behind launch_render_mesh_colored.  Everything up to the
+// last stage is this file's code unchanged; the attribute array is `red` [3T] where the textured build has `uv` [3T][2], the LDS
+// record carries one attribute plane, and the fragment shader is shade_color.  Without the macro this file compiles exactly as
+// it did before the coloured build existed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "nmi_kernels.h"
 #include "nmi_warp_device.h"
+#ifdef NMI_MESH_COLOR
+#include "nmi_mesh_color.h"
+// (no kernel calls across translation units: the coloured build has its own copies of the passes in front of the tile kernel)
+#define nmi_mesh_bin_kernel nmi_mesh_bin_color_kernel
+#define nmi_mesh_cull_kernel nmi_mesh_cull_color_kernel
+#define nmi_mesh_bin_pairs_kernel nmi_mesh_bin_pairs_color_kernel
+#define nmi_mesh_clip_kernel nmi_mesh_clip_color_kernel
+#endif
 
 namespace nmi {
 
@@ -249,7 +263,11 @@ __device__ __forceinline__ void load_tri(const float *__restrict__ xyz, const fl
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         px[k] = xyz[(tri * 3 + k) * 3], py[k] = xyz[(tri * 3 + k) * 3 + 1], pz[k] = xyz[(tri * 3 + k) * 3 + 2];
+#ifdef NMI_MESH_COLOR
+        tu[k] = uv[tri * 3 + k], tv[k] = 0.0f;   // `uv` is red [3T]: the colour takes u's way through the clipper and the planes, v's is dead code
+#else
         tu[k] = uv[(tri * 3 + k) * 2], tv[k] = uv[(tri * 3 + k) * 2 + 1];
+#endif
     }
 }
 
@@ -368,6 +386,21 @@ __device__ __forceinline__ uint32_t shade_pixel(const Planes &P, const float *__
     }
     return (uint32_t)(fminf(fmaxf(luma, 0.0f), 1.0f) * 255.0f + 0.5f);
 }
+
+#ifdef NMI_MESH_COLOR
+// The coloured fragment shader (shaders/ShadingWithColor.*: the interpolated vertex colour, passed through): c = S / Q with S the
+// plane of colour / w -- shade_pixel's u, by the same operations and the same reciprocal -- and the point renderer's grey rule
+// (nmi_producers.hip): clamp to [0, 1], times 255, rounded; fmaxf drops a NaN, so a NaN colour gives 0.
+__device__ __forceinline__ uint32_t shade_color(const Planes &P, float fxp, float fyp)
+{
+    const float dx = fxp - P.xr, dy = fyp - P.yr;
+    const float S = (P.sr0.x + P.srx.x * dx) + P.sry.x * dy;
+    const float Q = (P.q0 + P.qx * dx) + P.qy * dy;
+    const float iq = __builtin_expect(warp_rcp_ok(Q), 1) ? warp_rcp_fast(Q) : 1.0f / Q;
+    const float c = S * iq;
+    return (uint32_t)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f + 0.5f);
+}
+#endif
 
 __device__ __forceinline__ unsigned long long make_key(uint32_t depth, unsigned long long id /* triangle << 1 | piece */, uint32_t slot)
 {
@@ -752,8 +785,13 @@ enum : int {
     R_BOX_W = 12,   // the box's width | its pixels << 16
     R_FIRST = 13,   // box pixels of the records before this one
     R_ID = 14,      // triangle << 1 | piece
+#ifdef NMI_MESH_COLOR
+    R_PLANES = 16,  // xr, yr, s0, sx, sy, q0, qx, qy: one attribute plane
+    R_WORDS = 24,
+#else
     R_PLANES = 16,  // xr, yr, s0, r0, sx, rx, sy, ry, q0, qx, qy
     R_WORDS = 28,
+#endif
 };
 
 template <int BINMAX>
@@ -762,7 +800,9 @@ struct TileLds {
     uint32_t rec[BINMAX][R_WORDS];
     uint32_t wave_sum[kTileThreads / 64];
     uint32_t hdr[4];
+#ifndef NMI_MESH_COLOR
     TexLevel tex[16];
+#endif
 };
 
 // Where the key of tile pixel (x, y) lives: row y, rotated by 8 keys per row (a multiple of 4: a lane's four neighbouring
@@ -774,8 +814,34 @@ __device__ __forceinline__ int key_index(int x, int y) { return y * kTile + ((x 
 __device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
 {
     const float *f = reinterpret_cast<const float *>(r + R_PLANES);
+#ifdef NMI_MESH_COLOR
+    P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], 0.0f}, P.srx = v2f{f[3], 0.0f}, P.sry = v2f{f[4], 0.0f}, P.q0 = f[5], P.qx = f[6], P.qy = f[7];
+#else
     P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], f[3]}, P.srx = v2f{f[4], f[5]}, P.sry = v2f{f[6], f[7]}, P.q0 = f[8], P.qx = f[9], P.qy = f[10];
+#endif
 }
+
+__device__ __forceinline__ void planes_to_lds(const Planes &P, uint32_t *r)
+{
+    float *f = reinterpret_cast<float *>(r);
+#ifdef NMI_MESH_COLOR
+    f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.srx.x, f[R_PLANES + 4] = P.sry.x;
+    f[R_PLANES + 5] = P.q0, f[R_PLANES + 6] = P.qx, f[R_PLANES + 7] = P.qy;
+#else
+    f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.sr0.y, f[R_PLANES + 4] = P.srx.x;
+    f[R_PLANES + 5] = P.srx.y, f[R_PLANES + 6] = P.sry.x, f[R_PLANES + 7] = P.sry.y, f[R_PLANES + 8] = P.q0, f[R_PLANES + 9] = P.qx;
+    f[R_PLANES + 10] = P.qy;
+#endif
+}
+
+// What the last stage takes besides a fragment's planes: the texture (a kernel argument, its level table in LDS) -- or nothing.
+#ifdef NMI_MESH_COLOR
+#define MESH_TEX_PARAM
+#define MESH_SHADE(P, fxp, fyp) shade_color(P, fxp, fyp)
+#else
+#define MESH_TEX_PARAM MeshTexture tex,
+#define MESH_SHADE(P, fxp, fyp) shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, fxp, fyp)
+#endif
 
 }  // namespace
 
@@ -784,7 +850,7 @@ __device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
 template <int BINMAX, bool COVER = false>
 __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, const float *__restrict__ uv,
                                                                      const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                     int height, MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover = nullptr)
+                                                                     int height, MESH_TEX_PARAM BinGrid g, uint8_t *__restrict__ cover = nullptr)
 {
     __shared__ TileLds<BINMAX> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -797,7 +863,9 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
     // dependent round trips with a barrier between them; the key clear runs under their latency.
     const uint32_t c_raw = g.state[2 * (size_t)bin], f_raw = g.state[2 * (size_t)bin + 1];
     const uint32_t my_id = tid < g.cap ? g.bins[(size_t)bin * g.stride + tid] : 0u;   // (meaningful for tid < n only)
+#ifndef NMI_MESH_COLOR
     if (tid >= 64 && tid < 64 + tex.levels) tex_level_fill(tex, tid - 64, &lds.tex[tid - 64]);
+#endif
     for (int i = tid; i < kTile * kTile; i += kTileThreads) lds.keys[i] = kEmptyKey;
     const int n = (int)(c_raw < (uint32_t)g.cap ? c_raw : (uint32_t)g.cap);
     const bool from_memory = f_raw != 0u;
@@ -850,9 +918,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
 #pragma unroll
                 for (int k = 0; k < 3; ++k) f[R_XW + k] = t.xw[k], f[R_YW + k] = t.yw[k], f[R_ZW + k] = t.zw[k];
                 f[R_INV_AREA] = t.inv_area;
-                f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.sr0.y, f[R_PLANES + 4] = P.srx.x;
-                f[R_PLANES + 5] = P.srx.y, f[R_PLANES + 6] = P.sry.x, f[R_PLANES + 7] = P.sry.y, f[R_PLANES + 8] = P.q0, f[R_PLANES + 9] = P.qx;
-                f[R_PLANES + 10] = P.qy;
+                planes_to_lds(P, r);
                 r[R_OWN] = (t.own[0] ? 1u : 0u) | (t.own[1] ? 2u : 0u) | (t.own[2] ? 4u : 0u);
                 r[R_BOX] = (uint32_t)bx0 | ((uint32_t)by0 << 16);
                 const uint32_t nsteps = (uint32_t)(((bx1 - bx0 + 2) >> 1) * (by1 - by0 + 1));  // steps of the visibility walk: pairs of pixels in a row; at most 2048
@@ -968,8 +1034,10 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
         if (tid == 0) g.state[2 * (size_t)bin + 1] = 0u;
     }
     if (!col_ok) return;
+#ifndef NMI_MESH_COLOR
     TexLevel base_level;
     tex_level_fill(tex, 0, &base_level);   // from the kernel's arguments: scalar registers
+#endif
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const int y = oy + 32 * half;
@@ -1011,7 +1079,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 if (setup_piece(xyz, uv, (long long)(id >> 1), (int)(id & 1ull), mvps + s * 16, width, height, t, su, sv)) {  // (true: it produced this key)
                     Planes P;
                     tri_planes(t, su, sv, P);
-                    grey = shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                    grey = MESH_SHADE(P, (float)(ox + k) + 0.5f, (float)y + 0.5f);
                     if (COVER) covered |= 1u << (8 * k);
                 }
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
@@ -1025,7 +1093,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
             if ((key != kEmptyKey) & (ox + k < width) & !(g.dbg & 1)) {
                 Planes P;
                 planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
-                const uint32_t grey = shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                const uint32_t grey = MESH_SHADE(P, (float)(ox + k) + 0.5f, (float)y + 0.5f);
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
                 if (COVER) covered |= 1u << (8 * k);
             }
@@ -1045,6 +1113,28 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
     }
 }
 
+#ifdef NMI_MESH_COLOR
+// The coloured tile kernels.  One build, 255 bin entries per tile.  The 24-word record makes it 56 KB of LDS: two workgroups per
+// CU, as the textured one (a third needs 53.3 KB or less, i.e. 21 words a record; the visibility fields and the two planes are
+// 23).  A 127-entry build (44 KB) would fit three, but the body needs 86 registers (88 with coverage) and three workgroups allow
+// 80: under that cap it spills 28 / 52 bytes per lane, and uncapped it is two workgroups again -- so there is none
+// (profiles/mesh_color/NOTES.md).
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
+                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
+                                                                           int height, BinGrid g)
+{
+    mesh_tile_body<kBinMax>(xyz, red, mvps, out, width, height, g);
+}
+
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
+                                                                                 const float *__restrict__ mvps, uint8_t *__restrict__ out,
+                                                                                 int width, int height, BinGrid g, uint8_t *__restrict__ cover)
+{
+    mesh_tile_body<kBinMax, true>(xyz, red, mvps, out, width, height, g, cover);
+}
+
+void mesh_geometry(int S, int width, int height, int *tiles_x, int *tiles_y, int *stride);   // (defined by nmi_mesh.hip's own build)
+#else
 // Two builds of the tile kernel.  The usual one holds 255 bin entries per tile (62 KB of LDS: two workgroups per CU).  For a mesh
 // whose tiles cannot fill that -- launch_render_mesh decides from the triangle count -- the small one holds 127 (48 KB) and is
 // held to 80 registers, so that THREE workgroups share a CU: the kernel spends half its wave-cycles waiting (set-up, barriers,
@@ -1128,11 +1218,19 @@ hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hi
 }
 
 size_t mesh_pairs_entries(long long ntri) { return (size_t)((ntri + 255) / 256) * kMaxViewsPerLaunch; }
+#endif  // NMI_MESH_COLOR
 
+#ifdef NMI_MESH_COLOR
+hipError_t launch_render_mesh_colored(const float *xyz, const float *uv /* red [3T] */, long long ntri, const float *mvps, int S, const MeshWork &w,
+                                      int layout_views, int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height,
+                                      hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn,
+                                      uint8_t *cover)
+#else
 hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri, const float *luma, int levels, const int *lw,
                               const int *lh, const long long *loff, const float *mvps, int S, const MeshWork &w, int layout_views,
                               int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
                               const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover)
+#endif
 {
     if (S > layout_views) return hipErrorInvalidValue;
     WarpFuse wf{warp_frame, warp_coeffs, warp_out, 0};
@@ -1142,11 +1240,13 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
     }
     if (ntri >= (1ll << 30) || width > 65535 || height > 65535) return hipErrorInvalidValue;  // triangle and piece share 31 bits of a key
     if (!w.zbuf || !w.bins || !w.state || !w.clip_queue || !w.clip_state) return hipErrorInvalidValue;
+#ifndef NMI_MESH_COLOR
     MeshTexture tex{};
     tex.luma = luma;
     tex.levels = levels;
     for (int l = 0; l < levels && l < 16; ++l)
         tex.w[l] = lw[l], tex.h[l] = lh[l], tex.off[l] = loff[l], tex.inv_w[l] = 1.0f / (float)lw[l], tex.inv_h[l] = 1.0f / (float)lh[l];
+#endif
     BinGrid g{};
     static const int dbg = getenv("NMI_MESH_DBG") ? atoi(getenv("NMI_MESH_DBG")) : 0;
     g.dbg = dbg;
@@ -1154,11 +1254,13 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
     g.cap = g.stride - 1 < bin_cap_limit ? g.stride - 1 : bin_cap_limit;
     if (g.cap < 0) g.cap = 0;
     const int tiles = g.tiles_x * g.tiles_y;
+#ifndef NMI_MESH_COLOR
     // The small tile kernel (127 entries per tile, three workgroups per CU) for meshes that could not fill more even if every
     // triangle were in view and touched two tiles; a fuller bin than its capacity takes the per-lane path as always.
     static const bool no_small = getenv("NMI_MESH_NO_SMALL_TILES") != nullptr;   // measurement switch
     const bool small_tiles = !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
     if (small_tiles && g.cap > kBinSmall - 1) g.cap = kBinSmall - 1;
+#endif
     const unsigned long long clip_cap = w.clip_cap < clip_cap_limit ? w.clip_cap : clip_cap_limit;
     for (int s0 = 0; s0 < S; s0 += kMaxViewsPerLaunch) {
         const int views = S - s0 < kMaxViewsPerLaunch ? S - s0 : kMaxViewsPerLaunch;
@@ -1196,6 +1298,14 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
             hipLaunchKernelGGL(nmi_mesh_clip_kernel, dim3(64), dim3(256), 0, stream, xyz, uv, ntri, mvps + (size_t)s0 * 16, views, width,
                                height, g, clipq, w.clip_state, clip_cap, w.pair_state);
         }
+#ifdef NMI_MESH_COLOR
+        if (cover)
+            hipLaunchKernelGGL(nmi_mesh_tile_color_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
+                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, g, cover + (size_t)s0 * width * height);
+        else
+            hipLaunchKernelGGL(nmi_mesh_tile_color_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
+                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, g);
+#else
         if (cover && small_tiles)
             hipLaunchKernelGGL(nmi_mesh_tile_small_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
                                mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g, cover + (size_t)s0 * width * height);
@@ -1208,6 +1318,7 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
         else
             hipLaunchKernelGGL(nmi_mesh_tile_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv, mvps + (size_t)s0 * 16,
                                out + (size_t)s0 * width * height, width, height, tex, g);
+#endif
     }
     return hipGetLastError();
 }

@@ -17,6 +17,7 @@ EXPORTED_SYMBOLS = (
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
     "nmi_config_parse_distortion", "nmi_config_load_distortion",
     "nmi_config_parse_color_order", "nmi_config_load_color_order", "nmi_config_reduce",
+    "nmi_map_load_obj_colored",
 )
 
 
@@ -109,6 +110,7 @@ def _lib():
         fpp, i64p = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)
         lib.nmi_map_load_obj.argtypes = [C.c_char_p, fpp, fpp, i64p]
         lib.nmi_map_load_xyz.argtypes = [C.c_char_p, C.c_char_p, fpp, fpp, fpp, i64p]
+        lib.nmi_map_load_obj_colored.argtypes = [C.c_char_p, fpp, fpp, fpp, i64p]
         lib.nmi_map_load_bmp.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.nmi_map_free.argtypes = [C.c_void_p]
         lib.nmi_map_free.restype = None
@@ -266,6 +268,16 @@ def load_obj(path):
     if rc != 0:
         raise ValueError(f"nmi_map_load_obj({path}) failed: {rc}")
     return _take(xyz, (n.value, 3), np.float32), _take(uv, (n.value, 2), np.float32)
+
+
+def load_obj_colored(path):
+    """An OBJ with "v x y z r g b" vertex lines -> (xyz float32 [3T,3], red float32 [3T], rgb float32 [3T,3]): the per-corner
+    arrays of nmi_render_mesh_colored (red) and the whole colour."""
+    xyz, red, rgb, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int64()
+    rc = _lib().nmi_map_load_obj_colored(str(path).encode(), C.byref(xyz), C.byref(red), C.byref(rgb), C.byref(n))
+    if rc != 0:
+        raise ValueError(f"nmi_map_load_obj_colored({path}) failed: {rc}")
+    return _take(xyz, (n.value, 3), np.float32), _take(red, (n.value,), np.float32), _take(rgb, (n.value, 3), np.float32)
 
 
 def load_xyz(path, offset_path):
