@@ -812,7 +812,7 @@ const char *nmi_error_string(int code);
 const char *nmi_last_error_detail(nmi_ctx *ctx); /* text of the last failing HIP/RCCL call, or "" */
 int nmi_get_info(nmi_ctx *ctx, int32_t *compute_units, int32_t *workgroups_per_launch, int32_t *lds_bytes);
 /* How the most recent search was scored (waits for it): *few_levels = 1 if it was sent down the few-levels path
- * (NMI_OPT_CONTENT_PATH) AND stayed there, 0 if the general kernel scored it; *nr, *nw = distinct intensities the most
+ * (NMI_OPT_CONTENT_PATH) AND stayed there (the device's own verdict, read back), 0 if the general kernel scored it; *nr, *nw = distinct intensities the most
  * recent probe found in a render / warp stack (0, 0 before the first probe).  Any pointer may be null.  Diagnostics. */
 int nmi_last_content(nmi_ctx *ctx, int32_t *few_levels, int32_t *nr, int32_t *nw);
 

@@ -840,8 +840,15 @@ int nmi_last_content(nmi_ctx *ctx, int32_t *few_levels, int32_t *nr, int32_t *nw
     const int32_t r = (int32_t)((posted >> 16) & 0xFFFFu), w = (int32_t)(posted & 0xFFFFu);
     if (nr) *nr = r;
     if (nw) *nw = w;
-    // a few-levels launch carries its own probe, so the post is about that very search
-    if (few_levels) *few_levels = (ctx->last_few && r > 0 && w > 0 && (int64_t)r * w <= ctx->fewlevels_bins) ? 1 : 0;
+    // a few-levels launch carries its own probe, so the post is about that very search -- and the probe's verdict
+    // (LevelPlan::use, untouched since: the stream is idle) is what let one of the two scoring kernels behind it run.  Read it,
+    // do not restate it: a restatement on the host agrees with any device-side slip at the limit.
+    uint32_t use = 0;
+    if (few_levels && ctx->last_few) {
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(&use, &ctx->d_plan->use, sizeof use, hipMemcpyDeviceToHost, ctx->stream));
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (few_levels) *few_levels = use ? 1 : 0;
     return NMI_OK;
 }
 
