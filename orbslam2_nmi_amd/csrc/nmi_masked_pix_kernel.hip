@@ -3,11 +3,12 @@
 // per-warp masks and term tables.  nmi_masked_grid_kernel gives a candidate to one workgroup, so 81 candidates fill 81 of
 // the 256 CUs; here they fill 243.
 //
-// Reused: the dealing (make_deal, pix_dealing), the hand-off blocks (PixHeader, unit layout, tagged mask granules), the owner's
-// merged decode (decode_merged) and final trees (final_phase_owner) from nmi_pix_device.h; the masked chunk and pixel forms
-// (masked_add_chunk: whole-chunk test, then add_chunk unchanged, per-pixel predication only on mixed chunks;
-// masked_histogram_phase for the exact path) from nmi_mask_device.h.  Written out here: the hand-off itself (a TWIN of
-// nmi_pix_kernel's, see there).  Results are bit-identical to nmi_masked_grid_kernel's: the
+// The kernel below is a sequence of steps shared with the other two pixel-range kernels (nmi_pix_device.h): pix_unit,
+// clear_counters, the masked dealt loop (masked_histogram_dealt, which the covered kernel uses with both masks; it adds with
+// masked_add_chunk of nmi_mask_device.h: whole-chunk test, then add_chunk unchanged, per-pixel predication only on mixed
+// chunks), the hand-off (pix_publish / pix_collect, with the range's pixel count in the header where nmi_pix_kernel sends side
+// counters), the owner's merged decode (decode_merged with TableTerms) and final trees (final_phase_owner); the heal runs the
+// exact path of nmi_mask_device.h (masked_histogram_phase).  Results are bit-identical to nmi_masked_grid_kernel's: the
 // decoded counters are the same sums, the trees the same code, the terms the same table.
 //
 // What differs from nmi_pix_kernel, and why:
@@ -29,93 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nmi_mask_device.h"  // masked_add_chunk, masked_histogram_phase, nonzero_byte_bits
-#include "nmi_pix_device.h"   // Deal, make_deal, PixHeader, decode_merged, final_phase_owner
+#include "nmi_mask_device.h"  // masked_histogram_phase (the exact path)
+#include "nmi_pix_device.h"   // pix_unit, clear_counters, masked_histogram_dealt, pix_publish / pix_collect, decode_merged, final_phase_owner
 
 namespace nmi {
 
-namespace {
-
-__device__ __forceinline__ uint32_t mask_popc(const uint4 &m)
-{
-    return __popc(nonzero_byte_bits(m.x)) + __popc(nonzero_byte_bits(m.y)) + __popc(nonzero_byte_bits(m.z)) + __popc(nonzero_byte_bits(m.w));
-}
-
-// This workgroup's dealt pieces (histogram_dealt's addressing, nmi_pix_kernel.hip) with the warp's mask, non-returning atomics.
-// Returns the pixels this lane added.
-template <bool SHIFTED>
-__device__ __forceinline__ uint32_t masked_histogram_dealt(Lds &lds, const GridArgs &a, const uint8_t *__restrict__ render,
-                                                          const uint8_t *__restrict__ warped, const uint8_t *__restrict__ mask, int wave,
-                                                          int lane, const Deal &d)
-{
-    const int nchunks = a.height * a.chunks_per_row, last = nchunks - 1, row_rem = a.width - (a.chunks_per_row << 4);
-    auto at = [&](int c) {  // byte of chunk c in the frame (and in the mask: same layout)
-        c = min(c, last);
-        return ((uint32_t)c << 4) + (uint32_t)__mul24((int)__umulhi((uint32_t)c, a.cpr_magic), row_rem);
-    };
-    auto ldr = [&](int c) {  // NMI.cu:82: row y of the frame meets row H-1-y of a bottom-up render
-        c = min(c, last);
-        const int y = (int)__umulhi((uint32_t)c, a.cpr_magic);
-        const int ry = a.flip ? a.height - 1 - y : y;
-        return *reinterpret_cast<const uint4 *>(render + (((uint32_t)(__mul24(y, a.flip_row) + c + a.flip_base) << 4) + (uint32_t)__mul24(ry, row_rem)));
-    };
-    auto chunk_of = [&](int it) {
-        const int i = it * kWaves + wave;  // wavefront-uniform
-        const int g = d.cnt > 1 ? (int)__umulhi((uint32_t)i, d.magic) : i;
-        const int t = g * d.L + d.off + (i - g * d.cnt);
-        return i < d.n ? (t << 6) + lane : 0x7FFFFFC0;
-    };
-    uint32_t added = 0;
-    if (d.off == 0 && row_rem > 0) {
-        // the owner also adds the last width % 16 pixels of every row
-        const int x0 = a.chunks_per_row << 4, n = a.height * row_rem;
-        for (int t = wave * 64 + lane; t < n; t += kBlock) {
-            const int y = t / row_rem, x = x0 + t - y * row_rem;
-            if (mask[y * a.width + x] == 0) continue;
-            uint32_t d1 = render[(a.flip ? a.height - 1 - y : y) * a.width + x], d2 = warped[y * a.width + x];
-            if (SHIFTED) {
-                d1 >>= a.shift;
-                d2 >>= a.shift;
-            }
-            (void)__hip_atomic_fetch_add(&lds.joint[joint_word(d1, d2)], joint_inc(d2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            ++added;
-        }
-    }
-    const int iters = (d.n + kWaves - 1) / kWaves;  // workgroup-uniform
-    if (iters <= 0) return added;
-    // one chunk of prefetch (masked_histogram_phase's loop); loads clamped to the last chunk, only the adds are predicated
-    int c = chunk_of(0);
-    uint32_t o = at(c);
-    uint4 wc = *reinterpret_cast<const uint4 *>(warped + o), mc = *reinterpret_cast<const uint4 *>(mask + o), rc = ldr(c);
-#pragma unroll 1
-    for (int it = 0; it < iters; ++it) {
-        const int cn = chunk_of(it + 1);
-        const uint32_t on = at(cn);
-        const uint4 wn = *reinterpret_cast<const uint4 *>(warped + on), mn = *reinterpret_cast<const uint4 *>(mask + on), rn = ldr(cn);
-        if (c < nchunks) {
-            masked_add_chunk<true, SHIFTED, 2>(lds, 0, rc, wc, mc, a.shift);
-            added += mask_popc(mc);
-        }
-        wc = wn;
-        mc = mn;
-        rc = rn;
-        c = cn;
-    }
-    return added;
-}
-
-// the workgroup's added pixels into *dst (LDS, zero before)
-__device__ __forceinline__ void add_count(uint32_t *dst, uint32_t n, int lane)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
-    if (lane == 0) atomicAdd(dst, n);
-}
-
-}  // namespace
-
-// Workgroup b: helpers first (blocks 0 .. total * (P - 1) - 1: range q = 1 + b / total of candidate b % total), then the owners
-// -- nmi_pix_kernel's liveness argument unchanged.  ZERO0: background rule off at 256 bins (row / column 0 cleared in the decode).
+// ZERO0: background rule off at 256 bins (row / column 0 cleared in the decode).
 template <bool ZERO0, bool SHIFTED>
 __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(MaskedGridArgs m, int P, DealArgs dealing, const uint32_t *replay,
                                                                           uint32_t *healed)
@@ -126,19 +46,14 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
     const int lane = tid & 63;
     const int wave = tid >> 6;
 
-    const int total = a.S_local * a.Wn;
-    const int helpers = total * (P - 1);
-    const int b = (int)blockIdx.x;
-    const int q = b < helpers ? 1 + (total > 1 ? (int)__umulhi((uint32_t)b, dealing.total_magic) : b) : 0;
-    const int p = b < helpers ? b - (q - 1) * total : b - helpers;
-    const bool owner = q == 0;
-    const int w = p / a.S_local, s = p - w * a.S_local;
+    const PixUnit u = pix_unit(a, P, dealing, replay);
+    const int p = u.p, w = u.w, s = u.s;
+    const bool owner = u.q == 0;
     const uint8_t *render = a.render_stack + (size_t)s * a.npix;
     const uint8_t *warped = a.warp_stack + (size_t)w * a.npix;
     const uint8_t *mask = m.warp_masks + (size_t)w * a.npix;
-    const uint32_t tag = 0x80000000u | ((a.epoch + (replay ? __hip_atomic_load(replay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u)) & 0x7FFFFFFFu);
 
-    if (b == 0 && tid == 0 && a.reset_key) *a.reset_key = 0ull;  // next launch's slot; idle during this one
+    if (blockIdx.x == 0 && tid == 0 && a.reset_key) *a.reset_key = 0ull;  // next launch's slot; idle during this one
     GridArgs aw = a;
     aw.table = m.tables + (size_t)w * ((size_t)a.npix + 1);
     float tab[kLdsTable / kBlock];
@@ -149,103 +64,27 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
             tab[k] = aw.table[c <= a.npix ? c : 0];
         }
     }
-    {
-        uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
-        const uint4 z = {0, 0, 0, 0};
-        for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
-    }
-    if (tid < kBins) lds.hist_warped[tid] = 0;
-    if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;  // total[0]: decoded counters, total[1]: pixels added by all ranges
-    if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;
-    if (tid == 0) lds.fallback = 0;
-    const Deal deal = make_deal(dealing, P, q);
+    clear_counters(lds, tid);
+    const Deal deal = make_deal(dealing, P, u.q);
     __syncthreads();
-    add_count(&lds.total[1], masked_histogram_dealt<SHIFTED>(lds, a, render, warped, mask, wave, lane, deal), lane);
+    add_count(&lds.total[1], masked_histogram_dealt<SHIFTED, false>(lds, a, render, warped, mask, nullptr, wave, lane, deal), lane);
 
-    char *const blocks = reinterpret_cast<char *>(a.blocks) + (size_t)p * (size_t)(P - 1) * kPixBlockBytes;
     if (!owner) {
-        // ---- helper: nmi_pix_kernel's hand-off, plus the count of pixels added (header word pad[0]) ----
-        // TWIN: nmi_pix_kernel's helper part and owner's wait and merge, written out (see there) -- a fix there belongs here too.
         __syncthreads();
-        char *const blk = blocks + (size_t)(q - 1) * kPixBlockBytes;
-        PixHeader *const hdr = reinterpret_cast<PixHeader *>(blk);
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)kPixBlockBytes, 0x00020000);
-        unsigned long long bits[kUnitsPerLane];
-        {
-            const int i = lane & 15, r = lane >> 4;
-#pragma unroll
-            for (int kk = 0; kk < kUnitsPerLane; ++kk) {
-                const int d1 = decode_row(wave, kk >> 1, r);
-                u32x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, (kk & 1) * 4 + j)];
-                const bool on = (v.x | v.y | v.z | v.w) != 0u;
-                bits[kk] = __ballot(on);
-                if (on) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
-            }
-        }
-        if (tid == 0) __hip_atomic_store(&hdr->pad[0], lds.total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t half = 0;
-#pragma unroll
-        for (int g = 0; g < 2 * kUnitsPerLane; ++g)
-            if (lane == g) half = (uint32_t)(bits[g >> 1] >> (32 * (g & 1)));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier the granules' lanes wait at
-        __syncthreads();
-        // (phase mask bit 9, tests only: helper 1 keeps its masks to itself, so its owner's wait must time out and heal)
-        if (lane < 2 * kUnitsPerLane && !((a.phase_mask & 512) && q == 1))
-            __hip_atomic_store(&hdr->granule[wave * 2 * kUnitsPerLane + lane], ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pix_publish<false>(lds, a, u, wave, lane);
         return;
     }
 
     // ---- owner ----
 #pragma unroll
     for (int k = 0; k < kLdsTable / kBlock; ++k) lds.table[tid + k * kBlock] = tab[k];
-    unsigned long long gv = 0;
-    bool seen = true;
-    if (lane < 16 * (P - 1)) {
-        const unsigned long long *g = reinterpret_cast<const PixHeader *>(blocks + (size_t)(lane >> 4) * kPixBlockBytes)->granule + wave * 16 + (lane & 15);
-        unsigned long long t0 = 0;
-        int tries = 0;
-        while ((uint32_t)((gv = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) != tag) {
-            __builtin_amdgcn_s_sleep(4);
-            if ((++tries & 15) == 1) {
-                const unsigned long long now = wall_clock64();
-                if (tries == 1) t0 = now;
-                if (now - t0 > kPixTimeoutTicks || tries > (1 << 20)) {
-                    seen = false;
-                    break;
-                }
-            }
-        }
-    }
-    seen = __all(seen);  // wave-uniform
-    if (!seen && lane == 0) lds.fallback = 1;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no instruction: keeps the loads below behind the poll)
-    const uint32_t gh = (uint32_t)gv;
     u32x4 acc[kUnitsPerLane];
-#pragma unroll
-    for (int kk = 0; kk < kUnitsPerLane; ++kk) acc[kk] = u32x4{0, 0, 0, 0};
-    if (seen) {
-        for (int h = 0; h < P - 1; ++h) {
-            const char *blk = blocks + (size_t)h * kPixBlockBytes;
-            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(blk), 0, (int)kPixBlockBytes, 0x00020000);
-            u32x4 v[kUnitsPerLane];
-#pragma unroll
-            for (int kk = 0; kk < kUnitsPerLane; ++kk) {
-                const uint32_t lo = __builtin_amdgcn_readlane(gh, h * 16 + 2 * kk), hi = __builtin_amdgcn_readlane(gh, h * 16 + 2 * kk + 1);
-                v[kk] = u32x4{0, 0, 0, 0};
-                if ((((((unsigned long long)hi << 32) | lo) >> lane) & 1ull) != 0ull) v[kk] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
-            }
-            if (wave == 0 && lane == 0) atomicAdd(&lds.total[1], __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, pad), 0, kAuxSc1));
-#pragma unroll
-            for (int kk = 0; kk < kUnitsPerLane; ++kk) acc[kk] += v[kk];
-        }
-    }
+    pix_collect<false>(lds, u, P, wave, lane, acc);
     __syncthreads();  // B1: every wavefront's pixels are in the counters, every helper's count in total[1]
     unsigned long long prev_key = 0;
     bool alone = lds.fallback != 0;  // some wave gave up on a helper (workgroup-uniform)
     if (!alone) {
-        decode_merged<ZERO0>(lds, aw, wave, lane, acc);
+        decode_merged<ZERO0>(lds, TableTerms{aw.table, (uint32_t)a.npix, a.dbg_joint}, wave, lane, acc);
         __syncthreads();
         alone = lds.total[0] != lds.total[1];  // some 16-bit field wrapped (workgroup-uniform, rare)
         if (!alone && wave == 0) final_phase_owner(lds, aw, lane, p, w, s, prev_key);
@@ -254,13 +93,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
         // cold: this candidate once more, by this workgroup alone, on the masked exact path
         if (tid == 0 && healed) __hip_atomic_fetch_add(healed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        {
-            uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
-            const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
-        }
-        if (tid < kBins) lds.hist_warped[tid] = 0;
-        if (tid < 2) lds.total[tid] = lds.ovf_n[tid] = 0;
+        clear_counters(lds, tid);
         __syncthreads();
         masked_histogram_phase<true, SHIFTED, 1>(lds, 0, m, render, warped, mask, tid);
         __syncthreads();
@@ -268,7 +101,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
         __syncthreads();
         if (wave == 0) final_phase(lds, aw, lane, p, w, s, prev_key);
     }
-    if (wave == 0) finish_search(a, lane, prev_key, (uint32_t)total);
+    if (wave == 0) finish_search(a, lane, prev_key, (uint32_t)u.total);
 }
 
 // One launch of total * pix_parts workgroups (nmi_masked.h).
@@ -277,16 +110,9 @@ hipError_t launch_pix_masked(const MaskedGridArgs &m, int pix_parts, double owne
 {
     const GridArgs &a = m.g;
     if (!pix_launch_ok(a, pix_parts, use_bg) || a.plan || !m.tables || !m.warp_masks) return hipErrorInvalidValue;
-    const long long total = (long long)a.S_local * a.Wn;
-    const DealArgs g = pix_dealing(a, pix_parts, owner_share);
-    const dim3 grid((unsigned)(total * pix_parts)), block(kBlock);
-    if (a.shift != 0)
-        hipLaunchKernelGGL((nmi_masked_pix_kernel<false, true>), grid, block, 0, stream, m, pix_parts, g, replay, healed);
-    else if (use_bg)
-        hipLaunchKernelGGL((nmi_masked_pix_kernel<false, false>), grid, block, 0, stream, m, pix_parts, g, replay, healed);
-    else
-        hipLaunchKernelGGL((nmi_masked_pix_kernel<true, false>), grid, block, 0, stream, m, pix_parts, g, replay, healed);
-    return hipGetLastError();
+    return pix_launch(a, pix_parts, owner_share, use_bg, [&](auto zero0, auto shifted, dim3 grid, const DealArgs &g) {
+        hipLaunchKernelGGL((nmi_masked_pix_kernel<decltype(zero0)::value, decltype(shifted)::value>), grid, dim3(kBlock), 0, stream, m, pix_parts, g, replay, healed);
+    });
 }
 
 }  // namespace nmi

@@ -1,11 +1,15 @@
 // nmi_pix_device.h -- the pixel-range kernels' shared device code (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip,
-// nmi_covered_pix_kernel.hip): the dealing of the pair's pieces, the hand-off blocks (PixHeader, unit layout, tagged mask
-// granules), the owner's merged decode and its final trees.
+// nmi_covered_pix_kernel.hip): which workgroup scores what (pix_unit), the dealing of the pair's pieces and their addressing
+// (Deal, Pieces), the plain and the masked dealt loops, the hand-off (PixHeader, unit layout, tagged mask granules; the helper's
+// pix_publish and the owner's pix_collect), the owner's merged decode and its final trees, and the launchers' shared host code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "nmi_grid_device.h"
+#include "nmi_mask_device.h"  // masked_add_chunk, nonzero_byte_bits, both_nonzero, popc4, cover_term
 
 namespace nmi {
 
@@ -69,52 +73,127 @@ __device__ __forceinline__ Deal make_deal(const DealArgs &g, int P, int q)
     return d;
 }
 
-template <bool SHIFTED>
-__device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, const uint8_t *__restrict__ render, const uint8_t *__restrict__ warped,
-                                                int wave, int lane, const Deal &d)
+// What a workgroup of a pixel-range launch scores.  Helpers first: blocks 0 .. total * (P - 1) - 1 are range q = 1 + b / total
+// of candidate p = b % total, then come the owners (q = 0) -- see Liveness in nmi_pix_kernel.hip.
+struct PixUnit {
+    int total, q, p, w, s;  // candidates of the launch; this workgroup's range, candidate, warp and render
+    uint32_t tag;           // the launch's tag: never 0 (the state of fresh memory); the replay word counts the replays of a
+                            // captured graph, whose arguments are frozen
+    char *blocks;           // the candidate's P - 1 hand-off blocks, helper q's at (q - 1) * kPixBlockBytes
+};
+__device__ __forceinline__ PixUnit pix_unit(const GridArgs &a, int P, const DealArgs &dealing, const uint32_t *replay)
 {
-    // chunk c = the j-th 16-byte chunk of row y: byte y * width + 16 j of the frame, ry * width + 16 j of the render -- rows need not
-    // be whole aligned chunks (histogram_phase's ROWS form, nmi_kernels.hip; row_rem = width % 16 pixels per row are left for
-    // add_row_tails below)
-    const int nchunks = a.height * a.chunks_per_row, last = nchunks - 1, row_rem = a.width - (a.chunks_per_row << 4);
-    auto ldw = [&](int c) {
-        c = min(c, last);
-        return *reinterpret_cast<const uint4 *>(warped + (((uint32_t)c << 4) + (uint32_t)__mul24((int)__umulhi((uint32_t)c, a.cpr_magic), row_rem)));
-    };
-    auto ldr = [&](int c) {  // NMI.cu:82: row y of the frame meets row H-1-y of a bottom-up render
-        c = min(c, last);
-        const int y = (int)__umulhi((uint32_t)c, a.cpr_magic);
-        const int ry = a.flip ? a.height - 1 - y : y;
-        return *reinterpret_cast<const uint4 *>(render + (((uint32_t)(__mul24(y, a.flip_row) + c + a.flip_base) << 4) + (uint32_t)__mul24(ry, row_rem)));
-    };
+    PixUnit u;
+    u.total = a.S_local * a.Wn;
+    const int helpers = u.total * (P - 1);
+    const int b = (int)blockIdx.x;
+    u.q = b < helpers ? 1 + (u.total > 1 ? (int)__umulhi((uint32_t)b, dealing.total_magic) : b) : 0;
+    u.p = b < helpers ? b - (u.q - 1) * u.total : b - helpers;
+    u.w = u.p / a.S_local;
+    u.s = u.p - u.w * a.S_local;
+    u.tag = 0x80000000u | ((a.epoch + (replay ? __hip_atomic_load(replay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u)) & 0x7FFFFFFFu);
+    u.blocks = reinterpret_cast<char *>(a.blocks) + (size_t)u.p * (size_t)(P - 1) * kPixBlockBytes;
+    return u;
+}
+
+// Every counter of the workgroup to zero, before its pixels and before a candidate is scored once more on an exact path.  (The
+// masked forms never set a side counter, so clearing them again before their heal stores zeros over zeros; and every thread has
+// read lds.fallback before the barrier that precedes a heal's clear.)
+__device__ __forceinline__ void clear_counters(Lds &lds, int tid)
+{
+    uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
+    const uint4 z = {0, 0, 0, 0};
+    for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
+    if (tid < kBins) lds.hist_warped[tid] = 0;
+    if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;  // total[0]: decoded counters; masked forms, total[1]: pixels added by all ranges
+    if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;
+    if (tid == 0) lds.fallback = 0;
+}
+
+// the workgroup's added pixels into *dst (LDS, zero before)
+__device__ __forceinline__ void add_count(uint32_t *dst, uint32_t n, int lane)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
+    if (lane == 0) atomicAdd(dst, n);
+}
+
+// A workgroup's piece addressing.  Chunk c = the j-th 16-byte chunk of row y: byte y * width + 16 j of the frame and of the warp
+// mask, ry * width + 16 j of the render and of its coverage mask -- rows need not be whole aligned chunks (histogram_phase's ROWS
+// form, nmi_kernels.hip); the row_rem = width % 16 pixels left per row are add_row_tails' below.  Loads are clamped to the last
+// chunk (a valid address); only the adds are predicated, by chunk < nchunks.
+struct Pieces {
+    const GridArgs &a;
+    const Deal &d;
+    int wave, lane, nchunks, row_rem;
+    __device__ __forceinline__ Pieces(const GridArgs &a_, const Deal &d_, int wave_, int lane_)
+        : a(a_), d(d_), wave(wave_), lane(lane_), nchunks(a_.height * a_.chunks_per_row), row_rem(a_.width - (a_.chunks_per_row << 4)) {}
+    __device__ __forceinline__ int iters() const { return (d.n + kWaves - 1) / kWaves; }  // workgroup-uniform
     // chunk of this lane in the workgroup's iteration `it`; beyond the workgroup's pieces: some chunk >= nchunks (not added)
-    auto chunk_of = [&](int it) {
+    __device__ __forceinline__ int chunk_of(int it) const
+    {
         const int i = it * kWaves + wave;  // wavefront-uniform
         const int g = d.cnt > 1 ? (int)__umulhi((uint32_t)i, d.magic) : i;
         const int t = g * d.L + d.off + (i - g * d.cnt);
         return i < d.n ? (t << 6) + lane : 0x7FFFFFC0;
-    };
-    const int iters = (d.n + kWaves - 1) / kWaves;  // workgroup-uniform
-    if (d.off == 0 && row_rem > 0) {
-        // the owner also adds the last width % 16 pixels of every row
-        const int x0 = a.chunks_per_row << 4, n = a.height * row_rem;
-        for (int t = wave * 64 + lane; t < n; t += kBlock) {
-            const int y = t / row_rem, x = x0 + t - y * row_rem;
-            uint32_t d1 = render[(a.flip ? a.height - 1 - y : y) * a.width + x], d2 = warped[y * a.width + x];
+    }
+    __device__ __forceinline__ uint32_t at(int c) const  // byte of chunk c in the frame (and in the warp mask: same layout)
+    {
+        c = min(c, nchunks - 1);
+        return ((uint32_t)c << 4) + (uint32_t)__mul24((int)__umulhi((uint32_t)c, a.cpr_magic), row_rem);
+    }
+    __device__ __forceinline__ uint32_t rat(int c) const  // ... in the render (and in its coverage mask): NMI.cu:82, row y meets row H-1-y of a bottom-up render
+    {
+        c = min(c, nchunks - 1);
+        const int y = (int)__umulhi((uint32_t)c, a.cpr_magic);
+        const int ry = a.flip ? a.height - 1 - y : y;
+        return ((uint32_t)(__mul24(y, a.flip_row) + c + a.flip_base) << 4) + (uint32_t)__mul24(ry, row_rem);
+    }
+};
+__device__ __forceinline__ uint4 ld16(const uint8_t *base, uint32_t o) { return *reinterpret_cast<const uint4 *>(base + o); }
+
+// The owner also adds the last width % 16 pixels of every row, one by one: those for which take(frame position, render
+// position) holds.  Returns the pixels this lane added.
+template <bool SHIFTED, class Take>
+__device__ __forceinline__ uint32_t add_row_tails(Lds &lds, const Pieces &pc, const uint8_t *__restrict__ render, const uint8_t *__restrict__ warped, Take take)
+{
+    const GridArgs &a = pc.a;
+    uint32_t added = 0;
+    if (pc.d.off == 0 && pc.row_rem > 0) {
+        const int x0 = a.chunks_per_row << 4, n = a.height * pc.row_rem;
+        for (int t = pc.wave * 64 + pc.lane; t < n; t += kBlock) {
+            const int y = t / pc.row_rem, x = x0 + t - y * pc.row_rem;
+            const int pos = y * a.width + x, rpos = (a.flip ? a.height - 1 - y : y) * a.width + x;
+            if (!take(pos, rpos)) continue;
+            uint32_t d1 = render[rpos], d2 = warped[pos];
             if (SHIFTED) {
                 d1 >>= a.shift;
                 d2 >>= a.shift;
             }
             (void)__hip_atomic_fetch_add(&lds.joint[joint_word(d1, d2)], joint_inc(d2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            ++added;
         }
     }
+    return added;
+}
+
+// This workgroup's dealt pieces, every pixel: nmi_grid_kernel's histogram phase (non-returning atomics, flat regions folded).
+template <bool SHIFTED>
+__device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, const uint8_t *__restrict__ render, const uint8_t *__restrict__ warped,
+                                                int wave, int lane, const Deal &d)
+{
+    const Pieces pc(a, d, wave, lane);
+    auto ldw = [&](int c) { return ld16(warped, pc.at(c)); };
+    auto ldr = [&](int c) { return ld16(render, pc.rat(c)); };
+    const int nchunks = pc.nchunks, iters = pc.iters();
+    (void)add_row_tails<SHIFTED>(lds, pc, render, warped, [](int, int) { return true; });
     if (iters <= 0) return;
     const bool try_flat = !(a.phase_mask & 4);
     int resume = -1;
-    int c = chunk_of(0);
+    int c = pc.chunk_of(0);
     uint4 wa = ldw(c), ra = ldr(c), wb, rb;
     for (int it = 0; it < iters; it += 2) {
-        const int cb = chunk_of(it + 1);
+        const int cb = pc.chunk_of(it + 1);
         wb = ldw(cb);
         rb = ldr(cb);
         if (__builtin_expect(flat_hint(ra, wa), 0)) {
@@ -122,7 +201,7 @@ __device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, con
             break;
         }
         if (c < nchunks) add_chunk<true, SHIFTED, 2, false>(lds, 0, ra, wa, a.shift, false);
-        c = chunk_of(it + 2);
+        c = pc.chunk_of(it + 2);
         wa = ldw(c);
         ra = ldr(c);
         if (__builtin_expect(flat_hint(rb, wb), 0)) {
@@ -133,11 +212,11 @@ __device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, con
     }
     if (resume >= 0) {
         // careful loop: same adds, flat chunks folded (fold_flat_chunk); one chunk of prefetch
-        int cc = chunk_of(resume);
+        int cc = pc.chunk_of(resume);
         uint4 wc = ldw(cc), rc = ldr(cc);
 #pragma unroll 1
         for (int it = resume; it < iters; ++it) {
-            const int cn = chunk_of(it + 1);
+            const int cn = pc.chunk_of(it + 1);
             const uint4 wn = ldw(cn), rn = ldr(cn);
             if (cc < nchunks) add_chunk<true, SHIFTED, 2, true>(lds, 0, rc, wc, a.shift, try_flat);
             wc = wn;
@@ -147,7 +226,159 @@ __device__ __forceinline__ void histogram_dealt(Lds &lds, const GridArgs &a, con
     }
 }
 
+__device__ __forceinline__ uint32_t mask_popc(const uint4 &m)
+{
+    return __popc(nonzero_byte_bits(m.x)) + __popc(nonzero_byte_bits(m.y)) + __popc(nonzero_byte_bits(m.z)) + __popc(nonzero_byte_bits(m.w));
+}
+
+// This workgroup's dealt pieces with masks, non-returning atomics; flat chunks are not folded (fold_flat_chunk's side counters
+// assume every pixel of a chunk counts).  A pixel is added where its byte of the warp's mask is nonzero and, COVERED, its byte of
+// the render's coverage mask (in the render's row order) too: the covered form is the masked form whose chunk mask is
+// both_nonzero of the two.  Returns the pixels this lane added.
+template <bool SHIFTED, bool COVERED>
+__device__ __forceinline__ uint32_t masked_histogram_dealt(Lds &lds, const GridArgs &a, const uint8_t *__restrict__ render,
+                                                          const uint8_t *__restrict__ warped, const uint8_t *__restrict__ wmask,
+                                                          const uint8_t *__restrict__ rmask, int wave, int lane, const Deal &d)
+{
+    const Pieces pc(a, d, wave, lane);
+    uint32_t added = add_row_tails<SHIFTED>(lds, pc, render, warped, [&](int pos, int rpos) { return wmask[pos] != 0 && (!COVERED || rmask[rpos] != 0); });
+    const int iters = pc.iters();
+    if (iters <= 0) return added;
+    // one chunk of prefetch (masked_histogram_phase's loop): the masks are folded after the adds, while the next loads fly
+    int c = pc.chunk_of(0);
+    uint32_t o = pc.at(c), ro = pc.rat(c);
+    uint4 wc = ld16(warped, o), rc = ld16(render, ro), mc = ld16(wmask, o);
+    if (COVERED) mc = both_nonzero(mc, ld16(rmask, ro));
+#pragma unroll 1
+    for (int it = 0; it < iters; ++it) {
+        const int cn = pc.chunk_of(it + 1);
+        o = pc.at(cn);
+        ro = pc.rat(cn);
+        const uint4 wn = ld16(warped, o), rn = ld16(render, ro), wmn = ld16(wmask, o), rmn = COVERED ? ld16(rmask, ro) : wmn;
+        if (c < pc.nchunks) {
+            added += COVERED ? popc4(mc) : mask_popc(mc);  // (both_nonzero already yields one bit per pixel)
+            masked_add_chunk<true, SHIFTED, 2>(lds, 0, rc, wc, mc, a.shift);
+        }
+        wc = wn;
+        rc = rn;
+        mc = COVERED ? both_nonzero(wmn, rmn) : wmn;
+        c = cn;
+    }
+    return added;
+}
+
 __device__ __forceinline__ int unit_offset(int wave, int kk, int lane) { return (int)sizeof(PixHeader) + ((wave * kUnitsPerLane + kk) * 64 + lane) * 16; }
+
+// ---- the hand-off --------------------------------------------------------------------------------------------------------------
+// What travels in the header beside the units is the one thing that differs between the callers.  SIDE (the plain kernel): the
+// helper's flat-region side counters, merged into the owner's (side_add), or, when those are taken, onto the packed field.
+// !SIDE (the masked forms, which fold nothing): the pixels the helper added, lds.total[1], in pad[0], summed into the owner's
+// lds.total[1].
+//
+// The helper's half, called after the barrier behind its pixels: units that hold a count -> memory, write-through; the header's
+// payload; drain; barrier; tagged masks.  The order matters: a granule's tag tells the owner that the units AND the payload
+// are in memory, so every storing wave drains before the barrier the granules' lanes wait at.
+template <bool SIDE>
+__device__ __forceinline__ void pix_publish(Lds &lds, const GridArgs &a, const PixUnit &u, int wave, int lane)
+{
+    char *const blk = u.blocks + (size_t)(u.q - 1) * kPixBlockBytes;
+    PixHeader *const hdr = reinterpret_cast<PixHeader *>(blk);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)kPixBlockBytes, 0x00020000);
+    const int tid = wave * 64 + lane;
+    unsigned long long mask[kUnitsPerLane];
+    {
+        const int i = lane & 15, r = lane >> 4;
+#pragma unroll
+        for (int kk = 0; kk < kUnitsPerLane; ++kk) {
+            const int d1 = decode_row(wave, kk >> 1, r);
+            u32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = lds.joint[decode_word(d1, i, (kk & 1) * 4 + j)];
+            const bool on = (v.x | v.y | v.z | v.w) != 0u;
+            mask[kk] = __ballot(on);
+            if (on) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
+        }
+    }
+    if (SIDE) {
+        if (tid < kSide) {
+            __hip_atomic_store(&hdr->side_key[tid], lds.side_key[0][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&hdr->side_cnt[tid], lds.side_cnt[0][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else {
+        if (tid == 0) __hip_atomic_store(&hdr->pad[0], lds.total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    uint32_t half = 0;
+#pragma unroll
+    for (int g = 0; g < 2 * kUnitsPerLane; ++g)
+        if (lane == g) half = (uint32_t)(mask[g >> 1] >> (32 * (g & 1)));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier the granules' lanes wait at
+    __syncthreads();
+    // (phase mask bit 9, tests only: helper 1 keeps its masks to itself, so its owner's wait must time out and heal)
+    if (lane < 2 * kUnitsPerLane && !((a.phase_mask & 512) && u.q == 1))
+        __hip_atomic_store(&hdr->granule[wave * 2 * kUnitsPerLane + lane], ((unsigned long long)u.tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The owner's half: the bounded wait for every helper's tag, then this lane's units of every helper, summed field by field as
+// packed words into acc (a field that wraps in the sum loses weight like any other wrap), and the header's payload into the LDS.
+// Called before the barrier behind the owner's pixels: the loads arrive while the slower wavefronts finish theirs.  A wave that
+// gives up on a helper (kPixTimeoutTicks) sets lds.fallback and leaves acc zero.
+template <bool SIDE>
+__device__ __forceinline__ void pix_collect(Lds &lds, const PixUnit &u, int P, int wave, int lane, u32x4 (&acc)[kUnitsPerLane])
+{
+    // every wave polls for itself: lane 16 h + g the granule g of helper h + 1 that belongs to this wave's units
+    unsigned long long gv = 0;
+    bool seen = true;
+    if (lane < 16 * (P - 1)) {
+        const unsigned long long *g = reinterpret_cast<const PixHeader *>(u.blocks + (size_t)(lane >> 4) * kPixBlockBytes)->granule + wave * 16 + (lane & 15);
+        unsigned long long t0 = 0;
+        int tries = 0;
+        while ((uint32_t)((gv = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) != u.tag) {
+            __builtin_amdgcn_s_sleep(4);
+            if ((++tries & 15) == 1) {
+                const unsigned long long now = wall_clock64();
+                if (tries == 1) t0 = now;
+                if (now - t0 > kPixTimeoutTicks || tries > (1 << 20)) {
+                    seen = false;
+                    break;
+                }
+            }
+        }
+    }
+    seen = __all(seen);  // wave-uniform
+    if (!seen && lane == 0) lds.fallback = 1;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no instruction: keeps the loads below behind the poll)
+    const uint32_t gh = (uint32_t)gv;  // this lane's mask half
+#pragma unroll
+    for (int kk = 0; kk < kUnitsPerLane; ++kk) acc[kk] = u32x4{0, 0, 0, 0};
+    if (!seen) return;
+    for (int h = 0; h < P - 1; ++h) {
+        const char *blk = u.blocks + (size_t)h * kPixBlockBytes;
+        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(blk), 0, (int)kPixBlockBytes, 0x00020000);
+        u32x4 v[kUnitsPerLane];
+#pragma unroll
+        for (int kk = 0; kk < kUnitsPerLane; ++kk) {
+            const uint32_t lo = __builtin_amdgcn_readlane(gh, h * 16 + 2 * kk), hi = __builtin_amdgcn_readlane(gh, h * 16 + 2 * kk + 1);
+            v[kk] = u32x4{0, 0, 0, 0};
+            if ((((((unsigned long long)hi << 32) | lo) >> lane) & 1ull) != 0ull) v[kk] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, unit_offset(wave, kk, lane), 0, kAuxSc1);
+        }
+        if (SIDE) {
+            if (wave == 0 && lane < kSide) {
+                // a helper's side counter: into a side counter of the owner's (atomics: other wavefronts may still be folding flat
+                // chunks of their own), or, when those are taken, onto the packed field (which may wrap it: the count test sees that)
+                const uint32_t skey = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, side_key) + lane * 4, 0, kAuxSc1);
+                const uint32_t scnt = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, side_cnt) + lane * 4, 0, kAuxSc1);
+                if (skey != 0u) {
+                    const uint32_t sd1 = (skey - 1u) >> 8, sd2 = (skey - 1u) & 0xFFu;
+                    if (!side_add(lds, 0, sd1, sd2, scnt)) atomicAdd(&lds.joint[joint_word(sd1, sd2)], (sd2 & 128u) ? scnt << 16 : scnt);
+                }
+            }
+        } else {
+            if (wave == 0 && lane == 0) atomicAdd(&lds.total[1], __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)offsetof(PixHeader, pad), 0, kAuxSc1));
+        }
+#pragma unroll
+        for (int kk = 0; kk < kUnitsPerLane; ++kk) acc[kk] += v[kk];
+    }
+}
 
 // The dealing pattern of a launch (host): own : hlp pieces per period, the closest to owner_share among periods of at most 48
 // pieces, and the magic numbers that spare the kernel every division.
@@ -179,14 +410,46 @@ inline bool pix_launch_ok(const GridArgs &a, int pix_parts, bool use_bg)
     return !(a.width < 32 || !a.blocks || a.hist_variant != 3 || (a.shift != 0 && !use_bg) || a.order);
 }
 
+// One launch of total * pix_parts workgroups (host): the dealing, the grid, and the choice among a kernel's three instantiations
+// <ZERO0, SHIFTED> -- fewer than 256 bins (background rule on), 256 bins with the rule on, 256 bins with it off.
+// launch(zero0, shifted, grid, dealing) enqueues the kernel; the two first arguments are std::bool_constant's.
+template <class Launch>
+inline hipError_t pix_launch(const GridArgs &a, int pix_parts, double owner_share, bool use_bg, Launch launch)
+{
+    const DealArgs g = pix_dealing(a, pix_parts, owner_share);
+    const dim3 grid((unsigned)((long long)a.S_local * a.Wn * pix_parts));
+    if (a.shift != 0)
+        launch(std::false_type{}, std::true_type{}, grid, g);
+    else if (use_bg)
+        launch(std::false_type{}, std::false_type{}, grid, g);
+    else
+        launch(std::true_type{}, std::false_type{}, grid, g);
+    return hipGetLastError();
+}
+
+// Where the owner's decode finds the term of a count at or above kLdsTable (below, lds.table has it), and what else it has:
+// side counters (fold_flat_chunk's, the plain dealt loop) and the debug copy of the joint histogram.
+struct TableTerms {  // a global table of npix + 1 terms: the plain and the masked kernel
+    const float *table;
+    uint32_t npix;
+    uint32_t *dbg_joint;
+    static constexpr bool kSideCounters = true;
+    __device__ __forceinline__ float high(uint32_t c) const { return table[min(c, npix)]; }  // (a wrapped helper field can read high; the detector rejects the candidate)
+};
+struct CoverTerms {  // the candidate's own terms, evaluated (as covered_decode_phase): the covered kernel, which folds nothing and has no debug copy
+    uint32_t len;
+    static constexpr uint32_t *dbg_joint = nullptr;
+    static constexpr bool kSideCounters = false;
+    __device__ __forceinline__ float high(uint32_t c) const { return cover_term(c, len); }
+};
+
 // The owner's decode: decode_phase (ComputeEntropyKernel + AddvectorParwiseMidKernel, NMI.cu:230-287) over its own packed
 // counters PLUS the helpers' (acc: their units of this lane, already summed field by field), with two differences: counters
 // are not cleared (the workgroup scores one candidate) and there are no wrap events to replay (nobody used returning atomics).
-// TWIN: covered_decode_merged (nmi_covered_pix_kernel.hip) is a copy with per-candidate terms -- a fix here belongs there too.
-template <bool ZERO0>
-__device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int wave, int lane, const u32x4 (&acc)[kUnitsPerLane])
+template <bool ZERO0, class Terms>
+__device__ __forceinline__ void decode_merged(Lds &lds, const Terms &terms, int wave, int lane, const u32x4 (&acc)[kUnitsPerLane])
 {
-    const bool side_any = lds.side_key[0][0] != 0u;
+    const bool side_any = Terms::kSideCounters && lds.side_key[0][0] != 0u;
     uint32_t wave_total = 0;
     const int i = lane & 15, r = lane >> 4;
     uint32_t col_lo[8], col_hi[8];
@@ -248,8 +511,8 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
         if (__builtin_expect(cmax >= (uint32_t)kLdsTable, 0)) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                if (lo[k] >= (uint32_t)kLdsTable) tl[k] = a.table[min(lo[k], (uint32_t)a.npix)];  // (a wrapped helper field can read high; the detector rejects the candidate)
-                if (hi[k] >= (uint32_t)kLdsTable) th[k] = a.table[min(hi[k], (uint32_t)a.npix)];
+                if (lo[k] >= (uint32_t)kLdsTable) tl[k] = terms.high(lo[k]);
+                if (hi[k] >= (uint32_t)kLdsTable) th[k] = terms.high(hi[k]);
             }
         }
         rsum = row_sum_16(rsum);
@@ -259,8 +522,8 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const GridArgs &a, int w
             lds.hist_render[d1] = rsum;
             lds.joint_row_sums[d1] = x;
         }
-        if (a.dbg_joint) {
-            uint32_t *row = a.dbg_joint + d1 * kBins;
+        if (terms.dbg_joint) {
+            uint32_t *row = terms.dbg_joint + d1 * kBins;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int q = i + 16 * k;

@@ -355,12 +355,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // window of any quad is covered by two aligned 16-byte loads).
 constexpr int kResolveRows = 8;
 
-template <int SIZE>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
-                                                                    int width, int height, int stride, const uint32_t *epoch, size_t pair_words)
+// The strips of both fast kernels below.  COVER: also cover[s][y][x] = 1 where the pixel's resolved key is not empty (a point won
+// it), 0 where it kept the clear colour.
+// requires width % 4 == 0, SIZE <= 5, stride % 4 == 0, (SIZE == 1 or stride >= width + 4) and, COVER, cover 4-byte aligned
+template <int SIZE, bool COVER>
+__device__ __forceinline__ void resolve_strips(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, uint8_t *__restrict__ cover, int views,
+                                               int width, int height, int stride)
 {
-    // requires width % 4 == 0, SIZE <= 5, stride % 4 == 0 and (SIZE == 1 or stride >= width + 4)
-    if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // a level's double-buffered anchors: the buffer this replay splatted into
     const int hp = height + SIZE - 1;
     const int quads = width >> 2, strips = (height + kResolveRows - 1) / kResolveRows;
     const size_t n = (size_t)views * strips * quads;
@@ -398,8 +399,22 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32
                 for (int j = 1; j < SIZE; ++j) best[k] = min(best[k], h[j][k]);
             }
             *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
+            if (COVER) {
+                uint32_t bits = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) bits |= (best[k] != 0xFFFFFFFFu ? 1u : 0u) << (8 * k);
+                *reinterpret_cast<uint32_t *>(cover + (dst - out) + (size_t)r * width) = bits;
+            }
         }
     }
+}
+
+template <int SIZE>
+__global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
+                                                                    int width, int height, int stride, const uint32_t *epoch, size_t pair_words)
+{
+    if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // a level's double-buffered anchors: the buffer this replay splatted into
+    resolve_strips<SIZE, false>(zbuf, out, nullptr, views, width, height, stride);
 }
 
 // Any size / width.
@@ -433,58 +448,15 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *_
     }
 }
 
-// The coverage forms of the two resolve kernels above (nmi_render_points_masked): the same code, which also writes
-// cover[s][y][x] = 1 where the pixel's resolved key is not empty (a point won it), 0 where it kept the clear colour.  Copies
-// rather than a template parameter of the kernels above, whose code stays as it is.
-// TWIN: nmi_zbuf_resolve_cover_level_kernel below is this kernel plus the epoch's buffer offset -- a fix here belongs there too.
+// The coverage forms of the two resolve kernels above (nmi_render_points_masked, covered levels): the same render bytes, and
+// the coverage mask beside them.
 template <int SIZE>
 __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
-                                                                          uint8_t *__restrict__ cover, int views, int width, int height, int stride)
+                                                                          uint8_t *__restrict__ cover, int views, int width, int height, int stride,
+                                                                          const uint32_t *epoch, size_t pair_words)
 {
-    // requires width % 4 == 0, SIZE <= 5, stride % 4 == 0, (SIZE == 1 or stride >= width + 4) and cover 4-byte aligned
-    const int hp = height + SIZE - 1;
-    const int quads = width >> 2, strips = (height + kResolveRows - 1) / kResolveRows;
-    const size_t n = (size_t)views * strips * quads;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % quads), st = (int)((i / quads) % strips), s = (int)(i / ((size_t)quads * strips));
-        const int py0 = st * kResolveRows;
-        const uint32_t *base = zbuf + ((size_t)s * hp + py0) * stride + q * 4;
-        uint8_t *dst = out + ((size_t)s * height + py0) * width + q * 4;
-        uint32_t h[SIZE][4];  // horizontal minima of the last SIZE anchor rows (ring, indices static after unrolling)
-        auto fetch = [&](int row, uint32_t (&m)[4]) {
-            const uint4 lo = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride);
-            uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            if (SIZE > 1) {
-                const uint4 hi = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride + 4);
-                v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                m[k] = v[k];
-#pragma unroll
-                for (int d = 1; d < SIZE; ++d) m[k] = min(m[k], v[k + d]);
-            }
-        };
-#pragma unroll
-        for (int r = 0; r < SIZE - 1; ++r) fetch(r, h[r]);  // (anchor rows py0 .. py0 + SIZE - 2 exist: hp = height + SIZE - 1)
-#pragma unroll
-        for (int r = 0; r < kResolveRows; ++r) {
-            if (py0 + r >= height) break;
-            fetch(r + SIZE - 1, h[(r + SIZE - 1) % SIZE]);
-            uint32_t best[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                best[k] = h[0][k];
-#pragma unroll
-                for (int j = 1; j < SIZE; ++j) best[k] = min(best[k], h[j][k]);
-            }
-            *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bits |= (best[k] != 0xFFFFFFFFu ? 1u : 0u) << (8 * k);
-            *reinterpret_cast<uint32_t *>(cover + (dst - out) + (size_t)r * width) = bits;
-        }
-    }
+    if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // as nmi_zbuf_resolve_fast_kernel
+    resolve_strips<SIZE, true>(zbuf, out, cover, views, width, height, stride);
 }
 
 // Any size / width (coverage form).
@@ -520,82 +492,26 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint3
     }
 }
 
-// The coverage form of a covered level's resolve (nmi_level_set_coverage, fused point-cloud front): nmi_zbuf_resolve_cover_fast_kernel
-// on the anchor buffer this replay splatted into (the epoch's parity, as nmi_zbuf_resolve_fast_kernel takes it).  A kernel of its
-// own rather than an epoch argument of the coverage form above, whose code stays as it is.
-// TWIN: a copy of nmi_zbuf_resolve_cover_fast_kernel above, line for line apart from the first statement (the buffer of this
-// replay) -- a fix to one belongs in the other.
-template <int SIZE>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_level_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
-                                                                           uint8_t *__restrict__ cover, int views, int width, int height, int stride,
-                                                                           const uint32_t *epoch, size_t pair_words)
-{
-    // requires width % 4 == 0, SIZE <= 5, stride % 4 == 0, (SIZE == 1 or stride >= width + 4) and cover 4-byte aligned
-    zbuf += (size_t)(*epoch & 1u) * pair_words;
-    const int hp = height + SIZE - 1;
-    const int quads = width >> 2, strips = (height + kResolveRows - 1) / kResolveRows;
-    const size_t n = (size_t)views * strips * quads;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % quads), st = (int)((i / quads) % strips), s = (int)(i / ((size_t)quads * strips));
-        const int py0 = st * kResolveRows;
-        const uint32_t *base = zbuf + ((size_t)s * hp + py0) * stride + q * 4;
-        uint8_t *dst = out + ((size_t)s * height + py0) * width + q * 4;
-        uint32_t h[SIZE][4];  // horizontal minima of the last SIZE anchor rows (ring, indices static after unrolling)
-        auto fetch = [&](int row, uint32_t (&m)[4]) {
-            const uint4 lo = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride);
-            uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            if (SIZE > 1) {
-                const uint4 hi = *reinterpret_cast<const uint4 *>(base + (size_t)row * stride + 4);
-                v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                m[k] = v[k];
-#pragma unroll
-                for (int d = 1; d < SIZE; ++d) m[k] = min(m[k], v[k + d]);
-            }
-        };
-#pragma unroll
-        for (int r = 0; r < SIZE - 1; ++r) fetch(r, h[r]);  // (anchor rows py0 .. py0 + SIZE - 2 exist: hp = height + SIZE - 1)
-#pragma unroll
-        for (int r = 0; r < kResolveRows; ++r) {
-            if (py0 + r >= height) break;
-            fetch(r + SIZE - 1, h[(r + SIZE - 1) % SIZE]);
-            uint32_t best[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                best[k] = h[0][k];
-#pragma unroll
-                for (int j = 1; j < SIZE; ++j) best[k] = min(best[k], h[j][k]);
-            }
-            *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bits |= (best[k] != 0xFFFFFFFFu ? 1u : 0u) << (8 * k);
-            *reinterpret_cast<uint32_t *>(cover + (dst - out) + (size_t)r * width) = bits;
-        }
-    }
-}
-
 // The coverage forms of launch_resolve's kernels (nmi_render_points_masked): the same choice of form, the render bytes the same.
-static void launch_resolve_cover(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, int S, int width, int height, int size, hipStream_t stream)
+static void launch_resolve_cover(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, int S, int width, int height, int size, hipStream_t stream,
+                                 const uint32_t *epoch = nullptr, size_t pair_words = 0)
 {
     const int stride = zbuf_stride(width, size);
     const size_t nq = (size_t)S * height * ((width + 3) / 4);
     dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
     const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && (((uintptr_t)cover & 3) == 0);
-    if (!fast) {
+    if (!fast) {  // (never with an epoch: launch_level_front_points checks the fast form's conditions first)
         hipLaunchKernelGGL(nmi_zbuf_resolve_cover_kernel, grid, block, 0, stream, zbuf, out, cover, S, width, height, size, stride);
         return;
     }
     const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
     grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
     switch (size) {
-    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<1>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
-    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<2>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
-    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<3>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
-    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<4>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
-    default: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<5>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride); break;
+    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<1>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
+    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<2>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
+    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<3>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
+    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<4>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
+    default: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<5>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
     }
 }
 
@@ -697,20 +613,10 @@ hipError_t launch_level_front_points(const void *packed, long long npoints, cons
     hipLaunchKernelGGL(nmi_level_front_kernel, dim3((unsigned)(warp_blocks + splat_blocks + clear_blocks)), dim3(256), 0, stream, pc, npoints, mvps,
                        S, zbuf, pair_words, epoch, width, height, size, stride, frame, coeffs, warps, warp_blocks, (int)splat_blocks, clear_blocks,
                        kept, kept_count);
-    if (!cover) {
+    if (cover)
+        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words);
+    else
         launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words);
-        return hipGetLastError();
-    }
-    // covered level: launch_resolve's fast form and grid, with the coverage masks
-    const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
-    const dim3 grid((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192)), block(256);
-    switch (size) {
-    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_level_kernel<1>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_level_kernel<2>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_level_kernel<3>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_level_kernel<4>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    default: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_level_kernel<5>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    }
     return hipGetLastError();
 }
 
