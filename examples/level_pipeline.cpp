@@ -96,6 +96,36 @@ static float surface_grey(float u, float v, float n)
     return fminf(fmaxf(t, 0.0f), 255.0f);
 }
 
+// The frame a fisheye camera (nmi_undistort_frame_fisheye's model, K_raw = K = fx fy cx cy, coefficients k) makes of the pinhole image
+// img (w x h, stored bottom-up as the renders are): each raw pixel's normalised point has radius td(theta); Newton gives theta, the
+// ray meets the pinhole's plane at radius tan(theta), and the image is read there bilinearly.  The forward direction of what the
+// level undoes on every replay; host double arithmetic, as a lens would do it.
+static std::vector<uint8_t> through_fisheye(const std::vector<uint8_t> &img, int w, int h, double fx, double fy, double cx, double cy,
+                                            const float k[4])
+{
+    std::vector<uint8_t> out((size_t)w * h, 0);
+    auto at = [&](int x, int y) -> double { return x < 0 || y < 0 || x >= w || y >= h ? 0.0 : (double)img[(size_t)(h - 1 - y) * w + x]; };
+    for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+            const double xd = (u - cx) / fx, yd = (v - cy) / fy, rd = std::sqrt(xd * xd + yd * yd);
+            double th = rd;
+            for (int it = 0; it < 20; ++it) {
+                const double t2 = th * th;
+                const double f = th * (1 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3])))) - rd;
+                th -= f / (1 + t2 * (3 * k[0] + t2 * (5 * k[1] + t2 * (7 * k[2] + t2 * 9 * k[3]))));
+            }
+            if (!(th >= 0.0 && th < 1.5)) continue;  // at or beyond ~86 degrees from the axis: nothing a pinhole image holds
+            const double s = rd > 0.0 ? std::tan(th) / rd : 1.0;
+            const double px = fx * xd * s + cx, py = fy * yd * s + cy;
+            if (!(px > -1.0 && px < w && py > -1.0 && py < h)) continue;
+            const int x0 = (int)std::floor(px), y0 = (int)std::floor(py);
+            const double ax = px - x0, ay = py - y0;
+            const double val = (1 - ax) * (1 - ay) * at(x0, y0) + ax * (1 - ay) * at(x0 + 1, y0) + (1 - ax) * ay * at(x0, y0 + 1) + ax * ay * at(x0 + 1, y0 + 1);
+            out[(size_t)(h - 1 - v) * w + u] = (uint8_t)std::lrint(val);
+        }
+    return out;
+}
+
 // --write-files DIR: the synthetic map as the files the reference's loaders read (OBJ + BMP, or XYZ + offset) and a settings file
 // in the reference's YAML format that names them.  Numbers are printed with enough digits to come back bit for bit.
 static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, const std::vector<float> &xyz, const std::vector<float> &attr,
@@ -176,7 +206,9 @@ int main(int argc, char **argv)
     //           With --write-files the settings file describes that full-size camera; with --files it is read as such and brought
     //           to the search size by nmi_config_reduce.
     //   --write-files DIR: write the map and a settings file into DIR and stop (no GPU needed)
-    //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names
+    //   --files DIR: take camera, grid, render parameters and the map from DIR/settings.yaml and the files it names; the lens too:
+    //           Camera.k1 k2 p1 p2 [k3] (nmi_level_set_distortion) or, with Camera.type "KannalaBrandt8", the fisheye Camera.k1 .. k4
+    //           (nmi_level_set_distortion_fisheye, K_raw = K), through which the camera's frame is then made
     //           (nmi_config_load, nmi_map_load_obj / _bmp / _xyz) instead of building them in memory
     int keyframes = 200, mesh_nx = 0, mesh_ny = 0;
     float density = 0.9f;
@@ -227,11 +259,14 @@ int main(int argc, char **argv)
     int tw = 0, th = 0;
     nmi_config cfg;
     memset(&cfg, 0, sizeof cfg);
+    int32_t lens_model = NMI_LENS_RADTAN;  // --files: the settings file's lens (nmi_config_load_lens)
+    float lens[5] = {0, 0, 0, 0, 0};
     unsigned s = 2468u;
     if (read_dir) {
         const std::string d = std::string(read_dir) + "/";
         int rc = nmi_config_load((d + "settings.yaml").c_str(), &cfg);
         if (rc == 0 && reduce > 1) rc = nmi_config_reduce(&cfg, reduce);  // the file describes the full-size camera
+        if (rc == 0) rc = nmi_config_load_lens((d + "settings.yaml").c_str(), &lens_model, lens);
         if (rc != 0 || cfg.width != W || cfg.height != H) {
             fprintf(stderr, "settings.yaml: rc %d, %d x %d (this program is built for %d x %d)\n", rc, cfg.width, cfg.height, W, H);
             return 1;
@@ -359,6 +394,7 @@ int main(int argc, char **argv)
         CHECK_NMI(nmi_synchronize(cctx));
         std::vector<uint8_t> img((size_t)CW * CH), frame((size_t)CW * CH);
         CHECK_HIP(hipMemcpy(img.data(), d_shot, img.size(), hipMemcpyDeviceToHost));
+        if (lens_model == NMI_LENS_FISHEYE) img = through_fisheye(img, CW, CH, crp.fx, crp.fy, crp.cx, crp.cy, lens);  // a fisheye camera's frame
         if (F > 1) {
             (void)hipFree(d_shot);
             if (mesh) nmi_texture_destroy(ctex);
@@ -459,10 +495,15 @@ int main(int argc, char **argv)
         CHECK_NMI(nmi_level_set_coverage(p.level, 1, d_hood));  // every replay: coverage + warp masks, covered search
     else if (masked)
         CHECK_NMI(nmi_level_set_masks(p.level, 1, d_hood));  // every replay: warp masks, counts, masked search
-    if (read_dir) {
+    if (lens_model == NMI_LENS_FISHEYE) {
+        // the fisheye lens of the settings file (Camera.type "KannalaBrandt8", Camera.k1 .. k4): calibrated with the file's camera
+        // matrix, and undistorted onto the same one (K_raw = NULL) by every replay
+        const double Kc[9] = {cfg.fx, 0, cfg.cx, 0, cfg.fy, cfg.cy, 0, 0, 1};
+        CHECK_NMI(nmi_level_set_distortion_fisheye(p.level, Kc, nullptr, lens));
+        printf("fisheye lens: k1 %g k2 %g k3 %g k4 %g\n", lens[0], lens[1], lens[2], lens[3]);
+    } else if (read_dir) {
         // the lens of the settings file (Camera.k1 k2 p1 p2 k3): a distorted camera's frame is undistorted by every replay
-        float dist[5];
-        CHECK_NMI(nmi_config_load_distortion((std::string(read_dir) + "/settings.yaml").c_str(), dist));
+        const float *dist = lens;
         if (dist[0] != 0.0f || dist[1] != 0.0f || dist[2] != 0.0f || dist[3] != 0.0f || dist[4] != 0.0f) {
             const double Kc[9] = {cfg.fx, 0, cfg.cx, 0, cfg.fy, cfg.cy, 0, 0, 1};
             CHECK_NMI(nmi_level_set_distortion(p.level, Kc, dist));

@@ -43,7 +43,9 @@ extern "C" {
                                  nmi_stream_copy_counts, and after nmi_undistort_frame,
                                  nmi_level_set_distortion, nmi_stream_set_distortion, and after nmi_gray_frame,
                                  nmi_level_set_frame_format, nmi_stream_set_frame_format, and after nmi_reduce_frame,
-                                 nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction */
+                                 nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction, and after
+                                 nmi_undistort_frame_fisheye, nmi_level_set_distortion_fisheye,
+                                 nmi_stream_set_distortion_fisheye */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -295,6 +297,39 @@ int nmi_pack_mask_bits(nmi_ctx *ctx, const uint8_t *d_masks /*[n][H][W]*/, int32
  */
 int nmi_undistort_frame(nmi_ctx *ctx, const double K[9], const float dist[5] /* k1 k2 p1 p2 k3 */, const uint8_t *d_raw,
                         const uint8_t *d_raw_mask /* nullable */, uint8_t *d_frame, uint8_t *d_frame_mask /* nullable: no mask written */);
+/*
+ * Fisheye lenses (new): the four-coefficient equidistant model -- Kannala-Brandt, cv::fisheye, Kalibr "equidistant", ORB-SLAM3
+ * Camera.type "KannalaBrandt8" -- of most wide-angle cameras.  nmi_undistort_frame_fisheye is nmi_undistort_frame for it, with
+ * two camera matrices: K is the pinhole camera of the renders and the warps (the output), K_raw the matrix the coefficients
+ * were calibrated with (the raw frame); K_raw = NULL means K.  A fisheye frame is normally undistorted onto a pinhole with a
+ * shorter focal length than K_raw's, to keep its field of view.
+ *   Host: cxn, cyn = fl32(K[2], K[5]); ifx = fl32(1.0 / K[0]), ify = fl32(1.0 / K[4]) in double; fx, fy, cx, cy =
+ *   fl32(K_raw[0], K_raw[4], K_raw[2], K_raw[5]); k1 .. k4 as given (fp32).  Per output pixel (u, v), fp32 in this order:
+ *     x = (u - cxn) * ifx;  y = (v - cyn) * ify;  r2 = x*x + y*y;  r = sqrtf(r2)
+ *     theta = atan32(r):
+ *         big = r > 2.414213562373095f;  mid = !big && r > 0.4142135623730950f
+ *         a    = big ? -1.0f / r : mid ? (r - 1.0f) / (r + 1.0f) : r
+ *         base = big ? fl32(pi/2) : mid ? fl32(pi/4) : 0.0f
+ *         z = a*a
+ *         q = ((8.05374449538e-2f*z - 1.38776856032e-1f)*z + 1.99777106478e-1f)*z - 3.33329491539e-1f
+ *         theta = base + ((q*z)*a + a)
+ *     t2 = theta*theta
+ *     td = theta + theta * (t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+ *     s  = r > 1e-8f ? td / r : 1.0f
+ *     xs = cx + fx * (x * s);  ys = cy + fy * (y * s)
+ *   (the arctangent written out in + - * /, a correctly rounded sqrtf and selects, not atanf, whose device and host forms
+ *   differ in the last bit).  Value and mask at (xs, ys) are nmi_undistort_frame's.  There is no identity case: zero
+ *   coefficients are an ideal equidistant lens, still a remap.  Where the polynomial folds over the result is whatever the
+ *   formula gives.  Rays at or beyond 90 degrees from the axis are not covered (a pinhole output cannot show them).  Parity
+ *   with cv::fisheye unpinned (OpenCV is not part of the reference tree).
+ * Enqueued on the context's stream.  NMI_ERR_INVALID_ARGUMENT, before anything is enqueued, as for nmi_undistort_frame, with
+ * K_raw (when given) held to K's rules and four coefficients.
+ * Captured levels: nmi_level_set_distortion_fisheye.  Streams: nmi_stream_set_distortion_fisheye.  Settings:
+ * nmi_config_parse_lens (include/nmi_host.h).
+ */
+int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_raw[9] /* NULL = K */, const float dist[4] /* k1 k2 k3 k4 */,
+                                const uint8_t *d_raw, const uint8_t *d_raw_mask /* nullable */, uint8_t *d_frame,
+                                uint8_t *d_frame_mask /* nullable: no mask written */);
 
 /*
  * Colour and pitched camera frames (new).  The reference's tracker turns each camera frame into the grey mImGray its NMI path
@@ -566,6 +601,17 @@ int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_w
  */
 int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[5] /* NULL = off */);
 /*
+ * Fisheye lenses.  nmi_level_set_distortion_fisheye is nmi_level_set_distortion for the model of nmi_undistort_frame_fisheye:
+ * every replay's undistortion node is that call's, and the replay equals the same chains with it in nmi_undistort_frame's
+ * place.  A level has one lens setting: of the two setters the later call wins, and dist = NULL in either turns it off.  Four
+ * zero coefficients do not (an ideal equidistant lens is still a remap).  With nmi_level_set_frame_reduction, K and K_raw are
+ * those of the reduced frame.  Everything else -- capturing again, waiting for a replay in flight, masks, coverage, frame
+ * format and reduction in any order, empty blocks, the RCCL and block forms, the buffers freed when off, the errors with K_raw
+ * (NULL = K) held to K's rules -- as nmi_level_set_distortion.
+ */
+int nmi_level_set_distortion_fisheye(nmi_level *lv, const double K[9], const double K_raw[9] /* NULL = K */,
+                                     const float dist[4] /* NULL = off */);
+/*
  * Colour and pitched frames.  nmi_level_set_frame_format(lv, format, pitch) makes a level of any of the four nmi_level_create*
  * forms (and its RCCL runs) read d_frame -- d_frame alone; a frame mask stays dense uint8 [H][W] in raw coordinates -- in place
  * on every replay as H rows of pitch bytes in format (pitch 0: dense).  The replay gains one node after the prep node, which
@@ -676,6 +722,10 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
  * stream left as it was).  Memory: 2 x H*W bytes on the first distorted frame, 2 x H*W more on the first masked or covered one.
  */
 int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5] /* NULL = off */);
+/* Fisheye lenses on a stream: nmi_stream_set_distortion for the model of nmi_undistort_frame_fisheye.  One lens setting per
+ * stream: of the two setters the later call wins, dist = NULL in either turns it off, four zero coefficients do not. */
+int nmi_stream_set_distortion_fisheye(nmi_stream *st, const double K[9], const double K_raw[9] /* NULL = K */,
+                                      const float dist[4] /* NULL = off */);
 /*
  * Colour and pitched frames on a stream: after nmi_stream_set_frame_format(st, format, pitch) every frame submission, of every
  * kind (plain, masked, covered and their _block forms), reads h_frame as H rows of pitch bytes in format (pitch 0: dense).  The

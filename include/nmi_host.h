@@ -126,6 +126,16 @@ int nmi_config_load(const char *yaml_path, nmi_config *out);
  * Camera.fx..cy.  Returns 0, or <0: -1 NULL argument, -2 syntax, -5 file not readable. */
 int nmi_config_parse_distortion(const char *text, size_t len, float dist[5]);
 int nmi_config_load_distortion(const char *yaml_path, float dist[5]);
+/* The lens model and its coefficients in one call.  Camera.type "KannalaBrandt8" (ORB-SLAM3's name for the four-coefficient
+ * equidistant fisheye model): *model = NMI_LENS_FISHEYE and dist = fl32 of Camera.k1, k2, k3, k4 with dist[4] = 0 -- input of
+ * nmi_undistort_frame_fisheye / nmi_level_set_distortion_fisheye / nmi_stream_set_distortion_fisheye with K_raw from
+ * Camera.fx..cy.  Camera.type missing or "PinHole": *model = NMI_LENS_RADTAN and dist exactly nmi_config_parse_distortion's.
+ * A missing coefficient reads as 0; any other Camera.type is a syntax error.  nmi_config keeps its layout.  Returns as the
+ * distortion pair does. */
+#define NMI_LENS_RADTAN 0  /* radial-tangential: k1 k2 p1 p2 k3 */
+#define NMI_LENS_FISHEYE 1 /* Kannala-Brandt equidistant: k1 k2 k3 k4 */
+int nmi_config_parse_lens(const char *text, size_t len, int32_t *model, float dist[5]);
+int nmi_config_load_lens(const char *yaml_path, int32_t *model, float dist[5]);
 /* The channel order of the same file's camera frames (src/Tracking.cc:179-183): *rgb = Camera.RGB as an int, 1 for RGB(A) and 0 for
  * BGR(A) -- NMI_FRAME_RGB / NMI_FRAME_BGR (or their 4-channel forms) of nmi_gray_frame, nmi_level_set_frame_format and
  * nmi_stream_set_frame_format (include/nmi_hip.h).  A missing key reads as 0, as cv::FileNode's int conversion gives it to

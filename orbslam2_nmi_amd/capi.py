@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "nmi_reduce_frame", "nmi_level_set_frame_reduction", "nmi_stream_set_frame_reduction",
     "nmi_render_mesh_colored", "nmi_render_mesh_colored_masked", "nmi_sort_triangles_colored", "nmi_level_create_mesh_colored",
     "nmi_level_create_mesh_colored_block",
+    "nmi_undistort_frame_fisheye", "nmi_level_set_distortion_fisheye", "nmi_stream_set_distortion_fisheye",
 )
 
 
@@ -147,6 +148,9 @@ def load_library(build_if_missing=False):
     lib.nmi_undistort_frame.argtypes = [vp, C.POINTER(C.c_double), f32p, vp, vp, vp, vp]
     lib.nmi_level_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
     lib.nmi_stream_set_distortion.argtypes = [vp, C.POINTER(C.c_double), f32p]
+    lib.nmi_undistort_frame_fisheye.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), f32p, vp, vp, vp, vp]
+    lib.nmi_level_set_distortion_fisheye.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), f32p]
+    lib.nmi_stream_set_distortion_fisheye.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), f32p]
     lib.nmi_gray_frame.argtypes = [vp, vp, i32, C.c_int64, vp]
     lib.nmi_level_set_frame_format.argtypes = [vp, i32, C.c_int64]
     lib.nmi_stream_set_frame_format.argtypes = [vp, i32, C.c_int64]
@@ -230,6 +234,23 @@ def _lens(K, dist):
     if d.size != 5:
         raise ValueError("dist must be k1 k2 p1 p2 k3 (5 entries; pad k3 = 0)")
     return k, d, k.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _fisheye(K, K_raw, dist):
+    """(K, K_raw [3,3] or [9] float64 -- K_raw None: K --, dist (k1, k2, k3, k4) float32 or None) -> the arrays (kept alive by the
+    caller) and the three pointers the fisheye calls take."""
+    if K is None and dist is None:
+        return (None, None, None), (None, None, None)
+    k = np.ascontiguousarray(K, np.float64).reshape(-1)
+    kr = None if K_raw is None else np.ascontiguousarray(K_raw, np.float64).reshape(-1)
+    if k.size != 9 or (kr is not None and kr.size != 9):
+        raise ValueError("K and K_raw must have 9 entries")
+    d = None if dist is None else np.ascontiguousarray(dist, np.float32).reshape(-1)
+    if d is not None and d.size != 4:
+        raise ValueError("dist must be k1 k2 k3 k4 (4 entries)")
+    dp = C.POINTER(C.c_double)
+    return (k, kr, d), (k.ctypes.data_as(dp), None if kr is None else kr.ctypes.data_as(dp),
+                        None if d is None else d.ctypes.data_as(C.POINTER(C.c_float)))
 
 
 def _dev_mask(t, ndim, what):
@@ -512,6 +533,23 @@ class NmiContext:
         lens coefficients dist = (k1, k2, p1, p2, k3) -> (frame [H,W] u8, mask [H,W] u8 or None).  raw_mask: optional device
         [H,W] uint8 / bool, nonzero = usable raw pixel.  out_mask=False: no mask is written (None is returned in its place);
         otherwise a new uint8 tensor when None.  Enqueued on the context's stream."""
+        k, d, kp, dp = _lens(K, dist)
+        if d is None:
+            raise ValueError("undistort_frame needs the five coefficients")
+        return self._undistort(lambda *bufs: self._lib.nmi_undistort_frame(self._h, kp, dp, *bufs), "nmi_undistort_frame", raw, raw_mask,
+                               out, out_mask, sync)
+
+    def undistort_frame_fisheye(self, raw, K, K_raw, dist, raw_mask=None, out=None, out_mask=None, sync=True):
+        """nmi_undistort_frame_fisheye: undistort_frame for the equidistant fisheye model (Kannala-Brandt): K ([3,3] float64) is the
+        pinhole camera of the output, K_raw the camera the coefficients dist = (k1, k2, k3, k4) were calibrated with (None: K)."""
+        keep, (kp, krp, dp) = _fisheye(K, K_raw, dist)
+        if dp is None:
+            raise ValueError("undistort_frame_fisheye needs the four coefficients")
+        return self._undistort(lambda *bufs: self._lib.nmi_undistort_frame_fisheye(self._h, kp, krp, dp, *bufs), "nmi_undistort_frame_fisheye",
+                               raw, raw_mask, out, out_mask, sync)
+
+    def _undistort(self, call, what, raw, raw_mask, out, out_mask, sync):
+        """The buffers of undistort_frame / undistort_frame_fisheye; call(raw, raw_mask, out, out_mask pointers) -> the C call's code."""
         import torch
         r = self._img(raw, "raw")
         rm = None
@@ -519,9 +557,6 @@ class NmiContext:
             rm = _dev_mask(raw_mask, 2, "raw_mask")
             if tuple(rm.shape) != (self.height, self.width):
                 raise ValueError(f"raw_mask is {tuple(rm.shape)}, context is {(self.height, self.width)}")
-        k, d, kp, dp = _lens(K, dist)
-        if d is None:
-            raise ValueError("undistort_frame needs the five coefficients")
         if out is None:
             out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
         o = self._img(out, "out")
@@ -533,8 +568,7 @@ class NmiContext:
             if tuple(om.shape) != (self.height, self.width):
                 raise ValueError(f"out_mask is {tuple(om.shape)}, context is {(self.height, self.width)}")
         self._order_after_torch()
-        self._check(self._lib.nmi_undistort_frame(self._h, kp, dp, r.data_ptr(), rm.data_ptr() if rm is not None else None, o.data_ptr(),
-                                                  om.data_ptr() if om is not None else None), "nmi_undistort_frame")
+        self._check(call(r.data_ptr(), rm.data_ptr() if rm is not None else None, o.data_ptr(), om.data_ptr() if om is not None else None), what)
         if sync:
             self.synchronize()
         return out, om
@@ -1051,6 +1085,14 @@ class NmiLevel:
         self.ctx._order_after_torch()
         self.ctx._check(self._lib.nmi_level_set_distortion(self._h, kp, dp), "nmi_level_set_distortion")
 
+    def set_distortion_fisheye(self, K, K_raw, dist):
+        """Fisheye lens (nmi_level_set_distortion_fisheye): set_distortion for the equidistant model, K the pinhole camera of the
+        renders, K_raw the raw frame's (None: K), dist = (k1, k2, k3, k4).  One lens setting per level: the later of the two calls
+        wins; dist=None turns it off (four zeros do not)."""
+        keep, (kp, krp, dp) = _fisheye(K, K_raw, dist)
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_distortion_fisheye(self._h, kp, krp, dp), "nmi_level_set_distortion_fisheye")
+
     def set_frame_format(self, fmt, pitch=0):
         """Colour or pitched frame (nmi_level_set_frame_format): every replay reads the level's frame in place as H rows of `pitch`
         bytes (0: dense) in format fmt (FRAME_*) and converts it to grey on the device (undistorting it in the same node when
@@ -1186,6 +1228,12 @@ class NmiStream:
         zeros turns it off."""
         k, d, kp, dp = _lens(K, dist)
         self.ctx._check(self._lib.nmi_stream_set_distortion(self._h, kp, dp), "nmi_stream_set_distortion")
+
+    def set_distortion_fisheye(self, K, K_raw, dist):
+        """Fisheye lens (nmi_stream_set_distortion_fisheye): set_distortion for the equidistant model, K the pinhole camera of the
+        renders, K_raw the raw frame's (None: K), dist = (k1, k2, k3, k4).  The later of the two calls wins; dist=None turns it off."""
+        keep, (kp, krp, dp) = _fisheye(K, K_raw, dist)
+        self.ctx._check(self._lib.nmi_stream_set_distortion_fisheye(self._h, kp, krp, dp), "nmi_stream_set_distortion_fisheye")
 
     def set_frame_format(self, fmt, pitch=0):
         """Colour or pitched host frames (nmi_stream_set_frame_format): frames of later submissions, of every kind, are H rows of

@@ -17,6 +17,15 @@ int intake_set_distortion(FrameIntake *in, const double K[9], const float dist[5
     return NMI_OK;
 }
 
+int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const double K_raw[9], const float dist[4])
+{
+    nmi::UndistortParams ud{};
+    if (dist && fisheye_params(K, K_raw, dist, &ud) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    in->distorted = dist != nullptr;  // no identity case: zero coefficients are an ideal equidistant lens, still a remap
+    in->ud = ud;
+    return NMI_OK;
+}
+
 int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch)
 {
     if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;

@@ -669,6 +669,15 @@ int nmi_level_set_distortion(nmi_level *lv, const double K[9], const float dist[
     return level_apply(lv, next, "nmi_level_set_distortion");
 }
 
+int nmi_level_set_distortion_fisheye(nmi_level *lv, const double K[9], const double K_raw[9], const float dist[4])
+{
+    FrameIntake probe;  // (as nmi_level_set_distortion: a bad argument is refused without reading *lv)
+    if (!lv || intake_set_distortion_fisheye(&probe, K, K_raw, dist) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    (void)intake_set_distortion_fisheye(&next.intake, K, K_raw, dist);
+    return level_apply(lv, next, "nmi_level_set_distortion_fisheye");
+}
+
 // nmi_level_set_frame_format is nmi_level_set_frame_reduction with factor 1: one setting, the later call wins.
 int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format, int64_t pitch)
 {
@@ -1077,6 +1086,11 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
 int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5])
 {
     return st ? intake_set_distortion(&st->intake, K, dist) : NMI_ERR_INVALID_ARGUMENT;
+}
+
+int nmi_stream_set_distortion_fisheye(nmi_stream *st, const double K[9], const double K_raw[9], const float dist[4])
+{
+    return st ? intake_set_distortion_fisheye(&st->intake, K, K_raw, dist) : NMI_ERR_INVALID_ARGUMENT;
 }
 
 int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t format, int64_t pitch)

@@ -10,7 +10,8 @@
 namespace nmi_internal {
 
 struct FrameIntake {
-    // Lens distortion (nmi_*_set_distortion): the source (and its mask) are the raw frame, undistorted into gray_out (mask_out).
+    // Lens distortion (nmi_*_set_distortion, nmi_*_set_distortion_fisheye: one setting, the later call wins; ud.model tells the
+    // two apart): the source (and its mask) are the raw frame, undistorted into gray_out (mask_out).
     bool distorted = false;
     nmi::UndistortParams ud{};
     // Frame format and reduction (nmi_*_set_frame_format, nmi_*_set_frame_reduction: one setting, the later call wins): the
@@ -26,6 +27,8 @@ struct FrameIntake {
 
 // dist == nullptr, or five zero coefficients: off.  A bad K or dist: NMI_ERR_INVALID_ARGUMENT, *in untouched.
 int intake_set_distortion(FrameIntake *in, const double K[9], const float dist[5]);
+// The fisheye form (K_raw == nullptr: K).  dist == nullptr: off; four zero coefficients stay on (an ideal equidistant lens).
+int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const double K_raw[9], const float dist[4]);
 // factor 1 .. 4, format and pitch checked on the full width factor * width (frame_format_check).  Dense grey of the search
 // size: off (NMI_FRAME_GRAY, pitch 0).  A bad argument: NMI_ERR_INVALID_ARGUMENT, *in untouched.
 int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch);

@@ -234,6 +234,35 @@ int nmi_config_load_distortion(const char *yaml_path, float dist[5])
     return nmi_config_parse_distortion(text.data(), text.size(), dist);
 }
 
+// ORB-SLAM3 settings name the camera model in Camera.type: "PinHole" (the coefficients above) or "KannalaBrandt8" (Camera.k1 ..
+// k4 of the equidistant fisheye model).  The reference's files have no such key: the radial-tangential model.
+int nmi_config_parse_lens(const char *text, size_t len, int32_t *model, float dist[5])
+{
+    if (!text || !model || !dist) return -1;
+    std::map<std::string, Node> m;
+    if (!parse(text, len, m)) return -2;
+    auto it = m.find("Camera.type");
+    const std::string type = it == m.end() || it->second.is_matrix ? "" : it->second.scalar;
+    if (type.empty() || type == "PinHole") return *model = NMI_LENS_RADTAN, nmi_config_parse_distortion(text, len, dist);
+    if (type != "KannalaBrandt8") return -2;
+    static const char *keys[4] = {"Camera.k1", "Camera.k2", "Camera.k3", "Camera.k4"};
+    for (int i = 0; i < 4; ++i) {
+        double v = 0.0;
+        dist[i] = number(m, keys[i], v) ? (float)v : 0.0f;
+    }
+    dist[4] = 0.0f;
+    *model = NMI_LENS_FISHEYE;
+    return 0;
+}
+
+int nmi_config_load_lens(const char *yaml_path, int32_t *model, float dist[5])
+{
+    if (!yaml_path || !model || !dist) return -1;
+    std::string text;
+    if (read_file(yaml_path, text) != 0) return -5;
+    return nmi_config_parse_lens(text.data(), text.size(), model, dist);
+}
+
 // Tracking.cc:179-183: int nRGB = fSettings["Camera.RGB"]; mbRGB = nRGB.  A missing key reads as 0 there (cv::FileNode's int
 // conversion of an empty node), and here; a real value is rounded to the nearest int (half to even), as that conversion's cvRound
 // does, and one out of int range is a syntax error.

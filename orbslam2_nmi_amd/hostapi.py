@@ -7,6 +7,8 @@ import numpy as np
 
 from .capi import load_library
 
+LENS_RADTAN = 0   # NMI_LENS_*: the model of config_parse_lens
+LENS_FISHEYE = 1
 AXES = ("synthX", "synthY", "synthZ", "warpX", "warpY", "warpZ")
 MAX_ITER = 16
 
@@ -15,7 +17,7 @@ EXPORTED_SYMBOLS = (
     "nmi_sk_format", "nmi_sk_linear_index", "nmi_sk_set_best_from_index", "nmi_find_max_elements",
     "nmi_calculate_translation", "nmi_calculate_relocalization", "nmi_mat4_inverse", "nmi_relocalize_with_strategy",
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
-    "nmi_config_parse_distortion", "nmi_config_load_distortion",
+    "nmi_config_parse_distortion", "nmi_config_load_distortion", "nmi_config_parse_lens", "nmi_config_load_lens",
     "nmi_config_parse_color_order", "nmi_config_load_color_order", "nmi_config_reduce",
     "nmi_map_load_obj_colored",
 )
@@ -104,6 +106,8 @@ def _lib():
         lib.nmi_config_load.argtypes = [C.c_char_p, C.POINTER(Config)]
         lib.nmi_config_parse_distortion.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_float)]
         lib.nmi_config_load_distortion.argtypes = [C.c_char_p, C.POINTER(C.c_float)]
+        lib.nmi_config_parse_lens.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        lib.nmi_config_load_lens.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         lib.nmi_config_parse_color_order.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.nmi_config_load_color_order.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
         lib.nmi_config_reduce.argtypes = [C.POINTER(Config), C.c_int32]
@@ -222,6 +226,25 @@ def config_load_distortion(path):
     if rc != 0:
         raise ValueError(f"nmi_config_load_distortion({path}) failed: {rc}")
     return out
+
+
+def config_parse_lens(text):
+    """The lens model of a settings file -> (model, dist float32 [5]).  Camera.type "KannalaBrandt8": (LENS_FISHEYE, (k1, k2, k3,
+    k4, 0)); missing or "PinHole": (LENS_RADTAN, config_parse_distortion's five).  Raises on errors."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    out, model = np.zeros(5, np.float32), C.c_int32(-1)
+    rc = _lib().nmi_config_parse_lens(raw, len(raw), C.byref(model), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError(f"nmi_config_parse_lens failed: {rc}")
+    return int(model.value), out
+
+
+def config_load_lens(path):
+    out, model = np.zeros(5, np.float32), C.c_int32(-1)
+    rc = _lib().nmi_config_load_lens(str(path).encode(), C.byref(model), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError(f"nmi_config_load_lens({path}) failed: {rc}")
+    return int(model.value), out
 
 
 def config_parse_color_order(text):
