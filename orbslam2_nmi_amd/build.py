@@ -57,7 +57,7 @@ def flags(ablations=False):
 
 def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None):
     """One object per source under lib/obj/ (recompiled when the source, any header or -- for the nmi_kernels_* wrappers --
-    nmi_kernels.hip, for nmi_mesh_color.hip nmi_mesh.hip, is newer), compiled in parallel, then one link.  Same flags for every translation unit; no relocatable
+    nmi_kernels.hip is newer), compiled in parallel, then one link.  Same flags for every translation unit; no relocatable
     device code (no kernel calls across units).  Objects and the library are written under private names and renamed, and one builder
     runs at a time (flock): concurrent callers wait and then find nothing left to do."""
     import fcntl
@@ -89,8 +89,6 @@ def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None
             dep = max(os.path.getmtime(src), newest_header)
             if os.path.basename(src).startswith("nmi_kernels_"):
                 dep = max(dep, os.path.getmtime(grid_src))
-            if os.path.basename(src) == "nmi_mesh_color.hip":   # includes nmi_mesh.hip the same way (NMI_MESH_COLOR)
-                dep = max(dep, os.path.getmtime(os.path.join(PKG, "csrc", "nmi_mesh.hip")))
             if force or not os.path.exists(obj) or os.path.getmtime(obj) < dep:
                 todo.append((src, obj))
         if todo:

@@ -6,7 +6,6 @@
 #include "nmi_intake.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
-#include "nmi_mesh_color.h"
 #include "nmi_reduce.h"
 #include "nmi_undistort.h"
 
@@ -235,12 +234,8 @@ static int level_capture(nmi_level *lv)
             if (covered) ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
-        if (lv->kind == MapKind::colored_mesh)
-            ok(nmi::launch_render_mesh_colored(d_xyz, d_attr, n_points, lv->d_mvps, S, lv->mesh, S,
-                                               (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit,
-                                               lv->d_renders, p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
-        else if (mesh)
-            ok(nmi::launch_render_mesh(d_xyz, d_attr, n_points, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, lv->d_mvps, S, lv->mesh, S,
+        if (mesh)
+            ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, lv->d_mvps, S, lv->mesh, S,
                                        (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
                                        p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
         else if (fused)

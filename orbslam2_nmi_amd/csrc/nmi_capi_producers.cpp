@@ -1,7 +1,6 @@
 // nmi_capi_producers.cpp -- C ABI of the stack producers: warp stack, point-cloud and textured-mesh
 // render stacks, vertex-coloured-mesh render stacks.  Declared in include/nmi_hip.h.
 #include "nmi_ctx.h"
-#include "nmi_mesh_color.h"
 
 using namespace nmi_internal;
 
@@ -377,17 +376,20 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
     int rc = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (rc != NMI_OK) return rc;
     const int bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
-    const hipError_t e =
-        textured ? nmi::launch_render_mesh(d_xyz, d_attr, n_triangles, tex->d_luma, tex->levels, tex->w, tex->h, tex->off, d_mvps, S, ctx->mesh, ctx->mesh_views,
-                                      bin_cap, ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
-                                      nullptr, nullptr, 0, cover)
-            : nmi::launch_render_mesh_colored(d_xyz, d_attr, n_triangles, d_mvps, S, ctx->mesh, ctx->mesh_views, bin_cap, ctx->clip_queue_limit,
-                                              d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr, nullptr, nullptr, 0, cover);
+    const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, d_mvps, S, ctx->mesh, ctx->mesh_views, bin_cap,
+                                                 ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
+                                                 nullptr, nullptr, 0, cover);
     if (e != hipSuccess) {
         ctx->mesh_views = 0;  // whatever state the buffers are in: allocate and clear afresh next time
-        return hip_fail(ctx, e, textured ? "launch_render_mesh" : "launch_render_mesh_colored");
+        return hip_fail(ctx, e, "launch_render_mesh");
     }
     return NMI_OK;
+}
+
+nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_texture *tex)
+{
+    if (kind == MapKind::textured_mesh) return nmi::MeshShading{true, d_attr, tex->d_luma, tex->levels, tex->w, tex->h, tex->off};
+    return nmi::MeshShading{false, d_attr};
 }
 
 }  // namespace nmi_internal

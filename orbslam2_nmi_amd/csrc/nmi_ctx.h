@@ -229,6 +229,7 @@ int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int
                        float point_size, uint8_t *d_render_stack, uint8_t *cover);
 int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_triangles, const nmi_texture *tex,
                      const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover);
+nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_texture *tex);  // launch_render_mesh's description of a mesh kind
 int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
                     int Wn);
 

@@ -155,7 +155,7 @@ size_t grid_kernel_scratch_bytes(int workgroups);
 hipError_t launch_warp(const uint8_t *frame, const float *coeffs /*[Wn][9] inverse maps*/, uint8_t *out, int width,
                        int height, int Wn, hipStream_t stream);
 
-// Textured-mesh renderer (nmi_mesh.hip): a binned, deferred rasteriser.  MeshWork = its device buffers, owned by a context
+// Mesh renderer (nmi_mesh.hip): a binned, deferred rasteriser for textured and for vertex-coloured meshes.  MeshWork = its device buffers, owned by a context
 // or by a level; zbuf must be all ones and state all zero before a render (launch_mesh_clear once after allocation) and
 // the renderer leaves them so.  bin_cap_limit: usable entries per bin (NMI_OPT_TILE_QUEUE; 0 = every triangle is
 // rasterised by its own lane); clip_cap_limit likewise for the queue of triangles crossing the near plane.
@@ -177,8 +177,16 @@ size_t mesh_bins_bytes(int S, int width, int height);
 size_t mesh_state_bytes(int S, int width, int height);
 size_t mesh_clip_item_bytes();
 hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hipStream_t stream);
-hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri, const float *luma, int levels, const int *lw,
-                              const int *lh, const long long *loff, const float *mvps /*[S][16]*/, int S, const MeshWork &w,
+// How a fragment gets its grey: from a texture at the corners' uv, or from the corners' own colours.
+struct MeshShading {
+    bool textured;
+    const float *attr;             // textured: uv [3T][2]; coloured: red [3T], one colour per corner; both in the order of xyz
+    const float *luma = nullptr;   // textured only: the luma pyramid, `levels` (<= 16) levels of lw[l] x lh[l] texels at luma + loff[l]
+    int levels = 0;
+    const int *lw = nullptr, *lh = nullptr;
+    const long long *loff = nullptr;
+};
+hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const float *mvps /*[S][16]*/, int S, const MeshWork &w,
                               int layout_views /* views the work area was allocated for (>= S) */, int bin_cap_limit,
                               unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
                               // a captured level: the Wn warps of `warp_frame` are made by extra workgroups of the first kernel

@@ -37,25 +37,16 @@
 // on the fly.  The memory buffer and the bin counters are left clean by the tile kernel (it re-clears what it read), so a
 // render has no clear pass; tiles without small triangles never touch the buffer.
 //
-// NMI_MESH_COLOR (nmi_mesh_color.hip includes this file with it set): the same rasteriser for a mesh with one colour per corner
-// instead of a texture, as kernels of their own (nmi_mesh_*_color_kernel) behind launch_render_mesh_colored.  Everything up to the
-// last stage is this file's code unchanged; the attribute array is `red` [3T] where the textured build has `uv` [3T][2], the LDS
-// record carries one attribute plane, and the fragment shader is shade_color.  Without the macro this file compiles exactly as
-// it did before the coloured build existed.
+//
+// Vertex-coloured meshes (a colour per corner, no texture; shaders/ShadingWithColor.*) take the same passes up to the tile kernel,
+// which read positions only; the last stage is mesh_tile_body<Attr, ...> over an attribute policy, TexturedAttr or ColoredAttr,
+// behind tile kernels of their own names (nmi_mesh_tile_color_kernel, its cover form).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "nmi_kernels.h"
 #include "nmi_warp_device.h"
-#ifdef NMI_MESH_COLOR
-#include "nmi_mesh_color.h"
-// (no kernel calls across translation units: the coloured build has its own copies of the passes in front of the tile kernel)
-#define nmi_mesh_bin_kernel nmi_mesh_bin_color_kernel
-#define nmi_mesh_cull_kernel nmi_mesh_cull_color_kernel
-#define nmi_mesh_bin_pairs_kernel nmi_mesh_bin_pairs_color_kernel
-#define nmi_mesh_clip_kernel nmi_mesh_clip_color_kernel
-#endif
 
 namespace nmi {
 
@@ -100,13 +91,13 @@ struct TexLevel {
     uint32_t off_lo, off_hi;  // offset of the level in `luma`, in texels
 };
 
-__device__ __forceinline__ void tex_level_fill(const MeshTexture &t, int l, TexLevel *out)
+__device__ __forceinline__ TexLevel tex_level(const MeshTexture &t, int l)
 {
     TexLevel L;
     L.w = (float)t.w[l], L.h = (float)t.h[l], L.inv_w = t.inv_w[l], L.inv_h = t.inv_h[l];
     L.wi = (uint32_t)t.w[l], L.hi = (uint32_t)t.h[l];
     L.off_lo = (uint32_t)((unsigned long long)t.off[l] & 0xFFFFFFFFull), L.off_hi = (uint32_t)((unsigned long long)t.off[l] >> 32);
-    *out = L;
+    return L;
 }
 
 // GL_LINEAR sample of one level at (u, v) with GL_REPEAT.  Written for instruction count (the shading loop is bound by
@@ -153,11 +144,10 @@ struct TriView {
     int x_lo, x_hi, y_lo, y_hi;        // pixel bounding box, clamped to the window
 };
 
-// A triangle in clip space after near-plane clipping: 3 or 4 corners in the original winding order with their uv.
-struct ClipPoly {
-    float cx[4], cy[4], cz[4], cw[4], u[4], v[4];
-    int n;  // 0 (nothing left), 3 or 4
-};
+// A triangle in clip space after near-plane clipping: n = 0 (nothing left), 3 or 4 corners in the original winding order.
+// ClipPoly: their positions, which is all that the binning side clips; ClipPolyUV: with their attributes, for the last stage.
+struct ClipPoly   { float cx[4], cy[4], cz[4], cw[4]; int n; };
+struct ClipPolyUV { float cx[4], cy[4], cz[4], cw[4], u[4], v[4]; int n; };
 
 // Clip coordinates of the three corners and their signed distances d = z + w to the near plane (inside iff >= 0).
 // Returns the number of corners inside.
@@ -181,36 +171,50 @@ __device__ __forceinline__ int tri_clip_coords(const float *__restrict__ m, cons
 // The rare case (1 or 2 corners inside): Sutherland-Hodgman against the near plane; corners are appended in winding
 // order (3 or 4 of them), new corners interpolated from the inside corner towards the outside one, so that two triangles
 // sharing an edge cut it at the same point.
+// Poly = ClipPoly: positions only.  Poly = ClipPolyUV: the corners' attributes tu[3], tv[3] are interpolated like the positions.
+template <typename Poly>
 __device__ __forceinline__ void tri_clip_poly(const float (&cx)[3], const float (&cy)[3], const float (&cz)[3], const float (&cw)[3],
-                                              const float (&d)[3], const float (&tu)[3], const float (&tv)[3], ClipPoly &P)
+                                              const float (&d)[3], Poly &P, const float *tu = nullptr, const float *tv = nullptr)
 {
+    constexpr bool ATTR = std::is_same<Poly, ClipPolyUV>::value;
     int n = 0;
     auto push = [&](float x, float y, float z, float w, float uu, float vv) {
         // n is 0..3 here; written as selects so that the arrays stay in registers
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (j == n) P.cx[j] = x, P.cy[j] = y, P.cz[j] = z, P.cw[j] = w, P.u[j] = uu, P.v[j] = vv;
+            if (j == n) {
+                P.cx[j] = x, P.cy[j] = y, P.cz[j] = z, P.cw[j] = w;
+                if constexpr (ATTR) P.u[j] = uu, P.v[j] = vv;
+            }
         ++n;
     };
-    P.cx[3] = P.cy[3] = P.cz[3] = P.cw[3] = P.u[3] = P.v[3] = 0.0f;
+    P.cx[3] = P.cy[3] = P.cz[3] = P.cw[3] = 0.0f;
+    if constexpr (ATTR) P.u[3] = P.v[3] = 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int b = (k + 1) % 3;
         const bool in_a = d[k] >= 0.0f, in_b = d[b] >= 0.0f;
-        if (in_a) push(cx[k], cy[k], cz[k], cw[k], tu[k], tv[k]);
+        if (in_a) push(cx[k], cy[k], cz[k], cw[k], ATTR ? tu[k] : 0.0f, ATTR ? tv[k] : 0.0f);
         if (in_a != in_b) {
             const int i = in_a ? k : b, o = in_a ? b : k;  // from the inside corner towards the outside one
             const float t = d[i] / (d[i] - d[o]);
             const float w = cw[i] + (cw[o] - cw[i]) * t;
-            push(cx[i] + (cx[o] - cx[i]) * t, cy[i] + (cy[o] - cy[i]) * t, -w /* on the near plane */, w, tu[i] + (tu[o] - tu[i]) * t,
-                 tv[i] + (tv[o] - tv[i]) * t);
+            push(cx[i] + (cx[o] - cx[i]) * t, cy[i] + (cy[o] - cy[i]) * t, -w /* on the near plane */, w,
+                 ATTR ? tu[i] + (tu[o] - tu[i]) * t : 0.0f, ATTR ? tv[i] + (tv[o] - tv[i]) * t : 0.0f);
         }
     }
     P.n = n;
 }
 
 // Corners (0, sub + 1, sub + 2) of a clipped polygon.
-__device__ __forceinline__ void poly_corners(const ClipPoly &P, int sub, float (&cx)[3], float (&cy)[3], float (&cz)[3], float (&cw)[3],
+__device__ __forceinline__ void poly_corners(const ClipPoly &P, int sub, float (&cx)[3], float (&cy)[3], float (&cz)[3], float (&cw)[3])
+{
+    cx[0] = P.cx[0], cy[0] = P.cy[0], cz[0] = P.cz[0], cw[0] = P.cw[0];
+    cx[1] = sub ? P.cx[2] : P.cx[1], cy[1] = sub ? P.cy[2] : P.cy[1], cz[1] = sub ? P.cz[2] : P.cz[1], cw[1] = sub ? P.cw[2] : P.cw[1];
+    cx[2] = sub ? P.cx[3] : P.cx[2], cy[2] = sub ? P.cy[3] : P.cy[2], cz[2] = sub ? P.cz[3] : P.cz[2], cw[2] = sub ? P.cw[3] : P.cw[2];
+}
+
+__device__ __forceinline__ void poly_corners(const ClipPolyUV &P, int sub, float (&cx)[3], float (&cy)[3], float (&cz)[3], float (&cw)[3],
                                              float (&su)[3], float (&sv)[3])
 {
     cx[0] = P.cx[0], cy[0] = P.cy[0], cz[0] = P.cz[0], cw[0] = P.cw[0], su[0] = P.u[0], sv[0] = P.v[0];
@@ -256,35 +260,38 @@ __device__ __forceinline__ bool tri_setup(const float (&cx)[3], const float (&cy
     return true;
 }
 
-// Corner arrays of triangle `tri`.
-__device__ __forceinline__ void load_tri(const float *__restrict__ xyz, const float *__restrict__ uv, long long tri, float (&px)[3], float (&py)[3],
-                                         float (&pz)[3], float (&tu)[3], float (&tv)[3])
+// Positions of corner `corner` (= triangle * 3 + 0..2) and of a triangle's three: all that the binning side reads of a mesh.
+__device__ __forceinline__ void load_corner(const float *__restrict__ xyz, long long corner, float &x, float &y, float &z)
 {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        px[k] = xyz[(tri * 3 + k) * 3], py[k] = xyz[(tri * 3 + k) * 3 + 1], pz[k] = xyz[(tri * 3 + k) * 3 + 2];
-#ifdef NMI_MESH_COLOR
-        tu[k] = uv[tri * 3 + k], tv[k] = 0.0f;   // `uv` is red [3T]: the colour takes u's way through the clipper and the planes, v's is dead code
-#else
-        tu[k] = uv[(tri * 3 + k) * 2], tv[k] = uv[(tri * 3 + k) * 2 + 1];
-#endif
-    }
+    x = xyz[corner * 3], y = xyz[corner * 3 + 1], z = xyz[corner * 3 + 2];
 }
 
-// (triangle, piece) as view `m` sees it: piece 0 of a triangle wholly behind... in front of the near plane is the triangle
-// itself; of one that crosses it, pieces 0 and 1 are the triangles of its clipped polygon.  Every kernel sets a triangle up
-// through this one function, so which of them handles a pixel does not change its value.
-__device__ __forceinline__ bool setup_piece(const float *__restrict__ xyz, const float *__restrict__ uv, long long tri, int sub,
+__device__ __forceinline__ void load_tri(const float *__restrict__ xyz, long long tri, float (&px)[3], float (&py)[3], float (&pz)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) load_corner(xyz, tri * 3 + k, px[k], py[k], pz[k]);
+}
+
+// (triangle, piece) as view `m` sees it, with its corners' attributes (su, sv; Attr: TexturedAttr or ColoredAttr, below): piece 0
+// of a triangle wholly in front of the near plane is the triangle itself; of one that crosses it, pieces 0 and 1 are the triangles
+// of its clipped polygon.  The tile kernel sets every triangle up through this one function, and the binning side takes the same
+// steps on the positions (bin_one_view, clip_and_bin), so which of them handles a pixel does not change its value.
+template <typename Attr>
+__device__ __forceinline__ bool setup_piece(const float *__restrict__ xyz, const float *__restrict__ attr, long long tri, int sub,
                                             const float *__restrict__ m, int width, int height, TriView &t, float (&su)[3], float (&sv)[3])
 {
     float px[3], py[3], pz[3], cx[3], cy[3], cz[3], cw[3], d[3];
-    load_tri(xyz, uv, tri, px, py, pz, su, sv);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        load_corner(xyz, tri * 3 + k, px[k], py[k], pz[k]);
+        Attr::load_corner(attr, tri * 3 + k, su[k], sv[k]);
+    }
     const int n_in = tri_clip_coords(m, px, py, pz, cx, cy, cz, cw, d);
     if (n_in == 0) return false;
     if (n_in < 3) {
-        ClipPoly P;
+        ClipPolyUV P;
         const float tu[3] = {su[0], su[1], su[2]}, tv[3] = {sv[0], sv[1], sv[2]};
-        tri_clip_poly(cx, cy, cz, cw, d, tu, tv, P);
+        tri_clip_poly(cx, cy, cz, cw, d, P, tu, tv);
         if (sub + 3 > P.n) return false;
         poly_corners(P, sub, cx, cy, cz, cw, su, sv);
     } else if (sub) {
@@ -387,7 +394,6 @@ __device__ __forceinline__ uint32_t shade_pixel(const Planes &P, const float *__
     return (uint32_t)(fminf(fmaxf(luma, 0.0f), 1.0f) * 255.0f + 0.5f);
 }
 
-#ifdef NMI_MESH_COLOR
 // The coloured fragment shader (shaders/ShadingWithColor.*: the interpolated vertex colour, passed through): c = S / Q with S the
 // plane of colour / w -- shade_pixel's u, by the same operations and the same reciprocal -- and the point renderer's grey rule
 // (nmi_producers.hip): clamp to [0, 1], times 255, rounded; fmaxf drops a NaN, so a NaN colour gives 0.
@@ -400,7 +406,6 @@ __device__ __forceinline__ uint32_t shade_color(const Planes &P, float fxp, floa
     const float c = S * iq;
     return (uint32_t)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f + 0.5f);
 }
-#endif
 
 __device__ __forceinline__ unsigned long long make_key(uint32_t depth, unsigned long long id /* triangle << 1 | piece */, uint32_t slot)
 {
@@ -599,10 +604,10 @@ struct WarpFuse {
     int blocks;  // 0: none
 };
 
-__global__ __launch_bounds__(256) void nmi_mesh_bin_kernel(const float *__restrict__ xyz, const float *__restrict__ uv, long long ntri,
-                                                           const float *__restrict__ mvps, int views, int width, int height, BinGrid g,
-                                                           ClipItem *__restrict__ clipq, unsigned long long *__restrict__ clip_state,
-                                                           unsigned long long clip_cap, int shares, WarpFuse wf)
+__global__ __launch_bounds__(256) void nmi_mesh_bin_kernel(const float *__restrict__ xyz, long long ntri, const float *__restrict__ mvps, int views,
+                                                           int width, int height, BinGrid g, ClipItem *__restrict__ clipq,
+                                                           unsigned long long *__restrict__ clip_state, unsigned long long clip_cap, int shares,
+                                                           WarpFuse wf)
 {
     // The triangle blocks come first in the launch: what they take is round trips (frustum test, appends) on the few hundred of
     // them that see anything, and those should start at once; the warp blocks are plain arithmetic and fill in behind
@@ -625,8 +630,8 @@ __global__ __launch_bounds__(256) void nmi_mesh_bin_kernel(const float *__restri
     for (int t = threadIdx.x; t < views; t += blockDim.x) beyond[t] = (t >= v_first && t < v_end) ? 0x3Fu : 0u;
     const long long tri = tri_block * (long long)blockDim.x + threadIdx.x;
     const bool valid = tri < ntri;
-    float px[3] = {0, 0, 0}, py[3] = {0, 0, 0}, pz[3] = {0, 0, 0}, tu[3], tv[3];
-    if (valid) load_tri(xyz, uv, tri, px, py, pz, tu, tv);
+    float px[3] = {0, 0, 0}, py[3] = {0, 0, 0}, pz[3] = {0, 0, 0};
+    if (valid) load_tri(xyz, tri, px, py, pz);
     // (Fetching the block's corners through LDS with 16-byte loads instead -- a lane's nine floats lie 36 bytes from its
     // neighbour's -- measured slower: 12.8 vs 10.4 us for this kernel up to the frustum test, 120 k triangles.)
     {
@@ -666,12 +671,12 @@ __global__ __launch_bounds__(256) void nmi_mesh_cull_kernel(const float *__restr
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     if (tri < ntri) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < 3; ++c) {
+            float v[3];
+            load_corner(xyz, tri * 3 + c, v[0], v[1], v[2]);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float v = xyz[(tri * 3 + c) * 3 + k];
-                lo[k] = fminf(lo[k], v), hi[k] = fmaxf(hi[k], v);
-            }
+            for (int k = 0; k < 3; ++k) lo[k] = fminf(lo[k], v[k]), hi[k] = fmaxf(hi[k], v[k]);
+        }
     }
     block_frustum_cull(m_all, 0, views, lo, hi, wave_box, beyond);
     if (threadIdx.x < 64) {   // wavefront 0: lane s speaks for view s
@@ -685,10 +690,10 @@ __global__ __launch_bounds__(256) void nmi_mesh_cull_kernel(const float *__restr
     }
 }
 
-__global__ __launch_bounds__(256) void nmi_mesh_bin_pairs_kernel(const float *__restrict__ xyz, const float *__restrict__ uv, long long ntri,
-                                                                 const float *__restrict__ mvps, int width, int height, BinGrid g,
-                                                                 ClipItem *__restrict__ clipq, unsigned long long *__restrict__ clip_state,
-                                                                 unsigned long long clip_cap, WarpFuse wf, const uint32_t *__restrict__ pairs,
+__global__ __launch_bounds__(256) void nmi_mesh_bin_pairs_kernel(const float *__restrict__ xyz, long long ntri, const float *__restrict__ mvps,
+                                                                 int width, int height, BinGrid g, ClipItem *__restrict__ clipq,
+                                                                 unsigned long long *__restrict__ clip_state, unsigned long long clip_cap,
+                                                                 WarpFuse wf, const uint32_t *__restrict__ pairs,
                                                                  const uint32_t *__restrict__ pair_state)
 {
     const unsigned workers = gridDim.x - (unsigned)wf.blocks;   // (workers first in the launch: their round trips start at once)
@@ -703,27 +708,26 @@ __global__ __launch_bounds__(256) void nmi_mesh_bin_pairs_kernel(const float *__
         const int s = (int)(pair % (uint32_t)kMaxViewsPerLaunch);
         const long long tri = (long long)(pair / (uint32_t)kMaxViewsPerLaunch) * 256ll + threadIdx.x;
         const bool valid = tri < ntri;
-        float px[3] = {0, 0, 0}, py[3] = {0, 0, 0}, pz[3] = {0, 0, 0}, tu[3], tv[3];
-        if (valid) load_tri(xyz, uv, tri, px, py, pz, tu, tv);
+        float px[3] = {0, 0, 0}, py[3] = {0, 0, 0}, pz[3] = {0, 0, 0};
+        if (valid) load_tri(xyz, tri, px, py, pz);
         bin_one_view(mvps + (size_t)s * 16, s, tri, valid, px, py, pz, width, height, g, clipq, clip_state, clip_cap);   // (uniform address: the matrix in scalar registers)
     }
 }
 
 // One (triangle, view) that crosses the near plane: clip, then each of the 1 or 2 pieces goes the way of any triangle.
-__device__ __forceinline__ void clip_and_bin(const float *__restrict__ xyz, const float *__restrict__ uv, long long tri, int s,
-                                             const float *__restrict__ m, int width, int height, const BinGrid &g)
+__device__ __forceinline__ void clip_and_bin(const float *__restrict__ xyz, long long tri, int s, const float *__restrict__ m, int width,
+                                             int height, const BinGrid &g)
 {
-    float px[3], py[3], pz[3], tu[3], tv[3], cx[3], cy[3], cz[3], cw[3], d[3];
-    load_tri(xyz, uv, tri, px, py, pz, tu, tv);
+    float px[3], py[3], pz[3], cx[3], cy[3], cz[3], cw[3], d[3];
+    load_tri(xyz, tri, px, py, pz);
     const int n_in = tri_clip_coords(m, px, py, pz, cx, cy, cz, cw, d);
     if (n_in == 0 || n_in == 3) return;  // not this kernel's (the rescan visits every triangle)
     ClipPoly P;
-    tri_clip_poly(cx, cy, cz, cw, d, tu, tv, P);
+    tri_clip_poly(cx, cy, cz, cw, d, P);
     const int tiles = g.tiles_x * g.tiles_y;
     for (int sub = 0; sub + 3 <= P.n; ++sub) {
         TriView t;
-        float su[3], sv[3];
-        poly_corners(P, sub, cx, cy, cz, cw, su, sv);
+        poly_corners(P, sub, cx, cy, cz, cw);
         if (!tri_setup(cx, cy, cz, cw, width, height, t)) continue;
         const unsigned long long id = ((unsigned long long)tri << 1) | (unsigned long long)sub;
         const int bw = t.x_hi - t.x_lo + 1, bh = t.y_hi - t.y_lo + 1;
@@ -744,10 +748,10 @@ __device__ __forceinline__ void clip_and_bin(const float *__restrict__ xyz, cons
     }
 }
 
-__global__ __launch_bounds__(256) void nmi_mesh_clip_kernel(const float *__restrict__ xyz, const float *__restrict__ uv, long long ntri,
-                                                            const float *__restrict__ mvps, int views, int width, int height, BinGrid g,
-                                                            const ClipItem *__restrict__ clipq, unsigned long long *__restrict__ clip_state,
-                                                            unsigned long long clip_cap, uint32_t *__restrict__ pair_state)
+__global__ __launch_bounds__(256) void nmi_mesh_clip_kernel(const float *__restrict__ xyz, long long ntri, const float *__restrict__ mvps, int views,
+                                                            int width, int height, BinGrid g, const ClipItem *__restrict__ clipq,
+                                                            unsigned long long *__restrict__ clip_state, unsigned long long clip_cap,
+                                                            uint32_t *__restrict__ pair_state)
 {
     __shared__ unsigned long long claimed_s;
     if (pair_state && blockIdx.x == 0 && threadIdx.x == 0) pair_state[0] = 0u;   // the binning pass that read the list has ended: clean for the next render
@@ -763,14 +767,14 @@ __global__ __launch_bounds__(256) void nmi_mesh_clip_kernel(const float *__restr
     const unsigned long long gid = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x, stride = (unsigned long long)gridDim.x * blockDim.x;
     if (claimed <= clip_cap) {
         for (unsigned long long i = gid; i < claimed; i += stride)
-            clip_and_bin(xyz, uv, (long long)clipq[i].tri, (int)clipq[i].view, mvps + clipq[i].view * 16, width, height, g);
+            clip_and_bin(xyz, (long long)clipq[i].tri, (int)clipq[i].view, mvps + clipq[i].view * 16, width, height, g);
     } else {
         // more crossing triangles than the queue holds: look at every (triangle, view) again
         const unsigned long long all = (unsigned long long)ntri * (unsigned long long)views;
         for (unsigned long long i = gid; i < all; i += stride) {
             const long long tri = (long long)(i / (unsigned long long)views);
             const int s = (int)(i % (unsigned long long)views);
-            clip_and_bin(xyz, uv, tri, s, mvps + s * 16, width, height, g);
+            clip_and_bin(xyz, tri, s, mvps + s * 16, width, height, g);
         }
     }
 }
@@ -785,24 +789,83 @@ enum : int {
     R_BOX_W = 12,   // the box's width | its pixels << 16
     R_FIRST = 13,   // box pixels of the records before this one
     R_ID = 14,      // triangle << 1 | piece
-#ifdef NMI_MESH_COLOR
-    R_PLANES = 16,  // xr, yr, s0, sx, sy, q0, qx, qy: one attribute plane
-    R_WORDS = 24,
-#else
-    R_PLANES = 16,  // xr, yr, s0, r0, sx, rx, sy, ry, q0, qx, qy
-    R_WORDS = 28,
-#endif
+    R_PLANES = 16,  // the attribute planes, as the policy lays them out; Attr::kRecordWords words in all
 };
 
-template <int BINMAX>
+// What the last stage does with a mesh's attributes: mesh_tile_body's policy.  Textured: `attr` is uv [3T][2], two attribute
+// planes (S = u/w, R = v/w), the texture is a kernel argument and its level table in LDS.
+struct TexturedAttr {
+    using Args = MeshTexture;      // what the kernel takes besides the grid
+    struct Lds { TexLevel tex[16]; };   // what the tile keeps in LDS besides keys and records
+    using Uniform = TexLevel;      // what every lane holds for the shading loop: level 0
+    static constexpr int kRecordWords = 28;   // planes: xr, yr, s0, r0, sx, rx, sy, ry, q0, qx, qy
+
+    static __device__ __forceinline__ void load_corner(const float *__restrict__ uv, long long corner, float &u, float &v)
+    {
+        u = uv[corner * 2], v = uv[corner * 2 + 1];
+    }
+    static __device__ __forceinline__ void planes_to_lds(const Planes &P, uint32_t *r)
+    {
+        float *f = reinterpret_cast<float *>(r);
+        f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.sr0.y, f[R_PLANES + 4] = P.srx.x;
+        f[R_PLANES + 5] = P.srx.y, f[R_PLANES + 6] = P.sry.x, f[R_PLANES + 7] = P.sry.y, f[R_PLANES + 8] = P.q0, f[R_PLANES + 9] = P.qx;
+        f[R_PLANES + 10] = P.qy;
+    }
+    static __device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
+    {
+        const float *f = reinterpret_cast<const float *>(r + R_PLANES);
+        P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], f[3]}, P.srx = v2f{f[4], f[5]}, P.sry = v2f{f[6], f[7]}, P.q0 = f[8], P.qx = f[9], P.qy = f[10];
+    }
+    static __device__ __forceinline__ void fill_lds(const MeshTexture &tex, int tid, Lds &lds)   // lanes 64..: the level table
+    {
+        if (tid >= 64 && tid < 64 + tex.levels) lds.tex[tid - 64] = tex_level(tex, tid - 64);
+    }
+    static __device__ __forceinline__ TexLevel uniform(const MeshTexture &tex) { return tex_level(tex, 0); }   // (kernel arguments: scalar registers)
+    static __device__ __forceinline__ uint32_t shade(const Planes &P, const MeshTexture &tex, const TexLevel &base_level, const Lds &lds, float fxp,
+                                                     float fyp)
+    {
+        return shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, fxp, fyp);
+    }
+};
+
+// Coloured: `attr` is red [3T].  The colour takes u's way through the clipper and the planes (v is 0, its arithmetic dead code that
+// the compiler drops), the record has one attribute plane, there is no texture.
+struct ColoredAttr {
+    struct Args {};
+    struct Lds {};
+    struct Uniform {};
+    static constexpr int kRecordWords = 24;   // planes: xr, yr, s0, sx, sy, q0, qx, qy
+
+    static __device__ __forceinline__ void load_corner(const float *__restrict__ red, long long corner, float &u, float &v)
+    {
+        u = red[corner], v = 0.0f;
+    }
+    static __device__ __forceinline__ void planes_to_lds(const Planes &P, uint32_t *r)
+    {
+        float *f = reinterpret_cast<float *>(r);
+        f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.srx.x, f[R_PLANES + 4] = P.sry.x;
+        f[R_PLANES + 5] = P.q0, f[R_PLANES + 6] = P.qx, f[R_PLANES + 7] = P.qy;
+    }
+    static __device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
+    {
+        const float *f = reinterpret_cast<const float *>(r + R_PLANES);
+        P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], 0.0f}, P.srx = v2f{f[3], 0.0f}, P.sry = v2f{f[4], 0.0f}, P.q0 = f[5], P.qx = f[6], P.qy = f[7];
+    }
+    static __device__ __forceinline__ void fill_lds(const Args &, int, Lds &) {}
+    static __device__ __forceinline__ Uniform uniform(const Args &) { return {}; }
+    static __device__ __forceinline__ uint32_t shade(const Planes &P, const Args &, const Uniform &, const Lds &, float fxp, float fyp)
+    {
+        return shade_color(P, fxp, fyp);
+    }
+};
+
+template <typename Attr, int BINMAX>
 struct TileLds {
     unsigned long long keys[kTile * kTile];
-    uint32_t rec[BINMAX][R_WORDS];
+    uint32_t rec[BINMAX][Attr::kRecordWords];
     uint32_t wave_sum[kTileThreads / 64];
     uint32_t hdr[4];
-#ifndef NMI_MESH_COLOR
-    TexLevel tex[16];
-#endif
+    [[no_unique_address]] typename Attr::Lds attr;
 };
 
 // Where the key of tile pixel (x, y) lives: row y, rotated by 8 keys per row (a multiple of 4: a lane's four neighbouring
@@ -811,48 +874,16 @@ constexpr int kVisChunk = 8;  // steps (pixel pairs) of one record a lane takes 
 
 __device__ __forceinline__ int key_index(int x, int y) { return y * kTile + ((x + 8 * y) & (kTile - 1)); }
 
-__device__ __forceinline__ void planes_from_lds(const uint32_t *r, Planes &P)
-{
-    const float *f = reinterpret_cast<const float *>(r + R_PLANES);
-#ifdef NMI_MESH_COLOR
-    P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], 0.0f}, P.srx = v2f{f[3], 0.0f}, P.sry = v2f{f[4], 0.0f}, P.q0 = f[5], P.qx = f[6], P.qy = f[7];
-#else
-    P.xr = f[0], P.yr = f[1], P.sr0 = v2f{f[2], f[3]}, P.srx = v2f{f[4], f[5]}, P.sry = v2f{f[6], f[7]}, P.q0 = f[8], P.qx = f[9], P.qy = f[10];
-#endif
-}
-
-__device__ __forceinline__ void planes_to_lds(const Planes &P, uint32_t *r)
-{
-    float *f = reinterpret_cast<float *>(r);
-#ifdef NMI_MESH_COLOR
-    f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.srx.x, f[R_PLANES + 4] = P.sry.x;
-    f[R_PLANES + 5] = P.q0, f[R_PLANES + 6] = P.qx, f[R_PLANES + 7] = P.qy;
-#else
-    f[R_PLANES + 0] = P.xr, f[R_PLANES + 1] = P.yr, f[R_PLANES + 2] = P.sr0.x, f[R_PLANES + 3] = P.sr0.y, f[R_PLANES + 4] = P.srx.x;
-    f[R_PLANES + 5] = P.srx.y, f[R_PLANES + 6] = P.sry.x, f[R_PLANES + 7] = P.sry.y, f[R_PLANES + 8] = P.q0, f[R_PLANES + 9] = P.qx;
-    f[R_PLANES + 10] = P.qy;
-#endif
-}
-
-// What the last stage takes besides a fragment's planes: the texture (a kernel argument, its level table in LDS) -- or nothing.
-#ifdef NMI_MESH_COLOR
-#define MESH_TEX_PARAM
-#define MESH_SHADE(P, fxp, fyp) shade_color(P, fxp, fyp)
-#else
-#define MESH_TEX_PARAM MeshTexture tex,
-#define MESH_SHADE(P, fxp, fyp) shade_pixel(P, tex.luma, base_level, lds.tex, tex.levels, fxp, fyp)
-#endif
-
 }  // namespace
 
 // COVER (nmi_render_mesh_masked): also writes cover[s][y][x] = 1 where a fragment won the pixel (its grey comes from a triangle,
 // from the LDS records or through the memory buffer), 0 where it kept the clear colour; same layout as `out`.
-template <int BINMAX, bool COVER = false>
-__device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, const float *__restrict__ uv,
-                                                                     const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                     int height, MESH_TEX_PARAM BinGrid g, uint8_t *__restrict__ cover = nullptr)
+template <typename Attr, int BINMAX, bool COVER = false>
+__device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, const float *__restrict__ attr, const float *__restrict__ mvps,
+                                               uint8_t *__restrict__ out, int width, int height, typename Attr::Args args, BinGrid g,
+                                               uint8_t *__restrict__ cover = nullptr)
 {
-    __shared__ TileLds<BINMAX> lds;
+    __shared__ TileLds<Attr, BINMAX> lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles = g.tiles_x * g.tiles_y;
     const int bin = blockIdx.x;
@@ -863,9 +894,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
     // dependent round trips with a barrier between them; the key clear runs under their latency.
     const uint32_t c_raw = g.state[2 * (size_t)bin], f_raw = g.state[2 * (size_t)bin + 1];
     const uint32_t my_id = tid < g.cap ? g.bins[(size_t)bin * g.stride + tid] : 0u;   // (meaningful for tid < n only)
-#ifndef NMI_MESH_COLOR
-    if (tid >= 64 && tid < 64 + tex.levels) tex_level_fill(tex, tid - 64, &lds.tex[tid - 64]);
-#endif
+    Attr::fill_lds(args, tid, lds.attr);
     for (int i = tid; i < kTile * kTile; i += kTileThreads) lds.keys[i] = kEmptyKey;
     const int n = (int)(c_raw < (uint32_t)g.cap ? c_raw : (uint32_t)g.cap);
     const bool from_memory = f_raw != 0u;
@@ -905,7 +934,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
             uint32_t *r = lds.rec[tid];
             TriView t;
             float su[3], sv[3];
-            bool ok = setup_piece(xyz, uv, (long long)(id >> 1), (int)(id & 1u), mvps + s * 16, width, height, t, su, sv);
+            bool ok = setup_piece<Attr>(xyz, attr, (long long)(id >> 1), (int)(id & 1u), mvps + s * 16, width, height, t, su, sv);
             int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
             if (ok) {
                 bx0 = max(t.x_lo, X0), bx1 = min(t.x_hi, X0 + kTile - 1), by0 = max(t.y_lo, Y0), by1 = min(t.y_hi, Y0 + kTile - 1);
@@ -918,7 +947,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
 #pragma unroll
                 for (int k = 0; k < 3; ++k) f[R_XW + k] = t.xw[k], f[R_YW + k] = t.yw[k], f[R_ZW + k] = t.zw[k];
                 f[R_INV_AREA] = t.inv_area;
-                planes_to_lds(P, r);
+                Attr::planes_to_lds(P, r);
                 r[R_OWN] = (t.own[0] ? 1u : 0u) | (t.own[1] ? 2u : 0u) | (t.own[2] ? 4u : 0u);
                 r[R_BOX] = (uint32_t)bx0 | ((uint32_t)by0 << 16);
                 const uint32_t nsteps = (uint32_t)(((bx1 - bx0 + 2) >> 1) * (by1 - by0 + 1));  // steps of the visibility walk: pairs of pixels in a row; at most 2048
@@ -1034,10 +1063,7 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
         if (tid == 0) g.state[2 * (size_t)bin + 1] = 0u;
     }
     if (!col_ok) return;
-#ifndef NMI_MESH_COLOR
-    TexLevel base_level;
-    tex_level_fill(tex, 0, &base_level);   // from the kernel's arguments: scalar registers
-#endif
+    const typename Attr::Uniform uni = Attr::uniform(args);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const int y = oy + 32 * half;
@@ -1076,10 +1102,10 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 float su[3], sv[3];
                 const unsigned long long id = (key >> 9) & 0x7FFFFFFFull;
                 uint32_t grey = 255u;
-                if (setup_piece(xyz, uv, (long long)(id >> 1), (int)(id & 1ull), mvps + s * 16, width, height, t, su, sv)) {  // (true: it produced this key)
+                if (setup_piece<Attr>(xyz, attr, (long long)(id >> 1), (int)(id & 1ull), mvps + s * 16, width, height, t, su, sv)) {  // (true: it produced this key)
                     Planes P;
                     tri_planes(t, su, sv, P);
-                    grey = MESH_SHADE(P, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                    grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
                     if (COVER) covered |= 1u << (8 * k);
                 }
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
@@ -1092,8 +1118,8 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
             const unsigned long long key = keys[k];
             if ((key != kEmptyKey) & (ox + k < width) & !(g.dbg & 1)) {
                 Planes P;
-                planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
-                const uint32_t grey = MESH_SHADE(P, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                Attr::planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
+                const uint32_t grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
                 packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
                 if (COVER) covered |= 1u << (8 * k);
             }
@@ -1113,28 +1139,6 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
     }
 }
 
-#ifdef NMI_MESH_COLOR
-// The coloured tile kernels.  One build, 255 bin entries per tile.  The 24-word record makes it 56 KB of LDS: two workgroups per
-// CU, as the textured one (a third needs 53.3 KB or less, i.e. 21 words a record; the visibility fields and the two planes are
-// 23).  A 127-entry build (44 KB) would fit three, but the body needs 86 registers (88 with coverage) and three workgroups allow
-// 80: under that cap it spills 28 / 52 bytes per lane, and uncapped it is two workgroups again -- so there is none
-// (profiles/mesh_color/NOTES.md).
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
-                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                           int height, BinGrid g)
-{
-    mesh_tile_body<kBinMax>(xyz, red, mvps, out, width, height, g);
-}
-
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
-                                                                                 const float *__restrict__ mvps, uint8_t *__restrict__ out,
-                                                                                 int width, int height, BinGrid g, uint8_t *__restrict__ cover)
-{
-    mesh_tile_body<kBinMax, true>(xyz, red, mvps, out, width, height, g, cover);
-}
-
-void mesh_geometry(int S, int width, int height, int *tiles_x, int *tiles_y, int *stride);   // (defined by nmi_mesh.hip's own build)
-#else
 // Two builds of the tile kernel.  The usual one holds 255 bin entries per tile (62 KB of LDS: two workgroups per CU).  For a mesh
 // whose tiles cannot fill that -- launch_render_mesh decides from the triangle count -- the small one holds 127 (48 KB) and is
 // held to 80 registers, so that THREE workgroups share a CU: the kernel spends half its wave-cycles waiting (set-up, barriers,
@@ -1144,7 +1148,7 @@ __global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_kernel(const float
                                                                      const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
                                                                      int height, MeshTexture tex, BinGrid g)
 {
-    mesh_tile_body<kBinMax>(xyz, uv, mvps, out, width, height, tex, g);
+    mesh_tile_body<TexturedAttr, kBinMax>(xyz, uv, mvps, out, width, height, tex, g);
 }
 
 constexpr int kBinSmall = 128;
@@ -1153,7 +1157,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6,
     const float *__restrict__ xyz, const float *__restrict__ uv, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width, int height,
     MeshTexture tex, BinGrid g)
 {
-    mesh_tile_body<kBinSmall>(xyz, uv, mvps, out, width, height, tex, g);
+    mesh_tile_body<TexturedAttr, kBinSmall>(xyz, uv, mvps, out, width, height, tex, g);
 }
 
 // The coverage forms of the two builds (nmi_render_mesh_masked): the same bodies, plus the mask stack.
@@ -1161,16 +1165,34 @@ __global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_cover_kernel(const
                                                                            const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
                                                                            int height, MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
 {
-    mesh_tile_body<kBinMax, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
+    mesh_tile_body<TexturedAttr, kBinMax, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
 }
 
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void nmi_mesh_tile_small_cover_kernel(
     const float *__restrict__ xyz, const float *__restrict__ uv, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width, int height,
     MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
 {
-    mesh_tile_body<kBinSmall, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
+    mesh_tile_body<TexturedAttr, kBinSmall, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
 }
 
+// The coloured tile kernels.  One build, 255 bin entries per tile.  The 24-word record makes it 56 KB of LDS: two workgroups per
+// CU, as the textured one (a third needs 53.3 KB or less, i.e. 21 words a record; the visibility fields and the two planes are
+// 23).  A 127-entry build (44 KB) would fit three, but the body needs 86 registers (88 with coverage) and three workgroups allow
+// 80: under that cap it spills 28 / 52 bytes per lane, and uncapped it is two workgroups again -- so there is none
+// (profiles/mesh_color/NOTES.md).
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
+                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
+                                                                           int height, BinGrid g)
+{
+    mesh_tile_body<ColoredAttr, kBinMax>(xyz, red, mvps, out, width, height, {}, g);
+}
+
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
+                                                                                 const float *__restrict__ mvps, uint8_t *__restrict__ out,
+                                                                                 int width, int height, BinGrid g, uint8_t *__restrict__ cover)
+{
+    mesh_tile_body<ColoredAttr, kBinMax, true>(xyz, red, mvps, out, width, height, {}, g, cover);
+}
 
 __global__ __launch_bounds__(256) void nmi_mesh_clear_kernel(unsigned long long *zbuf, size_t n, uint32_t *state, size_t n_state,
                                                              unsigned long long *clip_state)
@@ -1218,19 +1240,10 @@ hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hi
 }
 
 size_t mesh_pairs_entries(long long ntri) { return (size_t)((ntri + 255) / 256) * kMaxViewsPerLaunch; }
-#endif  // NMI_MESH_COLOR
 
-#ifdef NMI_MESH_COLOR
-hipError_t launch_render_mesh_colored(const float *xyz, const float *uv /* red [3T] */, long long ntri, const float *mvps, int S, const MeshWork &w,
-                                      int layout_views, int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height,
-                                      hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn,
-                                      uint8_t *cover)
-#else
-hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri, const float *luma, int levels, const int *lw,
-                              const int *lh, const long long *loff, const float *mvps, int S, const MeshWork &w, int layout_views,
-                              int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
-                              const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover)
-#endif
+hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const float *mvps, int S, const MeshWork &w,
+                              int layout_views, int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height,
+                              hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover)
 {
     if (S > layout_views) return hipErrorInvalidValue;
     WarpFuse wf{warp_frame, warp_coeffs, warp_out, 0};
@@ -1240,13 +1253,12 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
     }
     if (ntri >= (1ll << 30) || width > 65535 || height > 65535) return hipErrorInvalidValue;  // triangle and piece share 31 bits of a key
     if (!w.zbuf || !w.bins || !w.state || !w.clip_queue || !w.clip_state) return hipErrorInvalidValue;
-#ifndef NMI_MESH_COLOR
-    MeshTexture tex{};
-    tex.luma = luma;
-    tex.levels = levels;
-    for (int l = 0; l < levels && l < 16; ++l)
-        tex.w[l] = lw[l], tex.h[l] = lh[l], tex.off[l] = loff[l], tex.inv_w[l] = 1.0f / (float)lw[l], tex.inv_h[l] = 1.0f / (float)lh[l];
-#endif
+    MeshTexture tex{};   // (a coloured mesh has no levels)
+    tex.luma = shading.luma, tex.levels = shading.levels;
+    for (int l = 0; l < tex.levels && l < 16; ++l) {
+        tex.w[l] = shading.lw[l], tex.h[l] = shading.lh[l], tex.off[l] = shading.loff[l];
+        tex.inv_w[l] = 1.0f / (float)tex.w[l], tex.inv_h[l] = 1.0f / (float)tex.h[l];
+    }
     BinGrid g{};
     static const int dbg = getenv("NMI_MESH_DBG") ? atoi(getenv("NMI_MESH_DBG")) : 0;
     g.dbg = dbg;
@@ -1254,13 +1266,12 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
     g.cap = g.stride - 1 < bin_cap_limit ? g.stride - 1 : bin_cap_limit;
     if (g.cap < 0) g.cap = 0;
     const int tiles = g.tiles_x * g.tiles_y;
-#ifndef NMI_MESH_COLOR
     // The small tile kernel (127 entries per tile, three workgroups per CU) for meshes that could not fill more even if every
-    // triangle were in view and touched two tiles; a fuller bin than its capacity takes the per-lane path as always.
+    // triangle were in view and touched two tiles; a fuller bin than its capacity takes the per-lane path as always.  Textured only:
+    // there is no small coloured build (see nmi_mesh_tile_color_kernel).
     static const bool no_small = getenv("NMI_MESH_NO_SMALL_TILES") != nullptr;   // measurement switch
-    const bool small_tiles = !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
+    const bool small_tiles = shading.textured && !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
     if (small_tiles && g.cap > kBinSmall - 1) g.cap = kBinSmall - 1;
-#endif
     const unsigned long long clip_cap = w.clip_cap < clip_cap_limit ? w.clip_cap : clip_cap_limit;
     for (int s0 = 0; s0 < S; s0 += kMaxViewsPerLaunch) {
         const int views = S - s0 < kMaxViewsPerLaunch ? S - s0 : kMaxViewsPerLaunch;
@@ -1284,41 +1295,36 @@ hipError_t launch_render_mesh(const float *xyz, const float *uv, long long ntri,
                 if (workers > nblocks * views) workers = nblocks * views;
                 hipLaunchKernelGGL(nmi_mesh_cull_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream, xyz, ntri, mvps + (size_t)s0 * 16, views, w.pairs,
                                    w.pair_state);
-                hipLaunchKernelGGL(nmi_mesh_bin_pairs_kernel, dim3((unsigned)(workers + wf.blocks)), dim3(256), 0, stream, xyz, uv, ntri,
+                hipLaunchKernelGGL(nmi_mesh_bin_pairs_kernel, dim3((unsigned)(workers + wf.blocks)), dim3(256), 0, stream, xyz, ntri,
                                    mvps + (size_t)s0 * 16, width, height, g, clipq, w.clip_state, clip_cap, wf, w.pairs, w.pair_state);
             } else {
                 // shares of the views: aim at ~half a million lanes
                 static const long long lanes_wanted = getenv("NMI_MESH_LANES") ? atoll(getenv("NMI_MESH_LANES")) : 500000;
                 long long shares = (lanes_wanted + ntri - 1) / ntri;
                 shares = shares < 1 ? 1 : (shares > views ? views : shares);
-                hipLaunchKernelGGL(nmi_mesh_bin_kernel, dim3((unsigned)(wf.blocks + ((ntri + 255) / 256) * shares)), dim3(256), 0, stream, xyz, uv, ntri,
+                hipLaunchKernelGGL(nmi_mesh_bin_kernel, dim3((unsigned)(wf.blocks + ((ntri + 255) / 256) * shares)), dim3(256), 0, stream, xyz, ntri,
                                    mvps + (size_t)s0 * 16, views, width, height, g, clipq, w.clip_state, clip_cap, (int)shares, wf);
             }
             // (crossing triangles are few: an empty pass should cost little)
-            hipLaunchKernelGGL(nmi_mesh_clip_kernel, dim3(64), dim3(256), 0, stream, xyz, uv, ntri, mvps + (size_t)s0 * 16, views, width,
-                               height, g, clipq, w.clip_state, clip_cap, w.pair_state);
+            hipLaunchKernelGGL(nmi_mesh_clip_kernel, dim3(64), dim3(256), 0, stream, xyz, ntri, mvps + (size_t)s0 * 16, views, width, height, g,
+                               clipq, w.clip_state, clip_cap, w.pair_state);
         }
-#ifdef NMI_MESH_COLOR
-        if (cover)
-            hipLaunchKernelGGL(nmi_mesh_tile_color_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
-                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, g, cover + (size_t)s0 * width * height);
-        else
-            hipLaunchKernelGGL(nmi_mesh_tile_color_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
-                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, g);
-#else
-        if (cover && small_tiles)
-            hipLaunchKernelGGL(nmi_mesh_tile_small_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
-                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g, cover + (size_t)s0 * width * height);
+        // the last stage: the tile kernel of the mesh's kind
+        const dim3 grid((unsigned)(views * tiles)), block(kTileThreads);
+        const float *m = mvps + (size_t)s0 * 16;
+        uint8_t *o = out + (size_t)s0 * width * height, *c = cover ? cover + (size_t)s0 * width * height : nullptr;
+        if (!shading.textured && cover)
+            hipLaunchKernelGGL(nmi_mesh_tile_color_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g, c);
+        else if (!shading.textured)
+            hipLaunchKernelGGL(nmi_mesh_tile_color_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g);
+        else if (cover && small_tiles)
+            hipLaunchKernelGGL(nmi_mesh_tile_small_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g, c);
         else if (cover)
-            hipLaunchKernelGGL(nmi_mesh_tile_cover_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
-                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g, cover + (size_t)s0 * width * height);
+            hipLaunchKernelGGL(nmi_mesh_tile_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g, c);
         else if (small_tiles)
-            hipLaunchKernelGGL(nmi_mesh_tile_small_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv,
-                               mvps + (size_t)s0 * 16, out + (size_t)s0 * width * height, width, height, tex, g);
+            hipLaunchKernelGGL(nmi_mesh_tile_small_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g);
         else
-            hipLaunchKernelGGL(nmi_mesh_tile_kernel, dim3((unsigned)(views * tiles)), dim3(kTileThreads), 0, stream, xyz, uv, mvps + (size_t)s0 * 16,
-                               out + (size_t)s0 * width * height, width, height, tex, g);
-#endif
+            hipLaunchKernelGGL(nmi_mesh_tile_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g);
     }
     return hipGetLastError();
 }

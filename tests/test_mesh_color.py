@@ -303,9 +303,9 @@ def test_gpu_colored_level_families(nmi, family, shape):
 
 @pytest.mark.gpu
 def test_gpu_colored_pairs_pass_vs_twin(nmi):
-    """The two-kernel binning pass of the coloured build (nmi_mesh_cull_color_kernel + nmi_mesh_bin_pairs_color_kernel): the 4,800-
-    triangle tessellation under 64 views at 160 x 120, as test_mesh_edges.test_gpu_mesh_pairs_pass_vs_twin builds it, with colours.
-    launch_render_mesh_colored takes that pass when nblocks * views > 4 * compute units (asserted for the device at hand).
+    """The two-kernel binning pass (nmi_mesh_cull_kernel + nmi_mesh_bin_pairs_kernel, which serve both kinds of mesh) in front of the
+    coloured tile kernel: the 4,800-triangle tessellation under 64 views at 160 x 120, as test_mesh_edges.test_gpu_mesh_pairs_pass_vs_twin builds it, with colours.
+    launch_render_mesh takes that pass when nblocks * views > 4 * compute units (asserted for the device at hand).
     Every byte of all 64 views and their masks is checked: every eighth view against the twin (the twin of all 64 is half a minute
     of Python, which that test already spends on the same geometry), and all 64 against the same view rendered alone, S = 1 --
     19 pairs, the one-kernel binning pass, which test_gpu_render_mesh_colored_families holds to the twin.  What the pairs pass can

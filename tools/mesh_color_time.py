@@ -8,7 +8,7 @@ The replays are cut into --reps repetitions; per repetition the median, over the
 (min .. max): the spread of the textured level is the yardstick for "not slower".
 
 Per-kernel times: run it under  rocprofv3 --kernel-trace --stats -- python tools/mesh_color_time.py --iters 300
-(the coloured build's kernels carry _color in their names).
+(the coloured tile kernels carry _color in their names; the passes in front of them are the textured mesh's).
 """
 import argparse
 import json
