@@ -213,7 +213,7 @@ int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward
  * nmi_search_grid_masked: nmi_search_grid with the masks; len_w is counted on the device from warp_masks (the source of
  * truth: the masks need not come from nmi_warp_stack_masked).  A NULL warp_masks is NMI_ERR_INVALID_ARGUMENT.  Blocking
  * exactly like nmi_search_grid.  NMI_OPT_SPLIT* choose the kernel, never the result: mid-size grids take the masked
- * pixel-range kernel where choose_pix's rules for nmi_search_grid pick pixel ranges (NMI_OPT_SPLIT 0 keeps the masked grid
+ * pixel-range kernel where plan_search's rules for nmi_search_grid pick pixel ranges (NMI_OPT_SPLIT 0 keeps the masked grid
  * kernel, NMI_OPT_SPLIT 1 + NMI_OPT_SPLIT_PIXELS P forces P ranges wherever they fit); NMI_OPT_CONTENT_PATH does not apply.
  *
  * nmi_last_mask_counts: len_w of the latest masked search's first n warps (n <= its Wn) to host memory.  Blocking.

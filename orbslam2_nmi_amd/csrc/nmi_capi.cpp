@@ -73,63 +73,27 @@ int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order)
     return NMI_OK;
 }
 
-// How the split kernel should cut each candidate of a launch of `total` candidates on `cap` workgroups: *parts row
-// parts and *pix_parts pixel ranges.  *parts = 0: use the one-workgroup-per-candidate kernel.  Automatic choice (256
-// CUs): up to 8 candidates 8 x 4, up to 16: 8 x 2, up to 32: 4 x 2, up to 64: 4 x 1 -- a part's time is its pixel stream
-// (>= 12 us for a whole 640x480 pair whatever the number of row parts), so pixel ranges come first and 2 row parts,
-// measured no faster than none, are available on request only.
-static void choose_split(const nmi_ctx *ctx, int64_t total, int cap, int *parts, int *pix_parts)
+nmi::PlanInputs plan_inputs(const nmi_ctx *ctx, nmi::SearchForm form, int64_t total, const nmi::GridArgs &a)
 {
-    *parts = 0;
-    *pix_parts = 1;
-    if (cap > ctx->compute_units) cap = ctx->compute_units;  // all workgroups of a split launch must be resident at once
-    if (ctx->hist_variant != 3 || ctx->split_mode == 0 || ctx->split_mode == 1 || total <= 0 || total > cap) return;
-    auto fits = [&](int k, int p) { return nmi::split_workgroups((int)total, k, p) <= cap; };
-    auto exists = [](int k, int p) { return p == 1 || (k == 8 && (p == 2 || p == 4)) || (k == 4 && p == 2); };
-    const int want_p = ctx->split_pixels;  // -1 automatic, 1 never, 2 / 4 that many when it fits
-    if (ctx->split_mode > 0) {
-        const int k = ctx->split_mode;
-        if (!fits(k, 1)) return;
-        *parts = k;
-        if (want_p == 1) return;
-        for (int p = 4; p >= 2; p >>= 1)
-            if ((want_p == -1 || want_p == p) && exists(k, p) && fits(k, p)) {
-                *pix_parts = p;
-                return;
-            }
-        return;
-    }
-    static const int order[][2] = {{8, 4}, {8, 2}, {4, 2}, {8, 1}, {4, 1}};
-    for (const auto &kp : order) {
-        if (kp[1] > 1 && want_p != -1 && want_p != kp[1]) continue;
-        if (fits(kp[0], kp[1])) {
-            *parts = kp[0];
-            *pix_parts = kp[1];
-            return;
-        }
-    }
-}
-
-// Pixel ranges per candidate for nmi_pix_kernel (nmi_pix_kernel.hip), 0 = another kernel.  The owner of a candidate adds
-// its P - 1 helpers' histograms to its own and waits for the slowest of them, so P grows only while the histogram phase
-// (21 us / P at 640x480) shrinks faster: automatic choice 3 up to 85 candidates, 2 up to 128 (256 CUs; measured, with 4 and
-// 5: profiles/r04_a/small_grid_time.txt); smaller grids keep the row-split forms, larger ones have no CU to spare.  NMI_OPT_SPLIT 1 + NMI_OPT_SPLIT_PIXELS P forces P wherever it fits.
-int choose_pix(const nmi_ctx *ctx, const nmi::GridArgs &a, int64_t total, int cap)
-{
-    if (cap > ctx->compute_units) cap = ctx->compute_units;  // (an owner that waits for a CU starts a second round)
-    if (ctx->hist_variant != 3 || a.width < 32 || (ctx->shift != 0 && !ctx->params.use_bg) || ctx->pair_renders || total <= 0) return 0;
-    if ((ctx->phase_mask & ~512) != 3 || (a.dbg_stamps != nullptr && ctx->split_mode != 1)) return 0;
-    if (ctx->split_mode == 1) {
-        const int p = ctx->split_pixels;
-        return (p >= 2 && p <= nmi::pix_max_ranges() && total * p <= cap) ? p : 0;
-    }
-    if (ctx->split_mode != -1 || ctx->split_pixels != -1 || total * 2 > cap) return 0;
-    const int p = (int)(cap / total);
-    // Frames whose rows are not whole aligned 16-byte chunks (width % 16 != 0, unaligned stacks): the row-split kernel would
-    // read them byte by byte, this one has the unaligned-row form -- so small grids and single pairs come here too, with more ranges
-    if (!a.vec_ok) return p > nmi::pix_max_ranges() ? nmi::pix_max_ranges() : p;
-    if (total <= 32) return 0;
-    return p > 3 ? 3 : p;
+    nmi::PlanInputs in;
+    in.compute_units = ctx->compute_units;
+    in.workgroups = ctx->workgroups;
+    in.hist_variant = ctx->hist_variant;
+    in.split_mode = ctx->split_mode;
+    in.split_pixels = ctx->split_pixels;
+    in.shift = ctx->shift;
+    in.use_bg = ctx->params.use_bg != 0;
+    in.phase_mask = ctx->phase_mask;
+    in.content_path = ctx->content_path;
+    in.xcd_tiling = ctx->xcd_tiling != 0;
+    in.cooldown = ctx->split_cooldown > 0;
+    in.few_hint = ctx->few_hint;
+    in.total = total;
+    in.width = a.width;
+    in.npix = ctx->npix;
+    in.vec_ok = a.vec_ok != 0;
+    in.form = form;
+    return in;
 }
 
 // the owner's share of a candidate's pixels: an equal one plus what it can add while its helpers' counters travel
@@ -139,7 +103,7 @@ double pix_owner_share(const nmi_ctx *ctx, int pix)
     return owner_px < ctx->npix ? owner_px / ctx->npix : 1.0;
 }
 
-int ensure_pix_timeouts(nmi_ctx *ctx)
+static int ensure_pix_timeouts(nmi_ctx *ctx)
 {
     if (ctx->d_pix_timeouts) return NMI_OK;
     NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pix_timeouts, sizeof(uint32_t)));
@@ -150,7 +114,7 @@ int ensure_pix_timeouts(nmi_ctx *ctx)
 // Epoch of the next split launch.  Slab granules carry all 32 bits, block granules the low 16: neither may be 0 (the
 // cleared state), and whenever the low 16 bits wrap the blocks are cleared so that no granule older than 65535 launches
 // can show the current tag (the slabs likewise when all 32 bits wrap).
-int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch)
+static int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch)
 {
     uint32_t e = ctx->split_epoch + 1;
     if ((e & 0xFFFFu) == 0) {
@@ -163,195 +127,75 @@ int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch)
     return NMI_OK;
 }
 
+int prepare_pix_handoff(nmi_ctx *ctx, uint32_t *epoch)
+{
+    if (*epoch == 0) {
+        const int rc = next_split_epoch(ctx, epoch);
+        if (rc != NMI_OK) return rc;
+    }
+    return ensure_pix_timeouts(ctx);
+}
+
+// A hand-off buffer of at least `bytes`, zero when allocated (tag / epoch 0 = never written); growing waits for the stream.  The
+// pixel-range kernels' blocks are a buffer of their own: the row-split kernel tags its granules with 16 bits in the top of an
+// 8-byte word, which a packed counter of the other kernel's layout can equal.
+static int ensure_zeroed(nmi_ctx *ctx, void **buf, size_t *have, size_t bytes)
+{
+    if (bytes <= *have) return NMI_OK;
+    if (*buf) {
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        NMI_HIP_TRY(ctx, hipFree(*buf));
+        *buf = nullptr;
+        *have = 0;
+    }
+    NMI_HIP_TRY(ctx, hipMalloc(buf, bytes));
+    NMI_HIP_TRY(ctx, hipMemsetAsync(*buf, 0, bytes, ctx->stream));
+    *have = bytes;
+    return NMI_OK;
+}
+
 static int ensure_slabs(nmi_ctx *ctx, int n)
 {
-    if (n <= ctx->slab_cap) return NMI_OK;
-    if (ctx->d_slabs) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        NMI_HIP_TRY(ctx, hipFree(ctx->d_slabs));
-        ctx->d_slabs = nullptr;
-        ctx->slab_cap = 0;
-    }
-    const int cap = n > 128 ? n : 128;
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_slabs, (size_t)cap * sizeof(nmi::SplitSlab)));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_slabs, 0, (size_t)cap * sizeof(nmi::SplitSlab), ctx->stream));  // epoch 0 = never written
-    ctx->slab_cap = cap;
-    return NMI_OK;
+    size_t have = (size_t)ctx->slab_cap * sizeof(nmi::SplitSlab);
+    const int rc = ensure_zeroed(ctx, (void **)&ctx->d_slabs, &have, (size_t)(n > 128 ? n : 128) * sizeof(nmi::SplitSlab));
+    ctx->slab_cap = (int)(have / sizeof(nmi::SplitSlab));
+    return rc;
 }
 
-// nmi_pix_kernel's hand-off blocks: a buffer of their own -- the row-split kernel tags its granules with 16 bits in the top of
-// an 8-byte word, which a packed counter of the other kernel's layout can equal.
-int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes)
+int prepare_search(nmi_ctx *ctx, const nmi::SearchPlan &plan, nmi::GridArgs &a)
 {
-    if (bytes <= ctx->pix_blocks_bytes) return NMI_OK;
-    if (ctx->d_pix_blocks) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        NMI_HIP_TRY(ctx, hipFree(ctx->d_pix_blocks));
-        ctx->d_pix_blocks = nullptr;
-        ctx->pix_blocks_bytes = 0;
-    }
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pix_blocks, bytes));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_blocks, 0, bytes, ctx->stream));  // tag 0 = never written
-    ctx->pix_blocks_bytes = bytes;
-    return NMI_OK;
-}
-
-static int ensure_blocks(nmi_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->blocks_bytes) return NMI_OK;
-    if (ctx->d_blocks) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        NMI_HIP_TRY(ctx, hipFree(ctx->d_blocks));
-        ctx->d_blocks = nullptr;
-        ctx->blocks_bytes = 0;
-    }
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_blocks, bytes));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_blocks, 0, bytes, ctx->stream));  // tag 0 = never written
-    ctx->blocks_bytes = bytes;
-    return NMI_OK;
-}
-
-// Enqueues the grid kernel (one launch, nothing else).  No synchronisation.
-int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total,
-                 const uint8_t *warp_stack, int Wn, float *d_ratings, unsigned long long *out_key, bool post,
-                 uint32_t *dbg_joint, uint32_t *dbg_h1, uint32_t *dbg_h2, float *dbg_sums, int w_offset, bool post_score)
-{
-    const nmi_params &p = ctx->params;
-    nmi::GridArgs a{};
-    a.render_stack = render_stack;
-    a.warp_stack = warp_stack;
-    a.S_local = S_local;
-    a.Wn = Wn;
-    a.s_offset = s_offset;
-    a.S_total = S_total;
-    a.w_offset = w_offset;
-    nmi::set_geometry(a, p.width, p.height, render_stack, warp_stack, p.render_bottom_up != 0);
-    if (ctx->pair_renders) {  // nmi_eval_pairs: per-pair pointers; the 16-byte path needs every one of them aligned
-        a.pair_renders = ctx->pair_renders;
-        a.pair_warps = ctx->pair_warps;
-        uintptr_t bits = 0;
-        for (int i = 0; i < S_local; ++i) bits |= (uintptr_t)ctx->pair_renders_host[i] | (uintptr_t)ctx->pair_warps_host[i];
-        if (bits % 16) nmi::set_geometry(a, p.width, p.height, (const void *)1, (const void *)1, p.render_bottom_up != 0);
-    }
-    a.shift = ctx->shift;
-    a.mode = p.mode;
-    a.table = ctx->table;
-    a.scratch = ctx->d_scratch;
-    a.order = nullptr;
-    a.ratings = d_ratings;
-    a.key = ctx->d_keys + ctx->slot;
-    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
-    a.out_key = out_key;
-    a.done = ctx->d_done;
-    // Only launches whose winner the host will poll for post to the mailbox (one bit of sequence is enough
-    // because those calls are blocking, hence strictly alternating).  The sequence numbers, the key-slot flip and the
-    // "posted" flag are committed only once the launch has been accepted: a failed launch leaves the protocol in step.
-    // does somebody look for a split-kernel timeout after this launch?  (blocking calls, nmi_eval_pairs, stream tickets, RCCL form)
-    const bool split_checked = post || post_score || ctx->allow_unchecked_split || ctx->pair_renders != nullptr;
-    post = post && ctx->result_path == 1;
-    post_score = post_score && ctx->result_path == 1;
-    a.mailbox = post ? ctx->mailbox : nullptr;
-    a.score_post = post_score ? ctx->score_mailbox : nullptr;
-    a.seq = post ? ctx->seq + 1 : (post_score ? ctx->pair_seq + 1 : 0);
-    a.dbg_joint = dbg_joint;
-    a.dbg_h1 = dbg_h1;
-    a.dbg_h2 = dbg_h2;
-    a.dbg_sums = dbg_sums;
-    a.hist_variant = ctx->hist_variant;
-    a.phase_mask = ctx->phase_mask;
-    a.dbg_stamps = ctx->dbg_stamps;
-
-    const int64_t total = (int64_t)S_local * Wn;
-    if (total == 0) {
-        // nothing to score: the winner is "none" (key 0); publish it the way the kernel would.  The key slot keeps its
-        // "zero on entry" state for the next launch (nothing ever writes a winner into a ping-pong slot from outside:
-        // the RCCL form reduces into ctx->d_reduced_key).
-        if (out_key) NMI_HIP_TRY(ctx, hipMemsetAsync(out_key, 0, sizeof(unsigned long long), ctx->stream));
-        NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_keys + ctx->slot, 0, sizeof(unsigned long long), ctx->stream));
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (post) {
-            ++ctx->seq;
-            ctx->mailbox->word = (unsigned long long)(ctx->seq & 1u) << 63;
-        }
-        ctx->posted = post;
-        ctx->last_slot = ctx->slot;
-        ctx->last_parts = 0;
-        ctx->last_pix = 0;
-        ctx->last_epoch = 0;
-        return NMI_OK;
-    }
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
-    int parts = 0, pix_parts = 1;
-    // the split kernel's consumers wait for their producers inside the launch: all its workgroups must be able to run at
-    // once, i.e. no more of them than compute units (each takes a whole CU)
-    choose_split(ctx, total, cap, &parts, &pix_parts);
-    if (pix_parts > 1 && ctx->npix >= (1 << 24)) pix_parts = 1;  // block granules hold 24-bit counts
-    int pix = choose_pix(ctx, a, total, cap);  // mid-size grids: pixel ranges (no residence condition, heals itself)
-    if (pix) parts = 0;
-    if (parts && !split_checked) parts = 0;  // enqueue-only call: nobody would notice a timed-out hand-off, so no split kernel
-    if (parts && ctx->split_cooldown > 0) {  // after a timeout: nmi_grid_kernel for a while, then the split forms again
-        --ctx->split_cooldown;
-        parts = 0;
-    }
-    if (!parts) pix_parts = 1;
-    // Few-levels path (nmi_fewlevels_kernel.hip).  The decision rests on what the most recent probe of a search's stacks
-    // found (frames and renders of consecutive searches look alike); it is only a matter of speed, because the probe that
-    // goes with every few-levels launch hands the search back to nmi_grid_kernel (gated launch below) when this
-    // search's stacks do not qualify.
-    bool few = false;
-    const bool few_eligible = !parts && !(pix && ctx->split_mode == 1) && a.vec_ok && (ctx->shift == 0 || p.use_bg) && ctx->hist_variant == 3 && ctx->phase_mask == 3 && !dbg_joint &&
-                              !dbg_h1 && !dbg_h2 && !dbg_sums && !ctx->pair_renders && !ctx->dbg_stamps && ctx->content_path != 0;
-    if (few_eligible) {
-        // What the most recent search found in its stacks (nr, nw), posted by the device: by the probe that goes with every
-        // few-levels launch, or by nmi_grid_kernel itself -- every general search counts the bins of its candidates'
-        // marginals on the way (publish_seen / post_seen), so a change of content shows after ONE search, with no extra launch.
-        const unsigned long long posted = __atomic_load_n(ctx->level_post, __ATOMIC_ACQUIRE);
-        if ((uint32_t)(posted >> 32) != ctx->level_seen) {
-            ctx->level_seen = (uint32_t)(posted >> 32);
-            const uint32_t joint = (uint32_t)((posted >> 16) & 0xFFFFu) * (uint32_t)(posted & 0xFFFFu);
-            ctx->few_hint = joint > 0 && joint <= (uint32_t)ctx->fewlevels_bins;
-        }
-        few = ctx->content_path == 1 || ctx->few_hint;
-    }
-    if (few) pix = 0;  // few distinct intensities: the few-levels kernels are the faster ones at any grid size
-    if (ctx->pair_renders && !parts) return NMI_ERR_UNSUPPORTED;  // per-pair pointers exist in the split kernel only (nmi_eval_pairs decides first)
-    int workgroups = (int)(total < cap ? total : cap);
-    if (parts) {
-        int rs = ensure_slabs(ctx, (int)total);
-        if (rs == NMI_OK && pix_parts > 1) rs = ensure_blocks(ctx, (size_t)total * nmi::split_block_bytes_per_candidate(pix_parts));
-        if (rs != NMI_OK) return rs;
-        if (rs == NMI_OK) rs = next_split_epoch(ctx, &a.epoch);
-        if (rs != NMI_OK) return rs;
+    const int64_t total = (int64_t)a.S_local * a.Wn;
+    int rc = NMI_OK;
+    if (plan.kind == nmi::SearchKernel::split) {
+        rc = ensure_slabs(ctx, (int)total);
+        if (rc == NMI_OK && plan.pix_parts > 1) rc = ensure_zeroed(ctx, (void **)&ctx->d_blocks, &ctx->blocks_bytes, (size_t)total * nmi::split_block_bytes_per_candidate(plan.pix_parts));
+        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
         a.slabs = ctx->d_slabs;
         a.blocks = ctx->d_blocks;
         a.split_error = ctx->d_split_error;
-        workgroups = nmi::split_workgroups((int)total, parts, pix_parts);
-    } else if (pix) {
-        int rs = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
-        if (rs == NMI_OK) rs = next_split_epoch(ctx, &a.epoch);
-        if (rs == NMI_OK) rs = ensure_pix_timeouts(ctx);
-        if (rs != NMI_OK) return rs;
+    } else if (plan.kind == nmi::SearchKernel::pix) {
+        rc = ensure_zeroed(ctx, (void **)&ctx->d_pix_blocks, &ctx->pix_blocks_bytes, nmi::pix_block_bytes((int)total, plan.pix));
+        if (rc == NMI_OK) rc = prepare_pix_handoff(ctx, &a.epoch);
         a.blocks = ctx->d_pix_blocks;
-        workgroups = (int)total * pix;
-    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {  // 4 B per candidate
-        const int orc = ensure_order(ctx, S_local, Wn, &a.order);
-        if (orc != NMI_OK) return orc;
+    } else if (plan.order_table) {
+        rc = ensure_order(ctx, a.S_local, a.Wn, &a.order);
     }
+    if (rc != NMI_OK) return rc;
 #ifdef NMI_BUILD_ABLATIONS
-    if (ctx->hist_variant == 4 && workgroups > ctx->scratch_workgroups) {
+    if (plan.scratch && plan.workgroups > ctx->scratch_workgroups) {
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->d_scratch) NMI_HIP_TRY(ctx, hipFree(ctx->d_scratch));
         ctx->d_scratch = nullptr;
         ctx->scratch_workgroups = 0;
-        const int alloc = workgroups > ctx->compute_units ? workgroups : ctx->compute_units;
+        const int alloc = plan.workgroups > ctx->compute_units ? plan.workgroups : ctx->compute_units;
         NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_scratch, nmi::grid_kernel_scratch_bytes(alloc)));
         ctx->scratch_workgroups = alloc;
         a.scratch = ctx->d_scratch;
     }
 #endif
-    if (!parts && !few && ctx->hist_variant == 3 && ctx->content_path != 0) a.plan = ctx->d_plan;  // the search doubles as a probe
-    if (few) {
-        const size_t need = (size_t)(S_local + Wn) * (size_t)ctx->npix;
+    if (plan.probe) a.plan = ctx->d_plan;  // the search doubles as a probe (few-levels: the plan of its own probe)
+    if (plan.kind == nmi::SearchKernel::few_levels) {
+        const size_t need = (size_t)(a.S_local + a.Wn) * (size_t)ctx->npix;
         if (need > ctx->rank_bytes) {
             NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (ctx->d_rank_stacks) NMI_HIP_TRY(ctx, hipFree(ctx->d_rank_stacks));
@@ -362,33 +206,24 @@ int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_o
             NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rank_stacks, want));
             ctx->rank_bytes = want;
         }
-        a.plan = ctx->d_plan;
     }
-    if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    if (few)
-        NMI_HIP_TRY(ctx, nmi::launch_levels(render_stack, S_local, warp_stack, Wn, ctx->npix, ctx->shift, ctx->d_plan, ctx->level_post, ++ctx->level_seq,
-                                            (uint32_t)ctx->fewlevels_bins, few, ctx->stream));
-    if (parts) {
-        NMI_HIP_TRY(ctx, nmi::launch_split(a, parts, pix_parts, workgroups, p.use_bg != 0, ctx->stream));
-    } else if (pix) {
-        NMI_HIP_TRY(ctx, nmi::launch_pix(a, pix, pix_owner_share(ctx, pix), p.use_bg != 0, nullptr, ctx->d_pix_timeouts, ctx->stream));
-    } else if (few) {
-        NMI_HIP_TRY(ctx, nmi::launch_fewlevels(a, ctx->d_rank_stacks, ctx->d_rank_stacks + (size_t)S_local * ctx->npix, workgroups,
-                                               p.use_bg != 0, ctx->stream));
-        NMI_HIP_TRY(ctx, nmi::launch_grid_gated(a, workgroups, p.use_bg != 0, ctx->stream));
-    } else {
-        NMI_HIP_TRY(ctx, nmi::launch_grid(a, workgroups, p.use_bg != 0, ctx->stream));
-    }
-    ctx->last_few = few ? 1 : 0;
-    // accepted: commit the protocol state
+    return NMI_OK;
+}
+
+// Only launches whose winner the host will poll for post to the mailbox (one bit of sequence is enough because those calls
+// are blocking, hence strictly alternating).  The sequence numbers, the key-slot flip, the "posted" flag and the launch
+// record are committed here, once the launch has been accepted: a failed launch leaves the protocol in step.  An empty
+// search (launched = false) keeps its key slot for the next launch: the slot is still "zero on entry".
+int commit_launch(nmi_ctx *ctx, bool post, bool post_score, const SearchLaunch &rec, bool launched, SearchLaunch *out)
+{
     if (post) ++ctx->seq;
     if (post_score) ++ctx->pair_seq;
     ctx->posted = post;
     ctx->last_slot = ctx->slot;
+    ctx->last = rec;
+    if (out) *out = rec;
+    if (!launched) return NMI_OK;
     ctx->slot ^= 1;
-    ctx->last_parts = parts;
-    ctx->last_pix = pix;
-    ctx->last_epoch = parts ? a.epoch : 0;
     if (ctx->profiling) {
         NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
         ctx->have_timing = true;
@@ -396,12 +231,122 @@ int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_o
     return NMI_OK;
 }
 
+// The grid arguments every search starts from: the request's block, the frame geometry, the key slots of this launch.
+nmi::GridArgs grid_args(const nmi_ctx *ctx, const SearchRequest &rq, bool post, bool post_score)
+{
+    const nmi_params &p = ctx->params;
+    nmi::GridArgs a{};
+    a.render_stack = rq.render_stack;
+    a.warp_stack = rq.warp_stack;
+    a.S_local = rq.S_local;
+    a.Wn = rq.Wn;
+    a.s_offset = rq.s_offset;
+    a.S_total = rq.S_total;
+    a.w_offset = rq.w_offset;
+    nmi::set_geometry(a, p.width, p.height, rq.render_stack, rq.warp_stack, p.render_bottom_up != 0);
+    a.shift = ctx->shift;
+    a.mode = p.mode;
+    a.ratings = rq.d_ratings;
+    a.key = ctx->d_keys + ctx->slot;
+    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
+    a.out_key = rq.out_key;
+    a.done = ctx->d_done;
+    a.mailbox = post ? ctx->mailbox : nullptr;
+    a.score_post = post_score ? ctx->score_mailbox : nullptr;
+    a.seq = post ? ctx->seq + 1 : (post_score ? ctx->pair_seq + 1 : 0);
+    a.hist_variant = ctx->hist_variant;
+    return a;
+}
+
+// Five steps: the arguments, the plan, its resources, the launch the plan names, the record.
+int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched)
+{
+    const nmi_params &p = ctx->params;
+    const bool post = rq.post && ctx->result_path == 1, post_score = rq.post_score && ctx->result_path == 1;
+    nmi::GridArgs a = grid_args(ctx, rq, post, post_score);
+    if (rq.pair_renders) {  // nmi_eval_pairs: per-pair pointers; the 16-byte path needs every one of them aligned
+        a.pair_renders = rq.pair_renders;
+        a.pair_warps = rq.pair_warps;
+        uintptr_t bits = 0;
+        for (int i = 0; i < rq.S_local; ++i) bits |= (uintptr_t)rq.pair_renders_host[i] | (uintptr_t)rq.pair_warps_host[i];
+        if (bits % 16) nmi::set_geometry(a, p.width, p.height, (const void *)1, (const void *)1, p.render_bottom_up != 0);
+    }
+    a.table = ctx->table;
+    a.scratch = ctx->d_scratch;
+    a.dbg_joint = rq.dbg_joint;
+    a.dbg_h1 = rq.dbg_h1;
+    a.dbg_h2 = rq.dbg_h2;
+    a.dbg_sums = rq.dbg_sums;
+    a.dbg_stamps = ctx->dbg_stamps;
+
+    const int64_t total = (int64_t)rq.S_local * rq.Wn;
+    if (total == 0) {
+        // nothing to score: the winner is "none" (key 0); publish it the way the kernel would.  The key slot keeps its
+        // "zero on entry" state for the next launch (nothing ever writes a winner into a ping-pong slot from outside:
+        // the RCCL form reduces into ctx->d_reduced_key).
+        if (rq.out_key) NMI_HIP_TRY(ctx, hipMemsetAsync(rq.out_key, 0, sizeof(unsigned long long), ctx->stream));
+        NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_keys + ctx->slot, 0, sizeof(unsigned long long), ctx->stream));
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (post) ctx->mailbox->word = (unsigned long long)((ctx->seq + 1) & 1u) << 63;
+        return commit_launch(ctx, post, false, SearchLaunch{}, /*launched=*/false, launched);
+    }
+    nmi::PlanInputs in = plan_inputs(ctx, nmi::SearchForm::plain, total, a);
+    in.debug_exports = rq.dbg_joint || rq.dbg_h1 || rq.dbg_h2 || rq.dbg_sums;
+    in.stamps = ctx->dbg_stamps != nullptr;
+    in.pair_pointers = rq.pair_renders != nullptr;
+    // does somebody look for a split-kernel timeout after this launch?  (blocking calls, nmi_eval_pairs, stream tickets, RCCL form)
+    in.split_checked = rq.post || rq.post_score || rq.caller_checks_split || in.pair_pointers;
+    // What the most recent search found in its stacks (nr, nw), posted by the device: by the probe that goes with every
+    // few-levels launch, or by nmi_grid_kernel itself -- every general search counts the bins of its candidates'
+    // marginals on the way (publish_seen / post_seen), so a change of content shows after ONE search, with no extra launch.
+    const unsigned long long posted = __atomic_load_n(ctx->level_post, __ATOMIC_ACQUIRE);
+    if ((uint32_t)(posted >> 32) != ctx->level_seen) {
+        const uint32_t joint = (uint32_t)((posted >> 16) & 0xFFFFu) * (uint32_t)(posted & 0xFFFFu);
+        in.few_hint = joint > 0 && joint <= (uint32_t)ctx->fewlevels_bins;
+    }
+    const nmi::SearchPlan plan = nmi::plan_search(in);
+    // the two stateful steps of the decision: a held-back split form takes one unit off the pause, a consulted hint is kept
+    if (plan.used_cooldown) --ctx->split_cooldown;
+    if (plan.read_hint) {
+        ctx->level_seen = (uint32_t)(posted >> 32);
+        ctx->few_hint = in.few_hint;
+    }
+    if (plan.unsupported) return NMI_ERR_UNSUPPORTED;  // (nmi_eval_pairs decides first)
+    a.phase_mask = plan.phase_mask;
+    const int rc = prepare_search(ctx, plan, a);
+    if (rc != NMI_OK) return rc;
+
+    const bool use_bg = p.use_bg != 0;
+    if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    switch (plan.kind) {
+    case nmi::SearchKernel::split:
+        NMI_HIP_TRY(ctx, nmi::launch_split(a, plan.parts, plan.pix_parts, plan.workgroups, use_bg, ctx->stream));
+        break;
+    case nmi::SearchKernel::pix:
+        NMI_HIP_TRY(ctx, nmi::launch_pix(a, plan.pix, pix_owner_share(ctx, plan.pix), use_bg, nullptr, ctx->d_pix_timeouts, ctx->stream));
+        break;
+    case nmi::SearchKernel::few_levels:
+        NMI_HIP_TRY(ctx, nmi::launch_levels(rq.render_stack, rq.S_local, rq.warp_stack, rq.Wn, ctx->npix, ctx->shift, ctx->d_plan, ctx->level_post,
+                                            ++ctx->level_seq, (uint32_t)ctx->fewlevels_bins, true, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_fewlevels(a, ctx->d_rank_stacks, ctx->d_rank_stacks + (size_t)rq.S_local * ctx->npix, plan.workgroups, use_bg,
+                                               ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_grid_gated(a, plan.workgroups, use_bg, ctx->stream));
+        break;
+    default:
+        NMI_HIP_TRY(ctx, nmi::launch_grid(a, plan.workgroups, use_bg, ctx->stream));
+    }
+    const bool few = plan.kind == nmi::SearchKernel::few_levels;
+    return commit_launch(ctx, post, post_score, SearchLaunch{plan.kind, plan.parts, plan.pix, plan.parts ? a.epoch : 0, few ? 1 : 0},
+                         /*launched=*/true, launched);
+}
+
 // A hand-off of the split kernel timed out (its workgroups could not all run at once -- e.g. the device exposes fewer
 // compute units to this process than it reports): wait for the launch to drain, switch the split forms off for this
 // context and tell the caller to redo the call, which then goes through nmi_grid_kernel.
-bool split_launch_failed(nmi_ctx *ctx, int parts, uint32_t epoch)
+bool split_launch_failed(nmi_ctx *ctx, const SearchLaunch &launch)
 {
-    if (!parts) return false;
+    if (!launch.parts) return false;
+    const uint32_t epoch = launch.epoch;
     uint32_t *word = ctx->h_split_error + (epoch % nmi::kSplitRing);
     if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != epoch) {
         // a split launch that went through re-arms the short cooldown -- if it was issued AFTER the last pause was set: a sibling
@@ -419,10 +364,11 @@ bool split_launch_failed(nmi_ctx *ctx, int parts, uint32_t epoch)
 }
 
 // Call once the most recent launch's result has arrived (the kernel raises the flag before it posts anything).
-bool split_timed_out(nmi_ctx *ctx) { return split_launch_failed(ctx, ctx->last_parts, ctx->last_epoch); }
+bool split_timed_out(nmi_ctx *ctx) { return split_launch_failed(ctx, ctx->last); }
 
-// what nmi_last_error_detail says after a call that was redone because of such a timeout (the call itself succeeded)
-static const char *const kSplitTimeoutNote = "split kernel hand-off timed out; call redone by the one-workgroup kernel, split forms paused (nmi_split_status)";
+const char *const kSplitTimeoutNote = "split kernel hand-off timed out; call redone by the one-workgroup kernel, split forms paused (nmi_split_status)";
+const char *const kSplitTimeoutTicketNote = "split kernel hand-off timed out; ticket redone by the one-workgroup kernel, split forms paused (nmi_split_status)";
+const char *const kSplitTimeoutTicketLost = "split kernel hand-off timed out and the ticket's warp stack is gone: submit the level again";
 
 // Polls a pinned host word until (word & mask) == want; *out receives the word.  NMI_OPT_WAIT_MODE 0 spins (lowest
 // latency; occupies the calling core for the duration of the search), 1 yields the core between polls (the Tracking
@@ -844,7 +790,7 @@ int nmi_last_content(nmi_ctx *ctx, int32_t *few_levels, int32_t *nr, int32_t *nw
     // (LevelPlan::use, untouched since: the stream is idle) is what let one of the two scoring kernels behind it run.  Read it,
     // do not restate it: a restatement on the host agrees with any device-side slip at the limit.
     uint32_t use = 0;
-    if (few_levels && ctx->last_few) {
+    if (few_levels && ctx->last.few) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(&use, &ctx->d_plan->use, sizeof use, hipMemcpyDeviceToHost, ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -908,10 +854,12 @@ int nmi_internal::search_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_
     if ((int64_t)S_total * Wn_total >= 0x7FFFFFFFll) return NMI_ERR_UNSUPPORTED;  // index lives in 32 bits of the key
     const int32_t Wn = Wn_local;
     DeviceGuard guard(ctx->device);
-    ctx->allow_unchecked_split = caller_checks;
-    rc = enqueue_grid(ctx, render_stack, S_local, s_offset, S_total, warp_stack, Wn, d_ratings, (unsigned long long *)d_key,
-                      h_key != nullptr, nullptr, nullptr, nullptr, nullptr, w_offset);
-    ctx->allow_unchecked_split = false;
+    SearchRequest rq = SearchRequest::block(render_stack, S_local, s_offset, S_total, warp_stack, Wn, w_offset);
+    rq.d_ratings = d_ratings;
+    rq.out_key = (unsigned long long *)d_key;
+    rq.post = h_key != nullptr;
+    rq.caller_checks_split = caller_checks;
+    rc = enqueue_grid(ctx, rq);
     if (rc != NMI_OK) return rc;
     if (h_key) {
         unsigned long long k = 0;
@@ -939,14 +887,14 @@ int nmi_split_status(nmi_ctx *ctx, int32_t *timeouts, int32_t *cooldown_calls_le
     if (timeouts) *timeouts = (int32_t)ctx->split_timeouts;
     if (cooldown_calls_left) *cooldown_calls_left = (int32_t)ctx->split_cooldown;
     if (next_cooldown) *next_cooldown = (int32_t)ctx->split_backoff;
-    if (last_launch_parts) *last_launch_parts = ctx->last_parts;
+    if (last_launch_parts) *last_launch_parts = ctx->last.parts;
     return NMI_OK;
 }
 
 int nmi_pix_status(nmi_ctx *ctx, int32_t *last_launch_ranges, int32_t *healed)
 {
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
-    if (last_launch_ranges) *last_launch_ranges = ctx->last_pix;
+    if (last_launch_ranges) *last_launch_ranges = ctx->last.pix;
     if (healed) {
         *healed = 0;
         if (ctx->d_pix_timeouts) {
@@ -976,8 +924,14 @@ int nmi_eval_pair_debug(nmi_ctx *ctx, const uint8_t *render, const uint8_t *warp
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     const bool dbg = d_joint || d_hist_render || d_hist_warped || d_sums;
-    int rc = enqueue_grid(ctx, render, 1, 0, 1, warped, 1, ctx->d_pair_rating, nullptr, false, d_joint, d_hist_render,
-                          d_hist_warped, d_sums, 0, /*post_score=*/true);
+    SearchRequest rq = SearchRequest::block(render, 1, 0, 1, warped, 1);
+    rq.d_ratings = ctx->d_pair_rating;
+    rq.post_score = true;
+    rq.dbg_joint = d_joint;
+    rq.dbg_h1 = d_hist_render;
+    rq.dbg_h2 = d_hist_warped;
+    rq.dbg_sums = d_sums;
+    int rc = enqueue_grid(ctx, rq);
     if (rc != NMI_OK) return rc;
     if (ctx->result_path == 1) {
         // kernel.cu:100 copies the score back with a blocking cudaMemcpy; here the scoring lane stores
@@ -1029,11 +983,11 @@ int nmi_eval_pairs(nmi_ctx *ctx, const uint8_t *const *h_renders, const uint8_t 
         }
         return NMI_OK;
     }
-    bool split_ok = ctx->hist_variant == 3 && ctx->split_mode != 0 && ctx->split_mode != 1 && ctx->split_cooldown == 0;
+    bool split_ok = true;
     for (int off = 0; split_ok && off < n; off += per_launch) {
-        int parts = 0, pix = 1;
-        choose_split(ctx, n - off < per_launch ? n - off : per_launch, ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units, &parts, &pix);
-        split_ok = parts != 0;
+        nmi::PlanInputs in = plan_inputs(ctx, nmi::SearchForm::plain, n - off < per_launch ? n - off : per_launch, nmi::GridArgs{});
+        in.pair_pointers = in.split_checked = true;
+        split_ok = !nmi::plan_search(in).unsupported;
     }
     if (!split_ok) {  // one pair at a time (nmi_eval_pair consumes the cooldown)
         for (int i = 0; i < n; ++i) {
@@ -1062,24 +1016,24 @@ int nmi_eval_pairs(nmi_ctx *ctx, const uint8_t *const *h_renders, const uint8_t 
         ctx->h_pair_table[i] = h_renders[i];
         ctx->h_pair_table[ctx->pairs_cap + i] = h_warps[i];
     }
-    uint32_t first_epoch = 0, n_launches = 0;
+    SearchLaunch launches[128];  // (the batch was cut to at most that many above)
+    int n_launches = 0;
     for (int off = 0; off < n; off += per_launch) {
         const int m = n - off < per_launch ? n - off : per_launch;
-        ctx->pair_renders = ctx->d_pair_table + off;
-        ctx->pair_warps = ctx->d_pair_table + ctx->pairs_cap + off;
-        ctx->pair_renders_host = h_renders + off;
-        ctx->pair_warps_host = h_warps + off;
-        const int rc = enqueue_grid(ctx, h_renders[off], m, 0, m, h_warps[off], 1, ctx->d_pair_scores + off, nullptr, false, nullptr,
-                                    nullptr, nullptr, nullptr);
-        ctx->pair_renders = ctx->pair_warps = nullptr;
+        SearchRequest rq = SearchRequest::block(h_renders[off], m, 0, m, h_warps[off], 1);
+        rq.d_ratings = ctx->d_pair_scores + off;
+        rq.pair_renders = ctx->d_pair_table + off;
+        rq.pair_warps = ctx->d_pair_table + ctx->pairs_cap + off;
+        rq.pair_renders_host = h_renders + off;
+        rq.pair_warps_host = h_warps + off;
+        const int rc = enqueue_grid(ctx, rq, &launches[n_launches]);
         if (rc != NMI_OK) return rc;  // (NMI_ERR_UNSUPPORTED, before any launch, had no split form fitted after all)
-        if (!n_launches++) first_epoch = ctx->last_epoch;
+        ++n_launches;
     }
     NMI_HIP_TRY(ctx, hipMemcpyAsync(h_scores, ctx->d_pair_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    bool failed = false;  // every launch of the batch answers for itself (epochs are consecutive, apart from the skipped multiples of 65536)
-    for (uint32_t e = first_epoch; n_launches && e - first_epoch <= ctx->last_epoch - first_epoch; ++e)
-        failed = split_launch_failed(ctx, ctx->last_parts, e) || failed;
+    bool failed = false;  // every launch of the batch answers for itself
+    for (int i = 0; i < n_launches; ++i) failed = split_launch_failed(ctx, launches[i]) || failed;
     if (failed) {  // now one pair at a time, through nmi_grid_kernel
         const int rc = nmi_eval_pairs(ctx, h_renders, h_warps, n, h_scores);
         if (rc == NMI_OK) ctx->detail = kSplitTimeoutNote;

@@ -40,8 +40,10 @@ int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uin
     if (rc == NMI_OK) rc = ensure_mask_redo(ctx, total);
     if (rc != NMI_OK) return rc;
 
-    rc = enqueue_grid_mask(ctx, render_stack, render_masks, S, 0, S, warp_stack, warp_masks, Wn, 0, ctx->d_cover_counts, nullptr,
-                           ctx->d_mask_redo, ctx->d_mask_redo_state, d_ratings, nullptr, /*post=*/true);
+    SearchRequest rq = SearchRequest::block(render_stack, S, 0, S, warp_stack, Wn);
+    rq.d_ratings = d_ratings;
+    rq.post = true;
+    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, render_masks, ctx->d_cover_counts, nullptr, ctx->d_mask_redo, ctx->d_mask_redo_state});
     if (rc != NMI_OK) return rc;
     ctx->cover_count_n = total;
     unsigned long long key = 0;

@@ -46,31 +46,30 @@ int nmi_internal::ensure_mask_redo(nmi_ctx *ctx, int64_t total)
     return NMI_OK;
 }
 
-MaskSearch nmi_internal::mask_search_args(const nmi::GridArgs &a, const uint8_t *warp_masks, const uint8_t *render_masks, int32_t *counts,
-                                          const float *tables, int32_t *redo, uint32_t *redo_state)
+MaskSearch nmi_internal::mask_search_args(const nmi::GridArgs &a, const MaskSide &side)
 {
     MaskSearch ms{};
-    ms.covered = render_masks != nullptr;
+    ms.covered = side.render_masks != nullptr;
     if (ms.covered) {
         nmi::CoveredGridArgs &m = ms.cover;
         m.g = a;
-        m.warp_masks = warp_masks;
-        m.render_masks = render_masks;
-        m.counts = counts;
-        m.vec_ok = a.vec_ok && (((uintptr_t)warp_masks | (uintptr_t)render_masks) % 16) == 0;
-        m.redo = redo;
-        m.redo_n = redo_state;
-        m.redo_done = redo_state + 1;
+        m.warp_masks = side.warp_masks;
+        m.render_masks = side.render_masks;
+        m.counts = side.counts;
+        m.vec_ok = a.vec_ok && (((uintptr_t)side.warp_masks | (uintptr_t)side.render_masks) % 16) == 0;
+        m.redo = side.redo;
+        m.redo_n = side.redo_state;
+        m.redo_done = side.redo_state + 1;
     } else {
         nmi::MaskedGridArgs &m = ms.masked;
         m.g = a;
-        m.warp_masks = warp_masks;
-        m.tables = tables;
-        m.counts = counts;
-        m.vec_ok = a.vec_ok && ((uintptr_t)warp_masks % 16) == 0;
-        m.redo = redo;
-        m.redo_n = redo_state;
-        m.redo_done = redo_state + 1;
+        m.warp_masks = side.warp_masks;
+        m.tables = side.tables;
+        m.counts = side.counts;
+        m.vec_ok = a.vec_ok && ((uintptr_t)side.warp_masks % 16) == 0;
+        m.redo = side.redo;
+        m.redo_n = side.redo_state;
+        m.redo_done = side.redo_state + 1;
     }
     return ms;
 }
@@ -86,75 +85,24 @@ hipError_t nmi_internal::launch_mask_search(const MaskSearch &ms, int pix, doubl
 }
 
 // nmi_search_grid_masked's and nmi_search_grid_covered's launches without their blocking tails (they also serve the masked and
-// covered stream tickets): the covered search when render_masks is set, see mask_search_args.  out_key: optional device word
-// that receives the packed key; post: the caller polls the mailbox (the blocking call).  Commits enqueue_grid's protocol
-// bookkeeping once the launches are accepted.  S_local * Wn > 0.
-int nmi_internal::enqueue_grid_mask(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int S_local, int s_offset,
-                                    int S_total, const uint8_t *warp_stack, const uint8_t *warp_masks, int Wn, int w_offset, int32_t *counts,
-                                    const float *tables, int32_t *redo, uint32_t *redo_state, float *d_ratings, unsigned long long *out_key,
-                                    bool post)
+// covered stream tickets): the covered search when m.render_masks is set, see MaskSide.  enqueue_grid's steps and its protocol
+// bookkeeping (commit_launch).  S_local * Wn > 0.
+int nmi_internal::enqueue_grid_mask(nmi_ctx *ctx, const SearchRequest &rq, const MaskSide &m, SearchLaunch *launched)
 {
     const nmi_params &p = ctx->params;
-    const int64_t total = (int64_t)S_local * Wn;
-    int rc = NMI_OK;
-    nmi::GridArgs a{};
-    a.render_stack = render_stack;
-    a.warp_stack = warp_stack;
-    a.S_local = S_local;
-    a.Wn = Wn;
-    a.s_offset = s_offset;
-    a.S_total = S_total;
-    a.w_offset = w_offset;
-    nmi::set_geometry(a, p.width, p.height, render_stack, warp_stack, p.render_bottom_up != 0);
-    a.shift = ctx->shift;
-    a.mode = p.mode;
-    a.table = nullptr;
-    a.plan = nullptr;
-    a.ratings = d_ratings;
-    a.key = ctx->d_keys + ctx->slot;
-    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
-    a.out_key = out_key;
-    a.done = ctx->d_done;
-    post = post && ctx->result_path == 1;
-    a.mailbox = post ? ctx->mailbox : nullptr;
-    a.seq = post ? ctx->seq + 1 : 0;
-    a.hist_variant = ctx->hist_variant;
-    a.phase_mask = 3;
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
-    const int workgroups = (int)(total < cap ? total : cap);
-    // mid-size grids: pixel ranges (nmi_masked_pix_kernel.hip, nmi_covered_pix_kernel.hip), by nmi_search_grid's rules and
-    // controls (choose_pix)
-    const int pix = choose_pix(ctx, a, total, cap);
-    if (pix) {
-        rc = ensure_pix_blocks(ctx, nmi::pix_block_bytes((int)total, pix));
-        if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
-        if (rc == NMI_OK) rc = ensure_pix_timeouts(ctx);
-        if (rc != NMI_OK) return rc;
-        a.blocks = ctx->d_pix_blocks;
-        a.phase_mask = 3 | (ctx->phase_mask & 512);  // (bit 9: the helpers' hand-off test hook, as for nmi_pix_kernel)
-    } else if (ctx->xcd_tiling && total <= (1ll << 24)) {
-        rc = ensure_order(ctx, S_local, Wn, &a.order);
-        if (rc != NMI_OK) return rc;
-    }
-    const MaskSearch ms = mask_search_args(a, warp_masks, render_masks, counts, tables, redo, redo_state);
+    const bool post = rq.post && ctx->result_path == 1;
+    nmi::GridArgs a = grid_args(ctx, rq, post, false);  // (no term table, no probe's plan: MaskSearch)
+    // mid-size grids: pixel ranges (nmi_masked_pix_kernel.hip, nmi_covered_pix_kernel.hip), by nmi_search_grid's rules and controls
+    const nmi::SearchPlan plan = nmi::plan_search(plan_inputs(ctx, nmi::SearchForm::masked, (int64_t)rq.S_local * rq.Wn, a));
+    a.phase_mask = plan.phase_mask;
+    const int rc = prepare_search(ctx, plan, a);
+    if (rc != NMI_OK) return rc;
+    const MaskSearch ms = mask_search_args(a, m);
     // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid -- not the masked search's counts and tables before them
     if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    NMI_HIP_TRY(ctx, launch_mask_search(ms, pix, pix ? pix_owner_share(ctx, pix) : 0.0, workgroups, p.use_bg != 0, ctx->hist_variant == 1, nullptr,
-                                        ctx->d_pix_timeouts, ctx->stream));
-    // accepted: commit the protocol state (enqueue_grid's bookkeeping)
-    if (post) ++ctx->seq;
-    ctx->posted = post;
-    ctx->last_slot = ctx->slot;
-    ctx->slot ^= 1;
-    ctx->last_parts = 0;
-    ctx->last_pix = pix;
-    ctx->last_epoch = 0;
-    ctx->last_few = 0;
-    if (ctx->profiling) {
-        NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-        ctx->have_timing = true;
-    }
-    return NMI_OK;
+    NMI_HIP_TRY(ctx, launch_mask_search(ms, plan.pix, plan.pix ? pix_owner_share(ctx, plan.pix) : 0.0, plan.workgroups, p.use_bg != 0,
+                                        ctx->hist_variant == 1, nullptr, ctx->d_pix_timeouts, ctx->stream));
+    return commit_launch(ctx, post, false, SearchLaunch{plan.kind, 0, plan.pix, 0, 0}, /*launched=*/true, launched);
 }
 
 extern "C" {
@@ -197,8 +145,10 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
         return nmi_key_unpack(0, h_best_index, h_best_score);
     }
 
-    rc = enqueue_grid_mask(ctx, render_stack, nullptr, S, 0, S, warp_stack, warp_masks, Wn, 0, ctx->d_mask_counts, ctx->d_mask_tables,
-                           ctx->d_mask_redo, ctx->d_mask_redo_state, d_ratings, nullptr, /*post=*/true);
+    SearchRequest rq = SearchRequest::block(render_stack, S, 0, S, warp_stack, Wn);
+    rq.d_ratings = d_ratings;
+    rq.post = true;
+    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, nullptr, ctx->d_mask_counts, ctx->d_mask_tables, ctx->d_mask_redo, ctx->d_mask_redo_state});
     if (rc != NMI_OK) return rc;
     unsigned long long key = 0;
     rc = fetch_key(ctx, &key);

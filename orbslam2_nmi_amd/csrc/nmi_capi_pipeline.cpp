@@ -178,11 +178,11 @@ static int level_capture(nmi_level *lv)
     const uint8_t *d_frame = in.own_frame() ? lv->d_ud : lv->d_frame;
     const uint8_t *d_frame_mask = in.distorted ? ud_mask : set.d_frame_mask;
     nmi::GridArgs a = lv->args;
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
     // (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip, nmi_covered_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the
     // prep kernel keeps; the level keeps one epoch for all its captures (the replay count only grows, so tags never repeat).
-    lv->pix = choose_pix(ctx, a, total, cap);
+    const nmi::SearchPlan plan = nmi::plan_search(plan_inputs(ctx, nmi::SearchForm::level, total, a));
+    lv->pix = plan.pix;
     if (lv->pix) {
         const size_t bytes = nmi::pix_block_bytes((int)total, lv->pix);
         if (bytes > lv->pix_blocks_bytes) {
@@ -193,8 +193,7 @@ static int level_capture(nmi_level *lv)
             if (ok.e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
             if (ok.e == hipSuccess) lv->pix_blocks_bytes = bytes;
         }
-        if (ok.e == hipSuccess && lv->args.epoch == 0 && next_split_epoch(ctx, &lv->args.epoch) != NMI_OK) ok.e = hipErrorOutOfMemory;
-        if (ok.e == hipSuccess && ensure_pix_timeouts(ctx) != NMI_OK) ok.e = hipErrorOutOfMemory;
+        if (ok.e == hipSuccess && prepare_pix_handoff(ctx, &lv->args.epoch) != NMI_OK) ok.e = hipErrorOutOfMemory;
         if (ok.e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
         a.epoch = lv->args.epoch;
         a.blocks = lv->d_pix_blocks;
@@ -202,9 +201,9 @@ static int level_capture(nmi_level *lv)
     }
     const int workgroups = lv->workgroups;
     nmi::GridArgs ma = a;
-    ma.phase_mask = lv->pix ? 3 | (ctx->phase_mask & 512) : 3;  // (bit 9: the pixel-range kernel's hand-off test hook)
-    const MaskSearch ms = mask_search_args(ma, lv->d_masks, covered ? lv->d_rmasks : nullptr, covered ? lv->d_cover_counts : lv->d_counts,
-                                           lv->d_tables, lv->d_redo, lv->d_redo_state);
+    ma.phase_mask = plan.phase_mask;  // (bit 9: the pixel-range kernel's hand-off test hook)
+    const MaskSearch ms = mask_search_args(ma, MaskSide{lv->d_masks, covered ? lv->d_rmasks : nullptr, covered ? lv->d_cover_counts : lv->d_counts,
+                                                        lv->d_tables, lv->d_redo, lv->d_redo_state});
     uint8_t *cover = covered ? lv->d_rmasks : nullptr;  // the renderers' coverage masks
     int32_t *d_prev = lv->d_counts + Wn, *d_changed = lv->d_counts + 2 * Wn;
     hipGraph_t graph = nullptr;
@@ -444,8 +443,6 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     a.out_key = hd_key;
     a.hist_variant = 3;
     a.phase_mask = 3;
-    const int cap = ctx->workgroups > 0 ? ctx->workgroups : ctx->compute_units;
-    const int workgroups = (int)(total < cap ? total : cap);
     // the graph (level_capture) is made from these; level_apply captures it again from them
     lv->d_xyz = d_xyz;
     lv->d_attr = d_attr;
@@ -455,7 +452,7 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     lv->args = a;
     lv->hd_mvps = hd_mvps;
     lv->hd_coeffs = hd_coeffs;
-    lv->workgroups = workgroups;
+    lv->workgroups = nmi::grid_workgroups(total, ctx->workgroups, ctx->compute_units);
     if (ok.e == hipSuccess) {
         const int rc = level_capture(lv);
         if (rc != NMI_OK) {
@@ -703,8 +700,8 @@ struct nmi_stream {
         int64_t ticket = -1;
         bool waited = true;
         bool failed = false;         // its search timed out in the split kernel and could not be redone (nmi_stream_wait)
-        int parts = 0;               // split form of the slot's launch (0: nmi_grid_kernel) and its epoch: the launch answers
-        uint32_t epoch = 0;          //   for itself when the ticket is waited for, whatever was launched after it
+        SearchLaunch launch;         // the slot's launch: it answers for itself (split form, epoch) when the ticket is waited
+                                     //   for, whatever was launched after it
         int s_offset = 0, S_total = 0, w_offset = 0;  // position of the slot's block in its level
         int warp_buf = 0;            // warp buffer the search read, and that buffer's generation at submission
         uint64_t warp_gen = 0;
@@ -877,7 +874,7 @@ int nmi_stream_submit(nmi_stream *st, const uint8_t *h_render_stack, int32_t S, 
 }  // extern "C"
 
 // Every submission form.  kind kPlain is nmi_stream_submit_block as it always was; kMasked / kCovered add the masks and take the
-// masked / covered search (never the split kernel: parts stays 0, so nmi_stream_wait never redoes them).
+// masked / covered search (never the split kernel: launch.parts stays 0, so nmi_stream_wait never redoes them).
 static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack, const uint8_t *h_bits, int32_t S, int32_t s_offset,
                          int32_t S_total, const uint8_t *h_frame, const uint8_t *h_frame_mask, const double *h_forward, int32_t Wn,
                          int32_t w_offset, int32_t Wn_total, void *nccl_comm, int64_t *ticket)
@@ -978,21 +975,21 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
     s.w_offset = w_offset;
     float *ratings = st->keep_ratings ? s.d_ratings : nullptr;
     int rc = NMI_OK;
+    SearchRequest rq = SearchRequest::block(s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->cur_Wn, w_offset);
+    rq.d_ratings = ratings;
+    rq.out_key = s.d_key;
     if (kind == kPlain || (int64_t)S * st->cur_Wn == 0) {
-        // nmi_stream_wait checks this very launch for a split-kernel timeout (parts, epoch below) and redoes it -- which it cannot
+        // nmi_stream_wait checks this very launch for a split-kernel timeout (s.launch) and redoes it -- which it cannot
         // do once the key has gone into a collective, so submissions with a communicator keep to the one-workgroup kernel.
         // (An empty masked / covered block comes here too: nothing is scored, the key is "none".)
-        ctx->allow_unchecked_split = nccl_comm == nullptr && kind == kPlain;
-        rc = enqueue_grid(ctx, s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->cur_Wn, ratings, s.d_key, false, nullptr, nullptr,
-                          nullptr, nullptr, w_offset);
-        ctx->allow_unchecked_split = false;
+        rq.caller_checks_split = nccl_comm == nullptr && kind == kPlain;
+        rc = enqueue_grid(ctx, rq, &s.launch);
     } else if (kind == kMasked) {
-        rc = enqueue_grid_mask(ctx, s.d_renders, nullptr, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn, w_offset,
-                               st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+        rc = enqueue_grid_mask(ctx, rq, MaskSide{st->d_wmasks[wb], nullptr, st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state},
+                               &s.launch);
     } else {
         NMI_HIP_TRY(ctx, nmi::launch_unpack_mask_bits(s.d_bits, S, ctx->npix, st->d_rmasks, ctx->stream));
-        rc = enqueue_grid_mask(ctx, s.d_renders, st->d_rmasks, S, s_offset, S_total, st->d_warps[wb], st->d_wmasks[wb], st->cur_Wn,
-                               w_offset, s.d_counts, nullptr, st->d_redo, st->d_redo_state, ratings, s.d_key, false);
+        rc = enqueue_grid_mask(ctx, rq, MaskSide{st->d_wmasks[wb], st->d_rmasks, s.d_counts, nullptr, st->d_redo, st->d_redo_state}, &s.launch);
     }
     if (rc != NMI_OK) return rc;
     s.kind = kind;
@@ -1000,8 +997,6 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
     if (kind == kMasked && s.n_counts > 0)  // len_w into the slot: the buffer's own may be rebuilt by a later frame
         NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_counts, st->d_wcounts[wb], (size_t)s.n_counts * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                         ctx->stream));
-    s.parts = ctx->last_parts;
-    s.epoch = ctx->last_epoch;
     s.warp_buf = wb;
     s.warp_gen = st->warp_gen[wb];
     const unsigned long long *result = s.d_key;
@@ -1123,26 +1118,28 @@ int nmi_stream_wait(nmi_stream *st, int64_t ticket, int64_t *h_best_index, float
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipEventSynchronize(s.done));
     s.waited = true;
-    if (split_launch_failed(ctx, s.parts, s.epoch)) {
+    if (split_launch_failed(ctx, s.launch)) {
         // This ticket's search (a small grid on the split kernel) timed out in a hand-off.  Its render stack is still in the
         // slot; if its warp stack is too (no later frame has refilled that buffer) the search is redone here, behind
         // whatever was submitted since, by nmi_grid_kernel (the split forms are paused now).  Otherwise the ticket fails:
         // NMI_ERR_NOT_READY, its rating table is withheld, and the caller submits the level again.
         if (st->warp_gen[s.warp_buf] != s.warp_gen) {
             s.failed = true;
-            ctx->detail = "split kernel hand-off timed out and the ticket's warp stack is gone: submit the level again";
+            ctx->detail = kSplitTimeoutTicketLost;
             return NMI_ERR_NOT_READY;
         }
-        const int rc = enqueue_grid(ctx, s.d_renders, s.S, s.s_offset, s.S_total, st->d_warps[s.warp_buf], s.Wn,
-                                    st->keep_ratings ? s.d_ratings : nullptr, s.d_key, false, nullptr, nullptr, nullptr, nullptr, s.w_offset);
+        // (enqueue-only and unchecked: never a split form)
+        SearchRequest rq = SearchRequest::block(s.d_renders, s.S, s.s_offset, s.S_total, st->d_warps[s.warp_buf], s.Wn, s.w_offset);
+        rq.d_ratings = st->keep_ratings ? s.d_ratings : nullptr;
+        rq.out_key = s.d_key;
+        const int rc = enqueue_grid(ctx, rq, &s.launch);
         if (rc != NMI_OK) {
             s.failed = true;
             return rc;
         }
-        s.parts = 0;
         NMI_HIP_TRY(ctx, hipMemcpyAsync(s.h_key, s.d_key, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->detail = "split kernel hand-off timed out; ticket redone by the one-workgroup kernel, split forms paused (nmi_split_status)";
+        ctx->detail = kSplitTimeoutTicketNote;
     }
     return nmi_key_unpack(*s.h_key, h_best_index, h_best_score);
 }

@@ -113,7 +113,7 @@ int nmi_search_grid_block_rccl(nmi_ctx *ctx, const uint8_t *render_stack, int32_
                           /*caller_checks=*/true);
     if (rc != NMI_OK) return rc;
     DeviceGuard guard(ctx->device);
-    if (ctx->last_parts) {
+    if (ctx->last.parts) {
         // A small block went to the split kernel, whose hand-offs can time out (nmi_split_kernel.hip).  Every rank must
         // issue exactly one collective with a valid key, so this rank settles its own search first: wait, and on a
         // timeout redo it with the one-workgroup kernel (the split forms are paused for a while, nmi_split_status).

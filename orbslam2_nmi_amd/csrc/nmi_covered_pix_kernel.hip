@@ -1,5 +1,5 @@
 // nmi_covered_pix_kernel.hip -- the covered search for MID-SIZE grids (33 ... 128 candidates on 256 compute units, and the
-// grids choose_pix sends here on frames whose rows are not whole aligned chunks): nmi_pix_kernel's pixel ranges (P workgroups
+// grids plan_search sends here on frames whose rows are not whole aligned chunks): nmi_pix_kernel's pixel ranges (P workgroups
 // per candidate, an owner and P - 1 helpers, dealt pieces of the frame) with nmi_covered_grid_kernel's masks on both sides and
 // per-candidate len.  nmi_covered_grid_kernel gives a candidate to one workgroup, so 81 candidates fill 81 of the 256 CUs;
 // here they fill 243.
@@ -19,7 +19,7 @@
 //     of the count test (a wrapped 16-bit field always loses weight, so the decoded sum falls short iff something wrapped) and
 //     as the terms' denominator.  The two are the same number only because every covered pixel is added -- the background
 //     rule on, or off at 256 bins (row / column 0 cleared in the decode).  The background rule off with fewer than 256 bins
-//     drops pixels by their raw values, which would make them differ; choose_pix never sends that case to a pixel-range kernel.
+//     drops pixels by their raw values, which would make them differ; plan_search never sends that case to a pixel-range kernel.
 //   * Terms.  Known only once every hand-off has arrived: the owner then evaluates the low terms (c <= min(len, kLdsTable - 1))
 //     into lds.table with cover_term, and counts at or above kLdsTable are evaluated inline during the merged decode and the
 //     final trees, as covered_decode_phase does.  No global table is read.

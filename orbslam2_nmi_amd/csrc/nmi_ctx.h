@@ -15,6 +15,16 @@
 #include "nmi_covered.h"
 #include "nmi_kernels.h"
 #include "nmi_masked.h"
+#include "nmi_search_plan.h"
+
+// What a search launched (enqueue_grid, enqueue_grid_mask): the split-timeout redo logic and the status getters go by it.
+struct SearchLaunch {
+    nmi::SearchKernel kind = nmi::SearchKernel::none;
+    int parts = 0;       // row parts per candidate (0 = not the row-split kernel)
+    int pix = 0;         // pixel ranges per candidate when it was a pixel-range kernel (0 = it was not)
+    uint32_t epoch = 0;  // its split epoch (meaningful when parts != 0)
+    int few = 0;         // it went down the few-levels path (it may have fallen back)
+};
 
 // Small host->device parameter uploads (warp coefficients, view matrices) go through a ring of pinned staging buffers so
 // that back-to-back submissions never have to wait for the stream: entry i is reused only after the copy that read it.
@@ -43,16 +53,13 @@ struct nmi_ctx {
     unsigned int seq = 0;                  // launches that post to the mailbox so far (blocking calls only)
     int slot = 0;                          // key slot of the next launch
     int last_slot = 0;                     // key slot of the most recent launch
-    int last_parts = 0;                    // row parts per candidate of the most recent launch (0 = not the row-split kernel)
+    SearchLaunch last;                     // the most recent launch (written by commit_launch only)
     int pix_owner_bias = 49152;            // NMI_OPT_PIX_OWNER_BIAS: pixels the owner of a candidate adds beyond an equal share
-    int last_pix = 0;                      // pixel ranges per candidate when it was nmi_pix_kernel (0 = it was not)
     uint32_t *d_pix_timeouts = nullptr;    // candidates whose owner gave up on a helper and scored them alone (nmi_pix_kernel)
-    uint32_t last_epoch = 0;               // its split epoch (meaningful when last_parts != 0)
     // Split-kernel liveness (nmi_split_kernel.hip: its consumers spin, so a launch whose workgroups are not all resident
     // times out after 2 ms).  A timeout is attributed to ITS launch (epoch), that search is redone by nmi_grid_kernel, and the
     // split forms stay off for split_cooldown further small-grid launches -- 16, doubling per consecutive timeout up to
     // 4096 -- after which they are tried again; a split launch that is checked and found good re-arms the short cooldown.
-    bool allow_unchecked_split = false;    // this launch's caller checks for a timeout itself (blocking calls, stream, RCCL)
     uint32_t split_timeouts = 0;           // timeouts seen so far
     uint32_t split_cooldown = 0;           // small-grid launches still to go through nmi_grid_kernel
     uint32_t split_backoff = kSplitBackoffMin;  // cooldown the next timeout starts
@@ -89,8 +96,6 @@ struct nmi_ctx {
     const uint8_t **h_pair_table = nullptr, **d_pair_table = nullptr;
     float *d_pair_scores = nullptr;
     int pairs_cap = 0;
-    const uint8_t *const *pair_renders = nullptr, *const *pair_warps = nullptr;            // device views for the launch being enqueued
-    const uint8_t *const *pair_renders_host = nullptr, *const *pair_warps_host = nullptr;  // the caller's arrays (alignment check)
     int split_pixels = -1;                // NMI_OPT_SPLIT_PIXELS: -1 automatic, 1 / 2 / 4 (with NMI_OPT_SPLIT 1: 2 ... 8)
     // Few-levels path (nmi_fewlevels_kernel.hip): which kernels score a search is decided from what the last probe of
     // the stacks found, posted by the device to *level_post = probe number << 32 | nr << 16 | nw.
@@ -103,7 +108,6 @@ struct nmi_ctx {
     int fewlevels_bins = 4096;            // NMI_OPT_FEWLEVELS_BINS: largest nr * nw sent down the few-levels path
     uint8_t *d_rank_stacks = nullptr;     // rank images of the search in flight: renders, then warps
     size_t rank_bytes = 0;
-    int last_few = 0;                     // the most recent launch went down the few-levels path (it may have fallen back)
     unsigned long long *dbg_stamps = nullptr;  // NMI_OPT_STAMPS
     int stamp_candidate = 0;                   // NMI_OPT_STAMP_CANDIDATE
     int split_mode = -1;                  // NMI_OPT_SPLIT: -1 automatic, 0 never, 2 / 4 / 8 row parts whenever the grid fits, 1: pixel ranges only
@@ -179,41 +183,80 @@ int rccl_allreduce_key(nmi_ctx *ctx, const unsigned long long *d_send, unsigned 
 int hip_fail(nmi_ctx *ctx, hipError_t e, const char *what);
 void build_order(int S, int Wn, int *order);
 int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order);
-// nmi_pix_kernel (mid-size grids): pixel ranges per candidate for a launch of `total` candidates on `cap` workgroups (0: another
-// kernel), the owner's share of the pixels, the next hand-off epoch, the context's counter of healed timeouts
-int choose_pix(const nmi_ctx *ctx, const nmi::GridArgs &a, int64_t total, int cap);
-double pix_owner_share(const nmi_ctx *ctx, int pix);
-int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch);
-int ensure_pix_timeouts(nmi_ctx *ctx);
-int ensure_pix_blocks(nmi_ctx *ctx, size_t bytes);  // the context's hand-off blocks of the pixel-range kernels (grown on demand)
-int enqueue_grid(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack, int Wn,
-                 float *d_ratings, unsigned long long *out_key, bool post, uint32_t *dbg_joint, uint32_t *dbg_h1, uint32_t *dbg_h2,
-                 float *dbg_sums, int w_offset = 0, bool post_score = false);
-// The masked and covered searches' kernel arguments around the grid arguments a (nmi_capi_masked.cpp): the covered search
-// when render_masks is set (counts receives len[w][s], [Wn][S_local]), else the masked one (counts: len_w [Wn], tables: the
-// warps' term tables).  redo has room for S_local * Wn candidates; redo_state [2] is zero.
+// What is to be scored: the S_local x Wn block at (s_offset, w_offset) of an S_total-render grid.  A call site names what it uses.
+struct SearchRequest {
+    const uint8_t *render_stack = nullptr, *warp_stack = nullptr;
+    int S_local = 0, s_offset = 0, S_total = 0, Wn = 0, w_offset = 0;
+    float *d_ratings = nullptr;
+    unsigned long long *out_key = nullptr;  // optional device word that receives the packed key
+    bool post = false;                      // the caller polls the mailbox for the winner (blocking calls)
+    bool post_score = false;                // ... the score mailbox (nmi_eval_pair)
+    uint32_t *dbg_joint = nullptr, *dbg_h1 = nullptr, *dbg_h2 = nullptr;
+    float *dbg_sums = nullptr;
+    bool caller_checks_split = false;       // the caller looks for a split-kernel timeout itself (stream tickets, RCCL form)
+    // nmi_eval_pairs: candidate p scores (pair_renders[p], pair_warps[p]); device views, and the caller's arrays (alignment check)
+    const uint8_t *const *pair_renders = nullptr, *const *pair_warps = nullptr;
+    const uint8_t *const *pair_renders_host = nullptr, *const *pair_warps_host = nullptr;
+    // the block alone, in the order of the C ABI's entry points
+    static SearchRequest block(const uint8_t *renders, int S_local, int s_offset, int S_total, const uint8_t *warps, int Wn, int w_offset = 0)
+    {
+        SearchRequest rq;
+        rq.render_stack = renders;
+        rq.warp_stack = warps;
+        rq.S_local = S_local;
+        rq.s_offset = s_offset;
+        rq.S_total = S_total;
+        rq.Wn = Wn;
+        rq.w_offset = w_offset;
+        return rq;
+    }
+};
+// The mask side of a masked or covered search: the covered search when render_masks is set (counts receives len[w][s],
+// [Wn][S_local]), else the masked one (counts: len_w [Wn], tables: the warps' term tables).  redo has room for S_local * Wn
+// candidates; redo_state [2] is zero.
+struct MaskSide {
+    const uint8_t *warp_masks = nullptr, *render_masks = nullptr;
+    int32_t *counts = nullptr;
+    const float *tables = nullptr;
+    int32_t *redo = nullptr;
+    uint32_t *redo_state = nullptr;
+};
+// The grid arguments every search starts from: the request's block, the frame geometry, the key slots of this launch.
+nmi::GridArgs grid_args(const nmi_ctx *ctx, const SearchRequest &rq, bool post, bool post_score);
+// The scalars of the context the planner reads (nmi_search_plan.h); the caller adds those of its launch.
+nmi::PlanInputs plan_inputs(const nmi_ctx *ctx, nmi::SearchForm form, int64_t total, const nmi::GridArgs &a);
+double pix_owner_share(const nmi_ctx *ctx, int pix);  // the owner's share of the pixels of a pixel-range launch
+// What every pixel-range launch needs beside its blocks: a hand-off epoch (a new one unless *epoch is set: a level keeps its
+// own) and the context's counter of healed timeouts
+int prepare_pix_handoff(nmi_ctx *ctx, uint32_t *epoch);
+// The buffers the planned launch needs, grown on demand, and their pointers, the epoch and the probe's plan into a
+int prepare_search(nmi_ctx *ctx, const nmi::SearchPlan &plan, nmi::GridArgs &a);
+// The protocol state after an accepted launch (or an empty search: launched = false): sequence numbers, key slot, ctx->last
+int commit_launch(nmi_ctx *ctx, bool post, bool post_score, const SearchLaunch &rec, bool launched, SearchLaunch *out);
+// Enqueues the search (its launches, nothing else).  No synchronisation.  *launched (optional) receives what ctx->last does.
+int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched = nullptr);
+// The masked and covered searches' kernel arguments around the grid arguments a (nmi_capi_masked.cpp)
 struct MaskSearch {
     bool covered;
     nmi::MaskedGridArgs masked;
     nmi::CoveredGridArgs cover;
 };
-MaskSearch mask_search_args(const nmi::GridArgs &a, const uint8_t *warp_masks, const uint8_t *render_masks, int32_t *counts,
-                            const float *tables, int32_t *redo, uint32_t *redo_state);
+MaskSearch mask_search_args(const nmi::GridArgs &a, const MaskSide &m);
 // Its launches: the pixel-range form when pix > 0 (replay, healed: as launch_pix_masked / _covered), else the grid form.
 hipError_t launch_mask_search(const MaskSearch &ms, int pix, double owner_share, int workgroups, bool use_bg, bool exact,
                               const uint32_t *replay, uint32_t *healed, hipStream_t stream);
 int ensure_mask_redo(nmi_ctx *ctx, int64_t total);  // the context's redo list, room for `total` candidates
 // The masked / covered search's launches without its blocking tail (nmi_capi_masked.cpp): serves nmi_search_grid_masked,
 // nmi_search_grid_covered and the masked / covered stream tickets.  S_local * Wn > 0; see the definition.
-int enqueue_grid_mask(nmi_ctx *ctx, const uint8_t *render_stack, const uint8_t *render_masks, int S_local, int s_offset, int S_total,
-                      const uint8_t *warp_stack, const uint8_t *warp_masks, int Wn, int w_offset, int32_t *counts, const float *tables,
-                      int32_t *redo, uint32_t *redo_state, float *d_ratings, unsigned long long *out_key, bool post);
+int enqueue_grid_mask(nmi_ctx *ctx, const SearchRequest &rq, const MaskSide &m, SearchLaunch *launched = nullptr);
 int wait_word(nmi_ctx *ctx, const volatile unsigned long long *word, unsigned long long mask, unsigned long long want,
               unsigned long long *out);
 int stage_floats(nmi_ctx *ctx, StagingRing &ring, const float *h_src, size_t n, float **d_out);
 int fetch_key(nmi_ctx *ctx, unsigned long long *key);
 bool split_timed_out(nmi_ctx *ctx);                                     // ... the most recent launch
-bool split_launch_failed(nmi_ctx *ctx, int parts, uint32_t epoch);      // ... the launch with this epoch (waits for the stream on a hit)
+bool split_launch_failed(nmi_ctx *ctx, const SearchLaunch &launch);     // ... this launch (waits for the stream on a hit)
+// what nmi_last_error_detail says after a call that was redone because of such a timeout (the call itself succeeded)
+extern const char *const kSplitTimeoutNote, *const kSplitTimeoutTicketNote, *const kSplitTimeoutTicketLost;
 // nmi_search_grid_block without the argument checks; caller_checks: the caller looks for a split timeout itself, so small
 // grids may use the split kernel although the call only enqueues (h_key == nullptr)
 int search_block(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_local, int32_t s_offset, int32_t S_total, const uint8_t *warp_stack,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nmi_search_plan.h"
+
 #define NMI_BLOCK_THREADS 1024
 #define NMI_MODE_ENMI_ 0  // Thirdparty/CUDA_Functions/kernel.cuh:22
 #define NMI_MODE_SUC_ 1   // Thirdparty/CUDA_Functions/kernel.cuh:23
@@ -139,7 +141,6 @@ struct SplitSlab {
 // pix_parts (1, 2 or 4; > 1 only with parts = 8): the pixels of the pair are additionally cut into that many ranges, one
 // workgroup per (row part, pixel range); the workgroups of a row part merge their counters through `blocks`.
 hipError_t launch_split(const GridArgs &a, int parts, int pix_parts, int workgroups, bool use_bg, hipStream_t stream);
-__host__ __device__ int split_workgroups(int candidates, int parts, int pix_parts);  // grid size of a split launch (one unit per workgroup)
 inline size_t split_block_bytes_per_candidate(int pix_parts) { return (size_t)pix_parts * 256 * 128 * sizeof(unsigned long long); }
 // Pixel-range form for mid-size grids (nmi_pix_kernel.hip): pix_parts workgroups per candidate, each adding a range of the
 // pair's pixels into a whole packed joint histogram; the helpers' histograms travel to the candidate's owner through
@@ -149,7 +150,6 @@ inline size_t split_block_bytes_per_candidate(int pix_parts) { return (size_t)pi
 // owner_share: fraction of the pair's pixels the owner adds itself (the helpers share the rest equally).
 hipError_t launch_pix(const GridArgs &a, int pix_parts, double owner_share, bool use_bg, const uint32_t *replay, uint32_t *timeouts, hipStream_t stream);
 size_t pix_block_bytes(int candidates, int pix_parts);
-int pix_max_ranges();
 int grid_kernel_lds_bytes();
 size_t grid_kernel_scratch_bytes(int workgroups);
 hipError_t launch_warp(const uint8_t *frame, const float *coeffs /*[Wn][9] inverse maps*/, uint8_t *out, int width,

@@ -43,7 +43,6 @@
 namespace nmi {
 
 size_t pix_block_bytes(int candidates, int pix_parts) { return (size_t)candidates * (size_t)(pix_parts - 1) * kPixBlockBytes; }
-int pix_max_ranges() { return kMaxRanges; }
 
 template <bool ZERO0, bool SHIFTED>
 __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, int P, DealArgs dealing, const uint32_t *replay, uint32_t *timeouts)

@@ -494,7 +494,6 @@ __device__ __forceinline__ void final_split(const SplitLds<K> &lds, const GridAr
 //     every XCD's L2 serves a share of the pixel stream.  (One pair: 32 workgroups instead of 256 dispatched, 1.2 us
 //     less per blocking call; the same 32 workgroups dealt without regard to XCDs finish 1-6 us later.)
 // Placement is a speed matter only.
-__host__ __device__ inline bool split_exact_grid(int total, int parts) { return total < 8 && parts == 8; }  // (row part j on XCD j needs 8 of them)
 __device__ __forceinline__ void split_unit(int u, int total, int parts, int pix_parts, int &cand, int &part, int &pix_part)
 {
     if (split_exact_grid(total, parts)) {
@@ -689,11 +688,6 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_split_kernel(GridArgs a
         const GridArgs a = fresh();
         if (a.dbg_stamps && tid == 0) a.dbg_stamps[blockIdx.x * 8 + 7] = (unsigned long long)(clock64() - clk0);
     }
-}
-
-__host__ __device__ int split_workgroups(int candidates, int parts, int pix_parts)
-{
-    return (split_exact_grid(candidates, parts) ? candidates : ((candidates + 7) / 8) * 8) * parts * pix_parts;
 }
 
 template <int K, int P>
