@@ -848,9 +848,18 @@ int nmi_split_status(nmi_ctx *ctx, int32_t *timeouts, int32_t *cooldown_calls_le
  * and a rank's share of a sharded 729-candidate grid) are scored by P workgroups per candidate, each adding a range of the
  * pair's PIXELS into a histogram of its own (csrc/nmi_pix_kernel.hip); bit-identical results; no residence condition, so
  * enqueue-only calls use it too.  *last_launch_ranges = P of the most recent launch (0: another kernel scored it);
- * *healed = candidates so far whose owner gave up waiting for a helper (2 ms) and scored them alone -- nothing for the
- * host to redo.  Waits for the context's stream when healed is asked for.  Any pointer may be null. */
+ * *healed = candidates so far that their owner scored once more, alone, inside the launch -- nothing for the host to redo.
+ * What it counts depends on the form: plain searches add the candidates whose owner gave up waiting for a helper (2 ms)
+ * and nothing else; masked and covered searches add those AND the candidates whose merged counters failed the count test
+ * (a 16-bit field wrapped).  nmi_pix_heal_counts tells the two causes apart for every form.  Waits for the context's
+ * stream when healed is asked for.  Any pointer may be null. */
 int nmi_pix_status(nmi_ctx *ctx, int32_t *last_launch_ranges, int32_t *healed);
+/* The two causes of such a heal, candidates so far on this context, over plain, masked and covered searches alike (those
+ * inside captured levels and stream tickets included): *timeouts = owners that gave up waiting for a helper; *count_test =
+ * merged decodes whose total was not the number of pixels added (W*H / the masked pixels / the covered pixels): a wrapped
+ * 16-bit field -- or, on content that cannot wrap one, a hand-off that was read stale.  Waits for the context's stream.
+ * Any pointer may be null. */
+int nmi_pix_heal_counts(nmi_ctx *ctx, int32_t *timeouts, int32_t *count_test);
 
 /* Introspection. */
 /* Copies the context's per-count term table, term[c] = (c/len) * log2(c/len) in the reference's fp32 form with

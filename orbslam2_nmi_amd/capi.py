@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "nmi_stream_submit", "nmi_stream_wait", "nmi_stream_keep_ratings", "nmi_stream_copy_ratings", "nmi_key_pack", "nmi_key_unpack", "nmi_search_grid_rccl", "nmi_search_grid_block_rccl",
     "nmi_rccl_unique_id", "nmi_rccl_comm_init", "nmi_rccl_comm_destroy", "nmi_set_profiling", "nmi_last_kernel_ms",
     "nmi_set_option", "nmi_copy_term_table", "nmi_abi_version", "nmi_error_string", "nmi_last_error_detail", "nmi_get_info", "nmi_last_content", "nmi_sort_points", "nmi_sort_triangles",
-    "nmi_split_status", "nmi_pix_status", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
+    "nmi_split_status", "nmi_pix_status", "nmi_pix_heal_counts", "nmi_level_create_block", "nmi_level_create_mesh_block", "nmi_level_run_rccl", "nmi_stream_submit_block",
     "nmi_warp_stack_masked", "nmi_search_grid_masked", "nmi_last_mask_counts", "nmi_level_set_masks", "nmi_level_copy_masks",
     "nmi_render_points_masked", "nmi_render_mesh_masked", "nmi_search_grid_covered", "nmi_last_cover_counts",
     "nmi_level_set_coverage", "nmi_level_copy_coverage",
@@ -177,6 +177,7 @@ def load_library(build_if_missing=False):
     lib.nmi_last_content.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.nmi_split_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.nmi_pix_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    lib.nmi_pix_heal_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     lib.nmi_sort_points.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.nmi_sort_triangles.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     _lib = lib
@@ -387,6 +388,13 @@ class NmiContext:
         v = [C.c_int32(0) for _ in range(2)]
         self._check(self._lib.nmi_pix_status(self._h, *[C.byref(x) for x in v]), "nmi_pix_status")
         return dict(zip(("last_launch_ranges", "healed"), (x.value for x in v)))
+
+    def pix_heal_counts(self):
+        """Why the pixel-range kernels scored candidates once more, so far on this context -> {"timeouts", "count_test"}
+        (nmi_pix_heal_counts; waits for the stream)."""
+        v = [C.c_int32(0) for _ in range(2)]
+        self._check(self._lib.nmi_pix_heal_counts(self._h, *[C.byref(x) for x in v]), "nmi_pix_heal_counts")
+        return dict(zip(("timeouts", "count_test"), (x.value for x in v)))
 
     def term_table(self):
         """The per-count entropy-term table (NMI.cu:242-263 evaluated once per possible count) as numpy float32 [W*H+1]."""

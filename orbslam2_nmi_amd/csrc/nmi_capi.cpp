@@ -106,8 +106,8 @@ double pix_owner_share(const nmi_ctx *ctx, int pix)
 static int ensure_pix_timeouts(nmi_ctx *ctx)
 {
     if (ctx->d_pix_timeouts) return NMI_OK;
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pix_timeouts, sizeof(uint32_t)));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_timeouts, 0, sizeof(uint32_t), ctx->stream));
+    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pix_timeouts, nmi::kPixHealWords * sizeof(uint32_t)));
+    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_timeouts, 0, nmi::kPixHealWords * sizeof(uint32_t), ctx->stream));
     return NMI_OK;
 }
 
@@ -891,20 +891,38 @@ int nmi_split_status(nmi_ctx *ctx, int32_t *timeouts, int32_t *cooldown_calls_le
     return NMI_OK;
 }
 
+// the pixel-range kernels' heal counters so far (kPixHeal*; zeros before the first such launch); waits for the stream
+static int read_pix_heal(nmi_ctx *ctx, uint32_t (&n)[nmi::kPixHealWords])
+{
+    for (uint32_t &x : n) x = 0;
+    if (!ctx->d_pix_timeouts) return NMI_OK;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(n, ctx->d_pix_timeouts, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NMI_OK;
+}
+
 int nmi_pix_status(nmi_ctx *ctx, int32_t *last_launch_ranges, int32_t *healed)
 {
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
     if (last_launch_ranges) *last_launch_ranges = ctx->last.pix;
     if (healed) {
-        *healed = 0;
-        if (ctx->d_pix_timeouts) {
-            DeviceGuard guard(ctx->device);
-            uint32_t n = 0;
-            NMI_HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->d_pix_timeouts, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
-            NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            *healed = (int32_t)n;
-        }
+        uint32_t n[nmi::kPixHealWords];
+        const int rc = read_pix_heal(ctx, n);
+        if (rc != NMI_OK) return rc;
+        *healed = (int32_t)n[nmi::kPixHealed];
     }
+    return NMI_OK;
+}
+
+int nmi_pix_heal_counts(nmi_ctx *ctx, int32_t *timeouts, int32_t *count_test)
+{
+    if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
+    uint32_t n[nmi::kPixHealWords];
+    const int rc = read_pix_heal(ctx, n);
+    if (rc != NMI_OK) return rc;
+    if (timeouts) *timeouts = (int32_t)n[nmi::kPixHealTimeouts];
+    if (count_test) *count_test = (int32_t)n[nmi::kPixHealCountTest];
     return NMI_OK;
 }
 

@@ -27,7 +27,8 @@
 //     launch_grid_covered.
 //   * Heal.  A candidate that fails the count test, or whose helper did not arrive within the bounded wait, is scored by its
 //     owner alone on the covered exact path (covered_histogram_phase with returning atomics + wrap bookkeeping,
-//     covered_decode_phase, covered_final_phase) inside the launch; both are counted in *healed (nmi_pix_status().healed).
+//     covered_decode_phase, covered_final_phase) inside the launch; both are counted in healed[kPixHealed] (nmi_pix_status().healed) and each under its
+//     cause (nmi_pix_heal_counts).
 //   * Shapes.  Rows need not be whole aligned chunks: the dealt chunks take nmi_pix_kernel's unaligned-row addressing for the
 //     frame, the render and both masks alike (the render mask in the render's row order), and the owner adds the rows' last
 //     width % 16 pixels one by one (frames of at least 32 pixels of width, e.g. 1241 x 376).
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_pix_kernel(Cove
     }
     if (alone) {
         // cold: this candidate once more, by this workgroup alone, on the covered exact path
-        if (tid == 0 && healed) __hip_atomic_fetch_add(healed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0 && healed) pix_count_heal(healed, lds.fallback != 0, true);
         __syncthreads();
         clear_counters(lds, tid);
         __syncthreads();

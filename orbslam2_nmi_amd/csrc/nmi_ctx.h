@@ -55,7 +55,7 @@ struct nmi_ctx {
     int last_slot = 0;                     // key slot of the most recent launch
     SearchLaunch last;                     // the most recent launch (written by commit_launch only)
     int pix_owner_bias = 49152;            // NMI_OPT_PIX_OWNER_BIAS: pixels the owner of a candidate adds beyond an equal share
-    uint32_t *d_pix_timeouts = nullptr;    // candidates whose owner gave up on a helper and scored them alone (nmi_pix_kernel)
+    uint32_t *d_pix_timeouts = nullptr;    // the pixel-range kernels' heal counters [kPixHealWords] (nmi_kernels.h): healed, timeouts, count-test redos
     // Split-kernel liveness (nmi_split_kernel.hip: its consumers spin, so a launch whose workgroups are not all resident
     // times out after 2 ms).  A timeout is attributed to ITS launch (epoch), that search is redone by nmi_grid_kernel, and the
     // split forms stay off for split_cooldown further small-grid launches -- 16, doubling per consecutive timeout up to

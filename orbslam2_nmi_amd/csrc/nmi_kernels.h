@@ -144,12 +144,15 @@ hipError_t launch_split(const GridArgs &a, int parts, int pix_parts, int workgro
 inline size_t split_block_bytes_per_candidate(int pix_parts) { return (size_t)pix_parts * 256 * 128 * sizeof(unsigned long long); }
 // Pixel-range form for mid-size grids (nmi_pix_kernel.hip): pix_parts workgroups per candidate, each adding a range of the
 // pair's pixels into a whole packed joint histogram; the helpers' histograms travel to the candidate's owner through
-// a.blocks (pix_block_bytes, zero when allocated; tag from a.epoch + *replay).  *timeouts counts candidates whose owner
-// gave up waiting and scored them alone (the launch heals itself).  Needs width >= 32 (rows need not be whole aligned
-// chunks), a.order == nullptr, a.epoch != 0.
+// a.blocks (pix_block_bytes, zero when allocated; tag from a.epoch + *replay).  timeouts points at the kPixHealWords heal
+// counters all three pixel-range kernels share (the launch heals itself; nmi_pix_status, nmi_pix_heal_counts).  Needs
+// width >= 32 (rows need not be whole aligned chunks), a.order == nullptr, a.epoch != 0.
 // owner_share: fraction of the pair's pixels the owner adds itself (the helpers share the rest equally).
 hipError_t launch_pix(const GridArgs &a, int pix_parts, double owner_share, bool use_bg, const uint32_t *replay, uint32_t *timeouts, hipStream_t stream);
 size_t pix_block_bytes(int candidates, int pix_parts);
+// The heal counters of the pixel-range kernels, candidates each: what nmi_pix_status calls healed (the plain kernel: timeouts;
+// the masked and the covered one: both causes), owners that gave up waiting for a helper, merged decodes that failed the count test.
+enum { kPixHealed = 0, kPixHealTimeouts = 1, kPixHealCountTest = 2, kPixHealWords = 3 };
 int grid_kernel_lds_bytes();
 size_t grid_kernel_scratch_bytes(int workgroups);
 hipError_t launch_warp(const uint8_t *frame, const float *coeffs /*[Wn][9] inverse maps*/, uint8_t *out, int width,

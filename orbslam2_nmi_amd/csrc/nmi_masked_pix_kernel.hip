@@ -21,7 +21,8 @@
 //     counts); helpers' side counters are therefore always empty and are not handed over.
 //   * Heal.  A candidate that fails the count test, or whose helper did not arrive within the bounded wait, is scored by its
 //     owner alone on the masked exact path (masked_histogram_phase with returning atomics + wrap bookkeeping, decode_phase,
-//     final_phase) inside the launch; both are counted in *healed (nmi_pix_status().healed).
+//     final_phase) inside the launch; both are counted in healed[kPixHealed] (nmi_pix_status().healed) and each under its
+//     cause (nmi_pix_heal_counts).
 //   * Tables.  The owner decodes with tables + w * (npix + 1) (its LDS copy of the low entries loaded once: one candidate per
 //     workgroup).
 //   * Shapes.  Rows need not be whole aligned chunks: the dealt chunks take nmi_pix_kernel's unaligned-row addressing for the
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_pix_kernel(Maske
     }
     if (alone) {
         // cold: this candidate once more, by this workgroup alone, on the masked exact path
-        if (tid == 0 && healed) __hip_atomic_fetch_add(healed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0 && healed) pix_count_heal(healed, lds.fallback != 0, true);
         __syncthreads();
         clear_counters(lds, tid);
         __syncthreads();

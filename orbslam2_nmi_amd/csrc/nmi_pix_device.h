@@ -110,6 +110,15 @@ __device__ __forceinline__ void clear_counters(Lds &lds, int tid)
     if (tid == 0) lds.fallback = 0;
 }
 
+// An owner's heal, counted by one thread on its way into the cold branch (kPixHeal*, nmi_kernels.h): why the candidate is scored
+// once more -- the wait for a helper was given up, or the merged decode failed the count test -- and the sum nmi_pix_status
+// reports, which for the plain kernel (!BOTH) has only ever held the timeouts.
+__device__ __forceinline__ void pix_count_heal(uint32_t *counters, bool gave_up, bool both)
+{
+    if (gave_up || both) __hip_atomic_fetch_add(counters + kPixHealed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(counters + (gave_up ? kPixHealTimeouts : kPixHealCountTest), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // the workgroup's added pixels into *dst (LDS, zero before)
 __device__ __forceinline__ void add_count(uint32_t *dst, uint32_t n, int lane)
 {

@@ -20,9 +20,12 @@
 // (AddVectorPairwiseKernel, NMI.cu:290-363), rating store, arg-max, completion.  Results are bit-identical.
 //   * Counter wraps: a wrapped 16-bit field always LOSES weight, in a helper, in the owner or in the merge, so the sum of all
 //     decoded counters still equals W*H iff nothing wrapped; a candidate that fails is redone by its owner alone on the exact
-//     path (exact_candidate), as in nmi_grid_kernel.
+//     path (exact_candidate), as in nmi_grid_kernel, and counted in timeouts[kPixHealCountTest] (nmi_pix_heal_counts:
+//     count_test).  A unit, side counter or mask read stale makes the total fall short in the same way: on content that cannot
+//     wrap a field, that counter is how a bad hand-off shows, for the bits come out right either way.
 //   * Liveness: helpers never wait, and the owner's wait is bounded: should a helper's flag not arrive within 2 ms
-//     (kPixTimeoutTicks), the owner scores the candidate alone on the exact path and counts the event in *timeouts.  That
+//     (kPixTimeoutTicks), the owner scores the candidate alone on the exact path and counts the event in
+//     timeouts[kPixHealTimeouts] (nmi_pix_heal_counts: timeouts) and in timeouts[kPixHealed] (nmi_pix_status: healed).  That
 //     bounded wait and the in-launch heal are the guarantee -- the launch always completes and heals itself, the host has
 //     nothing to redo -- which is why this form may also be used by calls that only enqueue.  The helpers are the FIRST
 //     total * (P - 1) workgroups of the launch, so they usually run before or beside their owners; but each XCD dispatches
@@ -104,10 +107,11 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_pix_kernel(GridArgs a, 
         alone = lds.total[0] != (uint32_t)a.npix;  // some 16-bit field wrapped (workgroup-uniform, rare)
         if (!alone && wave == 0) final_phase_owner(lds, a, lane, p, w, s, prev_key);
     } else if (tid == 0 && timeouts) {
-        __hip_atomic_fetch_add(timeouts, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pix_count_heal(timeouts, true, false);  // a wait was given up
     }
     if (alone) {
         // cold: this candidate once more, by this workgroup alone, on the exact path
+        if (tid == 0 && timeouts && lds.fallback == 0) pix_count_heal(timeouts, false, false);  // the count test failed
         __syncthreads();
         clear_counters(lds, tid);
         __syncthreads();

@@ -8,6 +8,7 @@ import pytest
 
 from helpers import covered_np as cnp
 from helpers import masked_np as mnp
+from helpers import pix_ranges_np as prn
 from orbslam2_nmi_amd import capi, synthetic as sy
 
 torch = pytest.importorskip("torch")
@@ -30,7 +31,7 @@ def bits(x):
 
 
 def covered(rs, ws, wm, rm, bottom_up=True, options=None, use_bg=True):
-    """-> (ratings, index, score, counts, pix_status) of one nmi_search_grid_covered on a fresh context."""
+    """-> (ratings, index, score, counts, pix_status + pix_heal_counts, compute units) of one nmi_search_grid_covered on a fresh context."""
     S, Wn = rs.shape[0], ws.shape[0]
     h, w = rs.shape[1:]
     with capi.NmiContext(w, h, render_bottom_up=bottom_up, use_bg=use_bg) as ctx:
@@ -39,7 +40,7 @@ def covered(rs, ws, wm, rm, bottom_up=True, options=None, use_bg=True):
         t = torch.full((Wn, S), -3.0, device="cuda")
         idx, best = ctx.search_grid_covered(dev(rs), dev(rm), dev(ws), dev(wm), t)
         counts = ctx.cover_counts(S * Wn).reshape(Wn, S)
-        st = ctx.pix_status()
+        st = {**ctx.pix_status(), **ctx.pix_heal_counts()}
         cus = ctx.info()["compute_units"]
     return t.cpu().numpy(), idx, best, counts, st, cus
 
@@ -108,7 +109,9 @@ def wrap_stacks(w, h):
 
 def test_counter_wraps_heal_in_the_covered_pixel_range_kernel():
     """Bins of ~70,000 hits under masks that keep most pixels wrap in helpers, owners and merges; the count test (decoded total
-    != len) sends those candidates to the covered exact path inside the launch: the same bits, healed > 0."""
+    != len) sends those candidates to the covered exact path inside the launch: the same bits, healed > 0 -- and exactly the
+    candidates with a bin above 65,535 in the owner's share of the covered pixels or in the helpers' shares together
+    (tests/helpers/pix_ranges_np.py), all of them count-test redos, none a timeout."""
     w, h = 640, 480
     rs, ws = wrap_stacks(w, h)
     wm = np.ones((2, h, w), np.uint8)
@@ -123,6 +126,8 @@ def test_counter_wraps_heal_in_the_covered_pixel_range_kernel():
         opts = {capi.NmiContext.OPT_SPLIT: 1, capi.NmiContext.OPT_SPLIT_PIXELS: ranges}
         got, idx, best, counts, st, _ = covered(rs, ws, wm, rm, False, opts)
         assert st["last_launch_ranges"] == ranges and st["healed"] > 0, st
+        redos = prn.count_test_redos(rs, ws, ranges, False, keep=lambda v, s: cnp.pair_mask(wm[v], rm[s], False))
+        assert redos > 0 and (st["healed"], st["timeouts"], st["count_test"]) == (redos, 0, redos), (st, redos)
         assert (idx, bits(best)) == (wi, bits(wb)), ranges
         assert (bits(got) == bits(want)).all(), ranges
         assert (counts == wc).all()
@@ -142,6 +147,7 @@ def test_a_missing_helper_is_healed_inside_the_launch():
         ctx.set_option(ctx.OPT_SPLIT_PIXELS, 3)
         assert ctx.search_grid_covered(rs, drm, ws, dwm) == (wi, wb)
         assert ctx.pix_status() == {"last_launch_ranges": 3, "healed": 0}
+        assert ctx.pix_heal_counts() == {"timeouts": 0, "count_test": 0}
         ctx.set_option(ctx.OPT_PHASE_MASK, 3 | 512)
         t = torch.zeros((Wn, S), device="cuda")
         t0 = time.perf_counter()
@@ -150,10 +156,12 @@ def test_a_missing_helper_is_healed_inside_the_launch():
         assert (bits(t.cpu().numpy()) == bits(want)).all()
         assert (ctx.cover_counts(S * Wn).reshape(Wn, S) == wc).all()
         assert ctx.pix_status() == {"last_launch_ranges": 3, "healed": S * Wn}
+        assert ctx.pix_heal_counts() == {"timeouts": S * Wn, "count_test": 0}
         ctx.set_option(ctx.OPT_PHASE_MASK, 3)
         assert ctx.search_grid_covered(rs, drm, ws, dwm, t) == (wi, wb)
         assert (bits(t.cpu().numpy()) == bits(want)).all()
         assert ctx.pix_status()["healed"] == S * Wn
+        assert ctx.pix_heal_counts() == {"timeouts": S * Wn, "count_test": 0}
 
 
 def test_empty_and_all_ones_masks():

@@ -105,6 +105,7 @@ def test_small_frames_on_forced_ranges(device, frame, grid, setting):
             for form in FORMS:
                 got = search(ctx, form, d, S, Wn)
                 assert ctx.pix_status() == {"last_launch_ranges": P, "healed": 0}, (form, P)
+                assert ctx.pix_heal_counts() == {"timeouts": 0, "count_test": 0}, (form, P)  # (no field can wrap: a redo would be a stale hand-off)
                 check(got, want[form], (form, P))
 
 
@@ -123,4 +124,5 @@ def test_a_withheld_hand_off_heals_on_a_frame_of_one_piece(device, form):
         ctx.set_option(ctx.OPT_PHASE_MASK, 3 | 512)
         got = search(ctx, form, d, S, Wn)
         assert ctx.pix_status() == {"last_launch_ranges": 3, "healed": S * Wn}
+        assert ctx.pix_heal_counts() == {"timeouts": S * Wn, "count_test": 0}
         check(got, want, form)

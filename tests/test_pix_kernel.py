@@ -76,8 +76,15 @@ def test_counter_wraps_in_helpers_owner_and_merge(nmi):
     """640x480, two intensities per image in a fine pattern (no flat chunks): bins of 76,800 hits.  With 2 ranges each
     workgroup stays below 65,536 per bin and only the MERGE wraps; with the whole pair in one bin pattern shifted, helpers
     and owner wrap on their own.  Either way the detector (sum of decoded counters != W*H) sends the candidate to the exact
-    path and the scores equal the oracle's."""
+    path and the scores equal the oracle's.
+    Both heal counters are pinned: no owner gives up a wait, and the count-test redos are exactly the candidates in which a
+    field must wrap.  The content has no flat chunks and no zeros, so every pixel lands in a 16-bit field: of the 64
+    candidates all have a bin above 65,535 in their joint histogram (the least: 76,800), and a field can only wrap in those;
+    but a candidate's hits are spread over its P workgroups and the owner adds its own fields to its helpers' in 32 bits, so
+    the ones that DO wrap are those with such a bin in the owner's share or in the helpers' shares taken together
+    (tests/helpers/pix_ranges_np.py, from the dealing): the 32 candidates of the second warp, at 2, 3 and 4 ranges alike."""
     from oracle import binding as oc
+    from helpers import pix_ranges_np as prn
     w, h = 640, 480
     yy, xx = np.mgrid[0:h, 0:w]
     a = np.where((xx + yy) % 2 == 0, 10, 200).astype(np.uint8)
@@ -87,13 +94,21 @@ def test_counter_wraps_in_helpers_owner_and_merge(nmi):
     ws = np.stack([b, c])
     with oc.rounded():
         ro, io, bo = oc.search_grid(rs, ws, render_bottom_up=False, threads=16)
+    joint_max = [np.bincount(rs[s].ravel().astype(np.int64) * 256 + ws[v].ravel(), minlength=65536).max() for v in range(2) for s in range(32)]
+    over_16_bits = sum(int(m > 65535) for m in joint_max)
+    assert over_16_bits == 64 and min(joint_max) == 76800
     for ranges in (2, 3, 4):
+        redos = prn.count_test_redos(rs, ws, ranges, render_bottom_up=False)
+        assert 0 < redos <= over_16_bits
         with nmi.NmiContext(w, h, render_bottom_up=False) as ctx:
             ctx.set_option(ctx.OPT_SPLIT, 1)
             ctx.set_option(ctx.OPT_SPLIT_PIXELS, ranges)
             t = torch.zeros((2, 32), device="cuda")
             got = ctx.search_grid(dev(rs), dev(ws), t)
             assert ctx.pix_status() == {"last_launch_ranges": ranges, "healed": 0}
+            counts = ctx.pix_heal_counts()
+            print(f"ranges {ranges}: {counts}, model {redos}, candidates with a bin above 16 bits {over_16_bits}")
+            assert counts == {"timeouts": 0, "count_test": redos}, ranges
         assert got == (io, bo), ranges
         assert (t.cpu().numpy().view(np.uint32) == ro.view(np.uint32)).all(), ranges
 
@@ -146,9 +161,11 @@ def test_a_missing_helper_is_healed_inside_the_launch(nmi):
         assert time.perf_counter() - t0 < 0.05
         assert (t.cpu().numpy().view(np.uint32) == ro.view(np.uint32)).all()
         assert ctx.pix_status() == {"last_launch_ranges": 3, "healed": 45}
+        assert ctx.pix_heal_counts() == {"timeouts": 45, "count_test": 0}
         ctx.set_option(ctx.OPT_PHASE_MASK, 3)
         assert ctx.search_grid(rs, ws) == (io, bo)          # the stale blocks of the failed launch carry an old tag
         assert ctx.pix_status()["healed"] == 45
+        assert ctx.pix_heal_counts() == {"timeouts": 45, "count_test": 0}
 
 
 def test_enqueue_only_calls_and_repeated_launches(nmi):
@@ -170,11 +187,13 @@ def test_enqueue_only_calls_and_repeated_launches(nmi):
             assert capi.key_unpack(int(k)) == (io, bo)
 
 
-def test_captured_level_with_a_mid_size_grid(nmi):
-    """nmi_level_* (one search level as a captured HIP graph): a 9 x 9 level's search is the pixel-range kernel inside the graph.
-    A replayed graph's arguments are frozen, so the hand-off tag comes from the epoch captured + the replay count the level's
-    prep kernel keeps in device memory: eight replays with different views and warps, every rating table == the oracle's on the
-    stacks that replay produced (a stale block taken for a fresh one would show at once), for a point cloud and a textured mesh."""
+def replay_captured_mid_size_level(nmi, replays, scale_of, frame_shifts=((0.05, 0, 0),)):
+    """A 9 x 9 point-cloud level at 320 x 240 (nmi_level_*: one search level as a captured HIP graph), replayed `replays` times:
+    replay `rep` takes its views and warps from a search kernel of steps / scale_of(rep), and its camera frame -- the graph reads
+    it in place -- from the view shifted by frame_shifts[rep % len(frame_shifts)].  Every replay's rating table must == the
+    oracle's on the stacks that replay produced, and its winner the oracle's.  -> the context's pix_status() and
+    pix_heal_counts() after the last replay, merged, and "largest_bin_bound": no joint histogram of any replay has a bin above
+    it (a bin holds at most the pixels of its intensity in the render, and in the warp)."""
     from oracle import binding as oc
     from orbslam2_nmi_amd import capi, hostapi as H, synthetic as sy
     import sys, os
@@ -189,10 +208,16 @@ def test_captured_level_with_a_mid_size_grid(nmi):
     K = sy.intrinsics(w, h)
     with nmi.NmiContext(w, h) as ctx:
         dx, dr = torch.from_numpy(xyz).cuda(), torch.from_numpy(red).cuda()
-        frame = torch.flip(ctx.render_points(dx, torch.sqrt(dr), capi.render_mvp(rp, pos, look, up, (0.05, 0, 0))[None], 3.0)[0], dims=[0]).contiguous()
+        frames = [torch.flip(ctx.render_points(dx, torch.sqrt(dr), capi.render_mvp(rp, pos, look, up, shift)[None], 3.0)[0], dims=[0]).contiguous()
+                  for shift in frame_shifts]
+        frame = frames[0].clone()
+        bound = 0
         with nmi.NmiLevel(ctx, dx, dr, frame, 9, 9, 3.0) as lv:
-            for rep in range(8):
-                g = H.SearchKernel.make([3, 3, 1, 3, 3, 1], [s / (1 + 0.3 * rep) for s in (0.2, 0.2, 0.5, 0.02, 0.02, 0.05)])
+            for rep in range(replays):
+                if len(frames) > 1:
+                    frame.copy_(frames[rep % len(frames)])
+                    torch.cuda.current_stream().synchronize()
+                g = H.SearchKernel.make([3, 3, 1, 3, 3, 1], [s / scale_of(rep) for s in (0.2, 0.2, 0.5, 0.02, 0.02, 0.05)])
                 mvps = np.stack([capi.render_mvp(rp, pos, look, up, H.calculate_translation(Twc, g, *c)) for c in cells])
                 Ms = capi.warp_homographies(K, (3, 3, 1), tuple(g.step[3:6]))
                 win = lv.run(mvps, Ms)
@@ -201,4 +226,16 @@ def test_captured_level_with_a_mid_size_grid(nmi):
                     ro, io, bo = oc.search_grid(rs, ws, render_bottom_up=True, threads=16)
                 assert (table.view(np.uint32) == ro.view(np.uint32)).all(), rep
                 assert win == (io, bo), rep
-        assert ctx.pix_status()["healed"] == 0
+                fullest = lambda stack: max(int(np.bincount(img.ravel(), minlength=256).max()) for img in stack)
+                bound = max(bound, min(fullest(rs), fullest(ws)))
+        return {**ctx.pix_status(), **ctx.pix_heal_counts(), "largest_bin_bound": bound}
+
+
+def test_captured_level_with_a_mid_size_grid(nmi):
+    """nmi_level_* (one search level as a captured HIP graph): a 9 x 9 level's search is the pixel-range kernel inside the graph.
+    A replayed graph's arguments are frozen, so the hand-off tag comes from the epoch captured + the replay count the level's
+    prep kernel keeps in device memory: eight replays with different views and warps, every rating table == the oracle's on the
+    stacks that replay produced (a stale block taken for a fresh one would show at once), for a point cloud and a textured mesh."""
+    st = replay_captured_mid_size_level(nmi, 8, lambda rep: 1 + 0.3 * rep)
+    assert st["healed"] == 0
+    assert (st["timeouts"], st["count_test"]) == (0, 0)
