@@ -46,30 +46,23 @@ int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order)
     for (auto &e : ctx->orders) {
         if (e.S == S && e.Wn == Wn) {
             e.last_use = ++ctx->order_clock;
-            *d_order = e.d;
+            *d_order = e.d.as<int>();
             return NMI_OK;
         }
-        if (!victim || (e.d == nullptr && victim->d != nullptr) || ((e.d == nullptr) == (victim->d == nullptr) && e.last_use < victim->last_use))
-            victim = &e;
+        if (!victim || (!e.d && victim->d) || (!e.d == !victim->d && e.last_use < victim->last_use)) victim = &e;
     }
     nmi_ctx::OrderEntry &e = *victim;
     if (e.d) NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // eviction: the old table / staging copy may be in use
-    if (total > e.cap) {
-        if (e.d) NMI_HIP_TRY(ctx, hipFree(e.d));
-        if (e.h) NMI_HIP_TRY(ctx, hipHostFree(e.h));
-        e.d = e.h = nullptr;
-        e.cap = 0;
-        e.S = e.Wn = -1;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&e.d, (size_t)total * sizeof(int)));
-        NMI_HIP_TRY(ctx, hipHostMalloc((void **)&e.h, (size_t)total * sizeof(int), hipHostMallocDefault));
-        e.cap = total;
-    }
-    build_order(S, Wn, e.h);
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(e.d, e.h, (size_t)total * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    e.S = e.Wn = -1;
+    const size_t bytes = (size_t)total * sizeof(int);
+    NMI_HIP_TRY(ctx, e.d.grow(bytes));  // (waited above)
+    NMI_HIP_TRY(ctx, e.h.grow(bytes, nmi_mem::kPinned));
+    build_order(S, Wn, e.h.as<int>());
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(e.d.as<int>(), e.h.as<int>(), bytes, hipMemcpyHostToDevice, ctx->stream));
     e.S = S;
     e.Wn = Wn;
     e.last_use = ++ctx->order_clock;
-    *d_order = e.d;
+    *d_order = e.d.as<int>();
     return NMI_OK;
 }
 
@@ -105,9 +98,7 @@ double pix_owner_share(const nmi_ctx *ctx, int pix)
 
 static int ensure_pix_timeouts(nmi_ctx *ctx)
 {
-    if (ctx->d_pix_timeouts) return NMI_OK;
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pix_timeouts, nmi::kPixHealWords * sizeof(uint32_t)));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_timeouts, 0, nmi::kPixHealWords * sizeof(uint32_t), ctx->stream));
+    NMI_HIP_TRY(ctx, ctx->d_pix_timeouts.grow(nmi::kPixHealWords * sizeof(uint32_t), ctx->stream, /*zero=*/true));
     return NMI_OK;
 }
 
@@ -118,9 +109,9 @@ static int next_split_epoch(nmi_ctx *ctx, uint32_t *epoch)
 {
     uint32_t e = ctx->split_epoch + 1;
     if ((e & 0xFFFFu) == 0) {
-        if (ctx->d_blocks) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_blocks, 0, ctx->blocks_bytes, ctx->stream));
-        if (ctx->d_pix_blocks) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_blocks, 0, ctx->pix_blocks_bytes, ctx->stream));  // (its tags: 31 bits)
-        if (e == 0 && ctx->d_slabs) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_slabs, 0, (size_t)ctx->slab_cap * sizeof(nmi::SplitSlab), ctx->stream));
+        if (ctx->d_blocks) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_blocks.as<>(), 0, ctx->d_blocks.size(), ctx->stream));
+        if (ctx->d_pix_blocks) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_pix_blocks.as<>(), 0, ctx->d_pix_blocks.size(), ctx->stream));  // (its tags: 31 bits)
+        if (e == 0 && ctx->d_slabs) NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_slabs.as<>(), 0, ctx->d_slabs.size(), ctx->stream));
         ++e;
     }
     ctx->split_epoch = *epoch = e;
@@ -139,27 +130,10 @@ int prepare_pix_handoff(nmi_ctx *ctx, uint32_t *epoch)
 // A hand-off buffer of at least `bytes`, zero when allocated (tag / epoch 0 = never written); growing waits for the stream.  The
 // pixel-range kernels' blocks are a buffer of their own: the row-split kernel tags its granules with 16 bits in the top of an
 // 8-byte word, which a packed counter of the other kernel's layout can equal.
-static int ensure_zeroed(nmi_ctx *ctx, void **buf, size_t *have, size_t bytes)
+static int ensure_zeroed(nmi_ctx *ctx, DeviceBuffer &buf, size_t bytes)
 {
-    if (bytes <= *have) return NMI_OK;
-    if (*buf) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        NMI_HIP_TRY(ctx, hipFree(*buf));
-        *buf = nullptr;
-        *have = 0;
-    }
-    NMI_HIP_TRY(ctx, hipMalloc(buf, bytes));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(*buf, 0, bytes, ctx->stream));
-    *have = bytes;
+    NMI_HIP_TRY(ctx, buf.grow(bytes, ctx->stream, /*zero=*/true));
     return NMI_OK;
-}
-
-static int ensure_slabs(nmi_ctx *ctx, int n)
-{
-    size_t have = (size_t)ctx->slab_cap * sizeof(nmi::SplitSlab);
-    const int rc = ensure_zeroed(ctx, (void **)&ctx->d_slabs, &have, (size_t)(n > 128 ? n : 128) * sizeof(nmi::SplitSlab));
-    ctx->slab_cap = (int)(have / sizeof(nmi::SplitSlab));
-    return rc;
 }
 
 int prepare_search(nmi_ctx *ctx, const nmi::SearchPlan &plan, nmi::GridArgs &a)
@@ -167,45 +141,34 @@ int prepare_search(nmi_ctx *ctx, const nmi::SearchPlan &plan, nmi::GridArgs &a)
     const int64_t total = (int64_t)a.S_local * a.Wn;
     int rc = NMI_OK;
     if (plan.kind == nmi::SearchKernel::split) {
-        rc = ensure_slabs(ctx, (int)total);
-        if (rc == NMI_OK && plan.pix_parts > 1) rc = ensure_zeroed(ctx, (void **)&ctx->d_blocks, &ctx->blocks_bytes, (size_t)total * nmi::split_block_bytes_per_candidate(plan.pix_parts));
+        rc = ensure_zeroed(ctx, ctx->d_slabs, (size_t)(total > 128 ? total : 128) * sizeof(nmi::SplitSlab));
+        if (rc == NMI_OK && plan.pix_parts > 1) rc = ensure_zeroed(ctx, ctx->d_blocks, (size_t)total * nmi::split_block_bytes_per_candidate(plan.pix_parts));
         if (rc == NMI_OK) rc = next_split_epoch(ctx, &a.epoch);
-        a.slabs = ctx->d_slabs;
-        a.blocks = ctx->d_blocks;
-        a.split_error = ctx->d_split_error;
+        a.slabs = ctx->d_slabs.as<nmi::SplitSlab>();
+        a.blocks = ctx->d_blocks.as<unsigned long long>();
+        a.split_error = ctx->split_error.device<uint32_t>();
     } else if (plan.kind == nmi::SearchKernel::pix) {
-        rc = ensure_zeroed(ctx, (void **)&ctx->d_pix_blocks, &ctx->pix_blocks_bytes, nmi::pix_block_bytes((int)total, plan.pix));
+        rc = ensure_zeroed(ctx, ctx->d_pix_blocks, nmi::pix_block_bytes((int)total, plan.pix));
         if (rc == NMI_OK) rc = prepare_pix_handoff(ctx, &a.epoch);
-        a.blocks = ctx->d_pix_blocks;
+        a.blocks = ctx->d_pix_blocks.as<unsigned long long>();
     } else if (plan.order_table) {
         rc = ensure_order(ctx, a.S_local, a.Wn, &a.order);
     }
     if (rc != NMI_OK) return rc;
 #ifdef NMI_BUILD_ABLATIONS
     if (plan.scratch && plan.workgroups > ctx->scratch_workgroups) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_scratch) NMI_HIP_TRY(ctx, hipFree(ctx->d_scratch));
-        ctx->d_scratch = nullptr;
         ctx->scratch_workgroups = 0;
         const int alloc = plan.workgroups > ctx->compute_units ? plan.workgroups : ctx->compute_units;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_scratch, nmi::grid_kernel_scratch_bytes(alloc)));
+        NMI_HIP_TRY(ctx, ctx->d_scratch.grow(nmi::grid_kernel_scratch_bytes(alloc), ctx->stream));
         ctx->scratch_workgroups = alloc;
-        a.scratch = ctx->d_scratch;
+        a.scratch = ctx->d_scratch.as<uint32_t>();
     }
 #endif
-    if (plan.probe) a.plan = ctx->d_plan;  // the search doubles as a probe (few-levels: the plan of its own probe)
+    if (plan.probe) a.plan = ctx->d_plan.as<nmi::LevelPlan>();  // the search doubles as a probe (few-levels: the plan of its own probe)
     if (plan.kind == nmi::SearchKernel::few_levels) {
         const size_t need = (size_t)(a.S_local + a.Wn) * (size_t)ctx->npix;
-        if (need > ctx->rank_bytes) {
-            NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_rank_stacks) NMI_HIP_TRY(ctx, hipFree(ctx->d_rank_stacks));
-            ctx->d_rank_stacks = nullptr;
-            ctx->rank_bytes = 0;
-            // with headroom: a coarse-to-fine search alternates between grid shapes, and growing drains the stream
-            const size_t want = need + need / 2;
-            NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rank_stacks, want));
-            ctx->rank_bytes = want;
-        }
+        // with headroom: a coarse-to-fine search alternates between grid shapes, and growing drains the stream
+        if (need > ctx->d_rank_stacks.size()) NMI_HIP_TRY(ctx, ctx->d_rank_stacks.grow(need + need / 2, ctx->stream));
     }
     return NMI_OK;
 }
@@ -247,12 +210,12 @@ nmi::GridArgs grid_args(const nmi_ctx *ctx, const SearchRequest &rq, bool post, 
     a.shift = ctx->shift;
     a.mode = p.mode;
     a.ratings = rq.d_ratings;
-    a.key = ctx->d_keys + ctx->slot;
-    a.reset_key = ctx->d_keys + (ctx->slot ^ 1);
+    a.key = ctx->d_keys.as<unsigned long long>() + ctx->slot;
+    a.reset_key = ctx->d_keys.as<unsigned long long>() + (ctx->slot ^ 1);
     a.out_key = rq.out_key;
-    a.done = ctx->d_done;
-    a.mailbox = post ? ctx->mailbox : nullptr;
-    a.score_post = post_score ? ctx->score_mailbox : nullptr;
+    a.done = ctx->d_done.as<unsigned int>();
+    a.mailbox = post ? ctx->mailbox.as<nmi::Mailbox>() : nullptr;
+    a.score_post = post_score ? ctx->score_mailbox.as<unsigned long long>() : nullptr;
     a.seq = post ? ctx->seq + 1 : (post_score ? ctx->pair_seq + 1 : 0);
     a.hist_variant = ctx->hist_variant;
     return a;
@@ -271,8 +234,8 @@ int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched)
         for (int i = 0; i < rq.S_local; ++i) bits |= (uintptr_t)rq.pair_renders_host[i] | (uintptr_t)rq.pair_warps_host[i];
         if (bits % 16) nmi::set_geometry(a, p.width, p.height, (const void *)1, (const void *)1, p.render_bottom_up != 0);
     }
-    a.table = ctx->table;
-    a.scratch = ctx->d_scratch;
+    a.table = ctx->table.as<float>();
+    a.scratch = ctx->d_scratch.as<uint32_t>();
     a.dbg_joint = rq.dbg_joint;
     a.dbg_h1 = rq.dbg_h1;
     a.dbg_h2 = rq.dbg_h2;
@@ -285,9 +248,9 @@ int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched)
         // "zero on entry" state for the next launch (nothing ever writes a winner into a ping-pong slot from outside:
         // the RCCL form reduces into ctx->d_reduced_key).
         if (rq.out_key) NMI_HIP_TRY(ctx, hipMemsetAsync(rq.out_key, 0, sizeof(unsigned long long), ctx->stream));
-        NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_keys + ctx->slot, 0, sizeof(unsigned long long), ctx->stream));
+        NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_keys.as<unsigned long long>() + ctx->slot, 0, sizeof(unsigned long long), ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (post) ctx->mailbox->word = (unsigned long long)((ctx->seq + 1) & 1u) << 63;
+        if (post) ctx->mailbox.as<nmi::Mailbox>()->word = (unsigned long long)((ctx->seq + 1) & 1u) << 63;
         return commit_launch(ctx, post, false, SearchLaunch{}, /*launched=*/false, launched);
     }
     nmi::PlanInputs in = plan_inputs(ctx, nmi::SearchForm::plain, total, a);
@@ -299,7 +262,7 @@ int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched)
     // What the most recent search found in its stacks (nr, nw), posted by the device: by the probe that goes with every
     // few-levels launch, or by nmi_grid_kernel itself -- every general search counts the bins of its candidates'
     // marginals on the way (publish_seen / post_seen), so a change of content shows after ONE search, with no extra launch.
-    const unsigned long long posted = __atomic_load_n(ctx->level_post, __ATOMIC_ACQUIRE);
+    const unsigned long long posted = __atomic_load_n(ctx->level_post.as<unsigned long long>(), __ATOMIC_ACQUIRE);
     if ((uint32_t)(posted >> 32) != ctx->level_seen) {
         const uint32_t joint = (uint32_t)((posted >> 16) & 0xFFFFu) * (uint32_t)(posted & 0xFFFFu);
         in.few_hint = joint > 0 && joint <= (uint32_t)ctx->fewlevels_bins;
@@ -323,13 +286,13 @@ int enqueue_grid(nmi_ctx *ctx, const SearchRequest &rq, SearchLaunch *launched)
         NMI_HIP_TRY(ctx, nmi::launch_split(a, plan.parts, plan.pix_parts, plan.workgroups, use_bg, ctx->stream));
         break;
     case nmi::SearchKernel::pix:
-        NMI_HIP_TRY(ctx, nmi::launch_pix(a, plan.pix, pix_owner_share(ctx, plan.pix), use_bg, nullptr, ctx->d_pix_timeouts, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_pix(a, plan.pix, pix_owner_share(ctx, plan.pix), use_bg, nullptr, ctx->d_pix_timeouts.as<uint32_t>(), ctx->stream));
         break;
     case nmi::SearchKernel::few_levels:
-        NMI_HIP_TRY(ctx, nmi::launch_levels(rq.render_stack, rq.S_local, rq.warp_stack, rq.Wn, ctx->npix, ctx->shift, ctx->d_plan, ctx->level_post,
-                                            ++ctx->level_seq, (uint32_t)ctx->fewlevels_bins, true, ctx->stream));
-        NMI_HIP_TRY(ctx, nmi::launch_fewlevels(a, ctx->d_rank_stacks, ctx->d_rank_stacks + (size_t)rq.S_local * ctx->npix, plan.workgroups, use_bg,
-                                               ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_levels(rq.render_stack, rq.S_local, rq.warp_stack, rq.Wn, ctx->npix, ctx->shift, ctx->d_plan.as<nmi::LevelPlan>(),
+                                            ctx->level_post.as<unsigned long long>(), ++ctx->level_seq, (uint32_t)ctx->fewlevels_bins, true, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_fewlevels(a, ctx->d_rank_stacks.as<uint8_t>(), ctx->d_rank_stacks.as<uint8_t>() + (size_t)rq.S_local * ctx->npix,
+                                               plan.workgroups, use_bg, ctx->stream));
         NMI_HIP_TRY(ctx, nmi::launch_grid_gated(a, plan.workgroups, use_bg, ctx->stream));
         break;
     default:
@@ -347,7 +310,7 @@ bool split_launch_failed(nmi_ctx *ctx, const SearchLaunch &launch)
 {
     if (!launch.parts) return false;
     const uint32_t epoch = launch.epoch;
-    uint32_t *word = ctx->h_split_error + (epoch % nmi::kSplitRing);
+    uint32_t *word = ctx->split_error.as<uint32_t>() + (epoch % nmi::kSplitRing);
     if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != epoch) {
         // a split launch that went through re-arms the short cooldown -- if it was issued AFTER the last pause was set: a sibling
         // of the failed launch (same nmi_eval_pairs batch, stream tickets already in flight) says nothing about the retry
@@ -403,45 +366,30 @@ int fetch_key(nmi_ctx *ctx, unsigned long long *key)
     if (ctx->posted) {
         // The last workgroup stores (key | parity << 63) to fine-grained pinned memory; poll that one word.
         unsigned long long word = 0;
-        const int rc = wait_word(ctx, &ctx->mailbox->word, 1ull << 63, (unsigned long long)(ctx->seq & 1u) << 63, &word);
+        const int rc = wait_word(ctx, &ctx->mailbox.as<nmi::Mailbox>()->word, 1ull << 63, (unsigned long long)(ctx->seq & 1u) << 63, &word);
         if (rc == NMI_OK) {
             *key = word & 0x7FFFFFFFFFFFFFFFull;
             return NMI_OK;
         }
         if (rc != NMI_ERR_NOT_READY) return rc;  // stream drained without a post: fall through to the copy path
     }
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key, ctx->d_keys + ctx->last_slot, sizeof(unsigned long long),
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key.as<>(), ctx->d_keys.as<unsigned long long>() + ctx->last_slot, sizeof(unsigned long long),
                                     hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *key = *ctx->h_key;
+    *key = *ctx->h_key.as<unsigned long long>();
     return NMI_OK;
 }
 
-// Uploads `n` floats through a StagingRing slot on the context's stream; *d_out is the device copy (valid for work
+// Uploads `n` floats through a slot of the ring on the context's stream; *d_out is the device copy (valid for work
 // enqueued on that stream until the slot comes round again).
-int stage_floats(nmi_ctx *ctx, StagingRing &ring, const float *h_src, size_t n, float **d_out)
+int stage_floats(nmi_ctx *ctx, nmi_mem::UploadRing &ring, const float *h_src, size_t n, float **d_out)
 {
-    if (n > ring.cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < StagingRing::kSlots; ++i) {
-            if (ring.d[i]) NMI_HIP_TRY(ctx, hipFree(ring.d[i]));
-            if (ring.h[i]) NMI_HIP_TRY(ctx, hipHostFree(ring.h[i]));
-            ring.d[i] = ring.h[i] = nullptr;
-        }
-        ring.cap = 0;
-        for (int i = 0; i < StagingRing::kSlots; ++i) {
-            NMI_HIP_TRY(ctx, hipMalloc((void **)&ring.d[i], n * sizeof(float)));
-            NMI_HIP_TRY(ctx, hipHostMalloc((void **)&ring.h[i], n * sizeof(float), hipHostMallocDefault));
-            if (!ring.ev[i]) NMI_HIP_TRY(ctx, hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
-        }
-        ring.cap = n;
-    }
-    const int slot = (int)(ring.uses++ % StagingRing::kSlots);
-    NMI_HIP_TRY(ctx, hipEventSynchronize(ring.ev[slot]));
-    memcpy(ring.h[slot], h_src, n * sizeof(float));
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(ring.d[slot], ring.h[slot], n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    NMI_HIP_TRY(ctx, hipEventRecord(ring.ev[slot], ctx->stream));
-    *d_out = ring.d[slot];
+    nmi_mem::UploadRing::Slot slot;
+    NMI_HIP_TRY(ctx, ring.acquire(n, ctx->stream, &slot));
+    memcpy(slot.h, h_src, n * sizeof(float));
+    NMI_HIP_TRY(ctx, ring.upload(slot, ctx->stream));
+    NMI_HIP_TRY(ctx, ring.release(slot, ctx->stream));
+    *d_out = slot.d;
     return NMI_OK;
 }
 
@@ -524,71 +472,57 @@ int nmi_create(const nmi_params *params, nmi_ctx **out_ctx)
     ctx->shift = shift;
     DeviceGuard guard(dev);
 
-    int rc = NMI_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        rc = hip_fail(ctx, e, what);
+    hipDeviceProp_t prop;
+    const char *what = "hipGetDeviceProperties";  // the step in hand: named by the detail text if it fails
+    hipError_t e = hipGetDeviceProperties(&prop, dev);
+    if (e == hipSuccess && (size_t)nmi::grid_kernel_lds_bytes() > prop.sharedMemPerBlock) {
+        // The kernel keeps a whole packed joint histogram in LDS: it needs a CU with >= 136 KiB (gfx950: 160 KiB).
+        delete ctx;
+        return NMI_ERR_UNSUPPORTED;
+    }
+    if (e == hipSuccess) ctx->compute_units = prop.multiProcessorCount;
+    auto step = [&](const char *name, auto &&call) {
+        if (e == hipSuccess) what = name, e = call();
+        return e == hipSuccess;
+    };
+    using nmi_mem::kPosted;
+    constexpr size_t kWord = sizeof(unsigned long long);
+    if (step("hipStreamCreateWithFlags", [&] { return ctx->own_stream.create(hipStreamNonBlocking); }))
+        ctx->stream = p.stream ? (hipStream_t)p.stream : (hipStream_t)ctx->own_stream;
+    hipStream_t st = ctx->stream;
+    step("device buffer (table)", [&] { return ctx->table.alloc(((size_t)ctx->npix + 1) * sizeof(float)); });
+    step("device buffer (key)", [&] { return ctx->d_keys.alloc(2 * kWord); });
+    step("device buffer (done)", [&] { return ctx->d_done.alloc(sizeof(unsigned int)); });
+    // on the context's own (non-blocking) stream: a legacy-stream hipMemset is not ordered against it
+    step("hipMemsetAsync(key)", [&] { return hipMemsetAsync(ctx->d_keys.as<>(), 0, 2 * kWord, st); });
+    step("hipMemsetAsync(done)", [&] { return hipMemsetAsync(ctx->d_done.as<>(), 0, sizeof(unsigned int), st); });
+    if (step("pinned buffer (mailbox)", [&] { return ctx->mailbox.alloc(sizeof(nmi::Mailbox), kPosted); })) memset(ctx->mailbox.as<>(), 0, sizeof(nmi::Mailbox));
+    step("device buffer (rating)", [&] { return ctx->d_pair_rating.alloc(sizeof(float)); });
+    step("device buffer (reduced key)", [&] { return ctx->d_reduced_key.alloc(kWord); });
+    if (step("pinned buffer (score mailbox)", [&] { return ctx->score_mailbox.alloc(2 * kWord, kPosted); })) memset(ctx->score_mailbox.as<>(), 0, 2 * kWord);
+    if (step("pinned buffer (split error)", [&] { return ctx->split_error.alloc(nmi::kSplitRing * sizeof(uint32_t), kPosted); }))
+        memset(ctx->split_error.as<>(), 0, nmi::kSplitRing * sizeof(uint32_t));
+    step("pinned buffer (key)", [&] { return ctx->h_key.alloc(kWord, nmi_mem::kPinned); });
+    if (step("pinned buffer (level post)", [&] { return ctx->level_post.alloc(64, kPosted); })) *ctx->level_post.as<unsigned long long>() = 0;
+    step("device buffer (level plan)", [&] { return ctx->d_plan.alloc(sizeof(nmi::LevelPlan)); });
+    step("hipMemsetAsync(level plan)", [&] { return hipMemsetAsync(ctx->d_plan.as<>(), 0, sizeof(nmi::LevelPlan), st); });
+    // where the general kernel's last workgroup posts what its search found (every search is a content probe)
+    nmi::LevelPlan *d_plan = ctx->d_plan.as<nmi::LevelPlan>();
+    unsigned long long *d_post = ctx->level_post.device<unsigned long long>();
+    const uint32_t max_joint = (uint32_t)ctx->fewlevels_bins;
+    step("hipMemcpyAsync(level post)", [&] { return hipMemcpyAsync(&d_plan->seen_post, &d_post, sizeof d_post, hipMemcpyHostToDevice, st); });
+    step("hipMemcpyAsync(level plan)", [&] { return hipMemcpyAsync(&d_plan->seen_max_joint, &max_joint, sizeof max_joint, hipMemcpyHostToDevice, st); });
+    step("hipStreamSynchronize", [&] { return hipStreamSynchronize(st); });  // (d_post and max_joint are locals)
+    step("hipEventCreate", [&] { return ctx->ev_start.create(hipEventDefault); });
+    step("hipEventCreate", [&] { return ctx->ev_stop.create(hipEventDefault); });
+    step("launch_table", [&] { return nmi::launch_table(ctx->table.as<float>(), ctx->npix, st); });
+    step("hipStreamSynchronize", [&] { return hipStreamSynchronize(st); });
+    if (e != hipSuccess) {
+        const int rc = hip_fail(ctx, e, what);
         fprintf(stderr, "nmi_create: %s\n", ctx->detail.c_str());
         nmi_destroy(ctx);
         return rc;
-    };
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, dev);
-    if (e != hipSuccess) return fail(e, "hipGetDeviceProperties");
-    ctx->compute_units = prop.multiProcessorCount;
-    if ((size_t)nmi::grid_kernel_lds_bytes() > prop.sharedMemPerBlock) {
-        // The kernel keeps a whole packed joint histogram in LDS: it needs a CU with >= 136 KiB (gfx950: 160 KiB).
-        nmi_destroy(ctx);
-        return NMI_ERR_UNSUPPORTED;
     }
-    if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess)
-        return fail(e, "hipStreamCreateWithFlags");
-    ctx->stream = p.stream ? (hipStream_t)p.stream : ctx->own_stream;
-    if ((e = hipMalloc((void **)&ctx->table, ((size_t)ctx->npix + 1) * sizeof(float))) != hipSuccess)
-        return fail(e, "hipMalloc(table)");
-    if ((e = hipMalloc((void **)&ctx->d_keys, 2 * sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMalloc(key)");
-    if ((e = hipMalloc((void **)&ctx->d_done, sizeof(unsigned int))) != hipSuccess) return fail(e, "hipMalloc(done)");
-    // on the context's own (non-blocking) stream: a legacy-stream hipMemset is not ordered against it
-    if ((e = hipMemsetAsync(ctx->d_keys, 0, 2 * sizeof(unsigned long long), ctx->stream)) != hipSuccess)
-        return fail(e, "hipMemsetAsync(key)");
-    if ((e = hipMemsetAsync(ctx->d_done, 0, sizeof(unsigned int), ctx->stream)) != hipSuccess)
-        return fail(e, "hipMemsetAsync(done)");
-    if ((e = hipHostMalloc((void **)&ctx->mailbox, sizeof(nmi::Mailbox), hipHostMallocCoherent | hipHostMallocMapped)) !=
-        hipSuccess)
-        return fail(e, "hipHostMalloc(mailbox)");
-    memset(ctx->mailbox, 0, sizeof(nmi::Mailbox));
-    if ((e = hipMalloc((void **)&ctx->d_pair_rating, sizeof(float))) != hipSuccess) return fail(e, "hipMalloc(rating)");
-    if ((e = hipMalloc((void **)&ctx->d_reduced_key, sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMalloc(reduced key)");
-    if ((e = hipHostMalloc((void **)&ctx->score_mailbox, 2 * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) !=
-        hipSuccess)
-        return fail(e, "hipHostMalloc(score mailbox)");
-    memset(ctx->score_mailbox, 0, 2 * sizeof(unsigned long long));
-    if ((e = hipHostMalloc((void **)&ctx->h_split_error, nmi::kSplitRing * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
-        return fail(e, "hipHostMalloc(split error)");
-    memset(ctx->h_split_error, 0, nmi::kSplitRing * sizeof(uint32_t));
-    if ((e = hipHostGetDevicePointer((void **)&ctx->d_split_error, ctx->h_split_error, 0)) != hipSuccess)
-        return fail(e, "hipHostGetDevicePointer(split error)");
-    if ((e = hipHostMalloc((void **)&ctx->h_key, sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
-        return fail(e, "hipHostMalloc(key)");
-    if ((e = hipHostMalloc((void **)&ctx->level_post, 64, hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
-        return fail(e, "hipHostMalloc(level post)");
-    *ctx->level_post = 0;
-    if ((e = hipMalloc((void **)&ctx->d_plan, sizeof(nmi::LevelPlan))) != hipSuccess) return fail(e, "hipMalloc(level plan)");
-    if ((e = hipMemsetAsync(ctx->d_plan, 0, sizeof(nmi::LevelPlan), ctx->stream)) != hipSuccess) return fail(e, "hipMemsetAsync(level plan)");
-    {
-        // where the general kernel's last workgroup posts what its search found (every search is a content probe)
-        unsigned long long *d_post = nullptr;
-        if ((e = hipHostGetDevicePointer((void **)&d_post, ctx->level_post, 0)) != hipSuccess) return fail(e, "hipHostGetDevicePointer(level post)");
-        if ((e = hipMemcpyAsync(&ctx->d_plan->seen_post, &d_post, sizeof d_post, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            return fail(e, "hipMemcpyAsync(level post)");
-        const uint32_t max_joint = (uint32_t)ctx->fewlevels_bins;
-        if ((e = hipMemcpyAsync(&ctx->d_plan->seen_max_joint, &max_joint, sizeof max_joint, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            return fail(e, "hipMemcpyAsync(level plan)");
-        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e, "hipStreamSynchronize");  // (d_post is a local)
-    }
-    if ((e = hipEventCreate(&ctx->ev_start)) != hipSuccess) return fail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&ctx->ev_stop)) != hipSuccess) return fail(e, "hipEventCreate");
-    if ((e = nmi::launch_table(ctx->table, ctx->npix, ctx->stream)) != hipSuccess) return fail(e, "launch_table");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e, "hipStreamSynchronize");
     *out_ctx = ctx;
     return NMI_OK;
 }
@@ -598,49 +532,6 @@ int nmi_destroy(nmi_ctx *ctx)
     if (!ctx) return NMI_OK;
     DeviceGuard guard(ctx->device);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-    if (ctx->table) (void)hipFree(ctx->table);
-    if (ctx->d_reduced_key) (void)hipFree(ctx->d_reduced_key);
-    if (ctx->score_mailbox) (void)hipHostFree(ctx->score_mailbox);
-    if (ctx->d_slabs) (void)hipFree(ctx->d_slabs);
-    if (ctx->h_pair_table) (void)hipHostFree(ctx->h_pair_table);
-    if (ctx->d_pair_scores) (void)hipFree(ctx->d_pair_scores);
-    if (ctx->d_blocks) (void)hipFree(ctx->d_blocks);
-    if (ctx->d_pix_timeouts) (void)hipFree(ctx->d_pix_timeouts);
-    if (ctx->d_pix_blocks) (void)hipFree(ctx->d_pix_blocks);
-    if (ctx->h_split_error) (void)hipHostFree(ctx->h_split_error);
-    if (ctx->level_post) (void)hipHostFree(ctx->level_post);
-    if (ctx->d_plan) (void)hipFree(ctx->d_plan);
-    if (ctx->d_rank_stacks) (void)hipFree(ctx->d_rank_stacks);
-    if (ctx->d_keys) (void)hipFree(ctx->d_keys);
-    if (ctx->d_done) (void)hipFree(ctx->d_done);
-    if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
-    if (ctx->d_pair_rating) (void)hipFree(ctx->d_pair_rating);
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_mask_counts) (void)hipFree(ctx->d_mask_counts);
-    if (ctx->d_mask_tables) (void)hipFree(ctx->d_mask_tables);
-    if (ctx->d_mask_redo) (void)hipFree(ctx->d_mask_redo);
-    if (ctx->d_mask_redo_state) (void)hipFree(ctx->d_mask_redo_state);
-    if (ctx->d_cover_counts) (void)hipFree(ctx->d_cover_counts);
-    if (ctx->d_zbuf) (void)hipFree(ctx->d_zbuf);
-    mesh_work_free(&ctx->mesh);
-    for (int i = 0; i < StagingRing::kSlots; ++i) {
-        if (ctx->mvp_ring.d[i]) (void)hipFree(ctx->mvp_ring.d[i]);
-        if (ctx->mvp_ring.h[i]) (void)hipHostFree(ctx->mvp_ring.h[i]);
-        if (ctx->mvp_ring.ev[i]) (void)hipEventDestroy(ctx->mvp_ring.ev[i]);
-    }
-    for (auto &oe : ctx->orders) {
-        if (oe.d) (void)hipFree(oe.d);
-        if (oe.h) (void)hipHostFree(oe.h);
-    }
-    for (int i = 0; i < nmi_ctx::kWarpRing; ++i) {
-        if (ctx->d_warp_coeffs[i]) (void)hipFree(ctx->d_warp_coeffs[i]);
-        if (ctx->h_warp_coeffs[i]) (void)hipHostFree(ctx->h_warp_coeffs[i]);
-        if (ctx->warp_ev[i]) (void)hipEventDestroy(ctx->warp_ev[i]);
-    }
-    if (ctx->h_key) (void)hipHostFree(ctx->h_key);
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return NMI_OK;
 }
@@ -648,7 +539,7 @@ int nmi_destroy(nmi_ctx *ctx)
 int nmi_set_stream(nmi_ctx *ctx, void *stream)
 {
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    ctx->stream = stream ? (hipStream_t)stream : (hipStream_t)ctx->own_stream;
     return NMI_OK;
 }
 
@@ -725,7 +616,7 @@ int nmi_set_option(nmi_ctx *ctx, int32_t option, int64_t value)
         {   // the device posts changes of its verdict only: start it from "not few" as well (blocking: a local is copied)
             DeviceGuard guard(ctx->device);
             const uint32_t zero = 0;
-            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan->seen_state, &zero, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
+            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan.as<nmi::LevelPlan>()->seen_state, &zero, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
             NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
         return NMI_OK;
@@ -735,8 +626,8 @@ int nmi_set_option(nmi_ctx *ctx, int32_t option, int64_t value)
         {
             DeviceGuard guard(ctx->device);
             const uint32_t max_joint = (uint32_t)value, zero = 0;
-            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan->seen_max_joint, &max_joint, sizeof max_joint, hipMemcpyHostToDevice, ctx->stream));
-            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan->seen_state, &zero, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
+            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan.as<nmi::LevelPlan>()->seen_max_joint, &max_joint, sizeof max_joint, hipMemcpyHostToDevice, ctx->stream));
+            NMI_HIP_TRY(ctx, hipMemcpyAsync(&ctx->d_plan.as<nmi::LevelPlan>()->seen_state, &zero, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
             NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             ctx->few_hint = false;
         }
@@ -782,7 +673,7 @@ int nmi_last_content(nmi_ctx *ctx, int32_t *few_levels, int32_t *nr, int32_t *nw
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned long long posted = __atomic_load_n(ctx->level_post, __ATOMIC_ACQUIRE);
+    const unsigned long long posted = __atomic_load_n(ctx->level_post.as<unsigned long long>(), __ATOMIC_ACQUIRE);
     const int32_t r = (int32_t)((posted >> 16) & 0xFFFFu), w = (int32_t)(posted & 0xFFFFu);
     if (nr) *nr = r;
     if (nw) *nw = w;
@@ -791,7 +682,7 @@ int nmi_last_content(nmi_ctx *ctx, int32_t *few_levels, int32_t *nr, int32_t *nw
     // do not restate it: a restatement on the host agrees with any device-side slip at the limit.
     uint32_t use = 0;
     if (few_levels && ctx->last.few) {
-        NMI_HIP_TRY(ctx, hipMemcpyAsync(&use, &ctx->d_plan->use, sizeof use, hipMemcpyDeviceToHost, ctx->stream));
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(&use, &ctx->d_plan.as<nmi::LevelPlan>()->use, sizeof use, hipMemcpyDeviceToHost, ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (few_levels) *few_levels = use ? 1 : 0;
@@ -802,7 +693,7 @@ int nmi_copy_term_table(nmi_ctx *ctx, float *h_out, int64_t n)
 {
     if (!ctx || !h_out || n != (int64_t)ctx->npix + 1) return NMI_ERR_INVALID_ARGUMENT;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_out, ctx->table, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_out, ctx->table.as<>(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NMI_OK;
 }
@@ -897,7 +788,7 @@ static int read_pix_heal(nmi_ctx *ctx, uint32_t (&n)[nmi::kPixHealWords])
     for (uint32_t &x : n) x = 0;
     if (!ctx->d_pix_timeouts) return NMI_OK;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(n, ctx->d_pix_timeouts, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(n, ctx->d_pix_timeouts.as<>(), sizeof n, hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NMI_OK;
 }
@@ -943,7 +834,7 @@ int nmi_eval_pair_debug(nmi_ctx *ctx, const uint8_t *render, const uint8_t *warp
     DeviceGuard guard(ctx->device);
     const bool dbg = d_joint || d_hist_render || d_hist_warped || d_sums;
     SearchRequest rq = SearchRequest::block(render, 1, 0, 1, warped, 1);
-    rq.d_ratings = ctx->d_pair_rating;
+    rq.d_ratings = ctx->d_pair_rating.as<float>();
     rq.post_score = true;
     rq.dbg_joint = d_joint;
     rq.dbg_h1 = d_hist_render;
@@ -955,7 +846,7 @@ int nmi_eval_pair_debug(nmi_ctx *ctx, const uint8_t *render, const uint8_t *warp
         // kernel.cu:100 copies the score back with a blocking cudaMemcpy; here the scoring lane stores
         // (score bits | call number << 32) into pinned host memory and the call polls that word (~10 us less per call).
         unsigned long long word = 0;
-        rc = wait_word(ctx, ctx->score_mailbox, 0xFFFFFFFF00000000ull, (unsigned long long)ctx->pair_seq << 32, &word);
+        rc = wait_word(ctx, ctx->score_mailbox.as<unsigned long long>(), 0xFFFFFFFF00000000ull, (unsigned long long)ctx->pair_seq << 32, &word);
         if (rc == NMI_OK && split_timed_out(ctx)) {
             rc = nmi_eval_pair_debug(ctx, render, warped, h_score, d_joint, d_hist_render, d_hist_warped, d_sums);
             if (rc == NMI_OK) ctx->detail = kSplitTimeoutNote;
@@ -969,7 +860,7 @@ int nmi_eval_pair_debug(nmi_ctx *ctx, const uint8_t *render, const uint8_t *warp
         }
         if (rc != NMI_ERR_NOT_READY) return rc;
     }
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_score, ctx->d_pair_rating, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_score, ctx->d_pair_rating.as<>(), sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (split_timed_out(ctx)) {
         rc = nmi_eval_pair_debug(ctx, render, warped, h_score, d_joint, d_hist_render, d_hist_warped, d_sums);
@@ -1015,40 +906,35 @@ int nmi_eval_pairs(nmi_ctx *ctx, const uint8_t *const *h_renders, const uint8_t 
         return NMI_OK;
     }
     // pointer tables (pinned, device-mapped) and the scores (device), grown on demand
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // growing or not: an earlier batch may still be reading the tables
     if (n > ctx->pairs_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_pair_table) NMI_HIP_TRY(ctx, hipHostFree(ctx->h_pair_table));
-        if (ctx->d_pair_scores) NMI_HIP_TRY(ctx, hipFree(ctx->d_pair_scores));
-        ctx->h_pair_table = nullptr;
-        ctx->d_pair_scores = nullptr;
         ctx->pairs_cap = 0;
         const int cap = n > 256 ? n : 256;
-        NMI_HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_pair_table, (size_t)cap * 2 * sizeof(void *), hipHostMallocMapped | hipHostMallocCoherent));
-        NMI_HIP_TRY(ctx, hipHostGetDevicePointer((void **)&ctx->d_pair_table, ctx->h_pair_table, 0));
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pair_scores, (size_t)cap * sizeof(float)));
+        NMI_HIP_TRY(ctx, ctx->pair_table.grow((size_t)cap * 2 * sizeof(void *), nmi_mem::kPosted));
+        NMI_HIP_TRY(ctx, ctx->d_pair_scores.grow((size_t)cap * sizeof(float)));
         ctx->pairs_cap = cap;
-    } else {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // an earlier batch may still be reading the tables
     }
+    const uint8_t **h_pair_table = ctx->pair_table.as<const uint8_t *>(), **d_pair_table = ctx->pair_table.device<const uint8_t *>();
+    float *d_pair_scores = ctx->d_pair_scores.as<float>();
     for (int i = 0; i < n; ++i) {
-        ctx->h_pair_table[i] = h_renders[i];
-        ctx->h_pair_table[ctx->pairs_cap + i] = h_warps[i];
+        h_pair_table[i] = h_renders[i];
+        h_pair_table[ctx->pairs_cap + i] = h_warps[i];
     }
     SearchLaunch launches[128];  // (the batch was cut to at most that many above)
     int n_launches = 0;
     for (int off = 0; off < n; off += per_launch) {
         const int m = n - off < per_launch ? n - off : per_launch;
         SearchRequest rq = SearchRequest::block(h_renders[off], m, 0, m, h_warps[off], 1);
-        rq.d_ratings = ctx->d_pair_scores + off;
-        rq.pair_renders = ctx->d_pair_table + off;
-        rq.pair_warps = ctx->d_pair_table + ctx->pairs_cap + off;
+        rq.d_ratings = d_pair_scores + off;
+        rq.pair_renders = d_pair_table + off;
+        rq.pair_warps = d_pair_table + ctx->pairs_cap + off;
         rq.pair_renders_host = h_renders + off;
         rq.pair_warps_host = h_warps + off;
         const int rc = enqueue_grid(ctx, rq, &launches[n_launches]);
         if (rc != NMI_OK) return rc;  // (NMI_ERR_UNSUPPORTED, before any launch, had no split form fitted after all)
         ++n_launches;
     }
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_scores, ctx->d_pair_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_scores, d_pair_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     bool failed = false;  // every launch of the batch answers for itself
     for (int i = 0; i < n_launches; ++i) failed = split_launch_failed(ctx, launches[i]) || failed;

@@ -12,15 +12,9 @@ namespace {
 // Counts [total].  Growing waits for the stream (the old buffer may be in use by a search in flight).
 int ensure_cover_work(nmi_ctx *ctx, int64_t total)
 {
-    if (total > ctx->cover_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_cover_counts) NMI_HIP_TRY(ctx, hipFree(ctx->d_cover_counts));
-        ctx->d_cover_counts = nullptr;
-        ctx->cover_cap = 0;
-        ctx->cover_count_n = 0;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_cover_counts, (size_t)total * sizeof(int32_t)));
-        ctx->cover_cap = total;
-    }
+    const size_t bytes = (size_t)total * sizeof(int32_t);
+    if (bytes > ctx->d_cover_counts.size()) ctx->cover_count_n = 0;
+    NMI_HIP_TRY(ctx, ctx->d_cover_counts.grow(bytes, ctx->stream));
     return NMI_OK;
 }
 
@@ -43,7 +37,8 @@ int nmi_search_grid_covered(nmi_ctx *ctx, const uint8_t *render_stack, const uin
     SearchRequest rq = SearchRequest::block(render_stack, S, 0, S, warp_stack, Wn);
     rq.d_ratings = d_ratings;
     rq.post = true;
-    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, render_masks, ctx->d_cover_counts, nullptr, ctx->d_mask_redo, ctx->d_mask_redo_state});
+    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, render_masks, ctx->d_cover_counts.as<int32_t>(), nullptr, ctx->d_mask_redo.as<int32_t>(),
+                                                ctx->d_mask_redo_state.as<uint32_t>()});
     if (rc != NMI_OK) return rc;
     ctx->cover_count_n = total;
     unsigned long long key = 0;
@@ -59,7 +54,7 @@ int nmi_last_cover_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n)
     if (!ctx || !h_counts || n < 0 || n > ctx->cover_count_n) return NMI_ERR_INVALID_ARGUMENT;
     if (n == 0) return NMI_OK;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, ctx->d_cover_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, ctx->d_cover_counts.as<>(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NMI_OK;
 }

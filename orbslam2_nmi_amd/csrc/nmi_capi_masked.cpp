@@ -1,4 +1,4 @@
-// nmi_capi_masked.cpp -- the masked entry points of include/nmi_hip.h: nmi_warp_stack_masked, nmi_search_grid_masked,
+// nmi_capi_masked.cpp -- the masked entry points of include/nmi_hip.h: nmi_search_grid_masked (nmi_warp_stack_masked is beside nmi_warp_stack),
 // nmi_last_mask_counts; and what the masked and covered searches share on the host: their kernel arguments, their launches and
 // their enqueue (nmi_capi_covered.cpp, the levels and the streams of nmi_capi_pipeline.cpp use them).  Kernels:
 // nmi_masked_producer.hip, nmi_masked_kernel.hip, nmi_masked_pix_kernel.hip (mid-size grids).
@@ -11,18 +11,9 @@ namespace {
 // Counts and tables for Wn warps.  Growing waits for the stream (the old buffers may be in use by a search in flight).
 int ensure_mask_work(nmi_ctx *ctx, int Wn)
 {
-    if (Wn > ctx->mask_warps_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_mask_counts) NMI_HIP_TRY(ctx, hipFree(ctx->d_mask_counts));
-        if (ctx->d_mask_tables) NMI_HIP_TRY(ctx, hipFree(ctx->d_mask_tables));
-        ctx->d_mask_counts = nullptr;
-        ctx->d_mask_tables = nullptr;
-        ctx->mask_warps_cap = 0;
-        ctx->mask_count_n = 0;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_mask_counts, (size_t)Wn * sizeof(int32_t)));
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_mask_tables, (size_t)Wn * ((size_t)ctx->npix + 1) * sizeof(float)));
-        ctx->mask_warps_cap = Wn;
-    }
+    if ((size_t)Wn * sizeof(int32_t) > ctx->d_mask_counts.size()) ctx->mask_count_n = 0;
+    NMI_HIP_TRY(ctx, ctx->d_mask_counts.grow((size_t)Wn * sizeof(int32_t), ctx->stream));
+    NMI_HIP_TRY(ctx, ctx->d_mask_tables.grow((size_t)Wn * ((size_t)ctx->npix + 1) * sizeof(float), ctx->stream));
     return NMI_OK;
 }
 
@@ -31,18 +22,8 @@ int ensure_mask_work(nmi_ctx *ctx, int Wn)
 // The redo list of `total` candidates.  Growing waits for the stream (the old list may be in use by a search in flight).
 int nmi_internal::ensure_mask_redo(nmi_ctx *ctx, int64_t total)
 {
-    if (!ctx->d_mask_redo_state) {
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_mask_redo_state, 2 * sizeof(uint32_t)));
-        NMI_HIP_TRY(ctx, hipMemsetAsync(ctx->d_mask_redo_state, 0, 2 * sizeof(uint32_t), ctx->stream));
-    }
-    if (total > ctx->mask_redo_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_mask_redo) NMI_HIP_TRY(ctx, hipFree(ctx->d_mask_redo));
-        ctx->d_mask_redo = nullptr;
-        ctx->mask_redo_cap = 0;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_mask_redo, (size_t)total * sizeof(int32_t)));
-        ctx->mask_redo_cap = total;
-    }
+    NMI_HIP_TRY(ctx, ctx->d_mask_redo_state.grow(2 * sizeof(uint32_t), ctx->stream, /*zero=*/true));
+    NMI_HIP_TRY(ctx, ctx->d_mask_redo.grow((size_t)total * sizeof(int32_t), ctx->stream));
     return NMI_OK;
 }
 
@@ -101,26 +82,11 @@ int nmi_internal::enqueue_grid_mask(nmi_ctx *ctx, const SearchRequest &rq, const
     // timed (nmi_set_profiling): the scoring launches, as for nmi_search_grid -- not the masked search's counts and tables before them
     if (ctx->profiling) NMI_HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     NMI_HIP_TRY(ctx, launch_mask_search(ms, plan.pix, plan.pix ? pix_owner_share(ctx, plan.pix) : 0.0, plan.workgroups, p.use_bg != 0,
-                                        ctx->hist_variant == 1, nullptr, ctx->d_pix_timeouts, ctx->stream));
+                                        ctx->hist_variant == 1, nullptr, ctx->d_pix_timeouts.as<uint32_t>(), ctx->stream));
     return commit_launch(ctx, post, false, SearchLaunch{plan.kind, 0, plan.pix, 0, 0}, /*launched=*/true, launched);
 }
 
 extern "C" {
-
-int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask, const double *h_forward, int32_t Wn,
-                          uint8_t *d_warp_stack, uint8_t *d_warp_masks)
-{
-    if (!ctx || !d_frame || !h_forward || !d_warp_stack || !d_warp_masks || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
-    // the warps themselves: nmi_warp_stack, byte for byte (it uploads the inverse maps to a ring slot of the context)
-    int rc = nmi_warp_stack(ctx, d_frame, h_forward, Wn, d_warp_stack);
-    if (rc != NMI_OK) return rc;
-    DeviceGuard guard(ctx->device);
-    const int ring = (int)((ctx->warp_uses - 1) % nmi_ctx::kWarpRing);  // the slot nmi_warp_stack just used
-    NMI_HIP_TRY(ctx, nmi::launch_warp_masks(d_frame_mask, ctx->d_warp_coeffs[ring], d_warp_masks, ctx->params.width, ctx->params.height,
-                                            Wn, ctx->stream));
-    NMI_HIP_TRY(ctx, hipEventRecord(ctx->warp_ev[ring], ctx->stream));  // the slot is free again after this kernel too
-    return NMI_OK;
-}
 
 int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S, const uint8_t *warp_stack, const uint8_t *warp_masks,
                            int32_t Wn, float *d_ratings, int64_t *h_best_index, float *h_best_score)
@@ -135,8 +101,8 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
         if (rc == NMI_OK) rc = ensure_mask_redo(ctx, total);
         if (rc != NMI_OK) return rc;
         // len_w from the masks of THIS call (they need not come from nmi_warp_stack_masked), then the per-warp tables
-        NMI_HIP_TRY(ctx, nmi::launch_mask_counts(warp_masks, Wn, ctx->npix, ctx->d_mask_counts, ctx->stream));
-        NMI_HIP_TRY(ctx, nmi::launch_mask_tables(ctx->d_mask_counts, Wn, ctx->npix, ctx->d_mask_tables, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_mask_counts(warp_masks, Wn, ctx->npix, ctx->d_mask_counts.as<int32_t>(), ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_mask_tables(ctx->d_mask_counts.as<int32_t>(), Wn, ctx->npix, ctx->d_mask_tables.as<float>(), ctx->stream));
         ctx->mask_count_n = Wn;
     }
     if (total == 0) {  // nothing to score: no winner (as nmi_search_grid)
@@ -148,7 +114,8 @@ int nmi_search_grid_masked(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S,
     SearchRequest rq = SearchRequest::block(render_stack, S, 0, S, warp_stack, Wn);
     rq.d_ratings = d_ratings;
     rq.post = true;
-    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, nullptr, ctx->d_mask_counts, ctx->d_mask_tables, ctx->d_mask_redo, ctx->d_mask_redo_state});
+    rc = enqueue_grid_mask(ctx, rq, MaskSide{warp_masks, nullptr, ctx->d_mask_counts.as<int32_t>(), ctx->d_mask_tables.as<float>(), ctx->d_mask_redo.as<int32_t>(),
+                                                ctx->d_mask_redo_state.as<uint32_t>()});
     if (rc != NMI_OK) return rc;
     unsigned long long key = 0;
     rc = fetch_key(ctx, &key);
@@ -163,7 +130,7 @@ int nmi_last_mask_counts(nmi_ctx *ctx, int32_t *h_counts, int32_t n)
     if (!ctx || !h_counts || n < 0 || n > ctx->mask_count_n) return NMI_ERR_INVALID_ARGUMENT;
     if (n == 0) return NMI_OK;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, ctx->d_mask_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, ctx->d_mask_counts.as<>(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NMI_OK;
 }

@@ -39,25 +39,27 @@ struct nmi_level {
     nmi_ctx *ctx = nullptr;
     int S = 0, Wn = 0, size = 1;                // this rank's block: S views x Wn warps ...
     int s_offset = 0, S_total = 0, w_offset = 0, Wn_total = 0;  // ... of an S_total x Wn_total level (block == level on one rank)
-    uint8_t *d_renders = nullptr, *d_warps = nullptr;
-    uint32_t *d_zbuf = nullptr;                 // point cloud: anchor buffer
-    void *d_packed = nullptr;                   // point cloud: the level's own packed copy of the cloud (16-byte records + wavefront boxes)
-    nmi::MeshWork mesh;                         // either mesh kind: the renderer's work area (kept clean by the renderer itself)
+    DeviceBuffer d_renders, d_warps;            // uint8_t [S][H][W], [Wn][H][W]
+    DeviceBuffer d_zbuf;                        // uint32_t, point cloud: anchor buffer
+    DeviceBuffer d_packed;                      // point cloud: the level's own packed copy of the cloud (16-byte records + wavefront boxes)
+    MeshWorkArea mesh;                          // either mesh kind: the renderer's work area (kept clean by the renderer itself)
     MapKind kind = MapKind::points;             // what the level draws; d_attr below is red [N], uv [3T][2] or red [3T] accordingly
     bool fused_points = false;                  // point cloud, one chain of kernels, double-buffered anchors
-    uint32_t *d_kept = nullptr, *d_kept_count = nullptr;  // ... and the wavefronts in reach of a view, listed by the prep kernel per replay
+    DeviceBuffer d_kept, d_kept_count;          // uint32_t: ... and the wavefronts in reach of a view, listed by the prep kernel per replay
     uint32_t replay = 0;                        // parity of the counters the prep kernel counts under
-    float *d_mvps = nullptr, *h_mvps = nullptr, *d_coeffs = nullptr, *h_coeffs = nullptr;
-    int *d_order = nullptr;
-    float *d_ratings = nullptr;                 // [Wn][S] rating table of the latest replay
-    unsigned long long *d_key = nullptr, *h_key = nullptr;
-    unsigned int *d_done = nullptr;
-    uint32_t *d_epoch = nullptr;                // replays so far, bumped by the prep kernel: parity of the double-buffered anchors (fused
+    DeviceBuffer d_mvps, d_coeffs;              // float
+    PinnedBuffer h_mvps, h_coeffs;              // float, mapped: the prep kernel reads this replay's parameters from them
+    DeviceBuffer d_order;                       // int
+    DeviceBuffer d_ratings;                     // float [Wn][S] rating table of the latest replay
+    DeviceBuffer d_key;                         // unsigned long long
+    PinnedBuffer h_key;                         // unsigned long long, mapped: the search kernel posts the winner
+    DeviceBuffer d_done;                        // unsigned int
+    DeviceBuffer d_epoch;                       // uint32_t: replays so far, bumped by the prep kernel: parity of the double-buffered anchors (fused
                                                 // point-cloud form), tag of the search kernel's hand-offs (nmi_pix_kernel)
-    unsigned long long *d_pix_blocks = nullptr; // nmi_pix_kernel's hand-off blocks when the level's grid is a mid-size one
+    DeviceBuffer d_pix_blocks;                  // nmi_pix_kernel's hand-off blocks when the level's grid is a mid-size one
     int pix = 0;                                // pixel ranges per candidate of the captured search (0: nmi_grid_kernel)
-    hipStream_t side = nullptr;                 // forked capture branch (warp)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    nmi_mem::Stream side;                       // forked capture branch (warp)
+    nmi_mem::Event ev_fork, ev_join;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     // What the graph is captured from (level_capture), kept so that level_apply can capture it again.
@@ -66,28 +68,26 @@ struct nmi_level {
     const nmi_texture *tex = nullptr;
     const uint8_t *d_frame = nullptr;
     nmi::GridArgs args{};                       // the search's arguments (unmasked form)
-    float *hd_mvps = nullptr, *hd_coeffs = nullptr;
     int workgroups = 0;
-    size_t pix_blocks_bytes = 0;
     // What the setters change, as one value (level_apply): masks (nmi_level_set_masks) or coverage (nmi_level_set_coverage, never
     // both at once), their frame mask, and the frame's way in (nmi_level_set_distortion, _set_frame_format, _set_frame_reduction).
     LevelSettings set;
     // The buffers that go with the settings: level_buffers says which of them a setting needs, level_apply allocates and frees.
     // Masked: the warps' masks and counts of the latest replay, the counts of the replay before (tables are rebuilt only for the
     // warps whose count changed), the per-warp term tables, the redo list of the masked grid kernel.
-    uint8_t *d_masks = nullptr;                 // [Wn][H][W]
-    int32_t *d_counts = nullptr;                // [3][Wn]: counts, previous counts, changed flags
-    float *d_tables = nullptr;                  // [Wn][npix + 1]
-    int32_t *d_redo = nullptr;                  // [S * Wn]
-    uint32_t *d_redo_state = nullptr;           // [2], zero between replays
+    DeviceBuffer d_masks;                       // uint8_t [Wn][H][W]
+    DeviceBuffer d_counts;                      // int32_t [3][Wn]: counts, previous counts, changed flags
+    DeviceBuffer d_tables;                      // float [Wn][npix + 1]
+    DeviceBuffer d_redo;                        // int32_t [S * Wn]
+    DeviceBuffer d_redo_state;                  // uint32_t [2], zero between replays
     // Covered: the renders' coverage masks and len[w][s] of the latest replay; the warps' masks and the redo list are the masked
     // level's fields above.
-    uint8_t *d_rmasks = nullptr;                // [S][H][W], render layout
-    int32_t *d_cover_counts = nullptr;          // [Wn][S]
+    DeviceBuffer d_rmasks;                      // uint8_t [S][H][W], render layout
+    DeviceBuffer d_cover_counts;                // int32_t [Wn][S]
     // Distorted, coloured or reduced: d_frame (and d_frame_mask) are the camera's frame; every replay brings it into d_ud, the
     // level's own grey frame (and, distorted and masked or covered, its mask into d_ud_mask), which the warps and their masks read
     // instead.  Reduced and distorted: reduced into d_small, which the undistortion node reads in d_frame's place.
-    uint8_t *d_ud = nullptr, *d_ud_mask = nullptr, *d_small = nullptr;  // [H][W] each
+    DeviceBuffer d_ud, d_ud_mask, d_small;      // uint8_t [H][W] each
 };
 
 extern "C" {
@@ -99,17 +99,6 @@ int nmi_level_destroy(nmi_level *lv)
     (void)hipStreamSynchronize(lv->ctx->stream);
     if (lv->exec) (void)hipGraphExecDestroy(lv->exec);
     if (lv->graph) (void)hipGraphDestroy(lv->graph);
-    void *dev[] = {lv->d_kept, lv->d_kept_count, lv->d_packed, lv->d_renders, lv->d_warps, lv->d_zbuf, lv->d_mvps, lv->d_coeffs, lv->d_order, lv->d_key, lv->d_done, lv->d_ratings, lv->d_epoch, lv->d_pix_blocks,
-                   lv->d_masks, lv->d_counts, lv->d_tables, lv->d_redo, lv->d_redo_state, lv->d_rmasks, lv->d_cover_counts, lv->d_ud, lv->d_ud_mask, lv->d_small};
-    for (void *q : dev)
-        if (q) (void)hipFree(q);
-    void *host[] = {lv->h_mvps, lv->h_coeffs, lv->h_key};
-    for (void *q : host)
-        if (q) (void)hipHostFree(q);
-    if (lv->ev_fork) (void)hipEventDestroy(lv->ev_fork);
-    if (lv->ev_join) (void)hipEventDestroy(lv->ev_join);
-    if (lv->side) (void)hipStreamDestroy(lv->side);
-    mesh_work_free(&lv->mesh);
     delete lv;
     return NMI_OK;
 }
@@ -134,7 +123,7 @@ static LevelNeeds level_needs(const LevelSettings &s)
 }
 
 struct LevelBuffer {
-    void **slot;
+    DeviceBuffer *slot;
     size_t bytes, zeroed;  // its size, and how much of it starts as zero
     bool needed;
 };
@@ -143,16 +132,16 @@ static std::vector<LevelBuffer> level_buffers(nmi_level *lv, const LevelSettings
 {
     const LevelNeeds n = level_needs(s);
     const size_t npix = (size_t)lv->ctx->npix, S = (size_t)lv->S, Wn = (size_t)lv->Wn, cells = S * Wn * sizeof(int32_t);
-    return {{(void **)&lv->d_masks, npix * Wn, npix * Wn, n.mode},
-            {(void **)&lv->d_redo, cells, 0, n.mode},
-            {(void **)&lv->d_redo_state, 2 * sizeof(uint32_t), 2 * sizeof(uint32_t), n.mode},
-            {(void **)&lv->d_counts, 3 * Wn * sizeof(int32_t), Wn * sizeof(int32_t), n.masks},
-            {(void **)&lv->d_tables, Wn * (npix + 1) * sizeof(float), 0, n.masks},
-            {(void **)&lv->d_rmasks, npix * S, npix * S, n.cover},
-            {(void **)&lv->d_cover_counts, cells, cells, n.cover},
-            {(void **)&lv->d_ud, npix, 0, n.ud},
-            {(void **)&lv->d_ud_mask, npix, 0, n.ud_mask},
-            {(void **)&lv->d_small, npix, 0, n.small}};
+    return {{&lv->d_masks, npix * Wn, npix * Wn, n.mode},
+            {&lv->d_redo, cells, 0, n.mode},
+            {&lv->d_redo_state, 2 * sizeof(uint32_t), 2 * sizeof(uint32_t), n.mode},
+            {&lv->d_counts, 3 * Wn * sizeof(int32_t), Wn * sizeof(int32_t), n.masks},
+            {&lv->d_tables, Wn * (npix + 1) * sizeof(float), 0, n.masks},
+            {&lv->d_rmasks, npix * S, npix * S, n.cover},
+            {&lv->d_cover_counts, cells, cells, n.cover},
+            {&lv->d_ud, npix, 0, n.ud},
+            {&lv->d_ud_mask, npix, 0, n.ud_mask},
+            {&lv->d_small, npix, 0, n.small}};
 }
 
 // Captures the level's graph for lv->set and instantiates it, replacing the previous one only on success.  The caller has waited
@@ -167,15 +156,23 @@ static int level_capture(nmi_level *lv)
     const bool mesh = lv->kind != MapKind::points;
     const float *d_xyz = lv->d_xyz, *d_attr = lv->d_attr, *d_red = lv->d_attr;
     const int64_t n_points = lv->n_points;
-    float *hd_mvps = lv->hd_mvps, *hd_coeffs = lv->hd_coeffs;
+    float *hd_mvps = lv->h_mvps.device<float>(), *hd_coeffs = lv->h_coeffs.device<float>();
+    // typed views of the level's buffers (null where the settings need none: level_buffers)
+    uint8_t *d_renders = lv->d_renders.as<uint8_t>(), *d_warps = lv->d_warps.as<uint8_t>(), *d_masks = lv->d_masks.as<uint8_t>();
+    uint8_t *d_rmasks = lv->d_rmasks.as<uint8_t>(), *d_ud = lv->d_ud.as<uint8_t>(), *d_small = lv->d_small.as<uint8_t>();
+    uint32_t *d_zbuf = lv->d_zbuf.as<uint32_t>(), *d_epoch = lv->d_epoch.as<uint32_t>(), *d_kept = lv->d_kept.as<uint32_t>();
+    uint32_t *d_kept_count = lv->d_kept_count.as<uint32_t>(), *d_redo_state = lv->d_redo_state.as<uint32_t>();
+    float *d_mvps = lv->d_mvps.as<float>(), *d_coeffs = lv->d_coeffs.as<float>(), *d_tables = lv->d_tables.as<float>();
+    int32_t *d_counts = lv->d_counts.as<int32_t>(), *d_cover_counts = lv->d_cover_counts.as<int32_t>(), *d_redo = lv->d_redo.as<int32_t>();
+    void *d_packed = lv->d_packed.as<>();
     FirstError ok;
     // Distorted or coloured: the chain reads the level's own grey (undistorted) frame (16-byte aligned: the fused front kernels
     // stay eligible) and, distorted and masked or covered, its mask.  A frame mask is dense [H][W] in every format.
     const LevelSettings &set = lv->set;
     const FrameIntake &in = set.intake;
     const bool masked = set.masked, covered = set.covered;
-    uint8_t *ud_mask = level_needs(set).ud_mask ? lv->d_ud_mask : nullptr;
-    const uint8_t *d_frame = in.own_frame() ? lv->d_ud : lv->d_frame;
+    uint8_t *ud_mask = level_needs(set).ud_mask ? lv->d_ud_mask.as<uint8_t>() : nullptr;
+    const uint8_t *d_frame = in.own_frame() ? d_ud : lv->d_frame;
     const uint8_t *d_frame_mask = in.distorted ? ud_mask : set.d_frame_mask;
     nmi::GridArgs a = lv->args;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
@@ -185,71 +182,66 @@ static int level_capture(nmi_level *lv)
     lv->pix = plan.pix;
     if (lv->pix) {
         const size_t bytes = nmi::pix_block_bytes((int)total, lv->pix);
-        if (bytes > lv->pix_blocks_bytes) {
-            if (lv->d_pix_blocks) ok(hipFree(lv->d_pix_blocks));
-            lv->d_pix_blocks = nullptr;
-            lv->pix_blocks_bytes = 0;
-            ok(hipMalloc((void **)&lv->d_pix_blocks, bytes));
-            if (ok.e == hipSuccess) ok(hipMemset(lv->d_pix_blocks, 0, bytes));
-            if (ok.e == hipSuccess) lv->pix_blocks_bytes = bytes;
-        }
+        // (no wait of its own: level_apply has waited; cleared at once, not on the stream)
+        if (bytes > lv->d_pix_blocks.size() && ok(lv->d_pix_blocks.grow(bytes)) && !ok(hipMemset(lv->d_pix_blocks.as<>(), 0, bytes)))
+            (void)lv->d_pix_blocks.reset();
         if (ok.e == hipSuccess && prepare_pix_handoff(ctx, &lv->args.epoch) != NMI_OK) ok.e = hipErrorOutOfMemory;
         if (ok.e == hipSuccess) ok(hipStreamSynchronize(ctx->stream));
         a.epoch = lv->args.epoch;
-        a.blocks = lv->d_pix_blocks;
+        a.blocks = lv->d_pix_blocks.as<unsigned long long>();
         a.order = nullptr;
     }
     const int workgroups = lv->workgroups;
     nmi::GridArgs ma = a;
     ma.phase_mask = plan.phase_mask;  // (bit 9: the pixel-range kernel's hand-off test hook)
-    const MaskSearch ms = mask_search_args(ma, MaskSide{lv->d_masks, covered ? lv->d_rmasks : nullptr, covered ? lv->d_cover_counts : lv->d_counts,
-                                                        lv->d_tables, lv->d_redo, lv->d_redo_state});
-    uint8_t *cover = covered ? lv->d_rmasks : nullptr;  // the renderers' coverage masks
-    int32_t *d_prev = lv->d_counts + Wn, *d_changed = lv->d_counts + 2 * Wn;
+    const MaskSearch ms = mask_search_args(ma, MaskSide{d_masks, covered ? d_rmasks : nullptr, covered ? d_cover_counts : d_counts,
+                                                        d_tables, d_redo, d_redo_state});
+    uint8_t *cover = covered ? d_rmasks : nullptr;  // the renderers' coverage masks
+    int32_t *d_prev = d_counts + Wn, *d_changed = d_counts + 2 * Wn;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipStream_t st = ctx->stream;
     if (ok.e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
         // (mesh: nothing to clear -- the renderer leaves its work area clean)
-        ok(nmi::launch_level_prep(hd_mvps, lv->d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, lv->d_coeffs, Wn * 9, lv->d_key, lv->d_zbuf,
+        ok(nmi::launch_level_prep(hd_mvps, d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, d_coeffs, Wn * 9, lv->d_key.as<unsigned long long>(), d_zbuf,
                                   (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
-                                  lv->d_epoch, lv->fused_points ? lv->d_packed : nullptr, n_points,
-                                  lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, lv->d_kept, lv->d_kept_count));
-        ok(launch_intake(in, lv->d_frame, in.frame_pitch, set.d_frame_mask, lv->d_small, lv->d_ud, ud_mask, p.width, p.height, st));
+                                  d_epoch, lv->fused_points ? d_packed : nullptr, n_points,
+                                  lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, d_kept, d_kept_count));
+        ok(launch_intake(in, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
-        const bool fused = mesh ? (nmi::level_front_eligible(d_frame, lv->d_warps, p.width, S) && n_points > 0) : lv->fused_points;
+        const bool fused = mesh ? (nmi::level_front_eligible(d_frame, d_warps, p.width, S) && n_points > 0) : lv->fused_points;
         // Masked: the masks, their counts and the changed warps' tables on that branch too (they need the inverse maps only),
         // beside the render.  Covered: the masks alone (no counts, no tables: len[w][s] is counted by the search).
         if (!fused || masked || covered) {
             ok(hipEventRecord(lv->ev_fork, st));
             ok(hipStreamWaitEvent(lv->side, lv->ev_fork, 0));
-            if (!fused) ok(nmi::launch_warp(d_frame, lv->d_coeffs, lv->d_warps, p.width, p.height, Wn, lv->side));
+            if (!fused) ok(nmi::launch_warp(d_frame, d_coeffs, d_warps, p.width, p.height, Wn, lv->side));
             if (masked) {
-                ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
-                ok(nmi::launch_level_mask_counts(lv->d_masks, Wn, ctx->npix, lv->d_counts, d_prev, d_changed, lv->side));
-                ok(nmi::launch_level_mask_tables(lv->d_counts, d_changed, Wn, ctx->npix, lv->d_tables, lv->side));
+                ok(nmi::launch_warp_masks(d_frame_mask, d_coeffs, d_masks, p.width, p.height, Wn, lv->side));
+                ok(nmi::launch_level_mask_counts(d_masks, Wn, ctx->npix, d_counts, d_prev, d_changed, lv->side));
+                ok(nmi::launch_level_mask_tables(d_counts, d_changed, Wn, ctx->npix, d_tables, lv->side));
             }
-            if (covered) ok(nmi::launch_warp_masks(d_frame_mask, lv->d_coeffs, lv->d_masks, p.width, p.height, Wn, lv->side));
+            if (covered) ok(nmi::launch_warp_masks(d_frame_mask, d_coeffs, d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
         if (mesh)
-            ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, lv->d_mvps, S, lv->mesh, S,
-                                       (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, lv->d_renders,
-                                       p.width, p.height, st, fused ? d_frame : nullptr, lv->d_coeffs, lv->d_warps, Wn, cover));
+            ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, d_mvps, S, lv->mesh.view, S,
+                                       (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, d_renders,
+                                       p.width, p.height, st, fused ? d_frame : nullptr, d_coeffs, d_warps, Wn, cover));
         else if (fused)
-            ok(nmi::launch_level_front_points(lv->d_packed, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_epoch, lv->d_renders, p.width, p.height,
-                                              lv->size, d_frame, lv->d_coeffs, lv->d_warps, Wn, st, lv->d_kept, lv->d_kept_count, ctx->compute_units,
+            ok(nmi::launch_level_front_points(d_packed, n_points, d_mvps, S, d_zbuf, d_epoch, d_renders, p.width, p.height,
+                                              lv->size, d_frame, d_coeffs, d_warps, Wn, st, d_kept, d_kept_count, ctx->compute_units,
                                               cover));
         else
-            ok(nmi::launch_render_points(d_xyz, d_red, n_points, lv->d_mvps, S, lv->d_zbuf, lv->d_renders, p.width, p.height, lv->size, st,
+            ok(nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, d_zbuf, d_renders, p.width, p.height, lv->size, st,
                                          /*clear_first=*/false, cover));
         if (!fused || masked || covered) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
         if (masked || covered)
-            ok(launch_mask_search(ms, lv->pix, lv->pix ? pix_owner_share(ctx, lv->pix) : 0.0, workgroups, true, false, lv->d_epoch,
-                                  ctx->d_pix_timeouts, st));
+            ok(launch_mask_search(ms, lv->pix, lv->pix ? pix_owner_share(ctx, lv->pix) : 0.0, workgroups, true, false, d_epoch,
+                                  ctx->d_pix_timeouts.as<uint32_t>(), st));
         else if (lv->pix)
-            ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, lv->d_epoch, ctx->d_pix_timeouts, st));
+            ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, d_epoch, ctx->d_pix_timeouts.as<uint32_t>(), st));
         else
             ok(nmi::launch_grid(a, workgroups, true, st));
         hipError_t ec = hipStreamEndCapture(st, &graph);
@@ -281,14 +273,14 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a replay in flight still reads the buffers and the graph
     FirstError ok;
-    std::vector<void **> fresh;  // allocated by this call
+    std::vector<DeviceBuffer *> fresh;  // allocated by this call
     for (const LevelBuffer &b : level_buffers(lv, next)) {
         if (!b.needed || *b.slot || ok.e != hipSuccess) continue;
-        if (ok(hipMalloc(b.slot, b.bytes))) fresh.push_back(b.slot);
-        if (ok.e == hipSuccess && b.zeroed) ok(hipMemset(*b.slot, 0, b.zeroed));
+        if (ok(b.slot->alloc(b.bytes))) fresh.push_back(b.slot);
+        if (ok.e == hipSuccess && b.zeroed) ok(hipMemset(b.slot->as<>(), 0, b.zeroed));
     }
     // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
-    if (ok.e == hipSuccess && all_tables) ok(hipMemset(lv->d_counts + lv->Wn, 0xFF, (size_t)lv->Wn * sizeof(int32_t)));
+    if (ok.e == hipSuccess && all_tables) ok(hipMemset(lv->d_counts.as<int32_t>() + lv->Wn, 0xFF, (size_t)lv->Wn * sizeof(int32_t)));
     int rc = ok.e == hipSuccess ? NMI_OK : hip_fail(ctx, ok.e, what);
     const LevelSettings was = lv->set;
     if (rc == NMI_OK) {
@@ -297,17 +289,11 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     }
     if (rc != NMI_OK) {
         lv->set = was;
-        for (void **slot : fresh) {
-            (void)hipFree(*slot);
-            *slot = nullptr;
-        }
+        for (DeviceBuffer *slot : fresh) (void)slot->reset();
         return rc;
     }
     for (const LevelBuffer &b : level_buffers(lv, lv->set))  // no graph reads these any more
-        if (!b.needed && *b.slot) {
-            (void)hipFree(*b.slot);
-            *b.slot = nullptr;
-        }
+        if (!b.needed) (void)b.slot->reset();
     return NMI_OK;
 }
 
@@ -349,8 +335,8 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     if (S == 0 || Wn == 0) {
         // An empty block (more ranks than cells on the sharded axis): nothing to render, warp or score.  The rank still owns
         // a key word -- "no candidate" -- for the level's collective (nmi_level_run_rccl).
-        hipError_t e0 = hipMalloc((void **)&lv->d_key, sizeof(unsigned long long));
-        if (e0 == hipSuccess) e0 = hipMemset(lv->d_key, 0, sizeof(unsigned long long));
+        hipError_t e0 = lv->d_key.alloc(sizeof(unsigned long long));
+        if (e0 == hipSuccess) e0 = hipMemset(lv->d_key.as<>(), 0, sizeof(unsigned long long));
         if (e0 != hipSuccess) {
             const int rc = hip_fail(ctx, e0, "nmi_level_create (empty block)");
             nmi_level_destroy(lv);
@@ -364,44 +350,45 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     const size_t npix = (size_t)ctx->npix;
     const int64_t total = (int64_t)S * Wn;
     FirstError ok;
-    ok(hipMalloc((void **)&lv->d_renders, npix * S));
-    ok(hipMalloc((void **)&lv->d_warps, npix * Wn));
+    ok(lv->d_renders.alloc(npix * S));
+    ok(lv->d_warps.alloc(npix * Wn));
     if (mesh) {
         if (mesh_work_alloc(ctx, S, &lv->mesh) != NMI_OK) ok.e = hipErrorOutOfMemory;
         if (ok.e == hipSuccess && ensure_mesh_pairs(ctx, &lv->mesh, n_points) != NMI_OK) ok.e = hipErrorOutOfMemory;
-        ok(hipMalloc((void **)&lv->d_epoch, sizeof(uint32_t)));
-        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
+        ok(lv->d_epoch.alloc(sizeof(uint32_t)));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch.as<>(), 0, sizeof(uint32_t), ctx->stream));
     } else {
         // Anchors: two buffers when the level runs as one chain of kernels (the front kernel of replay k clears the buffer of
         // replay k + 1); the classic form keeps one and clears it in its prep node.
         lv->fused_points = nmi::level_front_eligible(d_frame, nullptr, p.width, S) && n_points > 0 && nmi::level_points_double_buffered(p.width, lv->size);
         const size_t words = lv->fused_points ? 2 * nmi::level_zbuf_pair_words(S, p.width, p.height, lv->size)
                                               : nmi::render_zbuf_words(S, p.width, p.height, lv->size);
-        ok(hipMalloc((void **)&lv->d_zbuf, words * sizeof(uint32_t)));
-        ok(hipMalloc((void **)&lv->d_epoch, sizeof(uint32_t)));
-        ok(hipMalloc(&lv->d_packed, nmi::cloud_pack_bytes(n_points, nullptr) + 16));
-        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_zbuf, 0xFF, words * sizeof(uint32_t), ctx->stream));
-        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch, 0, sizeof(uint32_t), ctx->stream));
-        if (ok.e == hipSuccess) ok(nmi::launch_cloud_pack(d_xyz, d_red, n_points, lv->d_packed, ctx->stream));
+        ok(lv->d_zbuf.alloc(words * sizeof(uint32_t)));
+        ok(lv->d_epoch.alloc(sizeof(uint32_t)));
+        ok(lv->d_packed.alloc(nmi::cloud_pack_bytes(n_points, nullptr) + 16));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_zbuf.as<>(), 0xFF, words * sizeof(uint32_t), ctx->stream));
+        if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch.as<>(), 0, sizeof(uint32_t), ctx->stream));
+        if (ok.e == hipSuccess) ok(nmi::launch_cloud_pack(d_xyz, d_red, n_points, lv->d_packed.as<>(), ctx->stream));
         if (lv->fused_points) {
-            ok(hipMalloc((void **)&lv->d_kept, (size_t)(2 * ((n_points + 63) / 64) + 1) * sizeof(uint32_t)));   // (twice the most one replay lists)
-            ok(hipMalloc((void **)&lv->d_kept_count, 2 * sizeof(uint32_t)));
-            if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_kept_count, 0, 2 * sizeof(uint32_t), ctx->stream));
+            ok(lv->d_kept.alloc((size_t)(2 * ((n_points + 63) / 64) + 1) * sizeof(uint32_t)));   // (twice the most one replay lists)
+            ok(lv->d_kept_count.alloc(2 * sizeof(uint32_t)));
+            if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_kept_count.as<>(), 0, 2 * sizeof(uint32_t), ctx->stream));
         }
     }
-    ok(hipMalloc((void **)&lv->d_mvps, ((size_t)S * 16 + nmi::kLevelMvpExtra) * sizeof(float)));
-    ok(hipMalloc((void **)&lv->d_coeffs, (size_t)Wn * 9 * sizeof(float)));
-    ok(hipMalloc((void **)&lv->d_order, (size_t)total * sizeof(int)));
-    ok(hipMalloc((void **)&lv->d_ratings, (size_t)total * sizeof(float)));
-    ok(hipMalloc((void **)&lv->d_key, sizeof(unsigned long long)));
-    ok(hipMalloc((void **)&lv->d_done, sizeof(unsigned int)));
+    const size_t mvp_bytes = ((size_t)S * 16 + nmi::kLevelMvpExtra) * sizeof(float), coeff_bytes = (size_t)Wn * 9 * sizeof(float);
+    ok(lv->d_mvps.alloc(mvp_bytes));
+    ok(lv->d_coeffs.alloc(coeff_bytes));
+    ok(lv->d_order.alloc((size_t)total * sizeof(int)));
+    ok(lv->d_ratings.alloc((size_t)total * sizeof(float)));
+    ok(lv->d_key.alloc(sizeof(unsigned long long)));
+    ok(lv->d_done.alloc(sizeof(unsigned int)));
     // pinned, device-mapped, fine-grained: the prep kernel reads the parameters and the search kernel posts the winner
-    ok(hipHostMalloc((void **)&lv->h_mvps, ((size_t)S * 16 + nmi::kLevelMvpExtra) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-    ok(hipHostMalloc((void **)&lv->h_coeffs, (size_t)Wn * 9 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-    ok(hipHostMalloc((void **)&lv->h_key, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    ok(hipStreamCreateWithFlags(&lv->side, hipStreamNonBlocking));
-    ok(hipEventCreateWithFlags(&lv->ev_fork, hipEventDisableTiming));
-    ok(hipEventCreateWithFlags(&lv->ev_join, hipEventDisableTiming));
+    ok(lv->h_mvps.alloc(mvp_bytes, nmi_mem::kPosted));
+    ok(lv->h_coeffs.alloc(coeff_bytes, nmi_mem::kPosted));
+    ok(lv->h_key.alloc(sizeof(unsigned long long), nmi_mem::kPosted));
+    ok(lv->side.create(hipStreamNonBlocking));
+    ok(lv->ev_fork.create(hipEventDisableTiming));
+    ok(lv->ev_join.create(hipEventDisableTiming));
     int *order = ok.e == hipSuccess ? new (std::nothrow) int[(size_t)total] : nullptr;
     if (ok.e != hipSuccess || !order) {
         const int rc = ok.e != hipSuccess ? hip_fail(ctx, ok.e, "nmi_level_create") : NMI_ERR_INVALID_ARGUMENT;
@@ -409,38 +396,31 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
         return rc;
     }
     build_order(S, Wn, order);
-    ok(hipMemcpy(lv->d_order, order, (size_t)total * sizeof(int), hipMemcpyHostToDevice));
+    ok(hipMemcpy(lv->d_order.as<>(), order, (size_t)total * sizeof(int), hipMemcpyHostToDevice));
     delete[] order;
-    ok(hipMemset(lv->d_done, 0, sizeof(unsigned int)));
-    memset(lv->h_mvps, 0, ((size_t)S * 16 + nmi::kLevelMvpExtra) * sizeof(float));
-    memset(lv->h_coeffs, 0, (size_t)Wn * 9 * sizeof(float));
+    ok(hipMemset(lv->d_done.as<>(), 0, sizeof(unsigned int)));
+    memset(lv->h_mvps.as<>(), 0, mvp_bytes);
+    memset(lv->h_coeffs.as<>(), 0, coeff_bytes);
     ok(hipDeviceSynchronize());
 
     nmi::GridArgs a{};
-    a.render_stack = lv->d_renders;
-    a.warp_stack = lv->d_warps;
+    a.render_stack = lv->d_renders.as<uint8_t>();
+    a.warp_stack = lv->d_warps.as<uint8_t>();
     a.S_local = S;
     a.Wn = Wn;
     a.s_offset = blk.s_offset;  // global indices in the key (commit_score): the winner of a block is a cell of the whole level
     a.S_total = blk.S_total;
     a.w_offset = blk.w_offset;
-    nmi::set_geometry(a, p.width, p.height, lv->d_renders, lv->d_warps, p.render_bottom_up != 0);
+    nmi::set_geometry(a, p.width, p.height, a.render_stack, a.warp_stack, p.render_bottom_up != 0);
     a.shift = ctx->shift;
     a.mode = p.mode;
-    a.table = ctx->table;
-    a.order = lv->d_order;
-    a.ratings = lv->d_ratings;  // 4 bytes per candidate: kept so that a level can be checked against an oracle (nmi_level_copy_outputs)
-    a.key = lv->d_key;        // reset by the prep node before every replay (the ping-pong of plain launches needs
+    a.table = ctx->table.as<float>();
+    a.order = lv->d_order.as<int>();
+    a.ratings = lv->d_ratings.as<float>();  // 4 bytes per candidate: kept so that a level can be checked against an oracle (nmi_level_copy_outputs)
+    a.key = lv->d_key.as<unsigned long long>();  // reset by the prep node before every replay (the ping-pong of plain launches needs
     a.reset_key = nullptr;    // alternating arguments, which a replayed graph does not have)
-    a.done = lv->d_done;
-    float *hd_mvps = nullptr, *hd_coeffs = nullptr;
-    unsigned long long *hd_key = nullptr;
-    if (ok.e == hipSuccess) {
-        ok(hipHostGetDevicePointer((void **)&hd_mvps, lv->h_mvps, 0));
-        ok(hipHostGetDevicePointer((void **)&hd_coeffs, lv->h_coeffs, 0));
-        ok(hipHostGetDevicePointer((void **)&hd_key, lv->h_key, 0));
-    }
-    a.out_key = hd_key;
+    a.done = lv->d_done.as<unsigned int>();
+    a.out_key = lv->h_key.device<unsigned long long>();
     a.hist_variant = 3;
     a.phase_mask = 3;
     // the graph (level_capture) is made from these; level_apply captures it again from them
@@ -450,8 +430,6 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     lv->tex = tex;
     lv->d_frame = d_frame;
     lv->args = a;
-    lv->hd_mvps = hd_mvps;
-    lv->hd_coeffs = hd_coeffs;
     lv->workgroups = nmi::grid_workgroups(total, ctx->workgroups, ctx->compute_units);
     if (ok.e == hipSuccess) {
         const int rc = level_capture(lv);
@@ -527,15 +505,16 @@ static int level_launch(nmi_level *lv, const float *h_mvps, const double *h_forw
     std::vector<float> coeffs((size_t)lv->Wn * 9);
     for (int w = 0; w < lv->Wn; ++w)
         if (warp_inverse_coeffs(h_forward + (size_t)w * 9, coeffs.data() + (size_t)w * 9) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    memcpy(lv->h_mvps, h_mvps, (size_t)lv->S * 16 * sizeof(float));
-    nmi::level_views_bound(h_mvps, lv->S, lv->h_mvps + (size_t)lv->S * 16);  // for the front kernel's first test: all views at once
+    float *own_mvps = lv->h_mvps.as<float>();
+    memcpy(own_mvps, h_mvps, (size_t)lv->S * 16 * sizeof(float));
+    nmi::level_views_bound(h_mvps, lv->S, own_mvps + (size_t)lv->S * 16);  // for the front kernel's first test: all views at once
     static const bool no_bound = getenv("NMI_LEVEL_NO_BOUND") != nullptr;      // measurement switch: six zero planes cull nothing
-    if (no_bound) memset(lv->h_mvps + (size_t)lv->S * 16, 0, 24 * sizeof(float));
+    if (no_bound) memset(own_mvps + (size_t)lv->S * 16, 0, 24 * sizeof(float));
     const uint32_t parity = ++lv->replay & 1u;  // which of its two counters the prep kernel's cull counts under (it zeroes the other one)
-    memcpy(lv->h_mvps + (size_t)lv->S * 16 + 24, &parity, sizeof parity);
-    memcpy(lv->h_coeffs, coeffs.data(), coeffs.size() * sizeof(float));
+    memcpy(own_mvps + (size_t)lv->S * 16 + 24, &parity, sizeof parity);
+    memcpy(lv->h_coeffs.as<>(), coeffs.data(), coeffs.size() * sizeof(float));
     constexpr unsigned long long kPending = ~0ull;
-    __atomic_store_n(lv->h_key, kPending, __ATOMIC_RELEASE);
+    __atomic_store_n(lv->h_key.as<unsigned long long>(), kPending, __ATOMIC_RELEASE);
     const hipError_t le = hipGraphLaunch(lv->exec, ctx->stream);
     if (le != hipSuccess) {
         --lv->replay;  // (the replay did not run: its counter has not been counted into, the other one has not been zeroed)
@@ -549,7 +528,7 @@ static int level_launch(nmi_level *lv, const float *h_mvps, const double *h_forw
 int nmi_internal::level_enqueue(nmi_level *lv, const float *h_mvps, const double *h_forward, const unsigned long long **d_key)
 {
     if (!lv || !d_key) return NMI_ERR_INVALID_ARGUMENT;
-    *d_key = lv->d_key;
+    *d_key = lv->d_key.as<unsigned long long>();
     if (lv->S == 0 || lv->Wn == 0) return NMI_OK;  // d_key holds 0 = "no candidate" since creation
     if (!h_mvps || !h_forward) return NMI_ERR_INVALID_ARGUMENT;
     lv->ctx->detail.clear();
@@ -574,13 +553,14 @@ int nmi_level_run(nmi_level *lv, const float *h_mvps, const double *h_forward, i
     constexpr unsigned long long kPending = ~0ull;
     const int lrc = level_launch(lv, h_mvps, h_forward);
     if (lrc != NMI_OK) return lrc;
+    const unsigned long long *h_key = lv->h_key.as<unsigned long long>();
     unsigned long long key = kPending;
     for (uint64_t spin = 0; key == kPending; ++spin) {
-        key = __atomic_load_n(lv->h_key, __ATOMIC_ACQUIRE);
+        key = __atomic_load_n(h_key, __ATOMIC_ACQUIRE);
         if (key == kPending && (spin & 0xFFFF) == 0xFFFF) {
             const hipError_t q = hipStreamQuery(ctx->stream);  // a faulted or finished stream must not leave us spinning
             if (q == hipSuccess) {
-                key = __atomic_load_n(lv->h_key, __ATOMIC_ACQUIRE);
+                key = __atomic_load_n(h_key, __ATOMIC_ACQUIRE);
                 break;
             }
             if (q != hipErrorNotReady) return hip_fail(ctx, q, "hipStreamQuery");
@@ -598,9 +578,9 @@ int nmi_level_copy_outputs(nmi_level *lv, uint8_t *h_renders, uint8_t *h_warps, 
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // nmi_level_run returns when the winner is posted, a little before the graph has drained
     const size_t npix = (size_t)ctx->npix;
-    if (h_renders) NMI_HIP_TRY(ctx, hipMemcpy(h_renders, lv->d_renders, npix * lv->S, hipMemcpyDeviceToHost));
-    if (h_warps) NMI_HIP_TRY(ctx, hipMemcpy(h_warps, lv->d_warps, npix * lv->Wn, hipMemcpyDeviceToHost));
-    if (h_ratings) NMI_HIP_TRY(ctx, hipMemcpy(h_ratings, lv->d_ratings, (size_t)lv->S * lv->Wn * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_renders) NMI_HIP_TRY(ctx, hipMemcpy(h_renders, lv->d_renders.as<>(), npix * lv->S, hipMemcpyDeviceToHost));
+    if (h_warps) NMI_HIP_TRY(ctx, hipMemcpy(h_warps, lv->d_warps.as<>(), npix * lv->Wn, hipMemcpyDeviceToHost));
+    if (h_ratings) NMI_HIP_TRY(ctx, hipMemcpy(h_ratings, lv->d_ratings.as<>(), (size_t)lv->S * lv->Wn * sizeof(float), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 
@@ -621,8 +601,8 @@ int nmi_level_copy_masks(nmi_level *lv, uint8_t *h_warp_masks, int32_t *h_counts
     nmi_ctx *ctx = lv->ctx;
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks, (size_t)ctx->npix * lv->Wn, hipMemcpyDeviceToHost));
-    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_counts, (size_t)lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks.as<>(), (size_t)ctx->npix * lv->Wn, hipMemcpyDeviceToHost));
+    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_counts.as<>(), (size_t)lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 
@@ -644,9 +624,9 @@ int nmi_level_copy_coverage(nmi_level *lv, uint8_t *h_render_masks, uint8_t *h_w
     DeviceGuard guard(ctx->device);
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->npix;
-    if (h_render_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_render_masks, lv->d_rmasks, npix * lv->S, hipMemcpyDeviceToHost));
-    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks, npix * lv->Wn, hipMemcpyDeviceToHost));
-    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_cover_counts, (size_t)lv->S * lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (h_render_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_render_masks, lv->d_rmasks.as<>(), npix * lv->S, hipMemcpyDeviceToHost));
+    if (h_warp_masks) NMI_HIP_TRY(ctx, hipMemcpy(h_warp_masks, lv->d_masks.as<>(), npix * lv->Wn, hipMemcpyDeviceToHost));
+    if (h_counts) NMI_HIP_TRY(ctx, hipMemcpy(h_counts, lv->d_cover_counts.as<>(), (size_t)lv->S * lv->Wn * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 
@@ -689,14 +669,14 @@ int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { r
 struct nmi_stream {
     nmi_ctx *ctx = nullptr;
     int depth = 0, max_S = 0, max_Wn = 0;
-    hipStream_t copy = nullptr;
+    nmi_mem::Stream copy;
     struct Slot {
-        uint8_t *d_renders = nullptr;
-        float *d_ratings = nullptr;  // [max_Wn][max_S], only with nmi_stream_keep_ratings
+        DeviceBuffer d_renders;      // uint8_t [max_S][H][W]
+        DeviceBuffer d_ratings;      // float [max_Wn][max_S], only with nmi_stream_keep_ratings
         int S = 0, Wn = 0;           // grid of the slot's latest submission
-        unsigned long long *d_key = nullptr;      // [2]: this rank's key, and the all-reduced one (block submissions with a communicator)
-        unsigned long long *h_key = nullptr;
-        hipEvent_t copied = nullptr, done = nullptr;
+        DeviceBuffer d_key;          // unsigned long long [2]: this rank's key, and the all-reduced one (block submissions with a communicator)
+        PinnedBuffer h_key;          // unsigned long long
+        nmi_mem::Event copied, done;
         int64_t ticket = -1;
         bool waited = true;
         bool failed = false;         // its search timed out in the split kernel and could not be redone (nmi_stream_wait)
@@ -708,13 +688,13 @@ struct nmi_stream {
         // masked / covered tickets (allocated on the stream's first such submission, see nmi_stream_submit_masked)
         int kind = 0;                // kPlain, kMasked, kCovered
         int64_t n_counts = 0;        // entries of d_counts the ticket wrote: len_w [Wn] (masked), len [Wn][S] (covered)
-        int32_t *d_counts = nullptr;  // [max_Wn * max_S]
-        uint8_t *d_bits = nullptr;   // [max_S][ceil(npix / 8)]: the render-mask bits, uploaded beside the render stack (covered)
+        DeviceBuffer d_counts;       // int32_t [max_Wn * max_S]
+        DeviceBuffer d_bits;         // uint8_t [max_S][ceil(npix / 8)]: the render-mask bits, uploaded beside the render stack (covered)
     };
-    Slot *slots = nullptr;
-    uint8_t *d_frame[2] = {nullptr, nullptr};  // frames alternate so an upload never overwrites one still being warped
-    uint8_t *d_warps[2] = {nullptr, nullptr};
-    hipEvent_t frame_copied = nullptr, warps_free[2] = {nullptr, nullptr};
+    std::vector<Slot> slots;   // [depth]
+    DeviceBuffer d_frame[2];   // uint8_t [H][W]: frames alternate so an upload never overwrites one still being warped
+    DeviceBuffer d_warps[2];   // uint8_t [max_Wn][H][W]
+    nmi_mem::Event frame_copied, warps_free[2];
     int warp_buf = 0;      // buffer holding the current warp stack
     uint64_t warp_gen[2] = {0, 0};  // refills of each warp buffer so far
     int cur_Wn = 0;
@@ -723,27 +703,26 @@ struct nmi_stream {
     int64_t next_ticket = 0;
     // Masks, beside the warp buffers: the frame mask and the warp masks of each buffer's frame, and -- for masked tickets --
     // len_w and the per-warp term tables, built once per frame submission (a frame-less ticket reuses them).
-    uint8_t *d_fmask[2] = {nullptr, nullptr};     // [H][W]
-    uint8_t *d_wmasks[2] = {nullptr, nullptr};    // [max_Wn][H][W]
-    int32_t *d_wcounts[2] = {nullptr, nullptr};   // [max_Wn]
-    float *d_wtables[2] = {nullptr, nullptr};     // [max_Wn][npix + 1]
+    DeviceBuffer d_fmask[2];                      // uint8_t [H][W]
+    DeviceBuffer d_wmasks[2];                     // uint8_t [max_Wn][H][W]
+    DeviceBuffer d_wcounts[2];                    // int32_t [max_Wn]
+    DeviceBuffer d_wtables[2];                    // float [max_Wn][npix + 1]
     bool masks_ok[2] = {false, false};            // the buffer's frame was submitted masked or covered: its warp masks exist
     bool tables_ok[2] = {false, false};           // ... and its len_w / tables have been built
     // Unpacked render masks of the covered ticket being searched.  ONE buffer for all slots: the unpack and the search that
     // reads it both run on the context's compute stream, so ticket i + 1's unpack cannot start before ticket i's search ended.
-    uint8_t *d_rmasks = nullptr;                  // [max_S][H][W]
-    int32_t *d_redo = nullptr;                    // [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
-    uint32_t *d_redo_state = nullptr;             // [2], zero between searches
+    DeviceBuffer d_rmasks;                        // uint8_t [max_S][H][W]
+    DeviceBuffer d_redo;                          // int32_t [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
+    DeviceBuffer d_redo_state;                    // uint32_t [2], zero between searches
     // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction): frames submitted while one of them
     // is set are brought on the compute stream into d_ud[b] (distorted, masked / covered: their masks into d_ud_mask[b]), and the
     // warps are made from those.  A coloured, pitched or full-size host frame (intake.colored) crosses as its rows of
     // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced and distorted, it is reduced into d_frame[b] (idle
     // meanwhile), which the undistortion reads as a grey frame.
     FrameIntake intake;
-    uint8_t *d_ud[2] = {nullptr, nullptr};        // [H][W], allocated on the first distorted (or coloured) frame
-    uint8_t *d_ud_mask[2] = {nullptr, nullptr};   // [H][W], allocated on the first distorted masked / covered frame
-    uint8_t *d_color[2] = {nullptr, nullptr};     // [f H][f W * bytes per pixel], allocated on the first coloured frame
-    size_t color_bytes = 0;                       // their size
+    DeviceBuffer d_ud[2];                         // uint8_t [H][W], allocated on the first distorted (or coloured) frame
+    DeviceBuffer d_ud_mask[2];                    // uint8_t [H][W], allocated on the first distorted masked / covered frame
+    DeviceBuffer d_color[2];                      // [f H][f W * bytes per pixel], allocated on the first coloured frame, grown for a larger one
 };
 
 namespace {
@@ -751,34 +730,28 @@ namespace {
 enum { kPlain = 0, kMasked = 1, kCovered = 2 };
 
 // Buffers of masked / covered tickets, allocated on the stream's first such submission (a plain-only stream never has them).
-// Each pointer is allocated once; after a failure the next submission allocates what is still missing.
+// Each buffer has one size and is allocated once (a grow that fits is no call at all); after a failure the next submission
+// allocates what is still missing.
 int stream_alloc_masks(nmi_stream *st, int kind)
 {
     nmi_ctx *ctx = st->ctx;
     const size_t npix = (size_t)ctx->npix, cells = (size_t)st->max_S * st->max_Wn;
-    auto alloc = [](void *p, size_t bytes) {
-        void **pp = (void **)p;
-        return *pp ? hipSuccess : hipMalloc(pp, bytes);
-    };
     for (int b = 0; b < 2; ++b) {
-        NMI_HIP_TRY(ctx, alloc(&st->d_fmask[b], npix));
-        NMI_HIP_TRY(ctx, alloc(&st->d_wmasks[b], npix * st->max_Wn));
+        NMI_HIP_TRY(ctx, st->d_fmask[b].grow(npix));
+        NMI_HIP_TRY(ctx, st->d_wmasks[b].grow(npix * st->max_Wn));
     }
-    for (int i = 0; i < st->depth; ++i) NMI_HIP_TRY(ctx, alloc(&st->slots[i].d_counts, cells * sizeof(int32_t)));
-    NMI_HIP_TRY(ctx, alloc(&st->d_redo, cells * sizeof(int32_t)));
-    if (!st->d_redo_state) {
-        NMI_HIP_TRY(ctx, alloc(&st->d_redo_state, 2 * sizeof(uint32_t)));
-        NMI_HIP_TRY(ctx, hipMemsetAsync(st->d_redo_state, 0, 2 * sizeof(uint32_t), ctx->stream));
-    }
+    for (nmi_stream::Slot &s : st->slots) NMI_HIP_TRY(ctx, s.d_counts.grow(cells * sizeof(int32_t)));
+    NMI_HIP_TRY(ctx, st->d_redo.grow(cells * sizeof(int32_t)));
+    NMI_HIP_TRY(ctx, st->d_redo_state.grow(2 * sizeof(uint32_t), ctx->stream, /*zero=*/true));
     if (kind == kMasked) {
         for (int b = 0; b < 2; ++b) {
-            NMI_HIP_TRY(ctx, alloc(&st->d_wcounts[b], (size_t)st->max_Wn * sizeof(int32_t)));
-            NMI_HIP_TRY(ctx, alloc(&st->d_wtables[b], (size_t)st->max_Wn * (npix + 1) * sizeof(float)));
+            NMI_HIP_TRY(ctx, st->d_wcounts[b].grow((size_t)st->max_Wn * sizeof(int32_t)));
+            NMI_HIP_TRY(ctx, st->d_wtables[b].grow((size_t)st->max_Wn * (npix + 1) * sizeof(float)));
         }
     }
     if (kind == kCovered) {
-        for (int i = 0; i < st->depth; ++i) NMI_HIP_TRY(ctx, alloc(&st->slots[i].d_bits, nmi::mask_bit_bytes(ctx->npix) * st->max_S));
-        NMI_HIP_TRY(ctx, alloc(&st->d_rmasks, npix * st->max_S));
+        for (nmi_stream::Slot &s : st->slots) NMI_HIP_TRY(ctx, s.d_bits.grow(nmi::mask_bit_bytes(ctx->npix) * st->max_S));
+        NMI_HIP_TRY(ctx, st->d_rmasks.grow(npix * st->max_S));
     }
     return NMI_OK;
 }
@@ -793,35 +766,6 @@ int nmi_stream_destroy(nmi_stream *st)
     DeviceGuard guard(st->ctx->device);
     (void)hipStreamSynchronize(st->ctx->stream);
     if (st->copy) (void)hipStreamSynchronize(st->copy);
-    for (int i = 0; st->slots && i < st->depth; ++i) {
-        nmi_stream::Slot &s = st->slots[i];
-        if (s.d_renders) (void)hipFree(s.d_renders);
-        if (s.d_ratings) (void)hipFree(s.d_ratings);
-        if (s.d_key) (void)hipFree(s.d_key);
-        if (s.h_key) (void)hipHostFree(s.h_key);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.d_counts) (void)hipFree(s.d_counts);
-        if (s.d_bits) (void)hipFree(s.d_bits);
-    }
-    delete[] st->slots;
-    for (int b = 0; b < 2; ++b) {
-        if (st->d_frame[b]) (void)hipFree(st->d_frame[b]);
-        if (st->d_warps[b]) (void)hipFree(st->d_warps[b]);
-        if (st->warps_free[b]) (void)hipEventDestroy(st->warps_free[b]);
-        if (st->d_fmask[b]) (void)hipFree(st->d_fmask[b]);
-        if (st->d_wmasks[b]) (void)hipFree(st->d_wmasks[b]);
-        if (st->d_wcounts[b]) (void)hipFree(st->d_wcounts[b]);
-        if (st->d_wtables[b]) (void)hipFree(st->d_wtables[b]);
-        if (st->d_ud[b]) (void)hipFree(st->d_ud[b]);
-        if (st->d_ud_mask[b]) (void)hipFree(st->d_ud_mask[b]);
-        if (st->d_color[b]) (void)hipFree(st->d_color[b]);
-    }
-    if (st->d_rmasks) (void)hipFree(st->d_rmasks);
-    if (st->d_redo) (void)hipFree(st->d_redo);
-    if (st->d_redo_state) (void)hipFree(st->d_redo_state);
-    if (st->frame_copied) (void)hipEventDestroy(st->frame_copied);
-    if (st->copy) (void)hipStreamDestroy(st->copy);
     delete st;
     return NMI_OK;
 }
@@ -837,26 +781,26 @@ int nmi_stream_create(nmi_ctx *ctx, int32_t max_S, int32_t max_Wn, int32_t depth
     st->depth = depth;
     st->max_S = max_S;
     st->max_Wn = max_Wn;
-    st->slots = new (std::nothrow) nmi_stream::Slot[depth];
+    st->slots = std::vector<nmi_stream::Slot>(depth);
     const size_t npix = (size_t)ctx->npix;
     FirstError ok;
-    ok(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
-    for (int i = 0; st->slots && i < depth && ok.e == hipSuccess; ++i) {
-        nmi_stream::Slot &s = st->slots[i];
-        ok(hipMalloc((void **)&s.d_renders, npix * max_S));
-        ok(hipMalloc((void **)&s.d_key, 2 * sizeof(unsigned long long)));
-        ok(hipHostMalloc((void **)&s.h_key, sizeof(unsigned long long), hipHostMallocDefault));
-        ok(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-        ok(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    ok(st->copy.create(hipStreamNonBlocking));
+    for (nmi_stream::Slot &s : st->slots) {
+        if (ok.e != hipSuccess) break;
+        ok(s.d_renders.alloc(npix * max_S));
+        ok(s.d_key.alloc(2 * sizeof(unsigned long long)));
+        ok(s.h_key.alloc(sizeof(unsigned long long), nmi_mem::kPinned));
+        ok(s.copied.create(hipEventDisableTiming));
+        ok(s.done.create(hipEventDisableTiming));
     }
     for (int b = 0; b < 2 && ok.e == hipSuccess; ++b) {
-        ok(hipMalloc((void **)&st->d_frame[b], npix));
-        ok(hipMalloc((void **)&st->d_warps[b], npix * max_Wn));
-        ok(hipEventCreateWithFlags(&st->warps_free[b], hipEventDisableTiming));
+        ok(st->d_frame[b].alloc(npix));
+        ok(st->d_warps[b].alloc(npix * max_Wn));
+        ok(st->warps_free[b].create(hipEventDisableTiming));
     }
-    ok(hipEventCreateWithFlags(&st->frame_copied, hipEventDisableTiming));
-    if (!st->slots || ok.e != hipSuccess) {
-        const int rc = st->slots ? hip_fail(ctx, ok.e, "nmi_stream_create") : NMI_ERR_INVALID_ARGUMENT;
+    ok(st->frame_copied.create(hipEventDisableTiming));
+    if (ok.e != hipSuccess) {
+        const int rc = hip_fail(ctx, ok.e, "nmi_stream_create");
         nmi_stream_destroy(st);
         return rc;
     }
@@ -906,47 +850,49 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
     const int64_t dense_row = (int64_t)factor * ctx->params.width * frame_bytes_per_pixel(in.frame_format);
     const size_t color_rows = (size_t)factor * ctx->params.height, color_need = (size_t)dense_row * color_rows;
     for (int b = 0; (undistort || colored) && b < 2; ++b) {
-        if (!st->d_ud[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud[b], npix));
-        if (undistort && kind != kPlain && !st->d_ud_mask[b]) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_ud_mask[b], npix));
+        NMI_HIP_TRY(ctx, st->d_ud[b].grow(npix));
+        if (undistort && kind != kPlain) NMI_HIP_TRY(ctx, st->d_ud_mask[b].grow(npix));
     }
-    if (colored && st->color_bytes < color_need) {  // (a wider format or a larger frame than the slots were made for)
+    if (colored && st->d_color[1].size() < color_need) {  // (a wider format or a larger frame than the slots were made for; [1] is allocated last)
         NMI_HIP_TRY(ctx, hipStreamSynchronize(st->copy));        // nothing in flight reads or fills the old slots
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        st->color_bytes = 0;
-        for (int b = 0; b < 2; ++b) {
-            if (st->d_color[b]) (void)hipFree(st->d_color[b]);
-            st->d_color[b] = nullptr;
-        }
-        for (int b = 0; b < 2; ++b) NMI_HIP_TRY(ctx, hipMalloc((void **)&st->d_color[b], color_need));
-        st->color_bytes = color_need;
+        for (int b = 0; b < 2; ++b) NMI_HIP_TRY(ctx, st->d_color[b].grow(color_need));
     }
 
+    // typed views of the slot's and the stream's buffers (a masked or covered ticket's: null on a stream that has had none)
+    uint8_t *d_renders = s.d_renders.as<uint8_t>(), *d_bits = s.d_bits.as<uint8_t>(), *d_rmasks = st->d_rmasks.as<uint8_t>();
+    unsigned long long *d_key = s.d_key.as<unsigned long long>();
+    int32_t *d_counts = s.d_counts.as<int32_t>(), *d_redo = st->d_redo.as<int32_t>();
+    uint32_t *d_redo_state = st->d_redo_state.as<uint32_t>();
+
     // copy stream: render stack of this level into the slot (the slot's previous search finished: it was waited for)
-    if (S > 0) NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_renders, h_render_stack, npix * S, hipMemcpyHostToDevice, st->copy));
+    if (S > 0) NMI_HIP_TRY(ctx, hipMemcpyAsync(d_renders, h_render_stack, npix * S, hipMemcpyHostToDevice, st->copy));
     if (kind == kCovered && S > 0)  // its coverage as bits: 1/8 of the render stack's bytes on the wire
-        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_bits, h_bits, nmi::mask_bit_bytes(ctx->npix) * S, hipMemcpyHostToDevice, st->copy));
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(d_bits, h_bits, nmi::mask_bit_bytes(ctx->npix) * S, hipMemcpyHostToDevice, st->copy));
     if (h_frame) {
         const int nb = st->have_warps ? st->warp_buf ^ 1 : 0;
+        uint8_t *d_frame = st->d_frame[nb].as<uint8_t>(), *d_fmask = st->d_fmask[nb].as<uint8_t>(), *d_color = st->d_color[nb].as<uint8_t>();
+        uint8_t *d_ud = st->d_ud[nb].as<uint8_t>(), *d_warps = st->d_warps[nb].as<uint8_t>(), *d_wmasks = st->d_wmasks[nb].as<uint8_t>();
         // the buffer being refilled was last read by searches submitted before the previous frame switch
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(st->copy, st->warps_free[nb], 0));
         if (colored)  // the rows of the host's pitch (H of them, or f H) into the dense colour slot
-            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(st->d_color[nb], (size_t)dense_row, h_frame, (size_t)in.frame_pitch, (size_t)dense_row, color_rows,
+            NMI_HIP_TRY(ctx, hipMemcpy2DAsync(d_color, (size_t)dense_row, h_frame, (size_t)in.frame_pitch, (size_t)dense_row, color_rows,
                                               hipMemcpyHostToDevice, st->copy));
         else
-            NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_frame[nb], h_frame, npix, hipMemcpyHostToDevice, st->copy));
-        if (h_frame_mask) NMI_HIP_TRY(ctx, hipMemcpyAsync(st->d_fmask[nb], h_frame_mask, npix, hipMemcpyHostToDevice, st->copy));
+            NMI_HIP_TRY(ctx, hipMemcpyAsync(d_frame, h_frame, npix, hipMemcpyHostToDevice, st->copy));
+        if (h_frame_mask) NMI_HIP_TRY(ctx, hipMemcpyAsync(d_fmask, h_frame_mask, npix, hipMemcpyHostToDevice, st->copy));
         NMI_HIP_TRY(ctx, hipEventRecord(st->frame_copied, st->copy));
         NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->frame_copied, 0));
         if (st->have_warps) NMI_HIP_TRY(ctx, hipEventRecord(st->warps_free[st->warp_buf], ctx->stream));
-        const uint8_t *frame = st->d_frame[nb], *frame_mask = h_frame_mask ? st->d_fmask[nb] : nullptr;
+        const uint8_t *frame = d_frame, *frame_mask = h_frame_mask ? d_fmask : nullptr;
         // the camera's frame (and mask) -> the grey, undistorted ones, on the compute stream: the warps read them next
-        uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb] : nullptr;
-        NMI_HIP_TRY(ctx, launch_intake(in, colored ? st->d_color[nb] : st->d_frame[nb], dense_row, frame_mask, st->d_frame[nb], st->d_ud[nb],
-                                       ud_mask, ctx->params.width, ctx->params.height, ctx->stream));
-        if (in.own_frame()) frame = st->d_ud[nb];
+        uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb].as<uint8_t>() : nullptr;
+        NMI_HIP_TRY(ctx, launch_intake(in, colored ? d_color : d_frame, dense_row, frame_mask, d_frame, d_ud, ud_mask, ctx->params.width,
+                                       ctx->params.height, ctx->stream));
+        if (in.own_frame()) frame = d_ud;
         if (undistort) frame_mask = ud_mask;
-        int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, st->d_warps[nb])
-                                : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, st->d_warps[nb], st->d_wmasks[nb]);
+        int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, d_warps)
+                                : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, d_warps, d_wmasks);
         if (rc != NMI_OK) return rc;
         st->warp_buf = nb;
         ++st->warp_gen[nb];
@@ -956,28 +902,29 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         st->tables_ok[nb] = false;
     }
     const int wb = st->warp_buf;
+    uint8_t *d_warps = st->d_warps[wb].as<uint8_t>(), *d_wmasks = st->d_wmasks[wb].as<uint8_t>();
+    int32_t *d_wcounts = st->d_wcounts[wb].as<int32_t>();
+    float *d_wtables = st->d_wtables[wb].as<float>();
     if (kind == kMasked && st->have_warps && !st->tables_ok[wb]) {
         // len_w and the per-warp term tables of this buffer's warp masks: once per frame (nmi_search_grid_masked's kernels)
-        NMI_HIP_TRY(ctx, nmi::launch_mask_counts(st->d_wmasks[wb], st->cur_Wn, ctx->npix, st->d_wcounts[wb], ctx->stream));
-        NMI_HIP_TRY(ctx, nmi::launch_mask_tables(st->d_wcounts[wb], st->cur_Wn, ctx->npix, st->d_wtables[wb], ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_mask_counts(d_wmasks, st->cur_Wn, ctx->npix, d_wcounts, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_mask_tables(d_wcounts, st->cur_Wn, ctx->npix, d_wtables, ctx->stream));
         st->tables_ok[wb] = true;
     }
     NMI_HIP_TRY(ctx, hipEventRecord(s.copied, st->copy));
 
     // compute stream: search on the slot, winner to pinned host memory
     NMI_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
-    if (st->keep_ratings && !s.d_ratings)
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&s.d_ratings, (size_t)st->max_S * st->max_Wn * sizeof(float)));
+    if (st->keep_ratings) NMI_HIP_TRY(ctx, s.d_ratings.grow((size_t)st->max_S * st->max_Wn * sizeof(float)));
     s.S = S;
     s.Wn = st->cur_Wn;
     s.s_offset = s_offset;
     s.S_total = S_total;
     s.w_offset = w_offset;
-    float *ratings = st->keep_ratings ? s.d_ratings : nullptr;
     int rc = NMI_OK;
-    SearchRequest rq = SearchRequest::block(s.d_renders, S, s_offset, S_total, st->d_warps[wb], st->cur_Wn, w_offset);
-    rq.d_ratings = ratings;
-    rq.out_key = s.d_key;
+    SearchRequest rq = SearchRequest::block(d_renders, S, s_offset, S_total, d_warps, st->cur_Wn, w_offset);
+    rq.d_ratings = st->keep_ratings ? s.d_ratings.as<float>() : nullptr;
+    rq.out_key = d_key;
     if (kind == kPlain || (int64_t)S * st->cur_Wn == 0) {
         // nmi_stream_wait checks this very launch for a split-kernel timeout (s.launch) and redoes it -- which it cannot
         // do once the key has gone into a collective, so submissions with a communicator keep to the one-workgroup kernel.
@@ -985,28 +932,26 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         rq.caller_checks_split = nccl_comm == nullptr && kind == kPlain;
         rc = enqueue_grid(ctx, rq, &s.launch);
     } else if (kind == kMasked) {
-        rc = enqueue_grid_mask(ctx, rq, MaskSide{st->d_wmasks[wb], nullptr, st->d_wcounts[wb], st->d_wtables[wb], st->d_redo, st->d_redo_state},
-                               &s.launch);
+        rc = enqueue_grid_mask(ctx, rq, MaskSide{d_wmasks, nullptr, d_wcounts, d_wtables, d_redo, d_redo_state}, &s.launch);
     } else {
-        NMI_HIP_TRY(ctx, nmi::launch_unpack_mask_bits(s.d_bits, S, ctx->npix, st->d_rmasks, ctx->stream));
-        rc = enqueue_grid_mask(ctx, rq, MaskSide{st->d_wmasks[wb], st->d_rmasks, s.d_counts, nullptr, st->d_redo, st->d_redo_state}, &s.launch);
+        NMI_HIP_TRY(ctx, nmi::launch_unpack_mask_bits(d_bits, S, ctx->npix, d_rmasks, ctx->stream));
+        rc = enqueue_grid_mask(ctx, rq, MaskSide{d_wmasks, d_rmasks, d_counts, nullptr, d_redo, d_redo_state}, &s.launch);
     }
     if (rc != NMI_OK) return rc;
     s.kind = kind;
     s.n_counts = kind == kMasked ? st->cur_Wn : kind == kCovered ? (int64_t)S * st->cur_Wn : 0;
     if (kind == kMasked && s.n_counts > 0)  // len_w into the slot: the buffer's own may be rebuilt by a later frame
-        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.d_counts, st->d_wcounts[wb], (size_t)s.n_counts * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                                        ctx->stream));
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(d_counts, d_wcounts, (size_t)s.n_counts * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     s.warp_buf = wb;
     s.warp_gen = st->warp_gen[wb];
-    const unsigned long long *result = s.d_key;
+    const unsigned long long *result = d_key;
     if (nccl_comm) {
         // the level's only exchange: 8-byte MAX all-reduce of the packed keys, issued in submission order on every rank
-        rc = rccl_allreduce_key(ctx, s.d_key, s.d_key + 1, nccl_comm);
+        rc = rccl_allreduce_key(ctx, d_key, d_key + 1, nccl_comm);
         if (rc != NMI_OK) return rc;
-        result = s.d_key + 1;
+        result = d_key + 1;
     }
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(s.h_key, result, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(s.h_key.as<>(), result, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipEventRecord(s.done, ctx->stream));
     s.ticket = t;
     s.waited = false;
@@ -1068,7 +1013,7 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
     if (n == 0) return NMI_OK;
     nmi_ctx *ctx = st->ctx;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpy(h_counts, s.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    NMI_HIP_TRY(ctx, hipMemcpy(h_counts, s.d_counts.as<>(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 
@@ -1105,7 +1050,7 @@ int nmi_stream_copy_ratings(nmi_stream *st, int64_t ticket, float *h_ratings, in
     if (s.ticket != ticket || !s.waited || s.failed || !s.d_ratings || n != (int64_t)s.S * s.Wn) return NMI_ERR_INVALID_ARGUMENT;
     nmi_ctx *ctx = st->ctx;
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, hipMemcpy(h_ratings, s.d_ratings, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    NMI_HIP_TRY(ctx, hipMemcpy(h_ratings, s.d_ratings.as<>(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return NMI_OK;
 }
 
@@ -1129,19 +1074,20 @@ int nmi_stream_wait(nmi_stream *st, int64_t ticket, int64_t *h_best_index, float
             return NMI_ERR_NOT_READY;
         }
         // (enqueue-only and unchecked: never a split form)
-        SearchRequest rq = SearchRequest::block(s.d_renders, s.S, s.s_offset, s.S_total, st->d_warps[s.warp_buf], s.Wn, s.w_offset);
-        rq.d_ratings = st->keep_ratings ? s.d_ratings : nullptr;
-        rq.out_key = s.d_key;
+        SearchRequest rq = SearchRequest::block(s.d_renders.as<uint8_t>(), s.S, s.s_offset, s.S_total, st->d_warps[s.warp_buf].as<uint8_t>(), s.Wn,
+                                                s.w_offset);
+        rq.d_ratings = st->keep_ratings ? s.d_ratings.as<float>() : nullptr;
+        rq.out_key = s.d_key.as<unsigned long long>();
         const int rc = enqueue_grid(ctx, rq, &s.launch);
         if (rc != NMI_OK) {
             s.failed = true;
             return rc;
         }
-        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.h_key, s.d_key, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(s.h_key.as<>(), s.d_key.as<>(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         ctx->detail = kSplitTimeoutTicketNote;
     }
-    return nmi_key_unpack(*s.h_key, h_best_index, h_best_score);
+    return nmi_key_unpack(*s.h_key.as<unsigned long long>(), h_best_index, h_best_score);
 }
 
 }  // extern "C"

@@ -8,59 +8,53 @@ namespace nmi_internal {
 
 // Buffers of the mesh renderer (nmi_mesh.hip) for S views: 8 bytes per pixel of visibility keys for the direct path, the
 // tile bins (at most 32 MiB) and their state words, the queue of (triangle, view) pairs crossing the near plane.
-int mesh_work_alloc(nmi_ctx *ctx, int S, nmi::MeshWork *w)
+int mesh_work_alloc(nmi_ctx *ctx, int S, MeshWorkArea *w)
 {
     const int width = ctx->params.width, height = ctx->params.height;
     constexpr unsigned long long kClipItems = 1ull << 18;  // beyond it the clip pass rescans the mesh
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&w->zbuf, nmi::mesh_zbuf_bytes(S, width, height)));
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&w->bins, nmi::mesh_bins_bytes(S, width, height)));
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&w->state, nmi::mesh_state_bytes(S, width, height)));
-    NMI_HIP_TRY(ctx, hipMalloc(&w->clip_queue, (size_t)kClipItems * nmi::mesh_clip_item_bytes()));
-    w->clip_cap = kClipItems;
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&w->clip_state, 2 * sizeof(unsigned long long)));
-    NMI_HIP_TRY(ctx, hipMalloc((void **)&w->pair_state, sizeof(uint32_t)));
-    NMI_HIP_TRY(ctx, hipMemsetAsync(w->pair_state, 0, sizeof(uint32_t), ctx->stream));
-    w->compute_units = ctx->compute_units;
-    NMI_HIP_TRY(ctx, nmi::launch_mesh_clear(*w, S, width, height, ctx->stream));
+    *w = MeshWorkArea{};
+    NMI_HIP_TRY(ctx, w->zbuf.alloc(nmi::mesh_zbuf_bytes(S, width, height)));
+    NMI_HIP_TRY(ctx, w->bins.alloc(nmi::mesh_bins_bytes(S, width, height)));
+    NMI_HIP_TRY(ctx, w->state.alloc(nmi::mesh_state_bytes(S, width, height)));
+    NMI_HIP_TRY(ctx, w->clip_queue.alloc((size_t)kClipItems * nmi::mesh_clip_item_bytes()));
+    NMI_HIP_TRY(ctx, w->clip_state.alloc(2 * sizeof(unsigned long long)));
+    NMI_HIP_TRY(ctx, w->pair_state.grow(sizeof(uint32_t), ctx->stream, /*zero=*/true));
+    nmi::MeshWork &v = w->view;
+    v.zbuf = w->zbuf.as<unsigned long long>();
+    v.bins = w->bins.as<uint32_t>();
+    v.state = w->state.as<uint32_t>();
+    v.clip_queue = w->clip_queue.as<>();
+    v.clip_cap = kClipItems;
+    v.clip_state = w->clip_state.as<unsigned long long>();
+    v.pair_state = w->pair_state.as<uint32_t>();
+    v.compute_units = ctx->compute_units;
+    NMI_HIP_TRY(ctx, nmi::launch_mesh_clear(v, S, width, height, ctx->stream));
     return NMI_OK;
 }
 
 // The pair list of the two-kernel binning pass: 64 entries per block of 256 triangles (grown on demand; a level sizes it once).
-int ensure_mesh_pairs(nmi_ctx *ctx, nmi::MeshWork *w, long long n_triangles)
+int ensure_mesh_pairs(nmi_ctx *ctx, MeshWorkArea *w, long long n_triangles)
 {
     const unsigned long long need = nmi::mesh_pairs_entries(n_triangles);
-    if (need <= w->pairs_cap) return NMI_OK;
-    if (w->pairs) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(w->pairs);
-        w->pairs = nullptr, w->pairs_cap = 0;
-    }
-    if (hipMalloc((void **)&w->pairs, (size_t)need * sizeof(uint32_t)) != hipSuccess) {
+    if (need <= w->view.pairs_cap) return NMI_OK;
+    w->view.pairs = nullptr, w->view.pairs_cap = 0;
+    if (w->pairs.grow((size_t)need * sizeof(uint32_t), ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
-        w->pairs = nullptr;   // (no list: launch_render_mesh takes the one-kernel form)
-        return NMI_OK;
+        return NMI_OK;  // (no list: launch_render_mesh takes the one-kernel form)
     }
-    w->pairs_cap = need;
+    w->view.pairs = w->pairs.as<uint32_t>();
+    w->view.pairs_cap = need;
     return NMI_OK;
-}
-
-void mesh_work_free(nmi::MeshWork *w)
-{
-    void *all[] = {w->zbuf, w->bins, w->state, w->clip_queue, w->clip_state, w->pairs, w->pair_state};
-    for (void *q : all)
-        if (q) (void)hipFree(q);
-    *w = nmi::MeshWork{};
 }
 
 int ensure_mesh_work(nmi_ctx *ctx, int S)
 {
     if (S <= ctx->mesh_views) return NMI_OK;
     if (ctx->mesh_views) NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    mesh_work_free(&ctx->mesh);
     ctx->mesh_views = 0;
     const int rc = mesh_work_alloc(ctx, S, &ctx->mesh);
     if (rc != NMI_OK) {
-        mesh_work_free(&ctx->mesh);
+        ctx->mesh = MeshWorkArea{};
         return rc;
     }
     ctx->mesh_views = S;
@@ -99,6 +93,26 @@ int warp_inverse_coeffs(const double *forward, float *coeffs)
         if (!std::isfinite(inv[i])) return NMI_ERR_INVALID_ARGUMENT;  // a subnormal determinant: singular to working precision
     scale_to_unit(inv);
     for (int i = 0; i < 9; ++i) coeffs[i] = (float)inv[i];
+    return NMI_OK;
+}
+
+// nmi_warp_stack (d_warp_masks null) and nmi_warp_stack_masked: the inverse maps go into a slot of the context's upload ring,
+// which is free again after the last kernel that read it.  The masked form's warps are the plain form's, byte for byte.
+static int warp_stack_impl(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask, const double *h_forward, int32_t Wn,
+                           uint8_t *d_warp_stack, uint8_t *d_warp_masks)
+{
+    if (!ctx || !d_frame || !h_forward || !d_warp_stack || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    nmi_mem::UploadRing::Slot slot;  // (last used four submissions ago; normally long finished)
+    NMI_HIP_TRY(ctx, ctx->warp_ring.acquire((size_t)Wn * 9, ctx->stream, &slot));
+    for (int w = 0; w < Wn; ++w)
+        if (warp_inverse_coeffs(h_forward + (size_t)w * 9, slot.h + (size_t)w * 9) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    NMI_HIP_TRY(ctx, ctx->warp_ring.upload(slot, ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_warp(d_frame, slot.d, d_warp_stack, ctx->params.width, ctx->params.height, Wn, ctx->stream));
+    if (d_warp_masks)
+        NMI_HIP_TRY(ctx, nmi::launch_warp_masks(d_frame_mask, slot.d, d_warp_masks, ctx->params.width, ctx->params.height, Wn, ctx->stream));
+    NMI_HIP_TRY(ctx, ctx->warp_ring.release(slot, ctx->stream));
     return NMI_OK;
 }
 
@@ -143,34 +157,14 @@ int nmi_warp_homographies(const double K[9], const int32_t num[3], const float s
 
 int nmi_warp_stack(nmi_ctx *ctx, const uint8_t *d_frame, const double *h_forward, int32_t Wn, uint8_t *d_warp_stack)
 {
-    if (!ctx || !d_frame || !h_forward || !d_warp_stack || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
-    ctx->detail.clear();
-    DeviceGuard guard(ctx->device);
-    if (Wn > ctx->warp_coeffs_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < nmi_ctx::kWarpRing; ++i) {
-            if (ctx->d_warp_coeffs[i]) NMI_HIP_TRY(ctx, hipFree(ctx->d_warp_coeffs[i]));
-            if (ctx->h_warp_coeffs[i]) NMI_HIP_TRY(ctx, hipHostFree(ctx->h_warp_coeffs[i]));
-            ctx->d_warp_coeffs[i] = ctx->h_warp_coeffs[i] = nullptr;
-        }
-        ctx->warp_coeffs_cap = 0;
-        for (int i = 0; i < nmi_ctx::kWarpRing; ++i) {
-            NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_warp_coeffs[i], (size_t)Wn * 9 * sizeof(float)));
-            NMI_HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_warp_coeffs[i], (size_t)Wn * 9 * sizeof(float), hipHostMallocDefault));
-            if (!ctx->warp_ev[i]) NMI_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->warp_ev[i], hipEventDisableTiming));
-        }
-        ctx->warp_coeffs_cap = Wn;
-    }
-    const int ring = (int)(ctx->warp_uses++ % nmi_ctx::kWarpRing);
-    // this ring entry was last used kWarpRing submissions ago; normally long finished
-    NMI_HIP_TRY(ctx, hipEventSynchronize(ctx->warp_ev[ring]));
-    float *h_coeffs = ctx->h_warp_coeffs[ring], *d_coeffs = ctx->d_warp_coeffs[ring];
-    for (int w = 0; w < Wn; ++w)
-        if (warp_inverse_coeffs(h_forward + (size_t)w * 9, h_coeffs + (size_t)w * 9) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(d_coeffs, h_coeffs, (size_t)Wn * 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    NMI_HIP_TRY(ctx, nmi::launch_warp(d_frame, d_coeffs, d_warp_stack, ctx->params.width, ctx->params.height, Wn, ctx->stream));
-    NMI_HIP_TRY(ctx, hipEventRecord(ctx->warp_ev[ring], ctx->stream));
-    return NMI_OK;
+    return warp_stack_impl(ctx, d_frame, nullptr, h_forward, Wn, d_warp_stack, nullptr);
+}
+
+int nmi_warp_stack_masked(nmi_ctx *ctx, const uint8_t *d_frame, const uint8_t *d_frame_mask, const double *h_forward, int32_t Wn,
+                          uint8_t *d_warp_stack, uint8_t *d_warp_masks)
+{
+    if (!d_warp_masks) return NMI_ERR_INVALID_ARGUMENT;
+    return warp_stack_impl(ctx, d_frame, d_frame_mask, h_forward, Wn, d_warp_stack, d_warp_masks);
 }
 
 // Projection (rendering.hpp:196-202, glm columns) * glm::lookAt(pos + t, look_at + t, up) (rendering.hpp:547-553), fp32.
@@ -240,18 +234,11 @@ int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int
     int size = 1;
     if (point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     const int64_t need = (int64_t)nmi::render_zbuf_words(S, ctx->params.width, ctx->params.height, size);
-    if (need > ctx->zbuf_cap) {
-        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_zbuf) NMI_HIP_TRY(ctx, hipFree(ctx->d_zbuf));
-        ctx->d_zbuf = nullptr;
-        ctx->zbuf_cap = 0;
-        NMI_HIP_TRY(ctx, hipMalloc((void **)&ctx->d_zbuf, (size_t)need * sizeof(uint32_t)));
-        ctx->zbuf_cap = need;
-    }
+    NMI_HIP_TRY(ctx, ctx->d_zbuf.grow((size_t)need * sizeof(uint32_t), ctx->stream));
     float *d_mvps = nullptr;
     const int src = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (src != NMI_OK) return src;
-    NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, ctx->d_zbuf, d_render_stack, ctx->params.width,
+    NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, ctx->d_zbuf.as<uint32_t>(), d_render_stack, ctx->params.width,
                                                ctx->params.height, size, ctx->stream, true, cover));
     return NMI_OK;
 }
@@ -272,7 +259,6 @@ int nmi_texture_destroy(nmi_texture *tex)
     if (!tex) return NMI_OK;
     DeviceGuard guard(tex->ctx->device);
     (void)hipStreamSynchronize(tex->ctx->stream);
-    if (tex->d_luma) (void)hipFree(tex->d_luma);
     delete tex;
     return NMI_OK;
 }
@@ -324,8 +310,8 @@ int nmi_texture_create(nmi_ctx *ctx, const uint8_t *h_rgb, int32_t tw, int32_t t
         cur.swap(next);
     }
     DeviceGuard guard(ctx->device);
-    hipError_t e = hipMalloc((void **)&tex->d_luma, (size_t)total * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(tex->d_luma, luma.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t e = tex->d_luma.alloc((size_t)total * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(tex->d_luma.as<>(), luma.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         const int rc = hip_fail(ctx, e, "nmi_texture_create");
         nmi_texture_destroy(tex);
@@ -376,7 +362,7 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
     int rc = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (rc != NMI_OK) return rc;
     const int bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
-    const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, d_mvps, S, ctx->mesh, ctx->mesh_views, bin_cap,
+    const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, d_mvps, S, ctx->mesh.view, ctx->mesh_views, bin_cap,
                                                  ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
                                                  nullptr, nullptr, 0, cover);
     if (e != hipSuccess) {
@@ -388,7 +374,7 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
 
 nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_texture *tex)
 {
-    if (kind == MapKind::textured_mesh) return nmi::MeshShading{true, d_attr, tex->d_luma, tex->levels, tex->w, tex->h, tex->off};
+    if (kind == MapKind::textured_mesh) return nmi::MeshShading{true, d_attr, tex->d_luma.as<float>(), tex->levels, tex->w, tex->h, tex->off};
     return nmi::MeshShading{false, d_attr};
 }
 

@@ -127,12 +127,12 @@ int nmi_search_grid_block_rccl(nmi_ctx *ctx, const uint8_t *render_stack, int32_
     // The only exchange of the search: 8 bytes per rank, max over ranks.  Out of place: the send
     // buffer is this launch's key slot (zero for a rank whose block is empty), the receive buffer a word of its own, so
     // the global winner never lands in a ping-pong slot that a later launch expects to find zero.
-    const unsigned long long *send = ctx->d_keys + ctx->last_slot;
-    rc = rccl_allreduce_key(ctx, send, ctx->d_reduced_key, nccl_comm);
+    const unsigned long long *send = ctx->d_keys.as<unsigned long long>() + ctx->last_slot;
+    rc = rccl_allreduce_key(ctx, send, ctx->d_reduced_key.as<unsigned long long>(), nccl_comm);
     if (rc != NMI_OK) return rc;
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key, ctx->d_reduced_key, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key.as<>(), ctx->d_reduced_key.as<>(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return nmi_key_unpack(*ctx->h_key, h_best_index, h_best_score);
+    return nmi_key_unpack(*ctx->h_key.as<unsigned long long>(), h_best_index, h_best_score);
 }
 
 // One search level sharded over the ranks of `nccl_comm` (the latency form of BASELINE.json configs[4]): this
@@ -148,11 +148,11 @@ int nmi_level_run_rccl(nmi_level *lv, const float *h_mvps, const double *h_forwa
     const unsigned long long *send = nullptr;
     int rc = level_enqueue(lv, h_mvps, h_forward, &send);
     if (rc != NMI_OK) return rc;
-    rc = rccl_allreduce_key(ctx, send, ctx->d_reduced_key, nccl_comm);
+    rc = rccl_allreduce_key(ctx, send, ctx->d_reduced_key.as<unsigned long long>(), nccl_comm);
     if (rc != NMI_OK) return rc;
-    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key, ctx->d_reduced_key, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    NMI_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_key.as<>(), ctx->d_reduced_key.as<>(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return nmi_key_unpack(*ctx->h_key, h_best_index, h_best_score);
+    return nmi_key_unpack(*ctx->h_key.as<unsigned long long>(), h_best_index, h_best_score);
 }
 
 int nmi_search_grid_rccl(nmi_ctx *ctx, const uint8_t *render_stack, int32_t S_local, int32_t s_offset, int32_t S_total,

@@ -15,6 +15,7 @@
 #include "nmi_covered.h"
 #include "nmi_kernels.h"
 #include "nmi_masked.h"
+#include "nmi_mem.h"
 #include "nmi_search_plan.h"
 
 // What a search launched (enqueue_grid, enqueue_grid_mask): the split-timeout redo logic and the status getters go by it.
@@ -26,15 +27,13 @@ struct SearchLaunch {
     int few = 0;         // it went down the few-levels path (it may have fallen back)
 };
 
-// Small host->device parameter uploads (warp coefficients, view matrices) go through a ring of pinned staging buffers so
-// that back-to-back submissions never have to wait for the stream: entry i is reused only after the copy that read it.
-struct StagingRing {
-    static constexpr int kSlots = 4;
-    float *h[kSlots] = {};
-    float *d[kSlots] = {};
-    hipEvent_t ev[kSlots] = {};
-    size_t cap = 0;  // floats per slot
-    unsigned uses = 0;
+using nmi_mem::DeviceBuffer;
+using nmi_mem::PinnedBuffer;
+
+// The mesh renderer's work area (nmi_render_mesh, a mesh level): the buffers, and the view of them nmi_mesh.hip takes.
+struct MeshWorkArea {
+    DeviceBuffer zbuf, bins, state, clip_queue, clip_state, pairs, pair_state;
+    nmi::MeshWork view;
 };
 
 struct nmi_ctx {
@@ -43,19 +42,19 @@ struct nmi_ctx {
     int compute_units = 0;
     int npix = 0;
     int shift = 0;
-    hipStream_t own_stream = nullptr;
+    nmi_mem::Stream own_stream;
     hipStream_t stream = nullptr;
-    float *table = nullptr;             // [npix + 1]
-    unsigned long long *d_keys = nullptr;  // two device slots for the packed winner, used alternately (ping-pong)
-    unsigned long long *h_key = nullptr;   // pinned host mirror (copy path)
-    unsigned int *d_done = nullptr;        // finished-workgroup counter
-    nmi::Mailbox *mailbox = nullptr;       // pinned, fine-grained: the kernel posts the winner here
+    DeviceBuffer table;                    // float [npix + 1]
+    DeviceBuffer d_keys;                   // unsigned long long [2]: device slots for the packed winner, used alternately (ping-pong)
+    PinnedBuffer h_key;                    // unsigned long long: pinned host mirror (copy path)
+    DeviceBuffer d_done;                   // unsigned int: finished-workgroup counter
+    PinnedBuffer mailbox;                  // nmi::Mailbox, fine-grained: the kernel posts the winner here
     unsigned int seq = 0;                  // launches that post to the mailbox so far (blocking calls only)
     int slot = 0;                          // key slot of the next launch
     int last_slot = 0;                     // key slot of the most recent launch
     SearchLaunch last;                     // the most recent launch (written by commit_launch only)
     int pix_owner_bias = 49152;            // NMI_OPT_PIX_OWNER_BIAS: pixels the owner of a candidate adds beyond an equal share
-    uint32_t *d_pix_timeouts = nullptr;    // the pixel-range kernels' heal counters [kPixHealWords] (nmi_kernels.h): healed, timeouts, count-test redos
+    DeviceBuffer d_pix_timeouts;           // uint32_t: the pixel-range kernels' heal counters [kPixHealWords] (nmi_kernels.h): healed, timeouts, count-test redos
     // Split-kernel liveness (nmi_split_kernel.hip: its consumers spin, so a launch whose workgroups are not all resident
     // times out after 2 ms).  A timeout is attributed to ITS launch (epoch), that search is redone by nmi_grid_kernel, and the
     // split forms stay off for split_cooldown further small-grid launches -- 16, doubling per consecutive timeout up to
@@ -67,83 +66,66 @@ struct nmi_ctx {
     static constexpr uint32_t kSplitBackoffMin = 16, kSplitBackoffMax = 4096;
     int result_path = 1;                   // 1 mailbox spin (default), 0 hipMemcpyAsync + stream sync
     bool posted = false;                   // the most recent launch posts to the mailbox
-    float *d_pair_rating = nullptr;
-    unsigned long long *d_reduced_key = nullptr;  // receive buffer of the RCCL all-reduce (never one of the ping-pong slots)
-    unsigned long long *score_mailbox = nullptr;  // pinned, fine-grained: nmi_eval_pair's (score bits | sequence << 32)
+    DeviceBuffer d_pair_rating;                   // float
+    DeviceBuffer d_reduced_key;                   // unsigned long long: receive buffer of the RCCL all-reduce (never one of the ping-pong slots)
+    PinnedBuffer score_mailbox;                   // unsigned long long [2], fine-grained: nmi_eval_pair's (score bits | sequence << 32)
     unsigned int pair_seq = 0;                    // nmi_eval_pair calls that posted so far
     int wait_mode = 0;                            // NMI_OPT_WAIT_MODE: 0 spin on the mailbox, 1 yield the core between polls
     // Visiting orders of the candidates (XCD-aware tiling), one per grid shape seen, so that a coarse-to-fine search
     // alternating between shapes (translation level 27 x 1, rotation level 1 x 27, ...) never waits for the stream.
     struct OrderEntry {
         int S = -1, Wn = -1;
-        int *d = nullptr, *h = nullptr;
-        int64_t cap = 0;
+        DeviceBuffer d;  // int [S * Wn], or larger: an entry keeps the largest table it has held
+        PinnedBuffer h;
         uint64_t last_use = 0;
     };
     static constexpr int kOrderCache = 16;
     OrderEntry orders[kOrderCache];
     uint64_t order_clock = 0;
     int xcd_tiling = 1;                   // NMI_OPT_XCD_TILING
-    nmi::SplitSlab *d_slabs = nullptr;    // hand-off slabs of the split kernel, one per candidate
-    int slab_cap = 0;
-    unsigned long long *d_blocks = nullptr;  // counter blocks (granules) of the split kernel's pixel parts
+    DeviceBuffer d_slabs;                 // nmi::SplitSlab: hand-off slabs of the split kernel, one per candidate
+    DeviceBuffer d_blocks;                // counter blocks (granules) of the split kernel's pixel parts
     uint32_t split_epoch = 0;             // tag of the latest split launch
-    uint32_t *h_split_error = nullptr, *d_split_error = nullptr;  // pinned ring [nmi::kSplitRing]: word (epoch % kSplitRing) = epoch of a launch whose hand-off timed out
-    size_t blocks_bytes = 0;
-    unsigned long long *d_pix_blocks = nullptr;  // hand-off blocks of nmi_pix_kernel (mid-size grids)
-    size_t pix_blocks_bytes = 0;
-    // nmi_eval_pairs: pointer tables [2][pairs_cap] in pinned host memory (renders, then warps) + device scores
-    const uint8_t **h_pair_table = nullptr, **d_pair_table = nullptr;
-    float *d_pair_scores = nullptr;
+    PinnedBuffer split_error;             // uint32_t [nmi::kSplitRing], mapped: word (epoch % kSplitRing) = epoch of a launch whose hand-off timed out
+    DeviceBuffer d_pix_blocks;            // hand-off blocks of nmi_pix_kernel (mid-size grids)
+    // nmi_eval_pairs: pointer tables [2][pairs_cap] in pinned, mapped host memory (renders, then warps) + device scores
+    PinnedBuffer pair_table;              // const uint8_t * [2 * pairs_cap]
+    DeviceBuffer d_pair_scores;           // float [pairs_cap]
     int pairs_cap = 0;
     int split_pixels = -1;                // NMI_OPT_SPLIT_PIXELS: -1 automatic, 1 / 2 / 4 (with NMI_OPT_SPLIT 1: 2 ... 8)
     // Few-levels path (nmi_fewlevels_kernel.hip): which kernels score a search is decided from what the last probe of
     // the stacks found, posted by the device to *level_post = probe number << 32 | nr << 16 | nw.
-    nmi::LevelPlan *d_plan = nullptr;
-    unsigned long long *level_post = nullptr;  // pinned, fine-grained
+    DeviceBuffer d_plan;                  // nmi::LevelPlan
+    PinnedBuffer level_post;              // unsigned long long, fine-grained
     uint32_t level_seq = 0;               // probes enqueued so far
     uint32_t level_seen = 0;              // number of the probe the hint below comes from
     bool few_hint = false;                // the last probe seen found nr * nw <= fewlevels_bins
     int content_path = -1;                // NMI_OPT_CONTENT_PATH: -1 automatic (hint), 0 nmi_grid_kernel only, 1 few-levels first
     int fewlevels_bins = 4096;            // NMI_OPT_FEWLEVELS_BINS: largest nr * nw sent down the few-levels path
-    uint8_t *d_rank_stacks = nullptr;     // rank images of the search in flight: renders, then warps
-    size_t rank_bytes = 0;
+    DeviceBuffer d_rank_stacks;           // rank images of the search in flight: renders, then warps
     unsigned long long *dbg_stamps = nullptr;  // NMI_OPT_STAMPS
     int stamp_candidate = 0;                   // NMI_OPT_STAMP_CANDIDATE
     int split_mode = -1;                  // NMI_OPT_SPLIT: -1 automatic, 0 never, 2 / 4 / 8 row parts whenever the grid fits, 1: pixel ranges only
-    uint32_t *d_zbuf = nullptr;           // depth|colour anchor buffers of the point-cloud renderer (padded, per view)
-    int64_t zbuf_cap = 0;
-    nmi::MeshWork mesh;                    // mesh renderer (nmi_render_mesh): bins, their state, key buffer, clip queue -- for mesh_views views
+    DeviceBuffer d_zbuf;                  // depth|colour anchor buffers of the point-cloud renderer (padded, per view)
+    MeshWorkArea mesh;                     // mesh renderer (nmi_render_mesh): bins, their state, key buffer, clip queue -- for mesh_views views
     int mesh_views = 0;
     unsigned long long tile_queue_limit = 4ull << 20;  // NMI_OPT_TILE_QUEUE: usable entries per bin (capped by the bins' size)
     unsigned long long clip_queue_limit = ~0ull;       // NMI_OPT_CLIP_QUEUE
-    StagingRing mvp_ring;
-    uint32_t *d_scratch = nullptr;        // drained-counter slabs of the pipelined kernel
+    nmi_mem::UploadRing mvp_ring, warp_ring;  // view matrices of the renderers, inverse homographies of the warp producer
+    DeviceBuffer d_scratch;               // drained-counter slabs of the pipelined kernel
     int scratch_workgroups = 0;
-    // inverse homographies for the warp producer: a small ring of (pinned staging, device copy, "copy consumed" event)
-    // so that back-to-back submissions never wait for the stream
-    static constexpr int kWarpRing = 4;
-    float *d_warp_coeffs[kWarpRing] = {};
-    float *h_warp_coeffs[kWarpRing] = {};
-    hipEvent_t warp_ev[kWarpRing] = {};
-    int warp_coeffs_cap = 0;
-    unsigned warp_uses = 0;
-    // Masked search (nmi_capi_masked.cpp): per-warp mask counts and term tables.  Allocated on first use, grown on demand,
-    // freed by nmi_destroy.
-    int32_t *d_mask_counts = nullptr;     // [mask_warps_cap] len_w of the latest masked search
-    float *d_mask_tables = nullptr;       // [mask_warps_cap][npix + 1]
-    int mask_warps_cap = 0;
+    // Masked search (nmi_capi_masked.cpp): per-warp mask counts and term tables.  Allocated on first use, grown on demand.
+    DeviceBuffer d_mask_counts;           // int32_t [warps] len_w of the latest masked search
+    DeviceBuffer d_mask_tables;           // float [warps][npix + 1]
     int mask_count_n = 0;                 // warps counted by the latest masked search
     // The redo list of the masked and the covered searches' optimistic launches: one for both, as in a level or a stream (the
     // searches are serialised on the context's stream, and each leaves the list empty).
-    int32_t *d_mask_redo = nullptr;       // [mask_redo_cap] candidates to score again exactly
-    uint32_t *d_mask_redo_state = nullptr;  // [2]: entries in the list, exact workgroups finished (zero between searches)
-    int64_t mask_redo_cap = 0;
+    DeviceBuffer d_mask_redo;             // int32_t: candidates to score again exactly
+    DeviceBuffer d_mask_redo_state;       // uint32_t [2]: entries in the list, exact workgroups finished (zero between searches)
     // Covered search (nmi_capi_covered.cpp): per-candidate pixel counts.
-    int32_t *d_cover_counts = nullptr;    // [cover_cap] len[w][s] of the latest covered search, layout [Wn][S]
-    int64_t cover_cap = 0;
+    DeviceBuffer d_cover_counts;          // int32_t len[w][s] of the latest covered search, layout [Wn][S]
     int64_t cover_count_n = 0;            // candidates counted by the latest covered search
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    nmi_mem::Event ev_start, ev_stop;
     int hist_variant = 3;
     int phase_mask = 3;
     int workgroups = 0;
@@ -155,7 +137,7 @@ struct nmi_ctx {
 // nmi_texture (nmi_texture_create): mip chain of a mesh texture as per-level fp32 luma on the device.
 struct nmi_texture {
     nmi_ctx *ctx = nullptr;
-    float *d_luma = nullptr;
+    DeviceBuffer d_luma;  // float
     int levels = 0;
     int w[16] = {}, h[16] = {};
     long long off[16] = {};
@@ -164,10 +146,9 @@ struct nmi_texture {
 namespace nmi_internal {
 
 // Device buffers of the mesh renderer for S views, allocated and brought to their clean state (the renderer keeps them clean).
-int mesh_work_alloc(nmi_ctx *ctx, int S, nmi::MeshWork *w);
-void mesh_work_free(nmi::MeshWork *w);
+int mesh_work_alloc(nmi_ctx *ctx, int S, MeshWorkArea *w);
 int ensure_mesh_work(nmi_ctx *ctx, int S);  // the context's own, grown on demand
-int ensure_mesh_pairs(nmi_ctx *ctx, nmi::MeshWork *w, long long n_triangles);  // the pair list of the two-kernel binning pass
+int ensure_mesh_pairs(nmi_ctx *ctx, MeshWorkArea *w, long long n_triangles);  // the pair list of the two-kernel binning pass
 // The 9 floats the warp kernels take for one forward homography (nmi_capi_producers.cpp): NMI_ERR_INVALID_ARGUMENT for a
 // non-finite or singular matrix.  Shared by nmi_warp_stack, nmi_warp_stack_masked and the level replays.
 int warp_inverse_coeffs(const double *forward /*[9]*/, float *coeffs /*[9]*/);
@@ -251,7 +232,7 @@ int ensure_mask_redo(nmi_ctx *ctx, int64_t total);  // the context's redo list, 
 int enqueue_grid_mask(nmi_ctx *ctx, const SearchRequest &rq, const MaskSide &m, SearchLaunch *launched = nullptr);
 int wait_word(nmi_ctx *ctx, const volatile unsigned long long *word, unsigned long long mask, unsigned long long want,
               unsigned long long *out);
-int stage_floats(nmi_ctx *ctx, StagingRing &ring, const float *h_src, size_t n, float **d_out);
+int stage_floats(nmi_ctx *ctx, nmi_mem::UploadRing &ring, const float *h_src, size_t n, float **d_out);
 int fetch_key(nmi_ctx *ctx, unsigned long long *key);
 bool split_timed_out(nmi_ctx *ctx);                                     // ... the most recent launch
 bool split_launch_failed(nmi_ctx *ctx, const SearchLaunch &launch);     // ... this launch (waits for the stream on a hit)
