@@ -190,7 +190,8 @@ static bool write_files(const char *dir, bool mesh, int mesh_nx, int mesh_ny, co
 
 int main(int argc, char **argv)
 {
-    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered] [--color rgb|bgr|rgba|bgra]
+    // usage: level_pipeline [keyframes] [--mesh [NXxNY]] [--density D] [--masked] [--covered]
+    //                       [--color rgb|bgr|rgba|bgra|yuyv|uyvy|bayer-rggb|bayer-grbg|bayer-gbrg|bayer-bggr]
     //                       [--reduce F] [--write-files DIR | --files DIR]
     //   --mesh: nmi_prop_RENDER 1, the reference's default render mode: the same surface as NX x NY quads = 2 NX NY textured
     //           triangles, default 300x200 = 120,000;  --density: points per pixel of a view along each axis (cloud; default 0.9)
@@ -201,6 +202,8 @@ int main(int argc, char **argv)
     //   --color FMT: the camera frame is a colour image in that format (a smooth chroma pattern over its grey values, so that the
     //           channel order matters), in rows padded to 256 bytes; the levels read it raw and turn it grey on the device
     //           (nmi_level_set_frame_format).  With --files the order (RGB or BGR) is the settings file's Camera.RGB.
+    //           yuyv, uyvy: the raw frame a UVC camera delivers, the grey values as luma beside neutral chroma; bayer-*: the 8-bit
+    //           mosaic a machine-vision camera delivers, each site keeping its channel of that colour image.
     //   --reduce F: the camera is F (2..4) times the search size in each direction: its frame is rendered at F * 848 x F * 480 (in
     //           colour with --color) and the levels reduce it to the search size on the device (nmi_level_set_frame_reduction).
     //           With --write-files the settings file describes that full-size camera; with --files it is read as such and brought
@@ -214,7 +217,8 @@ int main(int argc, char **argv)
     float density = 0.9f;
     const char *write_dir = nullptr, *read_dir = nullptr;
     bool masked = false, covered = false;
-    int color_bpp = 0, color_rgb = 0;  // --color: 3 or 4 bytes per pixel, RGB (1) or BGR (0) order
+    int color_bpp = 0, color_rgb = 0;  // --color: 3 or 4 bytes per pixel, RGB (1) or BGR (0) order; 2: packed YUV; 1: a Bayer mosaic
+    int32_t sensor_format = 0;         // --color yuyv ... bayer-bggr: the NMI_FRAME_* id
     int reduce = 1;                    // --reduce: the camera frame is this many times the search size
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mesh")) {
@@ -228,8 +232,13 @@ int main(int argc, char **argv)
             const char *c = argv[++i];
             color_bpp = !strcmp(c, "rgb") || !strcmp(c, "bgr") ? 3 : !strcmp(c, "rgba") || !strcmp(c, "bgra") ? 4 : 0;
             color_rgb = c[0] == 'r';
+            static const struct { const char *name; int32_t format; int bpp; } sensors[] = {
+                {"yuyv", NMI_FRAME_YUYV, 2}, {"uyvy", NMI_FRAME_UYVY, 2}, {"bayer-rggb", NMI_FRAME_BAYER_RGGB, 1},
+                {"bayer-grbg", NMI_FRAME_BAYER_GRBG, 1}, {"bayer-gbrg", NMI_FRAME_BAYER_GBRG, 1}, {"bayer-bggr", NMI_FRAME_BAYER_BGGR, 1}};
+            for (const auto &sn : sensors)
+                if (!strcmp(c, sn.name)) sensor_format = sn.format, color_bpp = sn.bpp;
             if (!color_bpp) {
-                fprintf(stderr, "--color takes rgb, bgr, rgba or bgra\n");
+                fprintf(stderr, "--color takes rgb, bgr, rgba, bgra, yuyv, uyvy or bayer-rggb, -grbg, -gbrg, -bggr\n");
                 return 2;
             }
         } else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) {
@@ -436,8 +445,12 @@ int main(int argc, char **argv)
         if (color_bpp) {
             // The camera's colour frame: R and B swing +-50 around the grey value (slowly across and down the frame), G makes up the
             // rest, so that the rule of nmi_gray_frame gives about the grey frame back -- and a wrong channel order does not.
-            if (read_dir) CHECK_NMI(nmi_config_load_color_order((std::string(read_dir) + "/settings.yaml").c_str(), &color_rgb));
-            color_format = color_bpp == 3 ? (color_rgb ? NMI_FRAME_RGB : NMI_FRAME_BGR) : (color_rgb ? NMI_FRAME_RGBA : NMI_FRAME_BGRA);
+            // A raw sensor frame is made from the same colour image: a Bayer site keeps its channel (red sites at column parity
+            // phase & 1, row parity phase >> 1), packed YUV the grey value as luma beside chroma 128.
+            if (read_dir && !sensor_format) CHECK_NMI(nmi_config_load_color_order((std::string(read_dir) + "/settings.yaml").c_str(), &color_rgb));
+            color_format = sensor_format ? sensor_format
+                         : color_bpp == 3 ? (color_rgb ? NMI_FRAME_RGB : NMI_FRAME_BGR) : (color_rgb ? NMI_FRAME_RGBA : NMI_FRAME_BGRA);
+            const int phase = sensor_format - NMI_FRAME_BAYER_RGGB, luma = sensor_format == NMI_FRAME_UYVY ? 1 : 0;
             color_pitch = ((int64_t)W * color_bpp + 255) / 256 * 256;  // a driver's padded rows
             std::vector<uint8_t> col((size_t)H * color_pitch, 0);
             const int ri = color_rgb ? 0 : 2;
@@ -448,17 +461,29 @@ int main(int argc, char **argv)
                     const double b = std::min(255.0, std::max(0.0, std::round(g - 50.0 * std::sin(6.2832 * 1.2 * y / H + 1.0))));
                     const double gg = std::min(255.0, std::max(0.0, std::round((g * 16384.0 - 4899.0 * r - 1868.0 * b) / 9617.0)));
                     uint8_t *px = &col[(size_t)y * color_pitch + (size_t)x * color_bpp];
+                    if (color_bpp == 1) {
+                        const int ca = (x ^ phase) & 1, cb = (y ^ (phase >> 1)) & 1;
+                        px[0] = (uint8_t)(ca != cb ? gg : ca == 0 ? r : b);
+                        continue;
+                    }
+                    if (color_bpp == 2) {
+                        px[luma] = (uint8_t)g, px[1 - luma] = 128;
+                        continue;
+                    }
                     px[ri] = (uint8_t)r, px[1] = (uint8_t)gg, px[2 - ri] = (uint8_t)b;
                     if (color_bpp == 4) px[3] = 255;
                 }
             CHECK_HIP(hipMalloc((void **)&d_color, col.size()));
             CHECK_HIP(hipMemcpy(d_color, col.data(), col.size(), hipMemcpyHostToDevice));
             static const char *names[] = {"GRAY", "BGR", "RGB", "BGRA", "RGBA"};
+            static const char *sensor_names[] = {"YUYV", "UYVY", "BAYER_RGGB", "BAYER_GRBG", "BAYER_GBRG", "BAYER_BGGR"};
+            const char *name = !sensor_format ? names[color_format] : sensor_names[color_bpp == 2 ? luma : 2 + phase];
+            const char *what = sensor_format ? "raw sensor" : "colour";
             if (F > 1)
-                printf("full-size colour frame: %s, %d x %d in rows of %lld bytes, turned grey and reduced %dx to %d x %d on the device by every replay\n",
-                       names[color_format], W, H, (long long)color_pitch, F, SW, SH);
+                printf("full-size %s frame: %s, %d x %d in rows of %lld bytes, turned grey and reduced %dx to %d x %d on the device by every replay\n",
+                       what, name, W, H, (long long)color_pitch, F, SW, SH);
             else
-                printf("colour frame: %s, %d x %d in rows of %lld bytes, turned grey on the device by every replay\n", names[color_format], W, H,
+                printf("%s frame: %s, %d x %d in rows of %lld bytes, turned grey on the device by every replay\n", what, name, W, H,
                        (long long)color_pitch);
         }
     }

@@ -11,7 +11,7 @@
  * Data conventions:
  *   image           uint8 [height][width], contiguous, row stride = width
  *                   (cv::cuda::createContinuous CV_8UC1, Thirdparty/Localization/image.cpp:67).
- *                   The camera frame alone may also come in colour or with a row stride: nmi_gray_frame,
+ *                   The camera frame alone may also come in colour, as a Bayer mosaic, as packed YUV or with a row stride: nmi_gray_frame,
  *                   nmi_level_set_frame_format, nmi_stream_set_frame_format (NMI_FRAME_*); and at 2, 3 or 4 times the
  *                   context's size: nmi_reduce_frame, nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction.
  *   render          same shape; stored bottom-up when nmi_params.render_bottom_up = 1, which is how
@@ -348,12 +348,42 @@ int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_
  * 0 < pitch < W * bytes per pixel, d_gray overlapping the source's bytes (rows 0 .. H-1 of W * bytes per pixel each, and the
  * bytes between them).
  * Captured levels: nmi_level_set_frame_format.  Streams: nmi_stream_set_frame_format.
+ *
+ * Raw sensor formats (new): the same entry points, here and wherever an NMI_FRAME_* format is taken (nmi_reduce_frame, the
+ * levels' and streams' setters), read what camera drivers deliver.  Every other id, 5 .. 15 included, stays unknown.
+ *   NMI_FRAME_YUYV, NMI_FRAME_UYVY  packed YUV 4:2:2 (UVC / V4L2), 2 bytes per pixel, any width, dense pitch 2 W.  The grey
+ *     value is the luma byte, unchanged (byte 2x of a YUYV row, 2x + 1 of a UYVY one), as COLOR_YUV2GRAY_YUY2 / _UYVY: no range
+ *     expansion, and the chroma bytes are never read.
+ *   NMI_FRAME_BAYER_RGGB / _GRBG / _GBRG / _BGGR  an 8-bit Bayer mosaic, 1 byte per pixel; the name is the 2x2 tile at (0, 0),
+ *     row 0 then row 1.  W >= 2 and H >= 2 (of the source, for a reduced frame), else NMI_ERR_INVALID_ARGUMENT.  The rule is a
+ *     bilinear demosaic followed by the weights above, in integers, with one rounding.  With p(dx, dy) the mosaic byte at
+ *     (x + dx, y + dy), and R4, G4, B4 four times the channels:
+ *       red site     R4 = 4 p(0,0)   G4 = p(-1,0) + p(1,0) + p(0,-1) + p(0,1)   B4 = p(-1,-1) + p(1,-1) + p(-1,1) + p(1,1)
+ *       blue site    as the red site, with R4 and B4 exchanged
+ *       green site in a red row    R4 = 2 (p(-1,0) + p(1,0))   G4 = 4 p(0,0)   B4 = 2 (p(0,-1) + p(0,1))
+ *       green site in a blue row   as in a red row, with R4 and B4 exchanged
+ *       gray = (4899 R4 + 9617 G4 + 1868 B4 + 32768) >> 16
+ *     A flat mosaic of value g gives g exactly, and the value is within 0.5 of the exact (4899 R4 + 9617 G4 + 1868 B4) / 65536.
+ *     Coordinates outside the frame are reflected without repeating the edge (-1 -> 1, W -> W - 2, and the same in y), which
+ *     keeps the colour phase of the mosaic.  The frame is the W x H (for nmi_reduce_frame the f W x f H) pixels the call covers:
+ *     a pitch's padding and spare columns or rows are never read, and the last covered column and row reflect inwards.  A caller
+ *     who crops by offsetting d_src by an odd number of columns or rows changes the pattern and must pass the one that results:
+ *     RGGB one column in is GRBG, one row down GBRG, both BGGR.  Parity with OpenCV's demosaicing is unpinned.
+ *   NV12 / NV21 / I420 (hardware video decoders) need no id: their luma plane is H rows of pitch bytes, which is NMI_FRAME_GRAY
+ *     with that pitch.  A stream then copies only the H luma rows of the host buffer, never the chroma plane behind them.
+ * Not covered: 10 / 12 / 16-bit mosaics, edge-aware demosaicing, chroma of any kind, planar 4:2:2 / 4:4:4.
  */
 #define NMI_FRAME_GRAY 0
 #define NMI_FRAME_BGR 1
 #define NMI_FRAME_RGB 2
 #define NMI_FRAME_BGRA 3
 #define NMI_FRAME_RGBA 4
+#define NMI_FRAME_YUYV 16        /* Y0 U Y1 V ...   2 bytes per pixel, luma at byte 2x     */
+#define NMI_FRAME_UYVY 17        /* U Y0 V Y1 ...   2 bytes per pixel, luma at byte 2x + 1 */
+#define NMI_FRAME_BAYER_RGGB 32  /* 1 byte per pixel; the name is the 2x2 tile at (0,0): row 0 then row 1 */
+#define NMI_FRAME_BAYER_GRBG 33
+#define NMI_FRAME_BAYER_GBRG 34
+#define NMI_FRAME_BAYER_BGGR 35
 int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, uint8_t *d_gray /* [H][W] */);
 
 /*

@@ -26,7 +26,15 @@ FRAME_BGR = 1
 FRAME_RGB = 2
 FRAME_BGRA = 3
 FRAME_RGBA = 4
-FRAME_BYTES_PER_PIXEL = {FRAME_GRAY: 1, FRAME_BGR: 3, FRAME_RGB: 3, FRAME_BGRA: 4, FRAME_RGBA: 4}
+# Raw sensor formats: packed YUV 4:2:2 (the luma byte is the grey value) and 8-bit Bayer mosaics (named by the 2x2 tile at (0, 0)).
+FRAME_YUYV = 16
+FRAME_UYVY = 17
+FRAME_BAYER_RGGB = 32
+FRAME_BAYER_GRBG = 33
+FRAME_BAYER_GBRG = 34
+FRAME_BAYER_BGGR = 35
+FRAME_BYTES_PER_PIXEL = {FRAME_GRAY: 1, FRAME_BGR: 3, FRAME_RGB: 3, FRAME_BGRA: 4, FRAME_RGBA: 4, FRAME_YUYV: 2, FRAME_UYVY: 2,
+                         FRAME_BAYER_RGGB: 1, FRAME_BAYER_GRBG: 1, FRAME_BAYER_GBRG: 1, FRAME_BAYER_BGGR: 1}
 
 # Every symbol include/nmi_hip.h declares; tests check that the library exports all of them.
 EXPORTED_SYMBOLS = (

@@ -1,6 +1,7 @@
 // nmi_capi_color.cpp -- nmi_gray_frame (include/nmi_hip.h) and the host side of the frame formats the captured levels and streams
 // share (nmi_level_set_frame_format, nmi_stream_set_frame_format: both through nmi_capi_intake.cpp's intake_set_frame and
-// launch_intake).  Kernels: nmi_color.hip, and the colour instantiation of the undistortion kernel in nmi_undistort.hip.
+// launch_intake).  Kernels: nmi_color.hip, nmi_bayer.hip (mosaics), and the colour instantiation of the undistortion kernel in
+// nmi_undistort.hip.
 #include "nmi_color.h"
 #include "nmi_ctx.h"
 
@@ -14,14 +15,21 @@ int nmi_internal::frame_bytes_per_pixel(int32_t format)
     case NMI_FRAME_RGB: return 3;
     case NMI_FRAME_BGRA:
     case NMI_FRAME_RGBA: return 4;
+    case NMI_FRAME_YUYV:
+    case NMI_FRAME_UYVY: return 2;
+    case NMI_FRAME_BAYER_RGGB:
+    case NMI_FRAME_BAYER_GRBG:
+    case NMI_FRAME_BAYER_GBRG:
+    case NMI_FRAME_BAYER_BGGR: return 1;
     default: return 0;
     }
 }
 
-int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, int64_t *row_bytes, bool *identity)
+int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity)
 {
     const int bpp = frame_bytes_per_pixel(format);
-    if (bpp == 0 || pitch < 0 || width <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    if (bpp == 0 || pitch < 0 || width <= 0 || height <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    if (nmi::frame_is_bayer(format) && (width < 2 || height < 2)) return NMI_ERR_INVALID_ARGUMENT;  // (the reflected edge needs a neighbour)
     const int64_t dense = (int64_t)width * bpp;
     if (pitch != 0 && pitch < dense) return NMI_ERR_INVALID_ARGUMENT;
     if (row_bytes) *row_bytes = pitch ? pitch : dense;
@@ -36,7 +44,7 @@ int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t p
     if (!ctx || !d_src || !d_gray) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
     int64_t rb = 0;
-    if (frame_format_check(format, pitch, W, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (frame_format_check(format, pitch, W, H, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     // the source's bytes run from d_src to the end of its last row's pixels; the grey frame's H x W bytes may not meet them
     const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + (int64_t)W * frame_bytes_per_pixel(format));
     const uintptr_t g0 = (uintptr_t)d_gray, g1 = g0 + (uintptr_t)ctx->npix;

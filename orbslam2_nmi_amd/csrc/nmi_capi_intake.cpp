@@ -26,13 +26,14 @@ int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const doub
     return NMI_OK;
 }
 
-int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch)
+int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int32_t format, int64_t pitch)
 {
     if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
     int64_t row_bytes = 0;
     bool identity = true;
-    const int64_t full_width = (int64_t)factor * width;
-    if (full_width > INT32_MAX || frame_format_check(format, pitch, (int)full_width, &row_bytes, &identity) != NMI_OK)
+    const int64_t full_width = (int64_t)factor * width, full_height = (int64_t)factor * height;
+    if (full_width > INT32_MAX || full_height > INT32_MAX ||
+        frame_format_check(format, pitch, (int)full_width, (int)full_height, &row_bytes, &identity) != NMI_OK)
         return NMI_ERR_INVALID_ARGUMENT;
     const bool on = !identity || factor > 1;  // dense grey of the search size: as never formatted
     in->colored = on;
@@ -51,6 +52,10 @@ hipError_t launch_intake(const FrameIntake &in, const uint8_t *src, int64_t src_
                                                 height, stream);
         if (e != hipSuccess || !in.distorted) return e;
         return nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
+    }
+    if (in.two_nodes()) {  // a mosaic: demosaiced to grey once, not at every tap
+        const hipError_t e = nmi::launch_gray(src, in.frame_format, src_row_bytes, scratch, width, height, stream);
+        return e != hipSuccess ? e : nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
     }
     if (in.distorted && in.colored)
         return nmi::launch_undistort_color(in.ud, src, in.frame_format, src_row_bytes, raw_mask, gray_out, mask_out, width, height, stream);

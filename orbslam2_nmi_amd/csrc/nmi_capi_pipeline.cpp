@@ -86,7 +86,8 @@ struct nmi_level {
     DeviceBuffer d_cover_counts;                // int32_t [Wn][S]
     // Distorted, coloured or reduced: d_frame (and d_frame_mask) are the camera's frame; every replay brings it into d_ud, the
     // level's own grey frame (and, distorted and masked or covered, its mask into d_ud_mask), which the warps and their masks read
-    // instead.  Reduced and distorted: reduced into d_small, which the undistortion node reads in d_frame's place.
+    // instead.  Reduced (or a Bayer mosaic) and distorted: brought to grey in d_small, which the undistortion node reads in
+    // d_frame's place.
     DeviceBuffer d_ud, d_ud_mask, d_small;      // uint8_t [H][W] each
 };
 
@@ -113,13 +114,13 @@ struct LevelNeeds {
     bool cover;    // covered: d_rmasks, d_cover_counts
     bool ud;       // the level's own grey frame
     bool ud_mask;  // ... and its mask: undistorted, for the warps' masks
-    bool small;    // the reduced frame the undistortion node reads
+    bool small;    // the reduced (or demosaiced) grey frame the undistortion node reads
 };
 
 static LevelNeeds level_needs(const LevelSettings &s)
 {
     const bool mode = s.masked || s.covered;
-    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.reduced() && s.intake.distorted};
+    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes()};
 }
 
 struct LevelBuffer {
@@ -655,7 +656,7 @@ int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format,
 {
     if (!lv) return NMI_ERR_INVALID_ARGUMENT;
     LevelSettings next = lv->set;
-    if (intake_set_frame(&next.intake, lv->ctx->params.width, factor, format, pitch) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (intake_set_frame(&next.intake, lv->ctx->params.width, lv->ctx->params.height, factor, format, pitch) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     return level_apply(lv, next, "nmi_level_set_frame_reduction");
 }
 
@@ -717,8 +718,8 @@ struct nmi_stream {
     // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction): frames submitted while one of them
     // is set are brought on the compute stream into d_ud[b] (distorted, masked / covered: their masks into d_ud_mask[b]), and the
     // warps are made from those.  A coloured, pitched or full-size host frame (intake.colored) crosses as its rows of
-    // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced and distorted, it is reduced into d_frame[b] (idle
-    // meanwhile), which the undistortion reads as a grey frame.
+    // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced (or a Bayer mosaic) and distorted, it is brought to
+    // grey in d_frame[b] (idle meanwhile), which the undistortion reads as a grey frame.
     FrameIntake intake;
     DeviceBuffer d_ud[2];                         // uint8_t [H][W], allocated on the first distorted (or coloured) frame
     DeviceBuffer d_ud_mask[2];                    // uint8_t [H][W], allocated on the first distorted masked / covered frame
@@ -1030,7 +1031,7 @@ int nmi_stream_set_distortion_fisheye(nmi_stream *st, const double K[9], const d
 
 int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t format, int64_t pitch)
 {
-    return st ? intake_set_frame(&st->intake, st->ctx->params.width, factor, format, pitch) : NMI_ERR_INVALID_ARGUMENT;
+    return st ? intake_set_frame(&st->intake, st->ctx->params.width, st->ctx->params.height, factor, format, pitch) : NMI_ERR_INVALID_ARGUMENT;
 }
 
 int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) { return nmi_stream_set_frame_reduction(st, 1, format, pitch); }

@@ -28,9 +28,9 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     if ((d_src_mask == nullptr) != (d_mask == nullptr)) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
     const int64_t fW = (int64_t)factor * W, fH = (int64_t)factor * H;
-    if (fW > INT32_MAX) return NMI_ERR_INVALID_ARGUMENT;
+    if (fW > INT32_MAX || fH > INT32_MAX) return NMI_ERR_INVALID_ARGUMENT;
     int64_t rb = 0;
-    if (frame_format_check(format, pitch, (int)fW, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     // the source's bytes run from d_src to the end of its last row's pixels, the source mask's over its dense f H x f W bytes;
     // neither output may meet them, or the other output
     const uintptr_t s0 = (uintptr_t)d_src, m0 = (uintptr_t)d_src_mask, g0 = (uintptr_t)d_gray, o0 = (uintptr_t)d_mask;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nmi_hip.h"
 #include "nmi_undistort.h"
 
 namespace nmi {
@@ -13,8 +14,15 @@ namespace nmi {
 // format (an NMI_FRAME_* value; pitch > 0, the rows' bytes).  gray is dense [height][width] and does not overlap the source.
 hipError_t launch_gray(const uint8_t *src, int format, int64_t pitch, uint8_t *gray, int width, int height, hipStream_t stream);
 
-// launch_undistort on the grey values of a colour or pitched raw frame, in one kernel: equal to launch_gray into a dense frame
-// followed by launch_undistort on it.  raw_mask and frame_mask are dense [height][width], as there.
+// format is one of NMI_FRAME_BAYER_*.
+inline bool frame_is_bayer(int format) { return format >= NMI_FRAME_BAYER_RGGB && format <= NMI_FRAME_BAYER_BGGR; }
+
+// launch_gray (factor 1) and launch_reduce (nmi_reduce.h; factor 2 .. 4) of a Bayer mosaic of factor * height rows of factor *
+// width bytes (both >= 2), in one kernel (nmi_bayer.hip): launch_gray and launch_reduce pass their Bayer formats on to it.
+hipError_t launch_bayer(const uint8_t *src, int format, int64_t pitch, int factor, uint8_t *gray, int width, int height, hipStream_t stream);
+
+// launch_undistort on the grey values of a colour, pitched or packed-YUV raw frame (not a Bayer mosaic), in one kernel: equal to
+// launch_gray into a dense frame followed by launch_undistort on it.  raw_mask and frame_mask are dense [height][width], as there.
 hipError_t launch_undistort_color(const UndistortParams &p, const uint8_t *src, int format, int64_t pitch, const uint8_t *raw_mask,
                                   uint8_t *frame, uint8_t *frame_mask, int width, int height, hipStream_t stream);
 
@@ -25,8 +33,9 @@ namespace nmi_internal {
 // Bytes per pixel of an NMI_FRAME_* format, 0 for an unknown one.
 int frame_bytes_per_pixel(int32_t format);
 
-// format known, pitch 0 (dense) or >= width * bytes per pixel -> NMI_OK, *row_bytes = the rows' pitch (width * bytes per pixel
-// for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion); else NMI_ERR_INVALID_ARGUMENT.
-int frame_format_check(int32_t format, int64_t pitch, int width, int64_t *row_bytes, bool *identity);
+// format known, pitch 0 (dense) or >= width * bytes per pixel, a Bayer mosaic at least 2 x 2 -> NMI_OK, *row_bytes = the rows'
+// pitch (width * bytes per pixel for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion);
+// else NMI_ERR_INVALID_ARGUMENT.  width and height are the source's.
+int frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity);
 
 }  // namespace nmi_internal

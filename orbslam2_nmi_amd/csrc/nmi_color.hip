@@ -1,6 +1,7 @@
 // nmi_color.hip -- colour and pitched camera frames to the dense grey frame the warps read (nmi_gray_frame, include/nmi_hip.h):
 // OpenCV's 8-bit fixed-point COLOR_{RGB,BGR,RGBA,BGRA}2GRAY, gray = (4899 R + 9617 G + 1868 B + 8192) >> 14
-// (nmi_color_device.h), or a copy of the rows of a pitched grey frame.  The kernel moves a frame's bytes once: at 848x480 RGB
+// (nmi_color_device.h), a copy of the rows of a pitched grey frame, or the luma bytes of packed YUV 4:2:2 (YUYV, UYVY); Bayer
+// mosaics go to nmi_bayer.hip.  The kernel moves a frame's bytes once: at 848x480 RGB
 // about 1.2 MB in and 0.4 MB out, so its time is mostly launch cost.  The same rule on each bilinear tap makes the colour
 // instantiation of the undistortion kernel (nmi_undistort.hip).
 #include <hip/hip_runtime.h>
@@ -58,8 +59,15 @@ hipError_t launch_gray(const uint8_t *src, int format, int64_t pitch, uint8_t *g
     const dim3 grid((quads + kGrayQuads - 1) / kGrayQuads, (height + 3) / 4), block(kGrayQuads, 4);
     const int vec_in = ((uintptr_t)src % 4) == 0 && (pitch % 4) == 0;
     const int vec_out = (width % 4) == 0 && ((uintptr_t)gray % 4) == 0;
+    if (frame_is_bayer(format)) return launch_bayer(src, format, pitch, 1, gray, width, height, stream);
     const size_t pb = (size_t)pitch;
     switch (format) {
+    case NMI_FRAME_YUYV:  // (2 bytes per pixel: a quad's 8 bytes in one load)
+        hipLaunchKernelGGL((nmi_gray_kernel<2, 0>), grid, block, 0, stream, src, pb, gray, width, height, vec_in, vec_out);
+        break;
+    case NMI_FRAME_UYVY:
+        hipLaunchKernelGGL((nmi_gray_kernel<2, 1>), grid, block, 0, stream, src, pb, gray, width, height, vec_in, vec_out);
+        break;
     case NMI_FRAME_GRAY:
         hipLaunchKernelGGL((nmi_gray_kernel<1, 0>), grid, block, 0, stream, src, pb, gray, width, height, vec_in, vec_out);
         break;

@@ -14,12 +14,14 @@ namespace {
 __device__ __forceinline__ uint32_t color_gray(uint32_t r, uint32_t g, uint32_t b) { return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14; }
 
 // The grey value of the pixel at p: C bytes per pixel (1: grey, copied; 3 or 4: colour, a fourth byte ignored), R at byte RI
-// and B at byte 2 - RI.
+// and B at byte 2 - RI.  C = 2: packed YUV 4:2:2, the luma byte RI (0: YUYV, 1: UYVY) copied, the chroma byte never read.
 template <int C, int RI>
 __device__ __forceinline__ uint32_t color_pixel(const uint8_t *p)
 {
     if constexpr (C == 1)
         return p[0];
+    else if constexpr (C == 2)
+        return p[RI];
     else
         return color_gray(p[RI], p[1], p[2 - RI]);
 }

@@ -5,6 +5,7 @@
 // launch the same kernels themselves.
 #pragma once
 #include "nmi_hip.h"
+#include "nmi_color.h"
 #include "nmi_undistort.h"
 
 namespace nmi_internal {
@@ -22,6 +23,10 @@ struct FrameIntake {
     int32_t frame_factor = 1;
 
     bool reduced() const { return frame_factor > 1; }
+    bool mosaic() const { return nmi::frame_is_bayer(frame_format); }
+    // grey frame first (into launch_intake's scratch), undistortion second: a reduction, and a Bayer mosaic, whose taps would
+    // each demosaic a 3 x 3 neighbourhood (profiles/sensor/README.md: the fused node takes twice the two nodes' time)
+    bool two_nodes() const { return distorted && (reduced() || mosaic()); }
     bool own_frame() const { return distorted || colored; }  // the warps read gray_out, not the source
 };
 
@@ -29,17 +34,18 @@ struct FrameIntake {
 int intake_set_distortion(FrameIntake *in, const double K[9], const float dist[5]);
 // The fisheye form (K_raw == nullptr: K).  dist == nullptr: off; four zero coefficients stay on (an ideal equidistant lens).
 int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const double K_raw[9], const float dist[4]);
-// factor 1 .. 4, format and pitch checked on the full width factor * width (frame_format_check).  Dense grey of the search
+// factor 1 .. 4, format and pitch checked on the full size factor * (width, height) (frame_format_check).  Dense grey of the search
 // size: off (NMI_FRAME_GRAY, pitch 0).  A bad argument: NMI_ERR_INVALID_ARGUMENT, *in untouched.
-int intake_set_frame(FrameIntake *in, int width, int32_t factor, int32_t format, int64_t pitch);
+int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int32_t format, int64_t pitch);
 
 // Enqueues the intake's kernels: src (rows of src_row_bytes) -> the dense grey [H][W] gray_out; nothing when !in.own_frame().
 //   reduced               launch_reduce, into scratch when distorted; then launch_undistort from scratch
+//   mosaic, distorted     launch_gray into scratch; then launch_undistort from scratch
 //   coloured, distorted   launch_undistort_color alone: each tap converted to grey, then the undistortion's arithmetic
 //   distorted             launch_undistort
 //   coloured              launch_gray
 // mask_out (may be null; only written when distorted) = the undistorted src_mask (dense [H][W], may be null: border only).
-// scratch is [H][W] and needed only when reduced and distorted.
+// scratch is [H][W] and needed only when in.two_nodes().
 hipError_t launch_intake(const FrameIntake &in, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask, uint8_t *scratch,
                          uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream);
 

@@ -1,14 +1,17 @@
 // nmi_reduce.hip -- full-size camera frames to the dense grey frame of the search size (nmi_reduce_frame, include/nmi_hip.h):
 // every source pixel turned grey by nmi_gray_frame's rule (nmi_color_device.h), then the rounded box average of each F x F
-// block, F = 2, 3 or 4 (F = 1 is nmi_color.hip).  The kernel moves a frame's bytes once -- 1920x1080 RGB is 6.2 MB in and 0.5 MB
+// block, F = 2, 3 or 4 (F = 1 is nmi_color.hip; a Bayer mosaic, whose pixels need their neighbours, is nmi_bayer.hip at every
+// F).  The kernel moves a frame's bytes once -- 1920x1080 RGB is 6.2 MB in and 0.5 MB
 // out -- with no LDS and no reuse between lanes.  The mask instantiation makes the reduced frame mask: 1 where a whole block of
 // the source mask is nonzero.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nmi_hip.h"
+#include "nmi_color.h"
 #include "nmi_color_device.h"
 #include "nmi_reduce.h"
+#include "nmi_reduce_device.h"
 
 namespace nmi {
 
@@ -21,21 +24,6 @@ template <int C, int F>
 constexpr int reduce_run()
 {
     return (4 * F * C) % 16 == 0 ? 4 : (8 * F * C) % 16 == 0 ? 8 : 16;
-}
-
-// The rounded mean of F * F grey values from their sum (include/nmi_hip.h): each is within 0.5 of the exact mean, and F = 4
-// rounds halves to even.
-template <int F>
-__device__ __forceinline__ uint32_t reduce_round(uint32_t s)
-{
-    if constexpr (F == 2) {
-        return (s + 2u) >> 2;
-    } else if constexpr (F == 3) {
-        return (s + 4u) / 9u;
-    } else {
-        const uint32_t q = s >> 4, r = s & 15u;
-        return q + ((r > 8u || (r == 8u && (q & 1u))) ? 1u : 0u);
-    }
 }
 
 // What one source pixel adds to its block's sum: its grey value, or (MASK) 1 for a nonzero mask byte.
@@ -146,9 +134,12 @@ bool reduce_by_factor(int factor, const uint8_t *src, size_t pitch, uint8_t *out
 
 hipError_t launch_reduce(const uint8_t *src, int format, int64_t pitch, int factor, uint8_t *gray, int width, int height, hipStream_t stream)
 {
+    if (frame_is_bayer(format)) return launch_bayer(src, format, pitch, factor, gray, width, height, stream);
     const size_t pb = (size_t)pitch;
     bool known = false;
     switch (format) {
+    case NMI_FRAME_YUYV: known = reduce_by_factor<2, 0, false>(factor, src, pb, gray, width, height, stream); break;
+    case NMI_FRAME_UYVY: known = reduce_by_factor<2, 1, false>(factor, src, pb, gray, width, height, stream); break;
     case NMI_FRAME_GRAY: known = reduce_by_factor<1, 0, false>(factor, src, pb, gray, width, height, stream); break;
     case NMI_FRAME_BGR: known = reduce_by_factor<3, 2, false>(factor, src, pb, gray, width, height, stream); break;
     case NMI_FRAME_RGB: known = reduce_by_factor<3, 0, false>(factor, src, pb, gray, width, height, stream); break;

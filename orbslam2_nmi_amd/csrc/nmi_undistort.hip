@@ -10,7 +10,8 @@
 // frame is copied and every mask byte is 1.  The value at (xs, ys) is warp_sample_global's (nmi_warp_device.h), the mask
 // warp_source_valid's: the rules of the warp stack and its masks.  No special case where the polynomial folds over.
 // Taps are gathered from global memory (a frame is well under 1 MB and stays in L2); no LDS staging.  The colour instantiation
-// (launch_undistort_color) takes its taps from a colour or pitched frame, converted to grey (nmi_color_device.h) one by one.
+// (launch_undistort_color) takes its taps from a colour, pitched or packed-YUV frame, converted to grey (nmi_color_device.h)
+// one by one; a Bayer mosaic is demosaiced first, in a node of its own (nmi_intake.h).
 //
 // The fisheye form (nmi_undistort_frame_fisheye): the four-coefficient equidistant model of Kannala-Brandt / cv::fisheye /
 // Kalibr "equidistant" / ORB-SLAM3 "KannalaBrandt8".  Two cameras: the output pinhole K (cxn, cyn, ifx, ify) and the raw
@@ -81,9 +82,9 @@ __device__ __forceinline__ void fisheye_source(const UndistortParams &p, float u
 
 // A lane makes 4 adjacent pixels of one row (and their mask bytes): one dword store each where every row starts on a 4-byte
 // boundary (aligned), byte stores otherwise.  raw fetches the raw frame's grey taps (warp_sample_taps): GrayTaps
-// (nmi_warp_device.h) for a dense grey frame (launch_undistort), ColorTaps (nmi_color_device.h) for a colour or pitched one
-// (launch_undistort_color: one node instead of launch_gray followed by this kernel, with the same bytes, each tap being the grey
-// value launch_gray would have stored).  Model (kLensRadTan, kLensFisheye) chooses the map from (u, v) to the source coordinate.
+// (nmi_warp_device.h) for a dense grey frame (launch_undistort), ColorTaps (nmi_color_device.h) for a colour, pitched or
+// packed-YUV one (launch_undistort_color: one node instead of launch_gray followed by this kernel, with the same bytes, each
+// tap being the grey value launch_gray would have stored).  Model (kLensRadTan, kLensFisheye) chooses the map from (u, v) to the source coordinate.
 template <class Taps, int Model>
 __global__ __launch_bounds__(256) void nmi_undistort_kernel(UndistortParams p, const Taps raw, const uint8_t *__restrict__ raw_mask,
                                                             uint8_t *__restrict__ frame, uint8_t *__restrict__ frame_mask, int width, int height,
@@ -147,6 +148,12 @@ hipError_t launch_undistort_color(const UndistortParams &p, const uint8_t *src, 
     const int aligned = (width % 4) == 0 && ((uintptr_t)frame % 4) == 0 && ((uintptr_t)frame_mask % 4) == 0;
     const size_t pb = (size_t)pitch;
     switch (format) {
+    case NMI_FRAME_YUYV:
+        launch_model(p, ColorTaps<2, 0>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned, stream);
+        break;
+    case NMI_FRAME_UYVY:
+        launch_model(p, ColorTaps<2, 1>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned, stream);
+        break;
     case NMI_FRAME_GRAY:
         launch_model(p, ColorTaps<1, 0>{src, pb}, raw_mask, frame, frame_mask, width, height, aligned, stream);
         break;
