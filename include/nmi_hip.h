@@ -371,7 +371,8 @@ int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_
  *     RGGB one column in is GRBG, one row down GBRG, both BGGR.  Parity with OpenCV's demosaicing is unpinned.
  *   NV12 / NV21 / I420 (hardware video decoders) need no id: their luma plane is H rows of pitch bytes, which is NMI_FRAME_GRAY
  *     with that pitch.  A stream then copies only the H luma rows of the host buffer, never the chroma plane behind them.
- * Not covered: 10 / 12 / 16-bit mosaics, edge-aware demosaicing, chroma of any kind, planar 4:2:2 / 4:4:4.
+ * Not covered: 10 / 12 / 16-bit mosaics (deep grey frames are NMI_FRAME_GRAY16, below), edge-aware demosaicing, chroma of any
+ * kind, planar 4:2:2 / 4:4:4.
  */
 #define NMI_FRAME_GRAY 0
 #define NMI_FRAME_BGR 1
@@ -384,6 +385,7 @@ int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_
 #define NMI_FRAME_BAYER_GRBG 33
 #define NMI_FRAME_BAYER_GBRG 34
 #define NMI_FRAME_BAYER_BGGR 35
+#define NMI_FRAME_GRAY16 48      /* 2 bytes per pixel, little-endian unsigned, H rows of pitch bytes; dense pitch 2 W */
 int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, uint8_t *d_gray /* [H][W] */);
 
 /*
@@ -416,6 +418,68 @@ int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t p
 int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */,
                      int32_t factor /* 1..4 */, const uint8_t *d_src_mask /* nullable, dense [f*H][f*W] */,
                      uint8_t *d_gray /* [H][W] */, uint8_t *d_mask /* nullable, [H][W] */);
+
+/*
+ * Deep frames (new).  Thermal, SWIR, NIR, depth and machine-vision cameras deliver more than 8 bits per pixel (GenICam Mono10 /
+ * Mono12 / Mono16, V4L2 Y10 / Y12 / Y16): NMI_FRAME_GRAY16 is their unpacked container, 2 bytes per pixel, little-endian
+ * unsigned, taken wherever an NMI_FRAME_* value is (nmi_gray_frame, nmi_reduce_frame, the levels' and streams' frame setters).
+ * Ids 47 and 49 stay unknown.  d_src and a non-zero pitch must be multiples of 2 (NMI_ERR_INVALID_ARGUMENT), the pitch and
+ * overlap rules are the other formats' with 2 bytes per pixel, and a frame has at most 2^32 - 1 pixels.
+ * The search bins 256 levels, so a deep pixel becomes 8-bit by a tone map, nmi_tone_map: per context (nmi_set_tone_map; read
+ * by nmi_gray_frame, nmi_reduce_frame and nmi_tone_lut at call time), per level and per stream.  It is ignored for every other
+ * format.  The rule is integers throughout.  M = 2^bits - 1; v = min(raw, M) (values above the declared depth saturate); N =
+ * the pixels the call covers, W x H of the source or f W x f H for a reduced frame (a pitch's padding and spare rows or columns
+ * are never read); h[v] = the exact count of v over them, c[v] its inclusive running sum.  A frame mask does not change h.
+ *   NMI_TONE_SHIFT       out = v >> (bits - 8)
+ *   NMI_TONE_WINDOW      v <= lo: 0; otherwise v >= hi: 255; otherwise ((v - lo) * 255 + ((hi - lo) >> 1)) / (hi - lo)
+ *   NMI_TONE_PERCENTILE  k_lo = N * p_lo / 10000, k_hi = N * p_hi / 10000 (64-bit, floor); lo = the smallest v with c[v] > k_lo,
+ *                        hi = the smallest v with c[v] >= N - k_hi; then WINDOW(lo, hi), whose order of cases makes a flat frame
+ *                        (hi == lo) all 0.  p_lo = p_hi = 0 is the min-max stretch.
+ *   NMI_TONE_EQUALIZE    h'[v] = plateau ? min(h[v], plateau) : h[v], c' its inclusive running sum, T = c'[M], vmin = the smallest
+ *                        v with h[v] > 0, c0 = h'[vmin].  T == c0: every pixel 0.  Otherwise, for v >= vmin,
+ *                        out = ((c'[v] - c0) * 255 + ((T - c0) >> 1)) / (T - c0) with 64-bit products, and 0 below vmin.  This is
+ *                        cv::equalizeHist's rule carried to 16 bits; with a plateau, the thermal cameras' plateau equalisation.
+ *                        Parity with an OpenCV build is unpinned.
+ *   NMI_TONE_TABLE       out = d_lut[v]: for callers who hold one mapping over a sequence (nmi_tone_lut makes one from a frame).
+ * A reduced frame maps each source pixel, then takes nmi_reduce_frame's rounded box average of the 8-bit values; the statistics
+ * are the full-size frame's.  SHIFT, WINDOW and TABLE cost the conversion kernel alone; PERCENTILE and EQUALIZE put a histogram
+ * kernel and two small table kernels in front of it, on the same stream (in a level: in the captured graph, from d_frame
+ * at every replay; in a stream: for every submitted frame).  With a lens distortion the grey frame is made first and
+ * undistorted second (two nodes, as for a mosaic).
+ * nmi_tone_map_default fills *tm with SHIFT, bits 16 (the setting of a new context, level or stream; also what a NULL tm
+ * sets).  NMI_ERR_INVALID_ARGUMENT, the setting left as it was: bits outside 8 .. 16, an unknown mode, a non-zero reserved
+ * word, WINDOW without 0 <= lo < hi <= M, PERCENTILE with a negative share or p_lo + p_hi >= 10000, EQUALIZE with a negative
+ * plateau, TABLE with a NULL d_lut.  Only the fields of the chosen mode (and bits, reserved) are read.
+ * nmi_level_set_tone_map captures the level again (waiting for a replay in flight), like the other level setters;
+ * nmi_stream_set_tone_map holds for later submissions.
+ * nmi_tone_lut writes the table the context's tone map gives for the frame at d_src (f H rows of pitch bytes, f W GRAY16 pixels
+ * each, f = factor) into d_lut, all 65,536 entries: entry i is the 8-bit value of v = min(i, M).  Enqueued on the context's
+ * stream; with h_window it blocks and returns {lo, hi}: PERCENTILE the chosen pair, EQUALIZE the smallest and largest value
+ * present, WINDOW the given pair, SHIFT and TABLE {0, M}.  NMI_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL ctx,
+ * d_src or d_lut, a factor outside 1 .. 4, an odd d_src or pitch, 0 < pitch < 2 f W, d_lut overlapping the source's bytes.
+ * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, mask-aware statistics, CLAHE
+ * (tiled equalisation), temporal smoothing of the window (TABLE is the hook: smooth on the host, pass the table).
+ */
+#define NMI_TONE_SHIFT 0
+#define NMI_TONE_WINDOW 1
+#define NMI_TONE_PERCENTILE 2
+#define NMI_TONE_EQUALIZE 3
+#define NMI_TONE_TABLE 4
+
+typedef struct nmi_tone_map {
+    int32_t mode;         /* NMI_TONE_* */
+    int32_t bits;         /* significant bits of the container, 8 .. 16 */
+    int32_t lo, hi;       /* WINDOW: 0 <= lo < hi <= 2^bits - 1 */
+    int32_t p_lo, p_hi;   /* PERCENTILE: shares of the pixels cut at each end, in 1/10000; >= 0, p_lo + p_hi < 10000 */
+    int32_t plateau;      /* EQUALIZE: per-level count limit, 0 = none; >= 0 */
+    int32_t reserved[5];  /* must be 0 */
+    const uint8_t *d_lut; /* TABLE: device uint8 [65536], must stay valid and unchanged while the setting is in force */
+} nmi_tone_map;
+
+int nmi_tone_map_default(nmi_tone_map *tm);
+int nmi_set_tone_map(nmi_ctx *ctx, const nmi_tone_map *tm /* NULL = the default */);
+int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
+                 uint8_t *d_lut /* [65536] */, int32_t h_window[2] /* nullable */);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU
@@ -667,6 +731,8 @@ int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch /* b
  * it.  NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, factor, format or pitch as for nmi_reduce_frame.
  */
 int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
+/* The tone map of a GRAY16 frame ("Deep frames", above); the level's d_frame must then be 2-byte aligned.  NULL = the default. */
+int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -778,6 +844,8 @@ int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch /*
  * holds them.
  */
 int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
+/* The tone map of GRAY16 host frames ("Deep frames", above), for later submissions.  NULL = the default. */
+int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

@@ -33,8 +33,16 @@ FRAME_BAYER_RGGB = 32
 FRAME_BAYER_GRBG = 33
 FRAME_BAYER_GBRG = 34
 FRAME_BAYER_BGGR = 35
+# Deep grey frames: 2 bytes per pixel, little-endian unsigned, made 8-bit by a tone map (ToneMap, TONE_*).
+FRAME_GRAY16 = 48
 FRAME_BYTES_PER_PIXEL = {FRAME_GRAY: 1, FRAME_BGR: 3, FRAME_RGB: 3, FRAME_BGRA: 4, FRAME_RGBA: 4, FRAME_YUYV: 2, FRAME_UYVY: 2,
-                         FRAME_BAYER_RGGB: 1, FRAME_BAYER_GRBG: 1, FRAME_BAYER_GBRG: 1, FRAME_BAYER_BGGR: 1}
+                         FRAME_BAYER_RGGB: 1, FRAME_BAYER_GRBG: 1, FRAME_BAYER_GBRG: 1, FRAME_BAYER_BGGR: 1, FRAME_GRAY16: 2}
+TONE_SHIFT = 0
+TONE_WINDOW = 1
+TONE_PERCENTILE = 2
+TONE_EQUALIZE = 3
+TONE_TABLE = 4
+TONE_LEVELS = 65536  # entries of a tone table
 
 # Every symbol include/nmi_hip.h declares; tests check that the library exports all of them.
 EXPORTED_SYMBOLS = (
@@ -56,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "nmi_render_mesh_colored", "nmi_render_mesh_colored_masked", "nmi_sort_triangles_colored", "nmi_level_create_mesh_colored",
     "nmi_level_create_mesh_colored_block",
     "nmi_undistort_frame_fisheye", "nmi_level_set_distortion_fisheye", "nmi_stream_set_distortion_fisheye",
+    "nmi_tone_map_default", "nmi_set_tone_map", "nmi_level_set_tone_map", "nmi_stream_set_tone_map", "nmi_tone_lut",
 )
 
 
@@ -65,6 +74,48 @@ class NmiParams(C.Structure):
         ("use_bg", C.c_int32), ("render_bottom_up", C.c_int32), ("device", C.c_int32),
         ("max_candidates", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 8),
     ]
+
+
+class ToneMap(C.Structure):
+    """nmi_tone_map (include/nmi_hip.h, "Deep frames"): how a FRAME_GRAY16 pixel becomes 8-bit.  The constructors below fill the
+    fields of their mode; `table` keeps the device tensor of a TABLE alive as long as the value."""
+    _fields_ = [("mode", C.c_int32), ("bits", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("p_lo", C.c_int32),
+                ("p_hi", C.c_int32), ("plateau", C.c_int32), ("reserved", C.c_int32 * 5), ("d_lut", C.c_void_p)]
+    table = None
+
+    @classmethod
+    def shift(cls, bits=16):
+        return cls(mode=TONE_SHIFT, bits=bits)
+
+    @classmethod
+    def window(cls, lo, hi, bits=16):
+        return cls(mode=TONE_WINDOW, bits=bits, lo=lo, hi=hi)
+
+    @classmethod
+    def percentile(cls, p_lo=0, p_hi=0, bits=16):
+        return cls(mode=TONE_PERCENTILE, bits=bits, p_lo=p_lo, p_hi=p_hi)
+
+    @classmethod
+    def equalize(cls, plateau=0, bits=16):
+        return cls(mode=TONE_EQUALIZE, bits=bits, plateau=plateau)
+
+    @classmethod
+    def from_table(cls, lut, bits=16):
+        """lut: device uint8 tensor of TONE_LEVELS entries (tone_lut makes one); it must stay unchanged while the setting holds."""
+        if not (lut.is_cuda and str(lut.dtype) == "torch.uint8" and lut.is_contiguous() and lut.numel() == TONE_LEVELS):
+            raise TypeError(f"lut must be a contiguous device uint8 tensor of {TONE_LEVELS} entries")
+        tm = cls(mode=TONE_TABLE, bits=bits, d_lut=lut.data_ptr())
+        tm.table = lut
+        return tm
+
+
+def _tone_ref(tm):
+    """The argument of a set_tone_map call: None -> NULL (the default setting)."""
+    if tm is None:
+        return None
+    if not isinstance(tm, ToneMap):
+        raise TypeError("tone map must be a ToneMap or None")
+    return C.byref(tm)
 
 
 class RenderParams(C.Structure):
@@ -165,6 +216,12 @@ def load_library(build_if_missing=False):
     lib.nmi_reduce_frame.argtypes = [vp, vp, i32, C.c_int64, i32, vp, vp, vp]
     lib.nmi_level_set_frame_reduction.argtypes = [vp, i32, i32, C.c_int64]
     lib.nmi_stream_set_frame_reduction.argtypes = [vp, i32, i32, C.c_int64]
+    if hasattr(lib, "nmi_tone_map_default"):  # (absent from a library of an earlier commit loaded through NMI_HIP_LIBRARY for A/B timing)
+        lib.nmi_tone_map_default.argtypes = [C.POINTER(ToneMap)]
+        lib.nmi_set_tone_map.argtypes = [vp, C.POINTER(ToneMap)]
+        lib.nmi_level_set_tone_map.argtypes = [vp, C.POINTER(ToneMap)]
+        lib.nmi_stream_set_tone_map.argtypes = [vp, C.POINTER(ToneMap)]
+        lib.nmi_tone_lut.argtypes = [vp, vp, C.c_int64, i32, vp, C.POINTER(i32)]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -611,6 +668,34 @@ class NmiContext:
         if sync:
             self.synchronize()
         return out
+
+    def set_tone_map(self, tm=None):
+        """nmi_set_tone_map: the tone map (ToneMap; None: SHIFT, 16 bits) gray_frame, reduce_frame and tone_lut apply to a
+        FRAME_GRAY16 source from now on.  Ignored for every other format."""
+        self._check(self._lib.nmi_set_tone_map(self._h, _tone_ref(tm)), "nmi_set_tone_map")
+        self._tone = tm  # (a TABLE's tensor stays alive)
+
+    def tone_lut(self, src, factor=1, pitch=0, out=None, window=True):
+        """nmi_tone_lut: the uint8 table [TONE_LEVELS] the context's tone map gives for the FRAME_GRAY16 frame src (factor * H rows
+        of `pitch` bytes, factor * W pixels each; src as for gray_frame).  window: blocks and returns (table, (lo, hi)); else the
+        table alone, enqueued."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        f = int(factor)
+        if int(pitch) >= 0 and 1 <= f <= 4:
+            need = (f * self.height - 1) * (int(pitch) or f * self.width * 2) + f * self.width * 2
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        if out is None:
+            out = torch.empty(TONE_LEVELS, dtype=torch.uint8, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == TONE_LEVELS):
+            raise TypeError(f"out must be a contiguous device uint8 tensor of {TONE_LEVELS} entries")
+        pair = (C.c_int32 * 2)()
+        self._order_after_torch()
+        self._check(self._lib.nmi_tone_lut(self._h, src.data_ptr(), int(pitch), f, out.data_ptr(), pair if window else None), "nmi_tone_lut")
+        return (out, (int(pair[0]), int(pair[1]))) if window else out
 
     def reduce_frame(self, src, fmt, factor, pitch=0, src_mask=None, out=None, out_mask=None, sync=True):
         """nmi_reduce_frame: the full-size camera frame src (device uint8 tensor holding factor * H rows of `pitch` bytes, each
@@ -1116,6 +1201,12 @@ class NmiLevel:
         self.ctx._order_after_torch()
         self.ctx._check(self._lib.nmi_level_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_level_set_frame_format")
 
+    def set_tone_map(self, tm=None):
+        """Tone map of a FRAME_GRAY16 frame (nmi_level_set_tone_map; ToneMap, None: SHIFT, 16 bits): PERCENTILE and EQUALIZE take
+        their statistics from the frame at every replay.  Ignored under every other format."""
+        self.ctx._check(self._lib.nmi_level_set_tone_map(self._h, _tone_ref(tm)), "nmi_level_set_tone_map")
+        self._tone = tm
+
     def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
         """Full-size frame (nmi_level_set_frame_reduction): every replay reads the level's frame in place as factor * H rows of
         `pitch` bytes (0: dense), each factor * W pixels in format fmt (FRAME_*), and reduces it to the grey frame of the search
@@ -1259,6 +1350,12 @@ class NmiStream:
         bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
         w, h = self.ctx.width, self.ctx.height
         self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
+
+    def set_tone_map(self, tm=None):
+        """Tone map of FRAME_GRAY16 host frames (nmi_stream_set_tone_map; ToneMap, None: SHIFT, 16 bits), for later submissions:
+        PERCENTILE and EQUALIZE take their statistics from each submitted frame."""
+        self.ctx._check(self._lib.nmi_stream_set_tone_map(self._h, _tone_ref(tm)), "nmi_stream_set_tone_map")
+        self._tone = tm
 
     def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
         """Full-size host frames (nmi_stream_set_frame_reduction): frames of later submissions, of every kind, are factor * H rows

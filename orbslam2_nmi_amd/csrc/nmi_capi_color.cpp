@@ -1,7 +1,7 @@
 // nmi_capi_color.cpp -- nmi_gray_frame (include/nmi_hip.h) and the host side of the frame formats the captured levels and streams
 // share (nmi_level_set_frame_format, nmi_stream_set_frame_format: both through nmi_capi_intake.cpp's intake_set_frame and
 // launch_intake).  Kernels: nmi_color.hip, nmi_bayer.hip (mosaics), and the colour instantiation of the undistortion kernel in
-// nmi_undistort.hip.
+// nmi_undistort.hip; deep grey frames (GRAY16) go through their tone table (nmi_tone.h).
 #include "nmi_color.h"
 #include "nmi_ctx.h"
 
@@ -16,7 +16,8 @@ int nmi_internal::frame_bytes_per_pixel(int32_t format)
     case NMI_FRAME_BGRA:
     case NMI_FRAME_RGBA: return 4;
     case NMI_FRAME_YUYV:
-    case NMI_FRAME_UYVY: return 2;
+    case NMI_FRAME_UYVY:
+    case NMI_FRAME_GRAY16: return 2;
     case NMI_FRAME_BAYER_RGGB:
     case NMI_FRAME_BAYER_GRBG:
     case NMI_FRAME_BAYER_GBRG:
@@ -30,6 +31,7 @@ int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, i
     const int bpp = frame_bytes_per_pixel(format);
     if (bpp == 0 || pitch < 0 || width <= 0 || height <= 0) return NMI_ERR_INVALID_ARGUMENT;
     if (nmi::frame_is_bayer(format) && (width < 2 || height < 2)) return NMI_ERR_INVALID_ARGUMENT;  // (the reflected edge needs a neighbour)
+    if (format == NMI_FRAME_GRAY16 && ((pitch % 2) != 0 || (int64_t)width * height > (int64_t)UINT32_MAX)) return NMI_ERR_INVALID_ARGUMENT;
     const int64_t dense = (int64_t)width * bpp;
     if (pitch != 0 && pitch < dense) return NMI_ERR_INVALID_ARGUMENT;
     if (row_bytes) *row_bytes = pitch ? pitch : dense;
@@ -44,13 +46,21 @@ int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t p
     if (!ctx || !d_src || !d_gray) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
     int64_t rb = 0;
-    if (frame_format_check(format, pitch, W, H, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (frame_format_check(format, pitch, W, H, &rb, nullptr) != NMI_OK || !frame_base_ok(format, d_src)) return NMI_ERR_INVALID_ARGUMENT;
     // the source's bytes run from d_src to the end of its last row's pixels; the grey frame's H x W bytes may not meet them
     const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + (int64_t)W * frame_bytes_per_pixel(format));
     const uintptr_t g0 = (uintptr_t)d_gray, g1 = g0 + (uintptr_t)ctx->npix;
     if (g0 < s1 && s0 < g1) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
+    if (format == NMI_FRAME_GRAY16) {  // through the context's tone map, as it is now
+        const nmi::ToneSetting t = ctx->tone;
+        const uint8_t *lut = nullptr;
+        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
+        NMI_HIP_TRY(ctx, launch_tone(ctx->tone_work, t, d_src, rb, W, H, &lut, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_gray16(d_src, rb, 1, lut, t.bits, d_gray, W, H, ctx->stream));
+        return NMI_OK;
+    }
     NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
     return NMI_OK;
 }

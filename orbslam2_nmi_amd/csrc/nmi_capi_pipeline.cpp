@@ -86,9 +86,11 @@ struct nmi_level {
     DeviceBuffer d_cover_counts;                // int32_t [Wn][S]
     // Distorted, coloured or reduced: d_frame (and d_frame_mask) are the camera's frame; every replay brings it into d_ud, the
     // level's own grey frame (and, distorted and masked or covered, its mask into d_ud_mask), which the warps and their masks read
-    // instead.  Reduced (or a Bayer mosaic) and distorted: brought to grey in d_small, which the undistortion node reads in
-    // d_frame's place.
+    // instead.  Reduced (or a Bayer mosaic, or a deep frame) and distorted: brought to grey in d_small, which the undistortion
+    // node reads in d_frame's place.
     DeviceBuffer d_ud, d_ud_mask, d_small;      // uint8_t [H][W] each
+    // A deep frame (GRAY16): its tone map's histogram and table (nmi_tone.h), prepared by level_apply before the capture.
+    ToneWork tone_work;
 };
 
 extern "C" {
@@ -114,7 +116,7 @@ struct LevelNeeds {
     bool cover;    // covered: d_rmasks, d_cover_counts
     bool ud;       // the level's own grey frame
     bool ud_mask;  // ... and its mask: undistorted, for the warps' masks
-    bool small;    // the reduced (or demosaiced) grey frame the undistortion node reads
+    bool small;    // the reduced (or demosaiced, or tone-mapped) grey frame the undistortion node reads
 };
 
 static LevelNeeds level_needs(const LevelSettings &s)
@@ -208,7 +210,7 @@ static int level_capture(nmi_level *lv)
                                   (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   d_epoch, lv->fused_points ? d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, d_kept, d_kept_count));
-        ok(launch_intake(in, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, p.width, p.height, st));
+        ok(launch_intake(in, lv->tone_work, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, p.width, p.height, st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = mesh ? (nmi::level_front_eligible(d_frame, d_warps, p.width, S) && n_points > 0) : lv->fused_points;
@@ -282,6 +284,8 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     }
     // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
     if (ok.e == hipSuccess && all_tables) ok(hipMemset(lv->d_counts.as<int32_t>() + lv->Wn, 0xFF, (size_t)lv->Wn * sizeof(int32_t)));
+    // a deep frame's tone buffers, and the table of a fixed mode (outside the capture: the graph only reads it)
+    if (ok.e == hipSuccess && next.intake.deep()) ok(tone_prepare(&lv->tone_work, next.intake.tone, ctx->stream));
     int rc = ok.e == hipSuccess ? NMI_OK : hip_fail(ctx, ok.e, what);
     const LevelSettings was = lv->set;
     if (rc == NMI_OK) {
@@ -291,10 +295,12 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     if (rc != NMI_OK) {
         lv->set = was;
         for (DeviceBuffer *slot : fresh) (void)slot->reset();
+        if (was.intake.deep()) (void)tone_prepare(&lv->tone_work, was.intake.tone, ctx->stream);  // the old graph's table again
         return rc;
     }
     for (const LevelBuffer &b : level_buffers(lv, lv->set))  // no graph reads these any more
         if (!b.needed) (void)b.slot->reset();
+    if (!lv->set.intake.deep()) lv->tone_work = ToneWork{};
     return NMI_OK;
 }
 
@@ -657,7 +663,17 @@ int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format,
     if (!lv) return NMI_ERR_INVALID_ARGUMENT;
     LevelSettings next = lv->set;
     if (intake_set_frame(&next.intake, lv->ctx->params.width, lv->ctx->params.height, factor, format, pitch) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (!frame_base_ok(format, lv->d_frame)) return NMI_ERR_INVALID_ARGUMENT;
     return level_apply(lv, next, "nmi_level_set_frame_reduction");
+}
+
+int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm)
+{
+    FrameIntake probe;  // (as nmi_level_set_distortion: a bad argument is refused without reading *lv)
+    if (!lv || intake_set_tone_map(&probe, tm) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    next.intake.tone = probe.tone;
+    return level_apply(lv, next, "nmi_level_set_tone_map");
 }
 
 int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return nmi_level_set_frame_reduction(lv, 1, format, pitch); }
@@ -718,12 +734,13 @@ struct nmi_stream {
     // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction): frames submitted while one of them
     // is set are brought on the compute stream into d_ud[b] (distorted, masked / covered: their masks into d_ud_mask[b]), and the
     // warps are made from those.  A coloured, pitched or full-size host frame (intake.colored) crosses as its rows of
-    // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced (or a Bayer mosaic) and distorted, it is brought to
+    // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced (or a Bayer mosaic, or deep) and distorted, it is brought to
     // grey in d_frame[b] (idle meanwhile), which the undistortion reads as a grey frame.
     FrameIntake intake;
     DeviceBuffer d_ud[2];                         // uint8_t [H][W], allocated on the first distorted (or coloured) frame
     DeviceBuffer d_ud_mask[2];                    // uint8_t [H][W], allocated on the first distorted masked / covered frame
     DeviceBuffer d_color[2];                      // [f H][f W * bytes per pixel], allocated on the first coloured frame, grown for a larger one
+    ToneWork tone_work;                           // deep frames (GRAY16): one histogram and table, used in turn on the compute stream
 };
 
 namespace {
@@ -888,8 +905,9 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const uint8_t *frame = d_frame, *frame_mask = h_frame_mask ? d_fmask : nullptr;
         // the camera's frame (and mask) -> the grey, undistorted ones, on the compute stream: the warps read them next
         uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb].as<uint8_t>() : nullptr;
-        NMI_HIP_TRY(ctx, launch_intake(in, colored ? d_color : d_frame, dense_row, frame_mask, d_frame, d_ud, ud_mask, ctx->params.width,
-                                       ctx->params.height, ctx->stream));
+        if (in.deep()) NMI_HIP_TRY(ctx, tone_prepare(&st->tone_work, in.tone, ctx->stream));
+        NMI_HIP_TRY(ctx, launch_intake(in, st->tone_work, colored ? d_color : d_frame, dense_row, frame_mask, d_frame, d_ud, ud_mask,
+                                       ctx->params.width, ctx->params.height, ctx->stream));
         if (in.own_frame()) frame = d_ud;
         if (undistort) frame_mask = ud_mask;
         int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, d_warps)
@@ -1035,6 +1053,8 @@ int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t forma
 }
 
 int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) { return nmi_stream_set_frame_reduction(st, 1, format, pitch); }
+
+int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm) { return st ? intake_set_tone_map(&st->intake, tm) : NMI_ERR_INVALID_ARGUMENT; }
 
 int nmi_stream_keep_ratings(nmi_stream *st, int32_t enabled)
 {

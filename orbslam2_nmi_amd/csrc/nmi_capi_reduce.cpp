@@ -30,7 +30,7 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     const int64_t fW = (int64_t)factor * W, fH = (int64_t)factor * H;
     if (fW > INT32_MAX || fH > INT32_MAX) return NMI_ERR_INVALID_ARGUMENT;
     int64_t rb = 0;
-    if (frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK || !frame_base_ok(format, d_src)) return NMI_ERR_INVALID_ARGUMENT;
     // the source's bytes run from d_src to the end of its last row's pixels, the source mask's over its dense f H x f W bytes;
     // neither output may meet them, or the other output
     const uintptr_t s0 = (uintptr_t)d_src, m0 = (uintptr_t)d_src_mask, g0 = (uintptr_t)d_gray, o0 = (uintptr_t)d_mask;
@@ -41,7 +41,13 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     if (meet(gray, src) || meet(gray, src_mask) || meet(mask, src) || meet(mask, src_mask) || meet(gray, mask)) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    if (factor == 1) {  // nmi_gray_frame; the mask is copied as 0 / 1
+    if (format == NMI_FRAME_GRAY16) {  // the tone table from the full-size frame, then nmi_tone.hip's conversion at every factor
+        const nmi::ToneSetting t = ctx->tone;
+        const uint8_t *lut = nullptr;
+        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
+        NMI_HIP_TRY(ctx, launch_tone(ctx->tone_work, t, d_src, rb, (int)fW, (int)fH, &lut, ctx->stream));
+        NMI_HIP_TRY(ctx, nmi::launch_gray16(d_src, rb, factor, lut, t.bits, d_gray, W, H, ctx->stream));
+    } else if (factor == 1) {  // nmi_gray_frame; the mask is copied as 0 / 1
         NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
     } else {
         NMI_HIP_TRY(ctx, nmi::launch_reduce(d_src, format, rb, factor, d_gray, W, H, ctx->stream));

@@ -1,0 +1,118 @@
+// nmi_capi_tone.cpp -- the tone map of the deep grey frames (NMI_FRAME_GRAY16, include/nmi_hip.h): nmi_tone_map_default,
+// nmi_set_tone_map, nmi_tone_lut, and the host side every GRAY16 conversion shares (nmi_tone.h): the check of a setting, the
+// buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and nmi_stream_set_tone_map are with
+// the other setters in nmi_capi_pipeline.cpp.  Kernels: nmi_tone.hip.
+#include "nmi_tone.h"
+
+#include "nmi_color.h"
+#include "nmi_ctx.h"
+
+using namespace nmi_internal;
+
+int nmi_internal::tone_check(const nmi_tone_map *tm, nmi::ToneSetting *out)
+{
+    nmi::ToneSetting t;  // (the default: SHIFT, 16 bits)
+    if (tm) {
+        if (tm->bits < 8 || tm->bits > 16) return NMI_ERR_INVALID_ARGUMENT;
+        for (int32_t r : tm->reserved)
+            if (r != 0) return NMI_ERR_INVALID_ARGUMENT;
+        const int32_t M = (1 << tm->bits) - 1;
+        t.mode = tm->mode;
+        t.bits = tm->bits;
+        t.hi = M;
+        switch (tm->mode) {
+        case NMI_TONE_SHIFT: break;
+        case NMI_TONE_WINDOW:
+            if (tm->lo < 0 || tm->lo >= tm->hi || tm->hi > M) return NMI_ERR_INVALID_ARGUMENT;
+            t.lo = tm->lo, t.hi = tm->hi;
+            break;
+        case NMI_TONE_PERCENTILE:
+            if (tm->p_lo < 0 || tm->p_hi < 0 || (int64_t)tm->p_lo + tm->p_hi >= 10000) return NMI_ERR_INVALID_ARGUMENT;
+            t.p_lo = tm->p_lo, t.p_hi = tm->p_hi;
+            break;
+        case NMI_TONE_EQUALIZE:
+            if (tm->plateau < 0) return NMI_ERR_INVALID_ARGUMENT;
+            t.plateau = tm->plateau;
+            break;
+        case NMI_TONE_TABLE:
+            if (!tm->d_lut) return NMI_ERR_INVALID_ARGUMENT;
+            t.d_lut = tm->d_lut;
+            break;
+        default: return NMI_ERR_INVALID_ARGUMENT;
+        }
+    }
+    *out = t;
+    return NMI_OK;
+}
+
+hipError_t nmi_internal::tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream)
+{
+    const size_t lut_bytes = (size_t)nmi::kToneLevels + 2 * sizeof(int32_t);
+    if (w->lut.size() < lut_bytes) w->built = false;
+    hipError_t e = w->lut.grow(lut_bytes, stream);
+    if (e != hipSuccess || t.mode == NMI_TONE_TABLE) return e;
+    if (t.from_frame()) {  // the table is each frame's own; the histogram starts clean and every table kernel leaves it so
+        w->built = false;
+        return w->hist.grow(nmi::kToneHistWords * sizeof(uint32_t), stream, /*zero=*/true);
+    }
+    if (w->built && w->fixed == t) return hipSuccess;
+    e = nmi::launch_tone_table(t, nullptr, w->table(), w->window(), stream);
+    w->built = e == hipSuccess;
+    w->fixed = t;
+    return e;
+}
+
+hipError_t nmi_internal::launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
+                                     const uint8_t **lut, hipStream_t stream)
+{
+    *lut = t.mode == NMI_TONE_TABLE ? t.d_lut : w.table();
+    if (!t.from_frame()) return hipSuccess;
+    const hipError_t e = nmi::launch_tone_hist(src, pitch, width, height, t.bits, w.hist.as<uint32_t>(), stream);
+    return e != hipSuccess ? e : nmi::launch_tone_table(t, w.hist.as<uint32_t>(), w.table(), w.window(), stream);
+}
+
+extern "C" {
+
+int nmi_tone_map_default(nmi_tone_map *tm)
+{
+    if (!tm) return NMI_ERR_INVALID_ARGUMENT;
+    *tm = nmi_tone_map{};
+    tm->mode = NMI_TONE_SHIFT;
+    tm->bits = 16;
+    tm->hi = 65535;
+    return NMI_OK;
+}
+
+int nmi_set_tone_map(nmi_ctx *ctx, const nmi_tone_map *tm)
+{
+    if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
+    return tone_check(tm, &ctx->tone);
+}
+
+int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, uint8_t *d_lut, int32_t h_window[2])
+{
+    if (!ctx || !d_src || !d_lut || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
+    int64_t rb = 0;
+    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
+        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
+        return NMI_ERR_INVALID_ARGUMENT;
+    // the table's 65,536 bytes may not meet the source's (from d_src to the end of its last row's pixels)
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * rb + fW * 2);
+    const uintptr_t l0 = (uintptr_t)d_lut, l1 = l0 + (uintptr_t)nmi::kToneLevels;
+    if (l0 < s1 && s0 < l1) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    const nmi::ToneSetting t = ctx->tone;
+    ToneWork &w = ctx->tone_work;
+    NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
+    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, (int)fW, (int)fH, t.bits, w.hist.as<uint32_t>(), ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_tone_table(t, w.hist.as<uint32_t>(), d_lut, w.window(), ctx->stream));
+    if (h_window) {
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(h_window, w.window(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return NMI_OK;
+}
+
+}  // extern "C"

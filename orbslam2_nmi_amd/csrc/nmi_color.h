@@ -17,6 +17,8 @@ hipError_t launch_gray(const uint8_t *src, int format, int64_t pitch, uint8_t *g
 // format is one of NMI_FRAME_BAYER_*.
 inline bool frame_is_bayer(int format) { return format >= NMI_FRAME_BAYER_RGGB && format <= NMI_FRAME_BAYER_BGGR; }
 
+// (NMI_FRAME_GRAY16 is not launch_gray's or launch_reduce's: it needs its tone table, nmi_tone.h's launch_gray16.)
+
 // launch_gray (factor 1) and launch_reduce (nmi_reduce.h; factor 2 .. 4) of a Bayer mosaic of factor * height rows of factor *
 // width bytes (both >= 2), in one kernel (nmi_bayer.hip): launch_gray and launch_reduce pass their Bayer formats on to it.
 hipError_t launch_bayer(const uint8_t *src, int format, int64_t pitch, int factor, uint8_t *gray, int width, int height, hipStream_t stream);
@@ -33,7 +35,11 @@ namespace nmi_internal {
 // Bytes per pixel of an NMI_FRAME_* format, 0 for an unknown one.
 int frame_bytes_per_pixel(int32_t format);
 
-// format known, pitch 0 (dense) or >= width * bytes per pixel, a Bayer mosaic at least 2 x 2 -> NMI_OK, *row_bytes = the rows'
+// The source's first byte is aligned as format asks: GRAY16 on 2 bytes, every other format anywhere.
+inline bool frame_base_ok(int32_t format, const void *src) { return format != NMI_FRAME_GRAY16 || ((uintptr_t)src % 2) == 0; }
+
+// format known, pitch 0 (dense) or >= width * bytes per pixel, a Bayer mosaic at least 2 x 2, a GRAY16 pitch even (and the
+// frame below 2^32 pixels: its histogram counts in 32 bits) -> NMI_OK, *row_bytes = the rows'
 // pitch (width * bytes per pixel for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion);
 // else NMI_ERR_INVALID_ARGUMENT.  width and height are the source's.
 int frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity);

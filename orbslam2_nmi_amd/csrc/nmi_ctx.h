@@ -17,6 +17,7 @@
 #include "nmi_masked.h"
 #include "nmi_mem.h"
 #include "nmi_search_plan.h"
+#include "nmi_tone.h"
 
 // What a search launched (enqueue_grid, enqueue_grid_mask): the split-timeout redo logic and the status getters go by it.
 struct SearchLaunch {
@@ -125,6 +126,10 @@ struct nmi_ctx {
     // Covered search (nmi_capi_covered.cpp): per-candidate pixel counts.
     DeviceBuffer d_cover_counts;          // int32_t len[w][s] of the latest covered search, layout [Wn][S]
     int64_t cover_count_n = 0;            // candidates counted by the latest covered search
+    // Deep grey frames (nmi_capi_tone.cpp): the tone map nmi_gray_frame, nmi_reduce_frame and nmi_tone_lut read at call time
+    // (nmi_set_tone_map), and its histogram and table.
+    nmi::ToneSetting tone;
+    nmi_internal::ToneWork tone_work;
     nmi_mem::Event ev_start, ev_stop;
     int hist_variant = 3;
     int phase_mask = 3;

@@ -6,6 +6,7 @@
 #pragma once
 #include "nmi_hip.h"
 #include "nmi_color.h"
+#include "nmi_tone.h"
 #include "nmi_undistort.h"
 
 namespace nmi_internal {
@@ -21,12 +22,16 @@ struct FrameIntake {
     int32_t frame_format = NMI_FRAME_GRAY;
     int64_t frame_pitch = 0;                 // row bytes (never 0 while colored)
     int32_t frame_factor = 1;
+    // Tone map (nmi_*_set_tone_map): how a GRAY16 source's pixels become 8-bit; kept, and ignored, under every other format.
+    nmi::ToneSetting tone;
 
     bool reduced() const { return frame_factor > 1; }
     bool mosaic() const { return nmi::frame_is_bayer(frame_format); }
-    // grey frame first (into launch_intake's scratch), undistortion second: a reduction, and a Bayer mosaic, whose taps would
-    // each demosaic a 3 x 3 neighbourhood (profiles/sensor/README.md: the fused node takes twice the two nodes' time)
-    bool two_nodes() const { return distorted && (reduced() || mosaic()); }
+    bool deep() const { return frame_format == NMI_FRAME_GRAY16; }
+    // grey frame first (into launch_intake's scratch), undistortion second: a reduction, a Bayer mosaic, whose taps would
+    // each demosaic a 3 x 3 neighbourhood (profiles/sensor/README.md: the fused node takes twice the two nodes' time), and a
+    // deep frame, whose table comes from the whole frame first
+    bool two_nodes() const { return distorted && (reduced() || mosaic() || deep()); }
     bool own_frame() const { return distorted || colored; }  // the warps read gray_out, not the source
 };
 
@@ -37,6 +42,8 @@ int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const doub
 // factor 1 .. 4, format and pitch checked on the full size factor * (width, height) (frame_format_check).  Dense grey of the search
 // size: off (NMI_FRAME_GRAY, pitch 0).  A bad argument: NMI_ERR_INVALID_ARGUMENT, *in untouched.
 int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int32_t format, int64_t pitch);
+// tm == nullptr: the default (SHIFT, 16 bits).  A bad *tm: NMI_ERR_INVALID_ARGUMENT, *in untouched.
+int intake_set_tone_map(FrameIntake *in, const nmi_tone_map *tm);
 
 // Enqueues the intake's kernels: src (rows of src_row_bytes) -> the dense grey [H][W] gray_out; nothing when !in.own_frame().
 //   reduced               launch_reduce, into scratch when distorted; then launch_undistort from scratch
@@ -44,9 +51,11 @@ int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int
 //   coloured, distorted   launch_undistort_color alone: each tap converted to grey, then the undistortion's arithmetic
 //   distorted             launch_undistort
 //   coloured              launch_gray
+// A deep frame (GRAY16) takes launch_gray16 in launch_gray's and launch_reduce's place, behind the histogram and table nodes of a
+// PERCENTILE or EQUALIZE tone map (launch_tone); tone is its prepared work area (tone_prepare), unused for every other format.
 // mask_out (may be null; only written when distorted) = the undistorted src_mask (dense [H][W], may be null: border only).
 // scratch is [H][W] and needed only when in.two_nodes().
-hipError_t launch_intake(const FrameIntake &in, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask, uint8_t *scratch,
-                         uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream);
+hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask,
+                         uint8_t *scratch, uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream);
 
 }  // namespace nmi_internal
