@@ -567,10 +567,30 @@ int nmi_render_mesh_colored_masked(nmi_ctx *ctx, const float *d_xyz, const float
 /*
  * Map order.  What the renderers draw does not depend on the order of the points / triangles (the depth test is a
  * minimum); how fast they draw does: neighbours in memory are culled together and their fragments share cache lines of the
- * depth buffer (3 M points into 27 views: 96 us in scan order, 406 us shuffled, 116 us after nmi_sort_points).  These two
+ * depth buffer (3 M points into 27 views: 96 us in scan order, 406 us shuffled, 116 us after nmi_sort_points).  These three
  * calls copy a map into Morton order of its positions (triangles: centroids), on the device; a loader calls them once
- * after loadXYZ / loadOBJ (objloader.cpp:140-264), whose arrays are in file order.  Outputs must not alias the inputs.
+ * after loadXYZ / loadOBJ (objloader.cpp:140-264), whose arrays are in file order.
  * Blocking (temporary device storage: 16 bytes per record).  n below 2^32.
+ *
+ * The order is fully determined -- key, then input index -- by this rule, all of it in fp32, every operation rounded on its own
+ * (tests/helpers/morton_np.py restates it in numpy, tests/test_map_order.py holds the device to it record for record):
+ *   Position  the point itself; for a triangle the centroid ((p0 + p1) + p2) / 3, per coordinate.
+ *   Placed    a position is placed iff all three coordinates have |c| <= 3.0e38f.  That is stricter than "finite": a coordinate
+ *             in (3.0e38, FLT_MAX] is not placed, and neither is a triangle whose corners are finite but whose sum overflows.
+ *             A NaN or an infinity anywhere in a position leaves it unplaced.  Records that are not placed come last, in input
+ *             order (key 0x40000000, above every placed key).
+ *   Box       per axis lo = the least and hi = the greatest coordinate of the placed positions (-0.0 below +0.0).
+ *   Cell      per axis (uint32)(min(max((c - lo) / (hi - lo), 0), 1) * 1023.0f): 0 .. 1023, truncated.  Where hi - lo is 0
+ *             (planar and collinear maps, identical points, lo = -0.0 with hi = +0.0) the cell is 0.  Where hi - lo overflows
+ *             fp32 (say lo = -3e38, hi = 3e38) the quotient is x / inf = 0 or inf / inf = NaN, the max() turns the NaN into 0,
+ *             and the cell is 0 for every record: a map that wide on all three axes comes out in input order.
+ *   Key       bit 3 b + k of the key is bit b of axis k's cell (x: k = 0, y: 1, z: 2): 30 bits, x lowest.
+ *   Ties      records with equal keys keep input order (the radix sort is stable and carries the input index).
+ * Every record travels whole: a triangle's 9 coordinates with its 6 texture coordinates or 3 colours.
+ *
+ * NMI_ERR_INVALID_ARGUMENT, before anything is launched or written: a NULL context; n < 0 or n >= 2^32; with n > 0 a NULL
+ * array, or an output whose bytes (n records of it) intersect those of either input or of the other output -- the gather
+ * reads records while other lanes write theirs, so no overlap at any offset is allowed.  n = 0 is NMI_OK and touches nothing.
  */
 int nmi_sort_points(nmi_ctx *ctx, const float *d_xyz /*[N][3]*/, const float *d_red /*[N]*/, int64_t n_points, float *d_xyz_out,
                     float *d_red_out);

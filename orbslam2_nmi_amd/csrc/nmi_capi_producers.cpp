@@ -380,36 +380,54 @@ nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_textu
 
 }  // namespace nmi_internal
 
+namespace {
+
+// The argument check of the three nmi_sort_* calls ("Map order", include/nmi_hip.h), before any HIP call: record counts, null
+// arrays, and outputs that share a byte with an input or with each other -- at any offset, not only at equal pointers: the gather
+// reads whole records of the inputs while other lanes write theirs.  `a` holds na floats per record, `b` nb.
+int sort_arguments(const nmi_ctx *ctx, const float *a, int na, const float *b, int nb, int64_t n, const float *a_out, const float *b_out)
+{
+    if (!ctx || n < 0 || n >= (1ll << 32)) return NMI_ERR_INVALID_ARGUMENT;
+    if (n == 0) return NMI_OK;
+    if (!a || !b || !a_out || !b_out || a == a_out || b == b_out) return NMI_ERR_INVALID_ARGUMENT;
+    const uintptr_t a_bytes = (uintptr_t)n * (uintptr_t)na * sizeof(float), b_bytes = (uintptr_t)n * (uintptr_t)nb * sizeof(float);
+    auto meet = [](const float *p, uintptr_t p_bytes, const float *q, uintptr_t q_bytes) {
+        const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
+        return x < y ? y - x < p_bytes : x - y < q_bytes;
+    };
+    if (meet(a_out, a_bytes, a, a_bytes) || meet(a_out, a_bytes, b, b_bytes) || meet(b_out, b_bytes, a, a_bytes) ||
+        meet(b_out, b_bytes, b, b_bytes) || meet(a_out, a_bytes, b_out, b_bytes))
+        return NMI_ERR_INVALID_ARGUMENT;
+    return NMI_OK;
+}
+
+int sort_map(nmi_ctx *ctx, const float *a, int na, int verts, const float *b, int nb, int64_t n, float *a_out, float *b_out)
+{
+    const int rc = sort_arguments(ctx, a, na, b, nb, n, a_out, b_out);
+    if (rc != NMI_OK) return rc;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, nmi::sort_records_morton(a, na, verts, b, nb, n, a_out, b_out, ctx->stream));
+    return NMI_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int nmi_sort_points(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, float *d_xyz_out, float *d_red_out)
 {
-    if (!ctx || n_points < 0 || n_points >= (1ll << 32)) return NMI_ERR_INVALID_ARGUMENT;
-    if (n_points > 0 && (!d_xyz || !d_red || !d_xyz_out || !d_red_out || d_xyz == d_xyz_out || d_red == d_red_out)) return NMI_ERR_INVALID_ARGUMENT;
-    ctx->detail.clear();
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, nmi::sort_records_morton(d_xyz, 3, 1, d_red, 1, n_points, d_xyz_out, d_red_out, ctx->stream));
-    return NMI_OK;
+    return sort_map(ctx, d_xyz, 3, 1, d_red, 1, n_points, d_xyz_out, d_red_out);
 }
 
 int nmi_sort_triangles(nmi_ctx *ctx, const float *d_xyz, const float *d_uv, int64_t n_triangles, float *d_xyz_out, float *d_uv_out)
 {
-    if (!ctx || n_triangles < 0 || n_triangles >= (1ll << 32)) return NMI_ERR_INVALID_ARGUMENT;
-    if (n_triangles > 0 && (!d_xyz || !d_uv || !d_xyz_out || !d_uv_out || d_xyz == d_xyz_out || d_uv == d_uv_out)) return NMI_ERR_INVALID_ARGUMENT;
-    ctx->detail.clear();
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, nmi::sort_records_morton(d_xyz, 9, 3, d_uv, 6, n_triangles, d_xyz_out, d_uv_out, ctx->stream));
-    return NMI_OK;
+    return sort_map(ctx, d_xyz, 9, 3, d_uv, 6, n_triangles, d_xyz_out, d_uv_out);
 }
 
 int nmi_sort_triangles_colored(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_triangles, float *d_xyz_out, float *d_red_out)
 {
-    if (!ctx || n_triangles < 0 || n_triangles >= (1ll << 32)) return NMI_ERR_INVALID_ARGUMENT;
-    if (n_triangles > 0 && (!d_xyz || !d_red || !d_xyz_out || !d_red_out || d_xyz == d_xyz_out || d_red == d_red_out)) return NMI_ERR_INVALID_ARGUMENT;
-    ctx->detail.clear();
-    DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, nmi::sort_records_morton(d_xyz, 9, 3, d_red, 3, n_triangles, d_xyz_out, d_red_out, ctx->stream));
-    return NMI_OK;
+    return sort_map(ctx, d_xyz, 9, 3, d_red, 3, n_triangles, d_xyz_out, d_red_out);
 }
 
 }  // extern "C"
