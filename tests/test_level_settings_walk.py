@@ -18,6 +18,7 @@ import pytest
 
 from helpers import color_np as cnp
 from helpers import undistort_np as unp
+from helpers.walk_plan import euler_circuit, neighbours
 from orbslam2_nmi_amd import capi
 from test_color_level import enable, lens_K
 from test_covered_level import CoveredScene
@@ -28,6 +29,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 KINDS, LENSES, FRAMES = ("plain", "masked", "covered"), ("none", "barrel"), ("gray", "format", "reduced")
+AXES = (KINDS, LENSES, FRAMES)
 STATES = [(k, l, f) for k in KINDS for l in LENSES for f in FRAMES]
 OFF = ("plain", "none", "off")
 START = ("covered", "barrel", "reduced")
@@ -41,26 +43,6 @@ def nmi():
     import orbslam2_nmi_amd as m
     m.load_library()
     return m
-
-
-def neighbours(state):
-    """The 5 states one move away, in a fixed order."""
-    out = []
-    for axis, values in enumerate((KINDS, LENSES, FRAMES)):
-        out += [state[:axis] + (v,) + state[axis + 1:] for v in values if v != state[axis]]
-    return out
-
-
-def euler_circuit(start):
-    """Hierholzer on the move graph, edges taken in neighbours()' order -> the states visited, first == last."""
-    left = {s: list(reversed(neighbours(s))) for s in STATES}
-    stack, circuit = [start], []
-    while stack:
-        if left[stack[-1]]:
-            stack.append(left[stack[-1]].pop())
-        else:
-            circuit.append(stack.pop())
-    return circuit[::-1]
 
 
 class Walk:
@@ -152,10 +134,10 @@ SHAPES = [(160, 120, 16), (100, 75, 5)]
 @pytest.mark.parametrize("shape", SHAPES, ids=["160x120", "100x75"])
 def test_one_level_walks_every_move_between_its_settings(nmi, shape, mesh):
     w, h, pad = shape
-    circuit = euler_circuit(START)
+    circuit = euler_circuit(START, AXES)
     edges = list(zip(circuit[:-1], circuit[1:]))
     assert len(edges) == 90 and len(set(edges)) == 90 and set(circuit) == set(STATES) and circuit[0] == circuit[-1] == START
-    assert all(dst in neighbours(src) for src, dst in edges)
+    assert all(dst in neighbours(src, AXES) for src, dst in edges)
     # rejected calls at fixed points of the walk: after these moves (the third one at the first masked state from move 60 on)
     at_masked = next(i for i, (_, dst) in enumerate(edges) if i >= 60 and dst[0] == "masked")
     with nmi.NmiContext(w, h) as ctx:
