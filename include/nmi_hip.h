@@ -426,7 +426,7 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * Ids 47 and 49 stay unknown.  d_src and a non-zero pitch must be multiples of 2 (NMI_ERR_INVALID_ARGUMENT), the pitch and
  * overlap rules are the other formats' with 2 bytes per pixel, and a frame has at most 2^32 - 1 pixels.
  * The search bins 256 levels, so a deep pixel becomes 8-bit by a tone map, nmi_tone_map: per context (nmi_set_tone_map; read
- * by nmi_gray_frame, nmi_reduce_frame and nmi_tone_lut at call time), per level and per stream.  It is ignored for every other
+ * by nmi_gray_frame, nmi_reduce_frame, nmi_tone_lut and nmi_tone_tile_luts at call time), per level and per stream.  It is ignored for every other
  * format.  The rule is integers throughout.  M = 2^bits - 1; v = min(raw, M) (values above the declared depth saturate); N =
  * the pixels the call covers, W x H of the source or f W x f H for a reduced frame (a pitch's padding and spare rows or columns
  * are never read); h[v] = the exact count of v over them, c[v] its inclusive running sum.  A frame mask does not change h.
@@ -441,15 +441,35 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  *                        cv::equalizeHist's rule carried to 16 bits; with a plateau, the thermal cameras' plateau equalisation.
  *                        Parity with an OpenCV build is unpinned.
  *   NMI_TONE_TABLE       out = d_lut[v]: for callers who hold one mapping over a sequence (nmi_tone_lut makes one from a frame).
+ *   NMI_TONE_CLAHE       (mode 6; 5 stays unknown) contrast-limited equalisation per tile, the standard answer where one hot
+ *                        object or a cold sky would take most of a global table's levels.  The source (Ws x Hs = f W x f H) is
+ *                        cut into tiles_x x tiles_y tiles: column x is in tile column ((2 x + 1) tiles_x) / (2 Ws), row y in tile
+ *                        row ((2 y + 1) tiles_y) / (2 Hs); no tile is empty, and tiles differ in size where the size does not
+ *                        divide.  Per tile t of n_t pixels with exact counts h_t and L = M + 1 levels: plateau P == 0: c'' = the
+ *                        running sum of h_t.  P >= 1: E = sum max(h_t[v] - P, 0), c' = the running sum of min(h_t[v], P), q = E / L,
+ *                        r = E % L, step = max(L / r, 1), c''[v] = c'[v] + q (v + 1) + (r ? min(r, v / step + 1) : 0): every level
+ *                        gets q of the excess and levels 0, step, 2 step, ... one more until r are given out (cv::CLAHE's
+ *                        redistribution in closed form); c''[M] == n_t.  T_t[v] = (c''[v] 255 + (n_t >> 1)) / n_t, 64-bit products.
+ *                        Per pixel: ax = (2 x + 1) tiles_x - Ws, dx = 2 Ws, i0 = floor(ax / dx) (-1 in the first half tile),
+ *                        wx = ((ax - i0 dx) 256) / dx, i1 = i0 + 1, both clamped to 0 .. tiles_x - 1; j0, j1, wy likewise from y;
+ *                        out = ((T[j0][i0][v] (256 - wx) + T[j0][i1][v] wx) (256 - wy)
+ *                             + (T[j1][i0][v] (256 - wx) + T[j1][i1][v] wx) wy + 32768) >> 16.
+ *                        Parity with an OpenCV build is unpinned (it pads by reflection and interpolates in float).
  * A reduced frame maps each source pixel, then takes nmi_reduce_frame's rounded box average of the 8-bit values; the statistics
- * are the full-size frame's.  SHIFT, WINDOW and TABLE cost the conversion kernel alone; PERCENTILE and EQUALIZE put a histogram
- * kernel and two small table kernels in front of it, on the same stream (in a level: in the captured graph, from d_frame
- * at every replay; in a stream: for every submitted frame).  With a lens distortion the grey frame is made first and
- * undistorted second (two nodes, as for a mosaic).
+ * (CLAHE: the tiles and the blend too) are the full-size frame's.  SHIFT, WINDOW and TABLE cost the conversion kernel alone;
+ * PERCENTILE and EQUALIZE put a histogram kernel and two small table kernels in front of it, CLAHE a tile-histogram kernel and a
+ * tile-table kernel in front of a conversion kernel of its own (four table reads per source pixel), on the same stream (in a
+ * level: in the captured graph, from d_frame at every replay; in a stream: for every submitted frame).  With a lens distortion
+ * the grey frame is made first and undistorted second (two nodes, as for a mosaic).
+ * A CLAHE setting adds device memory to whoever converts with it -- the context (at the first nmi_gray_frame, nmi_reduce_frame
+ * or nmi_tone_tile_luts), a level, a stream, each for itself: tiles_x tiles_y (4 * 2^bits + 65536) bytes + 256, that is 20 MiB at
+ * 8 x 8 tiles of 16 bits, 8 MiB at 14 bits; kept until the owner is destroyed (a level drops it when its format leaves GRAY16).
  * nmi_tone_map_default fills *tm with SHIFT, bits 16 (the setting of a new context, level or stream; also what a NULL tm
  * sets).  NMI_ERR_INVALID_ARGUMENT, the setting left as it was: bits outside 8 .. 16, an unknown mode, a non-zero reserved
- * word, WINDOW without 0 <= lo < hi <= M, PERCENTILE with a negative share or p_lo + p_hi >= 10000, EQUALIZE with a negative
- * plateau, TABLE with a NULL d_lut.  Only the fields of the chosen mode (and bits, reserved) are read.
+ * word (tiles_x and tiles_y count as such under every mode but CLAHE), WINDOW without 0 <= lo < hi <= M, PERCENTILE with a
+ * negative share or p_lo + p_hi >= 10000, EQUALIZE or CLAHE with a negative plateau, TABLE with a NULL d_lut, CLAHE with a tile
+ * count outside 1 .. 8 or tiles_x > W or tiles_y > H of the context.  Only the fields of the chosen mode (and bits, tiles_x,
+ * tiles_y, reserved) are read.
  * nmi_level_set_tone_map captures the level again (waiting for a replay in flight), like the other level setters;
  * nmi_stream_set_tone_map holds for later submissions.
  * nmi_tone_lut writes the table the context's tone map gives for the frame at d_src (f H rows of pitch bytes, f W GRAY16 pixels
@@ -457,22 +477,31 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * stream; with h_window it blocks and returns {lo, hi}: PERCENTILE the chosen pair, EQUALIZE the smallest and largest value
  * present, WINDOW the given pair, SHIFT and TABLE {0, M}.  NMI_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL ctx,
  * d_src or d_lut, a factor outside 1 .. 4, an odd d_src or pitch, 0 < pitch < 2 f W, d_lut overlapping the source's bytes.
- * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, mask-aware statistics, CLAHE
- * (tiled equalisation), temporal smoothing of the window (TABLE is the hook: smooth on the host, pass the table).
+ * Under CLAHE there is no single table: NMI_ERR_UNSUPPORTED, nothing enqueued, d_lut untouched.
+ * nmi_tone_tile_luts is its CLAHE counterpart: T_t of every tile into d_luts [tiles_y][tiles_x][65536] (entry i the value of
+ * min(i, M)), enqueued on the context's stream; with h_counts it blocks and returns the tiles' pixel counts n_t.  The argument
+ * checks are nmi_tone_lut's (d_luts' tiles_x tiles_y 65,536 bytes may not meet the source's); under any other mode
+ * NMI_ERR_UNSUPPORTED, nothing enqueued, d_luts untouched.
+ * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, mask-aware statistics, CLAHE of
+ * 8-bit formats, caller-supplied tile tables, more than 8 x 8 tiles, temporal smoothing of the window (TABLE is the hook: smooth
+ * on the host, pass the table).
  */
 #define NMI_TONE_SHIFT 0
 #define NMI_TONE_WINDOW 1
 #define NMI_TONE_PERCENTILE 2
 #define NMI_TONE_EQUALIZE 3
 #define NMI_TONE_TABLE 4
+#define NMI_TONE_CLAHE 6 /* (not 5: mode 5 stays an unknown mode, NMI_ERR_INVALID_ARGUMENT) */
 
 typedef struct nmi_tone_map {
     int32_t mode;         /* NMI_TONE_* */
     int32_t bits;         /* significant bits of the container, 8 .. 16 */
     int32_t lo, hi;       /* WINDOW: 0 <= lo < hi <= 2^bits - 1 */
     int32_t p_lo, p_hi;   /* PERCENTILE: shares of the pixels cut at each end, in 1/10000; >= 0, p_lo + p_hi < 10000 */
-    int32_t plateau;      /* EQUALIZE: per-level count limit, 0 = none; >= 0 */
-    int32_t reserved[5];  /* must be 0 */
+    int32_t plateau;      /* EQUALIZE, CLAHE: per-level count limit (CLAHE: per tile), 0 = none; >= 0 */
+    int32_t tiles_x, tiles_y; /* CLAHE: tiles per axis, 1 .. 8, tiles_x <= W, tiles_y <= H; 0 under every other mode (they were
+                                 the first two reserved words: layout and size are unchanged) */
+    int32_t reserved[3];  /* must be 0 */
     const uint8_t *d_lut; /* TABLE: device uint8 [65536], must stay valid and unchanged while the setting is in force */
 } nmi_tone_map;
 
@@ -480,6 +509,8 @@ int nmi_tone_map_default(nmi_tone_map *tm);
 int nmi_set_tone_map(nmi_ctx *ctx, const nmi_tone_map *tm /* NULL = the default */);
 int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
                  uint8_t *d_lut /* [65536] */, int32_t h_window[2] /* nullable */);
+int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
+                       uint8_t *d_luts /* [tiles_y][tiles_x][65536] */, int32_t *h_counts /* nullable, [tiles_y][tiles_x] */);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU

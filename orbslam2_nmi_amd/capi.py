@@ -42,7 +42,9 @@ TONE_WINDOW = 1
 TONE_PERCENTILE = 2
 TONE_EQUALIZE = 3
 TONE_TABLE = 4
+TONE_CLAHE = 6       # (5 stays an unknown mode)
 TONE_LEVELS = 65536  # entries of a tone table
+TONE_MAX_TILES = 8   # CLAHE: tiles per axis
 
 # Every symbol include/nmi_hip.h declares; tests check that the library exports all of them.
 EXPORTED_SYMBOLS = (
@@ -65,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "nmi_level_create_mesh_colored_block",
     "nmi_undistort_frame_fisheye", "nmi_level_set_distortion_fisheye", "nmi_stream_set_distortion_fisheye",
     "nmi_tone_map_default", "nmi_set_tone_map", "nmi_level_set_tone_map", "nmi_stream_set_tone_map", "nmi_tone_lut",
+    "nmi_tone_tile_luts",
 )
 
 
@@ -82,6 +85,31 @@ class ToneMap(C.Structure):
     _fields_ = [("mode", C.c_int32), ("bits", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("p_lo", C.c_int32),
                 ("p_hi", C.c_int32), ("plateau", C.c_int32), ("reserved", C.c_int32 * 5), ("d_lut", C.c_void_p)]
     table = None
+
+    # CLAHE's tile counts are the first two of the header's five former reserved words (tiles_x, tiles_y, reserved[3]).
+    @property
+    def tiles_x(self):
+        return int(self.reserved[0])
+
+    @tiles_x.setter
+    def tiles_x(self, n):
+        self.reserved[0] = int(n)
+
+    @property
+    def tiles_y(self):
+        return int(self.reserved[1])
+
+    @tiles_y.setter
+    def tiles_y(self, n):
+        self.reserved[1] = int(n)
+
+    @classmethod
+    def clahe(cls, tiles_x=8, tiles_y=8, plateau=0, bits=16):
+        """Contrast-limited equalisation per tile (TONE_CLAHE): tiles_x x tiles_y tiles, 1 .. TONE_MAX_TILES each and no more
+        than the context's width and height; plateau: the per-level count limit within a tile, 0 = none."""
+        tm = cls(mode=TONE_CLAHE, bits=bits, plateau=plateau)
+        tm.tiles_x, tm.tiles_y = tiles_x, tiles_y
+        return tm
 
     @classmethod
     def shift(cls, bits=16):
@@ -222,6 +250,8 @@ def load_library(build_if_missing=False):
         lib.nmi_level_set_tone_map.argtypes = [vp, C.POINTER(ToneMap)]
         lib.nmi_stream_set_tone_map.argtypes = [vp, C.POINTER(ToneMap)]
         lib.nmi_tone_lut.argtypes = [vp, vp, C.c_int64, i32, vp, C.POINTER(i32)]
+    if hasattr(lib, "nmi_tone_tile_luts"):
+        lib.nmi_tone_tile_luts.argtypes = [vp, vp, C.c_int64, i32, vp, C.POINTER(i32)]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -670,8 +700,8 @@ class NmiContext:
         return out
 
     def set_tone_map(self, tm=None):
-        """nmi_set_tone_map: the tone map (ToneMap; None: SHIFT, 16 bits) gray_frame, reduce_frame and tone_lut apply to a
-        FRAME_GRAY16 source from now on.  Ignored for every other format."""
+        """nmi_set_tone_map: the tone map (ToneMap; None: SHIFT, 16 bits) gray_frame, reduce_frame, tone_lut and tone_tile_luts
+        apply to a FRAME_GRAY16 source from now on.  Ignored for every other format."""
         self._check(self._lib.nmi_set_tone_map(self._h, _tone_ref(tm)), "nmi_set_tone_map")
         self._tone = tm  # (a TABLE's tensor stays alive)
 
@@ -696,6 +726,31 @@ class NmiContext:
         self._order_after_torch()
         self._check(self._lib.nmi_tone_lut(self._h, src.data_ptr(), int(pitch), f, out.data_ptr(), pair if window else None), "nmi_tone_lut")
         return (out, (int(pair[0]), int(pair[1]))) if window else out
+
+    def tone_tile_luts(self, src, factor=1, pitch=0, out=None, counts=True):
+        """nmi_tone_tile_luts: the uint8 tables [tiles_y, tiles_x, TONE_LEVELS] the context's CLAHE tone map gives for the tiles of
+        the FRAME_GRAY16 frame src (as for tone_lut).  counts: blocks and returns (tables, int32 [tiles_y, tiles_x] pixels per
+        tile); else the tables alone, enqueued.  out: any contiguous device uint8 tensor of that many bytes."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        tm = getattr(self, "_tone", None)
+        ty, tx = (tm.tiles_y, tm.tiles_x) if tm is not None and tm.mode == TONE_CLAHE else (1, 1)  # (else the call refuses)
+        f = int(factor)
+        if int(pitch) >= 0 and 1 <= f <= 4:
+            need = (f * self.height - 1) * (int(pitch) or f * self.width * 2) + f * self.width * 2
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        if out is None:
+            out = torch.empty((ty, tx, TONE_LEVELS), dtype=torch.uint8, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == ty * tx * TONE_LEVELS):
+            raise TypeError(f"out must be a contiguous device uint8 tensor of {ty * tx * TONE_LEVELS} entries")
+        n = (C.c_int32 * (ty * tx))()
+        self._order_after_torch()
+        self._check(self._lib.nmi_tone_tile_luts(self._h, src.data_ptr(), int(pitch), f, out.data_ptr(), n if counts else None),
+                    "nmi_tone_tile_luts")
+        return (out, np.array(n, dtype=np.int32).reshape(ty, tx)) if counts else out
 
     def reduce_frame(self, src, fmt, factor, pitch=0, src_mask=None, out=None, out_mask=None, sync=True):
         """nmi_reduce_frame: the full-size camera frame src (device uint8 tensor holding factor * H rows of `pitch` bytes, each
@@ -1202,8 +1257,8 @@ class NmiLevel:
         self.ctx._check(self._lib.nmi_level_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_level_set_frame_format")
 
     def set_tone_map(self, tm=None):
-        """Tone map of a FRAME_GRAY16 frame (nmi_level_set_tone_map; ToneMap, None: SHIFT, 16 bits): PERCENTILE and EQUALIZE take
-        their statistics from the frame at every replay.  Ignored under every other format."""
+        """Tone map of a FRAME_GRAY16 frame (nmi_level_set_tone_map; ToneMap, None: SHIFT, 16 bits): PERCENTILE, EQUALIZE and CLAHE
+        take their statistics from the frame at every replay.  Ignored under every other format."""
         self.ctx._check(self._lib.nmi_level_set_tone_map(self._h, _tone_ref(tm)), "nmi_level_set_tone_map")
         self._tone = tm
 
@@ -1353,7 +1408,7 @@ class NmiStream:
 
     def set_tone_map(self, tm=None):
         """Tone map of FRAME_GRAY16 host frames (nmi_stream_set_tone_map; ToneMap, None: SHIFT, 16 bits), for later submissions:
-        PERCENTILE and EQUALIZE take their statistics from each submitted frame."""
+        PERCENTILE, EQUALIZE and CLAHE take their statistics from each submitted frame."""
         self.ctx._check(self._lib.nmi_stream_set_tone_map(self._h, _tone_ref(tm)), "nmi_stream_set_tone_map")
         self._tone = tm
 

@@ -43,28 +43,15 @@ int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int
     return NMI_OK;
 }
 
-int intake_set_tone_map(FrameIntake *in, const nmi_tone_map *tm) { return tone_check(tm, &in->tone); }
-
-namespace {
-
-// The deep frame's nodes: the tone table of the full-size source where it comes from the frame, then the conversion (and reduction).
-hipError_t launch_deep(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, uint8_t *gray, int width,
-                       int height, hipStream_t stream)
-{
-    const int f = in.frame_factor;
-    const uint8_t *lut = nullptr;
-    const hipError_t e = launch_tone(tone, in.tone, src, src_row_bytes, f * width, f * height, &lut, stream);
-    return e != hipSuccess ? e : nmi::launch_gray16(src, src_row_bytes, f, lut, in.tone.bits, gray, width, height, stream);
-}
-
-}  // namespace
+int intake_set_tone_map(FrameIntake *in, int width, int height, const nmi_tone_map *tm) { return tone_check(tm, width, height, &in->tone); }
 
 hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask,
                          uint8_t *scratch, uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream)
 {
     const uint8_t *raw_mask = mask_out ? src_mask : nullptr;
     if (in.deep()) {  // (distorted: two_nodes())
-        const hipError_t e = launch_deep(in, tone, src, src_row_bytes, in.distorted ? scratch : gray_out, width, height, stream);
+        // the tone tables of the full-size source where they come from the frame, then the conversion (and reduction)
+        const hipError_t e = deep_gray(tone, in.tone, src, src_row_bytes, in.frame_factor, in.distorted ? scratch : gray_out, width, height, stream);
         if (e != hipSuccess || !in.distorted) return e;
         return nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
     }

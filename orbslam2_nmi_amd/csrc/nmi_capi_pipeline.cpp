@@ -669,8 +669,8 @@ int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor, int32_t format,
 
 int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm)
 {
-    FrameIntake probe;  // (as nmi_level_set_distortion: a bad argument is refused without reading *lv)
-    if (!lv || intake_set_tone_map(&probe, tm) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    FrameIntake probe;
+    if (!lv || intake_set_tone_map(&probe, lv->ctx->params.width, lv->ctx->params.height, tm) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     LevelSettings next = lv->set;
     next.intake.tone = probe.tone;
     return level_apply(lv, next, "nmi_level_set_tone_map");
@@ -1054,7 +1054,10 @@ int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor, int32_t forma
 
 int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) { return nmi_stream_set_frame_reduction(st, 1, format, pitch); }
 
-int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm) { return st ? intake_set_tone_map(&st->intake, tm) : NMI_ERR_INVALID_ARGUMENT; }
+int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm)
+{
+    return st ? intake_set_tone_map(&st->intake, st->ctx->params.width, st->ctx->params.height, tm) : NMI_ERR_INVALID_ARGUMENT;
+}
 
 int nmi_stream_keep_ratings(nmi_stream *st, int32_t enabled)
 {

@@ -43,10 +43,8 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     DeviceGuard guard(ctx->device);
     if (format == NMI_FRAME_GRAY16) {  // the tone table from the full-size frame, then nmi_tone.hip's conversion at every factor
         const nmi::ToneSetting t = ctx->tone;
-        const uint8_t *lut = nullptr;
         NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
-        NMI_HIP_TRY(ctx, launch_tone(ctx->tone_work, t, d_src, rb, (int)fW, (int)fH, &lut, ctx->stream));
-        NMI_HIP_TRY(ctx, nmi::launch_gray16(d_src, rb, factor, lut, t.bits, d_gray, W, H, ctx->stream));
+        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, d_src, rb, factor, d_gray, W, H, ctx->stream));
     } else if (factor == 1) {  // nmi_gray_frame; the mask is copied as 0 / 1
         NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
     } else {

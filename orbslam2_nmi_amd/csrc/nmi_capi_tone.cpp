@@ -1,7 +1,8 @@
 // nmi_capi_tone.cpp -- the tone map of the deep grey frames (NMI_FRAME_GRAY16, include/nmi_hip.h): nmi_tone_map_default,
-// nmi_set_tone_map, nmi_tone_lut, and the host side every GRAY16 conversion shares (nmi_tone.h): the check of a setting, the
-// buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and nmi_stream_set_tone_map are with
-// the other setters in nmi_capi_pipeline.cpp.  Kernels: nmi_tone.hip.
+// nmi_set_tone_map, nmi_tone_lut, nmi_tone_tile_luts, and the host side every GRAY16 conversion shares (nmi_tone.h): the check of
+// a setting, the buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and
+// nmi_stream_set_tone_map are with the other setters in nmi_capi_pipeline.cpp.  Kernels: nmi_tone.hip, and nmi_clahe.hip for the
+// tiled mode.
 #include "nmi_tone.h"
 
 #include "nmi_color.h"
@@ -9,11 +10,13 @@
 
 using namespace nmi_internal;
 
-int nmi_internal::tone_check(const nmi_tone_map *tm, nmi::ToneSetting *out)
+int nmi_internal::tone_check(const nmi_tone_map *tm, int width, int height, nmi::ToneSetting *out)
 {
     nmi::ToneSetting t;  // (the default: SHIFT, 16 bits)
     if (tm) {
         if (tm->bits < 8 || tm->bits > 16) return NMI_ERR_INVALID_ARGUMENT;
+        // the tile counts were reserved words: 0 under every mode but CLAHE
+        if (tm->mode != NMI_TONE_CLAHE && (tm->tiles_x != 0 || tm->tiles_y != 0)) return NMI_ERR_INVALID_ARGUMENT;
         for (int32_t r : tm->reserved)
             if (r != 0) return NMI_ERR_INVALID_ARGUMENT;
         const int32_t M = (1 << tm->bits) - 1;
@@ -38,6 +41,13 @@ int nmi_internal::tone_check(const nmi_tone_map *tm, nmi::ToneSetting *out)
             if (!tm->d_lut) return NMI_ERR_INVALID_ARGUMENT;
             t.d_lut = tm->d_lut;
             break;
+        case NMI_TONE_CLAHE:
+            if (tm->plateau < 0 || tm->tiles_x < 1 || tm->tiles_x > nmi::kClaheMaxTiles || tm->tiles_y < 1 || tm->tiles_y > nmi::kClaheMaxTiles ||
+                tm->tiles_x > width || tm->tiles_y > height)
+                return NMI_ERR_INVALID_ARGUMENT;
+            t.plateau = tm->plateau;
+            t.tiles_x = tm->tiles_x, t.tiles_y = tm->tiles_y;
+            break;
         default: return NMI_ERR_INVALID_ARGUMENT;
         }
     }
@@ -51,6 +61,11 @@ hipError_t nmi_internal::tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hi
     if (w->lut.size() < lut_bytes) w->built = false;
     hipError_t e = w->lut.grow(lut_bytes, stream);
     if (e != hipSuccess || t.mode == NMI_TONE_TABLE) return e;
+    if (t.tiled()) {  // the tiles' histograms start clean and the table kernel leaves them so; a setting of fewer bits or tiles fits
+        w->built = false;
+        e = w->tile_luts.grow(nmi::clahe_luts_bytes(t) + nmi::kClaheMaxTileCount * sizeof(uint32_t), stream);
+        return e != hipSuccess ? e : w->tile_hist.grow(nmi::clahe_hist_bytes(t), stream, /*zero=*/true);
+    }
     if (t.from_frame()) {  // the table is each frame's own; the histogram starts clean and every table kernel leaves it so
         w->built = false;
         return w->hist.grow(nmi::kToneHistWords * sizeof(uint32_t), stream, /*zero=*/true);
@@ -71,6 +86,43 @@ hipError_t nmi_internal::launch_tone(const ToneWork &w, const nmi::ToneSetting &
     return e != hipSuccess ? e : nmi::launch_tone_table(t, w.hist.as<uint32_t>(), w.table(), w.window(), stream);
 }
 
+hipError_t nmi_internal::launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width,
+                                           int height, hipStream_t stream)
+{
+    const hipError_t e = nmi::launch_clahe_hist(t, src, pitch, width, height, w.tile_hist.as<uint32_t>(), stream);
+    return e != hipSuccess ? e : nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), w.tile_tables(), w.tile_counts(t), stream);
+}
+
+hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray,
+                                   int width, int height, hipStream_t stream)
+{
+    if (t.tiled()) {
+        const hipError_t e = launch_clahe_tone(w, t, src, pitch, factor * width, factor * height, stream);
+        return e != hipSuccess ? e : nmi::launch_clahe_gray16(t, src, pitch, factor, w.tile_tables(), gray, width, height, stream);
+    }
+    const uint8_t *lut = nullptr;
+    const hipError_t e = launch_tone(w, t, src, pitch, factor * width, factor * height, &lut, stream);
+    return e != hipSuccess ? e : nmi::launch_gray16(src, pitch, factor, lut, t.bits, gray, width, height, stream);
+}
+
+namespace {
+
+// nmi_tone_lut's and nmi_tone_tile_luts' arguments: the f W x f H GRAY16 source, and `bytes` of table at d_out that may not
+// meet the source's bytes (from d_src to the end of its last row's pixels).  NMI_OK: *rb = the row bytes.
+int tone_source_check(const nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, const uint8_t *d_out, size_t bytes, int64_t *rb)
+{
+    if (!ctx || !d_src || !d_out || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
+    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, rb, nullptr) != NMI_OK ||
+        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
+        return NMI_ERR_INVALID_ARGUMENT;
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * *rb + fW * 2);
+    const uintptr_t l0 = (uintptr_t)d_out, l1 = l0 + (uintptr_t)bytes;
+    return l0 < s1 && s0 < l1 ? NMI_ERR_INVALID_ARGUMENT : NMI_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int nmi_tone_map_default(nmi_tone_map *tm)
@@ -86,30 +138,47 @@ int nmi_tone_map_default(nmi_tone_map *tm)
 int nmi_set_tone_map(nmi_ctx *ctx, const nmi_tone_map *tm)
 {
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
-    return tone_check(tm, &ctx->tone);
+    return tone_check(tm, ctx->params.width, ctx->params.height, &ctx->tone);
 }
 
 int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, uint8_t *d_lut, int32_t h_window[2])
 {
-    if (!ctx || !d_src || !d_lut || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
-    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
     int64_t rb = 0;
-    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
-        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
-        return NMI_ERR_INVALID_ARGUMENT;
-    // the table's 65,536 bytes may not meet the source's (from d_src to the end of its last row's pixels)
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * rb + fW * 2);
-    const uintptr_t l0 = (uintptr_t)d_lut, l1 = l0 + (uintptr_t)nmi::kToneLevels;
-    if (l0 < s1 && s0 < l1) return NMI_ERR_INVALID_ARGUMENT;
+    if (tone_source_check(ctx, d_src, pitch, factor, d_lut, nmi::kToneLevels, &rb) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const int fW = factor * ctx->params.width, fH = factor * ctx->params.height;
+    const nmi::ToneSetting t = ctx->tone;
+    if (t.tiled()) return NMI_ERR_UNSUPPORTED;  // no single table: nmi_tone_tile_luts
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    const nmi::ToneSetting t = ctx->tone;
     ToneWork &w = ctx->tone_work;
     NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
-    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, (int)fW, (int)fH, t.bits, w.hist.as<uint32_t>(), ctx->stream));
+    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, fW, fH, t.bits, w.hist.as<uint32_t>(), ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_tone_table(t, w.hist.as<uint32_t>(), d_lut, w.window(), ctx->stream));
     if (h_window) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(h_window, w.window(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return NMI_OK;
+}
+
+int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, uint8_t *d_luts, int32_t *h_counts)
+{
+    if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
+    const nmi::ToneSetting t = ctx->tone;
+    const size_t bytes = t.tiled() ? nmi::clahe_luts_bytes(t) : (size_t)nmi::kToneLevels;
+    int64_t rb = 0;
+    if (tone_source_check(ctx, d_src, pitch, factor, d_luts, bytes, &rb) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (!t.tiled()) return NMI_ERR_UNSUPPORTED;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    ToneWork &w = ctx->tone_work;
+    NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_clahe_hist(t, d_src, rb, factor * ctx->params.width, factor * ctx->params.height, w.tile_hist.as<uint32_t>(),
+                                            ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), d_luts, w.tile_counts(t), ctx->stream));
+    if (h_counts) {
+        NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, w.tile_counts(t), (size_t)t.tiles_x * t.tiles_y * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                        ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return NMI_OK;

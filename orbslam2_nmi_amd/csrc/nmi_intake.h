@@ -42,8 +42,9 @@ int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const doub
 // factor 1 .. 4, format and pitch checked on the full size factor * (width, height) (frame_format_check).  Dense grey of the search
 // size: off (NMI_FRAME_GRAY, pitch 0).  A bad argument: NMI_ERR_INVALID_ARGUMENT, *in untouched.
 int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int32_t format, int64_t pitch);
-// tm == nullptr: the default (SHIFT, 16 bits).  A bad *tm: NMI_ERR_INVALID_ARGUMENT, *in untouched.
-int intake_set_tone_map(FrameIntake *in, const nmi_tone_map *tm);
+// tm == nullptr: the default (SHIFT, 16 bits).  A bad *tm (CLAHE: for a context of width x height): NMI_ERR_INVALID_ARGUMENT, *in
+// untouched.
+int intake_set_tone_map(FrameIntake *in, int width, int height, const nmi_tone_map *tm);
 
 // Enqueues the intake's kernels: src (rows of src_row_bytes) -> the dense grey [H][W] gray_out; nothing when !in.own_frame().
 //   reduced               launch_reduce, into scratch when distorted; then launch_undistort from scratch
@@ -51,8 +52,9 @@ int intake_set_tone_map(FrameIntake *in, const nmi_tone_map *tm);
 //   coloured, distorted   launch_undistort_color alone: each tap converted to grey, then the undistortion's arithmetic
 //   distorted             launch_undistort
 //   coloured              launch_gray
-// A deep frame (GRAY16) takes launch_gray16 in launch_gray's and launch_reduce's place, behind the histogram and table nodes of a
-// PERCENTILE or EQUALIZE tone map (launch_tone); tone is its prepared work area (tone_prepare), unused for every other format.
+// A deep frame (GRAY16) takes deep_gray (nmi_tone.h) in launch_gray's and launch_reduce's place: launch_gray16 behind the histogram
+// and table nodes of a PERCENTILE or EQUALIZE tone map, or CLAHE's tile histograms, tile tables and blending conversion; tone is
+// its prepared work area (tone_prepare), unused for every other format.
 // mask_out (may be null; only written when distorted) = the undistorted src_mask (dense [H][W], may be null: border only).
 // scratch is [H][W] and needed only when in.two_nodes().
 hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask,

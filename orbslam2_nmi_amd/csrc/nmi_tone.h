@@ -3,6 +3,8 @@
 // the fixed modes' (SHIFT, WINDOW) is built when the setting changes, the data-dependent ones' (PERCENTILE, EQUALIZE) by two
 // kernels in front of every conversion, and TABLE's is the caller's.  Used by nmi_capi_tone.cpp (the entries), nmi_capi_color.cpp,
 // nmi_capi_reduce.cpp and nmi_capi_intake.cpp (levels and streams).
+// CLAHE is the one mode with a table per tile, four of them blended per pixel: its kernels are nmi_clahe.hip's, its buffers
+// ToneWork's tile_hist and tile_luts, and deep_gray() below is where a conversion takes one way or the other.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,13 +24,15 @@ struct ToneSetting {
     int32_t mode = NMI_TONE_SHIFT, bits = 16;
     int32_t lo = 0, hi = 65535;      // WINDOW
     int32_t p_lo = 0, p_hi = 0;      // PERCENTILE
-    int32_t plateau = 0;             // EQUALIZE
+    int32_t plateau = 0;             // EQUALIZE, CLAHE
+    int32_t tiles_x = 0, tiles_y = 0;  // CLAHE: 1 .. kClaheMaxTiles each (0 under every other mode)
     const uint8_t *d_lut = nullptr;  // TABLE: the caller's
-    bool from_frame() const { return mode == NMI_TONE_PERCENTILE || mode == NMI_TONE_EQUALIZE; }
+    bool tiled() const { return mode == NMI_TONE_CLAHE; }
+    bool from_frame() const { return mode == NMI_TONE_PERCENTILE || mode == NMI_TONE_EQUALIZE || mode == NMI_TONE_CLAHE; }
     bool operator==(const ToneSetting &o) const
     {
         return mode == o.mode && bits == o.bits && lo == o.lo && hi == o.hi && p_lo == o.p_lo && p_hi == o.p_hi && plateau == o.plateau &&
-               d_lut == o.d_lut;
+               tiles_x == o.tiles_x && tiles_y == o.tiles_y && d_lut == o.d_lut;
     }
 };
 
@@ -47,18 +51,45 @@ hipError_t launch_tone_table(const ToneSetting &t, uint32_t *hist, uint8_t *lut,
 hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, uint8_t *gray, int width, int height,
                          hipStream_t stream);
 
+// --- CLAHE (nmi_clahe.hip; the rule: include/nmi_hip.h "Deep frames") ---------------------------------------------------------
+constexpr int kClaheMaxTiles = 8;                                  // per axis
+constexpr int kClaheMaxTileCount = kClaheMaxTiles * kClaheMaxTiles;
+// Bytes of the tile histograms (uint32 [ty][tx][2^bits], zero between frames) and of the tile tables (uint8 [ty][tx][65536],
+// then the tiles' pixel counts, uint32 [kClaheMaxTileCount]).
+inline size_t clahe_hist_bytes(const ToneSetting &t) { return ((size_t)t.tiles_x * t.tiles_y << t.bits) * sizeof(uint32_t); }
+inline size_t clahe_luts_bytes(const ToneSetting &t) { return (size_t)t.tiles_x * t.tiles_y * kToneLevels; }
+
+// hist[tile][v] += the number of pixels with min(raw, 2^bits - 1) == v in each tile of the tiles_x x tiles_y grid over the
+// width x height source (rows of pitch bytes; src and pitch even; tiles_x <= width, tiles_y <= height).  Exact for any content.
+hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, uint32_t *hist, hipStream_t stream);
+
+// luts[tile][i] = the tile's 8-bit value of min(i, 2^bits - 1) for all kToneLevels indices, counts[tile] = its pixels; hist is
+// left all zero for the next frame.
+hipError_t launch_clahe_tables(const ToneSetting &t, uint32_t *hist, uint8_t *luts, uint32_t *counts, hipStream_t stream);
+
+// launch_gray16 under CLAHE: the blend of the four nearest tiles' tables per source pixel of the factor * width x factor * height
+// source, then the rounded box average.
+hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, uint8_t *gray,
+                               int width, int height, hipStream_t stream);
+
 }  // namespace nmi
 
 namespace nmi_internal {
 
-// *tm well formed (include/nmi_hip.h; null: the default) -> NMI_OK and *out; else NMI_ERR_INVALID_ARGUMENT, *out untouched.
-int tone_check(const nmi_tone_map *tm, nmi::ToneSetting *out);
+// *tm well formed for a context of width x height (include/nmi_hip.h; null: the default) -> NMI_OK and *out; else
+// NMI_ERR_INVALID_ARGUMENT, *out untouched.
+int tone_check(const nmi_tone_map *tm, int width, int height, nmi::ToneSetting *out);
 
 // The device side of one tone setting's user (a context, a level, a stream): the histogram (zero between frames), the table
-// with the window pair behind it, and which fixed setting the table currently holds.
+// with the window pair behind it, and which fixed setting the table currently holds; under CLAHE the tiles' histograms (zero
+// between frames) and tables, up to 16 MiB and 4 MiB at 8 x 8 tiles of 16 bits.
 struct ToneWork {
     nmi_mem::DeviceBuffer hist;  // uint32_t [kToneHistWords]
     nmi_mem::DeviceBuffer lut;   // uint8_t [kToneLevels], then int32_t [2]
+    nmi_mem::DeviceBuffer tile_hist;  // CLAHE: clahe_hist_bytes
+    nmi_mem::DeviceBuffer tile_luts;  // CLAHE: clahe_luts_bytes, then uint32_t [kClaheMaxTileCount]
+    uint8_t *tile_tables() const { return tile_luts.as<uint8_t>(); }
+    uint32_t *tile_counts(const nmi::ToneSetting &t) const { return reinterpret_cast<uint32_t *>(tile_luts.as<uint8_t>() + nmi::clahe_luts_bytes(t)); }
     bool built = false;          // lut holds the table of `fixed`
     nmi::ToneSetting fixed;
     uint8_t *table() const { return lut.as<uint8_t>(); }
@@ -69,9 +100,20 @@ struct ToneWork {
 // cleared), and for SHIFT and WINDOW the table itself, built once per setting.  Not to be called inside a stream capture.
 hipError_t tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream);
 
-// The nodes in front of a GRAY16 conversion of the f W x f H source: the histogram and the table for a from_frame() mode,
-// nothing otherwise.  Returns through *lut the table the conversion reads.  *w was prepared for t.
+// The nodes in front of a GRAY16 conversion of the f W x f H source through one table: the histogram and the table for
+// PERCENTILE and EQUALIZE, nothing otherwise.  Returns through *lut the table the conversion reads.  *w was prepared for t,
+// which is not CLAHE.
 hipError_t launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
                        const uint8_t **lut, hipStream_t stream);
+
+
+// The CLAHE nodes in front of a conversion: the tile histograms of the width x height source, then the tile tables.
+hipError_t launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
+                             hipStream_t stream);
+
+// Every node of a GRAY16 conversion (nmi_gray_frame at factor 1, nmi_reduce_frame's, the intake's): the factor * width x factor *
+// height source to the dense grey [height][width] under t -- launch_tone and launch_gray16, or CLAHE's three.  *w was prepared for t.
+hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray, int width,
+                     int height, hipStream_t stream);
 
 }  // namespace nmi_internal

@@ -18,6 +18,7 @@
 
 #include "nmi_hip.h"
 #include "nmi_tone.h"
+#include "nmi_tone_device.h"
 #include "nmi_reduce_device.h"
 
 namespace nmi {
@@ -32,15 +33,6 @@ constexpr int kHistMaxWorkgroups = 1024;
 constexpr int kSegThreads = 256;                          // lanes of a table workgroup, four levels each
 constexpr int kSegments = kToneLevels / (4 * kSegThreads);  // 64 segments of 1024 levels = kToneRecords
 static_assert(kSegments == kToneRecords && kSegments == 64, "a wave scans the segments' records");
-
-// floor(num / den) for num < 2^42, 0 < den < 2^32, inv_den = 1.0 / den: the fp64 product is within one of it.
-__device__ __forceinline__ uint32_t floor_div(uint64_t num, uint32_t den, double inv_den)
-{
-    uint64_t q = (uint64_t)((double)num * inv_den);
-    if (q * den > num) --q;
-    if ((q + 1) * den <= num) ++q;
-    return (uint32_t)q;
-}
 
 // WINDOW's rule (include/nmi_hip.h); the order of the cases makes hi == lo all 0.
 __device__ __forceinline__ uint32_t tone_window(uint32_t v, uint32_t lo, uint32_t hi)
