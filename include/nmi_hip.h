@@ -429,7 +429,8 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * by nmi_gray_frame, nmi_reduce_frame, nmi_tone_lut and nmi_tone_tile_luts at call time), per level and per stream.  It is ignored for every other
  * format.  The rule is integers throughout.  M = 2^bits - 1; v = min(raw, M) (values above the declared depth saturate); N =
  * the pixels the call covers, W x H of the source or f W x f H for a reduced frame (a pitch's padding and spare rows or columns
- * are never read); h[v] = the exact count of v over them, c[v] its inclusive running sum.  A frame mask does not change h.
+ * are never read); h[v] = the exact count of v over them, c[v] its inclusive running sum.  A frame mask does not change h; a
+ * valid range (below) does: h and N are then those of the valid pixels.
  *   NMI_TONE_SHIFT       out = v >> (bits - 8)
  *   NMI_TONE_WINDOW      v <= lo: 0; otherwise v >= hi: 255; otherwise ((v - lo) * 255 + ((hi - lo) >> 1)) / (hi - lo)
  *   NMI_TONE_PERCENTILE  k_lo = N * p_lo / 10000, k_hi = N * p_hi / 10000 (64-bit, floor); lo = the smallest v with c[v] > k_lo,
@@ -482,9 +483,43 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * min(i, M)), enqueued on the context's stream; with h_counts it blocks and returns the tiles' pixel counts n_t.  The argument
  * checks are nmi_tone_lut's (d_luts' tiles_x tiles_y 65,536 bytes may not meet the source's); under any other mode
  * NMI_ERR_UNSUPPORTED, nothing enqueued, d_luts untouched.
- * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, mask-aware statistics, CLAHE of
+ * Valid range.  Deep sensors reserve values for "no measurement": a depth stream writes 0 where it has no return, a 12-bit
+ * sensor in a 16-bit container 65535 for a dead pixel, a thermal core parks saturated pixels at its top code.  A valid range
+ * keeps them out of the statistics and marks them in a mask the masked and covered searches take (nmi_warp_stack_masked's frame
+ * mask).  nmi_set_valid_range (per context, read at call time by nmi_gray_frame, nmi_reduce_frame, nmi_tone_lut,
+ * nmi_tone_tile_luts and nmi_deep_frame) takes 0 <= lo <= hi <= 65535, else NMI_ERR_INVALID_ARGUMENT with the setting left as it
+ * was.  (0, 65535) is off: the setting of every new context, under which every output byte and every kernel launched is what it
+ * was without this setting.  The range is kept, and ignored, under every format other than GRAY16, like the tone map;
+ * nmi_tone_map itself is untouched.
+ *   Validity    a source pixel is valid iff lo <= raw <= hi, raw being the container's value BEFORE it saturates to M: (0, 4095)
+ *               at bits = 12 drops a 65535 sentinel that would otherwise count as 4095.
+ *   Statistics  h[v] counts valid pixels only, and N is their number, in PERCENTILE's k_lo, k_hi and c[v] >= N - k_hi and in
+ *               EQUALIZE's T; CLAHE's h_t and n_t are per tile, over its valid pixels.  nmi_tone_lut's h_window and
+ *               nmi_tone_tile_luts' h_counts report the valid pixels' values and numbers.
+ *   No pixels   a global mode with N == 0: the table is all 0 and the window {0, 0}.  A CLAHE tile with n_t == 0: T_t is SHIFT's
+ *               table, min(i, M) >> (bits - 8) -- a neutral table, so that the valid pixels of neighbouring tiles that blend
+ *               with it are not pulled to black.
+ *   Grey bytes  an invalid pixel still becomes table[min(raw, M)] (under CLAHE: the blend), as before: only the tables change,
+ *               and SHIFT, WINDOW and TABLE give the same grey bytes with and without a range.
+ *   Mask        the validity mask is dense uint8 [H][W] at the search size, 1 or 0: 1 iff all f x f source pixels under (x, y)
+ *               are valid (nmi_reduce_frame's "all of them" rule) and, where a frame mask is given, its byte at (x, y) is
+ *               nonzero.
+ * nmi_reduce_frame's own mask pair keeps its rule and its argument checks; when both mask pointers are given, the source is
+ * GRAY16 and a range is on, d_mask is additionally ANDed with validity.
+ * nmi_deep_frame is the entry for a frame mask at the search size, which nmi_gray_frame cannot take: the GRAY16 source at d_src
+ * (f H rows of pitch bytes, f = factor) under the context's tone map and range -> d_gray, the grey frame nmi_gray_frame /
+ * nmi_reduce_frame give, and d_mask, the validity mask ANDed with d_frame_mask (nullable), both written by one conversion kernel
+ * (range off: every pixel is valid).  Enqueued on the context's stream.  NMI_ERR_INVALID_ARGUMENT, before anything is enqueued
+ * and with the outputs untouched: a NULL ctx, d_src, d_gray or d_mask, a factor outside 1 .. 4, an odd d_src or pitch, pitch < 0
+ * or 0 < pitch < 2 f W, any two of the source's bytes, the frame mask and the two outputs overlapping.
+ * The masked chain on a deep frame is then nmi_deep_frame, nmi_undistort_frame* with d_mask as its raw mask (if distorted),
+ * nmi_warp_stack_masked with the result as its frame mask, nmi_search_grid_masked or nmi_search_grid_covered.  Captured levels
+ * and streams take no valid range: their GRAY16 intake counts every pixel.
+ * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, CLAHE of
  * 8-bit formats, caller-supplied tile tables, more than 8 x 8 tiles, temporal smoothing of the window (TABLE is the hook: smooth
- * on the host, pass the table).
+ * on the host, pass the table), statistics under the caller's own frame mask, validity for the 8-bit formats (saturated 0 /
+ * 255), a valid range in captured levels and streams, hole filling or inpainting, a per-pixel weight instead of a mask,
+ * renormalised CLAHE blends beside an empty tile, the CUDAF shim.
  */
 #define NMI_TONE_SHIFT 0
 #define NMI_TONE_WINDOW 1
@@ -511,6 +546,10 @@ int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 =
                  uint8_t *d_lut /* [65536] */, int32_t h_window[2] /* nullable */);
 int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
                        uint8_t *d_luts /* [tiles_y][tiles_x][65536] */, int32_t *h_counts /* nullable, [tiles_y][tiles_x] */);
+int nmi_set_valid_range(nmi_ctx *ctx, int32_t lo, int32_t hi /* 0 <= lo <= hi <= 65535; (0, 65535) = off */);
+int nmi_deep_frame(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
+                   const uint8_t *d_frame_mask /* nullable, dense [H][W], search size */, uint8_t *d_gray /* [H][W] */,
+                   uint8_t *d_mask /* [H][W] */);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU

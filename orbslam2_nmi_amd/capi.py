@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "nmi_undistort_frame_fisheye", "nmi_level_set_distortion_fisheye", "nmi_stream_set_distortion_fisheye",
     "nmi_tone_map_default", "nmi_set_tone_map", "nmi_level_set_tone_map", "nmi_stream_set_tone_map", "nmi_tone_lut",
     "nmi_tone_tile_luts",
+    "nmi_set_valid_range", "nmi_deep_frame",
 )
 
 
@@ -252,6 +253,9 @@ def load_library(build_if_missing=False):
         lib.nmi_tone_lut.argtypes = [vp, vp, C.c_int64, i32, vp, C.POINTER(i32)]
     if hasattr(lib, "nmi_tone_tile_luts"):
         lib.nmi_tone_tile_luts.argtypes = [vp, vp, C.c_int64, i32, vp, C.POINTER(i32)]
+    if hasattr(lib, "nmi_set_valid_range"):
+        lib.nmi_set_valid_range.argtypes = [vp, i32, i32]
+        lib.nmi_deep_frame.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -704,6 +708,43 @@ class NmiContext:
         apply to a FRAME_GRAY16 source from now on.  Ignored for every other format."""
         self._check(self._lib.nmi_set_tone_map(self._h, _tone_ref(tm)), "nmi_set_tone_map")
         self._tone = tm  # (a TABLE's tensor stays alive)
+
+    def set_valid_range(self, lo=0, hi=65535):
+        """nmi_set_valid_range: a FRAME_GRAY16 pixel is valid iff lo <= raw <= hi.  Invalid pixels stay out of the tone map's
+        statistics (gray_frame, reduce_frame, tone_lut, tone_tile_luts, deep_frame) and are 0 in deep_frame's mask.  (0, 65535):
+        off.  Ignored for every other format."""
+        self._check(self._lib.nmi_set_valid_range(self._h, int(lo), int(hi)), "nmi_set_valid_range")
+
+    def deep_frame(self, src, factor=1, pitch=0, frame_mask=None, out=None, out_mask=None, sync=True):
+        """nmi_deep_frame: the FRAME_GRAY16 frame src (factor * H rows of `pitch` bytes, factor * W pixels each; src as for
+        gray_frame) under the context's tone map and valid range -> (its grey frame [H,W] u8, its validity mask [H,W] u8: 1 where
+        all factor x factor source pixels are valid and frame_mask -- optional device [H,W] uint8 / bool -- is nonzero).  New
+        tensors when out / out_mask are None.  Enqueued on the context's stream."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        f = int(factor)
+        if int(pitch) >= 0 and 1 <= f <= 4:
+            need = (f * self.height - 1) * (int(pitch) or f * self.width * 2) + f * self.width * 2
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        fm = None
+        if frame_mask is not None:
+            fm = _dev_mask(frame_mask, 2, "frame_mask")
+            if tuple(fm.shape) != (self.height, self.width):
+                raise ValueError(f"frame_mask is {tuple(fm.shape)}, the search size is {(self.height, self.width)}")
+        if out is None:
+            out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        if out_mask is None:
+            out_mask = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        o, om = self._img(out, "out"), self._img(out_mask, "out_mask")
+        self._order_after_torch()
+        self._check(self._lib.nmi_deep_frame(self._h, src.data_ptr(), int(pitch), f, fm.data_ptr() if fm is not None else None, o.data_ptr(),
+                                             om.data_ptr()), "nmi_deep_frame")
+        if sync:
+            self.synchronize()
+        return out, out_mask
 
     def tone_lut(self, src, factor=1, pitch=0, out=None, window=True):
         """nmi_tone_lut: the uint8 table [TONE_LEVELS] the context's tone map gives for the FRAME_GRAY16 frame src (factor * H rows

@@ -56,7 +56,7 @@ int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t p
     if (format == NMI_FRAME_GRAY16) {  // through the context's tone map, as it is now
         const nmi::ToneSetting t = ctx->tone;
         NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
-        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, d_src, rb, 1, d_gray, W, H, ctx->stream));
+        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, ctx->valid, d_src, rb, 1, nullptr, d_gray, nullptr, W, H, ctx->stream));
         return NMI_OK;
     }
     NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));

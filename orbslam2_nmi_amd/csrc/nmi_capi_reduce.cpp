@@ -44,7 +44,13 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     if (format == NMI_FRAME_GRAY16) {  // the tone table from the full-size frame, then nmi_tone.hip's conversion at every factor
         const nmi::ToneSetting t = ctx->tone;
         NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
-        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, d_src, rb, factor, d_gray, W, H, ctx->stream));
+        const nmi::ValidRange range = ctx->valid;
+        if (d_mask && range.on()) {  // the mask pair's rule first, then validity ANDed into it by the conversion (in place)
+            NMI_HIP_TRY(ctx, nmi::launch_reduce_mask(d_src_mask, factor, d_mask, W, H, ctx->stream));
+            NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, d_mask, d_gray, d_mask, W, H, ctx->stream));
+            return NMI_OK;
+        }
+        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, nullptr, d_gray, nullptr, W, H, ctx->stream));
     } else if (factor == 1) {  // nmi_gray_frame; the mask is copied as 0 / 1
         NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
     } else {

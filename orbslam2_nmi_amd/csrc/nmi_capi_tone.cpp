@@ -1,6 +1,6 @@
 // nmi_capi_tone.cpp -- the tone map of the deep grey frames (NMI_FRAME_GRAY16, include/nmi_hip.h): nmi_tone_map_default,
-// nmi_set_tone_map, nmi_tone_lut, nmi_tone_tile_luts, and the host side every GRAY16 conversion shares (nmi_tone.h): the check of
-// a setting, the buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and
+// nmi_set_tone_map, nmi_set_valid_range, nmi_tone_lut, nmi_tone_tile_luts, nmi_deep_frame, and the host side every GRAY16
+// conversion shares (nmi_tone.h): the check of a setting, the buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and
 // nmi_stream_set_tone_map are with the other setters in nmi_capi_pipeline.cpp.  Kernels: nmi_tone.hip, and nmi_clahe.hip for the
 // tiled mode.
 #include "nmi_tone.h"
@@ -77,32 +77,46 @@ hipError_t nmi_internal::tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hi
     return e;
 }
 
-hipError_t nmi_internal::launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
-                                     const uint8_t **lut, hipStream_t stream)
+int nmi_internal::valid_range_check(int32_t lo, int32_t hi, nmi::ValidRange *out)
+{
+    if (lo < 0 || lo > hi || hi > 65535) return NMI_ERR_INVALID_ARGUMENT;
+    out->lo = lo, out->hi = hi;
+    return NMI_OK;
+}
+
+hipError_t nmi_internal::launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src,
+                                     int64_t pitch, int width, int height, const uint8_t **lut, hipStream_t stream)
 {
     *lut = t.mode == NMI_TONE_TABLE ? t.d_lut : w.table();
     if (!t.from_frame()) return hipSuccess;
-    const hipError_t e = nmi::launch_tone_hist(src, pitch, width, height, t.bits, w.hist.as<uint32_t>(), stream);
+    const hipError_t e = nmi::launch_tone_hist(src, pitch, width, height, t.bits, range, w.hist.as<uint32_t>(), stream);
     return e != hipSuccess ? e : nmi::launch_tone_table(t, w.hist.as<uint32_t>(), w.table(), w.window(), stream);
 }
 
-hipError_t nmi_internal::launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width,
-                                           int height, hipStream_t stream)
+hipError_t nmi_internal::launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src,
+                                           int64_t pitch, int width, int height, hipStream_t stream)
 {
-    const hipError_t e = nmi::launch_clahe_hist(t, src, pitch, width, height, w.tile_hist.as<uint32_t>(), stream);
+    const hipError_t e = nmi::launch_clahe_hist(t, src, pitch, width, height, range, w.tile_hist.as<uint32_t>(), stream);
     return e != hipSuccess ? e : nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), w.tile_tables(), w.tile_counts(t), stream);
 }
 
-hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray,
-                                   int width, int height, hipStream_t stream)
+hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch,
+                                   int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height,
+                                   hipStream_t stream)
 {
+    const bool masked = mask_out != nullptr;
     if (t.tiled()) {
-        const hipError_t e = launch_clahe_tone(w, t, src, pitch, factor * width, factor * height, stream);
-        return e != hipSuccess ? e : nmi::launch_clahe_gray16(t, src, pitch, factor, w.tile_tables(), gray, width, height, stream);
+        const hipError_t e = launch_clahe_tone(w, t, range, src, pitch, factor * width, factor * height, stream);
+        if (e != hipSuccess) return e;
+        return masked ? nmi::launch_clahe_gray16_masked(t, src, pitch, factor, w.tile_tables(), range, frame_mask, gray, mask_out, width, height,
+                                                        stream)
+                      : nmi::launch_clahe_gray16(t, src, pitch, factor, w.tile_tables(), gray, width, height, stream);
     }
     const uint8_t *lut = nullptr;
-    const hipError_t e = launch_tone(w, t, src, pitch, factor * width, factor * height, &lut, stream);
-    return e != hipSuccess ? e : nmi::launch_gray16(src, pitch, factor, lut, t.bits, gray, width, height, stream);
+    const hipError_t e = launch_tone(w, t, range, src, pitch, factor * width, factor * height, &lut, stream);
+    if (e != hipSuccess) return e;
+    return masked ? nmi::launch_gray16_masked(src, pitch, factor, lut, t.bits, range, frame_mask, gray, mask_out, width, height, stream)
+                  : nmi::launch_gray16(src, pitch, factor, lut, t.bits, gray, width, height, stream);
 }
 
 namespace {
@@ -141,6 +155,12 @@ int nmi_set_tone_map(nmi_ctx *ctx, const nmi_tone_map *tm)
     return tone_check(tm, ctx->params.width, ctx->params.height, &ctx->tone);
 }
 
+int nmi_set_valid_range(nmi_ctx *ctx, int32_t lo, int32_t hi)
+{
+    if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
+    return valid_range_check(lo, hi, &ctx->valid);
+}
+
 int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, uint8_t *d_lut, int32_t h_window[2])
 {
     int64_t rb = 0;
@@ -152,7 +172,7 @@ int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t fact
     DeviceGuard guard(ctx->device);
     ToneWork &w = ctx->tone_work;
     NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
-    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, fW, fH, t.bits, w.hist.as<uint32_t>(), ctx->stream));
+    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, fW, fH, t.bits, ctx->valid, w.hist.as<uint32_t>(), ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_tone_table(t, w.hist.as<uint32_t>(), d_lut, w.window(), ctx->stream));
     if (h_window) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(h_window, w.window(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -173,14 +193,42 @@ int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_
     DeviceGuard guard(ctx->device);
     ToneWork &w = ctx->tone_work;
     NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
-    NMI_HIP_TRY(ctx, nmi::launch_clahe_hist(t, d_src, rb, factor * ctx->params.width, factor * ctx->params.height, w.tile_hist.as<uint32_t>(),
-                                            ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_clahe_hist(t, d_src, rb, factor * ctx->params.width, factor * ctx->params.height, ctx->valid,
+                                            w.tile_hist.as<uint32_t>(), ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), d_luts, w.tile_counts(t), ctx->stream));
     if (h_counts) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, w.tile_counts(t), (size_t)t.tiles_x * t.tiles_y * sizeof(int32_t), hipMemcpyDeviceToHost,
                                         ctx->stream));
         NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return NMI_OK;
+}
+
+int nmi_deep_frame(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, const uint8_t *d_frame_mask, uint8_t *d_gray,
+                   uint8_t *d_mask)
+{
+    if (!ctx || !d_src || !d_gray || !d_mask || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    const int W = ctx->params.width, H = ctx->params.height;
+    const int64_t fW = (int64_t)factor * W, fH = (int64_t)factor * H;
+    int64_t rb = 0;
+    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
+        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
+        return NMI_ERR_INVALID_ARGUMENT;
+    // the source's bytes run from d_src to the end of its last row's pixels; the frame mask and the two outputs are dense [H][W];
+    // no two of the four may meet (a NULL frame mask meets nothing)
+    const uintptr_t npix = (uintptr_t)ctx->npix;
+    const uintptr_t lo[4] = {(uintptr_t)d_src, (uintptr_t)d_frame_mask, (uintptr_t)d_gray, (uintptr_t)d_mask};
+    const uintptr_t hi[4] = {lo[0] + (uintptr_t)((fH - 1) * rb + fW * 2), d_frame_mask ? lo[1] + npix : lo[1], lo[2] + npix, lo[3] + npix};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (lo[a] < hi[a] && lo[b] < hi[b] && lo[a] < hi[b] && lo[b] < hi[a]) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    const nmi::ToneSetting t = ctx->tone;
+    const nmi::ValidRange range = ctx->valid;
+    NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
+    // (range off: every pixel is valid, and the masked conversion writes the frame mask as 0 / 1, all 1 without one)
+    NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, d_frame_mask, d_gray, d_mask, W, H, ctx->stream));
     return NMI_OK;
 }
 

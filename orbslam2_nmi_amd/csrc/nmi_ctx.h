@@ -130,6 +130,7 @@ struct nmi_ctx {
     // (nmi_set_tone_map), and its histogram and table.
     nmi::ToneSetting tone;
     nmi_internal::ToneWork tone_work;
+    nmi::ValidRange valid;                // nmi_set_valid_range: which raw values count in those statistics and in validity masks
     nmi_mem::Event ev_start, ev_stop;
     int hist_variant = 3;
     int phase_mask = 3;

@@ -36,13 +36,26 @@ struct ToneSetting {
     }
 };
 
+// The valid range of a GRAY16 source (nmi_set_valid_range): a pixel counts in the statistics, and is 1 in the validity mask,
+// iff lo <= raw <= hi, raw being the container's value before it saturates to 2^bits - 1.  (0, 65535): off, and every launch below
+// that takes a range is then the one without.
+struct ValidRange {
+    int32_t lo = 0, hi = 65535;
+    bool on() const { return lo != 0 || hi != 65535; }
+    bool operator==(const ValidRange &o) const { return lo == o.lo && hi == o.hi; }
+};
+
 // hist[v] += the number of pixels with min(raw, 2^bits - 1) == v among the height rows of pitch bytes at src, each width
 // little-endian 16-bit pixels (src and pitch even).  Exact for any content; hist is uint32 [kToneLevels].
 hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, uint32_t *hist, hipStream_t stream);
+// ... counting the pixels inside `range` only (a kernel of its own; range off: the launch above).
+hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, const ValidRange &range, uint32_t *hist,
+                            hipStream_t stream);
 
 // lut[i] = the setting's 8-bit value of min(i, 2^bits - 1) for all kToneLevels indices, and window[0 .. 1] = the {lo, hi} pair
 // nmi_tone_lut reports (window may be null).  hist: for a from_frame() mode the frame's histogram at the head of a buffer of
-// kToneHistWords words, left all zero for the next frame (two kernels); never read otherwise (one kernel).
+// kToneHistWords words, left all zero for the next frame (two kernels); never read otherwise (one kernel).  N is the histogram's
+// sum; N == 0 (a ranged histogram of a frame with no valid pixel): the table all 0, the window {0, 0}.
 hipError_t launch_tone_table(const ToneSetting &t, uint32_t *hist, uint8_t *lut, int32_t *window, hipStream_t stream);
 
 // nmi_gray_frame (factor 1) and nmi_reduce_frame (factor 2 .. 4) of a GRAY16 source of factor * height rows of pitch bytes,
@@ -50,6 +63,10 @@ hipError_t launch_tone_table(const ToneSetting &t, uint32_t *hist, uint8_t *lut,
 // lut is the table of launch_tone_table, or a TABLE setting's own.
 hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, uint8_t *gray, int width, int height,
                          hipStream_t stream);
+// ... and, from the same kernel (one of its own), the validity mask: mask[y][x] = 1 iff all factor x factor source pixels under
+// (x, y) are inside `range` and frame_mask[y][x] != 0 (frame_mask: dense [height][width], may be null, may be `mask` itself).
+hipError_t launch_gray16_masked(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
+                                const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream);
 
 // --- CLAHE (nmi_clahe.hip; the rule: include/nmi_hip.h "Deep frames") ---------------------------------------------------------
 constexpr int kClaheMaxTiles = 8;                                  // per axis
@@ -62,19 +79,29 @@ inline size_t clahe_luts_bytes(const ToneSetting &t) { return (size_t)t.tiles_x 
 // hist[tile][v] += the number of pixels with min(raw, 2^bits - 1) == v in each tile of the tiles_x x tiles_y grid over the
 // width x height source (rows of pitch bytes; src and pitch even; tiles_x <= width, tiles_y <= height).  Exact for any content.
 hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, uint32_t *hist, hipStream_t stream);
+// ... counting the pixels inside `range` only (a kernel of its own; range off: the launch above).
+hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, const ValidRange &range,
+                             uint32_t *hist, hipStream_t stream);
 
-// luts[tile][i] = the tile's 8-bit value of min(i, 2^bits - 1) for all kToneLevels indices, counts[tile] = its pixels; hist is
-// left all zero for the next frame.
+// luts[tile][i] = the tile's 8-bit value of min(i, 2^bits - 1) for all kToneLevels indices, counts[tile] = its pixels (the
+// histogram's sum; 0, a tile with no valid pixel: SHIFT's table); hist is left all zero for the next frame.
 hipError_t launch_clahe_tables(const ToneSetting &t, uint32_t *hist, uint8_t *luts, uint32_t *counts, hipStream_t stream);
 
 // launch_gray16 under CLAHE: the blend of the four nearest tiles' tables per source pixel of the factor * width x factor * height
 // source, then the rounded box average.
 hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, uint8_t *gray,
                                int width, int height, hipStream_t stream);
+// ... and the validity mask, as launch_gray16_masked.
+hipError_t launch_clahe_gray16_masked(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts,
+                                      const ValidRange &range, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height,
+                                      hipStream_t stream);
 
 }  // namespace nmi
 
 namespace nmi_internal {
+
+// 0 <= lo <= hi <= 65535 -> NMI_OK and *out; else NMI_ERR_INVALID_ARGUMENT, *out untouched.
+int valid_range_check(int32_t lo, int32_t hi, nmi::ValidRange *out);
 
 // *tm well formed for a context of width x height (include/nmi_hip.h; null: the default) -> NMI_OK and *out; else
 // NMI_ERR_INVALID_ARGUMENT, *out untouched.
@@ -102,18 +129,26 @@ hipError_t tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stre
 
 // The nodes in front of a GRAY16 conversion of the f W x f H source through one table: the histogram and the table for
 // PERCENTILE and EQUALIZE, nothing otherwise.  Returns through *lut the table the conversion reads.  *w was prepared for t,
-// which is not CLAHE.
-hipError_t launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
-                       const uint8_t **lut, hipStream_t stream);
+// which is not CLAHE.  The histogram counts the pixels inside `range`.
+hipError_t launch_tone(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch,
+                       int width, int height, const uint8_t **lut, hipStream_t stream);
 
 
 // The CLAHE nodes in front of a conversion: the tile histograms of the width x height source, then the tile tables.
-hipError_t launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height,
-                             hipStream_t stream);
+hipError_t launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch,
+                             int width, int height, hipStream_t stream);
 
 // Every node of a GRAY16 conversion (nmi_gray_frame at factor 1, nmi_reduce_frame's, the intake's): the factor * width x factor *
 // height source to the dense grey [height][width] under t -- launch_tone and launch_gray16, or CLAHE's three.  *w was prepared for t.
-hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray, int width,
-                     int height, hipStream_t stream);
+// The statistics are those of the pixels inside `range`.  mask_out (may be null): the conversion is the masked one and writes the
+// validity mask, ANDed with frame_mask (dense [height][width], may be null, may be mask_out itself).
+hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch, int factor,
+                     const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height, hipStream_t stream);
+// ... with the range off and no mask: the intake of levels and streams (nmi_capi_intake.cpp), which take no valid range.
+inline hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray, int width,
+                            int height, hipStream_t stream)
+{
+    return deep_gray(w, t, nmi::ValidRange{}, src, pitch, factor, nullptr, gray, nullptr, width, height, stream);
+}
 
 }  // namespace nmi_internal

@@ -6,6 +6,10 @@
 //   nmi_gray16_kernel       table[min(raw, M)] per source pixel, then the rounded F x F box average (F = 1: the value itself)
 // All arithmetic is integer (the one fp64 quotient is corrected to the exact floor), so tests/helpers/tone_np.py equals it bit
 // for bit.
+// With a valid range (nmi_set_valid_range) the histogram and the conversion are kernels of their own, compiled from this file's
+// kernel text once more (nmi_tone_valid.hip defines NMI_TONE_VALID and includes this file, as the nmi_kernels_* wrappers include
+// nmi_kernels.hip): nmi_tone_hist_ranged_kernel counts the pixels with lo <= raw <= hi only, nmi_gray16_masked_kernel also writes
+// the validity mask.  The kernels of this unit are what they were before the range existed, instruction for instruction.
 //
 // The histogram counts in a per-workgroup uint32 LDS histogram of 16384 bins (64 KiB; a count cannot wrap, a frame has fewer
 // than 2^32 pixels) and adds its nonzero bins to the global one.  LDS atomics on one address cost a wave some 64 LDS cycles,
@@ -20,6 +24,14 @@
 #include "nmi_tone.h"
 #include "nmi_tone_device.h"
 #include "nmi_reduce_device.h"
+
+#ifdef NMI_TONE_VALID
+#define NMI_TONE_HIST_KERNEL nmi_tone_hist_ranged_kernel
+#define NMI_GRAY16_KERNEL nmi_gray16_masked_kernel
+#else
+#define NMI_TONE_HIST_KERNEL nmi_tone_hist_kernel
+#define NMI_GRAY16_KERNEL nmi_gray16_kernel
+#endif
 
 namespace nmi {
 
@@ -49,8 +61,14 @@ __device__ __forceinline__ uint32_t tone_window(uint32_t v, uint32_t lo, uint32_
 // lane loads its two runs once and keeps them in registers over the passes.  vec: every row starts on a 16-byte boundary (base
 // and pitch), so a whole run comes in one load; otherwise, and for the last run of a row whose width is not a multiple of 8,
 // 2-byte loads of just the pixels inside the frame.  The flush clears the bins it adds to the global histogram.
-__global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8_t *__restrict__ src, size_t pitch, int width, int height,
-                                                                     uint32_t vmax, int passes, int vec, uint32_t *__restrict__ hist)
+// NMI_TONE_VALID: a pixel is counted (and seen, for the quarters) iff it is inside the frame and lo <= raw <= hi, tested on the
+// raw half-word before the saturation: bit k of ok[r].
+__global__ __launch_bounds__(kHistThreads) void NMI_TONE_HIST_KERNEL(const uint8_t *__restrict__ src, size_t pitch, int width, int height,
+                                                                     uint32_t vmax, int passes, int vec,
+#ifdef NMI_TONE_VALID
+                                                                     uint32_t lo, uint32_t hi,
+#endif
+                                                                     uint32_t *__restrict__ hist)
 {
     __shared__ uint4 bins4[kHistBins / 4];
     __shared__ uint32_t quarters;  // bit q: a pixel of this chunk has v >> 14 == q
@@ -64,6 +82,9 @@ __global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8
         uint32_t w[kHistRunsPerLane][kHistRun / 2];  // pixel k of run r is half k % 2 of word k / 2
         int n[kHistRunsPerLane];
         uint32_t seen = 0;
+#ifdef NMI_TONE_VALID
+        uint32_t ok[kHistRunsPerLane] = {};
+#endif
 #pragma unroll
         for (int r = 0; r < kHistRunsPerLane; ++r) {
             const uint32_t item = first + (blockIdx.x * kHistRunsPerLane + r) * kHistThreads + tid;
@@ -88,9 +109,16 @@ __global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8
         for (int r = 0; r < kHistRunsPerLane; ++r) {
 #pragma unroll
             for (int k = 0; k < kHistRun; ++k) {  // saturate in place
+#ifdef NMI_TONE_VALID
+                const uint32_t raw = (w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu;
+                const uint32_t v = min(raw, vmax);
+                w[r][k / 2] = (w[r][k / 2] & ~(0xFFFFu << (16 * (k % 2)))) | (v << (16 * (k % 2)));
+                if (k < n[r] && raw >= lo && raw <= hi) ok[r] |= 1u << k, seen |= 1u << (v >> 14);
+#else
                 const uint32_t v = min((w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu, vmax);
                 w[r][k / 2] = (w[r][k / 2] & ~(0xFFFFu << (16 * (k % 2)))) | (v << (16 * (k % 2)));
                 if (k < n[r]) seen |= 1u << (v >> 14);
+#endif
             }
         }
         uint32_t present = 1u;
@@ -110,7 +138,11 @@ __global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8
 #pragma unroll
                 for (int k = 0; k < kHistRun; ++k) {
                     const uint32_t v = (w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu;
+#ifdef NMI_TONE_VALID
+                    if (((ok[r] >> k) & 1u) && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
+#else
                     if (k < n[r] && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
+#endif
                 }
             }
             __syncthreads();
@@ -132,6 +164,7 @@ __global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8
     }
 }
 
+#ifndef NMI_TONE_VALID
 // The histogram's way to the table, in two kernels of 64 workgroups x 256 lanes; workgroup p has the segment of 1024 levels
 // [1024 p, 1024 p + 1024), lane t four of them.  (One workgroup doing all of it takes 25 .. 43 us: a single CU's loads of the
 // 256 KiB the atomics left in memory, profiles/deep/README.md.)
@@ -198,7 +231,8 @@ __device__ __forceinline__ uint32_t segment_below(const uint4 q, uint32_t clip, 
 // frame's total, first and last occupied level from them; PERCENTILE finds the segments in which the running sum crosses its
 // two ranks and scans those for the levels (every workgroup for itself: 4 KiB each); EQUALIZE scans its own segment for the
 // running sum at each of its levels.  Levels above M hold no pixel, so their running sum -- and entry -- is M's, which is the
-// rule for an index i > M (v = min(i, M)).
+// rule for an index i > M (v = min(i, M)).  A histogram that counted nothing (N == 0: a valid range no pixel of the frame is in)
+// gives the table all 0 and the pair {0, 0}.
 __global__ __launch_bounds__(kSegThreads) void nmi_tone_table_kernel(ToneSetting t, const uint32_t *__restrict__ copy,
                                                                      const uint32_t *__restrict__ records, uint8_t *__restrict__ lut,
                                                                      int32_t *__restrict__ window)
@@ -265,6 +299,8 @@ __global__ __launch_bounds__(kSegThreads) void nmi_tone_table_kernel(ToneSetting
     } else if (t.mode == NMI_TONE_WINDOW) {
         lo = (uint32_t)t.lo, hi = (uint32_t)t.hi;
     }
+    const bool nothing = copy && total == 0u;
+    if (nothing) lo = 0u, hi = 0u;
     const uint32_t den = total - c0;  // EQUALIZE: T - c0
     const double inv_den = den ? 1.0 / (double)den : 0.0;
     const uint32_t h[4] = {own.x, own.y, own.z, own.w};
@@ -284,6 +320,7 @@ __global__ __launch_bounds__(kSegThreads) void nmi_tone_table_kernel(ToneSetting
             break;
         default: out = t.d_lut[v]; break;  // TABLE
         }
+        if (nothing) out = 0u;
         word |= out << (8 * k);
     }
     if (((uintptr_t)lut % 4) == 0) {
@@ -294,15 +331,23 @@ __global__ __launch_bounds__(kSegThreads) void nmi_tone_table_kernel(ToneSetting
     }
     if (p == 0 && tid == 0 && window) window[0] = (int32_t)lo, window[1] = (int32_t)hi;
 }
+#endif  // !NMI_TONE_VALID
 
 // A lane makes 4 adjacent grey pixels of one output row from 4 F pixels of each of its F source rows.  vec_in: every source
 // row starts on an 8-byte boundary (base and pitch), so a row's 8 F bytes come in F 8-byte loads; otherwise, and for the last
 // quad of a row whose width is not a multiple of 4, 2-byte loads of just the pixels inside the frame.  vec_out: width % 4 == 0
 // and gray 4-byte aligned, one dword store; otherwise byte stores.
+// NMI_TONE_VALID: the lane also writes the quad of the validity mask, from the raw values it holds: mask pixel k is 1 iff each of
+// its F x F source pixels has lo <= raw <= hi and, with a frame mask, frame_mask's byte there is nonzero (write_valid_quad; the
+// two may be one buffer).  vec_out then also asks for 4-byte aligned masks.
 template <int F>
-__global__ __launch_bounds__(256) void nmi_gray16_kernel(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ lut,
+__global__ __launch_bounds__(256) void NMI_GRAY16_KERNEL(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ lut,
                                                          uint32_t vmax, uint8_t *__restrict__ gray, int width, int height, int vec_in,
+#ifdef NMI_TONE_VALID
+                                                         int vec_out, uint32_t lo, uint32_t hi, const uint8_t *frame_mask, uint8_t *mask)
+#else
                                                          int vec_out)
+#endif
 {
     const int x0 = (blockIdx.x * 64 + (int)threadIdx.x) * 4;
     const int y = blockIdx.y * 4 + (int)threadIdx.y;
@@ -310,13 +355,24 @@ __global__ __launch_bounds__(256) void nmi_gray16_kernel(const uint8_t *__restri
     const int n = min(4, width - x0);
     const uint8_t *row = src + (size_t)y * F * pitch + (size_t)x0 * (F * 2);
     uint32_t s[4] = {};
+#ifdef NMI_TONE_VALID
+    uint32_t bad = 0;  // bit k: a source pixel of output pixel k is outside the range
+#endif
     if (vec_in && n == 4) {
 #pragma unroll
         for (int r = 0; r < F; ++r) {
             uint32_t w[2 * F];  // source pixel i of the row is half i % 2 of word i / 2
             __builtin_memcpy(w, __builtin_assume_aligned(row + (size_t)r * pitch, 8), 8 * F);
 #pragma unroll
+#ifdef NMI_TONE_VALID
+            for (int i = 0; i < 4 * F; ++i) {
+                const uint32_t raw = (w[i / 2] >> (16 * (i % 2))) & 0xFFFFu;
+                s[i / F] += lut[min(raw, vmax)];
+                bad |= (uint32_t)(raw < lo || raw > hi) << (i / F);
+            }
+#else
             for (int i = 0; i < 4 * F; ++i) s[i / F] += lut[min((w[i / 2] >> (16 * (i % 2))) & 0xFFFFu, vmax)];
+#endif
         }
     } else {
 #pragma unroll
@@ -326,7 +382,15 @@ __global__ __launch_bounds__(256) void nmi_gray16_kernel(const uint8_t *__restri
                 for (int r = 0; r < F; ++r) {
                     const uint16_t *p16 = reinterpret_cast<const uint16_t *>(row + (size_t)r * pitch) + k * F;
 #pragma unroll
+#ifdef NMI_TONE_VALID
+                    for (int j = 0; j < F; ++j) {
+                        const uint32_t raw = p16[j];
+                        s[k] += lut[min(raw, vmax)];
+                        bad |= (uint32_t)(raw < lo || raw > hi) << k;
+                    }
+#else
                     for (int j = 0; j < F; ++j) s[k] += lut[min((uint32_t)p16[j], vmax)];
+#endif
                 }
             }
         }
@@ -340,8 +404,12 @@ __global__ __launch_bounds__(256) void nmi_gray16_kernel(const uint8_t *__restri
     } else {
         for (int k = 0; k < n; ++k) gray[o + k] = (uint8_t)(packed >> (8 * k));
     }
+#ifdef NMI_TONE_VALID
+    write_valid_quad(bad, frame_mask, mask, o, n, vec_out);
+#endif
 }
 
+#ifndef NMI_TONE_VALID
 hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, uint32_t *hist, hipStream_t stream)
 {
     const long long items = (long long)((width + kHistRun - 1) / kHistRun) * height, per = kHistThreads * kHistRunsPerLane;
@@ -393,5 +461,53 @@ hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const ui
     }
     return hipGetLastError();
 }
+
+#else  // NMI_TONE_VALID
+
+hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, const ValidRange &range, uint32_t *hist,
+                            hipStream_t stream)
+{
+    if (!range.on()) return launch_tone_hist(src, pitch, width, height, bits, hist, stream);
+    const long long items = (long long)((width + kHistRun - 1) / kHistRun) * height, per = kHistThreads * kHistRunsPerLane;
+    const long long want = (items + per - 1) / per;  // (launch_tone_hist's grid)
+    const int workgroups = (int)(want < 1 ? 1 : want > kHistMaxWorkgroups ? kHistMaxWorkgroups : want);
+    const int passes = bits <= 14 ? 1 : bits == 15 ? 2 : 4;
+    const int vec = ((uintptr_t)src % 16) == 0 && (pitch % 16) == 0;
+    hipLaunchKernelGGL(nmi_tone_hist_ranged_kernel, dim3(workgroups), dim3(kHistThreads), 0, stream, src, (size_t)pitch, width, height,
+                       (1u << bits) - 1u, passes, vec, (uint32_t)range.lo, (uint32_t)range.hi, hist);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <int F>
+void gray16_masked_launch(const uint8_t *src, size_t pitch, const uint8_t *lut, uint32_t vmax, const ValidRange &range, const uint8_t *frame_mask,
+                          uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
+{
+    const int quads = (width + 3) / 4;
+    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
+    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
+    const int vec_out = (width % 4) == 0 && (((uintptr_t)gray | (uintptr_t)mask | (uintptr_t)frame_mask) % 4) == 0;
+    hipLaunchKernelGGL(nmi_gray16_masked_kernel<F>, grid, block, 0, stream, src, pitch, lut, vmax, gray, width, height, vec_in, vec_out,
+                       (uint32_t)range.lo, (uint32_t)range.hi, frame_mask, mask);
+}
+
+}  // namespace
+
+hipError_t launch_gray16_masked(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
+                                const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
+{
+    const uint32_t vmax = (1u << bits) - 1u;
+    switch (factor) {
+    case 1: gray16_masked_launch<1>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
+    case 2: gray16_masked_launch<2>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
+    case 3: gray16_masked_launch<3>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
+    case 4: gray16_masked_launch<4>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+#endif  // NMI_TONE_VALID
 
 }  // namespace nmi

@@ -1,6 +1,6 @@
 """Summary of a rocprofv3 --kernel-trace --output-format csv run of tools/clahe_time.py (its *_kernel_trace.csv) -> JSON on stdout.
 The tool's phases run one after the other, CALLS conversions each, and a conversion ends with its conversion kernel
-(nmi_gray16_kernel<F> or nmi_clahe_gray16_kernel<F>), so the dispatches are cut into phases after every CALLS-th such dispatch;
+(nmi_gray16_kernel<F> or nmi_clahe_gray16_kernel<F>, or their _masked forms: tools/valid_time.py), so the dispatches are cut into phases after every CALLS-th such dispatch;
 per phase, the median duration of every nmi_* kernel that ran at least once per two calls, and their sum.  PHASES names them,
 comma-separated, in the tool's order (its "phase_names").
 Usage: python tools/summarize_clahe_trace.py TRACE.csv CALLS [PHASES]"""
@@ -31,7 +31,7 @@ def main():
         if not k.startswith("nmi_"):
             continue
         cur[k].append((t1 - t0) / 1e3)
-        if re.fullmatch(r"nmi_(clahe_)?gray16_kernel<\d>", k):
+        if re.fullmatch(r"nmi_(clahe_)?gray16(_masked)?_kernel<\d>", k):
             done += 1
             if done == calls:
                 phases.append(cur)
