@@ -371,8 +371,8 @@ int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_
  *     RGGB one column in is GRBG, one row down GBRG, both BGGR.  Parity with OpenCV's demosaicing is unpinned.
  *   NV12 / NV21 / I420 (hardware video decoders) need no id: their luma plane is H rows of pitch bytes, which is NMI_FRAME_GRAY
  *     with that pitch.  A stream then copies only the H luma rows of the host buffer, never the chroma plane behind them.
- * Not covered: 10 / 12 / 16-bit mosaics (deep grey frames are NMI_FRAME_GRAY16, below), edge-aware demosaicing, chroma of any
- * kind, planar 4:2:2 / 4:4:4.
+ * Not covered: packed 10 / 12-bit mosaics (16-bit mosaics are NMI_FRAME_BAYER16_*, deep grey frames NMI_FRAME_GRAY16 and its
+ * packed forms, all below), edge-aware demosaicing, chroma of any kind, planar 4:2:2 / 4:4:4.
  */
 #define NMI_FRAME_GRAY 0
 #define NMI_FRAME_BGR 1
@@ -386,6 +386,16 @@ int nmi_undistort_frame_fisheye(nmi_ctx *ctx, const double K[9], const double K_
 #define NMI_FRAME_BAYER_GBRG 34
 #define NMI_FRAME_BAYER_BGGR 35
 #define NMI_FRAME_GRAY16 48      /* 2 bytes per pixel, little-endian unsigned, H rows of pitch bytes; dense pitch 2 W */
+/* Deep raw formats ("Deep frames" below: each unpacks to the GRAY16 container; 51 stays unknown) */
+#define NMI_FRAME_GRAY16_BE 50   /* 2 bytes per pixel, big-endian unsigned */
+#define NMI_FRAME_MONO10P 52     /* PFNC Mono10p: 4 pixels in 5 bytes, lsb-packed */
+#define NMI_FRAME_MONO12P 53     /* PFNC Mono12p: 2 pixels in 3 bytes, lsb-packed */
+#define NMI_FRAME_RAW10 54       /* CSI-2 RAW10 / V4L2 Y10P: 4 pixels in 5 bytes, the low bits in the fifth */
+#define NMI_FRAME_RAW12 55       /* CSI-2 RAW12 / V4L2 Y12P: 2 pixels in 3 bytes, the low bits in the third */
+#define NMI_FRAME_BAYER16_RGGB 56 /* 2 bytes per site, little-endian; named as the 8-bit mosaics */
+#define NMI_FRAME_BAYER16_GRBG 57
+#define NMI_FRAME_BAYER16_GBRG 58
+#define NMI_FRAME_BAYER16_BGGR 59
 int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, uint8_t *d_gray /* [H][W] */);
 
 /*
@@ -515,7 +525,43 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * The masked chain on a deep frame is then nmi_deep_frame, nmi_undistort_frame* with d_mask as its raw mask (if distorted),
  * nmi_warp_stack_masked with the result as its frame mask, nmi_search_grid_masked or nmi_search_grid_covered.  Captured levels
  * and streams take no valid range: their GRAY16 intake counts every pixel.
- * Not covered: deep Bayer mosaics, packed Mono10p / Mono12p / MIPI RAW, big-endian containers, CLAHE of
+ * Deep raw formats (new).  What deep sensors put on the wire is rarely the container: GigE / USB3 Vision cameras pack Mono10p /
+ * Mono12p, CSI-2 sensors MIPI RAW10 / RAW12 (V4L2 Y10P / Y12P), colour machine-vision cameras send a Bayer mosaic in 16-bit
+ * words, PGM files and some thermal cores are big-endian.  Nine formats, taken wherever NMI_FRAME_GRAY16 is (nmi_gray_frame,
+ * nmi_reduce_frame, the levels' and streams' frame setters), each UNPACK to a container pixel u(x, y), right-justified, whose
+ * depth the tone map's bits states.  With b the bytes of a row (row y starts at d_src + y * pitch):
+ *   NMI_FRAME_GRAY16_BE   2 bytes per pixel: u(x) = b[2x] << 8 | b[2x+1]
+ *   NMI_FRAME_MONO10P     PFNC lsb-packed, 4 pixels in 5 bytes: pixel k of the row is bits [10k, 10k + 10) of the row read as one
+ *                         little-endian bit string (bit j of the string is bit j % 8 of b[j / 8])
+ *   NMI_FRAME_MONO12P     PFNC lsb-packed, 2 pixels in 3 bytes: pixel k is bits [12k, 12k + 12) of that string
+ *   NMI_FRAME_RAW10       CSI-2 / Y10P, 4 pixels in 5 bytes: u(4g + i) = b[5g + i] << 2 | ((b[5g + 4] >> 2i) & 3), i = 0 .. 3
+ *   NMI_FRAME_RAW12       CSI-2 / Y12P, 2 pixels in 3 bytes: u(2g) = b[3g] << 4 | (b[3g + 2] & 15), u(2g + 1) = b[3g + 1] << 4 |
+ *                         (b[3g + 2] >> 4)
+ *   NMI_FRAME_BAYER16_RGGB / _GRBG / _GBRG / _BGGR   2 bytes per site, little-endian: u = (4899 R4 + 9617 G4 + 1868 B4 + 32768)
+ *                         >> 16, with R4, G4, B4 the 8-bit mosaics' bilinear sums (nmi_gray_frame) over the raw 16-bit sites, the
+ *                         same reflected edges and the same pattern naming.  A site is not saturated to M first (u is, like any
+ *                         container pixel, afterwards); the sum stays below 2^32, and a flat mosaic of g gives g.
+ * A call on one of them is, byte for byte, the unpacking into a dense container followed by the same call on NMI_FRAME_GRAY16:
+ * tone map, statistics, CLAHE tiles and blends, reduction and valid range are all taken on u (for a mosaic: on the demosaiced
+ * grey value).  That is also how it runs: one unpack kernel writes the container (2 f W f H bytes of device memory, kept by
+ * the context, level or stream beside its tone tables), and the GRAY16 kernels read it.  GRAY16 itself and the 8-bit formats
+ * launch what they always did.
+ * Rows: every row starts on a byte; pitch = 0 means dense, Ws 10 / 8, Ws 12 / 8 or 2 Ws bytes for a source row of Ws = f W
+ * pixels (nmi_frame_row_bytes).  Whole groups only: Ws % 4 == 0 for the 10-bit formats, Ws % 2 == 0 for the 12-bit ones, else
+ * NMI_ERR_INVALID_ARGUMENT.  A packed row and its base may sit at any byte address, and a packed pitch may be odd; the 2-byte
+ * formats keep GRAY16's rules (even base, even pitch), BAYER16 the mosaics' Ws, Hs >= 2.  The pitch, overlap and frame-size
+ * checks are the other formats' with the row's true byte count in place of W * bytes per pixel; nothing past a row's last byte
+ * is read.  A stream copies f H rows of the packed row bytes: 1.25 or 1.5 bytes per pixel on the wire instead of 2.
+ * nmi_frame_row_bytes: the dense bytes of a row of `width` pixels in any NMI_FRAME_* format; 0 for an unknown format or a width
+ * that is not whole groups.  Host only, no context.
+ * nmi_unpack_frame writes the container itself: f H rows of pitch bytes at d_src in `format` -> d_gray16, dense uint16 [f H][f W]
+ * (H and W the context's).  Enqueued on the context's stream.  nmi_tone_lut, nmi_tone_tile_luts and nmi_deep_frame take no
+ * format: a caller with a packed, mosaic or big-endian source feeds them nmi_unpack_frame's output as GRAY16 with pitch 0.
+ * NMI_ERR_INVALID_ARGUMENT before anything is enqueued, d_gray16 untouched: a NULL pointer, a factor outside 1 .. 4, the pitch,
+ * alignment, group and overlap rules above (d_gray16's 2 f W f H bytes may not meet the source's; d_gray16 is 2-byte aligned),
+ * any format other than these nine (GRAY16 included: it is its own container).
+ * Not covered: GigE Vision Mono12Packed (the GVSP layout, not Mono12p), MSB-justified containers, RAW14, packed Bayer (10 / 12-bit
+ * mosaics in 5 / 3-byte groups), rows that do not start on a byte, CLAHE of
  * 8-bit formats, caller-supplied tile tables, more than 8 x 8 tiles, temporal smoothing of the window (TABLE is the hook: smooth
  * on the host, pass the table), statistics under the caller's own frame mask, validity for the 8-bit formats (saturated 0 /
  * 255), a valid range in captured levels and streams, hole filling or inpainting, a per-pixel weight instead of a mask,
@@ -550,6 +596,9 @@ int nmi_set_valid_range(nmi_ctx *ctx, int32_t lo, int32_t hi /* 0 <= lo <= hi <=
 int nmi_deep_frame(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
                    const uint8_t *d_frame_mask /* nullable, dense [H][W], search size */, uint8_t *d_gray /* [H][W] */,
                    uint8_t *d_mask /* [H][W] */);
+int64_t nmi_frame_row_bytes(int32_t format, int32_t width);
+int nmi_unpack_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch /* bytes, 0 = dense */, int32_t factor /* 1..4 */,
+                     uint16_t *d_gray16 /* [f*H][f*W] */);
 
 /*
  * Render-stack producer for coloured point clouds: replaces Rendering<4>::renderToTextureOnGPU

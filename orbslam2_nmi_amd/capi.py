@@ -35,8 +35,38 @@ FRAME_BAYER_GBRG = 34
 FRAME_BAYER_BGGR = 35
 # Deep grey frames: 2 bytes per pixel, little-endian unsigned, made 8-bit by a tone map (ToneMap, TONE_*).
 FRAME_GRAY16 = 48
+# Deep raw formats, each unpacked on the device to the GRAY16 container: big-endian words, PFNC Mono10p / Mono12p (lsb-packed), CSI-2
+# RAW10 / RAW12 (V4L2 Y10P / Y12P) and 16-bit Bayer mosaics (2 bytes per site, little-endian).
+FRAME_GRAY16_BE = 50
+FRAME_MONO10P = 52
+FRAME_MONO12P = 53
+FRAME_RAW10 = 54
+FRAME_RAW12 = 55
+FRAME_BAYER16_RGGB = 56
+FRAME_BAYER16_GRBG = 57
+FRAME_BAYER16_GBRG = 58
+FRAME_BAYER16_BGGR = 59
+FRAME_UNPACKED = (FRAME_GRAY16_BE, FRAME_MONO10P, FRAME_MONO12P, FRAME_RAW10, FRAME_RAW12, FRAME_BAYER16_RGGB, FRAME_BAYER16_GRBG,
+                  FRAME_BAYER16_GBRG, FRAME_BAYER16_BGGR)
+# (the byte-packed formats have no whole number of bytes per pixel: frame_row_bytes)
 FRAME_BYTES_PER_PIXEL = {FRAME_GRAY: 1, FRAME_BGR: 3, FRAME_RGB: 3, FRAME_BGRA: 4, FRAME_RGBA: 4, FRAME_YUYV: 2, FRAME_UYVY: 2,
-                         FRAME_BAYER_RGGB: 1, FRAME_BAYER_GRBG: 1, FRAME_BAYER_GBRG: 1, FRAME_BAYER_BGGR: 1, FRAME_GRAY16: 2}
+                         FRAME_BAYER_RGGB: 1, FRAME_BAYER_GRBG: 1, FRAME_BAYER_GBRG: 1, FRAME_BAYER_BGGR: 1, FRAME_GRAY16: 2,
+                         FRAME_GRAY16_BE: 2, FRAME_BAYER16_RGGB: 2, FRAME_BAYER16_GRBG: 2, FRAME_BAYER16_GBRG: 2, FRAME_BAYER16_BGGR: 2}
+
+
+def frame_row_bytes(fmt, width):
+    """nmi_frame_row_bytes: the dense bytes of a row of `width` pixels in format fmt (FRAME_*); 0 for an unknown format or a width
+    that is not whole groups (4 pixels in 5 bytes for the 10-bit packed formats, 2 in 3 for the 12-bit ones).  Host only."""
+    lib = load_library()
+    if not hasattr(lib, "nmi_frame_row_bytes"):  # (a library of an earlier commit, loaded for A/B timing: whole bytes per pixel only)
+        return max(int(width), 0) * FRAME_BYTES_PER_PIXEL.get(int(fmt), 0)
+    return int(lib.nmi_frame_row_bytes(int(fmt), int(width)))
+
+
+def _frame_bytes(fmt, pitch, width, height):
+    """Bytes from a frame's first to the end of its last row's pixels, or None where the library will refuse the arguments."""
+    row = frame_row_bytes(fmt, width)
+    return (height - 1) * (int(pitch) or row) + row if row > 0 and int(pitch) >= 0 else None
 TONE_SHIFT = 0
 TONE_WINDOW = 1
 TONE_PERCENTILE = 2
@@ -69,6 +99,7 @@ EXPORTED_SYMBOLS = (
     "nmi_tone_map_default", "nmi_set_tone_map", "nmi_level_set_tone_map", "nmi_stream_set_tone_map", "nmi_tone_lut",
     "nmi_tone_tile_luts",
     "nmi_set_valid_range", "nmi_deep_frame",
+    "nmi_frame_row_bytes", "nmi_unpack_frame",
 )
 
 
@@ -256,6 +287,10 @@ def load_library(build_if_missing=False):
     if hasattr(lib, "nmi_set_valid_range"):
         lib.nmi_set_valid_range.argtypes = [vp, i32, i32]
         lib.nmi_deep_frame.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
+    if hasattr(lib, "nmi_frame_row_bytes"):
+        lib.nmi_frame_row_bytes.argtypes = [i32, i32]
+        lib.nmi_frame_row_bytes.restype = C.c_int64
+        lib.nmi_unpack_frame.argtypes = [vp, vp, i32, C.c_int64, i32, vp]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -688,9 +723,8 @@ class NmiContext:
         import torch
         if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
             raise TypeError("src must be a device uint8 tensor")
-        bpp = FRAME_BYTES_PER_PIXEL.get(int(fmt))
-        if bpp is not None and int(pitch) >= 0:
-            need = (self.height - 1) * (int(pitch) or self.width * bpp) + self.width * bpp
+        need = _frame_bytes(fmt, pitch, self.width, self.height)
+        if need is not None:
             avail = src.untyped_storage().nbytes() - src.storage_offset()
             if avail < need:
                 raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
@@ -745,6 +779,33 @@ class NmiContext:
         if sync:
             self.synchronize()
         return out, out_mask
+
+    def unpack_frame(self, src, fmt, factor=1, pitch=0, out=None, sync=True):
+        """nmi_unpack_frame: the packed, big-endian or 16-bit mosaic deep frame src (factor * H rows of `pitch` bytes, factor * W
+        pixels each in format fmt, one of FRAME_UNPACKED; src as for gray_frame) -> its dense FRAME_GRAY16 container, a device
+        int16 tensor [factor*H, factor*W] holding the uint16 pixels' bits (view(torch.uint8) is what tone_lut, tone_tile_luts and
+        deep_frame take).  A new tensor when out is None.  Enqueued on the context's stream."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+            raise TypeError("src must be a device uint8 tensor")
+        f = int(factor)
+        shape = (f * self.height, f * self.width)
+        need = _frame_bytes(fmt, pitch, shape[1], shape[0]) if 1 <= f <= 4 else None
+        if need is not None:
+            avail = src.untyped_storage().nbytes() - src.storage_offset()
+            if avail < need:
+                raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
+        if out is None:
+            out = torch.empty(shape if 1 <= f <= 4 else (self.height, self.width), dtype=torch.int16, device=self.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int16 and out.is_contiguous()):
+            raise TypeError("out must be a contiguous device int16 tensor")
+        if 1 <= f <= 4 and tuple(out.shape) != shape:
+            raise ValueError(f"out is {tuple(out.shape)}, the container is {shape}")
+        self._order_after_torch()
+        self._check(self._lib.nmi_unpack_frame(self._h, src.data_ptr(), int(fmt), int(pitch), f, out.data_ptr()), "nmi_unpack_frame")
+        if sync:
+            self.synchronize()
+        return out
 
     def tone_lut(self, src, factor=1, pitch=0, out=None, window=True):
         """nmi_tone_lut: the uint8 table [TONE_LEVELS] the context's tone map gives for the FRAME_GRAY16 frame src (factor * H rows
@@ -804,9 +865,8 @@ class NmiContext:
         if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
             raise TypeError("src must be a device uint8 tensor")
         f = int(factor)
-        bpp = FRAME_BYTES_PER_PIXEL.get(int(fmt))
-        if bpp is not None and int(pitch) >= 0 and 1 <= f <= 4:
-            need = (f * self.height - 1) * (int(pitch) or f * self.width * bpp) + f * self.width * bpp
+        need = _frame_bytes(fmt, pitch, f * self.width, f * self.height) if 1 <= f <= 4 else None
+        if need is not None:
             avail = src.untyped_storage().nbytes() - src.storage_offset()
             if avail < need:
                 raise ValueError(f"src holds {avail} bytes from its first element, the frame needs {need}")
@@ -1443,9 +1503,7 @@ class NmiStream:
         `pitch` bytes (0: dense) in format fmt (FRAME_*), converted to grey on the device before their warps.  Frame masks stay
         dense [H,W].  (FRAME_GRAY, 0) or (FRAME_GRAY, W) turns it off."""
         self.ctx._check(self._lib.nmi_stream_set_frame_format(self._h, int(fmt), int(pitch)), "nmi_stream_set_frame_format")
-        bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
-        w, h = self.ctx.width, self.ctx.height
-        self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
+        self._frame_bytes = _frame_bytes(fmt, pitch, self.ctx.width, self.ctx.height)
 
     def set_tone_map(self, tm=None):
         """Tone map of FRAME_GRAY16 host frames (nmi_stream_set_tone_map; ToneMap, None: SHIFT, 16 bits), for later submissions:
@@ -1459,9 +1517,7 @@ class NmiStream:
         on the device before their warps.  Frame masks stay [H,W].  set_frame_format with a factor: the later call wins;
         (1, FRAME_GRAY, 0) turns both off."""
         self.ctx._check(self._lib.nmi_stream_set_frame_reduction(self._h, int(factor), int(fmt), int(pitch)), "nmi_stream_set_frame_reduction")
-        bpp = FRAME_BYTES_PER_PIXEL[int(fmt)]
-        w, h = int(factor) * self.ctx.width, int(factor) * self.ctx.height
-        self._frame_bytes = (h - 1) * (int(pitch) or w * bpp) + w * bpp
+        self._frame_bytes = _frame_bytes(fmt, pitch, int(factor) * self.ctx.width, int(factor) * self.ctx.height)
 
     def _frame_ptr(self, frame_host):
         """A host frame's pointer, its size checked against the frame format (dense grey: exactly H x W bytes)."""

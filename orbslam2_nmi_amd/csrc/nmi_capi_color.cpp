@@ -1,7 +1,7 @@
 // nmi_capi_color.cpp -- nmi_gray_frame (include/nmi_hip.h) and the host side of the frame formats the captured levels and streams
 // share (nmi_level_set_frame_format, nmi_stream_set_frame_format: both through nmi_capi_intake.cpp's intake_set_frame and
 // launch_intake).  Kernels: nmi_color.hip, nmi_bayer.hip (mosaics), and the colour instantiation of the undistortion kernel in
-// nmi_undistort.hip; deep grey frames (GRAY16) go through their tone table (nmi_tone.h).
+// nmi_undistort.hip; deep grey frames (GRAY16 and the formats that unpack to it) go through their tone table (nmi_tone.h).
 #include "nmi_color.h"
 #include "nmi_ctx.h"
 
@@ -17,7 +17,12 @@ int nmi_internal::frame_bytes_per_pixel(int32_t format)
     case NMI_FRAME_RGBA: return 4;
     case NMI_FRAME_YUYV:
     case NMI_FRAME_UYVY:
-    case NMI_FRAME_GRAY16: return 2;
+    case NMI_FRAME_GRAY16:
+    case NMI_FRAME_GRAY16_BE:
+    case NMI_FRAME_BAYER16_RGGB:
+    case NMI_FRAME_BAYER16_GRBG:
+    case NMI_FRAME_BAYER16_GBRG:
+    case NMI_FRAME_BAYER16_BGGR: return 2;
     case NMI_FRAME_BAYER_RGGB:
     case NMI_FRAME_BAYER_GRBG:
     case NMI_FRAME_BAYER_GBRG:
@@ -26,13 +31,26 @@ int nmi_internal::frame_bytes_per_pixel(int32_t format)
     }
 }
 
+int64_t nmi_internal::frame_row_bytes(int32_t format, int64_t width)
+{
+    if (width <= 0) return 0;
+    switch (format) {
+    case NMI_FRAME_MONO10P:
+    case NMI_FRAME_RAW10: return width % 4 == 0 ? width / 4 * 5 : 0;
+    case NMI_FRAME_MONO12P:
+    case NMI_FRAME_RAW12: return width % 2 == 0 ? width / 2 * 3 : 0;
+    default: return width * frame_bytes_per_pixel(format);
+    }
+}
+
 int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity)
 {
-    const int bpp = frame_bytes_per_pixel(format);
-    if (bpp == 0 || pitch < 0 || width <= 0 || height <= 0) return NMI_ERR_INVALID_ARGUMENT;
-    if (nmi::frame_is_bayer(format) && (width < 2 || height < 2)) return NMI_ERR_INVALID_ARGUMENT;  // (the reflected edge needs a neighbour)
-    if (format == NMI_FRAME_GRAY16 && ((pitch % 2) != 0 || (int64_t)width * height > (int64_t)UINT32_MAX)) return NMI_ERR_INVALID_ARGUMENT;
-    const int64_t dense = (int64_t)width * bpp;
+    const int64_t dense = frame_row_bytes(format, width);
+    if (dense == 0 || pitch < 0 || width <= 0 || height <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    // (the reflected edge needs a neighbour)
+    if ((nmi::frame_is_bayer(format) || nmi::frame_is_bayer16(format)) && (width < 2 || height < 2)) return NMI_ERR_INVALID_ARGUMENT;
+    if (nmi::frame_is_words(format) && (pitch % 2) != 0) return NMI_ERR_INVALID_ARGUMENT;
+    if (nmi::frame_is_deep(format) && (int64_t)width * height > (int64_t)UINT32_MAX) return NMI_ERR_INVALID_ARGUMENT;
     if (pitch != 0 && pitch < dense) return NMI_ERR_INVALID_ARGUMENT;
     if (row_bytes) *row_bytes = pitch ? pitch : dense;
     if (identity) *identity = format == NMI_FRAME_GRAY && (pitch == 0 || pitch == dense);
@@ -48,15 +66,15 @@ int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t p
     int64_t rb = 0;
     if (frame_format_check(format, pitch, W, H, &rb, nullptr) != NMI_OK || !frame_base_ok(format, d_src)) return NMI_ERR_INVALID_ARGUMENT;
     // the source's bytes run from d_src to the end of its last row's pixels; the grey frame's H x W bytes may not meet them
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + (int64_t)W * frame_bytes_per_pixel(format));
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + frame_row_bytes(format, W));
     const uintptr_t g0 = (uintptr_t)d_gray, g1 = g0 + (uintptr_t)ctx->npix;
     if (g0 < s1 && s0 < g1) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    if (format == NMI_FRAME_GRAY16) {  // through the context's tone map, as it is now
+    if (nmi::frame_is_deep(format)) {  // through the context's tone map, as it is now (and through the container, if not GRAY16)
         const nmi::ToneSetting t = ctx->tone;
-        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
-        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, ctx->valid, d_src, rb, 1, nullptr, d_gray, nullptr, W, H, ctx->stream));
+        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream, container_bytes(format, 1, W, H)));
+        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, ctx->valid, d_src, format, rb, 1, nullptr, d_gray, nullptr, W, H, ctx->stream));
         return NMI_OK;
     }
     NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));

@@ -51,7 +51,8 @@ hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint
     const uint8_t *raw_mask = mask_out ? src_mask : nullptr;
     if (in.deep()) {  // (distorted: two_nodes())
         // the tone tables of the full-size source where they come from the frame, then the conversion (and reduction)
-        const hipError_t e = deep_gray(tone, in.tone, src, src_row_bytes, in.frame_factor, in.distorted ? scratch : gray_out, width, height, stream);
+        const hipError_t e = deep_gray(tone, in.tone, src, in.frame_format, src_row_bytes, in.frame_factor, in.distorted ? scratch : gray_out, width,
+                                       height, stream);
         if (e != hipSuccess || !in.distorted) return e;
         return nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
     }

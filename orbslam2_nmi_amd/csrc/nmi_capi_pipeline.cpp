@@ -285,7 +285,11 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     // every warp "changed": the first replay builds all the tables (the previous counts may be another frame mask's)
     if (ok.e == hipSuccess && all_tables) ok(hipMemset(lv->d_counts.as<int32_t>() + lv->Wn, 0xFF, (size_t)lv->Wn * sizeof(int32_t)));
     // a deep frame's tone buffers, and the table of a fixed mode (outside the capture: the graph only reads it)
-    if (ok.e == hipSuccess && next.intake.deep()) ok(tone_prepare(&lv->tone_work, next.intake.tone, ctx->stream));
+    // (and the container of a deep source that unpacks; it only grows, and a grown one is a new address)
+    const nmi_params &p = ctx->params;
+    const void *container_was = lv->tone_work.container.as<>();
+    if (ok.e == hipSuccess && next.intake.deep())
+        ok(tone_prepare(&lv->tone_work, next.intake.tone, ctx->stream, next.intake.container(p.width, p.height)));
     int rc = ok.e == hipSuccess ? NMI_OK : hip_fail(ctx, ok.e, what);
     const LevelSettings was = lv->set;
     if (rc == NMI_OK) {
@@ -295,7 +299,10 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
     if (rc != NMI_OK) {
         lv->set = was;
         for (DeviceBuffer *slot : fresh) (void)slot->reset();
-        if (was.intake.deep()) (void)tone_prepare(&lv->tone_work, was.intake.tone, ctx->stream);  // the old graph's table again
+        if (was.intake.deep()) {  // the old graph's table again; its container moved: the old settings captured again
+            (void)tone_prepare(&lv->tone_work, was.intake.tone, ctx->stream, was.intake.container(p.width, p.height));
+            if (was.intake.container(p.width, p.height) && lv->tone_work.container.as<>() != container_was) (void)level_capture(lv);
+        }
         return rc;
     }
     for (const LevelBuffer &b : level_buffers(lv, lv->set))  // no graph reads these any more
@@ -865,7 +872,7 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
     const FrameIntake in = st->intake;  // (this submission's: a later setter call does not reach it)
     const bool undistort = h_frame && in.distorted, colored = h_frame && in.colored;
     const int32_t factor = in.frame_factor;
-    const int64_t dense_row = (int64_t)factor * ctx->params.width * frame_bytes_per_pixel(in.frame_format);
+    const int64_t dense_row = frame_row_bytes(in.frame_format, (int64_t)factor * ctx->params.width);  // (packed: 10 or 12 bits per pixel)
     const size_t color_rows = (size_t)factor * ctx->params.height, color_need = (size_t)dense_row * color_rows;
     for (int b = 0; (undistort || colored) && b < 2; ++b) {
         NMI_HIP_TRY(ctx, st->d_ud[b].grow(npix));
@@ -905,7 +912,7 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const uint8_t *frame = d_frame, *frame_mask = h_frame_mask ? d_fmask : nullptr;
         // the camera's frame (and mask) -> the grey, undistorted ones, on the compute stream: the warps read them next
         uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb].as<uint8_t>() : nullptr;
-        if (in.deep()) NMI_HIP_TRY(ctx, tone_prepare(&st->tone_work, in.tone, ctx->stream));
+        if (in.deep()) NMI_HIP_TRY(ctx, tone_prepare(&st->tone_work, in.tone, ctx->stream, in.container(ctx->params.width, ctx->params.height)));
         NMI_HIP_TRY(ctx, launch_intake(in, st->tone_work, colored ? d_color : d_frame, dense_row, frame_mask, d_frame, d_ud, ud_mask,
                                        ctx->params.width, ctx->params.height, ctx->stream));
         if (in.own_frame()) frame = d_ud;

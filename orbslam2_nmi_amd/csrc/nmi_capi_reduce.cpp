@@ -34,23 +34,23 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
     // the source's bytes run from d_src to the end of its last row's pixels, the source mask's over its dense f H x f W bytes;
     // neither output may meet them, or the other output
     const uintptr_t s0 = (uintptr_t)d_src, m0 = (uintptr_t)d_src_mask, g0 = (uintptr_t)d_gray, o0 = (uintptr_t)d_mask;
-    const Span src{s0, s0 + (uintptr_t)((fH - 1) * rb + fW * frame_bytes_per_pixel(format))};
+    const Span src{s0, s0 + (uintptr_t)((fH - 1) * rb + frame_row_bytes(format, fW))};
     const Span src_mask{m0, d_src_mask ? m0 + (uintptr_t)(fW * fH) : m0};
     const Span gray{g0, g0 + (uintptr_t)ctx->npix};
     const Span mask{o0, d_mask ? o0 + (uintptr_t)ctx->npix : o0};
     if (meet(gray, src) || meet(gray, src_mask) || meet(mask, src) || meet(mask, src_mask) || meet(gray, mask)) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    if (format == NMI_FRAME_GRAY16) {  // the tone table from the full-size frame, then nmi_tone.hip's conversion at every factor
+    if (nmi::frame_is_deep(format)) {  // the tone table from the full-size frame, then nmi_tone.hip's conversion at every factor
         const nmi::ToneSetting t = ctx->tone;
-        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
+        NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream, container_bytes(format, factor, W, H)));
         const nmi::ValidRange range = ctx->valid;
         if (d_mask && range.on()) {  // the mask pair's rule first, then validity ANDed into it by the conversion (in place)
             NMI_HIP_TRY(ctx, nmi::launch_reduce_mask(d_src_mask, factor, d_mask, W, H, ctx->stream));
-            NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, d_mask, d_gray, d_mask, W, H, ctx->stream));
+            NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, format, rb, factor, d_mask, d_gray, d_mask, W, H, ctx->stream));
             return NMI_OK;
         }
-        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, nullptr, d_gray, nullptr, W, H, ctx->stream));
+        NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, format, rb, factor, nullptr, d_gray, nullptr, W, H, ctx->stream));
     } else if (factor == 1) {  // nmi_gray_frame; the mask is copied as 0 / 1
         NMI_HIP_TRY(ctx, nmi::launch_gray(d_src, format, rb, d_gray, W, H, ctx->stream));
     } else {

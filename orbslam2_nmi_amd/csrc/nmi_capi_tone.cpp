@@ -1,5 +1,6 @@
 // nmi_capi_tone.cpp -- the tone map of the deep grey frames (NMI_FRAME_GRAY16, include/nmi_hip.h): nmi_tone_map_default,
-// nmi_set_tone_map, nmi_set_valid_range, nmi_tone_lut, nmi_tone_tile_luts, nmi_deep_frame, and the host side every GRAY16
+// nmi_set_tone_map, nmi_set_valid_range, nmi_tone_lut, nmi_tone_tile_luts, nmi_deep_frame, nmi_unpack_frame (the container of a
+// packed, big-endian or mosaic deep source: nmi_unpack.h) with nmi_frame_row_bytes, and the host side every GRAY16
 // conversion shares (nmi_tone.h): the check of a setting, the buffers that go with it and the nodes in front of the conversion.  nmi_level_set_tone_map and
 // nmi_stream_set_tone_map are with the other setters in nmi_capi_pipeline.cpp.  Kernels: nmi_tone.hip, and nmi_clahe.hip for the
 // tiled mode.
@@ -7,6 +8,7 @@
 
 #include "nmi_color.h"
 #include "nmi_ctx.h"
+#include "nmi_unpack.h"
 
 using namespace nmi_internal;
 
@@ -55,11 +57,18 @@ int nmi_internal::tone_check(const nmi_tone_map *tm, int width, int height, nmi:
     return NMI_OK;
 }
 
-hipError_t nmi_internal::tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream)
+size_t nmi_internal::container_bytes(int32_t format, int factor, int width, int height)
+{
+    return nmi::frame_needs_unpack(format) ? 2 * ((size_t)factor * width) * ((size_t)factor * height) : 0;
+}
+
+hipError_t nmi_internal::tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream, size_t container)
 {
     const size_t lut_bytes = (size_t)nmi::kToneLevels + 2 * sizeof(int32_t);
     if (w->lut.size() < lut_bytes) w->built = false;
-    hipError_t e = w->lut.grow(lut_bytes, stream);
+    hipError_t e = container ? w->container.grow(container, stream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    e = w->lut.grow(lut_bytes, stream);
     if (e != hipSuccess || t.mode == NMI_TONE_TABLE) return e;
     if (t.tiled()) {  // the tiles' histograms start clean and the table kernel leaves them so; a setting of fewer bits or tiles fits
         w->built = false;
@@ -100,11 +109,18 @@ hipError_t nmi_internal::launch_clahe_tone(const ToneWork &w, const nmi::ToneSet
     return e != hipSuccess ? e : nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), w.tile_tables(), w.tile_counts(t), stream);
 }
 
-hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch,
-                                   int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height,
-                                   hipStream_t stream)
+hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int format,
+                                   int64_t pitch, int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width,
+                                   int height, hipStream_t stream)
 {
     const bool masked = mask_out != nullptr;
+    if (format != NMI_FRAME_GRAY16) {  // the container first; from here on the source is dense GRAY16
+        if (w.container.size() < container_bytes(format, factor, width, height) || !w.container) return hipErrorInvalidValue;
+        const hipError_t e = nmi::launch_unpack(src, format, pitch, w.container.as<uint16_t>(), factor * width, factor * height, stream);
+        if (e != hipSuccess) return e;
+        src = w.container.as<uint8_t>();
+        pitch = 2 * (int64_t)factor * width;
+    }
     if (t.tiled()) {
         const hipError_t e = launch_clahe_tone(w, t, range, src, pitch, factor * width, factor * height, stream);
         if (e != hipSuccess) return e;
@@ -228,7 +244,27 @@ int nmi_deep_frame(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t fa
     const nmi::ValidRange range = ctx->valid;
     NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
     // (range off: every pixel is valid, and the masked conversion writes the frame mask as 0 / 1, all 1 without one)
-    NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, rb, factor, d_frame_mask, d_gray, d_mask, W, H, ctx->stream));
+    NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, NMI_FRAME_GRAY16, rb, factor, d_frame_mask, d_gray, d_mask, W, H, ctx->stream));
+    return NMI_OK;
+}
+
+int64_t nmi_frame_row_bytes(int32_t format, int32_t width) { return frame_row_bytes(format, width); }
+
+int nmi_unpack_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch, int32_t factor, uint16_t *d_gray16)
+{
+    if (!ctx || !d_src || !d_gray16 || factor < 1 || factor > 4 || !nmi::frame_needs_unpack(format)) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
+    int64_t rb = 0;
+    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
+        !frame_base_ok(format, d_src) || ((uintptr_t)d_gray16 % 2) != 0)
+        return NMI_ERR_INVALID_ARGUMENT;
+    // the source's bytes run from d_src to the end of its last row's pixels; the container's 2 f W f H bytes may not meet them
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * rb + frame_row_bytes(format, fW));
+    const uintptr_t c0 = (uintptr_t)d_gray16, c1 = c0 + (uintptr_t)(2 * fW * fH);
+    if (c0 < s1 && s0 < c1) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, nmi::launch_unpack(d_src, format, rb, d_gray16, (int)fW, (int)fH, ctx->stream));
     return NMI_OK;
 }
 

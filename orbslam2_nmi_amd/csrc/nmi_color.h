@@ -19,6 +19,14 @@ inline bool frame_is_bayer(int format) { return format >= NMI_FRAME_BAYER_RGGB &
 
 // (NMI_FRAME_GRAY16 is not launch_gray's or launch_reduce's: it needs its tone table, nmi_tone.h's launch_gray16.)
 
+// The deep raw formats (include/nmi_hip.h "Deep frames"): format is one of NMI_FRAME_BAYER16_*; a deep source that is not its
+// own container and goes through nmi_unpack.h's kernel first; any deep source, GRAY16 included; a deep source of 2-byte words
+// (even base, even pitch), as against the byte-packed ones.
+inline bool frame_is_bayer16(int format) { return format >= NMI_FRAME_BAYER16_RGGB && format <= NMI_FRAME_BAYER16_BGGR; }
+inline bool frame_needs_unpack(int format) { return format == NMI_FRAME_GRAY16_BE || (format >= NMI_FRAME_MONO10P && format <= NMI_FRAME_BAYER16_BGGR); }
+inline bool frame_is_deep(int format) { return format == NMI_FRAME_GRAY16 || frame_needs_unpack(format); }
+inline bool frame_is_words(int format) { return format == NMI_FRAME_GRAY16 || format == NMI_FRAME_GRAY16_BE || frame_is_bayer16(format); }
+
 // launch_gray (factor 1) and launch_reduce (nmi_reduce.h; factor 2 .. 4) of a Bayer mosaic of factor * height rows of factor *
 // width bytes (both >= 2), in one kernel (nmi_bayer.hip): launch_gray and launch_reduce pass their Bayer formats on to it.
 hipError_t launch_bayer(const uint8_t *src, int format, int64_t pitch, int factor, uint8_t *gray, int width, int height, hipStream_t stream);
@@ -32,15 +40,19 @@ hipError_t launch_undistort_color(const UndistortParams &p, const uint8_t *src, 
 
 namespace nmi_internal {
 
-// Bytes per pixel of an NMI_FRAME_* format, 0 for an unknown one.
+// Bytes per pixel of an NMI_FRAME_* format, 0 for an unknown one and for the byte-packed ones (10 and 12 bits per pixel).
 int frame_bytes_per_pixel(int32_t format);
 
-// The source's first byte is aligned as format asks: GRAY16 on 2 bytes, every other format anywhere.
-inline bool frame_base_ok(int32_t format, const void *src) { return format != NMI_FRAME_GRAY16 || ((uintptr_t)src % 2) == 0; }
+// Dense bytes of a row of width pixels in an NMI_FRAME_* format (nmi_frame_row_bytes): 0 for an unknown format, a width <= 0
+// or one that is not whole groups (4 pixels in 5 bytes, 2 in 3).
+int64_t frame_row_bytes(int32_t format, int64_t width);
 
-// format known, pitch 0 (dense) or >= width * bytes per pixel, a Bayer mosaic at least 2 x 2, a GRAY16 pitch even (and the
-// frame below 2^32 pixels: its histogram counts in 32 bits) -> NMI_OK, *row_bytes = the rows'
-// pitch (width * bytes per pixel for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion);
+// The source's first byte is aligned as format asks: the 2-byte deep formats on 2 bytes, every other format anywhere.
+inline bool frame_base_ok(int32_t format, const void *src) { return !nmi::frame_is_words(format) || ((uintptr_t)src % 2) == 0; }
+
+// format known, width whole groups, pitch 0 (dense) or >= the row's bytes, a Bayer mosaic (8 or 16 bits) at least 2 x 2, a
+// 2-byte deep format's pitch even (and a deep frame below 2^32 pixels: its histogram counts in 32 bits) -> NMI_OK, *row_bytes =
+// the rows' pitch (frame_row_bytes for 0) and *identity = the frame is dense grey (GRAY with pitch 0 or width: no conversion);
 // else NMI_ERR_INVALID_ARGUMENT.  width and height are the source's.
 int frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity);
 

@@ -27,7 +27,9 @@ struct FrameIntake {
 
     bool reduced() const { return frame_factor > 1; }
     bool mosaic() const { return nmi::frame_is_bayer(frame_format); }
-    bool deep() const { return frame_format == NMI_FRAME_GRAY16; }
+    bool deep() const { return nmi::frame_is_deep(frame_format); }  // GRAY16, or a format that unpacks to it
+    // bytes of the container a deep source that is not GRAY16 is unpacked into (tone_prepare), 0 for every other format
+    size_t container(int width, int height) const { return container_bytes(frame_format, frame_factor, width, height); }
     // grey frame first (into launch_intake's scratch), undistortion second: a reduction, a Bayer mosaic, whose taps would
     // each demosaic a 3 x 3 neighbourhood (profiles/sensor/README.md: the fused node takes twice the two nodes' time), and a
     // deep frame, whose table comes from the whole frame first
@@ -54,7 +56,8 @@ int intake_set_tone_map(FrameIntake *in, int width, int height, const nmi_tone_m
 //   coloured              launch_gray
 // A deep frame (GRAY16) takes deep_gray (nmi_tone.h) in launch_gray's and launch_reduce's place: launch_gray16 behind the histogram
 // and table nodes of a PERCENTILE or EQUALIZE tone map, or CLAHE's tile histograms, tile tables and blending conversion; tone is
-// its prepared work area (tone_prepare), unused for every other format.
+// its prepared work area (tone_prepare), unused for every other format.  A deep format that is not GRAY16 (packed, big-endian,
+// a 16-bit mosaic) has one more node in front of those, on the same chain: the unpack kernel into tone's container.
 // mask_out (may be null; only written when distorted) = the undistorted src_mask (dense [H][W], may be null: border only).
 // scratch is [H][W] and needed only when in.two_nodes().
 hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask,

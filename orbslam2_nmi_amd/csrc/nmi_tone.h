@@ -117,6 +117,9 @@ struct ToneWork {
     nmi_mem::DeviceBuffer tile_luts;  // CLAHE: clahe_luts_bytes, then uint32_t [kClaheMaxTileCount]
     uint8_t *tile_tables() const { return tile_luts.as<uint8_t>(); }
     uint32_t *tile_counts(const nmi::ToneSetting &t) const { return reinterpret_cast<uint32_t *>(tile_luts.as<uint8_t>() + nmi::clahe_luts_bytes(t)); }
+    // A deep source that is not GRAY16 (packed, big-endian, a 16-bit mosaic): its dense container, uint16_t [f H][f W], written by
+    // nmi_unpack.h's kernel in front of every conversion and read by the GRAY16 kernels in the source's place.
+    nmi_mem::DeviceBuffer container;
     bool built = false;          // lut holds the table of `fixed`
     nmi::ToneSetting fixed;
     uint8_t *table() const { return lut.as<uint8_t>(); }
@@ -125,7 +128,12 @@ struct ToneWork {
 
 // Brings *w to what a GRAY16 conversion under t needs, on `stream`: the buffers (grown by nmi_mem.h's rule, the histogram
 // cleared), and for SHIFT and WINDOW the table itself, built once per setting.  Not to be called inside a stream capture.
-hipError_t tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream);
+// container: the bytes of the source's container (container_bytes; 0 for GRAY16, which needs none), grown by the same rule.
+hipError_t tone_prepare(ToneWork *w, const nmi::ToneSetting &t, hipStream_t stream, size_t container = 0);
+
+// Bytes of the dense container of a factor * width x factor * height source in `format`: 2 per pixel for a deep format that
+// unpacks (nmi_color.h's frame_needs_unpack), 0 for every other.
+size_t container_bytes(int32_t format, int factor, int width, int height);
 
 // The nodes in front of a GRAY16 conversion of the f W x f H source through one table: the histogram and the table for
 // PERCENTILE and EQUALIZE, nothing otherwise.  Returns through *lut the table the conversion reads.  *w was prepared for t,
@@ -142,13 +150,15 @@ hipError_t launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const
 // height source to the dense grey [height][width] under t -- launch_tone and launch_gray16, or CLAHE's three.  *w was prepared for t.
 // The statistics are those of the pixels inside `range`.  mask_out (may be null): the conversion is the masked one and writes the
 // validity mask, ANDed with frame_mask (dense [height][width], may be null, may be mask_out itself).
-hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int64_t pitch, int factor,
-                     const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height, hipStream_t stream);
+// format: NMI_FRAME_GRAY16, or a deep format that unpacks: then one more node in front, the unpack kernel (nmi_unpack.h) from
+// src's rows of pitch bytes into w.container (prepared with container_bytes), which every node behind it reads as dense GRAY16.
+hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int format, int64_t pitch,
+                     int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height, hipStream_t stream);
 // ... with the range off and no mask: the intake of levels and streams (nmi_capi_intake.cpp), which take no valid range.
-inline hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, uint8_t *gray, int width,
-                            int height, hipStream_t stream)
+inline hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int format, int64_t pitch, int factor,
+                            uint8_t *gray, int width, int height, hipStream_t stream)
 {
-    return deep_gray(w, t, nmi::ValidRange{}, src, pitch, factor, nullptr, gray, nullptr, width, height, stream);
+    return deep_gray(w, t, nmi::ValidRange{}, src, format, pitch, factor, nullptr, gray, nullptr, width, height, stream);
 }
 
 }  // namespace nmi_internal
