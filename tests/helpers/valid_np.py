@@ -202,6 +202,22 @@ def block_corner(ws, hs, f, seed=0):
     return px.astype(np.uint16), (0, 16383), 14
 
 
+def seam_pixels(ws, hs, f, columns, seed=0):
+    """Exactly one invalid source pixel (0) in the f x f block of one output pixel per entry of `columns` (output x), each on a
+    different output row and in a different corner of its block; everything else valid: range (1, 65535), 14 bits.  Returns
+    (pixels, range, bits, [(x, y) of the output pixels whose mask is 0])."""
+    rng = np.random.default_rng(seed)
+    px = rng.integers(3000, 16000, (hs, ws))
+    h = hs // f
+    assert len(columns) <= min(h, 4)
+    corners = [(f - 1, f - 1), (0, f - 1), (f - 1, 0), (0, 0)]                  # (dy, dx)
+    rows = [(1 + i * (h - 2) // max(len(columns) - 1, 1)) for i in range(len(columns))]   # from row 1 to the last row
+    assert len(set(rows)) == len(rows) and max(rows) == h - 1
+    for x, y, (dy, dx) in zip(columns, rows, corners):
+        px[y * f + dy, x * f + dx] = 0
+    return px.astype(np.uint16), (1, 65535), 14, list(zip(columns, rows))
+
+
 def nothing_valid(ws, hs, seed=0):
     """Every pixel outside the range (100, 200): N == 0.  (The one content whose mask is all 0.)"""
     rng = np.random.default_rng(seed)

@@ -84,8 +84,15 @@ def test_the_half_tiles_at_the_edges_and_a_frame_whose_tiles_differ(nmi, grid):
 @pytest.mark.parametrize("tiles", [(8, 8), (3, 2)], ids=["8x8", "3x2"])
 def test_reduce_frame_equals_the_model(nmi, factor, tiles):
     """Statistics, tiles and blend on the full-size source, then the box average; with a source mask the mask is the existing
-    rule's and the grey frame is unchanged."""
-    w, h = cases.REDUCED[:2]
+    rule's and the grey frame is unchanged.  Factors 3 and 4 under the 8 x 8 grid also at a context of 264 x 8: a second block
+    column of the conversion."""
+    reduce_frame_equals_the_model(nmi, cases.REDUCED[:2], factor, tiles)
+    if factor >= 3 and tiles == (8, 8):
+        reduce_frame_equals_the_model(nmi, (264, 8), factor, tiles)
+
+
+def reduce_frame_equals_the_model(nmi, size, factor, tiles):
+    w, h = size
     tx, ty = tiles
     sw, sh = factor * w, factor * h
     mask = (np.random.default_rng(7).random((sh, sw)) < 0.9).astype(np.uint8) * 3

@@ -8,6 +8,7 @@ import pytest
 
 from helpers import clahe_cases as cases
 from helpers import clahe_np as cnp
+from helpers import seam_cases as seams
 from helpers import tone_np as tnp
 from orbslam2_nmi_amd import capi
 
@@ -95,6 +96,18 @@ def test_a_tile_larger_than_a_workgroups_chunk(nmi):
             for plateau in (0, 1, 50):
                 check_tables(ctx, px, cnp.clahe(2, 1, plateau, bits))
         check_tables(ctx, px, cnp.clahe(1, 1, 7, 16))
+
+
+@pytest.mark.parametrize("bits", [16, 14])
+@pytest.mark.parametrize("run", list(seams.SECOND_TRIP_RUNS))
+def test_a_second_trip_of_every_tile(nmi, run, bits):
+    """2104 x 2012 (factor 4) and 2101 x 2011 in 8 x 8 tiles: every tile holds more than 16 workgroups x 4096 pixels, so each
+    workgroup's stride loop makes a second, ragged trip (tests/test_intake_geometry.py), and only its pixels are in the top
+    quarter of 16 bits: `quarters` is reset and read again there; at 14 bits they carry over in the bins to the one flush."""
+    w, h, f = seams.SECOND_TRIP_RUNS[run]
+    px = seams.second_trip_frame(run, "clahe")
+    with nmi.NmiContext(w, h) as ctx:
+        check_tables(ctx, px, cnp.clahe(*seams.SECOND_TRIP_GRID, 2, bits), factor=f)
 
 
 @pytest.mark.parametrize("extra,off", [(2, 0), (10, 2), (64, 6)])

@@ -12,9 +12,10 @@ from test_tone_frame import dev, tones
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-# search size, factor, source pitch (0: dense), base offset.  620x188: the 1241x376 source's spare column is never read
+# search size, factor, source pitch (0: dense), base offset.  620x188: the 1241x376 source's spare column is never read;
+# 261x9 and 264x8: a second block column of the conversion at factors 3 (its last quad one pixel) and 4
 CASES = [(5, 3, 2, 0, 0), (5, 3, 3, 2 * 15 + 2, 2), (5, 3, 4, 2 * 20 + 10, 6), (64, 48, 2, 0, 0), (64, 48, 3, 2 * 192 + 64, 0),
-         (64, 48, 4, 2 * 256 + 6, 2), (620, 188, 2, 2 * 1241, 0)]
+         (64, 48, 4, 2 * 256 + 6, 2), (620, 188, 2, 2 * 1241, 0), (261, 9, 3, 0, 0), (264, 8, 4, 2 * 1056 + 8, 0)]
 CONTENTS = {"uniform": (lambda w, h: tnp.uniform(w, h, 5), 16), "thermal": (lambda w, h: tnp.thermal(w, h, 6), 14),
             "flat": (lambda w, h: tnp.flat(w, h), 16)}
 

@@ -50,16 +50,15 @@ def set_tone(ctx, tm, keep):
     ctx.set_tone_map(cases.capi_tone(capi, tm, d_lut))
 
 
-@pytest.mark.parametrize("size", cases.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
-@pytest.mark.parametrize("name", list(cases.FRAMES))
-def test_every_entry_equals_the_twin(nmi, name, size):
+def every_entry_equals_the_twin(nmi, name, size, factors, frame=cases.frame):
+    """Every entry on the planted frame frame(name, w, h, f) of a w x h context, at every factor, tone map and layout."""
     w, h = size
     keep = []
     fm = (np.random.default_rng(11).random((h, w)) < 0.85).astype(np.uint8) * 5          # a frame mask at the search size
     with nmi.NmiContext(w, h) as ctx:
-        for f in cases.FRAMES[name]["factors"]:
+        for f in factors:
             ws, hs = f * w, f * h
-            px, rng, bits = cases.frame(name, w, h, f)
+            px, rng, bits = frame(name, w, h, f)
             sm = (np.random.default_rng(12 + f).random((hs, ws)) < 0.95).astype(np.uint8) * 9  # nmi_reduce_frame's own, full size
             ctx.set_valid_range(*rng)
             for tm in cases.tone_maps(bits, ws, hs):
@@ -94,6 +93,12 @@ def test_every_entry_equals_the_twin(nmi, name, size):
                         want_lut, want_window = vnp.table(px, tm, rng)
                         same(lut, want_lut, what + ("lut", li))
                         assert tuple(pair) == tuple(int(x) for x in want_window), (what, pair, want_window)
+
+
+@pytest.mark.parametrize("size", cases.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name", list(cases.FRAMES))
+def test_every_entry_equals_the_twin(nmi, name, size):
+    every_entry_equals_the_twin(nmi, name, size, cases.FRAMES[name]["factors"])
 
 
 def test_the_next_frame_starts_from_clean_histograms(nmi):
