@@ -80,8 +80,7 @@ def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None
         fcntl.flock(lock, fcntl.LOCK_EX)
         newest_header = max(os.path.getmtime(f) for f in headers() + [os.path.abspath(__file__)])
         # nmi_grid_kernel is compiled more than once, through wrappers that #include its file (nmi_kernels_{gated,stamped,
-        # rows}.hip): those depend on nmi_kernels.hip too; shared device code is in headers.  Likewise nmi_tone_valid.hip and
-        # nmi_clahe_valid.hip, which include nmi_tone.hip and nmi_clahe.hip.
+        # rows}.hip): those depend on nmi_kernels.hip too; shared device code is in headers.
         grid_src = os.path.join(PKG, "csrc", "nmi_kernels.hip")
         todo, objs = [], []
         for src in sources():
@@ -90,8 +89,6 @@ def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None
             dep = max(os.path.getmtime(src), newest_header)
             if os.path.basename(src).startswith("nmi_kernels_"):
                 dep = max(dep, os.path.getmtime(grid_src))
-            if os.path.basename(src).endswith("_valid.hip"):
-                dep = max(dep, os.path.getmtime(src[:-len("_valid.hip")] + ".hip"))
             if force or not os.path.exists(obj) or os.path.getmtime(obj) < dep:
                 todo.append((src, obj))
         if todo:

@@ -57,18 +57,30 @@ int nmi_internal::frame_format_check(int32_t format, int64_t pitch, int width, i
     return NMI_OK;
 }
 
+int nmi_internal::frame_source_check(int32_t format, int64_t pitch, int32_t factor, int width, int height, const void *d_src, FrameSource *out)
+{
+    if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t fW = (int64_t)factor * width, fH = (int64_t)factor * height;
+    FrameSource s;
+    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(format, pitch, (int)fW, (int)fH, &s.row_bytes, &s.identity) != NMI_OK ||
+        !frame_base_ok(format, d_src))
+        return NMI_ERR_INVALID_ARGUMENT;
+    s.width = (int)fW, s.height = (int)fH;
+    s.bytes = span_of(d_src, (size_t)((fH - 1) * s.row_bytes + frame_row_bytes(format, fW)));
+    *out = s;
+    return NMI_OK;
+}
+
 extern "C" {
 
 int nmi_gray_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch, uint8_t *d_gray)
 {
     if (!ctx || !d_src || !d_gray) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
-    int64_t rb = 0;
-    if (frame_format_check(format, pitch, W, H, &rb, nullptr) != NMI_OK || !frame_base_ok(format, d_src)) return NMI_ERR_INVALID_ARGUMENT;
-    // the source's bytes run from d_src to the end of its last row's pixels; the grey frame's H x W bytes may not meet them
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((H - 1) * rb + frame_row_bytes(format, W));
-    const uintptr_t g0 = (uintptr_t)d_gray, g1 = g0 + (uintptr_t)ctx->npix;
-    if (g0 < s1 && s0 < g1) return NMI_ERR_INVALID_ARGUMENT;
+    FrameSource src;
+    if (frame_source_check(format, pitch, 1, W, H, d_src, &src) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t rb = src.row_bytes;
+    if (meet(span_of(d_gray, ctx->npix), src.bytes)) return NMI_ERR_INVALID_ARGUMENT;  // the grey frame's H x W bytes
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     if (nmi::frame_is_deep(format)) {  // through the context's tone map, as it is now (and through the container, if not GRAY16)

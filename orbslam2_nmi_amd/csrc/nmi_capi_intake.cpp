@@ -28,17 +28,12 @@ int intake_set_distortion_fisheye(FrameIntake *in, const double K[9], const doub
 
 int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int32_t format, int64_t pitch)
 {
-    if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
-    int64_t row_bytes = 0;
-    bool identity = true;
-    const int64_t full_width = (int64_t)factor * width, full_height = (int64_t)factor * height;
-    if (full_width > INT32_MAX || full_height > INT32_MAX ||
-        frame_format_check(format, pitch, (int)full_width, (int)full_height, &row_bytes, &identity) != NMI_OK)
-        return NMI_ERR_INVALID_ARGUMENT;
-    const bool on = !identity || factor > 1;  // dense grey of the search size: as never formatted
+    FrameSource full;  // (no frame yet: its base is checked where it is set)
+    if (frame_source_check(format, pitch, factor, width, height, nullptr, &full) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const bool on = !full.identity || factor > 1;  // dense grey of the search size: as never formatted
     in->colored = on;
     in->frame_format = on ? format : NMI_FRAME_GRAY;
-    in->frame_pitch = on ? row_bytes : 0;
+    in->frame_pitch = on ? full.row_bytes : 0;
     in->frame_factor = factor;
     return NMI_OK;
 }

@@ -8,36 +8,20 @@
 
 using namespace nmi_internal;
 
-namespace {
-
-struct Span {
-    uintptr_t lo, hi;  // [lo, hi); lo == hi: nothing
-};
-
-bool meet(const Span &a, const Span &b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
-
-}  // namespace
-
 extern "C" {
 
 int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch, int32_t factor, const uint8_t *d_src_mask,
                      uint8_t *d_gray, uint8_t *d_mask)
 {
     if (!ctx || !d_src || !d_gray) return NMI_ERR_INVALID_ARGUMENT;
-    if (factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
     if ((d_src_mask == nullptr) != (d_mask == nullptr)) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
-    const int64_t fW = (int64_t)factor * W, fH = (int64_t)factor * H;
-    if (fW > INT32_MAX || fH > INT32_MAX) return NMI_ERR_INVALID_ARGUMENT;
-    int64_t rb = 0;
-    if (frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK || !frame_base_ok(format, d_src)) return NMI_ERR_INVALID_ARGUMENT;
-    // the source's bytes run from d_src to the end of its last row's pixels, the source mask's over its dense f H x f W bytes;
-    // neither output may meet them, or the other output
-    const uintptr_t s0 = (uintptr_t)d_src, m0 = (uintptr_t)d_src_mask, g0 = (uintptr_t)d_gray, o0 = (uintptr_t)d_mask;
-    const Span src{s0, s0 + (uintptr_t)((fH - 1) * rb + frame_row_bytes(format, fW))};
-    const Span src_mask{m0, d_src_mask ? m0 + (uintptr_t)(fW * fH) : m0};
-    const Span gray{g0, g0 + (uintptr_t)ctx->npix};
-    const Span mask{o0, d_mask ? o0 + (uintptr_t)ctx->npix : o0};
+    FrameSource full;
+    if (frame_source_check(format, pitch, factor, W, H, d_src, &full) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const int64_t rb = full.row_bytes;
+    // the source mask's bytes are its dense f H x f W; neither output may meet the source's or the source mask's, or the other output
+    const Span src = full.bytes, src_mask = span_of(d_src_mask, (size_t)full.width * full.height);
+    const Span gray = span_of(d_gray, ctx->npix), mask = span_of(d_mask, ctx->npix);
     if (meet(gray, src) || meet(gray, src_mask) || meet(mask, src) || meet(mask, src_mask) || meet(gray, mask)) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);

@@ -113,7 +113,6 @@ hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t,
                                    int64_t pitch, int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width,
                                    int height, hipStream_t stream)
 {
-    const bool masked = mask_out != nullptr;
     if (format != NMI_FRAME_GRAY16) {  // the container first; from here on the source is dense GRAY16
         if (w.container.size() < container_bytes(format, factor, width, height) || !w.container) return hipErrorInvalidValue;
         const hipError_t e = nmi::launch_unpack(src, format, pitch, w.container.as<uint16_t>(), factor * width, factor * height, stream);
@@ -124,31 +123,24 @@ hipError_t nmi_internal::deep_gray(const ToneWork &w, const nmi::ToneSetting &t,
     if (t.tiled()) {
         const hipError_t e = launch_clahe_tone(w, t, range, src, pitch, factor * width, factor * height, stream);
         if (e != hipSuccess) return e;
-        return masked ? nmi::launch_clahe_gray16_masked(t, src, pitch, factor, w.tile_tables(), range, frame_mask, gray, mask_out, width, height,
-                                                        stream)
-                      : nmi::launch_clahe_gray16(t, src, pitch, factor, w.tile_tables(), gray, width, height, stream);
+        return nmi::launch_clahe_gray16(t, src, pitch, factor, w.tile_tables(), range, frame_mask, gray, mask_out, width, height, stream);
     }
     const uint8_t *lut = nullptr;
     const hipError_t e = launch_tone(w, t, range, src, pitch, factor * width, factor * height, &lut, stream);
     if (e != hipSuccess) return e;
-    return masked ? nmi::launch_gray16_masked(src, pitch, factor, lut, t.bits, range, frame_mask, gray, mask_out, width, height, stream)
-                  : nmi::launch_gray16(src, pitch, factor, lut, t.bits, gray, width, height, stream);
+    return nmi::launch_gray16(src, pitch, factor, lut, t.bits, range, frame_mask, gray, mask_out, width, height, stream);
 }
 
 namespace {
 
 // nmi_tone_lut's and nmi_tone_tile_luts' arguments: the f W x f H GRAY16 source, and `bytes` of table at d_out that may not
-// meet the source's bytes (from d_src to the end of its last row's pixels).  NMI_OK: *rb = the row bytes.
-int tone_source_check(const nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, const uint8_t *d_out, size_t bytes, int64_t *rb)
+// meet the source's bytes.  NMI_OK: *src.
+int tone_source_check(const nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, const uint8_t *d_out, size_t bytes, FrameSource *src)
 {
-    if (!ctx || !d_src || !d_out || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
-    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
-    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, rb, nullptr) != NMI_OK ||
-        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
+    if (!ctx || !d_src || !d_out) return NMI_ERR_INVALID_ARGUMENT;
+    if (frame_source_check(NMI_FRAME_GRAY16, pitch, factor, ctx->params.width, ctx->params.height, d_src, src) != NMI_OK)
         return NMI_ERR_INVALID_ARGUMENT;
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * *rb + fW * 2);
-    const uintptr_t l0 = (uintptr_t)d_out, l1 = l0 + (uintptr_t)bytes;
-    return l0 < s1 && s0 < l1 ? NMI_ERR_INVALID_ARGUMENT : NMI_OK;
+    return meet(span_of(d_out, bytes), src->bytes) ? NMI_ERR_INVALID_ARGUMENT : NMI_OK;
 }
 
 }  // namespace
@@ -179,16 +171,15 @@ int nmi_set_valid_range(nmi_ctx *ctx, int32_t lo, int32_t hi)
 
 int nmi_tone_lut(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, uint8_t *d_lut, int32_t h_window[2])
 {
-    int64_t rb = 0;
-    if (tone_source_check(ctx, d_src, pitch, factor, d_lut, nmi::kToneLevels, &rb) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
-    const int fW = factor * ctx->params.width, fH = factor * ctx->params.height;
+    FrameSource src;
+    if (tone_source_check(ctx, d_src, pitch, factor, d_lut, nmi::kToneLevels, &src) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     const nmi::ToneSetting t = ctx->tone;
     if (t.tiled()) return NMI_ERR_UNSUPPORTED;  // no single table: nmi_tone_tile_luts
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     ToneWork &w = ctx->tone_work;
     NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
-    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, rb, fW, fH, t.bits, ctx->valid, w.hist.as<uint32_t>(), ctx->stream));
+    if (t.from_frame()) NMI_HIP_TRY(ctx, nmi::launch_tone_hist(d_src, src.row_bytes, src.width, src.height, t.bits, ctx->valid, w.hist.as<uint32_t>(), ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_tone_table(t, w.hist.as<uint32_t>(), d_lut, w.window(), ctx->stream));
     if (h_window) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(h_window, w.window(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -202,15 +193,14 @@ int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_
     if (!ctx) return NMI_ERR_INVALID_ARGUMENT;
     const nmi::ToneSetting t = ctx->tone;
     const size_t bytes = t.tiled() ? nmi::clahe_luts_bytes(t) : (size_t)nmi::kToneLevels;
-    int64_t rb = 0;
-    if (tone_source_check(ctx, d_src, pitch, factor, d_luts, bytes, &rb) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    FrameSource src;
+    if (tone_source_check(ctx, d_src, pitch, factor, d_luts, bytes, &src) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
     if (!t.tiled()) return NMI_ERR_UNSUPPORTED;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     ToneWork &w = ctx->tone_work;
     NMI_HIP_TRY(ctx, tone_prepare(&w, t, ctx->stream));
-    NMI_HIP_TRY(ctx, nmi::launch_clahe_hist(t, d_src, rb, factor * ctx->params.width, factor * ctx->params.height, ctx->valid,
-                                            w.tile_hist.as<uint32_t>(), ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_clahe_hist(t, d_src, src.row_bytes, src.width, src.height, ctx->valid, w.tile_hist.as<uint32_t>(), ctx->stream));
     NMI_HIP_TRY(ctx, nmi::launch_clahe_tables(t, w.tile_hist.as<uint32_t>(), d_luts, w.tile_counts(t), ctx->stream));
     if (h_counts) {
         NMI_HIP_TRY(ctx, hipMemcpyAsync(h_counts, w.tile_counts(t), (size_t)t.tiles_x * t.tiles_y * sizeof(int32_t), hipMemcpyDeviceToHost,
@@ -223,28 +213,22 @@ int nmi_tone_tile_luts(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_
 int nmi_deep_frame(nmi_ctx *ctx, const uint8_t *d_src, int64_t pitch, int32_t factor, const uint8_t *d_frame_mask, uint8_t *d_gray,
                    uint8_t *d_mask)
 {
-    if (!ctx || !d_src || !d_gray || !d_mask || factor < 1 || factor > 4) return NMI_ERR_INVALID_ARGUMENT;
+    if (!ctx || !d_src || !d_gray || !d_mask) return NMI_ERR_INVALID_ARGUMENT;
     const int W = ctx->params.width, H = ctx->params.height;
-    const int64_t fW = (int64_t)factor * W, fH = (int64_t)factor * H;
-    int64_t rb = 0;
-    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(NMI_FRAME_GRAY16, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
-        !frame_base_ok(NMI_FRAME_GRAY16, d_src))
-        return NMI_ERR_INVALID_ARGUMENT;
-    // the source's bytes run from d_src to the end of its last row's pixels; the frame mask and the two outputs are dense [H][W];
-    // no two of the four may meet (a NULL frame mask meets nothing)
-    const uintptr_t npix = (uintptr_t)ctx->npix;
-    const uintptr_t lo[4] = {(uintptr_t)d_src, (uintptr_t)d_frame_mask, (uintptr_t)d_gray, (uintptr_t)d_mask};
-    const uintptr_t hi[4] = {lo[0] + (uintptr_t)((fH - 1) * rb + fW * 2), d_frame_mask ? lo[1] + npix : lo[1], lo[2] + npix, lo[3] + npix};
+    FrameSource src;
+    if (frame_source_check(NMI_FRAME_GRAY16, pitch, factor, W, H, d_src, &src) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    // the frame mask and the two outputs are dense [H][W]; no two of the four may meet (a NULL frame mask meets nothing)
+    const Span spans[4] = {src.bytes, span_of(d_frame_mask, ctx->npix), span_of(d_gray, ctx->npix), span_of(d_mask, ctx->npix)};
     for (int a = 0; a < 4; ++a)
         for (int b = a + 1; b < 4; ++b)
-            if (lo[a] < hi[a] && lo[b] < hi[b] && lo[a] < hi[b] && lo[b] < hi[a]) return NMI_ERR_INVALID_ARGUMENT;
+            if (meet(spans[a], spans[b])) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     const nmi::ToneSetting t = ctx->tone;
     const nmi::ValidRange range = ctx->valid;
     NMI_HIP_TRY(ctx, tone_prepare(&ctx->tone_work, t, ctx->stream));
     // (range off: every pixel is valid, and the masked conversion writes the frame mask as 0 / 1, all 1 without one)
-    NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, NMI_FRAME_GRAY16, rb, factor, d_frame_mask, d_gray, d_mask, W, H, ctx->stream));
+    NMI_HIP_TRY(ctx, deep_gray(ctx->tone_work, t, range, d_src, NMI_FRAME_GRAY16, src.row_bytes, factor, d_frame_mask, d_gray, d_mask, W, H, ctx->stream));
     return NMI_OK;
 }
 
@@ -252,19 +236,14 @@ int64_t nmi_frame_row_bytes(int32_t format, int32_t width) { return frame_row_by
 
 int nmi_unpack_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t pitch, int32_t factor, uint16_t *d_gray16)
 {
-    if (!ctx || !d_src || !d_gray16 || factor < 1 || factor > 4 || !nmi::frame_needs_unpack(format)) return NMI_ERR_INVALID_ARGUMENT;
-    const int64_t fW = (int64_t)factor * ctx->params.width, fH = (int64_t)factor * ctx->params.height;
-    int64_t rb = 0;
-    if (fW > INT32_MAX || fH > INT32_MAX || frame_format_check(format, pitch, (int)fW, (int)fH, &rb, nullptr) != NMI_OK ||
-        !frame_base_ok(format, d_src) || ((uintptr_t)d_gray16 % 2) != 0)
-        return NMI_ERR_INVALID_ARGUMENT;
-    // the source's bytes run from d_src to the end of its last row's pixels; the container's 2 f W f H bytes may not meet them
-    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((fH - 1) * rb + frame_row_bytes(format, fW));
-    const uintptr_t c0 = (uintptr_t)d_gray16, c1 = c0 + (uintptr_t)(2 * fW * fH);
-    if (c0 < s1 && s0 < c1) return NMI_ERR_INVALID_ARGUMENT;
+    if (!ctx || !d_src || !d_gray16 || !nmi::frame_needs_unpack(format) || ((uintptr_t)d_gray16 % 2) != 0) return NMI_ERR_INVALID_ARGUMENT;
+    FrameSource src;
+    if (frame_source_check(format, pitch, factor, ctx->params.width, ctx->params.height, d_src, &src) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    // the container's 2 f W f H bytes may not meet the source's
+    if (meet(span_of(d_gray16, 2 * (size_t)src.width * src.height), src.bytes)) return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
-    NMI_HIP_TRY(ctx, nmi::launch_unpack(d_src, format, rb, d_gray16, (int)fW, (int)fH, ctx->stream));
+    NMI_HIP_TRY(ctx, nmi::launch_unpack(d_src, format, src.row_bytes, d_gray16, src.width, src.height, ctx->stream));
     return NMI_OK;
 }
 

@@ -5,10 +5,10 @@
 //   nmi_clahe_gray16_kernel   the blend per source pixel, then the rounded F x F box average (F = 1: the value itself)
 // All arithmetic is integer (the one fp64 quotient is corrected to the exact floor), so tests/helpers/clahe_np.py equals it bit
 // for bit.
-// With a valid range (nmi_set_valid_range) the histogram and the conversion are kernels of their own, compiled from this file's
-// kernel text once more (nmi_clahe_valid.hip defines NMI_CLAHE_VALID and includes this file): nmi_clahe_hist_ranged_kernel counts
-// the pixels with lo <= raw <= hi only, nmi_clahe_gray16_masked_kernel also writes the validity mask.  The histogram and conversion
-// kernels of this unit are what they were before the range existed, instruction for instruction.
+// With a valid range (nmi_set_valid_range) the histogram and the conversion are instantiations of their own of the same kernel
+// templates, as in nmi_tone.hip: nmi_clahe_hist_kernel<true> counts the pixels with lo <= raw <= hi only, nmi_clahe_gray16_kernel<F,
+// true> also writes the validity mask.  The plain instantiations are what they were before the range existed, instruction for
+// instruction (profiles/deep_templates/isa_vs_parent.txt).
 //
 // Tile column i holds the source columns x with ((2 x + 1) tiles_x) / (2 Ws) == i, that is [x0[i], x0[i + 1]) with x0[i] =
 // ceil((2 Ws i - tiles_x) / (2 tiles_x)); rows likewise.  The host works the edges out once (clahe_grid) and the histogram kernel
@@ -27,14 +27,6 @@
 #include "nmi_tone.h"
 #include "nmi_tone_device.h"
 #include "nmi_reduce_device.h"
-
-#ifdef NMI_CLAHE_VALID
-#define NMI_CLAHE_HIST_KERNEL nmi_clahe_hist_ranged_kernel
-#define NMI_CLAHE_GRAY16_KERNEL nmi_clahe_gray16_masked_kernel
-#else
-#define NMI_CLAHE_HIST_KERNEL nmi_clahe_hist_kernel
-#define NMI_CLAHE_GRAY16_KERNEL nmi_clahe_gray16_kernel
-#endif
 
 namespace nmi {
 
@@ -75,15 +67,14 @@ ClaheGrid clahe_grid(int tx, int ty, int width, int height)
 // Workgroup (c, t) counts chunks c, c + gridDim.x, ... of 256 x 16 pixels of tile t = blockIdx.y, pixel p of a tile being row
 // p / tile width, column p % tile width of it.  2-byte loads: a tile's rows start wherever its edge falls.  The flush clears the
 // bins it adds to the tile's global histogram.
-// NMI_CLAHE_VALID: a pixel is held (and seen, for the quarters) iff it is inside the tile and lo <= raw <= hi, tested on the raw
-// half-word before the saturation.
-__global__ __launch_bounds__(kHistThreads) void NMI_CLAHE_HIST_KERNEL(const uint8_t *__restrict__ src, size_t pitch, ClaheGrid g, uint32_t vmax,
-                                                                      int bits, int passes,
-#ifdef NMI_CLAHE_VALID
-                                                                      uint32_t lo, uint32_t hi,
-#endif
-                                                                      uint32_t *__restrict__ hist)
+// Ranged (Range: uint32_t lo, uint32_t hi; else nothing): a pixel is held (and seen, for the quarters) iff it is inside the tile
+// and lo <= raw <= hi, tested on the raw half-word before the saturation.
+template <bool Ranged, class... Range>
+__global__ __launch_bounds__(kHistThreads) void nmi_clahe_hist_kernel(const uint8_t *__restrict__ src, size_t pitch, ClaheGrid g, uint32_t vmax,
+                                                                      int bits, int passes, Range... lo_hi, uint32_t *__restrict__ hist)
 {
+    static_assert(sizeof...(Range) == (Ranged ? 2 : 0), "RangeArgs<Ranged>'s members");
+    const RangeArgs<Ranged> range{lo_hi...};
     __shared__ uint4 bins4[kHistBins / 4];
     __shared__ uint32_t quarters;  // bit q: a pixel of this chunk has v >> 14 == q
     uint32_t *bins = reinterpret_cast<uint32_t *>(bins4);
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(kHistThreads) void NMI_CLAHE_HIST_KERNEL(const uint
     __syncthreads();
     for (uint64_t first = (uint64_t)blockIdx.x * kHistChunk; first < n; first += (uint64_t)gridDim.x * kHistChunk) {  // (uniform)
         uint32_t w[kHistPerLane / 2];  // pixel k is half k % 2 of word k / 2, saturated
-        uint32_t have = 0, seen = 0;   // bit k: pixel k is inside the tile (NMI_CLAHE_VALID: and the range)
+        uint32_t have = 0, seen = 0;   // bit k: pixel k is inside the tile (Ranged: and the range)
 #pragma unroll
         for (int k = 0; k < kHistPerLane / 2; ++k) w[k] = 0u;
 #pragma unroll
@@ -108,22 +99,16 @@ __global__ __launch_bounds__(kHistThreads) void NMI_CLAHE_HIST_KERNEL(const uint
                 const uint32_t row = (uint32_t)p / tw, col = (uint32_t)p - row * tw;  // row < th, col < tw: inside the frame
                 const uint16_t raw = *reinterpret_cast<const uint16_t *>(src + (size_t)(y0 + row) * pitch + (size_t)(x0 + col) * 2);
                 const uint32_t v = min((uint32_t)raw, vmax);
-#ifdef NMI_CLAHE_VALID
-                if ((uint32_t)raw < lo || (uint32_t)raw > hi) continue;  // not counted, not seen
-#endif
+                if constexpr (Ranged) {
+                    if ((uint32_t)raw < range.lo || (uint32_t)raw > range.hi) continue;  // not counted, not seen
+                }
                 w[k / 2] |= v << (16 * (k % 2));
                 have |= 1u << k;
                 seen |= 1u << (v >> 14);
             }
         }
         uint32_t present = 1u;
-        if (passes > 1) {
-            if (tid == 0) quarters = 0u;
-            __syncthreads();
-            if (seen) atomicOr(&quarters, seen);
-            __syncthreads();
-            present = quarters;
-        }
+        if (passes > 1) present = quarters_present(&quarters, seen, tid);
         for (int pass = 0; pass < passes; ++pass) {
             if (!((present >> pass) & 1u)) continue;  // (uniform over the workgroup)
 #pragma unroll
@@ -134,16 +119,7 @@ __global__ __launch_bounds__(kHistThreads) void NMI_CLAHE_HIST_KERNEL(const uint
             if (passes == 1) continue;  // one flush behind the last chunk
             __syncthreads();
             uint32_t *out = tile_hist + pass * kHistBins;  // (index < passes * 16384 <= 2^bits)
-            for (int i = tid; i < kHistBins / 4; i += kHistThreads) {
-                const uint4 c = bins4[i];
-                if (c.x | c.y | c.z | c.w) {
-                    bins4[i] = make_uint4(0u, 0u, 0u, 0u);
-                    if (c.x) atomicAdd(&out[4 * i], c.x);
-                    if (c.y) atomicAdd(&out[4 * i + 1], c.y);
-                    if (c.z) atomicAdd(&out[4 * i + 2], c.z);
-                    if (c.w) atomicAdd(&out[4 * i + 3], c.w);
-                }
-            }
+            for (int i = tid; i < kHistBins / 4; i += kHistThreads) flush_bins_quad(bins4, out, i);
             __syncthreads();
         }
         __syncthreads();  // (quarters is read by all before the next chunk resets it)
@@ -160,7 +136,6 @@ __global__ __launch_bounds__(kHistThreads) void NMI_CLAHE_HIST_KERNEL(const uint
     }
 }
 
-#ifndef NMI_CLAHE_VALID
 namespace {
 
 // The sum of x over the workgroup's kTableThreads lanes; all call it.  part: shared [kTableWaves], free again on return.
@@ -264,7 +239,6 @@ __global__ __launch_bounds__(kTableThreads) void nmi_clahe_table_kernel(uint32_t
     for (uint32_t at = L / 4u + tid; at < (uint32_t)kToneLevels / 4u; at += kTableThreads) lut4[at] = fill;
     if (tid == 0) counts[tile] = n;
 }
-#endif  // !NMI_CLAHE_VALID
 
 namespace {
 
@@ -290,18 +264,16 @@ __device__ __forceinline__ uint32_t clahe_axis(uint32_t x, uint32_t tiles, uint3
 // loaded first (vec_in: 8-byte loads, every source row starting on an 8-byte boundary; otherwise, and for the last quad of a row
 // whose width is not a multiple of 4, 2-byte loads of just the pixels inside the frame), then taken column by column: a column's
 // tile pair and weight once, four gathers and the blend for each of its F pixels.  luts: [tiles_y][tiles_x][65536].
-// NMI_CLAHE_VALID: the lane also writes the quad of the validity mask, as nmi_gray16_masked_kernel does (write_valid_quad); vec_out
-// then also asks for 4-byte aligned masks.
-template <int F>
-__global__ __launch_bounds__(256) void NMI_CLAHE_GRAY16_KERNEL(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ luts,
+// Masked (Valid: uint32_t lo, uint32_t hi, const uint8_t *frame_mask, uint8_t *mask; else nothing): the lane also writes the quad
+// of the validity mask, as nmi_gray16_kernel<F, true> does (write_valid_quad); vec_out then also asks for 4-byte aligned masks.
+template <int F, bool Masked, class... Valid>
+__global__ __launch_bounds__(256) void nmi_clahe_gray16_kernel(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ luts,
                                                                uint32_t vmax, uint32_t tiles_x, uint32_t tiles_y, uint8_t *__restrict__ gray,
-#ifdef NMI_CLAHE_VALID
-                                                               int width, int height, int vec_in, int vec_out, int wide, uint32_t lo, uint32_t hi,
-                                                               const uint8_t *frame_mask, uint8_t *mask)
-#else
-                                                               int width, int height, int vec_in, int vec_out, int wide)
-#endif
+                                                               int width, int height, int vec_in, int vec_out, int wide,
+                                                               Valid... range_and_masks)
 {
+    static_assert(sizeof...(Valid) == (Masked ? 4 : 0), "MaskArgs<Masked>'s members");
+    const MaskArgs<Masked> valid{range_and_masks...};
     const int x0 = (blockIdx.x * 64 + (int)threadIdx.x) * 4;
     const int y = blockIdx.y * 4 + (int)threadIdx.y;
     if (x0 >= width || y >= height) return;
@@ -324,9 +296,7 @@ __global__ __launch_bounds__(256) void NMI_CLAHE_GRAY16_KERNEL(const uint8_t *__
 #pragma unroll
     for (int r = 0; r < F; ++r) rows[r] = clahe_axis((uint32_t)(y * F + r), tiles_y, (uint32_t)height * F, wide);
     uint32_t s[4] = {};
-#ifdef NMI_CLAHE_VALID
-    uint32_t bad = 0;  // bit k: a source pixel of output pixel k is outside the range
-#endif
+    [[maybe_unused]] uint32_t bad = 0;  // (Masked) bit k: a source pixel of output pixel k is outside the range
 #pragma unroll
     for (int i = 0; i < 4 * F; ++i) {
         if (i < n * F) {
@@ -334,11 +304,9 @@ __global__ __launch_bounds__(256) void NMI_CLAHE_GRAY16_KERNEL(const uint8_t *__
             const uint32_t i0 = cx & 255u, i1 = (cx >> 8) & 255u, wx = cx >> 16;
 #pragma unroll
             for (int r = 0; r < F; ++r) {
-                const uint32_t v = min((w[r][i / 2] >> (16 * (i % 2))) & 0xFFFFu, vmax);
-#ifdef NMI_CLAHE_VALID
                 const uint32_t raw = (w[r][i / 2] >> (16 * (i % 2))) & 0xFFFFu;
-                bad |= (uint32_t)(raw < lo || raw > hi) << (i / F);
-#endif
+                const uint32_t v = min(raw, vmax);
+                if constexpr (Masked) bad |= (uint32_t)(raw < valid.lo || raw > valid.hi) << (i / F);
                 const uint32_t j0 = rows[r] & 255u, j1 = (rows[r] >> 8) & 255u, wy = rows[r] >> 16;
                 const uint8_t *t0 = luts + ((size_t)(j0 * tiles_x) << 16) + v, *t1 = luts + ((size_t)(j1 * tiles_x) << 16) + v;
                 const uint32_t A = t0[(size_t)i0 << 16], B = t0[(size_t)i1 << 16], C = t1[(size_t)i0 << 16], D = t1[(size_t)i1 << 16];
@@ -356,13 +324,11 @@ __global__ __launch_bounds__(256) void NMI_CLAHE_GRAY16_KERNEL(const uint8_t *__
     } else {
         for (int k = 0; k < n; ++k) gray[o + k] = (uint8_t)(packed >> (8 * k));
     }
-#ifdef NMI_CLAHE_VALID
-    write_valid_quad(bad, frame_mask, mask, o, n, vec_out);
-#endif
+    if constexpr (Masked) write_valid_quad(bad, valid.frame_mask, valid.mask, o, n, vec_out);
 }
 
-#ifndef NMI_CLAHE_VALID
-hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, uint32_t *hist, hipStream_t stream)
+hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, const ValidRange &range,
+                             uint32_t *hist, hipStream_t stream)
 {
     const ClaheGrid g = clahe_grid(t.tiles_x, t.tiles_y, width, height);
     const int tiles = t.tiles_x * t.tiles_y;
@@ -371,8 +337,14 @@ hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t p
     const long long chunks = (widest * tallest + kHistChunk - 1) / kHistChunk, most = kHistMaxWorkgroups / tiles;
     const int per_tile = (int)(chunks < most ? chunks : most);
     const int passes = t.bits <= 14 ? 1 : t.bits == 15 ? 2 : 4;
-    hipLaunchKernelGGL(nmi_clahe_hist_kernel, dim3(per_tile, tiles), dim3(kHistThreads), 0, stream, src, (size_t)pitch, g, (1u << t.bits) - 1u,
-                       t.bits, passes, hist);
+    const uint32_t vmax = (1u << t.bits) - 1u;
+    if (range.on()) {
+        hipLaunchKernelGGL((nmi_clahe_hist_kernel<true, uint32_t, uint32_t>), dim3(per_tile, tiles), dim3(kHistThreads), 0, stream, src,
+                           (size_t)pitch, g, vmax, t.bits, passes, (uint32_t)range.lo, (uint32_t)range.hi, hist);
+    } else {
+        hipLaunchKernelGGL(nmi_clahe_hist_kernel<false>, dim3(per_tile, tiles), dim3(kHistThreads), 0, stream, src, (size_t)pitch, g, vmax, t.bits,
+                           passes, hist);
+    }
     return hipGetLastError();
 }
 
@@ -383,85 +355,23 @@ hipError_t launch_clahe_tables(const ToneSetting &t, uint32_t *hist, uint8_t *lu
     return hipGetLastError();
 }
 
-namespace {
-
-template <int F>
-void clahe_gray16_launch(const ToneSetting &t, const uint8_t *src, size_t pitch, const uint8_t *luts, uint8_t *gray, int width, int height,
-                         hipStream_t stream)
+hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, const ValidRange &range,
+                               const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
 {
-    const int quads = (width + 3) / 4;
-    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
-    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
-    const int vec_out = (width % 4) == 0 && ((uintptr_t)gray % 4) == 0;
-    const int wide = (long long)width * F >= (1 << 19) || (long long)height * F >= (1 << 19);  // 4352 * 2^19 < 2^32
-    hipLaunchKernelGGL(nmi_clahe_gray16_kernel<F>, grid, block, 0, stream, src, pitch, luts, (1u << t.bits) - 1u, (uint32_t)t.tiles_x,
-                       (uint32_t)t.tiles_y, gray, width, height, vec_in, vec_out, wide);
+    const uint32_t vmax = (1u << t.bits) - 1u, tx = (uint32_t)t.tiles_x, ty = (uint32_t)t.tiles_y;
+    const QuadLaunch q = quad_launch(src, pitch, frame_mask, gray, mask, width, height);
+    const uint32_t lo = (uint32_t)range.lo, hi = (uint32_t)range.hi;
+    return launch_for_factor(factor, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        const int wide = (long long)width * F >= (1 << 19) || (long long)height * F >= (1 << 19);  // 4352 * 2^19 < 2^32
+        if (mask) {
+            hipLaunchKernelGGL((nmi_clahe_gray16_kernel<F, true>), q.grid, q.block, 0, stream, src, (size_t)pitch, luts, vmax, tx, ty, gray, width,
+                               height, q.vec_in, q.vec_out, wide, lo, hi, frame_mask, mask);
+        } else {
+            hipLaunchKernelGGL((nmi_clahe_gray16_kernel<F, false>), q.grid, q.block, 0, stream, src, (size_t)pitch, luts, vmax, tx, ty, gray, width,
+                               height, q.vec_in, q.vec_out, wide);
+        }
+    });
 }
-
-}  // namespace
-
-hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, uint8_t *gray,
-                               int width, int height, hipStream_t stream)
-{
-    switch (factor) {
-    case 1: clahe_gray16_launch<1>(t, src, (size_t)pitch, luts, gray, width, height, stream); break;
-    case 2: clahe_gray16_launch<2>(t, src, (size_t)pitch, luts, gray, width, height, stream); break;
-    case 3: clahe_gray16_launch<3>(t, src, (size_t)pitch, luts, gray, width, height, stream); break;
-    case 4: clahe_gray16_launch<4>(t, src, (size_t)pitch, luts, gray, width, height, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-#else  // NMI_CLAHE_VALID
-
-hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, const ValidRange &range,
-                             uint32_t *hist, hipStream_t stream)
-{
-    if (!range.on()) return launch_clahe_hist(t, src, pitch, width, height, hist, stream);
-    const ClaheGrid g = clahe_grid(t.tiles_x, t.tiles_y, width, height);
-    const int tiles = t.tiles_x * t.tiles_y;
-    // (launch_clahe_hist's grid)
-    const long long widest = (long long)(width + t.tiles_x - 1) / t.tiles_x + 1, tallest = (long long)(height + t.tiles_y - 1) / t.tiles_y + 1;
-    const long long chunks = (widest * tallest + kHistChunk - 1) / kHistChunk, most = kHistMaxWorkgroups / tiles;
-    const int per_tile = (int)(chunks < most ? chunks : most);
-    const int passes = t.bits <= 14 ? 1 : t.bits == 15 ? 2 : 4;
-    hipLaunchKernelGGL(nmi_clahe_hist_ranged_kernel, dim3(per_tile, tiles), dim3(kHistThreads), 0, stream, src, (size_t)pitch, g,
-                       (1u << t.bits) - 1u, t.bits, passes, (uint32_t)range.lo, (uint32_t)range.hi, hist);
-    return hipGetLastError();
-}
-
-namespace {
-
-template <int F>
-void clahe_gray16_masked_launch(const ToneSetting &t, const uint8_t *src, size_t pitch, const uint8_t *luts, const ValidRange &range,
-                                const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
-{
-    const int quads = (width + 3) / 4;
-    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
-    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
-    const int vec_out = (width % 4) == 0 && (((uintptr_t)gray | (uintptr_t)mask | (uintptr_t)frame_mask) % 4) == 0;
-    const int wide = (long long)width * F >= (1 << 19) || (long long)height * F >= (1 << 19);  // 4352 * 2^19 < 2^32
-    hipLaunchKernelGGL(nmi_clahe_gray16_masked_kernel<F>, grid, block, 0, stream, src, pitch, luts, (1u << t.bits) - 1u, (uint32_t)t.tiles_x,
-                       (uint32_t)t.tiles_y, gray, width, height, vec_in, vec_out, wide, (uint32_t)range.lo, (uint32_t)range.hi, frame_mask, mask);
-}
-
-}  // namespace
-
-hipError_t launch_clahe_gray16_masked(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts,
-                                      const ValidRange &range, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height,
-                                      hipStream_t stream)
-{
-    switch (factor) {
-    case 1: clahe_gray16_masked_launch<1>(t, src, (size_t)pitch, luts, range, frame_mask, gray, mask, width, height, stream); break;
-    case 2: clahe_gray16_masked_launch<2>(t, src, (size_t)pitch, luts, range, frame_mask, gray, mask, width, height, stream); break;
-    case 3: clahe_gray16_masked_launch<3>(t, src, (size_t)pitch, luts, range, frame_mask, gray, mask, width, height, stream); break;
-    case 4: clahe_gray16_masked_launch<4>(t, src, (size_t)pitch, luts, range, frame_mask, gray, mask, width, height, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-#endif  // NMI_CLAHE_VALID
 
 }  // namespace nmi

@@ -56,4 +56,24 @@ inline bool frame_base_ok(int32_t format, const void *src) { return !nmi::frame_
 // else NMI_ERR_INVALID_ARGUMENT.  width and height are the source's.
 int frame_format_check(int32_t format, int64_t pitch, int width, int height, int64_t *row_bytes, bool *identity);
 
+// The bytes [lo, hi) of a device buffer; lo == hi: nothing, which is what a NULL buffer comes to.  Two buffers an entry may not
+// see overlap `meet`; nothing meets nothing.
+struct Span {
+    uintptr_t lo, hi;
+};
+inline Span span_of(const void *p, size_t bytes) { return {(uintptr_t)p, (uintptr_t)p + (p ? bytes : 0)}; }
+inline bool meet(const Span &a, const Span &b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
+
+// The full-size source of an entry that converts factor * width x factor * height pixels at d_src to width x height.
+struct FrameSource {
+    int width = 0, height = 0;  // the full size
+    int64_t row_bytes = 0;      // the rows' pitch (frame_format_check's)
+    bool identity = false;      // frame_format_check's
+    Span bytes{0, 0};           // from d_src to the end of its last row's pixels; nothing for a NULL d_src
+};
+
+// factor 1 .. 4, the full size fits int, frame_format_check on it, and d_src aligned as format asks (frame_base_ok; NULL, a
+// setting checked ahead of its frames, passes) -> NMI_OK and *out; else NMI_ERR_INVALID_ARGUMENT, *out untouched.
+int frame_source_check(int32_t format, int64_t pitch, int32_t factor, int width, int height, const void *d_src, FrameSource *out);
+
 }  // namespace nmi_internal

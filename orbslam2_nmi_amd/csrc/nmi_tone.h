@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "nmi_hip.h"
 #include "nmi_mem.h"
 
@@ -37,18 +39,17 @@ struct ToneSetting {
 };
 
 // The valid range of a GRAY16 source (nmi_set_valid_range): a pixel counts in the statistics, and is 1 in the validity mask,
-// iff lo <= raw <= hi, raw being the container's value before it saturates to 2^bits - 1.  (0, 65535): off, and every launch below
-// that takes a range is then the one without.
+// iff lo <= raw <= hi, raw being the container's value before it saturates to 2^bits - 1.  (0, 65535): off, and the histogram
+// launches below then launch the plain instantiation of their kernel.
 struct ValidRange {
     int32_t lo = 0, hi = 65535;
     bool on() const { return lo != 0 || hi != 65535; }
     bool operator==(const ValidRange &o) const { return lo == o.lo && hi == o.hi; }
 };
 
-// hist[v] += the number of pixels with min(raw, 2^bits - 1) == v among the height rows of pitch bytes at src, each width
-// little-endian 16-bit pixels (src and pitch even).  Exact for any content; hist is uint32 [kToneLevels].
-hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, uint32_t *hist, hipStream_t stream);
-// ... counting the pixels inside `range` only (a kernel of its own; range off: the launch above).
+// hist[v] += the number of pixels with min(raw, 2^bits - 1) == v and raw inside `range` among the height rows of pitch bytes at
+// src, each width little-endian 16-bit pixels (src and pitch even).  Exact for any content; hist is uint32 [kToneLevels].  The
+// ranged count is an instantiation of its own of the kernel, so range off launches what it did before the range existed.
 hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, const ValidRange &range, uint32_t *hist,
                             hipStream_t stream);
 
@@ -61,12 +62,42 @@ hipError_t launch_tone_table(const ToneSetting &t, uint32_t *hist, uint8_t *lut,
 // nmi_gray_frame (factor 1) and nmi_reduce_frame (factor 2 .. 4) of a GRAY16 source of factor * height rows of pitch bytes,
 // each factor * width pixels: lut[min(raw, 2^bits - 1)] per source pixel, then the rounded box average (nmi_reduce_device.h).
 // lut is the table of launch_tone_table, or a TABLE setting's own.
-hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, uint8_t *gray, int width, int height,
-                         hipStream_t stream);
-// ... and, from the same kernel (one of its own), the validity mask: mask[y][x] = 1 iff all factor x factor source pixels under
-// (x, y) are inside `range` and frame_mask[y][x] != 0 (frame_mask: dense [height][width], may be null, may be `mask` itself).
-hipError_t launch_gray16_masked(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
-                                const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream);
+// mask (may be null): the masked instantiation of the kernel, which also writes the validity mask: mask[y][x] = 1 iff all factor x
+// factor source pixels under (x, y) are inside `range` and frame_mask[y][x] != 0 (frame_mask: dense [height][width], may be null,
+// may be `mask` itself).  Without a mask neither `range` nor frame_mask is read.
+hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
+                         const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream);
+
+// The launch geometry of the two conversions (launch_gray16, launch_clahe_gray16): a lane makes a quad of 4 adjacent grey pixels,
+// a workgroup 64 quads of each of 4 rows.  vec_in: every source row starts on an 8-byte boundary (base and pitch); vec_out: width
+// % 4 == 0 and the grey frame -- with a mask, the mask pair too -- 4-byte aligned.
+struct QuadLaunch {
+    dim3 grid, block;
+    int vec_in, vec_out;
+};
+inline QuadLaunch quad_launch(const uint8_t *src, int64_t pitch, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height)
+{
+    const int quads = (width + 3) / 4;
+    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
+    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
+    const uintptr_t masks = mask ? (uintptr_t)mask | (uintptr_t)frame_mask : 0;
+    const int vec_out = (width % 4) == 0 && (((uintptr_t)gray | masks) % 4) == 0;
+    return {grid, block, vec_in, vec_out};
+}
+
+// launch(std::integral_constant<int, factor>{}) for a factor of 1 .. 4, then hipGetLastError(); hipErrorInvalidValue for any other.
+template <class Launch>
+hipError_t launch_for_factor(int factor, Launch &&launch)
+{
+    switch (factor) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 // --- CLAHE (nmi_clahe.hip; the rule: include/nmi_hip.h "Deep frames") ---------------------------------------------------------
 constexpr int kClaheMaxTiles = 8;                                  // per axis
@@ -76,10 +107,9 @@ constexpr int kClaheMaxTileCount = kClaheMaxTiles * kClaheMaxTiles;
 inline size_t clahe_hist_bytes(const ToneSetting &t) { return ((size_t)t.tiles_x * t.tiles_y << t.bits) * sizeof(uint32_t); }
 inline size_t clahe_luts_bytes(const ToneSetting &t) { return (size_t)t.tiles_x * t.tiles_y * kToneLevels; }
 
-// hist[tile][v] += the number of pixels with min(raw, 2^bits - 1) == v in each tile of the tiles_x x tiles_y grid over the
-// width x height source (rows of pitch bytes; src and pitch even; tiles_x <= width, tiles_y <= height).  Exact for any content.
-hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, uint32_t *hist, hipStream_t stream);
-// ... counting the pixels inside `range` only (a kernel of its own; range off: the launch above).
+// hist[tile][v] += the number of pixels with min(raw, 2^bits - 1) == v and raw inside `range` in each tile of the tiles_x x tiles_y
+// grid over the width x height source (rows of pitch bytes; src and pitch even; tiles_x <= width, tiles_y <= height).  Exact for
+// any content.  Ranged and plain: as launch_tone_hist.
 hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t pitch, int width, int height, const ValidRange &range,
                              uint32_t *hist, hipStream_t stream);
 
@@ -88,13 +118,9 @@ hipError_t launch_clahe_hist(const ToneSetting &t, const uint8_t *src, int64_t p
 hipError_t launch_clahe_tables(const ToneSetting &t, uint32_t *hist, uint8_t *luts, uint32_t *counts, hipStream_t stream);
 
 // launch_gray16 under CLAHE: the blend of the four nearest tiles' tables per source pixel of the factor * width x factor * height
-// source, then the rounded box average.
-hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, uint8_t *gray,
-                               int width, int height, hipStream_t stream);
-// ... and the validity mask, as launch_gray16_masked.
-hipError_t launch_clahe_gray16_masked(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts,
-                                      const ValidRange &range, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height,
-                                      hipStream_t stream);
+// source, then the rounded box average; with a mask, the validity mask as there.
+hipError_t launch_clahe_gray16(const ToneSetting &t, const uint8_t *src, int64_t pitch, int factor, const uint8_t *luts, const ValidRange &range,
+                               const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream);
 
 }  // namespace nmi
 

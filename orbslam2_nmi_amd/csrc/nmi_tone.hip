@@ -6,10 +6,10 @@
 //   nmi_gray16_kernel       table[min(raw, M)] per source pixel, then the rounded F x F box average (F = 1: the value itself)
 // All arithmetic is integer (the one fp64 quotient is corrected to the exact floor), so tests/helpers/tone_np.py equals it bit
 // for bit.
-// With a valid range (nmi_set_valid_range) the histogram and the conversion are kernels of their own, compiled from this file's
-// kernel text once more (nmi_tone_valid.hip defines NMI_TONE_VALID and includes this file, as the nmi_kernels_* wrappers include
-// nmi_kernels.hip): nmi_tone_hist_ranged_kernel counts the pixels with lo <= raw <= hi only, nmi_gray16_masked_kernel also writes
-// the validity mask.  The kernels of this unit are what they were before the range existed, instruction for instruction.
+// With a valid range (nmi_set_valid_range) the histogram and the conversion are instantiations of their own of the same kernel
+// templates: nmi_tone_hist_kernel<true> counts the pixels with lo <= raw <= hi only, nmi_gray16_kernel<F, true> also writes the
+// validity mask.  What the range adds stands under `if constexpr`, and the plain instantiations are what they were before the range
+// existed, instruction for instruction (profiles/deep_templates/isa_vs_parent.txt).
 //
 // The histogram counts in a per-workgroup uint32 LDS histogram of 16384 bins (64 KiB; a count cannot wrap, a frame has fewer
 // than 2^32 pixels) and adds its nonzero bins to the global one.  LDS atomics on one address cost a wave some 64 LDS cycles,
@@ -24,14 +24,6 @@
 #include "nmi_tone.h"
 #include "nmi_tone_device.h"
 #include "nmi_reduce_device.h"
-
-#ifdef NMI_TONE_VALID
-#define NMI_TONE_HIST_KERNEL nmi_tone_hist_ranged_kernel
-#define NMI_GRAY16_KERNEL nmi_gray16_masked_kernel
-#else
-#define NMI_TONE_HIST_KERNEL nmi_tone_hist_kernel
-#define NMI_GRAY16_KERNEL nmi_gray16_kernel
-#endif
 
 namespace nmi {
 
@@ -61,15 +53,15 @@ __device__ __forceinline__ uint32_t tone_window(uint32_t v, uint32_t lo, uint32_
 // lane loads its two runs once and keeps them in registers over the passes.  vec: every row starts on a 16-byte boundary (base
 // and pitch), so a whole run comes in one load; otherwise, and for the last run of a row whose width is not a multiple of 8,
 // 2-byte loads of just the pixels inside the frame.  The flush clears the bins it adds to the global histogram.
-// NMI_TONE_VALID: a pixel is counted (and seen, for the quarters) iff it is inside the frame and lo <= raw <= hi, tested on the
-// raw half-word before the saturation: bit k of ok[r].
-__global__ __launch_bounds__(kHistThreads) void NMI_TONE_HIST_KERNEL(const uint8_t *__restrict__ src, size_t pitch, int width, int height,
-                                                                     uint32_t vmax, int passes, int vec,
-#ifdef NMI_TONE_VALID
-                                                                     uint32_t lo, uint32_t hi,
-#endif
+// Ranged (Range: uint32_t lo, uint32_t hi; else nothing): a pixel is counted (and seen, for the quarters) iff it is inside the
+// frame and lo <= raw <= hi, tested on the raw half-word before the saturation: bit k of ok[r].
+template <bool Ranged, class... Range>
+__global__ __launch_bounds__(kHistThreads) void nmi_tone_hist_kernel(const uint8_t *__restrict__ src, size_t pitch, int width, int height,
+                                                                     uint32_t vmax, int passes, int vec, Range... lo_hi,
                                                                      uint32_t *__restrict__ hist)
 {
+    static_assert(sizeof...(Range) == (Ranged ? 2 : 0), "RangeArgs<Ranged>'s members");
+    const RangeArgs<Ranged> range{lo_hi...};
     __shared__ uint4 bins4[kHistBins / 4];
     __shared__ uint32_t quarters;  // bit q: a pixel of this chunk has v >> 14 == q
     uint32_t *bins = reinterpret_cast<uint32_t *>(bins4);
@@ -82,9 +74,7 @@ __global__ __launch_bounds__(kHistThreads) void NMI_TONE_HIST_KERNEL(const uint8
         uint32_t w[kHistRunsPerLane][kHistRun / 2];  // pixel k of run r is half k % 2 of word k / 2
         int n[kHistRunsPerLane];
         uint32_t seen = 0;
-#ifdef NMI_TONE_VALID
-        uint32_t ok[kHistRunsPerLane] = {};
-#endif
+        [[maybe_unused]] uint32_t ok[kHistRunsPerLane] = {};  // (Ranged)
 #pragma unroll
         for (int r = 0; r < kHistRunsPerLane; ++r) {
             const uint32_t item = first + (blockIdx.x * kHistRunsPerLane + r) * kHistThreads + tid;
@@ -109,25 +99,19 @@ __global__ __launch_bounds__(kHistThreads) void NMI_TONE_HIST_KERNEL(const uint8
         for (int r = 0; r < kHistRunsPerLane; ++r) {
 #pragma unroll
             for (int k = 0; k < kHistRun; ++k) {  // saturate in place
-#ifdef NMI_TONE_VALID
                 const uint32_t raw = (w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu;
                 const uint32_t v = min(raw, vmax);
                 w[r][k / 2] = (w[r][k / 2] & ~(0xFFFFu << (16 * (k % 2)))) | (v << (16 * (k % 2)));
-                if (k < n[r] && raw >= lo && raw <= hi) ok[r] |= 1u << k, seen |= 1u << (v >> 14);
-#else
-                const uint32_t v = min((w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu, vmax);
-                w[r][k / 2] = (w[r][k / 2] & ~(0xFFFFu << (16 * (k % 2)))) | (v << (16 * (k % 2)));
-                if (k < n[r]) seen |= 1u << (v >> 14);
-#endif
+                if constexpr (Ranged) {
+                    if (k < n[r] && raw >= range.lo && raw <= range.hi) ok[r] |= 1u << k, seen |= 1u << (v >> 14);
+                } else {
+                    if (k < n[r]) seen |= 1u << (v >> 14);
+                }
             }
         }
         uint32_t present = 1u;
         if (passes > 1) {
-            if (tid == 0) quarters = 0u;
-            __syncthreads();
-            if (seen) atomicOr(&quarters, seen);
-            __syncthreads();
-            present = quarters;
+            present = quarters_present(&quarters, seen, tid);
         } else {
             __syncthreads();  // (the bins are clear: the first zeroing, or the flush of the chunk before)
         }
@@ -138,33 +122,23 @@ __global__ __launch_bounds__(kHistThreads) void NMI_TONE_HIST_KERNEL(const uint8
 #pragma unroll
                 for (int k = 0; k < kHistRun; ++k) {
                     const uint32_t v = (w[r][k / 2] >> (16 * (k % 2))) & 0xFFFFu;
-#ifdef NMI_TONE_VALID
-                    if (((ok[r] >> k) & 1u) && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
-#else
-                    if (k < n[r] && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
-#endif
+                    if constexpr (Ranged) {
+                        if (((ok[r] >> k) & 1u) && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
+                    } else {
+                        if (k < n[r] && (v >> 14) == (uint32_t)pass) atomicAdd(&bins[v & (kHistBins - 1)], 1u);
+                    }
                 }
             }
             __syncthreads();
             uint32_t *out = hist + pass * kHistBins;  // (index < passes * 16384 <= 65536)
 #pragma unroll 4
-            for (int i = tid; i < kHistBins / 4; i += kHistThreads) {
-                const uint4 c = bins4[i];
-                if (c.x | c.y | c.z | c.w) {
-                    bins4[i] = make_uint4(0u, 0u, 0u, 0u);
-                    if (c.x) atomicAdd(&out[4 * i], c.x);
-                    if (c.y) atomicAdd(&out[4 * i + 1], c.y);
-                    if (c.z) atomicAdd(&out[4 * i + 2], c.z);
-                    if (c.w) atomicAdd(&out[4 * i + 3], c.w);
-                }
-            }
+            for (int i = tid; i < kHistBins / 4; i += kHistThreads) flush_bins_quad(bins4, out, i);
             __syncthreads();
         }
         __syncthreads();  // (quarters is read by all before the next chunk resets it)
     }
 }
 
-#ifndef NMI_TONE_VALID
 // The histogram's way to the table, in two kernels of 64 workgroups x 256 lanes; workgroup p has the segment of 1024 levels
 // [1024 p, 1024 p + 1024), lane t four of them.  (One workgroup doing all of it takes 25 .. 43 us: a single CU's loads of the
 // 256 KiB the atomics left in memory, profiles/deep/README.md.)
@@ -331,48 +305,40 @@ __global__ __launch_bounds__(kSegThreads) void nmi_tone_table_kernel(ToneSetting
     }
     if (p == 0 && tid == 0 && window) window[0] = (int32_t)lo, window[1] = (int32_t)hi;
 }
-#endif  // !NMI_TONE_VALID
 
 // A lane makes 4 adjacent grey pixels of one output row from 4 F pixels of each of its F source rows.  vec_in: every source
 // row starts on an 8-byte boundary (base and pitch), so a row's 8 F bytes come in F 8-byte loads; otherwise, and for the last
 // quad of a row whose width is not a multiple of 4, 2-byte loads of just the pixels inside the frame.  vec_out: width % 4 == 0
 // and gray 4-byte aligned, one dword store; otherwise byte stores.
-// NMI_TONE_VALID: the lane also writes the quad of the validity mask, from the raw values it holds: mask pixel k is 1 iff each of
-// its F x F source pixels has lo <= raw <= hi and, with a frame mask, frame_mask's byte there is nonzero (write_valid_quad; the
-// two may be one buffer).  vec_out then also asks for 4-byte aligned masks.
-template <int F>
-__global__ __launch_bounds__(256) void NMI_GRAY16_KERNEL(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ lut,
+// Masked (Valid: uint32_t lo, uint32_t hi, const uint8_t *frame_mask, uint8_t *mask; else nothing): the lane also writes the quad
+// of the validity mask, from the raw values it holds: mask pixel k is 1 iff each of its F x F source pixels has lo <= raw <= hi
+// and, with a frame mask, frame_mask's byte there is nonzero (write_valid_quad; the two may be one buffer).  vec_out then also
+// asks for 4-byte aligned masks.
+template <int F, bool Masked, class... Valid>
+__global__ __launch_bounds__(256) void nmi_gray16_kernel(const uint8_t *__restrict__ src, size_t pitch, const uint8_t *__restrict__ lut,
                                                          uint32_t vmax, uint8_t *__restrict__ gray, int width, int height, int vec_in,
-#ifdef NMI_TONE_VALID
-                                                         int vec_out, uint32_t lo, uint32_t hi, const uint8_t *frame_mask, uint8_t *mask)
-#else
-                                                         int vec_out)
-#endif
+                                                         int vec_out, Valid... range_and_masks)
 {
+    static_assert(sizeof...(Valid) == (Masked ? 4 : 0), "MaskArgs<Masked>'s members");
+    const MaskArgs<Masked> valid{range_and_masks...};
     const int x0 = (blockIdx.x * 64 + (int)threadIdx.x) * 4;
     const int y = blockIdx.y * 4 + (int)threadIdx.y;
     if (x0 >= width || y >= height) return;
     const int n = min(4, width - x0);
     const uint8_t *row = src + (size_t)y * F * pitch + (size_t)x0 * (F * 2);
     uint32_t s[4] = {};
-#ifdef NMI_TONE_VALID
-    uint32_t bad = 0;  // bit k: a source pixel of output pixel k is outside the range
-#endif
+    [[maybe_unused]] uint32_t bad = 0;  // (Masked) bit k: a source pixel of output pixel k is outside the range
     if (vec_in && n == 4) {
 #pragma unroll
         for (int r = 0; r < F; ++r) {
             uint32_t w[2 * F];  // source pixel i of the row is half i % 2 of word i / 2
             __builtin_memcpy(w, __builtin_assume_aligned(row + (size_t)r * pitch, 8), 8 * F);
 #pragma unroll
-#ifdef NMI_TONE_VALID
             for (int i = 0; i < 4 * F; ++i) {
                 const uint32_t raw = (w[i / 2] >> (16 * (i % 2))) & 0xFFFFu;
                 s[i / F] += lut[min(raw, vmax)];
-                bad |= (uint32_t)(raw < lo || raw > hi) << (i / F);
+                if constexpr (Masked) bad |= (uint32_t)(raw < valid.lo || raw > valid.hi) << (i / F);
             }
-#else
-            for (int i = 0; i < 4 * F; ++i) s[i / F] += lut[min((w[i / 2] >> (16 * (i % 2))) & 0xFFFFu, vmax)];
-#endif
         }
     } else {
 #pragma unroll
@@ -382,15 +348,11 @@ __global__ __launch_bounds__(256) void NMI_GRAY16_KERNEL(const uint8_t *__restri
                 for (int r = 0; r < F; ++r) {
                     const uint16_t *p16 = reinterpret_cast<const uint16_t *>(row + (size_t)r * pitch) + k * F;
 #pragma unroll
-#ifdef NMI_TONE_VALID
                     for (int j = 0; j < F; ++j) {
                         const uint32_t raw = p16[j];
                         s[k] += lut[min(raw, vmax)];
-                        bad |= (uint32_t)(raw < lo || raw > hi) << k;
+                        if constexpr (Masked) bad |= (uint32_t)(raw < valid.lo || raw > valid.hi) << k;
                     }
-#else
-                    for (int j = 0; j < F; ++j) s[k] += lut[min((uint32_t)p16[j], vmax)];
-#endif
                 }
             }
         }
@@ -404,21 +366,25 @@ __global__ __launch_bounds__(256) void NMI_GRAY16_KERNEL(const uint8_t *__restri
     } else {
         for (int k = 0; k < n; ++k) gray[o + k] = (uint8_t)(packed >> (8 * k));
     }
-#ifdef NMI_TONE_VALID
-    write_valid_quad(bad, frame_mask, mask, o, n, vec_out);
-#endif
+    if constexpr (Masked) write_valid_quad(bad, valid.frame_mask, valid.mask, o, n, vec_out);
 }
 
-#ifndef NMI_TONE_VALID
-hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, uint32_t *hist, hipStream_t stream)
+hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, const ValidRange &range, uint32_t *hist,
+                            hipStream_t stream)
 {
     const long long items = (long long)((width + kHistRun - 1) / kHistRun) * height, per = kHistThreads * kHistRunsPerLane;
     const long long want = (items + per - 1) / per;  // one chunk per workgroup up to 2M pixels
     const int workgroups = (int)(want < 1 ? 1 : want > kHistMaxWorkgroups ? kHistMaxWorkgroups : want);
     const int passes = bits <= 14 ? 1 : bits == 15 ? 2 : 4;
     const int vec = ((uintptr_t)src % 16) == 0 && (pitch % 16) == 0;
-    hipLaunchKernelGGL(nmi_tone_hist_kernel, dim3(workgroups), dim3(kHistThreads), 0, stream, src, (size_t)pitch, width, height,
-                       (1u << bits) - 1u, passes, vec, hist);
+    const uint32_t vmax = (1u << bits) - 1u;
+    if (range.on()) {
+        hipLaunchKernelGGL((nmi_tone_hist_kernel<true, uint32_t, uint32_t>), dim3(workgroups), dim3(kHistThreads), 0, stream, src, (size_t)pitch,
+                           width, height, vmax, passes, vec, (uint32_t)range.lo, (uint32_t)range.hi, hist);
+    } else {
+        hipLaunchKernelGGL(nmi_tone_hist_kernel<false>, dim3(workgroups), dim3(kHistThreads), 0, stream, src, (size_t)pitch, width, height, vmax,
+                           passes, vec, hist);
+    }
     return hipGetLastError();
 }
 
@@ -434,80 +400,22 @@ hipError_t launch_tone_table(const ToneSetting &t, uint32_t *hist, uint8_t *lut,
     return hipGetLastError();
 }
 
-namespace {
-
-template <int F>
-void gray16_launch(const uint8_t *src, size_t pitch, const uint8_t *lut, uint32_t vmax, uint8_t *gray, int width, int height, hipStream_t stream)
-{
-    const int quads = (width + 3) / 4;
-    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
-    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
-    const int vec_out = (width % 4) == 0 && ((uintptr_t)gray % 4) == 0;
-    hipLaunchKernelGGL(nmi_gray16_kernel<F>, grid, block, 0, stream, src, pitch, lut, vmax, gray, width, height, vec_in, vec_out);
-}
-
-}  // namespace
-
-hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, uint8_t *gray, int width, int height,
-                         hipStream_t stream)
+hipError_t launch_gray16(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
+                         const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
 {
     const uint32_t vmax = (1u << bits) - 1u;
-    switch (factor) {
-    case 1: gray16_launch<1>(src, (size_t)pitch, lut, vmax, gray, width, height, stream); break;
-    case 2: gray16_launch<2>(src, (size_t)pitch, lut, vmax, gray, width, height, stream); break;
-    case 3: gray16_launch<3>(src, (size_t)pitch, lut, vmax, gray, width, height, stream); break;
-    case 4: gray16_launch<4>(src, (size_t)pitch, lut, vmax, gray, width, height, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const QuadLaunch q = quad_launch(src, pitch, frame_mask, gray, mask, width, height);
+    const uint32_t lo = (uint32_t)range.lo, hi = (uint32_t)range.hi;
+    return launch_for_factor(factor, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        if (mask) {
+            hipLaunchKernelGGL((nmi_gray16_kernel<F, true>), q.grid, q.block, 0, stream, src, (size_t)pitch, lut, vmax, gray, width, height,
+                               q.vec_in, q.vec_out, lo, hi, frame_mask, mask);
+        } else {
+            hipLaunchKernelGGL((nmi_gray16_kernel<F, false>), q.grid, q.block, 0, stream, src, (size_t)pitch, lut, vmax, gray, width, height,
+                               q.vec_in, q.vec_out);
+        }
+    });
 }
-
-#else  // NMI_TONE_VALID
-
-hipError_t launch_tone_hist(const uint8_t *src, int64_t pitch, int width, int height, int bits, const ValidRange &range, uint32_t *hist,
-                            hipStream_t stream)
-{
-    if (!range.on()) return launch_tone_hist(src, pitch, width, height, bits, hist, stream);
-    const long long items = (long long)((width + kHistRun - 1) / kHistRun) * height, per = kHistThreads * kHistRunsPerLane;
-    const long long want = (items + per - 1) / per;  // (launch_tone_hist's grid)
-    const int workgroups = (int)(want < 1 ? 1 : want > kHistMaxWorkgroups ? kHistMaxWorkgroups : want);
-    const int passes = bits <= 14 ? 1 : bits == 15 ? 2 : 4;
-    const int vec = ((uintptr_t)src % 16) == 0 && (pitch % 16) == 0;
-    hipLaunchKernelGGL(nmi_tone_hist_ranged_kernel, dim3(workgroups), dim3(kHistThreads), 0, stream, src, (size_t)pitch, width, height,
-                       (1u << bits) - 1u, passes, vec, (uint32_t)range.lo, (uint32_t)range.hi, hist);
-    return hipGetLastError();
-}
-
-namespace {
-
-template <int F>
-void gray16_masked_launch(const uint8_t *src, size_t pitch, const uint8_t *lut, uint32_t vmax, const ValidRange &range, const uint8_t *frame_mask,
-                          uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
-{
-    const int quads = (width + 3) / 4;
-    const dim3 grid((quads + 63) / 64, (height + 3) / 4), block(64, 4);
-    const int vec_in = ((uintptr_t)src % 8) == 0 && (pitch % 8) == 0;
-    const int vec_out = (width % 4) == 0 && (((uintptr_t)gray | (uintptr_t)mask | (uintptr_t)frame_mask) % 4) == 0;
-    hipLaunchKernelGGL(nmi_gray16_masked_kernel<F>, grid, block, 0, stream, src, pitch, lut, vmax, gray, width, height, vec_in, vec_out,
-                       (uint32_t)range.lo, (uint32_t)range.hi, frame_mask, mask);
-}
-
-}  // namespace
-
-hipError_t launch_gray16_masked(const uint8_t *src, int64_t pitch, int factor, const uint8_t *lut, int bits, const ValidRange &range,
-                                const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask, int width, int height, hipStream_t stream)
-{
-    const uint32_t vmax = (1u << bits) - 1u;
-    switch (factor) {
-    case 1: gray16_masked_launch<1>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
-    case 2: gray16_masked_launch<2>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
-    case 3: gray16_masked_launch<3>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
-    case 4: gray16_masked_launch<4>(src, (size_t)pitch, lut, vmax, range, frame_mask, gray, mask, width, height, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-#endif  // NMI_TONE_VALID
 
 }  // namespace nmi

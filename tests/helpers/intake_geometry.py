@@ -1,5 +1,5 @@
-"""Python mirror of the launch geometry of the deep intake's kernels (nmi_unpack.hip, nmi_tone.hip, nmi_clahe.hip and their
-valid-range twins) -- TEST INFRASTRUCTURE ONLY.
+"""Python mirror of the launch geometry of the deep intake's kernels (nmi_unpack.hip, nmi_tone.hip, nmi_clahe.hip, plain and
+valid-range instantiations alike) -- TEST INFRASTRUCTURE ONLY.
 
 Which lane, block column, chunk and trip of a loop a pixel falls to decides which branch of a kernel a test runs.  The tests of
 tests/test_packed_seams.py, tests/test_valid_seams.py and the second-trip cases choose their sizes by these functions, and

@@ -46,14 +46,22 @@ def test_the_unpack_constants_are_the_kernels():
     assert vec and [int(g) for g in vec.groups()] == [16, 8, 8, 4]
 
 
+GRID = r"const int quads = \(width \+ (\d+)\) / (\d+);\s*const dim3 grid\(\(quads \+ (\d+)\) / (\d+), \(height \+ 3\) / 4\), block\((\d+), 4\);"
+
+
 @pytest.mark.parametrize("name,own", [("nmi_tone.hip", "nmi_gray16"), ("nmi_clahe.hip", "nmi_clahe_gray16")])
 def test_the_conversion_constants_are_the_kernels(name, own):
     text = source(name)
     x0 = re.findall(r"const int x0 = \(blockIdx\.x \* (\d+) \+ \(int\)threadIdx\.x\) \* (\d+);", text)
-    assert x0 == [(str(geo.kBlockRowLanes), str(geo.kQuad))], x0            # (one kernel text, compiled twice)
-    grids = re.findall(r"const int quads = \(width \+ (\d+)\) / (\d+);\s*const dim3 grid\(\(quads \+ (\d+)\) / (\d+), \(height \+ 3\) / 4\), block\((\d+), 4\);", text)
+    assert x0 == [(str(geo.kBlockRowLanes), str(geo.kQuad))], x0            # (one kernel template, plain and masked)
+    # the launch grid: defined once, in nmi_tone.h's quad_launch; each file launches both instantiations by it and has none of its own
+    grids = re.findall(GRID, source("nmi_tone.h"))
     want = tuple(str(v) for v in (geo.kQuad - 1, geo.kQuad, geo.kBlockRowLanes - 1, geo.kBlockRowLanes, geo.kBlockRowLanes))
-    assert grids == [want, want], grids                                     # the plain and the masked launcher
+    assert grids == [want], grids
+    assert len(re.findall(r"const QuadLaunch q = quad_launch\(", text)) == 1
+    launches = re.findall(own + r"_kernel<F, (true|false)>\), q\.grid, q\.block,", text)
+    assert sorted(launches) == ["false", "true"], launches
+    assert not re.search(r"int quads\b|dim3 grid\(|block\(\d+|<<<", text), "a grid of the file's own"
 
 
 def test_the_histogram_constants_are_the_kernels():
@@ -68,10 +76,11 @@ def test_the_histogram_constants_are_the_kernels():
     assert re.search(r"const uint32_t chunk = gridDim\.x \* \(uint32_t\)\(kHistThreads \* kHistRunsPerLane\);", tone)
     assert re.search(r"for \(uint32_t first = 0; first < items; first \+= chunk\)", tone)
     assert re.search(r"first = \(uint64_t\)blockIdx\.x \* kHistChunk; first < n; first \+= \(uint64_t\)gridDim\.x \* kHistChunk", clahe)
-    # the valid-range twins are these files compiled once more, not kernels with constants of their own
-    for twin, parent in (("nmi_tone_valid.hip", "nmi_tone.hip"), ("nmi_clahe_valid.hip", "nmi_clahe.hip")):
-        text = source(twin)
-        assert f'#include "{parent}"' in text and "constexpr" not in text
+    # the ranged kernels are instantiations of these templates, not units of their own with constants of their own
+    for twin in ("nmi_tone_valid.hip", "nmi_clahe_valid.hip"):
+        assert not os.path.exists(os.path.join(CSRC, twin)), twin
+    assert len(re.findall(r"template <bool Ranged, class\.\.\. Range>\s*__global__ __launch_bounds__\(kHistThreads\) void nmi_tone_hist_kernel\(", tone)) == 1
+    assert len(re.findall(r"template <bool Ranged, class\.\.\. Range>\s*__global__ __launch_bounds__\(kHistThreads\) void nmi_clahe_hist_kernel\(", clahe)) == 1
 
 
 @pytest.mark.parametrize("tiles,size", [(8, 2101), (8, 2011), (8, 2104), (8, 2012), (3, 264), (2, 8), (8, 8), (8, 9), (3, 783), (8, 64),

@@ -95,6 +95,30 @@ def test_frame_rejections_leave_the_output(nmi):
     assert (out.cpu().numpy() == 0xAB).all() and (small.cpu().numpy() == 0xAB).all() and (lut.cpu().numpy() == 0xAB).all()
 
 
+def test_a_bad_source_is_refused_before_the_mode_is(nmi):
+    """nmi_tone_lut under CLAHE and nmi_tone_tile_luts under any other mode answer NMI_ERR_UNSUPPORTED -- for good arguments
+    only: a bad source, factor or table pointer is NMI_ERR_INVALID_ARGUMENT under every mode."""
+    w, h = 8, 8
+    src = torch.zeros(w * h * 2 + 64, dtype=torch.uint8, device="cuda")
+    lut = torch.full((tnp.LEVELS,), 0xAB, dtype=torch.uint8, device="cuda")
+    sp, lp = src.data_ptr(), lut.data_ptr()
+    with nmi.NmiContext(w, h) as ctx:
+        lib, hd = ctx._lib, ctx._h
+        for tm, entry in ((capi.ToneMap.clahe(1, 1, plateau=0, bits=12), lib.nmi_tone_lut), (capi.ToneMap.equalize(bits=12), lib.nmi_tone_tile_luts),
+                          (None, lib.nmi_tone_tile_luts)):
+            ctx.set_tone_map(tm)
+            assert entry(hd, sp, 0, 1, lp, None) == capi.ERR_UNSUPPORTED
+            assert entry(hd, sp + 1, 0, 1, lp, None) == E                  # an odd base
+            assert entry(hd, sp, 2 * w + 1, 1, lp, None) == E              # an odd pitch
+            assert entry(hd, sp, 2 * w - 2, 1, lp, None) == E              # a pitch below the row
+            assert entry(hd, sp, 0, 0, lp, None) == E and entry(hd, sp, 0, 5, lp, None) == E
+            assert entry(hd, None, 0, 1, lp, None) == E and entry(hd, sp, 0, 1, None, None) == E
+            assert entry(hd, sp, 0, 1, sp + 2 * w * h - 1, None) == E      # the table meets the source's last byte
+        ctx.synchronize()
+    torch.cuda.synchronize()
+    assert (lut.cpu().numpy() == 0xAB).all()
+
+
 def test_bad_tone_maps_leave_the_setting(nmi):
     px = tnp.thermal(W, H, 4)
     d = dev(tnp.pack16(px))

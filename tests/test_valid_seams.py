@@ -1,13 +1,12 @@
 """GPU tests (-m gpu) of the valid-range kernels past one block column and past one trip of the histogram loops
-(nmi_tone_valid.hip, nmi_clahe_valid.hip; include/nmi_hip.h "Deep frames"), == the numpy twin (tests/helpers/valid_np.py) byte for
+(the <true> instantiations of nmi_tone.hip and nmi_clahe.hip; include/nmi_hip.h "Deep frames"), == the numpy twin (tests/helpers/valid_np.py) byte for
 byte and count for count:
   * every entry of tests/test_valid_frame.py's sweep at contexts 264 x 8 (whole quads) and 261 x 9 (the last quad one pixel, byte
-    stores): two block columns of nmi_gray16_masked_kernel<F> and nmi_clahe_gray16_masked_kernel<F> at F = 1 .. 4, on frames with
+    stores): two block columns of nmi_gray16_kernel<F, true> and nmi_clahe_gray16_kernel<F, true> at F = 1 .. 4, on frames with
     invalid pixels on both sides of output column 256 -- among them seam_pixels, one invalid source pixel under each of the
     output pixels 255, 256 and W - 1;
-  * a source of 2104 x 2012 (factor 4) and one of 2101 x 2011 (factor 1): a second chunk of nmi_tone_hist_kernel and
-    nmi_tone_hist_ranged_kernel, a ragged second trip of every tile's workgroups in nmi_clahe_hist_kernel and
-    nmi_clahe_hist_ranged_kernel, on late_quarters frames whose second-trip pixels alone reach the top quarter of 16 bits.
+  * a source of 2104 x 2012 (factor 4) and one of 2101 x 2011 (factor 1): a second chunk of nmi_tone_hist_kernel<false> and
+    <true>, a ragged second trip of every tile's workgroups in nmi_clahe_hist_kernel<false> and <true>, on late_quarters frames whose second-trip pixels alone reach the top quarter of 16 bits.
 tests/test_intake_geometry.py proves these premises on the CPU."""
 import numpy as np
 import pytest
@@ -66,7 +65,7 @@ def both_ranges():
 @pytest.mark.parametrize("run", list(cases.SECOND_TRIP_RUNS))
 def test_a_second_chunk_of_the_tone_histograms(nmi, run, bits):
     """nmi_tone_lut under EQUALIZE and PERCENTILE: the table and the window, with the range off (nmi_tone_hist_kernel) and on
-    (nmi_tone_hist_ranged_kernel), each call twice -- the second on the histogram the first left."""
+    (nmi_tone_hist_kernel<true>), each call twice -- the second on the histogram the first left."""
     w, h, f = cases.SECOND_TRIP_RUNS[run]
     px = cases.second_trip_frame(run, "tone")
     d = dev(tnp.pack16(px))
@@ -87,7 +86,7 @@ def test_a_second_chunk_of_the_tone_histograms(nmi, run, bits):
 @pytest.mark.parametrize("bits", [16, 14])
 @pytest.mark.parametrize("run", list(cases.SECOND_TRIP_RUNS))
 def test_a_second_trip_of_every_tile_under_the_range(nmi, run, bits):
-    """nmi_tone_tile_luts, tables and counts, with the range on (nmi_clahe_hist_ranged_kernel), twice.  (The range off:
+    """nmi_tone_tile_luts, tables and counts, with the range on (nmi_clahe_hist_kernel<true>), twice.  (The range off:
     tests/test_clahe_tables.py.)"""
     w, h, f = cases.SECOND_TRIP_RUNS[run]
     px = cases.second_trip_frame(run, "clahe")

@@ -1,8 +1,10 @@
 """Summary of a rocprofv3 --kernel-trace --output-format csv run of tools/clahe_time.py (its *_kernel_trace.csv) -> JSON on stdout.
 The tool's phases run one after the other, CALLS conversions each, and a conversion ends with its conversion kernel
-(nmi_gray16_kernel<F> or nmi_clahe_gray16_kernel<F>, or their _masked forms: tools/valid_time.py), so the dispatches are cut into phases after every CALLS-th such dispatch;
+(nmi_gray16_kernel<F, Masked> or nmi_clahe_gray16_kernel<F, Masked>; the masked ones: tools/valid_time.py), so the dispatches are cut into phases after every CALLS-th such dispatch;
 per phase, the median duration of every nmi_* kernel that ran at least once per two calls, and their sum.  PHASES names them,
-comma-separated, in the tool's order (its "phase_names").
+comma-separated, in the tool's order (its "phase_names").  The masked conversions (<F, true, ...>) and the ranged histograms
+(<true, ...>) are listed as nmi_*gray16_masked_kernel<F> and nmi_*_hist_ranged_kernel, the plain ones as nmi_*gray16_kernel<F> and
+nmi_*_hist_kernel: the labels of the summaries under profiles/.
 Usage: python tools/summarize_clahe_trace.py TRACE.csv CALLS [PHASES]"""
 import collections
 import csv
@@ -13,7 +15,16 @@ import sys
 import numpy as np
 
 
+ON = r"(true|false|\(bool\)[01])"
+
+
 def short(name):
+    m = re.search(r"(nmi_(?:clahe_)?gray16)_kernel<(\d), " + ON, name)
+    if m:
+        return f"{m.group(1)}{'_masked' if m.group(3) in ('true', '(bool)1') else ''}_kernel<{m.group(2)}>"
+    m = re.search(r"(nmi_(?:tone|clahe)_hist)_kernel<" + ON, name)
+    if m:
+        return f"{m.group(1)}{'_ranged' if m.group(2) in ('true', '(bool)1') else ''}_kernel"
     m = re.search(r"(nmi_\w+?)(<(\d)>)?\(", name + "(")
     if not m:
         return name

@@ -16,8 +16,10 @@ import numpy as np
 def short(name):
     m = re.search(r"(nmi_\w+?)(<.*)?\(", name + "(")
     base = m.group(1) if m else name
-    t = re.search(r"nmi_gray16_kernel<(\d)>", name)
-    return f"nmi_gray16_kernel<{t.group(1)}>" if t else base
+    t = re.search(r"nmi_gray16_kernel<(\d), (true|false|\(bool\)[01])", name)  # <F, Masked, ...>
+    if t:
+        return f"nmi_gray16{'_masked' if t.group(2) in ('true', '(bool)1') else ''}_kernel<{t.group(1)}>"
+    return base
 
 
 def main():
