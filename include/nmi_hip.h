@@ -45,7 +45,8 @@ extern "C" {
                                  nmi_level_set_frame_format, nmi_stream_set_frame_format, and after nmi_reduce_frame,
                                  nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction, and after
                                  nmi_undistort_frame_fisheye, nmi_level_set_distortion_fisheye,
-                                 nmi_stream_set_distortion_fisheye */
+                                 nmi_stream_set_distortion_fisheye, and after nmi_level_set_valid_range,
+                                 nmi_stream_set_valid_range */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -523,8 +524,10 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * and with the outputs untouched: a NULL ctx, d_src, d_gray or d_mask, a factor outside 1 .. 4, an odd d_src or pitch, pitch < 0
  * or 0 < pitch < 2 f W, any two of the source's bytes, the frame mask and the two outputs overlapping.
  * The masked chain on a deep frame is then nmi_deep_frame, nmi_undistort_frame* with d_mask as its raw mask (if distorted),
- * nmi_warp_stack_masked with the result as its frame mask, nmi_search_grid_masked or nmi_search_grid_covered.  Captured levels
- * and streams take no valid range: their GRAY16 intake counts every pixel.
+ * nmi_warp_stack_masked with the result as its frame mask, nmi_search_grid_masked or nmi_search_grid_covered.
+ * Captured levels and streams have a range of their own, like their tone map: nmi_level_set_valid_range and
+ * nmi_stream_set_valid_range (below, beside the other setters).  The context's nmi_set_valid_range governs the standalone entries
+ * only and never reaches a level or a stream.
  * Deep raw formats (new).  What deep sensors put on the wire is rarely the container: GigE / USB3 Vision cameras pack Mono10p /
  * Mono12p, CSI-2 sensors MIPI RAW10 / RAW12 (V4L2 Y10P / Y12P), colour machine-vision cameras send a Bayer mosaic in 16-bit
  * words, PGM files and some thermal cores are big-endian.  Nine formats, taken wherever NMI_FRAME_GRAY16 is (nmi_gray_frame,
@@ -564,8 +567,8 @@ int nmi_reduce_frame(nmi_ctx *ctx, const uint8_t *d_src, int32_t format, int64_t
  * mosaics in 5 / 3-byte groups), rows that do not start on a byte, CLAHE of
  * 8-bit formats, caller-supplied tile tables, more than 8 x 8 tiles, temporal smoothing of the window (TABLE is the hook: smooth
  * on the host, pass the table), statistics under the caller's own frame mask, validity for the 8-bit formats (saturated 0 /
- * 255), a valid range in captured levels and streams, hole filling or inpainting, a per-pixel weight instead of a mask,
- * renormalised CLAHE blends beside an empty tile, the CUDAF shim.
+ * 255), hole filling or inpainting, a way to read a level's validity mask back other than through its warp masks, a per-pixel
+ * weight instead of a mask, renormalised CLAHE blends beside an empty tile, the CUDAF shim.
  */
 #define NMI_TONE_SHIFT 0
 #define NMI_TONE_WINDOW 1
@@ -872,6 +875,33 @@ int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch /* b
 int nmi_level_set_frame_reduction(nmi_level *lv, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 /* The tone map of a GRAY16 frame ("Deep frames", above); the level's d_frame must then be 2-byte aligned.  NULL = the default. */
 int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm);
+/*
+ * The valid range of a deep frame ("Deep frames", above: Valid range) as the level's own setting, like its tone map: 0 <= lo <=
+ * hi <= 65535, (0, 65535) = off, the setting of every new level, under which the graph, every kernel launched, every buffer and
+ * every output byte are what they are without this call.  nmi_set_valid_range does not reach a level.  The range is kept, and
+ * ignored, under every frame format that is not deep; it applies to NMI_FRAME_GRAY16 and to every format that unpacks to it
+ * (validity is taken on the container).
+ *   Plain level        statistics only: the grey frame the warps read is nmi_gray_frame's / nmi_reduce_frame's under that range.
+ *                      No mask is made.
+ *   Masked or covered  also the frame mask the warp masks are made from: nmi_deep_frame's d_mask, 1 iff all f x f source pixels
+ *                      are valid and the d_frame_mask given to nmi_level_set_masks / _set_coverage is nonzero there (NULL:
+ *                      validity alone -- nmi_level_set_masks(lv, 1, NULL) plus a range is how a depth level says "validity
+ *                      only").  Dense [H][W] at the search size, written by the same conversion node (its masked form, no extra
+ *                      node) into a buffer of the level's own: the caller's d_frame_mask is only ever read.  With a lens set it
+ *                      is the undistortion node's raw mask, and the warps read the undistorted one, exactly as a caller's raw
+ *                      frame mask.
+ * Each replay equals, on a context whose range and tone map are the level's, the standalone chain [nmi_unpack_frame] ->
+ * nmi_deep_frame(src, pitch, f, d_frame_mask, gray, mask) -> [nmi_undistort_frame* (gray, mask)] -> nmi_warp_stack_masked -> the
+ * renders -> nmi_search_grid_masked / _covered: winner index and score bits ==, rating table, warps, warp masks and counts
+ * byte-equal.  A frame with no valid pixel: the global modes' table is all 0, the mask all 0, and the search is the masked
+ * search's on all-zero warp masks.
+ * Captures again and waits for a replay in flight, as the other setters do; set and clear it in any order with masks, coverage,
+ * distortion (both models), frame format, reduction and tone map, which all keep it.  All six nmi_level_create* forms,
+ * nmi_level_run and nmi_level_run_rccl; an empty block takes the setting and has no node.  Memory: H x W bytes more while the
+ * range is on, the format is deep and the level is masked or covered; freed otherwise.
+ * NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, lo < 0, lo > hi, hi > 65535.
+ */
+int nmi_level_set_valid_range(nmi_level *lv, int32_t lo, int32_t hi /* 0 <= lo <= hi <= 65535; (0, 65535) = off */);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -985,6 +1015,18 @@ int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch /*
 int nmi_stream_set_frame_reduction(nmi_stream *st, int32_t factor /* 1..4 */, int32_t format, int64_t pitch /* bytes, 0 = dense */);
 /* The tone map of GRAY16 host frames ("Deep frames", above), for later submissions.  NULL = the default. */
 int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm);
+/*
+ * The valid range of deep host frames (nmi_level_set_valid_range's rule), the stream's own setting, for later submissions of
+ * every kind: plain, masked, covered and their _block forms.  A plain ticket takes the statistics only.  A masked or covered
+ * ticket's frame mask is nmi_deep_frame's d_mask -- validity ANDed with h_frame_mask, NULL: validity alone -- made on the device
+ * by the frame's conversion, in place in the stream's frame-mask slot, so a depth stream uploads no H x W mask per keyframe; with
+ * a lens set it is undistorted like an uploaded raw mask.  A ticket equals the same submission on a plain-grey stream given
+ * nmi_deep_frame's grey frame and mask.  Tickets already submitted are not affected; frame-less tickets reuse the latest warps
+ * and warp masks as always.  (0, 65535) = off, the setting of every new stream; kept, and ignored, under every format that is not
+ * deep.  Memory: none beyond the frame-mask pair a masked or covered stream already owns.
+ * NMI_ERR_INVALID_ARGUMENT (the stream left as it was): a NULL stream, lo < 0, lo > hi, hi > 65535.
+ */
+int nmi_stream_set_valid_range(nmi_stream *st, int32_t lo, int32_t hi /* 0 <= lo <= hi <= 65535; (0, 65535) = off */);
 
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);

@@ -100,6 +100,7 @@ EXPORTED_SYMBOLS = (
     "nmi_tone_tile_luts",
     "nmi_set_valid_range", "nmi_deep_frame",
     "nmi_frame_row_bytes", "nmi_unpack_frame",
+    "nmi_level_set_valid_range", "nmi_stream_set_valid_range",
 )
 
 
@@ -291,6 +292,9 @@ def load_library(build_if_missing=False):
         lib.nmi_frame_row_bytes.argtypes = [i32, i32]
         lib.nmi_frame_row_bytes.restype = C.c_int64
         lib.nmi_unpack_frame.argtypes = [vp, vp, i32, C.c_int64, i32, vp]
+    if hasattr(lib, "nmi_level_set_valid_range"):
+        lib.nmi_level_set_valid_range.argtypes = [vp, i32, i32]
+        lib.nmi_stream_set_valid_range.argtypes = [vp, i32, i32]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -1363,6 +1367,14 @@ class NmiLevel:
         self.ctx._check(self._lib.nmi_level_set_tone_map(self._h, _tone_ref(tm)), "nmi_level_set_tone_map")
         self._tone = tm
 
+    def set_valid_range(self, lo=0, hi=65535):
+        """Valid range of a deep frame (nmi_level_set_valid_range): a pixel is valid iff lo <= raw <= hi.  Invalid pixels stay out
+        of the tone map's statistics at every replay, and a masked or covered level's frame mask becomes the validity mask ANDed
+        with the frame_mask given to set_masks / set_coverage (None: validity alone).  The level's own setting: the context's
+        set_valid_range does not reach it.  (0, 65535) turns it off; ignored under every format that is not deep."""
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_valid_range(self._h, int(lo), int(hi)), "nmi_level_set_valid_range")
+
     def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
         """Full-size frame (nmi_level_set_frame_reduction): every replay reads the level's frame in place as factor * H rows of
         `pitch` bytes (0: dense), each factor * W pixels in format fmt (FRAME_*), and reduces it to the grey frame of the search
@@ -1510,6 +1522,12 @@ class NmiStream:
         PERCENTILE, EQUALIZE and CLAHE take their statistics from each submitted frame."""
         self.ctx._check(self._lib.nmi_stream_set_tone_map(self._h, _tone_ref(tm)), "nmi_stream_set_tone_map")
         self._tone = tm
+
+    def set_valid_range(self, lo=0, hi=65535):
+        """Valid range of deep host frames (nmi_stream_set_valid_range), for later submissions: a pixel is valid iff lo <= raw <=
+        hi.  Invalid pixels stay out of the tone map's statistics, and a masked or covered ticket's frame mask is the validity
+        mask ANDed with frame_mask_host (None: validity alone), made on the device.  (0, 65535) turns it off."""
+        self.ctx._check(self._lib.nmi_stream_set_valid_range(self._h, int(lo), int(hi)), "nmi_stream_set_valid_range")
 
     def set_frame_reduction(self, factor, fmt=FRAME_GRAY, pitch=0):
         """Full-size host frames (nmi_stream_set_frame_reduction): frames of later submissions, of every kind, are factor * H rows

@@ -1,4 +1,4 @@
-// nmi_capi_intake.cpp -- the frame intake the captured levels and the streams share (nmi_intake.h): its two settings, checked
+// nmi_capi_intake.cpp -- the frame intake the captured levels and the streams share (nmi_intake.h): its settings, checked
 // and normalised, and its kernel launches.
 #include "nmi_intake.h"
 
@@ -40,15 +40,20 @@ int intake_set_frame(FrameIntake *in, int width, int height, int32_t factor, int
 
 int intake_set_tone_map(FrameIntake *in, int width, int height, const nmi_tone_map *tm) { return tone_check(tm, width, height, &in->tone); }
 
+int intake_set_valid_range(FrameIntake *in, int32_t lo, int32_t hi) { return valid_range_check(lo, hi, &in->valid); }
+
 hipError_t launch_intake(const FrameIntake &in, const ToneWork &tone, const uint8_t *src, int64_t src_row_bytes, const uint8_t *src_mask,
-                         uint8_t *scratch, uint8_t *gray_out, uint8_t *mask_out, int width, int height, hipStream_t stream)
+                         uint8_t *scratch, uint8_t *gray_out, uint8_t *mask_out, uint8_t *valid_out, int width, int height,
+                         hipStream_t stream)
 {
     const uint8_t *raw_mask = mask_out ? src_mask : nullptr;
     if (in.deep()) {  // (distorted: two_nodes())
-        // the tone tables of the full-size source where they come from the frame, then the conversion (and reduction)
-        const hipError_t e = deep_gray(tone, in.tone, src, in.frame_format, src_row_bytes, in.frame_factor, in.distorted ? scratch : gray_out, width,
-                                       height, stream);
+        // the tone tables of the full-size source where they come from the frame, then the conversion (and reduction); with
+        // valid_out the masked conversion, whose validity mask takes src_mask's place from here on
+        const hipError_t e = deep_gray(tone, in.tone, in.valid, src, in.frame_format, src_row_bytes, in.frame_factor,
+                                       valid_out ? src_mask : nullptr, in.distorted ? scratch : gray_out, valid_out, width, height, stream);
         if (e != hipSuccess || !in.distorted) return e;
+        if (valid_out && mask_out) raw_mask = valid_out;
         return nmi::launch_undistort(in.ud, scratch, raw_mask, gray_out, mask_out, width, height, stream);
     }
     if (in.reduced()) {  // one node converts and reduces; distorted: the undistortion node reads the reduced frame

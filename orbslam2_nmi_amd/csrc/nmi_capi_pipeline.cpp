@@ -70,7 +70,8 @@ struct nmi_level {
     nmi::GridArgs args{};                       // the search's arguments (unmasked form)
     int workgroups = 0;
     // What the setters change, as one value (level_apply): masks (nmi_level_set_masks) or coverage (nmi_level_set_coverage, never
-    // both at once), their frame mask, and the frame's way in (nmi_level_set_distortion, _set_frame_format, _set_frame_reduction).
+    // both at once), their frame mask, and the frame's way in (nmi_level_set_distortion, _set_frame_format, _set_frame_reduction,
+    // _set_tone_map, _set_valid_range).
     LevelSettings set;
     // The buffers that go with the settings: level_buffers says which of them a setting needs, level_apply allocates and frees.
     // Masked: the warps' masks and counts of the latest replay, the counts of the replay before (tables are rebuilt only for the
@@ -89,6 +90,9 @@ struct nmi_level {
     // instead.  Reduced (or a Bayer mosaic, or a deep frame) and distorted: brought to grey in d_small, which the undistortion
     // node reads in d_frame's place.
     DeviceBuffer d_ud, d_ud_mask, d_small;      // uint8_t [H][W] each
+    // A deep frame under a valid range, masked or covered: the validity mask its conversion node writes (ANDed with d_frame_mask,
+    // which stays the caller's, read only): the frame mask of the warp masks, or, distorted, the undistortion node's raw mask.
+    DeviceBuffer d_valid;                       // uint8_t [H][W]
     // A deep frame (GRAY16): its tone map's histogram and table (nmi_tone.h), prepared by level_apply before the capture.
     ToneWork tone_work;
 };
@@ -117,12 +121,13 @@ struct LevelNeeds {
     bool ud;       // the level's own grey frame
     bool ud_mask;  // ... and its mask: undistorted, for the warps' masks
     bool small;    // the reduced (or demosaiced, or tone-mapped) grey frame the undistortion node reads
+    bool valid;    // the validity mask of a deep frame under a valid range, for the warps' masks: d_valid
 };
 
 static LevelNeeds level_needs(const LevelSettings &s)
 {
     const bool mode = s.masked || s.covered;
-    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes()};
+    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes(), s.intake.validity() && mode};
 }
 
 struct LevelBuffer {
@@ -144,7 +149,8 @@ static std::vector<LevelBuffer> level_buffers(nmi_level *lv, const LevelSettings
             {&lv->d_cover_counts, cells, cells, n.cover},
             {&lv->d_ud, npix, 0, n.ud},
             {&lv->d_ud_mask, npix, 0, n.ud_mask},
-            {&lv->d_small, npix, 0, n.small}};
+            {&lv->d_small, npix, 0, n.small},
+            {&lv->d_valid, npix, 0, n.valid}};
 }
 
 // Captures the level's graph for lv->set and instantiates it, replacing the previous one only on success.  The caller has waited
@@ -175,8 +181,9 @@ static int level_capture(nmi_level *lv)
     const FrameIntake &in = set.intake;
     const bool masked = set.masked, covered = set.covered;
     uint8_t *ud_mask = level_needs(set).ud_mask ? lv->d_ud_mask.as<uint8_t>() : nullptr;
+    uint8_t *valid = level_needs(set).valid ? lv->d_valid.as<uint8_t>() : nullptr;  // the conversion's validity mask goes here
     const uint8_t *d_frame = in.own_frame() ? d_ud : lv->d_frame;
-    const uint8_t *d_frame_mask = in.distorted ? ud_mask : set.d_frame_mask;
+    const uint8_t *d_frame_mask = in.distorted ? ud_mask : valid ? valid : set.d_frame_mask;
     nmi::GridArgs a = lv->args;
     // Mid-size grids (the live strategy's collapsed levels, a rank's block of a sharded level): P workgroups per candidate
     // (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip, nmi_covered_pix_kernel.hip).  Its hand-off tag = the epoch frozen into the graph + the replay count the
@@ -210,7 +217,8 @@ static int level_capture(nmi_level *lv)
                                   (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
                                   d_epoch, lv->fused_points ? d_packed : nullptr, n_points,
                                   lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, d_kept, d_kept_count));
-        ok(launch_intake(in, lv->tone_work, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, p.width, p.height, st));
+        ok(launch_intake(in, lv->tone_work, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, valid, p.width, p.height,
+                         st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
         // 16-byte aligned); otherwise the warp kernel runs on a forked branch beside the render.
         const bool fused = mesh ? (nmi::level_front_eligible(d_frame, d_warps, p.width, S) && n_points > 0) : lv->fused_points;
@@ -683,6 +691,15 @@ int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm)
     return level_apply(lv, next, "nmi_level_set_tone_map");
 }
 
+int nmi_level_set_valid_range(nmi_level *lv, int32_t lo, int32_t hi)
+{
+    FrameIntake probe;
+    if (!lv || intake_set_valid_range(&probe, lo, hi) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    next.intake.valid = probe.valid;
+    return level_apply(lv, next, "nmi_level_set_valid_range");
+}
+
 int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return nmi_level_set_frame_reduction(lv, 1, format, pitch); }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -738,7 +755,8 @@ struct nmi_stream {
     DeviceBuffer d_rmasks;                        // uint8_t [max_S][H][W]
     DeviceBuffer d_redo;                          // int32_t [max_S * max_Wn] redo list of the optimistic masked / covered launch (stream-ordered too)
     DeviceBuffer d_redo_state;                    // uint32_t [2], zero between searches
-    // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction): frames submitted while one of them
+    // The frame's way in (nmi_stream_set_distortion, _set_frame_format, _set_frame_reduction; with them the tone map and the valid
+    // range of a deep frame, nmi_stream_set_tone_map, _set_valid_range): frames submitted while one of the former
     // is set are brought on the compute stream into d_ud[b] (distorted, masked / covered: their masks into d_ud_mask[b]), and the
     // warps are made from those.  A coloured, pitched or full-size host frame (intake.colored) crosses as its rows of
     // intake.frame_pitch bytes into the dense colour slot d_color[b]; reduced (or a Bayer mosaic, or deep) and distorted, it is brought to
@@ -912,10 +930,15 @@ static int stream_submit(nmi_stream *st, int kind, const uint8_t *h_render_stack
         const uint8_t *frame = d_frame, *frame_mask = h_frame_mask ? d_fmask : nullptr;
         // the camera's frame (and mask) -> the grey, undistorted ones, on the compute stream: the warps read them next
         uint8_t *ud_mask = undistort && kind != kPlain ? st->d_ud_mask[nb].as<uint8_t>() : nullptr;
+        // A deep frame under a valid range, masked or covered: the conversion writes validity into the frame-mask slot, in place
+        // over an uploaded h_frame_mask.  The slot is now written on the compute stream; the copy stream's next upload into it
+        // still waits for warps_free[nb], recorded on the compute stream behind this frame's conversion (at the next frame switch).
+        uint8_t *valid = kind != kPlain && in.validity() ? d_fmask : nullptr;
         if (in.deep()) NMI_HIP_TRY(ctx, tone_prepare(&st->tone_work, in.tone, ctx->stream, in.container(ctx->params.width, ctx->params.height)));
         NMI_HIP_TRY(ctx, launch_intake(in, st->tone_work, colored ? d_color : d_frame, dense_row, frame_mask, d_frame, d_ud, ud_mask,
-                                       ctx->params.width, ctx->params.height, ctx->stream));
+                                       valid, ctx->params.width, ctx->params.height, ctx->stream));
         if (in.own_frame()) frame = d_ud;
+        if (valid) frame_mask = valid;
         if (undistort) frame_mask = ud_mask;
         int rc = kind == kPlain ? nmi_warp_stack(ctx, frame, h_forward, Wn, d_warps)
                                 : nmi_warp_stack_masked(ctx, frame, frame_mask, h_forward, Wn, d_warps, d_wmasks);
@@ -1043,7 +1066,7 @@ int nmi_stream_copy_counts(nmi_stream *st, int64_t ticket, int32_t *h_counts, in
     return NMI_OK;
 }
 
-// The three frame settings: later frame submissions read them at their upload; tickets already submitted are not affected.
+// The frame settings: later frame submissions read them at their upload; tickets already submitted are not affected.
 int nmi_stream_set_distortion(nmi_stream *st, const double K[9], const float dist[5])
 {
     return st ? intake_set_distortion(&st->intake, K, dist) : NMI_ERR_INVALID_ARGUMENT;
@@ -1064,6 +1087,11 @@ int nmi_stream_set_frame_format(nmi_stream *st, int32_t format, int64_t pitch) {
 int nmi_stream_set_tone_map(nmi_stream *st, const nmi_tone_map *tm)
 {
     return st ? intake_set_tone_map(&st->intake, st->ctx->params.width, st->ctx->params.height, tm) : NMI_ERR_INVALID_ARGUMENT;
+}
+
+int nmi_stream_set_valid_range(nmi_stream *st, int32_t lo, int32_t hi)
+{
+    return st ? intake_set_valid_range(&st->intake, lo, hi) : NMI_ERR_INVALID_ARGUMENT;
 }
 
 int nmi_stream_keep_ratings(nmi_stream *st, int32_t enabled)

@@ -2,7 +2,7 @@
 // value, the device buffers that go with it, and the kernels of nmi_tone.hip.  Every mode goes through one uint8 [65536] table:
 // the fixed modes' (SHIFT, WINDOW) is built when the setting changes, the data-dependent ones' (PERCENTILE, EQUALIZE) by two
 // kernels in front of every conversion, and TABLE's is the caller's.  Used by nmi_capi_tone.cpp (the entries), nmi_capi_color.cpp,
-// nmi_capi_reduce.cpp and nmi_capi_intake.cpp (levels and streams).
+// nmi_capi_reduce.cpp and nmi_capi_intake.cpp (levels and streams, with a range of their own).
 // CLAHE is the one mode with a table per tile, four of them blended per pixel: its kernels are nmi_clahe.hip's, its buffers
 // ToneWork's tile_hist and tile_luts, and deep_gray() below is where a conversion takes one way or the other.
 #pragma once
@@ -38,9 +38,10 @@ struct ToneSetting {
     }
 };
 
-// The valid range of a GRAY16 source (nmi_set_valid_range): a pixel counts in the statistics, and is 1 in the validity mask,
-// iff lo <= raw <= hi, raw being the container's value before it saturates to 2^bits - 1.  (0, 65535): off, and the histogram
-// launches below then launch the plain instantiation of their kernel.
+// The valid range of a GRAY16 source (nmi_set_valid_range; a level's and a stream's own: nmi_level_set_valid_range,
+// nmi_stream_set_valid_range): a pixel counts in the statistics, and is 1 in the validity mask, iff lo <= raw <= hi, raw being
+// the container's value before it saturates to 2^bits - 1.  (0, 65535): off, and the histogram launches below then launch the
+// plain instantiation of their kernel.
 struct ValidRange {
     int32_t lo = 0, hi = 65535;
     bool on() const { return lo != 0 || hi != 65535; }
@@ -180,11 +181,5 @@ hipError_t launch_clahe_tone(const ToneWork &w, const nmi::ToneSetting &t, const
 // src's rows of pitch bytes into w.container (prepared with container_bytes), which every node behind it reads as dense GRAY16.
 hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const nmi::ValidRange &range, const uint8_t *src, int format, int64_t pitch,
                      int factor, const uint8_t *frame_mask, uint8_t *gray, uint8_t *mask_out, int width, int height, hipStream_t stream);
-// ... with the range off and no mask: the intake of levels and streams (nmi_capi_intake.cpp), which take no valid range.
-inline hipError_t deep_gray(const ToneWork &w, const nmi::ToneSetting &t, const uint8_t *src, int format, int64_t pitch, int factor,
-                            uint8_t *gray, int width, int height, hipStream_t stream)
-{
-    return deep_gray(w, t, nmi::ValidRange{}, src, format, pitch, factor, nullptr, gray, nullptr, width, height, stream);
-}
 
 }  // namespace nmi_internal
