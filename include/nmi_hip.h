@@ -687,6 +687,50 @@ int nmi_render_mesh_colored_masked(nmi_ctx *ctx, const float *d_xyz, const float
                                    int32_t S, uint8_t *d_render_stack, uint8_t *d_render_masks);
 
 /*
+ * Depth maps (new): the map's own geometry as the search image.  For a depth camera (or any map without an appearance attribute:
+ * a LiDAR cloud without intensity, a CAD model, an untextured reconstruction) the render shows, per pixel, the DEPTH of whatever
+ * won it instead of its colour.  Nothing in front of the shader changes -- culling, clipping, splats, bins, the 24-bit depth
+ * test and its tie rules are those of nmi_render_points / nmi_render_mesh -- and the output is a pure function of the winner's
+ * 24-bit window depth d.  The rule, in fp32, every operation rounded on its own, both divisions IEEE divisions:
+ *     u    = (float)(2^24 - 1 - d) / (2^24 - 1)                       1 - zw; the numerator is exact
+ *     den  = near + u * (far - near)
+ *     z    = (near * far) / den                                       eye-space Z: what RealSense / Kinect-class cameras report
+ *     v    = clamp((uint32)(z * scale + 0.5), 1, 65535)               raw 16-bit depth; 0 is kept for "nothing there"
+ *     grey = v <= lo ? 0 : v >= hi ? 255 : ((v - lo) * 255 + ((hi - lo) >> 1)) / (hi - lo)      NMI_TONE_WINDOW(lo, hi)'s integer rule
+ * A pixel nothing won has v = 0 and grey = 255, the background every renderer clears to.  The grey is therefore what
+ * NMI_TONE_WINDOW(lo, hi) makes of v: a depth frame brought in through nmi_deep_frame (or a level's intake) with that tone map and
+ * the valid range (1, 65535) and the depth render see depth through one mapping ("Depth maps").
+ * near_plane and far_plane must be those of the projection inside h_mvps (nmi_render_mvp's rp); the rule does not read the matrices.
+ *   nmi_render_points_depth  nmi_render_points_masked's draw.  d_red may be NULL (every point splats colour 0: the context then
+ *                            keeps n_points floats of zeros in their place); with a d_red the
+ *                            coverage is nmi_render_points_masked's byte for byte, the far-plane point of colour 255 (whose key is
+ *                            the background's) included -- the colour only breaks ties between equal depths and never shows.
+ *   nmi_render_mesh_depth    nmi_render_mesh's front passes on positions alone; the coverage is nmi_render_mesh_colored_masked's.
+ *   d_render_stack  uint8 [S][H][W], bottom-up rows: grey.   d_render_masks (nullable) uint8 [S][H][W]: 1 where something won.
+ *   d_depth16 (nullable)  uint16 [S][H][W], bottom-up rows: v -- each view's synthetic depth-camera frame; flip the rows for a
+ *                         camera's top-down order.
+ *   nmi_depth_shade_apply    the rule on n depths (bits above the 24th ignored): d_v and d_grey receive v and grey, either may be NULL.
+ * NMI_ERR_INVALID_ARGUMENT, nothing enqueued, the context as usable as before: a NULL shade; a non-finite near_plane, far_plane or
+ * scale; near_plane <= 0; far_plane <= near_plane; scale <= 0; a window outside 0 <= lo < hi <= 65535; a non-zero reserved word;
+ * the renderers' own cases (a NULL context, h_mvps or d_render_stack, S < 1, a negative count, a NULL d_xyz with something to
+ * draw); for nmi_depth_shade_apply n < 0, or n > 0 with a NULL d_depth24.  Enqueued on the context's stream.
+ */
+typedef struct nmi_depth_shade {
+    float near_plane, far_plane; /* those of the projection inside h_mvps */
+    float scale;                 /* raw units per world unit: 1000 = millimetres of a map in metres */
+    int32_t lo, hi;              /* window in raw units, 0 <= lo < hi <= 65535 */
+    int32_t reserved[3];         /* must be 0 */
+} nmi_depth_shade;
+int nmi_render_points_depth(nmi_ctx *ctx, const float *d_xyz, const float *d_red /* nullable */, int64_t n_points, const float *h_mvps,
+                            int32_t S, float point_size, const nmi_depth_shade *shade, uint8_t *d_render_stack,
+                            uint8_t *d_render_masks /* nullable */, uint16_t *d_depth16 /* nullable */);
+int nmi_render_mesh_depth(nmi_ctx *ctx, const float *d_xyz, int64_t n_triangles, const float *h_mvps, int32_t S,
+                          const nmi_depth_shade *shade, uint8_t *d_render_stack, uint8_t *d_render_masks /* nullable */,
+                          uint16_t *d_depth16 /* nullable */);
+int nmi_depth_shade_apply(nmi_ctx *ctx, const nmi_depth_shade *shade, const uint32_t *d_depth24, int64_t n, uint16_t *d_v /* nullable */,
+                          uint8_t *d_grey /* nullable */);
+
+/*
  * Map order.  What the renderers draw does not depend on the order of the points / triangles (the depth test is a
  * minimum); how fast they draw does: neighbours in memory are culled together and their fragments share cache lines of the
  * depth buffer (3 M points into 27 views: 96 us in scan order, 406 us shuffled, 116 us after nmi_sort_points).  These three
@@ -902,6 +946,37 @@ int nmi_level_set_tone_map(nmi_level *lv, const nmi_tone_map *tm);
  * NMI_ERR_INVALID_ARGUMENT (the level left as it was): a NULL level, lo < 0, lo > hi, hi > 65535.
  */
 int nmi_level_set_valid_range(nmi_level *lv, int32_t lo, int32_t hi /* 0 <= lo <= hi <= 65535; (0, 65535) = off */);
+
+/*
+ * Depth levels (new): a level whose renders are depth renders ("Depth maps" above: nmi_render_points_depth /
+ * nmi_render_mesh_depth).  The shade is one more setting of the level: the render node of the captured graph shades from the
+ * winners' depths, everything behind or beside it -- warps, masks, coverage, every intake setting, the search, nmi_level_run_rccl
+ * -- is unchanged and unaware.  The coverage of a covered depth level is the depth shader's own mask.
+ *   nmi_level_create_depth        a level of a map WITHOUT attributes: map_kind NMI_MAP_POINTS (d_xyz float [n][3], every point
+ *                                 splats colour 0; point_size as nmi_level_create) or NMI_MAP_MESH (d_xyz float [3 n][3], n
+ *                                 triangles; point_size ignored).  Otherwise nmi_level_create's arguments.
+ *   nmi_level_create_depth_block  its block form: the block arguments of nmi_level_create_block.
+ *   nmi_level_set_depth_shade     on ANY level -- cloud, textured mesh, coloured mesh, depth, block forms included: `shade` turns
+ *                                 its renders into depth renders, NULL turns them back into the map's colour.  NULL on a level
+ *                                 created without attributes is NMI_ERR_INVALID_ARGUMENT (it has no colour to go back to).
+ * Each replay's renders equal nmi_render_points_depth's / nmi_render_mesh_depth's byte for byte (nmi_level_copy_outputs), its
+ * coverage masks theirs (nmi_level_copy_coverage).  The depth-camera level is such a level plus nmi_level_set_frame_format(
+ * NMI_FRAME_GRAY16), nmi_level_set_tone_map(NMI_TONE_WINDOW(lo, hi), 16 bits), nmi_level_set_valid_range(1, 65535) and
+ * nmi_level_set_masks(1, NULL) or nmi_level_set_coverage(1, NULL), with the same (lo, hi) in the shade.
+ * The setter captures again and waits for a replay in flight, as the other setters do; a refused or failed call leaves the level
+ * as it was.  An empty block takes the setting and has no node.  Memory: a point-cloud level created here holds n floats of zeros
+ * for the colours it does not have.
+ * NMI_ERR_INVALID_ARGUMENT: a bad shade (as nmi_render_points_depth), a map_kind that is neither constant, the create forms' own
+ * cases (nmi_level_create, nmi_level_create_block), a NULL level.
+ */
+#define NMI_MAP_POINTS 0
+#define NMI_MAP_MESH 1
+int nmi_level_create_depth(nmi_ctx *ctx, int32_t map_kind, const float *d_xyz, int64_t n, const uint8_t *d_frame, int32_t S, int32_t Wn,
+                           float point_size, const nmi_depth_shade *shade, nmi_level **out);
+int nmi_level_create_depth_block(nmi_ctx *ctx, int32_t map_kind, const float *d_xyz, int64_t n, const uint8_t *d_frame, int32_t S_local,
+                                 int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float point_size,
+                                 const nmi_depth_shade *shade, nmi_level **out);
+int nmi_level_set_depth_shade(nmi_level *lv, const nmi_depth_shade *shade /* NULL = back to the map's colour */);
 int nmi_level_destroy(nmi_level *lv);
 
 /*

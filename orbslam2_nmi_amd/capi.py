@@ -101,7 +101,11 @@ EXPORTED_SYMBOLS = (
     "nmi_set_valid_range", "nmi_deep_frame",
     "nmi_frame_row_bytes", "nmi_unpack_frame",
     "nmi_level_set_valid_range", "nmi_stream_set_valid_range",
+    "nmi_render_points_depth", "nmi_render_mesh_depth", "nmi_depth_shade_apply",
+    "nmi_level_create_depth", "nmi_level_create_depth_block", "nmi_level_set_depth_shade",
 )
+MAP_POINTS = 0   # nmi_level_create_depth's map_kind
+MAP_MESH = 1
 
 
 class NmiParams(C.Structure):
@@ -177,6 +181,22 @@ def _tone_ref(tm):
     if not isinstance(tm, ToneMap):
         raise TypeError("tone map must be a ToneMap or None")
     return C.byref(tm)
+
+
+class NmiDepthShade(C.Structure):
+    """nmi_depth_shade (include/nmi_hip.h, "Depth maps"): how a depth render turns the winner's window depth into a raw 16-bit
+    depth (near_plane / far_plane of the projection, scale raw units per world unit) and that into grey (the window lo < hi,
+    NMI_TONE_WINDOW's rule)."""
+    _fields_ = [("near_plane", C.c_float), ("far_plane", C.c_float), ("scale", C.c_float), ("lo", C.c_int32), ("hi", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+def _shade_ref(shade, allow_none=False):
+    if shade is None and allow_none:
+        return None
+    if not isinstance(shade, NmiDepthShade):
+        raise TypeError("shade must be an NmiDepthShade")
+    return C.byref(shade)
 
 
 class RenderParams(C.Structure):
@@ -295,6 +315,14 @@ def load_library(build_if_missing=False):
     if hasattr(lib, "nmi_level_set_valid_range"):
         lib.nmi_level_set_valid_range.argtypes = [vp, i32, i32]
         lib.nmi_stream_set_valid_range.argtypes = [vp, i32, i32]
+    if hasattr(lib, "nmi_render_points_depth"):
+        sp = C.POINTER(NmiDepthShade)
+        lib.nmi_render_points_depth.argtypes = [vp, vp, vp, C.c_int64, f32p, i32, C.c_float, sp, vp, vp, vp]
+        lib.nmi_render_mesh_depth.argtypes = [vp, vp, C.c_int64, f32p, i32, sp, vp, vp, vp]
+        lib.nmi_depth_shade_apply.argtypes = [vp, sp, vp, C.c_int64, vp, vp]
+        lib.nmi_level_create_depth.argtypes = [vp, i32, vp, C.c_int64, vp, i32, i32, C.c_float, sp, C.POINTER(vp)]
+        lib.nmi_level_create_depth_block.argtypes = [vp, i32, vp, C.c_int64, vp, i32, i32, i32, i32, i32, i32, C.c_float, sp, C.POINTER(vp)]
+        lib.nmi_level_set_depth_shade.argtypes = [vp, sp]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -1101,6 +1129,78 @@ class NmiContext:
                                                                  o.data_ptr(), masks.data_ptr()), "nmi_render_mesh_colored_masked")
         return out
 
+    def _depth_outputs(self, S, out, out_masks, depth16):
+        """The three stacks of a depth render: grey (made if None), masks and raw depths (None, True = make one, or a tensor)."""
+        import torch
+        shape = (S, self.height, self.width)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        o = self._stack(out, "out")
+        if out_masks is True:
+            out_masks = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        om = None
+        if out_masks is not None:
+            om = self._mask_stack(out_masks, "out_masks")
+            if om.shape[0] != S:
+                raise ValueError("out_masks has the wrong number of views")
+        if depth16 is True:
+            depth16 = torch.empty(shape, dtype=torch.int16, device=self.device)
+        if depth16 is not None and not (depth16.is_cuda and depth16.element_size() == 2 and depth16.is_contiguous()
+                                        and tuple(depth16.shape) == shape):
+            raise TypeError(f"depth16 must be a contiguous 16-bit device tensor {shape}")
+        return out, o, out_masks, om, depth16
+
+    def render_points_depth(self, xyz, red, mvps, point_size, shade, out=None, out_masks=None, depth16=None, sync=True):
+        """The depth render of a cloud (nmi_render_points_depth): xyz [N,3], red [N] or None (every point splats colour 0), host MVPs
+        [S,16], an NmiDepthShade -> (grey [S,H,W] u8, masks or None, depth16 or None).  out_masks / depth16: None (not wanted),
+        True (made here; depth16 as int16, the raw depths being its bits as uint16) or a tensor of the stack's shape."""
+        import torch
+        if not xyz.is_cuda or xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 2:
+            raise TypeError("xyz must be a contiguous float32 device tensor [N,3]")
+        if red is not None and (not red.is_cuda or red.dtype != torch.float32 or not red.is_contiguous() or red.dim() != 1):
+            raise TypeError("red must be a contiguous float32 device tensor [N] or None")
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        out, o, out_masks, om, depth16 = self._depth_outputs(m.shape[0], out, out_masks, depth16)
+        self._order_after_torch()
+        self._check(self._lib.nmi_render_points_depth(self._h, xyz.data_ptr(), red.data_ptr() if red is not None else None, xyz.shape[0],
+                                                      m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], float(point_size), _shade_ref(shade),
+                                                      o.data_ptr(), om.data_ptr() if om is not None else None,
+                                                      depth16.data_ptr() if depth16 is not None else None), "nmi_render_points_depth")
+        if sync:
+            self.synchronize()
+        return out, out_masks, depth16
+
+    def render_mesh_depth(self, xyz, mvps, shade, out=None, out_masks=None, depth16=None, sync=True):
+        """The depth render of a mesh (nmi_render_mesh_depth): corner positions xyz [3T,3] alone, host MVPs [S,16], an NmiDepthShade
+        -> (grey [S,H,W] u8, masks or None, depth16 or None), as render_points_depth."""
+        import torch
+        if not xyz.is_cuda or xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] % 3:
+            raise TypeError("xyz must be a contiguous float32 device tensor [3T,3]")
+        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        out, o, out_masks, om, depth16 = self._depth_outputs(m.shape[0], out, out_masks, depth16)
+        self._order_after_torch()
+        self._check(self._lib.nmi_render_mesh_depth(self._h, xyz.data_ptr(), xyz.shape[0] // 3, m.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    m.shape[0], _shade_ref(shade), o.data_ptr(), om.data_ptr() if om is not None else None,
+                                                    depth16.data_ptr() if depth16 is not None else None), "nmi_render_mesh_depth")
+        if sync:
+            self.synchronize()
+        return out, out_masks, depth16
+
+    def depth_shade_apply(self, shade, depth24, sync=True):
+        """The depth shade on an array (nmi_depth_shade_apply): depth24 a contiguous 32-bit integer device tensor of 24-bit window
+        depths -> (v int16 tensor holding the raw depths' bits as uint16, grey uint8 tensor), both of depth24's shape."""
+        import torch
+        if not depth24.is_cuda or depth24.element_size() != 4 or depth24.is_floating_point() or not depth24.is_contiguous():
+            raise TypeError("depth24 must be a contiguous 32-bit integer device tensor")
+        v = torch.empty(depth24.shape, dtype=torch.int16, device=depth24.device)
+        g = torch.empty(depth24.shape, dtype=torch.uint8, device=depth24.device)
+        self._order_after_torch()
+        self._check(self._lib.nmi_depth_shade_apply(self._h, _shade_ref(shade), depth24.data_ptr(), depth24.numel(), v.data_ptr(), g.data_ptr()),
+                    "nmi_depth_shade_apply")
+        if sync:
+            self.synchronize()
+        return v, g
+
     def search_grid(self, render_stack, warp_stack, ratings=None):
         """Candidate loop + arg-max (Tracking.cc:1879-1905,1952).  -> (best linear index w*S+s, best score).
 
@@ -1213,12 +1313,15 @@ class NmiTexture:
 class NmiLevel:
     """nmi_level wrapper: cloud + frame -> renders, warps, search, winner as one captured HIP graph."""
 
-    def __init__(self, ctx, xyz, red, frame, S, Wn, point_size, texture=None, block=None, colors=False):
+    def __init__(self, ctx, xyz, red, frame, S, Wn, point_size, texture=None, block=None, colors=False, depth=None, mesh=False):
         """Point cloud: xyz [N,3], red [N], point_size.  Textured mesh: pass texture=NmiTexture, xyz [3T,3] corner
         positions and `red` = uv [3T,2] (point_size is ignored).  Vertex-coloured mesh: colors=True, xyz [3T,3] and red [3T],
         no texture (point_size is ignored).
         block = (s_offset, S_total, w_offset, Wn_total): this level is one rank's block (S views x Wn warps, either may be 0)
-        of a level sharded over ranks (nmi_level_create_block); winners then carry global indices."""
+        of a level sharded over ranks (nmi_level_create_block); winners then carry global indices.
+        depth = NmiDepthShade with red=None: a depth level of a map without attributes (nmi_level_create_depth_block) -- a cloud
+        xyz [N,3], or with mesh=True the corner positions xyz [3T,3] of a mesh.  (A level WITH attributes becomes a depth level
+        through set_depth_shade.)"""
         self.ctx, self._lib = ctx, ctx._lib
         self._keep = (xyz, red, frame, texture)  # the graph holds their device addresses
         self.S, self.Wn = int(S), int(Wn)
@@ -1227,7 +1330,15 @@ class NmiLevel:
         if block is None:
             block = (0, self.S, 0, self.Wn)
         so, st, wo, wt = (int(v) for v in block)
-        if colors:
+        if depth is not None:
+            if red is not None or texture is not None or colors:
+                raise ValueError("a depth level is created without attributes; use set_depth_shade on a level that has them")
+            self._shade = depth
+            ctx._check(self._lib.nmi_level_create_depth_block(ctx._h, MAP_MESH if mesh else MAP_POINTS, xyz.data_ptr(),
+                                                              xyz.shape[0] // 3 if mesh else xyz.shape[0], frame.data_ptr(), self.S, so, st,
+                                                              self.Wn, wo, wt, float(point_size), _shade_ref(depth), C.byref(self._h)),
+                       "nmi_level_create_depth_block")
+        elif colors:
             if texture is not None:
                 raise ValueError("a vertex-coloured mesh level takes no texture")
             ctx._check(self._lib.nmi_level_create_mesh_colored_block(ctx._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3,
@@ -1337,6 +1448,13 @@ class NmiLevel:
         self.ctx._check(self._lib.nmi_level_copy_coverage(self._h, r.ctypes.data, m.ctypes.data, n.ctypes.data_as(C.POINTER(C.c_int32))),
                         "nmi_level_copy_coverage")
         return r, m, n
+
+    def set_depth_shade(self, shade):
+        """Depth renders (nmi_level_set_depth_shade): with an NmiDepthShade every replay's renders are the depth renders of the
+        level's map; None turns them back into the map's colour (refused on a level created without attributes)."""
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_depth_shade(self._h, _shade_ref(shade, allow_none=True)), "nmi_level_set_depth_shade")
+        self._shade = shade
 
     def set_distortion(self, K, dist):
         """Distorted lens (nmi_level_set_distortion): the level's frame, and a frame mask given to set_masks / set_coverage, are

@@ -33,6 +33,8 @@ struct LevelSettings {
     bool masked = false, covered = false;
     const uint8_t *d_frame_mask = nullptr;      // the caller's, read in place on every replay
     FrameIntake intake;
+    bool depth = false;                         // the renders are depth renders (nmi_level_set_depth_shade), shaded by ...
+    nmi::DepthShade shade{};                    // ... this (checked; its depth16 null: a level keeps no raw depths)
 };
 
 struct nmi_level {
@@ -44,6 +46,8 @@ struct nmi_level {
     DeviceBuffer d_packed;                      // point cloud: the level's own packed copy of the cloud (16-byte records + wavefront boxes)
     MeshWorkArea mesh;                          // either mesh kind: the renderer's work area (kept clean by the renderer itself)
     MapKind kind = MapKind::points;             // what the level draws; d_attr below is red [N], uv [3T][2] or red [3T] accordingly
+    bool no_attr = false;                       // created without attributes (nmi_level_create_depth): it has depth renders only.  A cloud's
+    DeviceBuffer d_no_red;                      // "colours" are then these zeros, float [N]; a mesh's d_attr is null (kind colored_mesh)
     bool fused_points = false;                  // point cloud, one chain of kernels, double-buffered anchors
     DeviceBuffer d_kept, d_kept_count;          // uint32_t: ... and the wavefronts in reach of a view, listed by the prep kernel per replay
     uint32_t replay = 0;                        // parity of the counters the prep kernel counts under
@@ -71,7 +75,7 @@ struct nmi_level {
     int workgroups = 0;
     // What the setters change, as one value (level_apply): masks (nmi_level_set_masks) or coverage (nmi_level_set_coverage, never
     // both at once), their frame mask, and the frame's way in (nmi_level_set_distortion, _set_frame_format, _set_frame_reduction,
-    // _set_tone_map, _set_valid_range).
+    // _set_tone_map, _set_valid_range), and what the renders show (nmi_level_set_depth_shade).
     LevelSettings set;
     // The buffers that go with the settings: level_buffers says which of them a setting needs, level_apply allocates and frees.
     // Masked: the warps' masks and counts of the latest replay, the counts of the replay before (tables are rebuilt only for the
@@ -207,6 +211,7 @@ static int level_capture(nmi_level *lv)
     const MaskSearch ms = mask_search_args(ma, MaskSide{d_masks, covered ? d_rmasks : nullptr, covered ? d_cover_counts : d_counts,
                                                         d_tables, d_redo, d_redo_state});
     uint8_t *cover = covered ? d_rmasks : nullptr;  // the renderers' coverage masks
+    const nmi::DepthShade *depth = set.depth ? &set.shade : nullptr;  // the renderers' shade: the map's colour, or its depth
     int32_t *d_prev = d_counts + Wn, *d_changed = d_counts + 2 * Wn;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
@@ -239,14 +244,14 @@ static int level_capture(nmi_level *lv)
         if (mesh)
             ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, d_mvps, S, lv->mesh.view, S,
                                        (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, d_renders,
-                                       p.width, p.height, st, fused ? d_frame : nullptr, d_coeffs, d_warps, Wn, cover));
+                                       p.width, p.height, st, fused ? d_frame : nullptr, d_coeffs, d_warps, Wn, cover, depth));
         else if (fused)
             ok(nmi::launch_level_front_points(d_packed, n_points, d_mvps, S, d_zbuf, d_epoch, d_renders, p.width, p.height,
                                               lv->size, d_frame, d_coeffs, d_warps, Wn, st, d_kept, d_kept_count, ctx->compute_units,
-                                              cover));
+                                              cover, depth));
         else
             ok(nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, d_zbuf, d_renders, p.width, p.height, lv->size, st,
-                                         /*clear_first=*/false, cover));
+                                         /*clear_first=*/false, cover, depth));
         if (!fused || masked || covered) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
         if (masked || covered)
             ok(launch_mask_search(ms, lv->pix, lv->pix ? pix_owner_share(ctx, lv->pix) : 0.0, workgroups, true, false, d_epoch,
@@ -321,17 +326,19 @@ static int level_apply(nmi_level *lv, const LevelSettings &next, const char *wha
 
 // Common part of nmi_level_create (kind points: d_attr = red), nmi_level_create_mesh (textured_mesh: d_attr = uv, tex, n =
 // triangles) and nmi_level_create_mesh_colored (colored_mesh: d_attr = red per corner, no texture, n = triangles).
+// depth (nmi_level_create_depth): a level without attributes -- d_attr is null, kind is points or colored_mesh -- that starts with
+// this shade and can never be without one.
 struct LevelBlock {
     int32_t S, s_offset, S_total, Wn, w_offset, Wn_total;
 };
 
 static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_points, const nmi_texture *tex,
-                        const uint8_t *d_frame, const LevelBlock &blk, float point_size, nmi_level **out)
+                        const uint8_t *d_frame, const LevelBlock &blk, float point_size, nmi_level **out, const nmi::DepthShade *depth = nullptr)
 {
     const bool mesh = kind != MapKind::points;
     const float *d_red = d_attr;
     const int32_t S = blk.S, Wn = blk.Wn;
-    if (!ctx || !out || !d_frame || S < 0 || Wn < 0 || n_points < 0 || (n_points > 0 && (!d_xyz || !d_attr)))
+    if (!ctx || !out || !d_frame || S < 0 || Wn < 0 || n_points < 0 || (n_points > 0 && (!d_xyz || (!d_attr && !depth))))
         return NMI_ERR_INVALID_ARGUMENT;
     if (blk.S_total <= 0 || blk.Wn_total <= 0 || blk.s_offset < 0 || blk.w_offset < 0 || blk.s_offset + S > blk.S_total ||
         blk.w_offset + Wn > blk.Wn_total)
@@ -348,6 +355,7 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
     if (!lv) return NMI_ERR_INVALID_ARGUMENT;
     lv->ctx = ctx;
     lv->kind = kind;
+    if (depth) lv->no_attr = true, lv->set.depth = true, lv->set.shade = *depth;
     lv->S = S;
     lv->Wn = Wn;
     lv->s_offset = blk.s_offset;
@@ -388,6 +396,11 @@ static int level_create(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const fl
         ok(lv->d_zbuf.alloc(words * sizeof(uint32_t)));
         ok(lv->d_epoch.alloc(sizeof(uint32_t)));
         ok(lv->d_packed.alloc(nmi::cloud_pack_bytes(n_points, nullptr) + 16));
+        if (depth && n_points > 0) {  // a cloud without colours: zeros stand in (the colour only breaks ties between equal depths)
+            ok(lv->d_no_red.alloc((size_t)n_points * sizeof(float)));
+            if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_no_red.as<>(), 0, (size_t)n_points * sizeof(float), ctx->stream));
+            d_attr = d_red = lv->d_no_red.as<float>();
+        }
         if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_zbuf.as<>(), 0xFF, words * sizeof(uint32_t), ctx->stream));
         if (ok.e == hipSuccess) ok(hipMemsetAsync(lv->d_epoch.as<>(), 0, sizeof(uint32_t), ctx->stream));
         if (ok.e == hipSuccess) ok(nmi::launch_cloud_pack(d_xyz, d_red, n_points, lv->d_packed.as<>(), ctx->stream));
@@ -490,6 +503,25 @@ int nmi_level_create_mesh_colored(nmi_ctx *ctx, const float *d_xyz, const float 
 {
     if (S <= 0 || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
     return level_create(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, d_frame, LevelBlock{S, 0, S, Wn, 0, Wn}, 1.0f, out);
+}
+
+// Depth levels: a level of a map without attributes, and the shade of any level.
+int nmi_level_create_depth_block(nmi_ctx *ctx, int32_t map_kind, const float *d_xyz, int64_t n, const uint8_t *d_frame, int32_t S_local,
+                                 int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float point_size,
+                                 const nmi_depth_shade *shade, nmi_level **out)
+{
+    nmi::DepthShade sh;
+    if ((map_kind != NMI_MAP_POINTS && map_kind != NMI_MAP_MESH) || depth_shade_check(shade, &sh) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    const bool mesh = map_kind == NMI_MAP_MESH;
+    return level_create(ctx, mesh ? MapKind::colored_mesh : MapKind::points, d_xyz, nullptr, n, nullptr, d_frame,
+                        LevelBlock{S_local, s_offset, S_total, Wn_local, w_offset, Wn_total}, mesh ? 1.0f : point_size, out, &sh);
+}
+
+int nmi_level_create_depth(nmi_ctx *ctx, int32_t map_kind, const float *d_xyz, int64_t n, const uint8_t *d_frame, int32_t S, int32_t Wn,
+                           float point_size, const nmi_depth_shade *shade, nmi_level **out)
+{
+    if (S <= 0 || Wn <= 0) return NMI_ERR_INVALID_ARGUMENT;
+    return nmi_level_create_depth_block(ctx, map_kind, d_xyz, n, d_frame, S, 0, S, Wn, 0, Wn, point_size, shade, out);
 }
 
 int nmi_level_create_block(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const uint8_t *d_frame, int32_t S_local,
@@ -698,6 +730,16 @@ int nmi_level_set_valid_range(nmi_level *lv, int32_t lo, int32_t hi)
     LevelSettings next = lv->set;
     next.intake.valid = probe.valid;
     return level_apply(lv, next, "nmi_level_set_valid_range");
+}
+
+int nmi_level_set_depth_shade(nmi_level *lv, const nmi_depth_shade *shade)
+{
+    nmi::DepthShade sh{};
+    if (!lv || (shade ? depth_shade_check(shade, &sh) != NMI_OK : lv->no_attr)) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    next.depth = shade != nullptr;
+    next.shade = sh;
+    return level_apply(lv, next, "nmi_level_set_depth_shade");
 }
 
 int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return nmi_level_set_frame_reduction(lv, 1, format, pitch); }

@@ -1,5 +1,5 @@
 // nmi_capi_producers.cpp -- C ABI of the stack producers: warp stack, point-cloud and textured-mesh
-// render stacks, vertex-coloured-mesh render stacks.  Declared in include/nmi_hip.h.
+// render stacks, vertex-coloured-mesh render stacks, the depth renders of clouds and meshes.  Declared in include/nmi_hip.h.
 #include "nmi_ctx.h"
 
 using namespace nmi_internal;
@@ -225,21 +225,35 @@ int point_sprite_size(float point_size, int *size)
 }
 
 int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
-                       float point_size, uint8_t *d_render_stack, uint8_t *cover)
+                       float point_size, uint8_t *d_render_stack, uint8_t *cover, const nmi::DepthShade *depth)
 {
-    if (!ctx || !h_mvps || !d_render_stack || S <= 0 || n_points < 0 || (n_points > 0 && (!d_xyz || !d_red)))
+    if (!ctx || !h_mvps || !d_render_stack || S <= 0 || n_points < 0 || (n_points > 0 && (!d_xyz || (!d_red && !depth))))
         return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
     int size = 1;
     if (point_sprite_size(point_size, &size) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    if (n_points > 0 && !d_red) {  // a cloud without colours: every point splats colour 0
+        NMI_HIP_TRY(ctx, ctx->d_no_red.grow((size_t)n_points * sizeof(float), ctx->stream, /*zero=*/true));
+        d_red = ctx->d_no_red.as<float>();
+    }
     const int64_t need = (int64_t)nmi::render_zbuf_words(S, ctx->params.width, ctx->params.height, size);
     NMI_HIP_TRY(ctx, ctx->d_zbuf.grow((size_t)need * sizeof(uint32_t), ctx->stream));
     float *d_mvps = nullptr;
     const int src = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (src != NMI_OK) return src;
     NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, ctx->d_zbuf.as<uint32_t>(), d_render_stack, ctx->params.width,
-                                               ctx->params.height, size, ctx->stream, true, cover));
+                                               ctx->params.height, size, ctx->stream, true, cover, depth));
+    return NMI_OK;
+}
+
+int depth_shade_check(const nmi_depth_shade *shade, nmi::DepthShade *out)
+{
+    if (!shade || !std::isfinite(shade->near_plane) || !std::isfinite(shade->far_plane) || !std::isfinite(shade->scale)) return NMI_ERR_INVALID_ARGUMENT;
+    if (!(shade->near_plane > 0.0f) || !(shade->far_plane > shade->near_plane) || !(shade->scale > 0.0f)) return NMI_ERR_INVALID_ARGUMENT;
+    if (shade->lo < 0 || shade->lo >= shade->hi || shade->hi > 65535) return NMI_ERR_INVALID_ARGUMENT;
+    if (shade->reserved[0] || shade->reserved[1] || shade->reserved[2]) return NMI_ERR_INVALID_ARGUMENT;
+    *out = nmi::DepthShade{shade->near_plane, shade->far_plane, shade->scale, (uint32_t)shade->lo, (uint32_t)shade->hi, nullptr};
     return NMI_OK;
 }
 
@@ -340,16 +354,45 @@ int nmi_render_mesh_colored_masked(nmi_ctx *ctx, const float *d_xyz, const float
     return render_mesh_impl(ctx, MapKind::colored_mesh, d_xyz, d_red, n_triangles, nullptr, h_mvps, S, d_render_stack, d_render_masks);
 }
 
+// The depth renders ("Depth maps", include/nmi_hip.h): the same draws, shaded from the winners' depths.
+int nmi_render_points_depth(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
+                            float point_size, const nmi_depth_shade *shade, uint8_t *d_render_stack, uint8_t *d_render_masks, uint16_t *d_depth16)
+{
+    nmi::DepthShade sh;
+    if (depth_shade_check(shade, &sh) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    sh.depth16 = d_depth16;
+    return render_points_impl(ctx, d_xyz, d_red, n_points, h_mvps, S, point_size, d_render_stack, d_render_masks, &sh);
+}
+
+int nmi_render_mesh_depth(nmi_ctx *ctx, const float *d_xyz, int64_t n_triangles, const float *h_mvps, int32_t S, const nmi_depth_shade *shade,
+                          uint8_t *d_render_stack, uint8_t *d_render_masks, uint16_t *d_depth16)
+{
+    nmi::DepthShade sh;
+    if (depth_shade_check(shade, &sh) != NMI_OK) return NMI_ERR_INVALID_ARGUMENT;
+    sh.depth16 = d_depth16;
+    return render_mesh_impl(ctx, MapKind::colored_mesh, d_xyz, nullptr, n_triangles, nullptr, h_mvps, S, d_render_stack, d_render_masks, &sh);
+}
+
+int nmi_depth_shade_apply(nmi_ctx *ctx, const nmi_depth_shade *shade, const uint32_t *d_depth24, int64_t n, uint16_t *d_v, uint8_t *d_grey)
+{
+    nmi::DepthShade sh;
+    if (!ctx || depth_shade_check(shade, &sh) != NMI_OK || n < 0 || (n > 0 && !d_depth24)) return NMI_ERR_INVALID_ARGUMENT;
+    ctx->detail.clear();
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, nmi::launch_depth_shade_apply(sh, d_depth24, n, d_v, d_grey, ctx->stream));
+    return NMI_OK;
+}
+
 }  // extern "C"
 
 namespace nmi_internal {
 
 int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_triangles, const nmi_texture *tex,
-                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover)
+                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover, const nmi::DepthShade *depth)
 {
     const bool textured = kind == MapKind::textured_mesh;
     if (!ctx || (textured ? (!tex || tex->ctx != ctx) : tex != nullptr) || !h_mvps || !d_render_stack || S <= 0 || n_triangles < 0 ||
-        (n_triangles > 0 && (!d_xyz || !d_attr)))
+        (n_triangles > 0 && (!d_xyz || (!d_attr && !depth))))
         return NMI_ERR_INVALID_ARGUMENT;
     ctx->detail.clear();
     DeviceGuard guard(ctx->device);
@@ -364,7 +407,7 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
     const int bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
     const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, d_mvps, S, ctx->mesh.view, ctx->mesh_views, bin_cap,
                                                  ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
-                                                 nullptr, nullptr, 0, cover);
+                                                 nullptr, nullptr, 0, cover, depth);
     if (e != hipSuccess) {
         ctx->mesh_views = 0;  // whatever state the buffers are in: allocate and clear afresh next time
         return hip_fail(ctx, e, "launch_render_mesh");

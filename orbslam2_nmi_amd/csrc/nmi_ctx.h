@@ -108,6 +108,7 @@ struct nmi_ctx {
     int stamp_candidate = 0;                   // NMI_OPT_STAMP_CANDIDATE
     int split_mode = -1;                  // NMI_OPT_SPLIT: -1 automatic, 0 never, 2 / 4 / 8 row parts whenever the grid fits, 1: pixel ranges only
     DeviceBuffer d_zbuf;                  // depth|colour anchor buffers of the point-cloud renderer (padded, per view)
+    DeviceBuffer d_no_red;                // float zeros: the colours of a cloud drawn without any (nmi_render_points_depth, d_red NULL)
     MeshWorkArea mesh;                     // mesh renderer (nmi_render_mesh): bins, their state, key buffer, clip queue -- for mesh_views views
     int mesh_views = 0;
     unsigned long long tile_queue_limit = 4ull << 20;  // NMI_OPT_TILE_QUEUE: usable entries per bin (capped by the bins' size)
@@ -255,10 +256,15 @@ enum class MapKind { points, textured_mesh, colored_mesh };
 // nmi_render_points / nmi_render_mesh / nmi_render_mesh_colored and their masked forms (nmi_capi_producers.cpp): cover = null,
 // or the coverage masks.  render_mesh_impl: kind is one of the two mesh kinds, d_attr its attribute array, tex the texture
 // (textured_mesh) or null (colored_mesh).
+// depth (nmi_render_points_depth, nmi_render_mesh_depth): the checked shade with its depth16; the render is the depth render, a
+// cloud's d_red may then be null (zeros of the context's stand in) and a mesh's d_attr is not read.
 int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int64_t n_points, const float *h_mvps, int32_t S,
-                       float point_size, uint8_t *d_render_stack, uint8_t *cover);
+                       float point_size, uint8_t *d_render_stack, uint8_t *cover, const nmi::DepthShade *depth = nullptr);
 int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float *d_attr, int64_t n_triangles, const nmi_texture *tex,
-                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover);
+                     const float *h_mvps, int32_t S, uint8_t *d_render_stack, uint8_t *cover, const nmi::DepthShade *depth = nullptr);
+// The argument check of every depth entry point (include/nmi_hip.h, "Depth maps"), before any HIP call: NMI_OK with the kernels'
+// form of the shade (depth16 null) in *out, or NMI_ERR_INVALID_ARGUMENT.
+int depth_shade_check(const nmi_depth_shade *shade, nmi::DepthShade *out);
 nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_texture *tex);  // launch_render_mesh's description of a mesh kind
 int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
                     int Wn);

@@ -158,6 +158,17 @@ size_t grid_kernel_scratch_bytes(int workgroups);
 hipError_t launch_warp(const uint8_t *frame, const float *coeffs /*[Wn][9] inverse maps*/, uint8_t *out, int width,
                        int height, int Wn, hipStream_t stream);
 
+// The depth shade (nmi_depth_device.h; include/nmi_hip.h, "Depth maps") as the kernels take it -- checked by the C ABI: finite,
+// 0 < near < far, scale > 0, 0 <= lo < hi <= 65535 -- and where the raw depths go: depth16 [S][H][W] in the render's layout, or null.
+// A renderer given one shades every pixel from the 24 depth bits of its winner instead of the map's colour.
+struct DepthShade {
+    float near_plane, far_plane, scale;
+    uint32_t lo, hi;
+    uint16_t *depth16;
+};
+// nmi_depth_shade_apply (nmi_depth.hip): the rule on n 24-bit depths; v and grey may each be null.
+hipError_t launch_depth_shade_apply(const DepthShade &shade, const uint32_t *depth24, long long n, uint16_t *v, uint8_t *grey, hipStream_t stream);
+
 // Mesh renderer (nmi_mesh.hip): a binned, deferred rasteriser for textured and for vertex-coloured meshes.  MeshWork = its device buffers, owned by a context
 // or by a level; zbuf must be all ones and state all zero before a render (launch_mesh_clear once after allocation) and
 // the renderer leaves them so.  bin_cap_limit: usable entries per bin (NMI_OPT_TILE_QUEUE; 0 = every triangle is
@@ -183,7 +194,8 @@ hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hi
 // How a fragment gets its grey: from a texture at the corners' uv, or from the corners' own colours.
 struct MeshShading {
     bool textured;
-    const float *attr;             // textured: uv [3T][2]; coloured: red [3T], one colour per corner; both in the order of xyz
+    const float *attr;             // textured: uv [3T][2]; coloured: red [3T], one colour per corner; both in the order of xyz;
+                                   // unread (may be null) under a depth shade
     const float *luma = nullptr;   // textured only: the luma pyramid, `levels` (<= 16) levels of lw[l] x lh[l] texels at luma + loff[l]
     int levels = 0;
     const int *lw = nullptr, *lh = nullptr;
@@ -196,14 +208,17 @@ hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long
                               // (level_front_eligible must hold; needs at least one triangle and S <= 64)
                               const uint8_t *warp_frame = nullptr, const float *warp_coeffs = nullptr, uint8_t *warp_out = nullptr, int Wn = 0,
                               // coverage masks [S][H][W] (1 where a fragment won the pixel, 0 where it kept the clear colour), or null
-                              uint8_t *cover = nullptr);
+                              uint8_t *cover = nullptr,
+                              // the depth render of the same mesh: every pixel shaded from its winner's depth, no attribute read
+                              const DepthShade *depth = nullptr);
 // Words between rows of the renderers' anchor / depth buffer: the padded width, rounded so that the resolve pass can
 // read 8 consecutive anchors of any output quad with two aligned 16-byte loads (point sizes > 1); width for size 1.
 inline int zbuf_stride(int width, int size) { return size > 1 ? ((width + size - 1 + 3) & ~3) + 4 : width; }
 size_t render_zbuf_words(int S, int width, int height, int size);
 hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps /*[S][16] column-major*/,
                                 int S, uint32_t *zbuf /*[render_zbuf_words]*/, uint8_t *out, int width, int height, int size, hipStream_t stream,
-                                bool clear_first = true, uint8_t *cover = nullptr /* [S][H][W]: 1 where a point won the pixel, or null */);
+                                bool clear_first = true, uint8_t *cover = nullptr /* [S][H][W]: 1 where a point won the pixel, or null */,
+                                const DepthShade *shade = nullptr /* the depth render: the resolve shades from the winner's depth */);
 // nmi_sort.hip: records (na floats each in `a`, the first 3 * verts being vertices; nb floats each in `b`, may be null) into
 // Morton order of their positions.  Drains the stream.
 hipError_t sort_records_morton(const float *a, int na, int verts, const float *b, int nb, long long n, float *a_out, float *b_out,
@@ -222,7 +237,8 @@ hipError_t launch_level_front_points(const void *packed, long long npoints, cons
                                      const float *coeffs, uint8_t *warps, int Wn, hipStream_t stream,
                                      const uint32_t *kept /* [ceil(n / 64)]: wavefronts in reach of a view, made by the prep kernel */,
                                      const uint32_t *kept_count /* [2], by replay parity */, int compute_units,
-                                     uint8_t *cover = nullptr /* [S][H][W] coverage masks (4-byte aligned), as launch_render_points */);
+                                     uint8_t *cover = nullptr /* [S][H][W] coverage masks (4-byte aligned), as launch_render_points */,
+                                     const DepthShade *shade = nullptr /* as launch_render_points; depth16 8-byte aligned */);
 hipError_t launch_level_prep(const float *h_mvps, float *d_mvps, int n_mvps, const float *h_coeffs, float *d_coeffs, int n_coeffs,
                              unsigned long long *key, uint32_t *zbuf, size_t nz, hipStream_t stream, uint32_t *epoch = nullptr,
                              const void *packed = nullptr, long long npoints = 0, const float *h_bound /* pinned: 24 floats + parity word */ = nullptr,

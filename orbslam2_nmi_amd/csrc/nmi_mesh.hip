@@ -41,12 +41,17 @@
 // Vertex-coloured meshes (a colour per corner, no texture; shaders/ShadingWithColor.*) take the same passes up to the tile kernel,
 // which read positions only; the last stage is mesh_tile_body<Attr, ...> over an attribute policy, TexturedAttr or ColoredAttr,
 // behind tile kernels of their own names (nmi_mesh_tile_color_kernel, its cover form).
+//
+// Depth renders (nmi_render_mesh_depth, depth levels) take the same passes too and end in mesh_tile_body<DepthAttr, ...>: no
+// attribute is read, the records hold the visibility fields only, and a pixel's grey is the depth shade (nmi_depth_device.h) of
+// the 24 depth bits of the key that won it, whichever way that key came (nmi_mesh_tile_depth_kernel, its cover form).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "nmi_kernels.h"
 #include "nmi_warp_device.h"
+#include "nmi_depth_device.h"
 
 namespace nmi {
 
@@ -798,6 +803,7 @@ struct TexturedAttr {
     using Args = MeshTexture;      // what the kernel takes besides the grid
     struct Lds { TexLevel tex[16]; };   // what the tile keeps in LDS besides keys and records
     using Uniform = TexLevel;      // what every lane holds for the shading loop: level 0
+    static constexpr bool kDepth = false;
     static constexpr int kRecordWords = 28;   // planes: xr, yr, s0, r0, sx, rx, sy, ry, q0, qx, qy
 
     static __device__ __forceinline__ void load_corner(const float *__restrict__ uv, long long corner, float &u, float &v)
@@ -834,6 +840,7 @@ struct ColoredAttr {
     struct Args {};
     struct Lds {};
     struct Uniform {};
+    static constexpr bool kDepth = false;
     static constexpr int kRecordWords = 24;   // planes: xr, yr, s0, sx, sy, q0, qx, qy
 
     static __device__ __forceinline__ void load_corner(const float *__restrict__ red, long long corner, float &u, float &v)
@@ -858,6 +865,48 @@ struct ColoredAttr {
         return shade_color(P, fxp, fyp);
     }
 };
+
+// Depth: no attribute at all.  The corners' "attributes" are constants (setup_piece's attribute arithmetic is dead code the compiler
+// drops; the positions take the same operations as in the other two), a record ends with the visibility fields, there are no
+// planes, and the shader is depth_shade on the winning key's depth: mesh_tile_body asks kDepth where the three differ.
+// Args: the shade, depth16 (if any) at the first view of the launch.
+struct DepthAttr {
+    using Args = DepthShade;
+    struct Lds {};
+    struct Uniform {};
+    static constexpr bool kDepth = true;
+    // R_XW .. R_ID: everything below R_PLANES.  255 records are 16 KB; with the keys 49 KB, which lets three workgroups share a CU.
+    // (17 words, an odd stride against LDS bank conflicts between records, measured slower: profiles/depth/README.md.)
+    static constexpr int kRecordWords = 16;
+
+    static __device__ __forceinline__ void load_corner(const float *__restrict__, long long, float &u, float &v) { u = 0.0f, v = 0.0f; }
+    static __device__ __forceinline__ void fill_lds(const Args &, int, Lds &) {}
+    static __device__ __forceinline__ Uniform uniform(const Args &) { return {}; }
+};
+
+// Depth: the four pixels of a lane's step from their keys -- grey into `packed`, coverage into `covered`, and the raw depths into
+// the shade's depth16 at pixel `at` of the launch's stack (pixel k exists iff k < n; `quad`: one 8-byte store).
+__device__ __forceinline__ void shade_depth_quad(const DepthShade &sh, const unsigned long long (&keys)[4], size_t at, bool quad, int n,
+                                                 uint32_t &packed, uint32_t &covered)
+{
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = kDepthNothing;
+        if ((keys[k] != kEmptyKey) & (k < n)) {
+            uint32_t grey;
+            depth_shade(sh, (uint32_t)(keys[k] >> 40), v[k], grey);
+            packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
+            covered |= 1u << (8 * k);
+        }
+    }
+    if (sh.depth16) {
+        if (quad && (((uintptr_t)sh.depth16 & 7) == 0))
+            *reinterpret_cast<uint2 *>(sh.depth16 + at) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+        else
+            for (int k = 0; k < 4 && k < n; ++k) sh.depth16[at + k] = (uint16_t)v[k];
+    }
+}
 
 template <typename Attr, int BINMAX>
 struct TileLds {
@@ -923,6 +972,11 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 else
                     for (int k = 0; k < 4 && ox + k < width; ++k) cdst[k] = 0;
             }
+            if constexpr (Attr::kDepth) {   // nothing there: raw depth 0
+                const unsigned long long none[4] = {kEmptyKey, kEmptyKey, kEmptyKey, kEmptyKey};
+                uint32_t p = 0, c = 0;
+                shade_depth_quad(args, none, (size_t)(dst - out), dword_ok, width - ox, p, c);
+            }
         }
         return;
     }
@@ -941,13 +995,13 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
                 ok = bx0 <= bx1 && by0 <= by1;
             }
             if (ok) {
-                Planes P;
-                tri_planes(t, su, sv, P);
+                Planes P;   // (depth: there are none)
+                if constexpr (!Attr::kDepth) tri_planes(t, su, sv, P);
                 float *f = reinterpret_cast<float *>(r);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) f[R_XW + k] = t.xw[k], f[R_YW + k] = t.yw[k], f[R_ZW + k] = t.zw[k];
                 f[R_INV_AREA] = t.inv_area;
-                Attr::planes_to_lds(P, r);
+                if constexpr (!Attr::kDepth) Attr::planes_to_lds(P, r);
                 r[R_OWN] = (t.own[0] ? 1u : 0u) | (t.own[1] ? 2u : 0u) | (t.own[2] ? 4u : 0u);
                 r[R_BOX] = (uint32_t)bx0 | ((uint32_t)by0 << 16);
                 const uint32_t nsteps = (uint32_t)(((bx1 - bx0 + 2) >> 1) * (by1 - by0 + 1));  // steps of the visibility walk: pairs of pixels in a row; at most 2048
@@ -1090,38 +1144,43 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
         // ---- shade every pixel once, by the triangle that won it ------------------------------------------------------------
         uint32_t packed = 0xFFFFFFFFu;
         uint32_t covered = 0;  // (COVER) 1 in byte k: pixel k's grey came from a fragment
-        // Pixels won through the memory buffer have no record in LDS: their triangle is set up here, on the fly.  One copy of
-        // that code, outside the unrolled loop below (for a mesh of pixel-sized triangles this IS the shading loop).
-        if (from_memory) {
+        // Depth: the grey is the shade of the key's own depth bits, whichever way the key came -- no record, no set-up.
+        if constexpr (Attr::kDepth) {
+            shade_depth_quad(args, keys, ((size_t)s * height + y) * width + ox, dword_ok, width - ox, packed, covered);
+        } else {
+            // Pixels won through the memory buffer have no record in LDS: their triangle is set up here, on the fly.  One copy of
+            // that code, outside the unrolled loop below (for a mesh of pixel-sized triangles this IS the shading loop).
+            if (from_memory) {
 #pragma unroll 1
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned long long key = keys[0];  // (the keys rotate through slot 0: no dynamic register indexing)
+                    keys[0] = keys[1], keys[1] = keys[2], keys[2] = keys[3], keys[3] = key;
+                    if (key == kEmptyKey || (uint32_t)(key & 0x1FFu) != kNoSlot || ox + k >= width) continue;
+                    TriView t;
+                    float su[3], sv[3];
+                    const unsigned long long id = (key >> 9) & 0x7FFFFFFFull;
+                    uint32_t grey = 255u;
+                    if (setup_piece<Attr>(xyz, attr, (long long)(id >> 1), (int)(id & 1ull), mvps + s * 16, width, height, t, su, sv)) {  // (true: it produced this key)
+                        Planes P;
+                        tri_planes(t, su, sv, P);
+                        grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                        if (COVER) covered |= 1u << (8 * k);
+                    }
+                    packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
+                    keys[3] = kEmptyKey;  // done
+                }
+            }
+            // the four pixels side by side: their texel fetches overlap
+#pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const unsigned long long key = keys[0];  // (the keys rotate through slot 0: no dynamic register indexing)
-                keys[0] = keys[1], keys[1] = keys[2], keys[2] = keys[3], keys[3] = key;
-                if (key == kEmptyKey || (uint32_t)(key & 0x1FFu) != kNoSlot || ox + k >= width) continue;
-                TriView t;
-                float su[3], sv[3];
-                const unsigned long long id = (key >> 9) & 0x7FFFFFFFull;
-                uint32_t grey = 255u;
-                if (setup_piece<Attr>(xyz, attr, (long long)(id >> 1), (int)(id & 1ull), mvps + s * 16, width, height, t, su, sv)) {  // (true: it produced this key)
+                const unsigned long long key = keys[k];
+                if ((key != kEmptyKey) & (ox + k < width) & !(g.dbg & 1)) {
                     Planes P;
-                    tri_planes(t, su, sv, P);
-                    grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                    Attr::planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
+                    const uint32_t grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
+                    packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
                     if (COVER) covered |= 1u << (8 * k);
                 }
-                packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
-                keys[3] = kEmptyKey;  // done
-            }
-        }
-        // the four pixels side by side: their texel fetches overlap
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const unsigned long long key = keys[k];
-            if ((key != kEmptyKey) & (ox + k < width) & !(g.dbg & 1)) {
-                Planes P;
-                Attr::planes_from_lds(lds.rec[(uint32_t)(key & 0x1FFu)], P);
-                const uint32_t grey = Attr::shade(P, args, uni, lds.attr, (float)(ox + k) + 0.5f, (float)y + 0.5f);
-                packed = (packed & ~(0xFFu << (8 * k))) | (grey << (8 * k));
-                if (COVER) covered |= 1u << (8 * k);
             }
         }
         uint8_t *dst = out + ((size_t)s * height + y) * width + ox;
@@ -1194,6 +1253,22 @@ __global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_cover_kernel
     mesh_tile_body<ColoredAttr, kBinMax, true>(xyz, red, mvps, out, width, height, {}, g, cover);
 }
 
+// The depth tile kernels.  One build, 255 bin entries per tile: its 16-word records make 49 KB of LDS, so the LDS allows three
+// workgroups per CU without a small build (profiles/depth/README.md has the resource table and what was measured).
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_depth_kernel(const float *__restrict__ xyz, const float *__restrict__ mvps,
+                                                                           uint8_t *__restrict__ out, int width, int height, DepthShade shade,
+                                                                           BinGrid g)
+{
+    mesh_tile_body<DepthAttr, kBinMax>(xyz, nullptr, mvps, out, width, height, shade, g);
+}
+
+__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_depth_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ mvps,
+                                                                                 uint8_t *__restrict__ out, int width, int height,
+                                                                                 DepthShade shade, BinGrid g, uint8_t *__restrict__ cover)
+{
+    mesh_tile_body<DepthAttr, kBinMax, true>(xyz, nullptr, mvps, out, width, height, shade, g, cover);
+}
+
 __global__ __launch_bounds__(256) void nmi_mesh_clear_kernel(unsigned long long *zbuf, size_t n, uint32_t *state, size_t n_state,
                                                              unsigned long long *clip_state)
 {
@@ -1243,7 +1318,8 @@ size_t mesh_pairs_entries(long long ntri) { return (size_t)((ntri + 255) / 256) 
 
 hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const float *mvps, int S, const MeshWork &w,
                               int layout_views, int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height,
-                              hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover)
+                              hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover,
+                              const DepthShade *depth)
 {
     if (S > layout_views) return hipErrorInvalidValue;
     WarpFuse wf{warp_frame, warp_coeffs, warp_out, 0};
@@ -1270,7 +1346,7 @@ hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long
     // triangle were in view and touched two tiles; a fuller bin than its capacity takes the per-lane path as always.  Textured only:
     // there is no small coloured build (see nmi_mesh_tile_color_kernel).
     static const bool no_small = getenv("NMI_MESH_NO_SMALL_TILES") != nullptr;   // measurement switch
-    const bool small_tiles = shading.textured && !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
+    const bool small_tiles = shading.textured && !depth && !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
     if (small_tiles && g.cap > kBinSmall - 1) g.cap = kBinSmall - 1;
     const unsigned long long clip_cap = w.clip_cap < clip_cap_limit ? w.clip_cap : clip_cap_limit;
     for (int s0 = 0; s0 < S; s0 += kMaxViewsPerLaunch) {
@@ -1313,7 +1389,13 @@ hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long
         const dim3 grid((unsigned)(views * tiles)), block(kTileThreads);
         const float *m = mvps + (size_t)s0 * 16;
         uint8_t *o = out + (size_t)s0 * width * height, *c = cover ? cover + (size_t)s0 * width * height : nullptr;
-        if (!shading.textured && cover)
+        DepthShade sh = depth ? *depth : DepthShade{};
+        if (sh.depth16) sh.depth16 += (size_t)s0 * width * height;
+        if (depth && cover)
+            hipLaunchKernelGGL(nmi_mesh_tile_depth_cover_kernel, grid, block, 0, stream, xyz, m, o, width, height, sh, g, c);
+        else if (depth)
+            hipLaunchKernelGGL(nmi_mesh_tile_depth_kernel, grid, block, 0, stream, xyz, m, o, width, height, sh, g);
+        else if (!shading.textured && cover)
             hipLaunchKernelGGL(nmi_mesh_tile_color_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g, c);
         else if (!shading.textured)
             hipLaunchKernelGGL(nmi_mesh_tile_color_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g);

@@ -9,6 +9,7 @@
 #include "nmi_kernels.h"
 #include "nmi_warp_device.h"
 #include "nmi_cloud_device.h"
+#include "nmi_depth_device.h"
 
 namespace nmi {
 
@@ -355,12 +356,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // window of any quad is covered by two aligned 16-byte loads).
 constexpr int kResolveRows = 8;
 
+// What a resolve kernel stores for four resolved keys side by side.  Without a shade (the colour renders): the keys' low bytes.
+// With one (the depth renders, nmi_depth_device.h): the grey of each key's 24 depth bits, 255 where the key is the empty one, and
+// the raw depths -- 0 there -- into shade.depth16 at pixel `at` of the stack, if given.  `quad`: all four pixels exist and may
+// leave as one store (depth16 8-byte aligned at `at`); else pixel k exists iff k < n.
+__device__ __forceinline__ uint32_t depth_quad(const DepthShade &sh, const uint32_t (&best)[4], size_t at, bool quad, int n)
+{
+    uint32_t grey[4], v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        depth_shade(sh, best[k] >> 8, v[k], grey[k]);
+        if (best[k] == 0xFFFFFFFFu) v[k] = kDepthNothing, grey[k] = kDepthBackground;
+    }
+    if (sh.depth16) {
+        if (quad)
+            *reinterpret_cast<uint2 *>(sh.depth16 + at) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+        else
+            for (int k = 0; k < 4 && k < n; ++k) sh.depth16[at + k] = (uint16_t)v[k];
+    }
+    return grey[0] | (grey[1] << 8) | (grey[2] << 16) | (grey[3] << 24);
+}
+
 // The strips of both fast kernels below.  COVER: also cover[s][y][x] = 1 where the pixel's resolved key is not empty (a point won
 // it), 0 where it kept the clear colour.
 // requires width % 4 == 0, SIZE <= 5, stride % 4 == 0, (SIZE == 1 or stride >= width + 4) and, COVER, cover 4-byte aligned
-template <int SIZE, bool COVER>
+// Shade: nothing, or one DepthShade (depth16 8-byte aligned or null) -- the depth form of the same kernel.
+template <int SIZE, bool COVER, class... Shade>
 __device__ __forceinline__ void resolve_strips(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, uint8_t *__restrict__ cover, int views,
-                                               int width, int height, int stride)
+                                               int width, int height, int stride, const Shade &...shade)
 {
     const int hp = height + SIZE - 1;
     const int quads = width >> 2, strips = (height + kResolveRows - 1) / kResolveRows;
@@ -398,7 +421,10 @@ __device__ __forceinline__ void resolve_strips(const uint32_t *__restrict__ zbuf
 #pragma unroll
                 for (int j = 1; j < SIZE; ++j) best[k] = min(best[k], h[j][k]);
             }
-            *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
+            if constexpr (sizeof...(Shade) == 0)
+                *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
+            else
+                *reinterpret_cast<uint32_t *>(dst + (size_t)r * width) = depth_quad(shade..., best, (size_t)(dst - out) + (size_t)r * width, true, 4);
             if (COVER) {
                 uint32_t bits = 0;
 #pragma unroll
@@ -409,17 +435,19 @@ __device__ __forceinline__ void resolve_strips(const uint32_t *__restrict__ zbuf
     }
 }
 
-template <int SIZE>
+template <int SIZE, class... Shade>
 __global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
-                                                                    int width, int height, int stride, const uint32_t *epoch, size_t pair_words)
+                                                                    int width, int height, int stride, const uint32_t *epoch, size_t pair_words,
+                                                                    Shade... shade)
 {
     if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // a level's double-buffered anchors: the buffer this replay splatted into
-    resolve_strips<SIZE, false>(zbuf, out, nullptr, views, width, height, stride);
+    resolve_strips<SIZE, false>(zbuf, out, nullptr, views, width, height, stride, shade...);
 }
 
 // Any size / width.
+template <class... Shade>
 __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
-                                                               int width, int height, int size, int stride)
+                                                               int width, int height, int size, int stride, Shade... shade)
 {
     const int wp = width + size - 1, hp = height + size - 1;
     const int quads = (width + 3) / 4;
@@ -440,7 +468,10 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *_
             }
         }
         uint8_t *dst = out + ((size_t)s * height + py) * width + px;
-        if (px + 3 < width && (width & 3) == 0) {
+        if constexpr (sizeof...(Shade) != 0) {  // the depth form: byte stores, as the pixels may end anywhere
+            const uint32_t grey = depth_quad(shade..., best, (size_t)(dst - out), false, width - px);
+            for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(grey >> (8 * k));
+        } else if (px + 3 < width && (width & 3) == 0) {
             *reinterpret_cast<uint32_t *>(dst) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
         } else {
             for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(best[k] & 0xFFu);  // untouched pixels keep 255
@@ -450,18 +481,20 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *_
 
 // The coverage forms of the two resolve kernels above (nmi_render_points_masked, covered levels): the same render bytes, and
 // the coverage mask beside them.
-template <int SIZE>
+template <int SIZE, class... Shade>
 __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
                                                                           uint8_t *__restrict__ cover, int views, int width, int height, int stride,
-                                                                          const uint32_t *epoch, size_t pair_words)
+                                                                          const uint32_t *epoch, size_t pair_words, Shade... shade)
 {
     if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // as nmi_zbuf_resolve_fast_kernel
-    resolve_strips<SIZE, true>(zbuf, out, cover, views, width, height, stride);
+    resolve_strips<SIZE, true>(zbuf, out, cover, views, width, height, stride, shade...);
 }
 
 // Any size / width (coverage form).
+template <class... Shade>
 __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
-                                                                     uint8_t *__restrict__ cover, int views, int width, int height, int size, int stride)
+                                                                     uint8_t *__restrict__ cover, int views, int width, int height, int size, int stride,
+                                                                     Shade... shade)
 {
     const int wp = width + size - 1, hp = height + size - 1;
     const int quads = (width + 3) / 4;
@@ -482,7 +515,10 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint3
             }
         }
         uint8_t *dst = out + ((size_t)s * height + py) * width + px;
-        if (px + 3 < width && (width & 3) == 0) {
+        if constexpr (sizeof...(Shade) != 0) {  // the depth form: byte stores, as the pixels may end anywhere
+            const uint32_t grey = depth_quad(shade..., best, (size_t)(dst - out), false, width - px);
+            for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(grey >> (8 * k));
+        } else if (px + 3 < width && (width & 3) == 0) {
             *reinterpret_cast<uint32_t *>(dst) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
         } else {
             for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(best[k] & 0xFFu);  // untouched pixels keep 255
@@ -492,55 +528,81 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint3
     }
 }
 
+// Whether a depth shade's raw depths can leave four at a time (the fast kernels' form).
+template <class... Shade>
+static bool depth16_quads(const Shade &...shade)
+{
+    return (... && (((uintptr_t)shade.depth16 & 7) == 0));
+}
+
 // The coverage forms of launch_resolve's kernels (nmi_render_points_masked): the same choice of form, the render bytes the same.
+// shade: nothing, or one DepthShade -- the depth forms of the same kernels (nmi_render_points_depth, depth levels).
+template <class... Shade>
 static void launch_resolve_cover(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, int S, int width, int height, int size, hipStream_t stream,
-                                 const uint32_t *epoch = nullptr, size_t pair_words = 0)
+                                 const uint32_t *epoch, size_t pair_words, Shade... shade)
 {
     const int stride = zbuf_stride(width, size);
     const size_t nq = (size_t)S * height * ((width + 3) / 4);
     dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
-    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && (((uintptr_t)cover & 3) == 0);
+    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && (((uintptr_t)cover & 3) == 0) &&
+                      depth16_quads(shade...);
     if (!fast) {  // (never with an epoch: launch_level_front_points checks the fast form's conditions first)
-        hipLaunchKernelGGL(nmi_zbuf_resolve_cover_kernel, grid, block, 0, stream, zbuf, out, cover, S, width, height, size, stride);
+        hipLaunchKernelGGL((nmi_zbuf_resolve_cover_kernel<Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, size, stride, shade...);
         return;
     }
     const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
     grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
     switch (size) {
-    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<1>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<2>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<3>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<4>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
-    default: hipLaunchKernelGGL(nmi_zbuf_resolve_cover_fast_kernel<5>, grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words); break;
+    case 1: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<1, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 2: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<2, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 3: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<3, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 4: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<4, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
+    default: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<5, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
     }
 }
 
+template <class... Shade>
 static void launch_resolve(const uint32_t *zbuf, uint8_t *out, int S, int width, int height, int size, hipStream_t stream,
-                           const uint32_t *epoch = nullptr, size_t pair_words = 0)
+                           const uint32_t *epoch, size_t pair_words, Shade... shade)
 {
     const int stride = zbuf_stride(width, size);
     const size_t nq = (size_t)S * height * ((width + 3) / 4);
     dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
-    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0);
+    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && depth16_quads(shade...);
     if (!fast) {  // (never with an epoch: launch_level_front_points checks resolve_fast_eligible first)
-        hipLaunchKernelGGL(nmi_zbuf_resolve_kernel, grid, block, 0, stream, zbuf, out, S, width, height, size, stride);
+        hipLaunchKernelGGL((nmi_zbuf_resolve_kernel<Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, size, stride, shade...);
         return;
     }
     const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
     grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
     switch (size) {
-    case 1: hipLaunchKernelGGL(nmi_zbuf_resolve_fast_kernel<1>, grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words); break;
-    case 2: hipLaunchKernelGGL(nmi_zbuf_resolve_fast_kernel<2>, grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words); break;
-    case 3: hipLaunchKernelGGL(nmi_zbuf_resolve_fast_kernel<3>, grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words); break;
-    case 4: hipLaunchKernelGGL(nmi_zbuf_resolve_fast_kernel<4>, grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words); break;
-    default: hipLaunchKernelGGL(nmi_zbuf_resolve_fast_kernel<5>, grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words); break;
+    case 1: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<1, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 2: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<2, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 3: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<3, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 4: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<4, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
+    default: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<5, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
     }
+}
+
+// The resolve of a render: plain or with coverage, the map's colour or (shade) its depth.
+static void launch_resolve_for(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, const DepthShade *shade, int S, int width, int height, int size,
+                               hipStream_t stream, const uint32_t *epoch = nullptr, size_t pair_words = 0)
+{
+    if (shade && cover)
+        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words, *shade);
+    else if (shade)
+        launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words, *shade);
+    else if (cover)
+        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words);
+    else
+        launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words);
 }
 
 size_t render_zbuf_words(int S, int width, int height, int size) { return (size_t)S * zbuf_stride(width, size) * (height + size - 1); }
 
 hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps, int S, uint32_t *zbuf,
-                                uint8_t *out, int width, int height, int size, hipStream_t stream, bool clear_first, uint8_t *cover)
+                                uint8_t *out, int width, int height, int size, hipStream_t stream, bool clear_first, uint8_t *cover,
+                                const DepthShade *shade)
 {
     const size_t nz = render_zbuf_words(S, width, height, size);
     const size_t n = (size_t)S * width * height;
@@ -555,10 +617,7 @@ hipError_t launch_render_points(const float *xyz, const float *red, long long np
                                mvps + (size_t)s0 * 16, views, zbuf + (size_t)s0 * per_view, width, height, size, stride);
         }
     }
-    if (cover)
-        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream);
-    else
-        launch_resolve(zbuf, out, S, width, height, size, stream);
+    launch_resolve_for(zbuf, out, cover, shade, S, width, height, size, stream);
     (void)n;
     return hipGetLastError();
 }
@@ -590,10 +649,11 @@ size_t level_zbuf_pair_words(int S, int width, int height, int size) { return (r
 hipError_t launch_level_front_points(const void *packed, long long npoints, const float *mvps, int S, uint32_t *zbuf, const uint32_t *epoch,
                                      uint8_t *out, int width, int height, int size, const uint8_t *frame, const float *coeffs, uint8_t *warps,
                                      int Wn, hipStream_t stream, const uint32_t *kept, const uint32_t *kept_count, int compute_units,
-                                     uint8_t *cover)
+                                     uint8_t *cover, const DepthShade *shade)
 {
     if (S > kMaxViewsPerLaunch || !warp_lds_eligible(frame, warps, width) || !kept || !kept_count) return hipErrorInvalidValue;
     if (cover && ((uintptr_t)cover & 3) != 0) return hipErrorInvalidValue;
+    if (shade && !depth16_quads(*shade)) return hipErrorInvalidValue;
     if (!((width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0))) return hipErrorInvalidValue;
     size_t off = 0;
     (void)cloud_pack_bytes(npoints, &off);
@@ -613,10 +673,7 @@ hipError_t launch_level_front_points(const void *packed, long long npoints, cons
     hipLaunchKernelGGL(nmi_level_front_kernel, dim3((unsigned)(warp_blocks + splat_blocks + clear_blocks)), dim3(256), 0, stream, pc, npoints, mvps,
                        S, zbuf, pair_words, epoch, width, height, size, stride, frame, coeffs, warps, warp_blocks, (int)splat_blocks, clear_blocks,
                        kept, kept_count);
-    if (cover)
-        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words);
-    else
-        launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words);
+    launch_resolve_for(zbuf, out, cover, shade, S, width, height, size, stream, epoch, pair_words);
     return hipGetLastError();
 }
 
