@@ -994,157 +994,118 @@ class NmiContext:
             self.synchronize()
         return out
 
-    def render_points_masked(self, xyz, red, mvps, point_size, out=None, out_masks=None, sync=True):
-        """render_points plus its coverage (nmi_render_points_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
-        where a point won the pixel, 0 where it kept the background; bottom-up rows like the renders, which are
-        byte-identical to render_points'.  out_masks may be uint8 or bool (default uint8)."""
+    def _new_stack(self, S, dtype=None):
         import torch
-        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
+        return torch.empty((S, self.height, self.width), dtype=dtype or torch.uint8, device=self.device)
+
+    def _out_masks(self, S, out_masks):
+        """The out_masks stack of a masked render of S views: made if None, else checked -> (what the caller gets back, its bytes)."""
         if out_masks is None:
-            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
+            out_masks = self._new_stack(S)
         om = self._mask_stack(out_masks, "out_masks")
-        if om.shape[0] != m.shape[0]:
+        if om.shape[0] != S:
             raise ValueError("out_masks has the wrong number of views")
-        out = self._render_points(xyz, red, m, point_size, out, om)
-        if sync:
-            self.synchronize()
-        return out, out_masks
+        return out_masks, om
 
-    def render_mesh_masked(self, xyz, uv, texture, mvps, out=None, out_masks=None, sync=True):
-        """render_mesh plus its coverage (nmi_render_mesh_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
-        where a triangle won the pixel, 0 where it kept the background; the renders are byte-identical to render_mesh's."""
-        import torch
+    def _render(self, mvps, out, sync, call, name, masked=False, out_masks=None):
+        """What the colour renders share: host MVPs as float32 [S,16], the render stack (made if None), with `masked` the masks stack,
+        ordering after torch, and the C call -- call(S, mvps pointer, out pointer[, masks pointer]) -> status of the C function `name`.
+        -> out, or (out, out_masks)."""
         m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
-        if out_masks is None:
-            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
-        om = self._mask_stack(out_masks, "out_masks")
-        if om.shape[0] != m.shape[0]:
-            raise ValueError("out_masks has the wrong number of views")
-        out = self._render_mesh(xyz, uv, texture, m, out, om)
+        S = m.shape[0]
+        ptrs = ()
+        if masked:
+            out_masks, om = self._out_masks(S, out_masks)
+            ptrs = (om.data_ptr(),)
+        if out is None:
+            out = self._new_stack(S)
+        o = self._stack(out, "out")
+        self._order_after_torch()
+        self._check(call(S, m.ctypes.data_as(C.POINTER(C.c_float)), o.data_ptr(), *ptrs), name)
         if sync:
             self.synchronize()
-        return out, out_masks
+        return (out, out_masks) if masked else out
 
-    def render_points(self, xyz, red, mvps, point_size, out=None, sync=True):
-        """Rendering<4>::renderToTextureOnGPU without OpenGL: device float32 xyz [N,3] + red [N], host MVPs [S,16]
-        (render_mvp) -> render stack [S,H,W] u8 on the device, bottom-up rows, background 255."""
-        out = self._render_points(xyz, red, mvps, point_size, out, None)
-        if sync:
-            self.synchronize()
-        return out
-
-    def _render_points(self, xyz, red, mvps, point_size, out, masks):
+    @staticmethod
+    def _cloud_tensors(xyz, red):
         import torch
         for t, shape in ((xyz, 2), (red, 1)):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != shape:
                 raise TypeError("xyz must be a contiguous float32 device tensor [N,3], red one of [N]")
-        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
-        S = m.shape[0]
-        if out is None:
-            out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
-        o = self._stack(out, "out")
-        self._order_after_torch()
-        if masks is None:
-            self._check(self._lib.nmi_render_points(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0],
-                                                    m.ctypes.data_as(C.POINTER(C.c_float)), S, float(point_size), o.data_ptr()),
-                        "nmi_render_points")
-        else:
-            self._check(self._lib.nmi_render_points_masked(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0],
-                                                           m.ctypes.data_as(C.POINTER(C.c_float)), S, float(point_size), o.data_ptr(),
-                                                           masks.data_ptr()), "nmi_render_points_masked")
-        return out
 
-    def render_mesh(self, xyz, uv, texture, mvps, out=None, sync=True):
-        """Rendering<1>::renderToTextureOnGPU without OpenGL: device float32 corner arrays xyz [3T,3], uv [3T,2], an
-        NmiTexture, host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
-        out = self._render_mesh(xyz, uv, texture, mvps, out, None)
-        if sync:
-            self.synchronize()
-        return out
-
-    def _render_mesh(self, xyz, uv, texture, mvps, out, masks):
+    @staticmethod
+    def _mesh_tensors(xyz, uv):
         import torch
         for t, cols in ((xyz, 3), (uv, 2)):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols:
                 raise TypeError("xyz / uv must be contiguous float32 device tensors [3T,3] / [3T,2]")
         if xyz.shape[0] != uv.shape[0] or xyz.shape[0] % 3:
             raise ValueError("xyz and uv must hold three corners per triangle")
-        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
-        S = m.shape[0]
-        if out is None:
-            out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
-        o = self._stack(out, "out")
-        self._order_after_torch()
-        if masks is None:
-            self._check(self._lib.nmi_render_mesh(self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h,
-                                                  m.ctypes.data_as(C.POINTER(C.c_float)), S, o.data_ptr()), "nmi_render_mesh")
-        else:
-            self._check(self._lib.nmi_render_mesh_masked(self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h,
-                                                         m.ctypes.data_as(C.POINTER(C.c_float)), S, o.data_ptr(), masks.data_ptr()),
-                        "nmi_render_mesh_masked")
-        return out
 
-    def render_mesh_colored(self, xyz, red, mvps, out=None, sync=True):
-        """A vertex-coloured mesh (nmi_render_mesh_colored): device float32 corner arrays xyz [3T,3] and red [3T] (one colour per
-        corner, no texture), host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
-        out = self._render_mesh_colored(xyz, red, mvps, out, None)
-        if sync:
-            self.synchronize()
-        return out
-
-    def render_mesh_colored_masked(self, xyz, red, mvps, out=None, out_masks=None, sync=True):
-        """render_mesh_colored plus its coverage (nmi_render_mesh_colored_masked) -> (renders [S,H,W] u8, masks [S,H,W]), as
-        render_mesh_masked."""
-        import torch
-        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
-        if out_masks is None:
-            out_masks = torch.empty((m.shape[0], self.height, self.width), dtype=torch.uint8, device=self.device)
-        om = self._mask_stack(out_masks, "out_masks")
-        if om.shape[0] != m.shape[0]:
-            raise ValueError("out_masks has the wrong number of views")
-        out = self._render_mesh_colored(xyz, red, m, out, om)
-        if sync:
-            self.synchronize()
-        return out, out_masks
-
-    def _render_mesh_colored(self, xyz, red, mvps, out, masks):
+    @staticmethod
+    def _colored_mesh_tensors(xyz, red):
         import torch
         for t, dims in ((xyz, 2), (red, 1)):
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != dims or (dims == 2 and t.shape[1] != 3):
                 raise TypeError("xyz / red must be contiguous float32 device tensors [3T,3] / [3T]")
         if xyz.shape[0] != red.shape[0] or xyz.shape[0] % 3:
             raise ValueError("xyz and red must hold three corners per triangle")
-        m = np.ascontiguousarray(mvps, np.float32).reshape(-1, 16)
-        S = m.shape[0]
-        if out is None:
-            out = torch.empty((S, self.height, self.width), dtype=torch.uint8, device=self.device)
-        o = self._stack(out, "out")
-        self._order_after_torch()
-        mp = m.ctypes.data_as(C.POINTER(C.c_float))
-        if masks is None:
-            self._check(self._lib.nmi_render_mesh_colored(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S, o.data_ptr()),
-                        "nmi_render_mesh_colored")
-        else:
-            self._check(self._lib.nmi_render_mesh_colored_masked(self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S,
-                                                                 o.data_ptr(), masks.data_ptr()), "nmi_render_mesh_colored_masked")
-        return out
+
+    def render_points_masked(self, xyz, red, mvps, point_size, out=None, out_masks=None, sync=True):
+        """render_points plus its coverage (nmi_render_points_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
+        where a point won the pixel, 0 where it kept the background; bottom-up rows like the renders, which are
+        byte-identical to render_points'.  out_masks may be uint8 or bool (default uint8)."""
+        self._cloud_tensors(xyz, red)
+        return self._render(mvps, out, sync, lambda S, mp, o, om: self._lib.nmi_render_points_masked(
+            self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0], mp, S, float(point_size), o, om), "nmi_render_points_masked", True, out_masks)
+
+    def render_mesh_masked(self, xyz, uv, texture, mvps, out=None, out_masks=None, sync=True):
+        """render_mesh plus its coverage (nmi_render_mesh_masked) -> (renders [S,H,W] u8, masks [S,H,W]): mask bytes are 1
+        where a triangle won the pixel, 0 where it kept the background; the renders are byte-identical to render_mesh's."""
+        self._mesh_tensors(xyz, uv)
+        return self._render(mvps, out, sync, lambda S, mp, o, om: self._lib.nmi_render_mesh_masked(
+            self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h, mp, S, o, om), "nmi_render_mesh_masked", True, out_masks)
+
+    def render_points(self, xyz, red, mvps, point_size, out=None, sync=True):
+        """Rendering<4>::renderToTextureOnGPU without OpenGL: device float32 xyz [N,3] + red [N], host MVPs [S,16]
+        (render_mvp) -> render stack [S,H,W] u8 on the device, bottom-up rows, background 255."""
+        self._cloud_tensors(xyz, red)
+        return self._render(mvps, out, sync, lambda S, mp, o: self._lib.nmi_render_points(
+            self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0], mp, S, float(point_size), o), "nmi_render_points")
+
+    def render_mesh(self, xyz, uv, texture, mvps, out=None, sync=True):
+        """Rendering<1>::renderToTextureOnGPU without OpenGL: device float32 corner arrays xyz [3T,3], uv [3T,2], an
+        NmiTexture, host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
+        self._mesh_tensors(xyz, uv)
+        return self._render(mvps, out, sync, lambda S, mp, o: self._lib.nmi_render_mesh(
+            self._h, xyz.data_ptr(), uv.data_ptr(), xyz.shape[0] // 3, texture._h, mp, S, o), "nmi_render_mesh")
+
+    def render_mesh_colored(self, xyz, red, mvps, out=None, sync=True):
+        """A vertex-coloured mesh (nmi_render_mesh_colored): device float32 corner arrays xyz [3T,3] and red [3T] (one colour per
+        corner, no texture), host MVPs [S,16] -> render stack [S,H,W] u8 on the device (bottom-up rows, background 255)."""
+        self._colored_mesh_tensors(xyz, red)
+        return self._render(mvps, out, sync, lambda S, mp, o: self._lib.nmi_render_mesh_colored(
+            self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S, o), "nmi_render_mesh_colored")
+
+    def render_mesh_colored_masked(self, xyz, red, mvps, out=None, out_masks=None, sync=True):
+        """render_mesh_colored plus its coverage (nmi_render_mesh_colored_masked) -> (renders [S,H,W] u8, masks [S,H,W]), as
+        render_mesh_masked."""
+        self._colored_mesh_tensors(xyz, red)
+        return self._render(mvps, out, sync, lambda S, mp, o, om: self._lib.nmi_render_mesh_colored_masked(
+            self._h, xyz.data_ptr(), red.data_ptr(), xyz.shape[0] // 3, mp, S, o, om), "nmi_render_mesh_colored_masked", True, out_masks)
 
     def _depth_outputs(self, S, out, out_masks, depth16):
         """The three stacks of a depth render: grey (made if None), masks and raw depths (None, True = make one, or a tensor)."""
         import torch
         shape = (S, self.height, self.width)
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            out = self._new_stack(S)
         o = self._stack(out, "out")
-        if out_masks is True:
-            out_masks = torch.empty(shape, dtype=torch.uint8, device=self.device)
         om = None
         if out_masks is not None:
-            om = self._mask_stack(out_masks, "out_masks")
-            if om.shape[0] != S:
-                raise ValueError("out_masks has the wrong number of views")
+            out_masks, om = self._out_masks(S, None if out_masks is True else out_masks)
         if depth16 is True:
-            depth16 = torch.empty(shape, dtype=torch.int16, device=self.device)
+            depth16 = self._new_stack(S, torch.int16)
         if depth16 is not None and not (depth16.is_cuda and depth16.element_size() == 2 and depth16.is_contiguous()
                                         and tuple(depth16.shape) == shape):
             raise TypeError(f"depth16 must be a contiguous 16-bit device tensor {shape}")

@@ -217,11 +217,21 @@ static int level_capture(nmi_level *lv)
     hipGraphExec_t exec = nullptr;
     hipStream_t st = ctx->stream;
     if (ok.e == hipSuccess && ok(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal))) {
+        nmi::FusedCloud cloud{};  // a fused point-cloud level's packed cloud and kept list; else empty
+        if (lv->fused_points) {
+            cloud.packed = d_packed, cloud.npoints = n_points;
+            cloud.h_bound = hd_mvps + (size_t)S * 16;
+            cloud.kept = d_kept, cloud.kept_count = d_kept_count;
+        }
+        nmi::LevelPrep prep{};
+        prep.h_mvps = hd_mvps, prep.d_mvps = d_mvps, prep.n_mvps = S * 16 + nmi::kLevelMvpExtra;
+        prep.h_coeffs = hd_coeffs, prep.d_coeffs = d_coeffs, prep.n_coeffs = Wn * 9;
+        prep.key = lv->d_key.as<unsigned long long>();
         // (mesh: nothing to clear -- the renderer leaves its work area clean)
-        ok(nmi::launch_level_prep(hd_mvps, d_mvps, S * 16 + nmi::kLevelMvpExtra, hd_coeffs, d_coeffs, Wn * 9, lv->d_key.as<unsigned long long>(), d_zbuf,
-                                  (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size), st,
-                                  d_epoch, lv->fused_points ? d_packed : nullptr, n_points,
-                                  lv->fused_points ? hd_mvps + (size_t)S * 16 : nullptr, d_kept, d_kept_count));
+        prep.zbuf = d_zbuf, prep.nz = (mesh || lv->fused_points) ? 0 : nmi::render_zbuf_words(S, p.width, p.height, lv->size);
+        prep.epoch = d_epoch;
+        prep.cloud = cloud;
+        ok(nmi::launch_level_prep(prep, st));
         ok(launch_intake(in, lv->tone_work, lv->d_frame, in.frame_pitch, set.d_frame_mask, d_small, d_ud, ud_mask, valid, p.width, p.height,
                          st));
         // One chain of kernels when the warp blocks can ride along with the render's first kernel (the usual case: frame rows
@@ -241,17 +251,17 @@ static int level_capture(nmi_level *lv)
             if (covered) ok(nmi::launch_warp_masks(d_frame_mask, d_coeffs, d_masks, p.width, p.height, Wn, lv->side));
             ok(hipEventRecord(lv->ev_join, lv->side));
         }
+        // The render, by whichever of the three renderers the level uses: the same target, views and (fused) ride-along warp.
+        const nmi::RenderTarget target = render_target(ctx, d_renders, cover, depth);
+        const nmi::RenderViews views{d_mvps, S};
+        nmi::RideAlongWarp warp{};
+        if (fused) warp.frame = d_frame, warp.coeffs = d_coeffs, warp.out = d_warps, warp.Wn = Wn;
         if (mesh)
-            ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, d_mvps, S, lv->mesh.view, S,
-                                       (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511), ctx->clip_queue_limit, d_renders,
-                                       p.width, p.height, st, fused ? d_frame : nullptr, d_coeffs, d_warps, Wn, cover, depth));
+            ok(nmi::launch_render_mesh(d_xyz, mesh_shading(lv->kind, d_attr, tex), n_points, views, lv->mesh.view, mesh_limits(ctx, S), target, st, warp));
         else if (fused)
-            ok(nmi::launch_level_front_points(d_packed, n_points, d_mvps, S, d_zbuf, d_epoch, d_renders, p.width, p.height,
-                                              lv->size, d_frame, d_coeffs, d_warps, Wn, st, d_kept, d_kept_count, ctx->compute_units,
-                                              cover, depth));
+            ok(nmi::launch_level_front_points(cloud, views, d_zbuf, d_epoch, lv->size, ctx->compute_units, target, warp, st));
         else
-            ok(nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, d_zbuf, d_renders, p.width, p.height, lv->size, st,
-                                         /*clear_first=*/false, cover, depth));
+            ok(nmi::launch_render_points(d_xyz, d_red, n_points, views, d_zbuf, lv->size, target, st, /*clear_first=*/false));
         if (!fused || masked || covered) ok(hipStreamWaitEvent(st, lv->ev_join, 0));
         if (masked || covered)
             ok(launch_mask_search(ms, lv->pix, lv->pix ? pix_owner_share(ctx, lv->pix) : 0.0, workgroups, true, false, d_epoch,

@@ -242,8 +242,8 @@ int render_points_impl(nmi_ctx *ctx, const float *d_xyz, const float *d_red, int
     float *d_mvps = nullptr;
     const int src = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (src != NMI_OK) return src;
-    NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, d_mvps, S, ctx->d_zbuf.as<uint32_t>(), d_render_stack, ctx->params.width,
-                                               ctx->params.height, size, ctx->stream, true, cover, depth));
+    NMI_HIP_TRY(ctx, nmi::launch_render_points(d_xyz, d_red, n_points, nmi::RenderViews{d_mvps, S}, ctx->d_zbuf.as<uint32_t>(), size,
+                                               render_target(ctx, d_render_stack, cover, depth), ctx->stream));
     return NMI_OK;
 }
 
@@ -259,13 +259,9 @@ int depth_shade_check(const nmi_depth_shade *shade, nmi::DepthShade *out)
 
 }  // namespace nmi_internal
 
-extern "C" {
-
 // ---------------------------------------------------------------------------------------------------------
 // Textured-mesh renderer: texture object (mip chain -> per-level luma on the device) and the draw call.
 // ---------------------------------------------------------------------------------------------------------
-}  // extern "C"
-
 extern "C" {
 
 int nmi_texture_destroy(nmi_texture *tex)
@@ -404,10 +400,8 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
     float *d_mvps = nullptr;
     int rc = stage_floats(ctx, ctx->mvp_ring, h_mvps, (size_t)S * 16, &d_mvps);
     if (rc != NMI_OK) return rc;
-    const int bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
-    const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, d_mvps, S, ctx->mesh.view, ctx->mesh_views, bin_cap,
-                                                 ctx->clip_queue_limit, d_render_stack, ctx->params.width, ctx->params.height, ctx->stream, nullptr,
-                                                 nullptr, nullptr, 0, cover, depth);
+    const hipError_t e = nmi::launch_render_mesh(d_xyz, mesh_shading(kind, d_attr, tex), n_triangles, nmi::RenderViews{d_mvps, S}, ctx->mesh.view,
+                                                 mesh_limits(ctx, ctx->mesh_views), render_target(ctx, d_render_stack, cover, depth), ctx->stream);
     if (e != hipSuccess) {
         ctx->mesh_views = 0;  // whatever state the buffers are in: allocate and clear afresh next time
         return hip_fail(ctx, e, "launch_render_mesh");
@@ -419,6 +413,23 @@ nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_textu
 {
     if (kind == MapKind::textured_mesh) return nmi::MeshShading{true, d_attr, tex->d_luma.as<float>(), tex->levels, tex->w, tex->h, tex->off};
     return nmi::MeshShading{false, d_attr};
+}
+
+nmi::RenderTarget render_target(const nmi_ctx *ctx, uint8_t *out, uint8_t *cover, const nmi::DepthShade *depth)
+{
+    nmi::RenderTarget t{};
+    t.out = out, t.cover = cover, t.depth = depth;
+    t.width = ctx->params.width, t.height = ctx->params.height;
+    return t;
+}
+
+nmi::MeshLimits mesh_limits(const nmi_ctx *ctx, int layout_views)
+{
+    nmi::MeshLimits l{};
+    l.layout_views = layout_views;
+    l.bin_cap = (int)(ctx->tile_queue_limit < 511 ? ctx->tile_queue_limit : 511);
+    l.clip_cap = ctx->clip_queue_limit;
+    return l;
 }
 
 }  // namespace nmi_internal

@@ -266,6 +266,9 @@ int render_mesh_impl(nmi_ctx *ctx, MapKind kind, const float *d_xyz, const float
 // form of the shade (depth16 null) in *out, or NMI_ERR_INVALID_ARGUMENT.
 int depth_shade_check(const nmi_depth_shade *shade, nmi::DepthShade *out);
 nmi::MeshShading mesh_shading(MapKind kind, const float *d_attr, const nmi_texture *tex);  // launch_render_mesh's description of a mesh kind
+// The renderers' records as a context fills them: a render of the context's frame size; the mesh renderer's queue limits (NMI_OPT_*).
+nmi::RenderTarget render_target(const nmi_ctx *ctx, uint8_t *out, uint8_t *cover, const nmi::DepthShade *depth);
+nmi::MeshLimits mesh_limits(const nmi_ctx *ctx, int layout_views);
 int check_grid_args(nmi_ctx *ctx, const uint8_t *render_stack, int S_local, int s_offset, int S_total, const uint8_t *warp_stack,
                     int Wn);
 

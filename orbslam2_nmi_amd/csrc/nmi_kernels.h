@@ -171,8 +171,7 @@ hipError_t launch_depth_shade_apply(const DepthShade &shade, const uint32_t *dep
 
 // Mesh renderer (nmi_mesh.hip): a binned, deferred rasteriser for textured and for vertex-coloured meshes.  MeshWork = its device buffers, owned by a context
 // or by a level; zbuf must be all ones and state all zero before a render (launch_mesh_clear once after allocation) and
-// the renderer leaves them so.  bin_cap_limit: usable entries per bin (NMI_OPT_TILE_QUEUE; 0 = every triangle is
-// rasterised by its own lane); clip_cap_limit likewise for the queue of triangles crossing the near plane.
+// the renderer leaves them so.
 struct MeshWork {
     unsigned long long *zbuf = nullptr;        // [S][H][W] visibility keys of the direct path (mesh_zbuf_bytes)
     uint32_t *bins = nullptr;                  // [S][tiles][stride] bin entries (mesh_bins_bytes)
@@ -191,6 +190,29 @@ size_t mesh_bins_bytes(int S, int width, int height);
 size_t mesh_state_bytes(int S, int width, int height);
 size_t mesh_clip_item_bytes();
 hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hipStream_t stream);
+// What the renderers below share.  Plain records, filled by name where a draw is put together.
+constexpr int kMaxViewsPerLaunch = 64;  // views one launch of a splat or binning kernel takes (a lane per view in their culling tests)
+// Where a render goes.
+struct RenderTarget {
+    uint8_t *out;              // [S][H][W]
+    uint8_t *cover;            // coverage masks [S][H][W] (1 where a point or fragment won the pixel, 0 where it kept the clear colour), or null
+    const DepthShade *depth;   // the depth render of the same map: every pixel shaded from its winner's depth, no colour read; or null
+    int width, height;
+};
+// The views of a draw, in device memory.
+struct RenderViews {
+    const float *mvps;         // [S][16] column-major
+    int S;
+};
+// A captured level's warp stack, made by extra workgroups of the render's first kernel (level_front_eligible must hold).
+// All null: none.
+struct RideAlongWarp {
+    const uint8_t *frame;
+    const float *coeffs;       // [Wn][9] inverse maps
+    uint8_t *out;
+    int Wn;
+};
+
 // How a fragment gets its grey: from a texture at the corners' uv, or from the corners' own colours.
 struct MeshShading {
     bool textured;
@@ -201,24 +223,20 @@ struct MeshShading {
     const int *lw = nullptr, *lh = nullptr;
     const long long *loff = nullptr;
 };
-hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const float *mvps /*[S][16]*/, int S, const MeshWork &w,
-                              int layout_views /* views the work area was allocated for (>= S) */, int bin_cap_limit,
-                              unsigned long long clip_cap_limit, uint8_t *out, int width, int height, hipStream_t stream,
-                              // a captured level: the Wn warps of `warp_frame` are made by extra workgroups of the first kernel
-                              // (level_front_eligible must hold; needs at least one triangle and S <= 64)
-                              const uint8_t *warp_frame = nullptr, const float *warp_coeffs = nullptr, uint8_t *warp_out = nullptr, int Wn = 0,
-                              // coverage masks [S][H][W] (1 where a fragment won the pixel, 0 where it kept the clear colour), or null
-                              uint8_t *cover = nullptr,
-                              // the depth render of the same mesh: every pixel shaded from its winner's depth, no attribute read
-                              const DepthShade *depth = nullptr);
+struct MeshLimits {
+    int layout_views;              // views the work area was allocated for (>= S)
+    int bin_cap;                   // usable entries per bin (NMI_OPT_TILE_QUEUE; 0 = every triangle is rasterised by its own lane)
+    unsigned long long clip_cap;   // likewise for the queue of triangles crossing the near plane
+};
+// (a ride-along warp needs at least one triangle and S <= kMaxViewsPerLaunch)
+hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const RenderViews &views, const MeshWork &w,
+                              const MeshLimits &limits, const RenderTarget &target, hipStream_t stream, const RideAlongWarp &warp = {});
 // Words between rows of the renderers' anchor / depth buffer: the padded width, rounded so that the resolve pass can
 // read 8 consecutive anchors of any output quad with two aligned 16-byte loads (point sizes > 1); width for size 1.
 inline int zbuf_stride(int width, int size) { return size > 1 ? ((width + size - 1 + 3) & ~3) + 4 : width; }
 size_t render_zbuf_words(int S, int width, int height, int size);
-hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps /*[S][16] column-major*/,
-                                int S, uint32_t *zbuf /*[render_zbuf_words]*/, uint8_t *out, int width, int height, int size, hipStream_t stream,
-                                bool clear_first = true, uint8_t *cover = nullptr /* [S][H][W]: 1 where a point won the pixel, or null */,
-                                const DepthShade *shade = nullptr /* the depth render: the resolve shades from the winner's depth */);
+hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const RenderViews &views, uint32_t *zbuf /*[render_zbuf_words]*/,
+                                int size, const RenderTarget &target, hipStream_t stream, bool clear_first = true);
 // nmi_sort.hip: records (na floats each in `a`, the first 3 * verts being vertices; nb floats each in `b`, may be null) into
 // Morton order of their positions.  Drains the stream.
 hipError_t sort_records_morton(const float *a, int na, int verts, const float *b, int nb, long long n, float *a_out, float *b_out,
@@ -232,16 +250,32 @@ void level_views_bound(const float *mvps /*[S][16] column-major*/, int S, float 
 constexpr int kLevelMvpExtra = 28;  // floats behind a level's S matrices: those planes (24), the replay's parity as a word, padding
 bool level_points_double_buffered(int width, int size);  // the fused front kernel's form of the anchors: two buffers, cleared in turn
 size_t level_zbuf_pair_words(int S, int width, int height, int size);
-hipError_t launch_level_front_points(const void *packed, long long npoints, const float *mvps, int S, uint32_t *zbuf /* two buffers */,
-                                     const uint32_t *epoch, uint8_t *out, int width, int height, int size, const uint8_t *frame,
-                                     const float *coeffs, uint8_t *warps, int Wn, hipStream_t stream,
-                                     const uint32_t *kept /* [ceil(n / 64)]: wavefronts in reach of a view, made by the prep kernel */,
-                                     const uint32_t *kept_count /* [2], by replay parity */, int compute_units,
-                                     uint8_t *cover = nullptr /* [S][H][W] coverage masks (4-byte aligned), as launch_render_points */,
-                                     const DepthShade *shade = nullptr /* as launch_render_points; depth16 8-byte aligned */);
-hipError_t launch_level_prep(const float *h_mvps, float *d_mvps, int n_mvps, const float *h_coeffs, float *d_coeffs, int n_coeffs,
-                             unsigned long long *key, uint32_t *zbuf, size_t nz, hipStream_t stream, uint32_t *epoch = nullptr,
-                             const void *packed = nullptr, long long npoints = 0, const float *h_bound /* pinned: 24 floats + parity word */ = nullptr,
-                             uint32_t *kept = nullptr, uint32_t *kept_count = nullptr);
+// The packed cloud of a fused point-cloud level and the list of its wavefronts in reach of a view, which the prep kernel makes and
+// the front kernel walks.
+struct FusedCloud {
+    const void *packed;
+    long long npoints;
+    const float *h_bound;      // pinned: 24 floats (level_views_bound) + the replay's parity word
+    uint32_t *kept;            // [ceil(n / 64)]
+    uint32_t *kept_count;      // [2], by replay parity
+};
+// (S <= kMaxViewsPerLaunch; target.cover 4-byte aligned, target.depth->depth16 8-byte aligned)
+hipError_t launch_level_front_points(const FusedCloud &cloud, const RenderViews &views, uint32_t *zbuf /* two buffers */, const uint32_t *epoch,
+                                     int size, int compute_units, const RenderTarget &target, const RideAlongWarp &warp, hipStream_t stream);
+// The first node of a captured level (nmi_level_prep_kernel).
+struct LevelPrep {
+    const float *h_mvps;       // pinned -> device, n_mvps floats
+    float *d_mvps;
+    int n_mvps;
+    const float *h_coeffs;     // likewise
+    float *d_coeffs;
+    int n_coeffs;
+    unsigned long long *key;   // reset
+    uint32_t *zbuf;            // nz anchors to clear (0: none)
+    size_t nz;
+    uint32_t *epoch;           // bumped, or null
+    FusedCloud cloud;          // a fused point-cloud level's culling pass: all of its pointers or none (and then nz = 0)
+};
+hipError_t launch_level_prep(const LevelPrep &p, hipStream_t stream);
 
 }  // namespace nmi

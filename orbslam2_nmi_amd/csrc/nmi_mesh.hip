@@ -29,8 +29,9 @@
 //                         out the pixel pairs of the records' boxes in uniform chunks and resolve visibility with ds_min_u64,
 //                         then every pixel is shaded ONCE, by the triangle that won it (deferred: attributes, LOD and texture
 //                         are not spent on hidden or uncovered pixels, and every lane has a pixel), and leaves as a byte of
-//                         the render -- four pixels side by side per lane and step, one dword store.  Two builds: 255 bin
-//                         entries per tile (two workgroups per CU) or 127 (nmi_mesh_tile_small_kernel: three).
+//                         the render -- four pixels side by side per lane and step, one dword store.  One template over
+//                         <Attr, BINMAX, COVER>; textured has two builds: 255 bin entries per tile (two workgroups per CU)
+//                         or 127 (three).
 // Visibility key = depth24 << 40 | triangle << 10 | piece << 9 | slot: smaller depth wins, equal depths go to the triangle
 // drawn first (GL_LESS keeps the earlier fragment of glDrawArrays' order) -- deterministic whatever the order of the
 // atomics.  Pixels won through the memory buffer (small triangles, bin overflow) carry slot 0x1FF and set their triangle up
@@ -39,12 +40,11 @@
 //
 //
 // Vertex-coloured meshes (a colour per corner, no texture; shaders/ShadingWithColor.*) take the same passes up to the tile kernel,
-// which read positions only; the last stage is mesh_tile_body<Attr, ...> over an attribute policy, TexturedAttr or ColoredAttr,
-// behind tile kernels of their own names (nmi_mesh_tile_color_kernel, its cover form).
+// which read positions only; the last stage is nmi_mesh_tile_kernel<Attr, ...> over an attribute policy, TexturedAttr or ColoredAttr.
 //
-// Depth renders (nmi_render_mesh_depth, depth levels) take the same passes too and end in mesh_tile_body<DepthAttr, ...>: no
+// Depth renders (nmi_render_mesh_depth, depth levels) take the same passes too and end in nmi_mesh_tile_kernel<DepthAttr, ...>: no
 // attribute is read, the records hold the visibility fields only, and a pixel's grey is the depth shade (nmi_depth_device.h) of
-// the 24 depth bits of the key that won it, whichever way that key came (nmi_mesh_tile_depth_kernel, its cover form).
+// the 24 depth bits of the key that won it, whichever way that key came.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -57,7 +57,6 @@ namespace nmi {
 
 namespace {
 
-constexpr int kMaxViewsPerLaunch = 64;
 constexpr int kTile = 64;
 constexpr int kBinMax = 256;           // largest bin stride; slots 0 .. 254 are usable
 constexpr int kTileThreads = 512;      // 8 wavefronts per tile, two tiles resident per CU (60 KiB of LDS each)
@@ -805,6 +804,7 @@ struct TexturedAttr {
     using Uniform = TexLevel;      // what every lane holds for the shading loop: level 0
     static constexpr bool kDepth = false;
     static constexpr int kRecordWords = 28;   // planes: xr, yr, s0, r0, sx, rx, sy, ry, q0, qx, qy
+    static constexpr int kSmallWavesPerEu = 6;   // there is a 127-entry build, held to that many wavefronts per SIMD (0: no such build)
 
     static __device__ __forceinline__ void load_corner(const float *__restrict__ uv, long long corner, float &u, float &v)
     {
@@ -842,6 +842,7 @@ struct ColoredAttr {
     struct Uniform {};
     static constexpr bool kDepth = false;
     static constexpr int kRecordWords = 24;   // planes: xr, yr, s0, sx, sy, q0, qx, qy
+    static constexpr int kSmallWavesPerEu = 0;
 
     static __device__ __forceinline__ void load_corner(const float *__restrict__ red, long long corner, float &u, float &v)
     {
@@ -878,6 +879,7 @@ struct DepthAttr {
     // R_XW .. R_ID: everything below R_PLANES.  255 records are 16 KB; with the keys 49 KB, which lets three workgroups share a CU.
     // (17 words, an odd stride against LDS bank conflicts between records, measured slower: profiles/depth/README.md.)
     static constexpr int kRecordWords = 16;
+    static constexpr int kSmallWavesPerEu = 0;
 
     static __device__ __forceinline__ void load_corner(const float *__restrict__, long long, float &u, float &v) { u = 0.0f, v = 0.0f; }
     static __device__ __forceinline__ void fill_lds(const Args &, int, Lds &) {}
@@ -1198,75 +1200,49 @@ __device__ __forceinline__ void mesh_tile_body(const float *__restrict__ xyz, co
     }
 }
 
-// Two builds of the tile kernel.  The usual one holds 255 bin entries per tile (62 KB of LDS: two workgroups per CU).  For a mesh
+// The tile kernel: one instantiation per policy, bin capacity and coverage.  Array: `const float *`, the policy's attribute
+// array, or nothing for the policy that reads none (an unread pointer in that place splits the depth kernels' scalar loads of
+// their arguments).  A policy without Args (coloured) and a build without coverage leave those arguments unread.
+//
+// Textured: two builds.  The usual one holds 255 bin entries per tile (62 KB of LDS: two workgroups per CU).  For a mesh
 // whose tiles cannot fill that -- launch_render_mesh decides from the triangle count -- the small one holds 127 (48 KB) and is
-// held to 80 registers, so that THREE workgroups share a CU: the kernel spends half its wave-cycles waiting (set-up, barriers,
-// texel fetches), and a third workgroup to switch to is worth more than the spills the register cap costs (93.5 -> 81.5 us at
-// 4,800 triangles, same box).
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_kernel(const float *__restrict__ xyz, const float *__restrict__ uv,
-                                                                     const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                     int height, MeshTexture tex, BinGrid g)
-{
-    mesh_tile_body<TexturedAttr, kBinMax>(xyz, uv, mvps, out, width, height, tex, g);
-}
-
-constexpr int kBinSmall = 128;
-
-__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void nmi_mesh_tile_small_kernel(
-    const float *__restrict__ xyz, const float *__restrict__ uv, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width, int height,
-    MeshTexture tex, BinGrid g)
-{
-    mesh_tile_body<TexturedAttr, kBinSmall>(xyz, uv, mvps, out, width, height, tex, g);
-}
-
-// The coverage forms of the two builds (nmi_render_mesh_masked): the same bodies, plus the mask stack.
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ uv,
-                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                           int height, MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
-{
-    mesh_tile_body<TexturedAttr, kBinMax, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
-}
-
-__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void nmi_mesh_tile_small_cover_kernel(
-    const float *__restrict__ xyz, const float *__restrict__ uv, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width, int height,
-    MeshTexture tex, BinGrid g, uint8_t *__restrict__ cover)
-{
-    mesh_tile_body<TexturedAttr, kBinSmall, true>(xyz, uv, mvps, out, width, height, tex, g, cover);
-}
-
-// The coloured tile kernels.  One build, 255 bin entries per tile.  The 24-word record makes it 56 KB of LDS: two workgroups per
+// held to 80 registers (Attr::kSmallWavesPerEu), so that THREE workgroups share a CU: the kernel spends half its wave-cycles
+// waiting (set-up, barriers, texel fetches), and a third workgroup to switch to is worth more than the spills the register cap
+// costs (93.5 -> 81.5 us at 4,800 triangles, same box).
+//
+// Coloured: one build, 255 bin entries per tile.  The 24-word record makes it 56 KB of LDS: two workgroups per
 // CU, as the textured one (a third needs 53.3 KB or less, i.e. 21 words a record; the visibility fields and the two planes are
 // 23).  A 127-entry build (44 KB) would fit three, but the body needs 86 registers (88 with coverage) and three workgroups allow
 // 80: under that cap it spills 28 / 52 bytes per lane, and uncapped it is two workgroups again -- so there is none
 // (profiles/mesh_color/NOTES.md).
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
-                                                                           const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
-                                                                           int height, BinGrid g)
-{
-    mesh_tile_body<ColoredAttr, kBinMax>(xyz, red, mvps, out, width, height, {}, g);
-}
-
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_color_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ red,
-                                                                                 const float *__restrict__ mvps, uint8_t *__restrict__ out,
-                                                                                 int width, int height, BinGrid g, uint8_t *__restrict__ cover)
-{
-    mesh_tile_body<ColoredAttr, kBinMax, true>(xyz, red, mvps, out, width, height, {}, g, cover);
-}
-
-// The depth tile kernels.  One build, 255 bin entries per tile: its 16-word records make 49 KB of LDS, so the LDS allows three
+//
+// Depth: one build, 255 bin entries per tile: its 16-word records make 49 KB of LDS, so the LDS allows three
 // workgroups per CU without a small build (profiles/depth/README.md has the resource table and what was measured).
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_depth_kernel(const float *__restrict__ xyz, const float *__restrict__ mvps,
-                                                                           uint8_t *__restrict__ out, int width, int height, DepthShade shade,
-                                                                           BinGrid g)
+constexpr int kBinSmall = 128;
+
+template <typename Attr, int BINMAX>
+constexpr int kTileWavesPerEu = BINMAX == kBinSmall ? Attr::kSmallWavesPerEu : 0;   // (0: no cap)
+
+template <typename Attr, int BINMAX, bool COVER, class... Array>
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(kTileWavesPerEu<Attr, BINMAX>, kTileWavesPerEu<Attr, BINMAX>)))
+void nmi_mesh_tile_kernel(const float *__restrict__ xyz, Array... attr, const float *__restrict__ mvps, uint8_t *__restrict__ out, int width,
+                          int height, typename Attr::Args args, BinGrid g, uint8_t *__restrict__ cover)
 {
-    mesh_tile_body<DepthAttr, kBinMax>(xyz, nullptr, mvps, out, width, height, shade, g);
+    const float *array = nullptr;
+    ((array = attr), ...);
+    mesh_tile_body<Attr, BINMAX, COVER>(xyz, array, mvps, out, width, height, args, g, cover);
 }
 
-__global__ __launch_bounds__(kTileThreads) void nmi_mesh_tile_depth_cover_kernel(const float *__restrict__ xyz, const float *__restrict__ mvps,
-                                                                                 uint8_t *__restrict__ out, int width, int height,
-                                                                                 DepthShade shade, BinGrid g, uint8_t *__restrict__ cover)
+// The one place that picks an instantiation: the policy from the caller, the small build where the policy has one and the mesh
+// is small, the coverage form where there are masks to write.
+template <typename Attr, class... Array>
+static void launch_tile_kernel(bool small_tiles, dim3 grid, hipStream_t stream, const float *xyz, const float *mvps, uint8_t *out, int width,
+                               int height, const typename Attr::Args &args, const BinGrid &g, uint8_t *cover, Array... attr)
 {
-    mesh_tile_body<DepthAttr, kBinMax, true>(xyz, nullptr, mvps, out, width, height, shade, g, cover);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kTileThreads), 0, stream, xyz, attr..., mvps, out, width, height, args, g, cover); };
+    if constexpr (Attr::kSmallWavesPerEu != 0)
+        if (small_tiles) return cover ? go(nmi_mesh_tile_kernel<Attr, kBinSmall, true, Array...>) : go(nmi_mesh_tile_kernel<Attr, kBinSmall, false, Array...>);
+    return cover ? go(nmi_mesh_tile_kernel<Attr, kBinMax, true, Array...>) : go(nmi_mesh_tile_kernel<Attr, kBinMax, false, Array...>);
 }
 
 __global__ __launch_bounds__(256) void nmi_mesh_clear_kernel(unsigned long long *zbuf, size_t n, uint32_t *state, size_t n_state,
@@ -1316,16 +1292,17 @@ hipError_t launch_mesh_clear(const MeshWork &w, int S, int width, int height, hi
 
 size_t mesh_pairs_entries(long long ntri) { return (size_t)((ntri + 255) / 256) * kMaxViewsPerLaunch; }
 
-hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const float *mvps, int S, const MeshWork &w,
-                              int layout_views, int bin_cap_limit, unsigned long long clip_cap_limit, uint8_t *out, int width, int height,
-                              hipStream_t stream, const uint8_t *warp_frame, const float *warp_coeffs, uint8_t *warp_out, int Wn, uint8_t *cover,
-                              const DepthShade *depth)
+hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long long ntri, const RenderViews &v, const MeshWork &w,
+                              const MeshLimits &limits, const RenderTarget &target, hipStream_t stream, const RideAlongWarp &warp)
 {
-    if (S > layout_views) return hipErrorInvalidValue;
-    WarpFuse wf{warp_frame, warp_coeffs, warp_out, 0};
-    if (warp_frame) {
-        if (!warp_lds_eligible(warp_frame, warp_out, width) || ntri <= 0 || S > kMaxViewsPerLaunch) return hipErrorInvalidValue;
-        wf.blocks = warp_blocks_x(width) * warp_blocks_y(height) * Wn;
+    const int S = v.S, width = target.width, height = target.height;
+    const float *mvps = v.mvps;
+    const DepthShade *depth = target.depth;
+    if (S > limits.layout_views) return hipErrorInvalidValue;
+    WarpFuse wf{warp.frame, warp.coeffs, warp.out, 0};
+    if (warp.frame) {
+        if (!warp_lds_eligible(warp.frame, warp.out, width) || ntri <= 0 || S > kMaxViewsPerLaunch) return hipErrorInvalidValue;
+        wf.blocks = warp_blocks_x(width) * warp_blocks_y(height) * warp.Wn;
     }
     if (ntri >= (1ll << 30) || width > 65535 || height > 65535) return hipErrorInvalidValue;  // triangle and piece share 31 bits of a key
     if (!w.zbuf || !w.bins || !w.state || !w.clip_queue || !w.clip_state) return hipErrorInvalidValue;
@@ -1338,17 +1315,17 @@ hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long
     BinGrid g{};
     static const int dbg = getenv("NMI_MESH_DBG") ? atoi(getenv("NMI_MESH_DBG")) : 0;
     g.dbg = dbg;
-    mesh_geometry(layout_views, width, height, &g.tiles_x, &g.tiles_y, &g.stride);  // the layout the work area was allocated for
-    g.cap = g.stride - 1 < bin_cap_limit ? g.stride - 1 : bin_cap_limit;
+    mesh_geometry(limits.layout_views, width, height, &g.tiles_x, &g.tiles_y, &g.stride);  // the layout the work area was allocated for
+    g.cap = g.stride - 1 < limits.bin_cap ? g.stride - 1 : limits.bin_cap;
     if (g.cap < 0) g.cap = 0;
     const int tiles = g.tiles_x * g.tiles_y;
     // The small tile kernel (127 entries per tile, three workgroups per CU) for meshes that could not fill more even if every
     // triangle were in view and touched two tiles; a fuller bin than its capacity takes the per-lane path as always.  Textured only:
-    // there is no small coloured build (see nmi_mesh_tile_color_kernel).
+    // the other policies have no small build (see nmi_mesh_tile_kernel).
     static const bool no_small = getenv("NMI_MESH_NO_SMALL_TILES") != nullptr;   // measurement switch
     const bool small_tiles = shading.textured && !depth && !no_small && (ntri * 2 <= (long long)(kBinSmall - 1) * tiles || g.cap <= kBinSmall - 1);
     if (small_tiles && g.cap > kBinSmall - 1) g.cap = kBinSmall - 1;
-    const unsigned long long clip_cap = w.clip_cap < clip_cap_limit ? w.clip_cap : clip_cap_limit;
+    const unsigned long long clip_cap = w.clip_cap < limits.clip_cap ? w.clip_cap : limits.clip_cap;
     for (int s0 = 0; s0 < S; s0 += kMaxViewsPerLaunch) {
         const int views = S - s0 < kMaxViewsPerLaunch ? S - s0 : kMaxViewsPerLaunch;
         g.bins = w.bins + (size_t)s0 * tiles * g.stride;
@@ -1386,27 +1363,17 @@ hipError_t launch_render_mesh(const float *xyz, const MeshShading &shading, long
                                clipq, w.clip_state, clip_cap, w.pair_state);
         }
         // the last stage: the tile kernel of the mesh's kind
-        const dim3 grid((unsigned)(views * tiles)), block(kTileThreads);
+        const dim3 grid((unsigned)(views * tiles));
         const float *m = mvps + (size_t)s0 * 16;
-        uint8_t *o = out + (size_t)s0 * width * height, *c = cover ? cover + (size_t)s0 * width * height : nullptr;
-        DepthShade sh = depth ? *depth : DepthShade{};
-        if (sh.depth16) sh.depth16 += (size_t)s0 * width * height;
-        if (depth && cover)
-            hipLaunchKernelGGL(nmi_mesh_tile_depth_cover_kernel, grid, block, 0, stream, xyz, m, o, width, height, sh, g, c);
-        else if (depth)
-            hipLaunchKernelGGL(nmi_mesh_tile_depth_kernel, grid, block, 0, stream, xyz, m, o, width, height, sh, g);
-        else if (!shading.textured && cover)
-            hipLaunchKernelGGL(nmi_mesh_tile_color_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g, c);
-        else if (!shading.textured)
-            hipLaunchKernelGGL(nmi_mesh_tile_color_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, g);
-        else if (cover && small_tiles)
-            hipLaunchKernelGGL(nmi_mesh_tile_small_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g, c);
-        else if (cover)
-            hipLaunchKernelGGL(nmi_mesh_tile_cover_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g, c);
-        else if (small_tiles)
-            hipLaunchKernelGGL(nmi_mesh_tile_small_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g);
+        uint8_t *o = target.out + (size_t)s0 * width * height, *c = target.cover ? target.cover + (size_t)s0 * width * height : nullptr;
+        if (depth) {
+            DepthShade sh = *depth;
+            if (sh.depth16) sh.depth16 += (size_t)s0 * width * height;
+            launch_tile_kernel<DepthAttr>(small_tiles, grid, stream, xyz, m, o, width, height, sh, g, c);
+        } else if (!shading.textured)
+            launch_tile_kernel<ColoredAttr>(small_tiles, grid, stream, xyz, m, o, width, height, {}, g, c, shading.attr);
         else
-            hipLaunchKernelGGL(nmi_mesh_tile_kernel, grid, block, 0, stream, xyz, shading.attr, m, o, width, height, tex, g);
+            launch_tile_kernel<TexturedAttr>(small_tiles, grid, stream, xyz, m, o, width, height, tex, g, c, shading.attr);
     }
     return hipGetLastError();
 }

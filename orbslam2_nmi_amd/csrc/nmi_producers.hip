@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "nmi_kernels.h"
 #include "nmi_warp_device.h"
@@ -175,22 +176,22 @@ __global__ __launch_bounds__(256) void nmi_level_prep_kernel(const float *__rest
     for (size_t i = (nz & ~(size_t)3) + t; i < nz; i += step) zbuf[i] = 0xFFFFFFFFu;
 }
 
-hipError_t launch_level_prep(const float *h_mvps, float *d_mvps, int n_mvps, const float *h_coeffs, float *d_coeffs, int n_coeffs,
-                             unsigned long long *key, uint32_t *zbuf, size_t nz, hipStream_t stream, uint32_t *epoch, const void *packed,
-                             long long npoints, const float *h_bound, uint32_t *kept, uint32_t *kept_count)
+hipError_t launch_level_prep(const LevelPrep &p, hipStream_t stream)
 {
+    const FusedCloud &c = p.cloud;
+    const bool fused = c.kept != nullptr;   // the culling pass: all of the cloud's pointers or none, and no anchors to clear
+    if (fused ? (p.nz || !c.packed || !c.h_bound || !c.kept_count) : (c.packed || c.h_bound || c.kept_count)) return hipErrorInvalidValue;
     const float4 *boxes = nullptr;
     long long nwaves = 0;
-    if (kept) {
-        if (nz || !packed || !h_bound || !kept_count) return hipErrorInvalidValue;
+    if (fused) {
         size_t off = 0;
-        (void)cloud_pack_bytes(npoints, &off);
-        boxes = reinterpret_cast<const float4 *>(static_cast<const char *>(packed) + off);
-        nwaves = (npoints + 63) / 64;
+        (void)cloud_pack_bytes(c.npoints, &off);
+        boxes = reinterpret_cast<const float4 *>(static_cast<const char *>(c.packed) + off);
+        nwaves = (c.npoints + 63) / 64;
     }
-    const unsigned blocks = kept ? 1u + (unsigned)((nwaves + 255) / 256) : (nz ? 2048u : 1u);
-    hipLaunchKernelGGL(nmi_level_prep_kernel, dim3(blocks), dim3(256), 0, stream, h_mvps, d_mvps, n_mvps, h_coeffs, d_coeffs, n_coeffs, key, zbuf, nz,
-                       epoch, boxes, nwaves, h_bound, kept, kept_count);
+    const unsigned blocks = fused ? 1u + (unsigned)((nwaves + 255) / 256) : (p.nz ? 2048u : 1u);
+    hipLaunchKernelGGL(nmi_level_prep_kernel, dim3(blocks), dim3(256), 0, stream, p.h_mvps, p.d_mvps, p.n_mvps, p.h_coeffs, p.d_coeffs, p.n_coeffs, p.key,
+                       p.zbuf, p.nz, p.epoch, boxes, nwaves, c.h_bound, c.kept, c.kept_count);
     return hipGetLastError();
 }
 
@@ -207,8 +208,6 @@ hipError_t launch_level_prep(const float *h_mvps, float *d_mvps, int n_mvps, con
 // 256-point block through LDS with two barriers and kept the matrices in LDS: 73 us for 3 M points x 27 views; this one
 // 62 us = 15 us loading the cloud + 16 us culling + 32 us in the view loop, the atomics being 5 of those -- ablations
 // in profiles/NOTES.md.)
-constexpr int kMaxViewsPerLaunch = 64;
-
 template <typename T>
 __device__ __forceinline__ T wave_min(T v)
 {
@@ -435,19 +434,22 @@ __device__ __forceinline__ void resolve_strips(const uint32_t *__restrict__ zbuf
     }
 }
 
-template <int SIZE, class... Shade>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
-                                                                    int width, int height, int stride, const uint32_t *epoch, size_t pair_words,
-                                                                    Shade... shade)
+// The two resolve kernels.  COVER (nmi_render_points_masked, covered levels): the same render bytes, and the coverage mask beside
+// them; without it `cover` is not read.
+template <int SIZE, bool COVER, class... Shade>
+__global__ __launch_bounds__(256) void nmi_zbuf_resolve_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
+                                                                    uint8_t *__restrict__ cover, int views, int width, int height, int stride,
+                                                                    const uint32_t *epoch, size_t pair_words, Shade... shade)
 {
     if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // a level's double-buffered anchors: the buffer this replay splatted into
-    resolve_strips<SIZE, false>(zbuf, out, nullptr, views, width, height, stride, shade...);
+    resolve_strips<SIZE, COVER>(zbuf, out, cover, views, width, height, stride, shade...);
 }
 
 // Any size / width.
-template <class... Shade>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out, int views,
-                                                               int width, int height, int size, int stride, Shade... shade)
+template <bool COVER, class... Shade>
+__global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
+                                                               uint8_t *__restrict__ cover, int views, int width, int height, int size, int stride,
+                                                               Shade... shade)
 {
     const int wp = width + size - 1, hp = height + size - 1;
     const int quads = (width + 3) / 4;
@@ -476,55 +478,10 @@ __global__ __launch_bounds__(256) void nmi_zbuf_resolve_kernel(const uint32_t *_
         } else {
             for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(best[k] & 0xFFu);  // untouched pixels keep 255
         }
-    }
-}
-
-// The coverage forms of the two resolve kernels above (nmi_render_points_masked, covered levels): the same render bytes, and
-// the coverage mask beside them.
-template <int SIZE, class... Shade>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_fast_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
-                                                                          uint8_t *__restrict__ cover, int views, int width, int height, int stride,
-                                                                          const uint32_t *epoch, size_t pair_words, Shade... shade)
-{
-    if (epoch) zbuf += (size_t)(*epoch & 1u) * pair_words;  // as nmi_zbuf_resolve_fast_kernel
-    resolve_strips<SIZE, true>(zbuf, out, cover, views, width, height, stride, shade...);
-}
-
-// Any size / width (coverage form).
-template <class... Shade>
-__global__ __launch_bounds__(256) void nmi_zbuf_resolve_cover_kernel(const uint32_t *__restrict__ zbuf, uint8_t *__restrict__ out,
-                                                                     uint8_t *__restrict__ cover, int views, int width, int height, int size, int stride,
-                                                                     Shade... shade)
-{
-    const int wp = width + size - 1, hp = height + size - 1;
-    const int quads = (width + 3) / 4;
-    const size_t n = (size_t)views * height * quads;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % quads), py = (int)((i / quads) % height), s = (int)(i / ((size_t)quads * height));
-        const int px = q * 4;
-        const uint32_t *base = zbuf + ((size_t)s * hp + py) * stride + px;
-        uint32_t best[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        for (int dy = 0; dy < size; ++dy) {
-            const uint32_t *row = base + (size_t)dy * stride;
-            for (int dx = 0; dx < size + 3; ++dx) {
-                if (px + dx >= wp) break;
-                const uint32_t v = row[dx];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (dx >= k && dx - k < size) best[k] = min(best[k], v);
-            }
+        if constexpr (COVER) {
+            uint8_t *cdst = cover + (dst - out);  // (byte stores: the mask stack has no alignment requirement here)
+            for (int k = 0; k < 4 && px + k < width; ++k) cdst[k] = best[k] != 0xFFFFFFFFu ? 1 : 0;
         }
-        uint8_t *dst = out + ((size_t)s * height + py) * width + px;
-        if constexpr (sizeof...(Shade) != 0) {  // the depth form: byte stores, as the pixels may end anywhere
-            const uint32_t grey = depth_quad(shade..., best, (size_t)(dst - out), false, width - px);
-            for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(grey >> (8 * k));
-        } else if (px + 3 < width && (width & 3) == 0) {
-            *reinterpret_cast<uint32_t *>(dst) = (best[0] & 0xFFu) | ((best[1] & 0xFFu) << 8) | ((best[2] & 0xFFu) << 16) | (best[3] << 24);
-        } else {
-            for (int k = 0; k < 4 && px + k < width; ++k) dst[k] = (uint8_t)(best[k] & 0xFFu);  // untouched pixels keep 255
-        }
-        uint8_t *cdst = cover + (dst - out);  // (byte stores: the mask stack has no alignment requirement here)
-        for (int k = 0; k < 4 && px + k < width; ++k) cdst[k] = best[k] != 0xFFFFFFFFu ? 1 : 0;
     }
 }
 
@@ -535,77 +492,57 @@ static bool depth16_quads(const Shade &...shade)
     return (... && (((uintptr_t)shade.depth16 & 7) == 0));
 }
 
-// The coverage forms of launch_resolve's kernels (nmi_render_points_masked): the same choice of form, the render bytes the same.
+// The one resolve launcher: the fast form where the frame, the point size and every buffer's alignment allow it (with an epoch
+// always: launch_level_front_points checks the same conditions first), else the any-size form.
 // shade: nothing, or one DepthShade -- the depth forms of the same kernels (nmi_render_points_depth, depth levels).
-template <class... Shade>
-static void launch_resolve_cover(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, int S, int width, int height, int size, hipStream_t stream,
-                                 const uint32_t *epoch, size_t pair_words, Shade... shade)
+template <bool COVER, class... Shade>
+static void launch_resolve(const uint32_t *zbuf, const RenderTarget &t, int S, int size, hipStream_t stream, const uint32_t *epoch,
+                           size_t pair_words, Shade... shade)
 {
-    const int stride = zbuf_stride(width, size);
-    const size_t nq = (size_t)S * height * ((width + 3) / 4);
-    dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
-    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && (((uintptr_t)cover & 3) == 0) &&
-                      depth16_quads(shade...);
-    if (!fast) {  // (never with an epoch: launch_level_front_points checks the fast form's conditions first)
-        hipLaunchKernelGGL((nmi_zbuf_resolve_cover_kernel<Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, size, stride, shade...);
+    const int width = t.width, height = t.height, stride = zbuf_stride(width, size);
+    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)t.out & 3) == 0) &&
+                      (!COVER || ((uintptr_t)t.cover & 3) == 0) && depth16_quads(shade...);
+    // one lane per quad of a row, or (fast) per strip
+    const size_t lanes = fast ? (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4) : (size_t)S * height * ((width + 3) / 4);
+    const dim3 grid((unsigned)((lanes + 255) / 256 < 8192 ? (lanes + 255) / 256 : 8192)), block(256);
+    if (!fast) {
+        hipLaunchKernelGGL((nmi_zbuf_resolve_kernel<COVER, Shade...>), grid, block, 0, stream, zbuf, t.out, t.cover, S, width, height, size, stride, shade...);
         return;
     }
-    const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
-    grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
+    auto sized = [&](auto n) {
+        hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<decltype(n)::value, COVER, Shade...>), grid, block, 0, stream, zbuf, t.out, t.cover, S, width,
+                           height, stride, epoch, pair_words, shade...);
+    };
     switch (size) {
-    case 1: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<1, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 2: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<2, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 3: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<3, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 4: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<4, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
-    default: hipLaunchKernelGGL((nmi_zbuf_resolve_cover_fast_kernel<5, Shade...>), grid, block, 0, stream, zbuf, out, cover, S, width, height, stride, epoch, pair_words, shade...); break;
+    case 1: sized(std::integral_constant<int, 1>{}); break;
+    case 2: sized(std::integral_constant<int, 2>{}); break;
+    case 3: sized(std::integral_constant<int, 3>{}); break;
+    case 4: sized(std::integral_constant<int, 4>{}); break;
+    default: sized(std::integral_constant<int, 5>{}); break;
     }
 }
 
-template <class... Shade>
-static void launch_resolve(const uint32_t *zbuf, uint8_t *out, int S, int width, int height, int size, hipStream_t stream,
-                           const uint32_t *epoch, size_t pair_words, Shade... shade)
+// The resolve of a render: plain or with coverage, the map's colour or (target.depth) its depth.
+static void launch_resolve_for(const uint32_t *zbuf, const RenderTarget &t, int S, int size, hipStream_t stream, const uint32_t *epoch = nullptr,
+                               size_t pair_words = 0)
 {
-    const int stride = zbuf_stride(width, size);
-    const size_t nq = (size_t)S * height * ((width + 3) / 4);
-    dim3 grid((unsigned)((nq + 255) / 256 < 8192 ? (nq + 255) / 256 : 8192)), block(256);
-    const bool fast = (width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0) && depth16_quads(shade...);
-    if (!fast) {  // (never with an epoch: launch_level_front_points checks resolve_fast_eligible first)
-        hipLaunchKernelGGL((nmi_zbuf_resolve_kernel<Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, size, stride, shade...);
-        return;
-    }
-    const size_t nstrips = (size_t)S * ((height + kResolveRows - 1) / kResolveRows) * (width / 4);  // one lane per strip
-    grid = dim3((unsigned)((nstrips + 255) / 256 < 8192 ? (nstrips + 255) / 256 : 8192));
-    switch (size) {
-    case 1: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<1, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 2: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<2, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 3: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<3, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
-    case 4: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<4, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
-    default: hipLaunchKernelGGL((nmi_zbuf_resolve_fast_kernel<5, Shade...>), grid, block, 0, stream, zbuf, out, S, width, height, stride, epoch, pair_words, shade...); break;
-    }
-}
-
-// The resolve of a render: plain or with coverage, the map's colour or (shade) its depth.
-static void launch_resolve_for(const uint32_t *zbuf, uint8_t *out, uint8_t *cover, const DepthShade *shade, int S, int width, int height, int size,
-                               hipStream_t stream, const uint32_t *epoch = nullptr, size_t pair_words = 0)
-{
-    if (shade && cover)
-        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words, *shade);
-    else if (shade)
-        launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words, *shade);
-    else if (cover)
-        launch_resolve_cover(zbuf, out, cover, S, width, height, size, stream, epoch, pair_words);
+    if (t.depth && t.cover)
+        launch_resolve<true>(zbuf, t, S, size, stream, epoch, pair_words, *t.depth);
+    else if (t.depth)
+        launch_resolve<false>(zbuf, t, S, size, stream, epoch, pair_words, *t.depth);
+    else if (t.cover)
+        launch_resolve<true>(zbuf, t, S, size, stream, epoch, pair_words);
     else
-        launch_resolve(zbuf, out, S, width, height, size, stream, epoch, pair_words);
+        launch_resolve<false>(zbuf, t, S, size, stream, epoch, pair_words);
 }
 
 size_t render_zbuf_words(int S, int width, int height, int size) { return (size_t)S * zbuf_stride(width, size) * (height + size - 1); }
 
-hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const float *mvps, int S, uint32_t *zbuf,
-                                uint8_t *out, int width, int height, int size, hipStream_t stream, bool clear_first, uint8_t *cover,
-                                const DepthShade *shade)
+hipError_t launch_render_points(const float *xyz, const float *red, long long npoints, const RenderViews &v, uint32_t *zbuf, int size,
+                                const RenderTarget &target, hipStream_t stream, bool clear_first)
 {
+    const int S = v.S, width = target.width, height = target.height;
     const size_t nz = render_zbuf_words(S, width, height, size);
-    const size_t n = (size_t)S * width * height;
     if (clear_first)
         hipLaunchKernelGGL(nmi_zbuf_clear_kernel, dim3((unsigned)((nz + 255) / 256 < 4096 ? (nz + 255) / 256 : 4096)), dim3(256), 0, stream, zbuf, nz);
     if (npoints > 0) {
@@ -614,11 +551,10 @@ hipError_t launch_render_points(const float *xyz, const float *red, long long np
         for (int s0 = 0; s0 < S; s0 += kMaxViewsPerLaunch) {
             const int views = S - s0 < kMaxViewsPerLaunch ? S - s0 : kMaxViewsPerLaunch;
             hipLaunchKernelGGL(nmi_splat_kernel, dim3((unsigned)((npoints + 255) / 256)), dim3(256), 0, stream, xyz, red, npoints,
-                               mvps + (size_t)s0 * 16, views, zbuf + (size_t)s0 * per_view, width, height, size, stride);
+                               v.mvps + (size_t)s0 * 16, views, zbuf + (size_t)s0 * per_view, width, height, size, stride);
         }
     }
-    launch_resolve_for(zbuf, out, cover, shade, S, width, height, size, stream);
-    (void)n;
+    launch_resolve_for(zbuf, target, S, size, stream);
     return hipGetLastError();
 }
 
@@ -645,20 +581,21 @@ size_t level_zbuf_pair_words(int S, int width, int height, int size) { return (r
 // Front of a captured point-cloud level: warp stack + splat (+ the clear of the other anchor buffer) in one launch, then the
 // resolve.  `zbuf` holds two buffers of level_zbuf_pair_words each, both cleared at creation; `epoch` is the device word the
 // level's prep node bumps.  `mvps` holds S matrices followed by 6 planes (a, b, c, d) with every view's frustum on their
-// non-negative side (level_views_bound; all zero switches the test off).  S <= 64 views.
-hipError_t launch_level_front_points(const void *packed, long long npoints, const float *mvps, int S, uint32_t *zbuf, const uint32_t *epoch,
-                                     uint8_t *out, int width, int height, int size, const uint8_t *frame, const float *coeffs, uint8_t *warps,
-                                     int Wn, hipStream_t stream, const uint32_t *kept, const uint32_t *kept_count, int compute_units,
-                                     uint8_t *cover, const DepthShade *shade)
+// non-negative side (level_views_bound; all zero switches the test off).
+hipError_t launch_level_front_points(const FusedCloud &cloud, const RenderViews &v, uint32_t *zbuf, const uint32_t *epoch, int size,
+                                     int compute_units, const RenderTarget &target, const RideAlongWarp &warp, hipStream_t stream)
 {
-    if (S > kMaxViewsPerLaunch || !warp_lds_eligible(frame, warps, width) || !kept || !kept_count) return hipErrorInvalidValue;
-    if (cover && ((uintptr_t)cover & 3) != 0) return hipErrorInvalidValue;
-    if (shade && !depth16_quads(*shade)) return hipErrorInvalidValue;
-    if (!((width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)out & 3) == 0))) return hipErrorInvalidValue;
+    const int S = v.S, width = target.width, height = target.height;
+    const float *mvps = v.mvps;
+    long long npoints = cloud.npoints;
+    if (S > kMaxViewsPerLaunch || !warp_lds_eligible(warp.frame, warp.out, width) || !cloud.kept || !cloud.kept_count) return hipErrorInvalidValue;
+    if (target.cover && ((uintptr_t)target.cover & 3) != 0) return hipErrorInvalidValue;
+    if (target.depth && !depth16_quads(*target.depth)) return hipErrorInvalidValue;
+    if (!((width & 3) == 0 && size <= 5 && (((uintptr_t)zbuf & 15) == 0) && (((uintptr_t)target.out & 3) == 0))) return hipErrorInvalidValue;
     size_t off = 0;
     (void)cloud_pack_bytes(npoints, &off);
-    PackedCloud pc{reinterpret_cast<const float4 *>(packed), reinterpret_cast<const float4 *>(static_cast<const char *>(packed) + off)};
-    int warp_blocks = warp_blocks_x(width) * warp_blocks_y(height) * Wn;
+    PackedCloud pc{reinterpret_cast<const float4 *>(cloud.packed), reinterpret_cast<const float4 *>(static_cast<const char *>(cloud.packed) + off)};
+    int warp_blocks = warp_blocks_x(width) * warp_blocks_y(height) * warp.Wn;
     // splat workers: three workgroups (12 wavefronts) per CU keep the CU's atomic path busy and leave five workgroup slots to the
     // warp blocks; never more than one wavefront per 64 points
     static const int per_cu = getenv("NMI_FRONT_WORKERS") ? atoi(getenv("NMI_FRONT_WORKERS")) : 3;
@@ -671,9 +608,9 @@ hipError_t launch_level_front_points(const void *packed, long long npoints, cons
     if (dbg & 2) splat_blocks = 0, npoints = 0;
     const int clear_blocks = (dbg & 4) ? 0 : 1024;
     hipLaunchKernelGGL(nmi_level_front_kernel, dim3((unsigned)(warp_blocks + splat_blocks + clear_blocks)), dim3(256), 0, stream, pc, npoints, mvps,
-                       S, zbuf, pair_words, epoch, width, height, size, stride, frame, coeffs, warps, warp_blocks, (int)splat_blocks, clear_blocks,
-                       kept, kept_count);
-    launch_resolve_for(zbuf, out, cover, shade, S, width, height, size, stream, epoch, pair_words);
+                       S, zbuf, pair_words, epoch, width, height, size, stride, warp.frame, warp.coeffs, warp.out, warp_blocks, (int)splat_blocks,
+                       clear_blocks, cloud.kept, cloud.kept_count);
+    launch_resolve_for(zbuf, target, S, size, stream, epoch, pair_words);
     return hipGetLastError();
 }
 

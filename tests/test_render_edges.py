@@ -323,7 +323,7 @@ def _replays(c):
 @pytest.mark.parametrize("shape", [(320, 240), (150, 90)], ids=["320x240-fused", "150x90"])
 def test_gpu_level_families(nmi, family, shape):
     """A point-cloud NmiLevel (prep with the common-plane cull of the packed cloud's boxes, the front kernel's splat, the
-    resolve) and a covered one (nmi_zbuf_resolve_cover_fast_kernel with the epoch) against the twin, over three replays with changing
+    resolve) and a covered one (nmi_zbuf_resolve_fast_kernel's coverage form with the epoch) against the twin, over three replays with changing
     matrices."""
     W, H = shape
     bad = []

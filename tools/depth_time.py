@@ -11,8 +11,8 @@ Per-kernel times come from the profiler, in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/depth_time.py --iters 300
     python tools/depth_time.py --trace DIR
 The second command reads the kernel trace and prints, per kernel of the tile and resolve families, the same statistic (dispatches in
-order, the warm-up share dropped, cut into repetitions): nmi_mesh_tile_depth_kernel against nmi_mesh_tile_color_kernel, and the
-resolve kernels with and without a DepthShade.
+order, the warm-up share dropped, cut into repetitions): nmi_mesh_tile_kernel<DepthAttr, ...> against
+nmi_mesh_tile_kernel<ColoredAttr, ...>, and the resolve kernels with and without a DepthShade.
 """
 import argparse
 import csv
@@ -48,7 +48,7 @@ def read_trace(directory, reps):
             for row in csv.DictReader(fh):
                 name = row["Kernel_Name"]
                 if "mesh_tile" in name or "zbuf_resolve" in name:
-                    name = name.split("(")[0].replace("void ", "").replace("nmi::", "")
+                    name = name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("nmi::", "")
                     per_kernel.setdefault(name, []).append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3))
     # measure() runs the tile kernels on the two meshes in turn, the same number of calls each: the halves of their dispatches
     out = {}

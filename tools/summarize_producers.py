@@ -16,12 +16,12 @@ for m in ("cloud", "60x40", "300x200"):
     kernels = {}
     for f in glob.glob(os.path.join(out, f"trace_{m}", "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("nmi::", "")
+            name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("nmi::", "")
             kernels.setdefault(name, {"dur": []})["dur"].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for tag in ("sq", "fetch", "write"):
         for f in glob.glob(os.path.join(out, f"pmc_{tag}_{m}", "**", "*counter_collection.csv"), recursive=True):
             for r in csv.DictReader(open(f)):
-                name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("nmi::", "")
+                name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("nmi::", "")
                 kernels.setdefault(name, {"dur": []}).setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     table = {}
     for name, d in kernels.items():
