@@ -22,29 +22,22 @@ int hip_fail(nmi_ctx *ctx, hipError_t e, const char *what)
 
 
 
-// Visiting order of the candidates of an S x Wn grid: tiles of kTileW warps x kTileS renders (32 candidates = the
-// 32 workgroups one XCD runs at a time), tile after tile; within a tile render-fastest.  Cached per grid shape.
-void build_order(int S, int Wn, int *order)
-{
-    const int tile_s = S >= 8 ? 8 : (S >= 4 ? 4 : (S >= 2 ? 2 : 1)), tile_w = 32 / tile_s;
-    int64_t o = 0;
-    for (int w0 = 0; w0 < Wn; w0 += tile_w)
-        for (int s0 = 0; s0 < S; s0 += tile_s)
-            for (int w = w0; w < w0 + tile_w && w < Wn; ++w)
-                for (int s = s0; s < s0 + tile_s && s < S; ++s) order[o++] = w * S + s;
-}
+// Visiting order of the candidates of an S x Wn grid in tiles (nmi_search_plan.h): the levels', streams', masked and covered searches'.
+void build_order(int S, int Wn, int *order) { nmi::build_tile_order(S, Wn, order); }
 
-// The cached visiting order for this grid shape (device pointer in *d_order), built and uploaded on first use.  Never
+// The cached visiting order for this grid shape (device pointer in *d_order), built and uploaded on first use.  grid > 0: the
+// order that keeps one warp per workgroup of a launch of `grid` workgroups (build_search_order), which depends on the grid and is
+// cached under it; grid = 0: the tiles.  Never
 // synchronises the stream on a hit or on a miss with a free entry; only evicting the least recently used of kOrderCache
 // shapes waits (its table may still be read by a kernel in flight).
-int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order)
+int ensure_order(nmi_ctx *ctx, int S, int Wn, int grid, const int **d_order)
 {
     *d_order = nullptr;
     if (!ctx->xcd_tiling) return NMI_OK;
     const int64_t total = (int64_t)S * Wn;
     nmi_ctx::OrderEntry *victim = nullptr;
     for (auto &e : ctx->orders) {
-        if (e.S == S && e.Wn == Wn) {
+        if (e.S == S && e.Wn == Wn && e.grid == grid) {
             e.last_use = ++ctx->order_clock;
             *d_order = e.d.as<int>();
             return NMI_OK;
@@ -57,10 +50,12 @@ int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order)
     const size_t bytes = (size_t)total * sizeof(int);
     NMI_HIP_TRY(ctx, e.d.grow(bytes));  // (waited above)
     NMI_HIP_TRY(ctx, e.h.grow(bytes, nmi_mem::kPinned));
-    build_order(S, Wn, e.h.as<int>());
+    if (grid > 0) nmi::build_search_order(S, Wn, grid, e.h.as<int>());
+    else build_order(S, Wn, e.h.as<int>());
     NMI_HIP_TRY(ctx, hipMemcpyAsync(e.d.as<int>(), e.h.as<int>(), bytes, hipMemcpyHostToDevice, ctx->stream));
     e.S = S;
     e.Wn = Wn;
+    e.grid = grid;
     e.last_use = ++ctx->order_clock;
     *d_order = e.d.as<int>();
     return NMI_OK;
@@ -152,7 +147,7 @@ int prepare_search(nmi_ctx *ctx, const nmi::SearchPlan &plan, nmi::GridArgs &a)
         if (rc == NMI_OK) rc = prepare_pix_handoff(ctx, &a.epoch);
         a.blocks = ctx->d_pix_blocks.as<unsigned long long>();
     } else if (plan.order_table) {
-        rc = ensure_order(ctx, a.S_local, a.Wn, &a.order);
+        rc = ensure_order(ctx, a.S_local, a.Wn, plan.shared_order ? plan.workgroups : 0, &a.order);
     }
     if (rc != NMI_OK) return rc;
 #ifdef NMI_BUILD_ABLATIONS

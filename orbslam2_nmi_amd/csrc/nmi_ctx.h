@@ -76,6 +76,7 @@ struct nmi_ctx {
     // alternating between shapes (translation level 27 x 1, rotation level 1 x 27, ...) never waits for the stream.
     struct OrderEntry {
         int S = -1, Wn = -1;
+        int grid = 0;    // workgroups of the launch the order was built for (one warp per workgroup), 0: the tiles
         DeviceBuffer d;  // int [S * Wn], or larger: an entry keeps the largest table it has held
         PinnedBuffer h;
         uint64_t last_use = 0;
@@ -170,7 +171,7 @@ int rccl_allreduce_key(nmi_ctx *ctx, const unsigned long long *d_send, unsigned 
 
 int hip_fail(nmi_ctx *ctx, hipError_t e, const char *what);
 void build_order(int S, int Wn, int *order);
-int ensure_order(nmi_ctx *ctx, int S, int Wn, const int **d_order);
+int ensure_order(nmi_ctx *ctx, int S, int Wn, int grid, const int **d_order);
 // What is to be scored: the S_local x Wn block at (s_offset, w_offset) of an S_total-render grid.  A call site names what it uses.
 struct SearchRequest {
     const uint8_t *render_stack = nullptr, *warp_stack = nullptr;

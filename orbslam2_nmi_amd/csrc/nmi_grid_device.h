@@ -52,7 +52,9 @@ struct Lds {
 // Candidate visited by workgroup `b` in its round `r`.  Workgroups are dealt to the 8 XCDs round-robin (b and b + 8
 // share an XCD and its L2), so the 32 workgroups of an XCD take 32 CONSECUTIVE ordinals of the visiting order, and the
 // host lays the order out in tiles of (few warps) x (few renders): an XCD's round then touches ~12 images (~3.6 MB at
-// 640x480, inside its 4 MiB L2) instead of ~29.  Placement is a speed matter only; any order gives the same results.
+// 640x480, inside its 4 MiB L2) instead of ~29.  nmi_grid_kernel's own plain searches read an order that also keeps one warp per
+// workgroup over its rounds (build_search_order, nmi_search_plan.h: 13-14 images per XCD and round for 27 x 27), so that the frame
+// marginal is formed once per workgroup.  Placement is a speed matter only; any order gives the same results.
 __device__ __forceinline__ int slot_in_round(int b, int grid) { return (grid & 7) == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b; }
 __device__ __forceinline__ int candidate_at(const GridArgs &a, int ordinal) { return a.order ? a.order[ordinal] : ordinal; }
 
@@ -459,7 +461,10 @@ __device__ __forceinline__ void apply_wraps(const Lds &lds, int par, uint32_t no
 // ZERO0 (background rule off, NMI.cu:85: a pixel counts only if both intensities are non-zero): the histogram phase
 // has counted every pixel -- the skipped ones are exactly row 0 and column 0 of the joint histogram, which are cleared
 // here, after they have entered the wrap detector's total.
-template <bool ZERO0 = false>
+// KEPT (nmi_grid_kernel's later candidates on one warp, every pixel counted): the frame marginal -- the column sums -- is the plain
+// histogram of the warp image, the same for every render it meets; the workgroup formed it and its entropy sum on an earlier
+// candidate (final_phase), so this form carries no column sums and ends without the 16 atomics per lane into hist_warped.
+template <bool ZERO0 = false, bool KEPT = false>
 __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &a, int wave, int lane)
 {
     const uint32_t novf = lds.ovf_n[par] < (uint32_t)kOvfCap ? lds.ovf_n[par] : (uint32_t)kOvfCap;
@@ -521,8 +526,10 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
         float tl[8], th[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            col_lo[k] += lo[k];
-            col_hi[k] += hi[k];
+            if (!KEPT) {
+                col_lo[k] += lo[k];
+                col_hi[k] += hi[k];
+            }
             rsum += lo[k] + hi[k];
             cmax = max(cmax, max(lo[k], hi[k]));
             // straight-line LDS lookups; counts beyond the LDS table are patched below (one branch per pass)
@@ -553,19 +560,23 @@ __device__ __forceinline__ void decode_phase(Lds &lds, int par, const GridArgs &
             }
         }
     }
+    if (!KEPT) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int q = i + 16 * k;
-        atomicAdd(&lds.hist_warped[q], col_lo[k]);
-        atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
+        for (int k = 0; k < 8; ++k) {
+            const int q = i + 16 * k;
+            atomicAdd(&lds.hist_warped[q], col_lo[k]);
+            atomicAdd(&lds.hist_warped[q + 128], col_hi[k]);
+        }
     }
     if (i == 0) atomicAdd(&lds.total[par], wave_total);
 }
 
 // Final stage, one wavefront: the three 256-element trees of AddVectorPairwiseKernel (NMI.cu:295-339) run
 // side by side in DPP rows 0 (render marginal), 1 (frame marginal), 2 (joint row sums); then the score.
+// `kept` (nmi_grid_kernel only, see decode_phase<.., true>): hist_warped was not formed for this candidate; row 1 idles and the
+// frame marginal's sum is *frame_sum, where the call that formed it for this warp left it (any call with frame_sum and !kept).
 __device__ __forceinline__ void final_phase(Lds &lds, const GridArgs &a, int lane, int p, int w, int s,
-                                            unsigned long long &prev_key)
+                                            unsigned long long &prev_key, bool kept = false, float *frame_sum = nullptr)
 {
     const int i = lane & 15, r = lane >> 4;
     float lo[8], hi[8];
@@ -576,8 +587,8 @@ __device__ __forceinline__ void final_phase(Lds &lds, const GridArgs &a, int lan
     uint32_t cl[8], ch[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        cl[k] = r < 2 ? h[i + 16 * k] : 0u;
-        ch[k] = r < 2 ? h[i + 16 * k + 128] : 0u;
+        cl[k] = r < (kept ? 1 : 2) ? h[i + 16 * k] : 0u;
+        ch[k] = r < (kept ? 1 : 2) ? h[i + 16 * k + 128] : 0u;
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -603,7 +614,12 @@ __device__ __forceinline__ void final_phase(Lds &lds, const GridArgs &a, int lan
         }
     }
     const float x = row_tree_16(lane_tree_16(lo, hi));
-    const float a1 = __shfl(x, 0, 64), a2 = __shfl(x, 16, 64), a3 = __shfl(x, 32, 64);
+    const float a1 = __shfl(x, 0, 64), a3 = __shfl(x, 32, 64);
+    float a2 = __shfl(x, 16, 64);
+    if (frame_sum) {  // (scalar: the sum lives in an SGPR across the next candidate's pixels)
+        if (kept) a2 = *frame_sum;
+        else *frame_sum = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a2)));
+    }
     if (a.dbg_h1 && lane < 64) {
         for (int t = lane; t < kBins; t += 64) {
             a.dbg_h1[t] = lds.hist_render[t];

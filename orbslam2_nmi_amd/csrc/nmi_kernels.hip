@@ -101,6 +101,13 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
     // Pixel shares by wavefront age (histogram_phase) where the fast loop runs; the exact-only instantiations (HIST = 1: careful
     // loop from the first chunk, cold) keep equal shares, like exact_candidate -- the slabs cost them up to 60 bytes of scratch.
     constexpr bool kSlabs = NMI_WAVE_SLABS != 0 && kFirst == 2;
+    // A workgroup keeps its warp (the host's visiting order sees to that, build_search_order): with every pixel counted the frame
+    // marginal and its entropy sum are the warp image's alone, so only the first of a run of candidates on one warp forms them
+    // (decode_phase<.., true>, final_phase's `kept`).  Not with the background rule off (the skipped pixels depend on the render),
+    // not while a debug export wants every candidate's marginal, and not for a candidate the content probe reads the frame
+    // marginal of (s == 0).  Every candidate this loop has scored passed the wrap test, so what is kept is exact; the cold loop
+    // below forms everything per candidate.
+    constexpr bool kKeepWarp = kOptimistic && BG;
 
     if (blockIdx.x == 0 && tid == 0 && a.reset_key) *a.reset_key = 0ull;  // next launch's slot; idle during this one
     // The LDS copy of the term table is first needed by the first decode phase: fetch it now, park it in
@@ -127,6 +134,9 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
     const int total = a.S_local * a.Wn;
     unsigned long long prev_key = 0;
     int par = 0;
+    int kept_w = -1;         // the warp whose frame marginal sum is in frame_sum (workgroup-uniform)
+    float frame_sum = 0.0f;  // (wavefront 0)
+    const bool keep_ok = kKeepWarp && !a.dbg_h1 && !a.dbg_h2;
     const int slot = slot_in_round(blockIdx.x, gridDim.x);
     int ordinal = slot;  // this workgroup visits ordinals slot, slot + grid, slot + 2 grid, ...
     for (; ordinal < total; ordinal += gridDim.x, par ^= 1) {
@@ -158,7 +168,12 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
 #endif
         __syncthreads();  // B1
         NMI_GRID_STAMP(3);
-        if (a.phase_mask & 2) decode_phase<kZero0>(lds, par, a, wave, lane);
+        const bool kept = keep_ok && w == kept_w && !(s == 0 && a.plan);
+        if (a.phase_mask & 2) {
+            if (kKeepWarp && kept) decode_phase<false, true>(lds, par, a, wave, lane);
+            else decode_phase<kZero0>(lds, par, a, wave, lane);
+        }
+        kept_w = w;
         __syncthreads();  // B2
         NMI_GRID_STAMP(4);
         if (kOptimistic && (a.phase_mask & 3) == 3 && lds.total[par] != (uint32_t)a.npix) {
@@ -168,8 +183,9 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void NMI_GRID_KERNEL_NAME(GridAr
             break;
         }
         if (wave == 0) {
-            if (a.phase_mask & 2) final_phase(lds, a, lane, p, w, s, prev_key);
-            for (int t = lane; t < kBins; t += 64) lds.hist_warped[t] = 0;
+            if (a.phase_mask & 2) final_phase(lds, a, lane, p, w, s, prev_key, kept, kKeepWarp ? &frame_sum : nullptr);
+            if (!kept)
+                for (int t = lane; t < kBins; t += 64) lds.hist_warped[t] = 0;
             if (lane == 0) {
                 lds.ovf_n[par] = 0;       // consumed by this candidate's decode; next used two candidates on
                 lds.total[par ^ 1] = 0;   // read by everyone right after the previous B2; next candidate adds to it

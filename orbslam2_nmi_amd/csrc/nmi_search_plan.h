@@ -55,6 +55,7 @@ struct SearchPlan {
     int workgroups = 0;        // grid of the launch (masked and level forms: of their grid kernel; their pixel-range launchers size themselves)
     int phase_mask = 3;        // what the kernel gets: the masked and level forms pass on the hand-off test hook (bit 9) only
     bool order_table = false;  // the launch reads an XCD-aware visiting order
+    bool shared_order = false; // ... the one that keeps a warp per workgroup (build_search_order): nmi_grid_kernel's own launches only
     bool probe = false;        // the launch doubles as a content probe (GridArgs::plan)
     bool scratch = false;      // the launch is the pipelined kernel's (ablation build): it needs the drained-counter slabs
     bool used_cooldown = false;  // a split form was held back by the pause: the caller takes one unit off it
@@ -181,10 +182,91 @@ inline SearchPlan plan_search(const PlanInputs &in)
     } else {
         plan.kind = few ? SearchKernel::few_levels : SearchKernel::grid;
         plan.order_table = in.xcd_tiling && in.total <= (1ll << 24);  // 4 B per candidate
+        plan.shared_order = plan.order_table && !few;
     }
     plan.scratch = in.hist_variant == 4;
     plan.probe = !plan.parts && in.hist_variant == 3 && in.content_path != 0;  // (the few-levels launch carries its own probe's plan)
     return plan;
+}
+
+// ---- visiting orders (host) ----------------------------------------------------------------------------------------------------
+// Workgroup b of a launch of `grid` workgroups visits the ordinals slot, slot + grid, slot + 2 grid, ... of the order table, where
+// slot = slot_in_round(b, grid) (nmi_grid_device.h); workgroups are dealt to the 8 XCDs round-robin.
+
+// Today's tiles: kTileW warps x kTileS renders (32 candidates = the 32 workgroups one XCD runs at a time), tile after tile; within
+// a tile render-fastest.  Independent of the grid.
+inline void build_tile_order(int S, int Wn, int *order)
+{
+    const int tile_s = S >= 8 ? 8 : (S >= 4 ? 4 : (S >= 2 ? 2 : 1)), tile_w = 32 / tile_s;
+    int64_t o = 0;
+    for (int w0 = 0; w0 < Wn; w0 += tile_w)
+        for (int s0 = 0; s0 < S; s0 += tile_s)
+            for (int w = w0; w < w0 + tile_w && w < Wn; ++w)
+                for (int s = s0; s < s0 + tile_s && s < S; ++s) order[o++] = w * S + s;
+}
+
+// The slot at position `pos` when the slots of a launch are listed XCD by XCD.  A grid that is a multiple of 8: slot_in_round has
+// done that already (slots [x grid/8, (x + 1) grid/8) run on XCD x).  Any other grid: slot = workgroup, XCD = slot % 8.
+inline int order_slot_at(int pos, int grid)
+{
+    if ((grid & 7) == 0) return pos;
+    for (int x = 0; x < 8; ++x) {
+        const int n = (grid - x + 7) / 8;
+        if (pos < n) return x + 8 * pos;
+        pos -= n;
+    }
+    return -1;
+}
+
+// A visiting order in which every workgroup of a launch of `grid` workgroups keeps ONE warp: the candidates at the ordinals
+// slot + k grid share w, so that nmi_grid_kernel forms the frame marginal once per workgroup.  With R = ceil(S Wn / grid) rounds, a
+// slot has R candidates (the first A slots) or R - 1 (the other B); warp w gets x_w slots of the first kind and y_w of the second
+// with R x_w + (R - 1) y_w = S, i.e. y_w = y0 + j_w R with y0 = -S mod R, and the j_w add up so that the y_w use up B (spread over
+// the last warps, one R at a time).  Slots are handed out in XCD order (order_slot_at), warp after warp, and slot t of a warp's m = x + y slots
+// takes render k m + t in round k: the 32 workgroups of an XCD then hold 32 / m + 1 or + 2 warps and, in one round, the same m
+// renders -- 13 or 14 images for 27 x 27 on 243 or 256 workgroups (m = 9, 10), where the tiles hold 12.
+// -> false, `order` untouched, where no such split exists (one round only, S or Wn of 1, S not reachable from R and R - 1).
+inline bool build_shared_order(int S, int Wn, int grid, int *order)
+{
+    const int64_t total = (int64_t)S * Wn;
+    if (S < 2 || Wn < 2 || grid < 1 || total <= grid) return false;
+    const int R = (int)((total + grid - 1) / grid);               // rounds; >= 2
+    const int A = (int)(total - (int64_t)(R - 1) * grid);         // slots [0, A) have R candidates, [A, grid) R - 1
+    const int B = grid - A;
+    const int y0 = (R - S % R) % R;
+    if ((int64_t)y0 * (R - 1) > S) return false;
+    const int x0 = (S - y0 * (R - 1)) / R;                        // (exact)
+    const int64_t rest = (int64_t)B - (int64_t)Wn * y0;
+    if (rest < 0 || rest % R) return false;
+    const int64_t J = rest / R;
+    const int jmax = x0 / (R - 1);
+    if (J > (int64_t)Wn * jmax) return false;
+    const int j_all = (int)(J / Wn), j_more = (int)(J % Wn);     // the last j_more warps take one more
+    // The slots with R candidates go to the warps in rising order and those with R - 1 in falling order, so that the one XCD that
+    // holds slots of both kinds holds them of the same (last) warps.
+    for (int kind = 0; kind < 2; ++kind) {
+        int pos = 0;
+        for (int v = 0; v < Wn; ++v) {
+            const int w = kind == 0 ? v : Wn - 1 - v;
+            const int j = j_all + (w >= Wn - j_more ? 1 : 0);
+            const int x = x0 - j * (R - 1), y = y0 + j * R, m = x + y;
+            for (int t = kind == 0 ? 0 : x; t < (kind == 0 ? x : m); ++t) {
+                int slot;
+                do slot = order_slot_at(pos++, grid);
+                while ((slot < A) != (kind == 0));
+                const int n = kind == 0 ? R : R - 1;
+                for (int k = 0; k < n; ++k) order[slot + (int64_t)k * grid] = w * S + k * m + t;
+            }
+        }
+    }
+    return true;
+}
+
+// The order a plain nmi_grid_kernel search of an S x Wn grid on `grid` workgroups reads: one warp per workgroup where that exists,
+// today's tiles otherwise.
+inline void build_search_order(int S, int Wn, int grid, int *order)
+{
+    if (!build_shared_order(S, Wn, grid, order)) build_tile_order(S, Wn, order);
 }
 
 }  // namespace nmi
