@@ -977,6 +977,22 @@ int nmi_level_create_depth_block(nmi_ctx *ctx, int32_t map_kind, const float *d_
                                  int32_t s_offset, int32_t S_total, int32_t Wn_local, int32_t w_offset, int32_t Wn_total, float point_size,
                                  const nmi_depth_shade *shade, nmi_level **out);
 int nmi_level_set_depth_shade(nmi_level *lv, const nmi_depth_shade *shade /* NULL = back to the map's colour */);
+/*
+ * Ranked peaks of a level ("Ranked peaks" below gives the rule).  nmi_level_set_peaks(lv, K, num, radius) with K in 1 .. 64 adds
+ * the peaks kernel to the level's graph, as one more node on the main chain after the search, reading the level's rating table;
+ * K = 0 takes it out again (num and radius may then be NULL).  A setting like every other: it captures the graph again, waits
+ * for a replay in flight, works with masks, coverage and every intake setting, and a refused call leaves the level as it was.
+ * nmi_level_run, its winner, its pinned word and its timing are the same with peaks on or off: the call returns at the winner,
+ * and the peaks node runs behind it on the context's stream.
+ * nmi_level_copy_peaks waits for the latest replay's peaks and copies the K keys (either pointer may be NULL, not both); h_count
+ * receives the number of non-zero keys.  Before the first replay after nmi_level_set_peaks turned them on the keys are zeros.
+ * NMI_ERR_INVALID_ARGUMENT: a NULL level, K outside 0 .. 64, with K > 0 a NULL num or radius, a count < 1, a negative radius, or
+ * num[0] * num[1] * num[2] != S or num[3] * num[4] * num[5] != Wn of the level; nmi_level_copy_peaks on a level without peaks.
+ * NMI_ERR_UNSUPPORTED: K > 0 on a block of a sharded level (greedy suppression over a block is not the suppression of the whole
+ * grid), or on a level of more than 65,536 candidates.
+ */
+int nmi_level_set_peaks(nmi_level *lv, int32_t K, const int32_t num[6], const int32_t radius[6]);
+int nmi_level_copy_peaks(nmi_level *lv, uint64_t *h_keys, int32_t *h_count);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -1106,6 +1122,38 @@ int nmi_stream_set_valid_range(nmi_stream *st, int32_t lo, int32_t hi /* 0 <= lo
 /* Packed-key helpers (host side, pure). */
 uint64_t nmi_key_pack(float score, int64_t global_linear_index);
 int nmi_key_unpack(uint64_t key, int64_t *global_linear_index, float *score);
+
+/*
+ * Ranked peaks.  The K best SEPARATED candidates of a rating table, on the device: is the winner ambiguous (a second pose,
+ * away from it, that scores almost as well), and which few poses are worth a finer level.  (New: the reference takes
+ * find_max_elements(...)[0], helperFunctions.cpp:50-103, src/Tracking.cc:1905, and nothing else of the table.)
+ *
+ * Inputs.  A rating table float [Wn][S] (nmi_search_grid's d_ratings, a level's table); the six axis counts num[6] in the axis
+ * order of nmi_host.h, S = num[0] * num[1] * num[2], Wn = num[3] * num[4] * num[5], the linear index nmi_sk_linear_index's
+ * (axis 0 fastest); K in 1 .. 64; a per-axis radius[6], every entry >= 0.
+ * Selection.  A cell qualifies when nmi_key_pack(score, index) != 0: negative scores (other than -0.0, which counts as 0.0) and
+ * NaN never do.  Peak 0 is the qualifying cell with the greatest key.  Peak j is the qualifying cell with the greatest key that
+ * is not inside the box of any of peaks 0 .. j - 1.  A cell is inside the box of peak p when |a_cell - a_p| <= radius[a] on all
+ * six axes, in axis coordinates: the box is clipped at the grid's edges and does not wrap (a cell that is linearly adjacent
+ * across a row end is no neighbour).  Selection stops after K peaks, or when no qualifying cell is left.
+ * Output.  The peaks' keys, uint64 [K], in rank order (nmi_key_unpack gives index and score); entries from `count` onward are
+ * 0; count = the number of peaks found.
+ * Everything is compares on integers and float bits: the device, nmi_find_peaks (nmi_host.h) and any model agree on every bit.
+ * With radius all zero this is a plain top-K.  Peak 0 is the winner nmi_search_grid reports for the same table.
+ *
+ * nmi_rank_peaks is enqueued on the context's stream, after whatever wrote d_ratings there: one launch of one workgroup
+ * (nmi_peaks.hip).  d_keys (device, uint64 [K]) and h_keys (host, uint64 [K]) may each be NULL, not both.  With h_keys the call
+ * blocks until the keys are there, and h_count (nullable) receives the number of non-zero keys; without h_keys it only enqueues
+ * and h_count is not written.
+ * NMI_ERR_INVALID_ARGUMENT, before anything is enqueued and with the outputs untouched: a NULL context, table, num or radius, a
+ * count < 1, K outside 1 .. 64, a negative radius, both outputs NULL.  NMI_ERR_UNSUPPORTED, likewise: a table of more than
+ * 65,536 cells (one workgroup keeps the table in its registers; a form of several launches is not provided).
+ * Not provided either: peaks of a keyframe stream's tickets, of sharded searches and blocks (greedy suppression over a block is
+ * not that of the whole grid) and of the RCCL forms; sub-cell interpolation of a peak.  The strategy driver
+ * (nmi_relocalize_with_strategy) is unchanged: it goes by the single winner.
+ */
+int nmi_rank_peaks(nmi_ctx *ctx, const float *d_ratings, const int32_t num[6], int32_t K, const int32_t radius[6],
+                   uint64_t *d_keys /* nullable */, uint64_t *h_keys /* nullable: enqueue only */, int32_t *h_count /* nullable */);
 
 /*
  * RCCL form: nmi_search_grid_shard / _block followed by ncclAllReduce(ncclMax, ncclUint64) of the key on the context's

@@ -58,6 +58,13 @@ int nmi_sk_set_best_from_index(nmi_search_kernel *k, int64_t linear_index, float
 /* Host arg-max with the reference's rule; writes up to `cap` tie indices in scan order, returns the tie count
  * (0 when no cell equals the maximum: every cell negative or NaN). */
 int64_t nmi_find_max_elements(const float *ratings, int64_t n, int64_t *ties, int64_t cap, float *max_value);
+/* The K best separated candidates of a host rating table (new; the rule is include/nmi_hip.h's "Ranked peaks", and the device
+ * form nmi_rank_peaks gives the same keys bit for bit): ratings in the linear order above, num[6] and radius[6] in the axis order
+ * of this header, K in 1 .. 64.  keys[K] receives the peaks' packed keys in rank order (nmi_key_unpack of nmi_hip.h: index and
+ * score; peak 0 is the first tie of nmi_find_max_elements), zeros after them.  Returns the number of peaks, or -1 for a NULL
+ * argument, a count < 1, a negative radius, K outside 1 .. 64 or a table whose indices do not fit 32 bits.  No limit of 65,536
+ * cells here: that is the device form's. */
+int64_t nmi_find_peaks(const float *ratings, const int32_t num[6], int32_t K, const int32_t radius[6], uint64_t *keys);
 
 /* Rendering::calculateTranslationCV for camera pose Twc and grid cell (sx, sy, sz) of `k`. */
 int nmi_calculate_translation(const float Twc[16], const nmi_search_kernel *k, int32_t sx, int32_t sy, int32_t sz,

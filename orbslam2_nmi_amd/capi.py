@@ -103,7 +103,9 @@ EXPORTED_SYMBOLS = (
     "nmi_level_set_valid_range", "nmi_stream_set_valid_range",
     "nmi_render_points_depth", "nmi_render_mesh_depth", "nmi_depth_shade_apply",
     "nmi_level_create_depth", "nmi_level_create_depth_block", "nmi_level_set_depth_shade",
+    "nmi_rank_peaks", "nmi_level_set_peaks", "nmi_level_copy_peaks",
 )
+PEAKS_MAX_K = 64   # nmi_rank_peaks: keys per call
 MAP_POINTS = 0   # nmi_level_create_depth's map_kind
 MAP_MESH = 1
 
@@ -323,6 +325,10 @@ def load_library(build_if_missing=False):
         lib.nmi_level_create_depth.argtypes = [vp, i32, vp, C.c_int64, vp, i32, i32, C.c_float, sp, C.POINTER(vp)]
         lib.nmi_level_create_depth_block.argtypes = [vp, i32, vp, C.c_int64, vp, i32, i32, i32, i32, i32, i32, C.c_float, sp, C.POINTER(vp)]
         lib.nmi_level_set_depth_shade.argtypes = [vp, sp]
+    if hasattr(lib, "nmi_rank_peaks"):
+        lib.nmi_rank_peaks.argtypes = [vp, vp, C.POINTER(i32), i32, C.POINTER(i32), vp, u64p, C.POINTER(i32)]
+        lib.nmi_level_set_peaks.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
+        lib.nmi_level_copy_peaks.argtypes = [vp, u64p, C.POINTER(i32)]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -1219,6 +1225,47 @@ class NmiContext:
                     "nmi_search_grid_block")
         return int(hk.value) if blocking else None
 
+    def rank_peaks(self, ratings, num, K, radius, keys_out=None, blocking=True):
+        """nmi_rank_peaks: the K best separated candidates of a device rating table (include/nmi_hip.h, "Ranked peaks").
+        ratings: contiguous float32 device tensor of prod(num) cells, [Wn, S] as search_grid fills it; num, radius: six ints each
+        (axis order of nmi_host.h); K in 1 .. PEAKS_MAX_K.  keys_out: optional device int64 / uint64 tensor of K elements that
+        receives the keys too.  blocking -> (keys uint64 [K] numpy, zeros after the peaks; count); else the call only enqueues
+        (keys_out is then required) and returns None."""
+        import torch
+        if not isinstance(ratings, torch.Tensor) or not ratings.is_cuda or ratings.dtype != torch.float32 or not ratings.is_contiguous():
+            raise TypeError("ratings must be a contiguous float32 device tensor")
+        num6, rad6 = (C.c_int32 * 6)(*[int(v) for v in num]), (C.c_int32 * 6)(*[int(v) for v in radius])
+        if all(v >= 1 for v in num6) and ratings.numel() != int(np.prod(list(num6), dtype=np.int64)):
+            raise ValueError("ratings must have prod(num) cells")
+        kp = None
+        if keys_out is not None:
+            if not keys_out.is_cuda or keys_out.numel() != int(K) or keys_out.element_size() != 8 or not keys_out.is_contiguous():
+                raise TypeError("keys_out must be a contiguous 64-bit device tensor of K elements")
+            kp = keys_out.data_ptr()
+        keys, n = np.zeros(max(int(K), 1), np.uint64), C.c_int32(0)
+        self._order_after_torch()
+        self._check(self._lib.nmi_rank_peaks(self._h, ratings.data_ptr(), num6, int(K), rad6, kp,
+                                             keys.ctypes.data_as(C.POINTER(C.c_uint64)) if blocking else None, C.byref(n)),
+                    "nmi_rank_peaks")
+        return (keys[:int(K)], int(n.value)) if blocking else None
+
+    def bind_rank_peaks(self, ratings, num, K, radius):
+        """The arguments of the blocking rank_peaks converted ONCE -> (call, keys): call() makes the nmi_rank_peaks call and nothing
+        else and returns the count; keys (uint64 [K] numpy) receives every call's keys.  For loops that time the call
+        (tools/peaks_time.py), as bind_search is for the search; the table must be complete on the context's stream."""
+        num6, rad6 = (C.c_int32 * 6)(*[int(v) for v in num]), (C.c_int32 * 6)(*[int(v) for v in radius])
+        keys, n = np.zeros(int(K), np.uint64), C.c_int32(0)
+        fn, handle, check = self._lib.nmi_rank_peaks, self._h, self._check
+        pr, pk, pn, cK = C.c_void_p(ratings.data_ptr()), keys.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), C.c_int32(int(K))
+        self._order_after_torch()
+
+        def call(_keep=(ratings, num6, rad6, keys)):
+            rc = fn(handle, pr, num6, cK, rad6, None, pk, pn)
+            if rc != NMI_OK:
+                check(rc, "nmi_rank_peaks")
+            return n.value
+        return call, keys
+
     def _ratings_ptr(self, ratings, Wn, S):
         import torch
         if ratings is None:
@@ -1416,6 +1463,22 @@ class NmiLevel:
         self.ctx._order_after_torch()
         self.ctx._check(self._lib.nmi_level_set_depth_shade(self._h, _shade_ref(shade, allow_none=True)), "nmi_level_set_depth_shade")
         self._shade = shade
+
+    def set_peaks(self, K, num=None, radius=None):
+        """Ranked peaks (nmi_level_set_peaks): every replay also ranks the K best separated candidates of its rating table, in one
+        more node after the search.  num, radius: six ints each (axis order of nmi_host.h; prod(num[:3]) = S, prod(num[3:]) = Wn).
+        K = 0 turns it off."""
+        num6 = None if num is None else (C.c_int32 * 6)(*[int(v) for v in num])
+        rad6 = None if radius is None else (C.c_int32 * 6)(*[int(v) for v in radius])
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_peaks(self._h, int(K), num6, rad6), "nmi_level_set_peaks")
+        self._peaks_K = int(K)
+
+    def copy_peaks(self):
+        """-> (keys uint64 [K] numpy in rank order, zeros after the peaks; count) of the latest run of a level with peaks."""
+        keys, n = np.zeros(PEAKS_MAX_K, np.uint64), C.c_int32(0)
+        self.ctx._check(self._lib.nmi_level_copy_peaks(self._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)), "nmi_level_copy_peaks")
+        return keys[:getattr(self, "_peaks_K", 0)], int(n.value)
 
     def set_distortion(self, K, dist):
         """Distorted lens (nmi_level_set_distortion): the level's frame, and a frame mask given to set_masks / set_coverage, are

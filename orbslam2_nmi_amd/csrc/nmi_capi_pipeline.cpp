@@ -6,6 +6,7 @@
 #include "nmi_intake.h"
 #include "nmi_mask_bits.h"
 #include "nmi_masked.h"
+#include "nmi_peaks.h"
 #include "nmi_reduce.h"
 #include "nmi_undistort.h"
 
@@ -35,6 +36,7 @@ struct LevelSettings {
     FrameIntake intake;
     bool depth = false;                         // the renders are depth renders (nmi_level_set_depth_shade), shaded by ...
     nmi::DepthShade shade{};                    // ... this (checked; its depth16 null: a level keeps no raw depths)
+    nmi::PeaksArgs peaks{};                     // nmi_level_set_peaks: K, the table's shape and the radii (checked); K = 0: off
 };
 
 struct nmi_level {
@@ -97,6 +99,8 @@ struct nmi_level {
     // A deep frame under a valid range, masked or covered: the validity mask its conversion node writes (ANDed with d_frame_mask,
     // which stays the caller's, read only): the frame mask of the warp masks, or, distorted, the undistortion node's raw mask.
     DeviceBuffer d_valid;                       // uint8_t [H][W]
+    // Ranked peaks (nmi_level_set_peaks): the keys of the latest replay, written by the node after the search.
+    DeviceBuffer d_peaks;                       // unsigned long long [nmi::kPeaksMaxK]
     // A deep frame (GRAY16): its tone map's histogram and table (nmi_tone.h), prepared by level_apply before the capture.
     ToneWork tone_work;
 };
@@ -126,12 +130,14 @@ struct LevelNeeds {
     bool ud_mask;  // ... and its mask: undistorted, for the warps' masks
     bool small;    // the reduced (or demosaiced, or tone-mapped) grey frame the undistortion node reads
     bool valid;    // the validity mask of a deep frame under a valid range, for the warps' masks: d_valid
+    bool peaks;    // ranked peaks: d_peaks
 };
 
 static LevelNeeds level_needs(const LevelSettings &s)
 {
     const bool mode = s.masked || s.covered;
-    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes(), s.intake.validity() && mode};
+    return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes(), s.intake.validity() && mode,
+            s.peaks.K > 0};
 }
 
 struct LevelBuffer {
@@ -154,7 +160,8 @@ static std::vector<LevelBuffer> level_buffers(nmi_level *lv, const LevelSettings
             {&lv->d_ud, npix, 0, n.ud},
             {&lv->d_ud_mask, npix, 0, n.ud_mask},
             {&lv->d_small, npix, 0, n.small},
-            {&lv->d_valid, npix, 0, n.valid}};
+            {&lv->d_valid, npix, 0, n.valid},
+            {&lv->d_peaks, nmi::kPeaksMaxK * sizeof(unsigned long long), nmi::kPeaksMaxK * sizeof(unsigned long long), n.peaks}};
 }
 
 // Captures the level's graph for lv->set and instantiates it, replacing the previous one only on success.  The caller has waited
@@ -270,6 +277,13 @@ static int level_capture(nmi_level *lv)
             ok(nmi::launch_pix(a, lv->pix, pix_owner_share(ctx, lv->pix), true, d_epoch, ctx->d_pix_timeouts.as<uint32_t>(), st));
         else
             ok(nmi::launch_grid(a, workgroups, true, st));
+        // Ranked peaks: one more node on the main chain, after the search (whichever of its kernels) has filled the table.
+        if (set.peaks.K > 0) {
+            nmi::PeaksArgs pk = set.peaks;
+            pk.ratings = a.ratings;
+            pk.out = lv->d_peaks.as<unsigned long long>();
+            ok(nmi::launch_peaks(pk, st));
+        }
         hipError_t ec = hipStreamEndCapture(st, &graph);
         ok(ec);
     }
@@ -753,6 +767,42 @@ int nmi_level_set_depth_shade(nmi_level *lv, const nmi_depth_shade *shade)
 }
 
 int nmi_level_set_frame_format(nmi_level *lv, int32_t format, int64_t pitch) { return nmi_level_set_frame_reduction(lv, 1, format, pitch); }
+
+int nmi_level_set_peaks(nmi_level *lv, int32_t K, const int32_t num[6], const int32_t radius[6])
+{
+    if (!lv || K < 0 || K > nmi::kPeaksMaxK || (K > 0 && (!num || !radius))) return NMI_ERR_INVALID_ARGUMENT;
+    nmi::PeaksArgs pk{};
+    if (K > 0) {
+        const int shape = nmi::peaks_shape(num, radius, pk);
+        if (shape == -1) return NMI_ERR_INVALID_ARGUMENT;
+        // greedy suppression over a block is not the suppression of the whole grid
+        if (lv->S != lv->S_total || lv->Wn != lv->Wn_total) return NMI_ERR_UNSUPPORTED;
+        if ((int64_t)num[0] * num[1] * num[2] != lv->S || (int64_t)num[3] * num[4] * num[5] != lv->Wn) return NMI_ERR_INVALID_ARGUMENT;
+        if (shape != 0) return NMI_ERR_UNSUPPORTED;
+        pk.K = K;
+    }
+    LevelSettings next = lv->set;
+    next.peaks = pk;
+    return level_apply(lv, next, "nmi_level_set_peaks");
+}
+
+int nmi_level_copy_peaks(nmi_level *lv, uint64_t *h_keys, int32_t *h_count)
+{
+    if (!lv || lv->set.peaks.K < 1 || (!h_keys && !h_count)) return NMI_ERR_INVALID_ARGUMENT;
+    nmi_ctx *ctx = lv->ctx;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // nmi_level_run returns at the winner, before the peaks node has run
+    const int K = lv->set.peaks.K;
+    uint64_t keys[nmi::kPeaksMaxK];
+    NMI_HIP_TRY(ctx, hipMemcpy(keys, lv->d_peaks.as<>(), (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (h_keys) memcpy(h_keys, keys, (size_t)K * sizeof(uint64_t));
+    if (h_count) {
+        int32_t n = 0;
+        while (n < K && keys[n] != 0) ++n;
+        *h_count = n;
+    }
+    return NMI_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Streaming pipeline (config 5): double-buffered render stacks, copy stream beside the compute stream.

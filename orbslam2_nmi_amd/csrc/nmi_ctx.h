@@ -133,6 +133,10 @@ struct nmi_ctx {
     nmi::ToneSetting tone;
     nmi_internal::ToneWork tone_work;
     nmi::ValidRange valid;                // nmi_set_valid_range: which raw values count in those statistics and in validity masks
+    // Ranked peaks (nmi_capi_peaks.cpp): where nmi_rank_peaks' kernel writes its keys when the caller reads them back -- mapped
+    // host memory, so that the blocking form is one launch and one polled word, no copy.  Allocated on first use.
+    PinnedBuffer h_peaks;                 // unsigned long long [nmi::kPeaksMaxK + 1], fine-grained: the keys, then the number of the call that wrote them
+    unsigned long long peaks_seq = 0;     // blocking nmi_rank_peaks calls so far
     nmi_mem::Event ev_start, ev_stop;
     int hist_variant = 3;
     int phase_mask = 3;

@@ -19,7 +19,7 @@ EXPORTED_SYMBOLS = (
     "nmi_config_parse", "nmi_config_load", "nmi_map_load_obj", "nmi_map_load_xyz", "nmi_map_load_bmp", "nmi_map_free",
     "nmi_config_parse_distortion", "nmi_config_load_distortion", "nmi_config_parse_lens", "nmi_config_load_lens",
     "nmi_config_parse_color_order", "nmi_config_load_color_order", "nmi_config_reduce",
-    "nmi_map_load_obj_colored",
+    "nmi_map_load_obj_colored", "nmi_find_peaks",
 )
 
 
@@ -97,6 +97,8 @@ def _lib():
         lib.nmi_sk_set_best_from_index.argtypes = [skp, C.c_int64, C.c_float]
         lib.nmi_find_max_elements.argtypes = [f32p, C.c_int64, C.POINTER(C.c_int64), C.c_int64, f32p]
         lib.nmi_find_max_elements.restype = C.c_int64
+        lib.nmi_find_peaks.argtypes = [f32p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        lib.nmi_find_peaks.restype = C.c_int64
         lib.nmi_calculate_translation.argtypes = [f32p, skp, C.c_int32, C.c_int32, C.c_int32, f32p]
         lib.nmi_calculate_relocalization.argtypes = [f32p, skp, f32p]
         lib.nmi_mat4_inverse.argtypes = [f32p, f32p]
@@ -169,6 +171,20 @@ def find_max_elements(ratings, cap=None):
     n = _lib().nmi_find_max_elements(r.ctypes.data_as(C.POINTER(C.c_float)), r.size,
                                      ties.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(mx))
     return ties[:min(n, cap)].tolist(), int(n), np.float32(mx.value)
+
+
+def find_peaks(ratings, num, K, radius):
+    """nmi_find_peaks: the K best separated candidates of a host rating table (include/nmi_hip.h, "Ranked peaks") ->
+    (keys uint64 [K] in rank order, zeros after the peaks; count).  num, radius: six ints each, axis order of AXES."""
+    r = np.ascontiguousarray(ratings, np.float32).reshape(-1)
+    num6, rad6 = (C.c_int32 * 6)(*[int(v) for v in num]), (C.c_int32 * 6)(*[int(v) for v in radius])
+    if r.size != int(np.prod([int(v) for v in num], dtype=np.int64)):
+        raise ValueError("ratings must have prod(num) entries")
+    keys = np.zeros(max(int(K), 1), np.uint64)
+    n = _lib().nmi_find_peaks(r.ctypes.data_as(C.POINTER(C.c_float)), num6, int(K), rad6, keys.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if n < 0:
+        raise ValueError(f"nmi_find_peaks failed: {n}")
+    return keys[:int(K)], int(n)
 
 
 def calculate_translation(Twc, k, sx, sy, sz):
