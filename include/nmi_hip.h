@@ -29,6 +29,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nmi_refined_peak.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -46,7 +48,8 @@ extern "C" {
                                  nmi_level_set_frame_reduction, nmi_stream_set_frame_reduction, and after
                                  nmi_undistort_frame_fisheye, nmi_level_set_distortion_fisheye,
                                  nmi_stream_set_distortion_fisheye, and after nmi_level_set_valid_range,
-                                 nmi_stream_set_valid_range */
+                                 nmi_stream_set_valid_range, and after nmi_refine_peaks, nmi_level_set_refine,
+                                 nmi_level_copy_refined */
 
 /* Error codes.  HIP errors are reported as NMI_ERR_HIP - (int)hipError_t, RCCL as NMI_ERR_RCCL - (int)ncclResult_t. */
 #define NMI_OK 0
@@ -993,6 +996,19 @@ int nmi_level_set_depth_shade(nmi_level *lv, const nmi_depth_shade *shade /* NUL
  */
 int nmi_level_set_peaks(nmi_level *lv, int32_t K, const int32_t num[6], const int32_t radius[6]);
 int nmi_level_copy_peaks(nmi_level *lv, uint64_t *h_keys, int32_t *h_count);
+/*
+ * Refined peaks of a level ("Refined peaks" below gives the rule).  nmi_level_set_refine(lv, on) with on != 0 adds the refine
+ * kernel to the level's graph, as one more node behind the peaks node, reading the keys that node wrote and the level's rating
+ * table; on = 0 takes it out again, and so does nmi_level_set_peaks with K = 0.  A setting like every other (see
+ * nmi_level_set_peaks): nmi_level_run, its winner, its pinned word and its timing are the same with it on or off.
+ * nmi_level_copy_refined waits for the latest replay's records and copies the K of them (K as given to nmi_level_set_peaks;
+ * either pointer may be NULL, not both); h_count receives the number of records with a key.  Before the first replay after
+ * nmi_level_set_refine turned them on the records are zeros.
+ * NMI_ERR_INVALID_ARGUMENT: a NULL level; nmi_level_set_refine on a level whose peaks are off; nmi_level_copy_refined on a level
+ * without refined peaks.  NMI_ERR_UNSUPPORTED: a block of a sharded level, as for its peaks.
+ */
+int nmi_level_set_refine(nmi_level *lv, int32_t on);
+int nmi_level_copy_refined(nmi_level *lv, nmi_refined_peak *h_records, int32_t *h_count);
 int nmi_level_destroy(nmi_level *lv);
 
 /*
@@ -1149,11 +1165,72 @@ int nmi_key_unpack(uint64_t key, int64_t *global_linear_index, float *score);
  * count < 1, K outside 1 .. 64, a negative radius, both outputs NULL.  NMI_ERR_UNSUPPORTED, likewise: a table of more than
  * 65,536 cells (one workgroup keeps the table in its registers; a form of several launches is not provided).
  * Not provided either: peaks of a keyframe stream's tickets, of sharded searches and blocks (greedy suppression over a block is
- * not that of the whole grid) and of the RCCL forms; sub-cell interpolation of a peak.  The strategy driver
- * (nmi_relocalize_with_strategy) is unchanged: it goes by the single winner.
+ * not that of the whole grid) and of the RCCL forms.  Sub-cell interpolation of a peak is "Refined peaks", next.  The strategy
+ * driver (nmi_relocalize_with_strategy) is unchanged: it goes by the single winner.
  */
 int nmi_rank_peaks(nmi_ctx *ctx, const float *d_ratings, const int32_t num[6], int32_t K, const int32_t radius[6],
                    uint64_t *d_keys /* nullable */, uint64_t *h_keys /* nullable: enqueue only */, int32_t *h_count /* nullable */);
+
+/*
+ * Refined peaks.  The quadratic through the 3 x ... x 3 neighbourhood of a peak of a rating table, on the device: the pose between
+ * the cells (a level's worth of precision without rendering, warping or scoring anything), the interpolated score, and the
+ * Hessian -- how sharp the optimum is on each axis and how the axes trade off, which is what tells an ambiguous search from a flat
+ * one and what a back end wants as the weight of a relocalisation.  (New: the reference reaches finer poses only by halving the
+ * step, src/Tracking.cc:2088-2130, and fixes NMI keyframes in BA with no weight, src/Optimizer.cc:82,548.)
+ *
+ * Inputs.  A rating table float [Wn][S]; num[6], axis order and linear index as for "Ranked peaks"; K keys, 1 <= K <= 64, as
+ * nmi_rank_peaks writes them.  Output.  K records nmi_refined_peak (nmi_refined_peak.h, 152 bytes), record k for key k.
+ * For a record, c is the cell of the key's index, f0 the table's value at c, f(c + ...) the table's value at a neighbour; the
+ * score bits of the key are copied and not used.  A sample is USABLE when it is >= 0 (so -0.0 is) and finite: "qualifies" of the
+ * peaks rule, plus finiteness.  All arithmetic is fp32, one rounding per operation, in the order written here.
+ *  1. Empty record.  A key of 0, or an index that is not below the number of cells: every byte 0 but flags = NMI_REFINE_EMPTY.
+ *     The table is not read for it.
+ *  2. Unusable centre (+inf, for a key nmi_rank_peaks wrote).  key as given, score = f0, flags = NMI_REFINE_NONFINITE, all else 0.
+ *  3. Active axes.  Axis a is active when 1 <= c_a <= num[a] - 2 and both f(c + e_a) and f(c - e_a) are usable.  num[a] == 1: no
+ *     flag.  c_a on the first or last cell of an axis with num[a] >= 2: NMI_REFINE_BORDER(a), and no neighbour on that axis is
+ *     looked at.  Else an unusable axial neighbour: NMI_REFINE_HOLE(a).  Offset, gradient and Hessian entries of an inactive axis
+ *     are 0; no sample is ever taken outside the grid or across a row end.
+ *  4. Gradient and diagonal of an active axis, f+ = f(c + e_a), f- = f(c - e_a):  g_a = 0.5f * (f+ - f-),
+ *     H_aa = (f+ - f0) + (f- - f0).
+ *  5. Cross terms of active axes a < b, f+- = f(c + e_a - e_b) and so on:  H_ab = 0.25f * ((f++ - f+-) - (f-+ - f--)).  If one of
+ *     the four is unusable, H_ab = 0 and NMI_REFINE_CROSS_HOLE is set.  A record reads at most 1 + 12 + 60 = 73 samples.
+ *  6. Coupled step.  With at least one active axis, A = -H on the active axes (A_ab = -H_ab) is factored as L D L^T without a
+ *     square root, the pivots in axis order, j ascending over the active axes, k < j and i > j over the active axes, k ascending:
+ *       d_j = A_jj - sum_k (L_jk * d_k) * L_jk        (v = A_jj; v = v - (L_jk * d_k) * L_jk for each k)
+ *       d_j > 0, or the coupled step is not accepted (NaN is not > 0)
+ *       L_ij = (A_ij - sum_k (L_ik * d_k) * L_jk) / d_j
+ *     then A x = g:  z_i = g_i - sum_{k < i} L_ik * z_k, i ascending;  x_i = z_i / d_i - sum_{k > i} L_ki * x_k, i descending, each
+ *     sum subtracted term by term, k ascending.  The step is accepted when every pivot passed and every -1 <= x_a <= 1: the offset
+ *     is x and NMI_REFINE_COUPLED is set.  The bound of 1 means that the step interpolates inside the stencil and never extrapolates.
+ *  7. Separable step, when the coupled step is not accepted: each active axis on its own.  H_aa < 0: offset_a = (-g_a) / H_aa,
+ *     clamped to [-1, 1]; otherwise offset_a = 0 and NMI_REFINE_FLAT(a) is set.
+ *  8. Score, the sums over the active axes in axis order, each from 0:
+ *       score = (f0 + sum_a g_a * o_a) + 0.5f * sum_a o_a * (sum_b H_ab * o_b).
+ * gradient and hessian (upper triangle, row-major) are those of items 4 and 5 whichever step was taken.
+ * Overflow.  Usable samples are finite and >= 0, so every single difference of two samples is finite; the sums of item 4's and
+ * item 5's differences can overflow to +-inf when samples are near the top of fp32's range (NMI scores are below 2).  The offsets
+ * are in [-1, 1] even then -- a coupled x that is NaN fails its bound, and the separable quotient of a finite g_a by a negative or
+ * infinite H_aa is never NaN -- but the score of item 8 can be NaN (0 * inf), and the Hessian holds the infinities.
+ * The order of every operation is fixed by the numpy model tests/helpers/refine_np.py (float32 scalars), which is the executable
+ * statement of this rule: the device, nmi_refine_peaks_host (nmi_host.h) and the model agree on every bit of every record.
+ *
+ * nmi_refine_peaks is enqueued on the context's stream, after whatever wrote d_ratings (and d_keys) there: one launch of K
+ * workgroups of one wavefront each (nmi_refine.hip).  Exactly one of d_keys (device, uint64 [K]) and h_keys (host, uint64 [K]) is
+ * non-NULL; host keys travel in the launch's arguments and are read before the call returns.  d_out (device) and h_out (host),
+ * nmi_refined_peak [K] each, may each be NULL, not both.  With h_out the call blocks until the records are there; without it the
+ * call only enqueues.
+ * NMI_ERR_INVALID_ARGUMENT, before anything is enqueued and with the outputs untouched: a NULL context, table or num, a
+ * count < 1, K outside 1 .. 64, both keys pointers or neither, both outputs NULL.  NMI_ERR_UNSUPPORTED, likewise: a table
+ * whose indices do not fit the 32 bits a key has for them (2^32 - 1 cells or more).  The 65,536-cell limit of nmi_rank_peaks does
+ * not apply: this kernel only gathers.
+ * Not provided: refined peaks of a keyframe stream's tickets, of sharded searches and blocks and of the RCCL forms; moving a peak
+ * to a neighbouring cell and fitting again (the bound of 1 and the clamp are the rule).  The strategy driver
+ * (nmi_relocalize_with_strategy) is unchanged and still goes by whole cells; nmi_calculate_relocalization_offset and
+ * nmi_refined_covariance (nmi_host.h) turn a record into a pose and a covariance for a caller who wants them.
+ */
+int nmi_refine_peaks(nmi_ctx *ctx, const float *d_ratings, const int32_t num[6], const uint64_t *d_keys /* or */,
+                     const uint64_t *h_keys, int32_t K, nmi_refined_peak *d_out /* nullable */,
+                     nmi_refined_peak *h_out /* nullable: enqueue only */);
 
 /*
  * RCCL form: nmi_search_grid_shard / _block followed by ncclAllReduce(ncclMax, ncclUint64) of the key on the context's

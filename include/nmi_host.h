@@ -19,6 +19,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nmi_refined_peak.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -65,12 +67,28 @@ int64_t nmi_find_max_elements(const float *ratings, int64_t n, int64_t *ties, in
  * argument, a count < 1, a negative radius, K outside 1 .. 64 or a table whose indices do not fit 32 bits.  No limit of 65,536
  * cells here: that is the device form's. */
 int64_t nmi_find_peaks(const float *ratings, const int32_t num[6], int32_t K, const int32_t radius[6], uint64_t *keys);
+/* Sub-cell offset, interpolated score and Hessian of K peaks of a host rating table (new; the rule is include/nmi_hip.h's "Refined
+ * peaks", and the device form nmi_refine_peaks gives the same records bit for bit): keys[K] as nmi_find_peaks or nmi_rank_peaks
+ * write them, K in 1 .. 64; records[K] receives record k for key k.  Returns the number of records with a key that names a cell
+ * (the others are empty records), or -1 for a NULL argument, a count < 1, K outside 1 .. 64 or a table whose indices do not fit 32
+ * bits. */
+int64_t nmi_refine_peaks_host(const float *ratings, const int32_t num[6], const uint64_t *keys, int32_t K, nmi_refined_peak *records);
+/* (-H)^-1 of a refined peak on its active axes -- the covariance of the pose under the quadratic, up to the caller's scale for the
+ * score -- in the units of the steps: cov[6 a + b] = step[a] * step[b] * ((-H)^-1)_ab, metres and radians; rows and columns of
+ * inactive axes are 0.  *active_mask (nullable) receives bit a for every active axis.  Computed in double.  Returns 0, or -1 for a
+ * NULL argument, a record whose step was not the coupled one (no NMI_REFINE_COUPLED: -H is then not known to be positive
+ * definite; cov and the mask are untouched), or a -H that is not positive definite in double. */
+int nmi_refined_covariance(const nmi_refined_peak *record, const float step[6], double cov[36], uint32_t *active_mask);
 
 /* Rendering::calculateTranslationCV for camera pose Twc and grid cell (sx, sy, sz) of `k`. */
 int nmi_calculate_translation(const float Twc[16], const nmi_search_kernel *k, int32_t sx, int32_t sy, int32_t sz,
                               float out_xyz[3]);
 /* Tracking::CalculateNMIRelocalization: refined Twc from the best indices of `k`. */
 int nmi_calculate_relocalization(const float Twc[16], const nmi_search_kernel *k, float out_Twc[16]);
+/* The same with real-valued cells (new): the pose of the cell best + offset, offset[6] in cells as nmi_refined_peak gives it.
+ * rot_a = ((float)(best_a - num_a / 2) + offset_a) * step_a with the integer n / 2, and the translation of the render cell
+ * (best + offset) through the same direction vectors.  With a zero offset it equals nmi_calculate_relocalization on every bit. */
+int nmi_calculate_relocalization_offset(const float Twc[16], const nmi_search_kernel *k, const float offset[6], float out_Twc[16]);
 int nmi_mat4_inverse(const float m[16], float out[16]);
 
 /*

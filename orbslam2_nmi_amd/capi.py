@@ -104,8 +104,28 @@ EXPORTED_SYMBOLS = (
     "nmi_render_points_depth", "nmi_render_mesh_depth", "nmi_depth_shade_apply",
     "nmi_level_create_depth", "nmi_level_create_depth_block", "nmi_level_set_depth_shade",
     "nmi_rank_peaks", "nmi_level_set_peaks", "nmi_level_copy_peaks",
+    "nmi_refine_peaks", "nmi_level_set_refine", "nmi_level_copy_refined",
 )
 PEAKS_MAX_K = 64   # nmi_rank_peaks: keys per call
+# nmi_refined_peak (include/nmi_refined_peak.h), 152 bytes, and its flags
+REFINED_PEAK = np.dtype([("key", np.uint64), ("offset", np.float32, 6), ("score", np.float32), ("flags", np.uint32),
+                         ("gradient", np.float32, 6), ("hessian", np.float32, 21), ("reserved", np.uint32)])
+assert REFINED_PEAK.itemsize == 152
+REFINE_EMPTY, REFINE_NONFINITE, REFINE_COUPLED, REFINE_CROSS_HOLE = 1, 2, 4, 8
+
+
+def refine_border(a):
+    return 0x100 << a
+
+
+def refine_hole(a):
+    return 0x10000 << a
+
+
+def refine_flat(a):
+    return 0x1000000 << a
+
+
 MAP_POINTS = 0   # nmi_level_create_depth's map_kind
 MAP_MESH = 1
 
@@ -329,6 +349,10 @@ def load_library(build_if_missing=False):
         lib.nmi_rank_peaks.argtypes = [vp, vp, C.POINTER(i32), i32, C.POINTER(i32), vp, u64p, C.POINTER(i32)]
         lib.nmi_level_set_peaks.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
         lib.nmi_level_copy_peaks.argtypes = [vp, u64p, C.POINTER(i32)]
+    if hasattr(lib, "nmi_refine_peaks"):
+        lib.nmi_refine_peaks.argtypes = [vp, vp, C.POINTER(i32), vp, u64p, i32, vp, vp]
+        lib.nmi_level_set_refine.argtypes = [vp, i32]
+        lib.nmi_level_copy_refined.argtypes = [vp, vp, C.POINTER(i32)]
     lib.nmi_key_pack.argtypes = [C.c_float, C.c_int64]
     lib.nmi_key_pack.restype = C.c_uint64
     lib.nmi_key_unpack.argtypes = [C.c_uint64, i64p, f32p]
@@ -1266,6 +1290,38 @@ class NmiContext:
             return n.value
         return call, keys
 
+    def refine_peaks(self, ratings, num, keys, records_out=None, blocking=True):
+        """nmi_refine_peaks: sub-cell offset, interpolated score and Hessian of K peaks of a device rating table
+        (include/nmi_hip.h, "Refined peaks").  ratings, num: as rank_peaks takes them.  keys: the K keys, 1 <= K <= PEAKS_MAX_K, as
+        rank_peaks gives them -- a contiguous 64-bit device tensor (read in stream order) or a host sequence / uint64 array (they
+        travel with the launch).  records_out: optional device uint8 tensor of K * 152 bytes that receives the records too.
+        blocking -> REFINED_PEAK [K] numpy; else the call only enqueues (records_out is then required) and returns None."""
+        import torch
+        if not isinstance(ratings, torch.Tensor) or not ratings.is_cuda or ratings.dtype != torch.float32 or not ratings.is_contiguous():
+            raise TypeError("ratings must be a contiguous float32 device tensor")
+        num6 = (C.c_int32 * 6)(*[int(v) for v in num])
+        if all(v >= 1 for v in num6) and ratings.numel() != int(np.prod(list(num6), dtype=np.int64)):
+            raise ValueError("ratings must have prod(num) cells")
+        dk = hk = None
+        if isinstance(keys, torch.Tensor):
+            if not keys.is_cuda or keys.element_size() != 8 or not keys.is_contiguous():
+                raise TypeError("device keys must be a contiguous 64-bit device tensor")
+            K, dk = keys.numel(), keys.data_ptr()
+        else:
+            host = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+            K, hk = host.size, host.ctypes.data_as(C.POINTER(C.c_uint64))
+        op = None
+        if records_out is not None:
+            if (not records_out.is_cuda or records_out.dtype != torch.uint8 or records_out.numel() != K * REFINED_PEAK.itemsize
+                    or not records_out.is_contiguous()):
+                raise TypeError("records_out must be a contiguous uint8 device tensor of K * 152 bytes")
+            op = records_out.data_ptr()
+        records = np.zeros(max(K, 1), REFINED_PEAK)
+        self._order_after_torch()
+        self._check(self._lib.nmi_refine_peaks(self._h, ratings.data_ptr(), num6, dk, hk, K, op, records.ctypes.data if blocking else None),
+                    "nmi_refine_peaks")
+        return records[:K] if blocking else None
+
     def _ratings_ptr(self, ratings, Wn, S):
         import torch
         if ratings is None:
@@ -1479,6 +1535,19 @@ class NmiLevel:
         keys, n = np.zeros(PEAKS_MAX_K, np.uint64), C.c_int32(0)
         self.ctx._check(self._lib.nmi_level_copy_peaks(self._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)), "nmi_level_copy_peaks")
         return keys[:getattr(self, "_peaks_K", 0)], int(n.value)
+
+    def set_refine(self, on=True):
+        """Refined peaks (nmi_level_set_refine): every replay also refines the peaks of set_peaks, in one more node behind theirs.
+        Needs set_peaks with K > 0; set_peaks(0) turns it off too."""
+        self.ctx._order_after_torch()
+        self.ctx._check(self._lib.nmi_level_set_refine(self._h, 1 if on else 0), "nmi_level_set_refine")
+
+    def copy_refined(self):
+        """-> (records REFINED_PEAK [K] numpy, record k for peak k of copy_peaks; count) of the latest run of a level with refined
+        peaks."""
+        records, n = np.zeros(PEAKS_MAX_K, REFINED_PEAK), C.c_int32(0)
+        self.ctx._check(self._lib.nmi_level_copy_refined(self._h, records.ctypes.data, C.byref(n)), "nmi_level_copy_refined")
+        return records[:getattr(self, "_peaks_K", 0)], int(n.value)
 
     def set_distortion(self, K, dist):
         """Distorted lens (nmi_level_set_distortion): the level's frame, and a frame mask given to set_masks / set_coverage, are

@@ -8,6 +8,7 @@
 #include "nmi_masked.h"
 #include "nmi_peaks.h"
 #include "nmi_reduce.h"
+#include "nmi_refine.h"
 #include "nmi_undistort.h"
 
 using namespace nmi_internal;
@@ -37,6 +38,7 @@ struct LevelSettings {
     bool depth = false;                         // the renders are depth renders (nmi_level_set_depth_shade), shaded by ...
     nmi::DepthShade shade{};                    // ... this (checked; its depth16 null: a level keeps no raw depths)
     nmi::PeaksArgs peaks{};                     // nmi_level_set_peaks: K, the table's shape and the radii (checked); K = 0: off
+    bool refine = false;                        // nmi_level_set_refine: the peaks are refined too (only with peaks.K > 0)
 };
 
 struct nmi_level {
@@ -101,6 +103,8 @@ struct nmi_level {
     DeviceBuffer d_valid;                       // uint8_t [H][W]
     // Ranked peaks (nmi_level_set_peaks): the keys of the latest replay, written by the node after the search.
     DeviceBuffer d_peaks;                       // unsigned long long [nmi::kPeaksMaxK]
+    // Refined peaks (nmi_level_set_refine): the records of the latest replay, written by the node after the peaks node.
+    DeviceBuffer d_refined;                     // nmi_refined_peak [nmi::kRefineMaxK]
     // A deep frame (GRAY16): its tone map's histogram and table (nmi_tone.h), prepared by level_apply before the capture.
     ToneWork tone_work;
 };
@@ -131,13 +135,14 @@ struct LevelNeeds {
     bool small;    // the reduced (or demosaiced, or tone-mapped) grey frame the undistortion node reads
     bool valid;    // the validity mask of a deep frame under a valid range, for the warps' masks: d_valid
     bool peaks;    // ranked peaks: d_peaks
+    bool refine;   // refined peaks: d_refined
 };
 
 static LevelNeeds level_needs(const LevelSettings &s)
 {
     const bool mode = s.masked || s.covered;
     return {mode, s.masked, s.covered, s.intake.own_frame(), s.intake.distorted && mode, s.intake.two_nodes(), s.intake.validity() && mode,
-            s.peaks.K > 0};
+            s.peaks.K > 0, s.refine};
 }
 
 struct LevelBuffer {
@@ -161,7 +166,8 @@ static std::vector<LevelBuffer> level_buffers(nmi_level *lv, const LevelSettings
             {&lv->d_ud_mask, npix, 0, n.ud_mask},
             {&lv->d_small, npix, 0, n.small},
             {&lv->d_valid, npix, 0, n.valid},
-            {&lv->d_peaks, nmi::kPeaksMaxK * sizeof(unsigned long long), nmi::kPeaksMaxK * sizeof(unsigned long long), n.peaks}};
+            {&lv->d_peaks, nmi::kPeaksMaxK * sizeof(unsigned long long), nmi::kPeaksMaxK * sizeof(unsigned long long), n.peaks},
+            {&lv->d_refined, nmi::kRefineMaxK * sizeof(nmi_refined_peak), nmi::kRefineMaxK * sizeof(nmi_refined_peak), n.refine}};
 }
 
 // Captures the level's graph for lv->set and instantiates it, replacing the previous one only on success.  The caller has waited
@@ -283,6 +289,17 @@ static int level_capture(nmi_level *lv)
             pk.ratings = a.ratings;
             pk.out = lv->d_peaks.as<unsigned long long>();
             ok(nmi::launch_peaks(pk, st));
+            // Refined peaks: one more node behind it, reading the keys it wrote and the same table.
+            if (set.refine) {
+                nmi::RefineArgs rf;
+                rf.ratings = a.ratings;
+                for (int i = 0; i < 6; ++i) rf.num[i] = pk.num[i];
+                rf.cells = (uint32_t)pk.cells;
+                rf.K = pk.K;
+                rf.keys = pk.out;
+                rf.out = lv->d_refined.as<nmi_refined_peak>();
+                ok(nmi::launch_refine(rf, st));
+            }
         }
         hipError_t ec = hipStreamEndCapture(st, &graph);
         ok(ec);
@@ -783,6 +800,7 @@ int nmi_level_set_peaks(nmi_level *lv, int32_t K, const int32_t num[6], const in
     }
     LevelSettings next = lv->set;
     next.peaks = pk;
+    if (K == 0) next.refine = false;  // nothing to refine
     return level_apply(lv, next, "nmi_level_set_peaks");
 }
 
@@ -799,6 +817,34 @@ int nmi_level_copy_peaks(nmi_level *lv, uint64_t *h_keys, int32_t *h_count)
     if (h_count) {
         int32_t n = 0;
         while (n < K && keys[n] != 0) ++n;
+        *h_count = n;
+    }
+    return NMI_OK;
+}
+
+int nmi_level_set_refine(nmi_level *lv, int32_t on)
+{
+    if (!lv) return NMI_ERR_INVALID_ARGUMENT;
+    if (lv->S != lv->S_total || lv->Wn != lv->Wn_total) return NMI_ERR_UNSUPPORTED;  // as the peaks of a block
+    if (lv->set.peaks.K < 1) return NMI_ERR_INVALID_ARGUMENT;
+    LevelSettings next = lv->set;
+    next.refine = on != 0;
+    return level_apply(lv, next, "nmi_level_set_refine");
+}
+
+int nmi_level_copy_refined(nmi_level *lv, nmi_refined_peak *h_records, int32_t *h_count)
+{
+    if (!lv || !lv->set.refine || (!h_records && !h_count)) return NMI_ERR_INVALID_ARGUMENT;
+    nmi_ctx *ctx = lv->ctx;
+    DeviceGuard guard(ctx->device);
+    NMI_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // nmi_level_run returns at the winner, before these nodes have run
+    const int K = lv->set.peaks.K;
+    nmi_refined_peak records[nmi::kRefineMaxK];
+    NMI_HIP_TRY(ctx, hipMemcpy(records, lv->d_refined.as<>(), (size_t)K * sizeof(nmi_refined_peak), hipMemcpyDeviceToHost));
+    if (h_records) memcpy(h_records, records, (size_t)K * sizeof(nmi_refined_peak));
+    if (h_count) {
+        int32_t n = 0;
+        while (n < K && records[n].key != 0) ++n;  // (empty records follow the peaks: none in between)
         *h_count = n;
     }
     return NMI_OK;

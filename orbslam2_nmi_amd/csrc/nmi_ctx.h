@@ -137,6 +137,10 @@ struct nmi_ctx {
     // host memory, so that the blocking form is one launch and one polled word, no copy.  Allocated on first use.
     PinnedBuffer h_peaks;                 // unsigned long long [nmi::kPeaksMaxK + 1], fine-grained: the keys, then the number of the call that wrote them
     unsigned long long peaks_seq = 0;     // blocking nmi_rank_peaks calls so far
+    // Refined peaks (nmi_capi_refine.cpp): the same for nmi_refine_peaks -- one posted word per record, since each record is a
+    // workgroup of its own.  Allocated on first use.
+    PinnedBuffer h_refine;                // fine-grained: nmi_refined_peak [nmi::kRefineMaxK], then unsigned long long [nmi::kRefineMaxK]: the number of the call that wrote record k
+    unsigned long long refine_seq = 0;    // blocking nmi_refine_peaks calls so far
     nmi_mem::Event ev_start, ev_stop;
     int hist_variant = 3;
     int phase_mask = 3;

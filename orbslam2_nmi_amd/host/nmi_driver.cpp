@@ -209,10 +209,10 @@ int nmi_mat4_inverse(const float m[16], float out[16])
 // (ioData.cpp:177-197: position = translation column, view direction = third column, up = second column):
 //   dir_y = up / |up|, dir_z = -view / |view|, dir_x = dir_y rotated by -90 degrees about dir_z,
 //   translation = sum over axes of (index - (n-1)/2) * step * dir.
-int nmi_calculate_translation(const float Twc[16], const nmi_search_kernel *k, int32_t sx, int32_t sy, int32_t sz,
-                              float out_xyz[3])
+// The cell is real-valued here (fx, fy, fz): a whole cell for nmi_calculate_translation, a cell plus a sub-cell offset for
+// nmi_calculate_relocalization_offset.
+static void translation_of_cell(const float Twc[16], const nmi_search_kernel *k, float fx, float fy, float fz, float out_xyz[3])
 {
-    if (!Twc || !k || !out_xyz) return -1;
     const float up[3] = {Twc[1], Twc[5], Twc[9]};
     const float view[3] = {Twc[2], Twc[6], Twc[10]};
     float len = sqrtf(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
@@ -231,19 +231,25 @@ int nmi_calculate_translation(const float Twc[16], const nmi_search_kernel *k, i
     const float ox = ((float)k->num[SX] - 1.0f) / 2.0f, oy = ((float)k->num[SY] - 1.0f) / 2.0f,
                 oz = ((float)k->num[SZ] - 1.0f) / 2.0f;
     for (int i = 0; i < 3; ++i)
-        out_xyz[i] = ((float)sx - ox) * k->step[SX] * dx[i] + ((float)sy - oy) * k->step[SY] * dy[i] +
-                     ((float)sz - oz) * k->step[SZ] * dz[i];
+        out_xyz[i] = (fx - ox) * k->step[SX] * dx[i] + (fy - oy) * k->step[SY] * dy[i] + (fz - oz) * k->step[SZ] * dz[i];
+}
+
+int nmi_calculate_translation(const float Twc[16], const nmi_search_kernel *k, int32_t sx, int32_t sy, int32_t sz,
+                              float out_xyz[3])
+{
+    if (!Twc || !k || !out_xyz) return -1;
+    translation_of_cell(Twc, k, (float)sx, (float)sy, (float)sz, out_xyz);
     return 0;
 }
 
 // Tracking::CalculateNMIRelocalization, Tracking.cc:2374-2419: rot_a = (best_a - n_a/2) * stepRad_a with integer
 // n/2, R = Rz*Ry*Rx, newLoc = Twc * [R|0], then the translation of the best render cell is added to the last column.
-int nmi_calculate_relocalization(const float Twc[16], const nmi_search_kernel *k, float out_Twc[16])
+// The cell is best + off (off: six zeros for the reference's whole cells; adding 0.0f changes no bit of the integers' floats).
+static void relocalization_of_cell(const float Twc[16], const nmi_search_kernel *k, const float off[6], float out_Twc[16])
 {
-    if (!Twc || !k || !out_Twc) return -1;
-    const float rx = (float)(k->best[WX] - k->num[WX] / 2) * k->step[WX];
-    const float ry = (float)(k->best[WY] - k->num[WY] / 2) * k->step[WY];
-    const float rz = (float)(k->best[WZ] - k->num[WZ] / 2) * k->step[WZ];
+    const float rx = ((float)(k->best[WX] - k->num[WX] / 2) + off[WX]) * k->step[WX];
+    const float ry = ((float)(k->best[WY] - k->num[WY] / 2) + off[WY]) * k->step[WY];
+    const float rz = ((float)(k->best[WZ] - k->num[WZ] / 2) + off[WZ]) * k->step[WZ];
     Mat4 Rx = identity(), Ry = identity(), Rz = identity(), T;
     Rx.at(1, 1) = cosf(rx), Rx.at(1, 2) = -sinf(rx), Rx.at(2, 1) = sinf(rx), Rx.at(2, 2) = cosf(rx);
     Ry.at(0, 0) = cosf(ry), Ry.at(0, 2) = sinf(ry), Ry.at(2, 0) = -sinf(ry), Ry.at(2, 2) = cosf(ry);
@@ -251,11 +257,25 @@ int nmi_calculate_relocalization(const float Twc[16], const nmi_search_kernel *k
     memcpy(T.m, Twc, sizeof T.m);
     const Mat4 n = mul(T, mul(Rz, mul(Ry, Rx)));
     float t[3];
-    nmi_calculate_translation(Twc, k, k->best[SX], k->best[SY], k->best[SZ], t);
+    translation_of_cell(Twc, k, (float)k->best[SX] + off[SX], (float)k->best[SY] + off[SY], (float)k->best[SZ] + off[SZ], t);
     memcpy(out_Twc, n.m, sizeof n.m);
     out_Twc[3] += t[0];
     out_Twc[7] += t[1];
     out_Twc[11] += t[2];
+}
+
+int nmi_calculate_relocalization(const float Twc[16], const nmi_search_kernel *k, float out_Twc[16])
+{
+    if (!Twc || !k || !out_Twc) return -1;
+    const float whole[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    relocalization_of_cell(Twc, k, whole, out_Twc);
+    return 0;
+}
+
+int nmi_calculate_relocalization_offset(const float Twc[16], const nmi_search_kernel *k, const float offset[6], float out_Twc[16])
+{
+    if (!Twc || !k || !offset || !out_Twc) return -1;
+    relocalization_of_cell(Twc, k, offset, out_Twc);
     return 0;
 }
 

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import load_library
+from .capi import REFINED_PEAK, load_library
 
 LENS_RADTAN = 0   # NMI_LENS_*: the model of config_parse_lens
 LENS_FISHEYE = 1
@@ -20,6 +20,7 @@ EXPORTED_SYMBOLS = (
     "nmi_config_parse_distortion", "nmi_config_load_distortion", "nmi_config_parse_lens", "nmi_config_load_lens",
     "nmi_config_parse_color_order", "nmi_config_load_color_order", "nmi_config_reduce",
     "nmi_map_load_obj_colored", "nmi_find_peaks",
+    "nmi_refine_peaks_host", "nmi_calculate_relocalization_offset", "nmi_refined_covariance",
 )
 
 
@@ -99,6 +100,11 @@ def _lib():
         lib.nmi_find_max_elements.restype = C.c_int64
         lib.nmi_find_peaks.argtypes = [f32p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
         lib.nmi_find_peaks.restype = C.c_int64
+        if hasattr(lib, "nmi_refine_peaks_host"):   # (absent from an older build named by NMI_HIP_LIBRARY: tools/refine_time.py times one)
+            lib.nmi_refine_peaks_host.argtypes = [f32p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]
+            lib.nmi_refine_peaks_host.restype = C.c_int64
+            lib.nmi_calculate_relocalization_offset.argtypes = [f32p, skp, f32p, f32p]
+            lib.nmi_refined_covariance.argtypes = [C.c_void_p, f32p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
         lib.nmi_calculate_translation.argtypes = [f32p, skp, C.c_int32, C.c_int32, C.c_int32, f32p]
         lib.nmi_calculate_relocalization.argtypes = [f32p, skp, f32p]
         lib.nmi_mat4_inverse.argtypes = [f32p, f32p]
@@ -185,6 +191,43 @@ def find_peaks(ratings, num, K, radius):
     if n < 0:
         raise ValueError(f"nmi_find_peaks failed: {n}")
     return keys[:int(K)], int(n)
+
+
+def refine_peaks(ratings, num, keys):
+    """nmi_refine_peaks_host: sub-cell offset, interpolated score and Hessian of the peaks `keys` (as find_peaks gives them) of a host
+    rating table (include/nmi_hip.h, "Refined peaks") -> records, a numpy array of capi.REFINED_PEAK, one per key."""
+    r = np.ascontiguousarray(ratings, np.float32).reshape(-1)
+    num6 = (C.c_int32 * 6)(*[int(v) for v in num])
+    if r.size != int(np.prod([int(v) for v in num], dtype=np.int64)):
+        raise ValueError("ratings must have prod(num) entries")
+    k = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    records = np.zeros(max(k.size, 1), REFINED_PEAK)
+    n = _lib().nmi_refine_peaks_host(r.ctypes.data_as(C.POINTER(C.c_float)), num6, k.ctypes.data_as(C.POINTER(C.c_uint64)), k.size,
+                                     records.ctypes.data)
+    if n < 0:
+        raise ValueError(f"nmi_refine_peaks_host failed: {n}")
+    return records[:k.size]
+
+
+def refined_covariance(record, step):
+    """nmi_refined_covariance: (-H)^-1 of a refined peak on its active axes, scaled by the steps -> (cov float64 [6, 6],
+    active_mask), or None when the record's step was not the coupled one."""
+    rec = np.array(record, REFINED_PEAK).reshape(-1)[:1].copy()
+    st, sp = _f32(step, 6)
+    cov, mask = np.zeros(36, np.float64), C.c_uint32(0)
+    if _lib().nmi_refined_covariance(rec.ctypes.data, sp, cov.ctypes.data_as(C.POINTER(C.c_double)), C.byref(mask)) != 0:
+        return None
+    return cov.reshape(6, 6), int(mask.value)
+
+
+def calculate_relocalization_offset(Twc, k, offset):
+    """nmi_calculate_relocalization_offset: calculate_relocalization for the real-valued cell best + offset."""
+    t, tp = _f32(Twc, 16)
+    o, op = _f32(offset, 6)
+    out = np.zeros(16, np.float32)
+    if _lib().nmi_calculate_relocalization_offset(tp, C.byref(k), op, out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("nmi_calculate_relocalization_offset failed")
+    return out.reshape(4, 4)
 
 
 def calculate_translation(Twc, k, sx, sy, sz):
