@@ -1,6 +1,6 @@
 """Builds orbslam2_nmi_amd/lib/libnmi_hip.so (gfx950) in-tree with hipcc.
 
-The shared library is the product: HIP kernels (csrc/nmi_kernels.hip scoring, csrc/nmi_producers.hip warp / render
+The shared library is the product: HIP kernels (csrc/nmi_grid_kernel.h + csrc/nmi_kernels*.hip scoring, csrc/nmi_producers.hip warp / render
 stacks) + the C ABI of include/nmi_hip.h (csrc/nmi_capi*.cpp over csrc/nmi_ctx.h) + the host-side mirror of the
 reference's driver types (host/*.cpp, include/nmi_host.h).
 """
@@ -56,8 +56,7 @@ def flags(ablations=False):
 
 
 def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None):
-    """One object per source under lib/obj/ (recompiled when the source, any header or -- for the nmi_kernels_* wrappers --
-    nmi_kernels.hip is newer), compiled in parallel, then one link.  Same flags for every translation unit; no relocatable
+    """One object per source under lib/obj/ (recompiled when the source or any header is newer), compiled in parallel, then one link.  Same flags for every translation unit; no relocatable
     device code (no kernel calls across units).  Objects and the library are written under private names and renamed, and one builder
     runs at a time (flock): concurrent callers wait and then find nothing left to do."""
     import fcntl
@@ -79,16 +78,11 @@ def compile_and_link(out, ablations=False, force=False, verbose=False, jobs=None
     with open(os.path.join(LIB_DIR, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         newest_header = max(os.path.getmtime(f) for f in headers() + [os.path.abspath(__file__)])
-        # nmi_grid_kernel is compiled more than once, through wrappers that #include its file (nmi_kernels_{gated,stamped,
-        # rows}.hip): those depend on nmi_kernels.hip too; shared device code is in headers.
-        grid_src = os.path.join(PKG, "csrc", "nmi_kernels.hip")
         todo, objs = [], []
         for src in sources():
             obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
             objs.append(obj)
             dep = max(os.path.getmtime(src), newest_header)
-            if os.path.basename(src).startswith("nmi_kernels_"):
-                dep = max(dep, os.path.getmtime(grid_src))
             if force or not os.path.exists(obj) or os.path.getmtime(obj) < dep:
                 todo.append((src, obj))
         if todo:

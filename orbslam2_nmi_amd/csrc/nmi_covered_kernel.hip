@@ -56,14 +56,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_grid_kernel(Cov
     unsigned long long prev_key = 0;
     const int slot = from_list ? (int)blockIdx.x : slot_in_round(blockIdx.x, gridDim.x);
     if (slot < total) {
-        {
-            uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
-            const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
-        }
-        if (tid < kBins) lds.hist_warped[tid] = 0;
-        if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;
-        if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;  // never set here; the decode reads them
+        clear_lds(lds, tid);
         __syncthreads();
     }
     int par = 0;
@@ -95,47 +88,18 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_covered_grid_kernel(Cov
             if (lane == 0) m.counts[p] = (int32_t)len;
             // a 16-bit counter wrapped (the sum of the decoded counters falls short of the pixels added): leave it to the redo
             if (kOptimistic && lds.total[par] != len) {
-                if (lane == 0) m.redo[__hip_atomic_fetch_add(m.redo_n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = p;
+                if (lane == 0) redo_append(m, p);
             } else {
                 covered_final_phase(lds, a, len, lane, p, w, s, prev_key);
             }
-            for (int t = lane; t < kBins; t += 64) lds.hist_warped[t] = 0;
-            if (lane == 0) {
-                lds.ovf_n[par] = 0;      // consumed by this candidate's decode; next used two candidates on
-                lds.total[par ^ 1] = 0;  // read by everyone right after the previous B2; next candidate adds to it
-            }
+            retire_candidate(lds, par, lane);
         }
     }
 
     if (wave == 0) {
-        if (from_list && lane == 0) {
-            // the list is consumed: the workgroup that arrives last (everyone has read the count) leaves it empty
-            if (__hip_atomic_fetch_add(m.redo_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-                __hip_atomic_store(m.redo_n, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(m.redo_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (from_list && lane == 0) redo_consumed(m);
         finish_search(a, lane, prev_key, gridDim.x);
     }
-}
-
-template <bool BG, bool SHIFTED>
-static void launch_covered_pair(const CoveredGridArgs &m, int workgroups, bool exact, hipStream_t stream)
-{
-    const dim3 grid(workgroups), block(kBlock);
-    if (exact) {
-        CoveredGridArgs e = m;
-        e.redo = nullptr;
-        hipLaunchKernelGGL((nmi_covered_grid_kernel<BG, SHIFTED, 1>), grid, block, 0, stream, e);
-        return;
-    }
-    CoveredGridArgs o = m;  // the optimistic launch publishes nothing; the exact one after it does
-    o.g.mailbox = nullptr;
-    o.g.out_key = nullptr;
-    o.g.score_post = nullptr;
-    hipLaunchKernelGGL((nmi_covered_grid_kernel<BG, SHIFTED, 3>), grid, block, 0, stream, o);
-    if (hipPeekAtLastError() != hipSuccess) return;
-    hipLaunchKernelGGL((nmi_covered_grid_kernel<BG, SHIFTED, 1>), grid, block, 0, stream, m);
 }
 
 hipError_t launch_grid_covered(const CoveredGridArgs &m, int workgroups, bool use_bg, bool exact, hipStream_t stream)
@@ -143,13 +107,9 @@ hipError_t launch_grid_covered(const CoveredGridArgs &m, int workgroups, bool us
     const bool shifted = m.g.shift != 0;
     exact = exact || (!use_bg && shifted);  // BG off below 256 bins: the rule looks at raw values, bin 0 also holds 1 .. 2^shift - 1
     if (m.g.plan || !m.counts || (!exact && (!m.redo || !m.redo_n || !m.redo_done))) return hipErrorInvalidValue;
-    if (use_bg) {
-        if (shifted) launch_covered_pair<true, true>(m, workgroups, exact, stream);
-        else launch_covered_pair<true, false>(m, workgroups, exact, stream);
-    } else {
-        if (shifted) launch_covered_pair<false, true>(m, workgroups, exact, stream);
-        else launch_covered_pair<false, false>(m, workgroups, exact, stream);
-    }
+    with_bg_shifted(use_bg, shifted, [&](auto bg, auto sh) {
+        launch_redo_pair<CoveredGridArgs>(nmi_covered_grid_kernel<bg.value, sh.value, 3>, nmi_covered_grid_kernel<bg.value, sh.value, 1>, m, workgroups, exact, stream);
+    });
     return hipGetLastError();
 }
 

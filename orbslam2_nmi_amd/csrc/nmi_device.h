@@ -1,6 +1,7 @@
-// nmi_device.h -- device-side helpers shared by the scoring kernels (nmi_kernels.hip: one workgroup per candidate;
-// nmi_split_kernel.hip: K workgroups per candidate): the reference's stride-halving trees as DPP / in-lane adds, the
-// score formulas, the packed arg-max key and the launch-completion protocol.
+// nmi_device.h -- device-side helpers shared by the scoring kernels (nmi_grid_kernel.h: one workgroup per candidate;
+// nmi_split_kernel.hip: K workgroups per candidate; nmi_fewlevels_kernel.hip): the reference's stride-halving trees as DPP /
+// in-lane adds, a workgroup's slot in a round (slot_in_round), the score formulas, the packed arg-max key and the
+// launch-completion protocol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +66,10 @@ __device__ __forceinline__ bool flat_hint(const uint4 &rv, const uint4 &wv)
                  : "vcc");
     return m == __builtin_amdgcn_read_exec();
 }
+
+// Slot of workgroup `b` in a round of `grid` candidates (candidate_at, nmi_grid_device.h, explains the placement): workgroups are
+// dealt to the 8 XCDs round-robin, so the workgroups of one XCD take consecutive ordinals of the visiting order.
+__device__ __forceinline__ int slot_in_round(int b, int grid) { return (grid & 7) == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b; }
 
 // Score from the three completed (<= 0) entropy sums, NMI.cu:342-362 (the reference reads them across blocks without
 // synchronisation, NMI.cu:340-342; this is the intended value), then: rating store, debug sums, and the arg-max update.

@@ -216,8 +216,6 @@ __global__ __launch_bounds__(256) void nmi_rank_kernel(const uint8_t *__restrict
 }
 
 // ---- scoring ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int slot_in_round(int b, int grid) { return (grid & 7) == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b; }
-
 // 16 pixels of one lane: byte address of the counter = rank_r * stride_r + (rank_w << shift_w) + copy * 4.
 __device__ __forceinline__ void add_chunk_ranks(char *base, const uint4 &rv, const uint4 &wv, uint32_t stride_r, uint32_t shift_w,
                                                 uint32_t copy4)

@@ -1,7 +1,7 @@
-// nmi_grid_device.h -- nmi_grid_kernel's device functions (nmi_kernels.hip), shared by every scoring kernel that keeps
-// a whole packed joint histogram per workgroup: the LDS layout, the chunk / pixel adders, histogram_phase, decode_phase,
-// final_phase, finish_search and exact_candidate.  Everything is in an unnamed namespace: each translation unit gets its own
-// copy, inlined into its own kernels.
+// nmi_grid_device.h -- nmi_grid_kernel's device functions (nmi_grid_kernel.h), shared by every scoring kernel that keeps
+// a whole packed joint histogram per workgroup: the LDS layout, the seams of a candidate (clear_lds, retire_candidate), the chunk /
+// pixel adders, histogram_phase, decode_phase, final_phase, finish_search and exact_candidate.  Everything is in an unnamed
+// namespace: each translation unit gets its own copy, inlined into its own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,8 +55,36 @@ struct Lds {
 // 640x480, inside its 4 MiB L2) instead of ~29.  nmi_grid_kernel's own plain searches read an order that also keeps one warp per
 // workgroup over its rounds (build_search_order, nmi_search_plan.h: 13-14 images per XCD and round for 27 x 27), so that the frame
 // marginal is formed once per workgroup.  Placement is a speed matter only; any order gives the same results.
-__device__ __forceinline__ int slot_in_round(int b, int grid) { return (grid & 7) == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b; }
+// (slot_in_round: nmi_device.h)
 __device__ __forceinline__ int candidate_at(const GridArgs &a, int ordinal) { return a.order ? a.order[ordinal] : ordinal; }
+
+// ---- the seams of the one-workgroup-per-candidate kernels (nmi_grid_kernel keeps its own text: profiles/grid_templates) ----
+// The small state beside the joint words to zero: the frame marginal, both parities' event counts and totals, the side counters
+// (kernels that never fold a flat chunk never set those, but decode_phase reads them).  A function of its own: written out inside
+// clear_lds, the same statements changed the machine code of 25 kernels instead of 12 (profiles/grid_templates/isa_vs_parent.txt).
+__device__ __forceinline__ void clear_candidate_state(Lds &lds, int tid)
+{
+    if (tid < kBins) lds.hist_warped[tid] = 0;
+    if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;
+    if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;
+}
+// Every counter of the workgroup to zero, before its first candidate.
+__device__ __forceinline__ void clear_lds(Lds &lds, int tid)
+{
+    uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
+    const uint4 z = {0, 0, 0, 0};
+    for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
+    clear_candidate_state(lds, tid);
+}
+// Wavefront 0 after it has scored the candidate of parity `par`, while the others add the next one's pixels.
+__device__ __forceinline__ void retire_candidate(Lds &lds, int par, int lane)
+{
+    for (int t = lane; t < kBins; t += 64) lds.hist_warped[t] = 0;
+    if (lane == 0) {
+        lds.ovf_n[par] = 0;      // consumed by this candidate's decode; next used two candidates on
+        lds.total[par ^ 1] = 0;  // read by everyone right after the previous B2; next candidate adds to it
+    }
+}
 
 // ---- histogram phase -------------------------------------------------------------------------------
 // One pixel -> one LDS atomic on the packed joint histogram (the reference does three atomics per
@@ -260,7 +288,7 @@ __device__ __forceinline__ void add_chunk(Lds &lds, int par, const uint4 &rv, co
 // Histogram phase for one candidate: histogram256Kernel's pixel loop, NMI.cu:79-87.
 // NT lanes (tid = 0..NT-1) share the pixels of the candidate -- on the 16-byte path the 16-pixel chunks [c_first, c_end)
 // of it (the whole pair: 0, npix / 16; nmi_pix_kernel.hip gives each of a candidate's workgroups a range of its own).
-// ROWS (nmi_kernels_rows.hip only): rows that are not whole aligned chunks -- width % 16 != 0 (KITTI's 1241 x 376), or stacks
+// ROWS (GridRows, nmi_kernels_rows.hip, only): rows that are not whole aligned chunks -- width % 16 != 0 (KITTI's 1241 x 376), or stacks
 // that are not 16-byte aligned.  Chunk c = (row y, j-th chunk of the row) starts at byte y * width + 16 j of the frame and at
 // ry * width + 16 j of the render (unaligned 16-byte loads); the width % 16 pixels left at the end of every row are added one
 // by one after the loop.  c_end is then height * (width / 16).  (Through the byte path below such frames took 4.1x the time per

@@ -1,7 +1,10 @@
-// nmi_kernels.h -- internal interface between the C ABI (nmi_capi.cpp) and the gfx950 kernels.
+// nmi_kernels.h -- internal interface between the C ABI (nmi_capi.cpp) and the gfx950 kernels: the argument records, one launcher per
+// kernel unit, and with_bg_shifted, the ladder all grid-kernel launchers share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "nmi_search_plan.h"
 
@@ -96,13 +99,25 @@ inline void set_geometry(GridArgs &a, int width, int height, const void *render_
     a.height = height;
     a.npix = width * height;
     a.vec_ok = (width % 16 == 0) && width >= 32 && (((uintptr_t)render_stack | (uintptr_t)warp_stack) % 16 == 0);
-    // widths that are not multiples of 16 (KITTI's 1241) and unaligned stacks: nmi_grid_kernel_rows takes floor(width / 16)
+    // widths that are not multiples of 16 (KITTI's 1241) and unaligned stacks: nmi_grid_kernel<GridRows, ..> takes floor(width / 16)
     // 16-byte chunks of every row with unaligned loads and the rows' last width % 16 pixels one by one (launch_grid)
     a.chunks_per_row = width >= 32 ? width / 16 : 1;
     a.cpr_magic = a.chunks_per_row > 1 ? (uint32_t)((0x100000000ull + a.chunks_per_row - 1) / a.chunks_per_row) : 0u;
     a.flip = render_bottom_up ? 1 : 0;
     a.flip_base = render_bottom_up ? (height - 1) * a.chunks_per_row : 0;
     a.flip_row = render_bottom_up ? -2 * a.chunks_per_row : 0;
+}
+
+// The launchers' ladder, written once: f(bg, shifted) with the background rule and "fewer than 256 bins" as std::bool_constant
+// values -- the first two template arguments of every grid kernel (plain, masked, covered).  What a launcher sends to the exact
+// path or refuses is its own rule, inside f.
+template <class F>
+inline void with_bg_shifted(bool use_bg, bool shifted, F &&f)
+{
+    if (use_bg && shifted) f(std::true_type{}, std::true_type{});
+    else if (use_bg) f(std::true_type{}, std::false_type{});
+    else if (shifted) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
 }
 
 hipError_t launch_table(float *table, int npix, hipStream_t stream);
@@ -128,6 +143,8 @@ hipError_t launch_fewlevels(const GridArgs &a, uint8_t *rank_renders, uint8_t *r
                             hipStream_t stream);
 int fewlevels_max_joint();  // largest nr * nw the scoring kernel takes
 bool ablation_variants_built();  // HIST variants 0 / 2 / 4 compiled in (-DNMI_BUILD_ABLATIONS)?
+// ablation build only (nmi_kernels_ablate.hip): the pipelined kernel of HIST variant 4; background rule on, no debug exports
+hipError_t launch_grid_pipelined(const GridArgs &a, int workgroups, hipStream_t stream);
 
 // Split form for grids with fewer candidates than compute units (nmi_split_kernel.hip): K workgroups per candidate, each
 // owning 256 / K complete rows (render intensities) of the joint histogram as 32-bit LDS counters.  parts = 2, 4 or 8.

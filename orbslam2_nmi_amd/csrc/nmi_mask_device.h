@@ -1,6 +1,7 @@
 // nmi_mask_device.h -- device code of the masked and covered searches (nmi_masked_kernel.hip, nmi_covered_kernel.hip,
 // their pixel-range forms and nmi_masked_level.hip): the masked chunk and pixel forms, the mask fold of the covered search,
-// its per-candidate terms and its decode / final trees.
+// its per-candidate terms and its decode / final trees, and what the masked and the covered grid kernel do alike around their
+// redo list (redo_append, redo_consumed, the launch pair).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +18,7 @@ namespace {
 __device__ __forceinline__ uint32_t nonzero_byte_bits(uint32_t v) { return (((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u; }
 
 // 16 pixels of one lane with their 16 mask bytes.  HIST 2: non-returning atomics (optimistic pass); a wavefront whose mask
-// bytes are all nonzero runs add_chunk (nmi_kernels.hip) unchanged.  The choice is per wavefront, not per lane: an LDS atomic
+// bytes are all nonzero runs add_chunk (nmi_grid_device.h) unchanged.  The choice is per wavefront, not per lane: an LDS atomic
 // costs its issue whatever the number of active lanes, so a wavefront that ran both forms for its lanes would issue 32 atomic
 // instructions per 16 pixels (measured: 1.4x the kernel time with the border masks of a rotation grid).  HIST 1: returning
 // atomics + wrap bookkeeping (exact path), in batches of 4 pixels -- 4 returned words in flight instead of add_chunk's 16
@@ -142,7 +143,7 @@ __device__ __forceinline__ float cover_term(uint32_t c, uint32_t len)
     return p * l;
 }
 
-// ---- decode phase: decode_phase (nmi_kernels.hip) with the candidate's terms -------------------------------------------------
+// ---- decode phase: decode_phase (nmi_grid_device.h) with the candidate's terms -------------------------------------------------
 // The same counters, wrap replay, trees and ZERO0 rule, word for word; what differs: counts at or above kLdsTable are
 // evaluated (cover_term) instead of read from a global table, and the side counters of fold_flat_chunk and the debug copy are
 // left out (neither exists here: the masked pixel forms never fold, and no covered entry point asks for the joint histogram).
@@ -296,7 +297,7 @@ __device__ __forceinline__ uint32_t covered_histogram_phase(Lds &lds, int par, c
     return n;
 }
 
-// final_phase (nmi_kernels.hip) with the candidate's terms: lds.table for counts below kLdsTable, evaluated above.
+// final_phase (nmi_grid_device.h) with the candidate's terms: lds.table for counts below kLdsTable, evaluated above.
 __device__ __forceinline__ void covered_final_phase(Lds &lds, const GridArgs &a, uint32_t len, int lane, int p, int w, int s,
                                                     unsigned long long &prev_key)
 {
@@ -330,6 +331,45 @@ __device__ __forceinline__ void covered_final_phase(Lds &lds, const GridArgs &a,
     const float x = row_tree_16(lane_tree_16(lo, hi));
     const float a1 = __shfl(x, 0, 64), a2 = __shfl(x, 16, 64), a3 = __shfl(x, 32, 64);
     if (lane == 0) commit_score(a, p, w, s, a1, a2, a3, prev_key);
+}
+
+// ---- the redo list of the masked and the covered grid kernel (M: MaskedGridArgs / CoveredGridArgs) ---------------------------
+// The optimistic launch (HIST 3) appends the candidates that failed its count test to m.redo; the exact launch (HIST 1) that
+// follows it scores them and leaves the list empty (why two launches: nmi_masked_kernel.hip).
+// One lane, optimistic launch: candidate p is left to the exact launch.
+template <class M>
+__device__ __forceinline__ void redo_append(const M &m, int p)
+{
+    m.redo[__hip_atomic_fetch_add(m.redo_n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = p;
+}
+// One lane of every workgroup of an exact launch that read the list, at its end: the list is consumed, and the workgroup that
+// arrives last (everyone has read the count) leaves it empty.
+template <class M>
+__device__ __forceinline__ void redo_consumed(const M &m)
+{
+    if (__hip_atomic_fetch_add(m.redo_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+        __hip_atomic_store(m.redo_n, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(m.redo_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// Host: a search as the pair of launches -- optimistic, then exact over the list -- or, `exact`, as one exact launch over the grid.
+template <class M>
+static void launch_redo_pair(void (*optimistic_kernel)(M), void (*exact_kernel)(M), const M &m, int workgroups, bool exact, hipStream_t stream)
+{
+    const dim3 grid(workgroups), block(kBlock);
+    if (exact) {
+        M e = m;
+        e.redo = nullptr;
+        hipLaunchKernelGGL(exact_kernel, grid, block, 0, stream, e);
+        return;
+    }
+    M o = m;  // the optimistic launch publishes nothing; the exact one after it does
+    o.g.mailbox = nullptr;
+    o.g.out_key = nullptr;
+    o.g.score_post = nullptr;
+    hipLaunchKernelGGL(optimistic_kernel, grid, block, 0, stream, o);
+    if (hipPeekAtLastError() != hipSuccess) return;
+    hipLaunchKernelGGL(exact_kernel, grid, block, 0, stream, m);
 }
 
 }  // namespace

@@ -35,9 +35,7 @@ namespace nmi {
 // histogram -> decode, B2 decode -> (wavefront 0: final trees + score + arg-max) || (the others: next candidate's pixels),
 // per-candidate state double-buffered by parity.
 //   HIST 3: optimistic pass (non-returning atomics) and the count test.  A candidate that fails it is not scored: it is
-//           appended to m.redo, and the HIST 1 launch that follows (m.redo set there too) scores it exactly.  nmi_grid_kernel
-//           redoes such candidates in a cold loop of its own; here that loop pushed the kernel past its 128 VGPRs into
-//           scratch, the second launch does not (and costs one launch that returns at once when nothing failed).
+//           appended to m.redo, and the HIST 1 launch that follows (m.redo set there too) scores it exactly ("Exact redo" above).
 //   HIST 1: exact throughout -- every candidate of the grid (m.redo null), or the candidates m.redo lists.
 template <bool BG, bool SHIFTED, int HIST>
 __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_grid_kernel(MaskedGridArgs m)
@@ -61,14 +59,7 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_grid_kernel(Mask
     unsigned long long prev_key = 0;
     const int slot = from_list ? (int)blockIdx.x : slot_in_round(blockIdx.x, gridDim.x);
     if (slot < total) {
-        {
-            uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
-            const uint4 z = {0, 0, 0, 0};
-            for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
-        }
-        if (tid < kBins) lds.hist_warped[tid] = 0;
-        if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;
-        if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;  // never set here; decode_phase reads them
+        clear_lds(lds, tid);
         __syncthreads();
     }
     const size_t stride = (size_t)a.npix + 1;
@@ -108,26 +99,16 @@ __global__ __launch_bounds__(NMI_BLOCK_THREADS) void nmi_masked_grid_kernel(Mask
         if (wave == 0) {
             // a 16-bit counter wrapped (the sum of the decoded counters falls short of the pixels added): leave it to the redo
             if (kOptimistic && lds.total[par] != (uint32_t)m.counts[w]) {
-                if (lane == 0) m.redo[__hip_atomic_fetch_add(m.redo_n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = p;
+                if (lane == 0) redo_append(m, p);
             } else {
                 final_phase(lds, aw, lane, p, w, s, prev_key);
             }
-            for (int t = lane; t < kBins; t += 64) lds.hist_warped[t] = 0;
-            if (lane == 0) {
-                lds.ovf_n[par] = 0;      // consumed by this candidate's decode; next used two candidates on
-                lds.total[par ^ 1] = 0;  // read by everyone right after the previous B2; next candidate adds to it
-            }
+            retire_candidate(lds, par, lane);
         }
     }
 
     if (wave == 0) {
-        if (from_list && lane == 0) {
-            // the list is consumed: the workgroup that arrives last (everyone has read the count) leaves it empty
-            if (__hip_atomic_fetch_add(m.redo_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-                __hip_atomic_store(m.redo_n, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(m.redo_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (from_list && lane == 0) redo_consumed(m);
         finish_search(a, lane, prev_key, gridDim.x);
     }
 }
@@ -190,37 +171,14 @@ hipError_t launch_mask_tables(const int32_t *counts, int Wn, int npix, float *ta
     return hipGetLastError();
 }
 
-template <bool BG, bool SHIFTED>
-static void launch_masked_pair(const MaskedGridArgs &m, int workgroups, bool exact, hipStream_t stream)
-{
-    const dim3 grid(workgroups), block(kBlock);
-    if (exact) {
-        MaskedGridArgs e = m;
-        e.redo = nullptr;
-        hipLaunchKernelGGL((nmi_masked_grid_kernel<BG, SHIFTED, 1>), grid, block, 0, stream, e);
-        return;
-    }
-    MaskedGridArgs o = m;  // the optimistic launch publishes nothing; the exact one after it does
-    o.g.mailbox = nullptr;
-    o.g.out_key = nullptr;
-    o.g.score_post = nullptr;
-    hipLaunchKernelGGL((nmi_masked_grid_kernel<BG, SHIFTED, 3>), grid, block, 0, stream, o);
-    if (hipPeekAtLastError() != hipSuccess) return;
-    hipLaunchKernelGGL((nmi_masked_grid_kernel<BG, SHIFTED, 1>), grid, block, 0, stream, m);
-}
-
 hipError_t launch_grid_masked(const MaskedGridArgs &m, int workgroups, bool use_bg, bool exact, hipStream_t stream)
 {
     const bool shifted = m.g.shift != 0;
     exact = exact || (!use_bg && shifted);  // BG off below 256 bins: the rule looks at raw values, bin 0 also holds 1 .. 2^shift - 1
     if (m.g.plan || (!exact && (!m.redo || !m.redo_n || !m.redo_done))) return hipErrorInvalidValue;
-    if (use_bg) {
-        if (shifted) launch_masked_pair<true, true>(m, workgroups, exact, stream);
-        else launch_masked_pair<true, false>(m, workgroups, exact, stream);
-    } else {
-        if (shifted) launch_masked_pair<false, true>(m, workgroups, exact, stream);
-        else launch_masked_pair<false, false>(m, workgroups, exact, stream);
-    }
+    with_bg_shifted(use_bg, shifted, [&](auto bg, auto sh) {
+        launch_redo_pair<MaskedGridArgs>(nmi_masked_grid_kernel<bg.value, sh.value, 3>, nmi_masked_grid_kernel<bg.value, sh.value, 1>, m, workgroups, exact, stream);
+    });
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // nmi_pix_device.h -- the pixel-range kernels' shared device code (nmi_pix_kernel.hip, nmi_masked_pix_kernel.hip,
 // nmi_covered_pix_kernel.hip): which workgroup scores what (pix_unit), the dealing of the pair's pieces and their addressing
-// (Deal, Pieces), the plain and the masked dealt loops, the hand-off (PixHeader, unit layout, tagged mask granules; the helper's
-// pix_publish and the owner's pix_collect), the owner's merged decode and its final trees, and the launchers' shared host code.
+// (Deal, Pieces), clear_counters (clear_lds of nmi_grid_device.h and the heal flag), the plain and the masked dealt loops, the
+// hand-off (PixHeader, unit layout, tagged mask granules; the helper's pix_publish and the owner's pix_collect), the owner's merged decode and its final trees, and the launchers' shared host code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,12 +101,7 @@ __device__ __forceinline__ PixUnit pix_unit(const GridArgs &a, int P, const Deal
 // read lds.fallback before the barrier that precedes a heal's clear.)
 __device__ __forceinline__ void clear_counters(Lds &lds, int tid)
 {
-    uint4 *j4 = reinterpret_cast<uint4 *>(lds.joint);
-    const uint4 z = {0, 0, 0, 0};
-    for (int i = tid; i < kJointWords / 4; i += kBlock) j4[i] = z;
-    if (tid < kBins) lds.hist_warped[tid] = 0;
-    if (tid < 2) lds.ovf_n[tid] = lds.total[tid] = 0;  // total[0]: decoded counters; masked forms, total[1]: pixels added by all ranges
-    if (tid < 2 * kSide) (&lds.side_key[0][0])[tid] = (&lds.side_cnt[0][0])[tid] = 0;
+    clear_lds(lds, tid);  // (total[0]: decoded counters; masked forms, total[1]: pixels added by all ranges)
     if (tid == 0) lds.fallback = 0;
 }
 
@@ -129,7 +124,7 @@ __device__ __forceinline__ void add_count(uint32_t *dst, uint32_t n, int lane)
 
 // A workgroup's piece addressing.  Chunk c = the j-th 16-byte chunk of row y: byte y * width + 16 j of the frame and of the warp
 // mask, ry * width + 16 j of the render and of its coverage mask -- rows need not be whole aligned chunks (histogram_phase's ROWS
-// form, nmi_kernels.hip); the row_rem = width % 16 pixels left per row are add_row_tails' below.  Loads are clamped to the last
+// form, nmi_grid_device.h); the row_rem = width % 16 pixels left per row are add_row_tails' below.  Loads are clamped to the last
 // chunk (a valid address); only the adds are predicated, by chunk < nchunks.
 struct Pieces {
     const GridArgs &a;
@@ -550,7 +545,7 @@ __device__ __forceinline__ void decode_merged(Lds &lds, const Terms &terms, int 
     if (i == 0) atomicAdd(&lds.total[0], wave_total);
 }
 
-// final_phase (nmi_kernels.hip: the three 256-element trees of AddVectorPairwiseKernel, NMI.cu:295-339, side by side in DPP rows
+// final_phase (nmi_grid_device.h: the three 256-element trees of AddVectorPairwiseKernel, NMI.cu:295-339, side by side in DPP rows
 // 0..2, then the score) with one difference: the marginal counts' terms come from the LDS copy of the table where the count is
 // below its 4096 entries (most of a 640x480 frame's 256 marginal bins are) and from memory only above -- the owner scores ONE
 // candidate, so the memory round trip of the lookups is on every launch's critical path instead of hidden behind the next

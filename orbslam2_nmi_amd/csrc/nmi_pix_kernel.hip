@@ -8,7 +8,7 @@
 // nmi_split_kernel.hip does not help there: a part issues one LDS atomic instruction per 64 pixels of the WHOLE pair
 // however few of its lanes own them, and the time of nmi_grid_kernel's histogram phase is its LDS atomic instructions.
 //
-// How: workgroup (candidate p, range q) runs nmi_grid_kernel's own histogram phase (NMI.cu:79-87; nmi_kernels.hip:
+// How: workgroup (candidate p, range q) runs nmi_grid_kernel's own histogram phase (NMI.cu:79-87; nmi_grid_device.h:
 // packed 16-bit counters, 129 KiB of LDS, one non-returning atomic per pixel, flat regions folded) over chunks
 // of its own.  Range 0 is the candidate's OWNER; ranges 1 .. P-1 are HELPERS: a helper writes the 16-byte units of its packed
 // histogram that hold a count (+ its flat-region side counters) to its block in memory with write-through stores, every wave

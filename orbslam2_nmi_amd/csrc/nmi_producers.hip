@@ -1,6 +1,6 @@
 // nmi_producers.hip -- gfx950 kernels of the stack producers that feed the scoring path:
 // warp stack (homography warps of the camera frame) and point-cloud render stacks (no OpenGL).  The textured-mesh
-// renderer is in nmi_mesh.hip, the scoring kernels themselves in nmi_kernels.hip.
+// renderer is in nmi_mesh.hip, the scoring kernels themselves in nmi_grid_kernel.h and nmi_kernels*.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>

@@ -178,7 +178,7 @@ __device__ __forceinline__ void add_pixel_split(uint32_t *joint, uint32_t d1, ui
 }
 
 // A chunk in the careful loop of the hot path: folded when every active lane's 16 pixels carry one (render, frame) pair
-// (see fold_flat_chunk in nmi_kernels.hip for why: 64 lanes adding to one LDS address serialise), added plainly otherwise.
+// (see fold_flat_chunk in nmi_grid_device.h for why: 64 lanes adding to one LDS address serialise), added plainly otherwise.
 template <int K>
 __device__ __forceinline__ void add_chunk_careful(uint32_t *joint, const uint4 &rv, const uint4 &wv, uint32_t xorpat, int part)
 {
@@ -202,7 +202,7 @@ __device__ __forceinline__ void add_chunk_careful(uint32_t *joint, const uint4 &
 }
 
 // 16-byte chunk c of the frame / of the render row that meets it (NMI.cu:82: row y of the frame meets row H-1-y of a
-// bottom-up render; see histogram_phase in nmi_kernels.hip).  Indices are clamped to the last chunk: loads are unconditional.
+// bottom-up render; see histogram_phase in nmi_grid_device.h).  Indices are clamped to the last chunk: loads are unconditional.
 __device__ __forceinline__ uint4 load_frame_chunk(const uint8_t *__restrict__ warped, int c, int last)
 {
     return *reinterpret_cast<const uint4 *>(warped + ((uint32_t)min(c, last) << 4));
@@ -353,7 +353,7 @@ __device__ __forceinline__ void add_short(uint32_t *joint, const ShortRange &sr,
 
 // Decode of this part's rows: counters -> per-bin terms (ComputeEntropyKernel, NMI.cu:242-263, through the per-count
 // table) -> row trees (AddvectorParwiseMidKernel, NMI.cu:270-287).  Same lane / word ownership as decode_phase in
-// nmi_kernels.hip: a wavefront takes 4 rows per pass, one per 16-lane DPP row; lane i of a row owns the bins
+// nmi_grid_device.h: a wavefront takes 4 rows per pass, one per 16-lane DPP row; lane i of a row owns the bins
 // d2 = i + 16*j, so the tree steps n = 128..16 are in-lane adds and n = 8..1 DPP shifts.  Odd DPP rows start one group
 // later so that the two rows of a 32-lane LDS access group hit disjoint banks.  Counters are cleared as they are read.
 template <int K>

@@ -174,7 +174,7 @@ def test_ragged_widths_take_the_generic_path(nmi, shape, split_mode):
 @pytest.mark.parametrize("kernel", [0, -1], ids=["grid-kernel", "auto"])
 @pytest.mark.parametrize("shape", [(641, 48), (1241, 24), (100, 60), (333, 21), (47, 33), (640, 30)])
 def test_grids_whose_rows_are_not_whole_chunks(nmi, shape, kernel):
-    """Widths that are not multiples of 16 (KITTI: 1241) and stacks that are not 16-byte aligned: nmi_grid_kernel_rows (floor(W / 16)
+    """Widths that are not multiples of 16 (KITTI: 1241) and stacks that are not 16-byte aligned: nmi_grid_kernel<GridRows, ..> (floor(W / 16)
     unaligned 16-byte chunks per row + the rows' last pixels one by one), and in automatic mode nmi_pix_kernel, which has the same
     form (such frames never take the row-split kernel: it would read them byte by byte) -- every switch, against the oracle with ==."""
     from oracle import binding as oc

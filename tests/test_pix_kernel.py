@@ -115,7 +115,7 @@ def test_counter_wraps_in_helpers_owner_and_merge(nmi):
 
 def test_flat_regions_travel_as_side_counters(nmi):
     """Large flat regions (render background 255 over a saturated sky / the frame's border 0) are folded into 32-bit side
-    counters per workgroup (fold_flat_chunk, nmi_kernels.hip); a helper's side counters travel in its block's header and
+    counters per workgroup (fold_flat_chunk, nmi_grid_device.h); a helper's side counters travel in its block's header and
     are merged into the owner's -- including the case where the owner's eight are taken."""
     from oracle import binding as oc
     rng = np.random.default_rng(11)

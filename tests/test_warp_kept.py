@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the kept frame marginal in nmi_grid_kernel (csrc/nmi_kernels.hip, decode_phase<.., KEPT> and final_phase's
+"""GPU tests (-m gpu) of the kept frame marginal in nmi_grid_kernel (csrc/nmi_grid_kernel.h, decode_phase<.., KEPT> and final_phase's
 `kept` in csrc/nmi_grid_device.h) and of the visiting order that feeds it (build_search_order, csrc/nmi_search_plan.h): a workgroup
 whose candidates stay on one warp forms the frame marginal and its entropy sum on the first of them only.  What can go wrong is a
 marginal kept across a change of warp, across a launch, into or out of the exact path after a counter wrap, with the background
@@ -145,7 +145,7 @@ def test_wrap_meets_the_kept_marginal(nmi, heavy_render):
 
 
 def test_rows_unit(nmi):
-    """Width 62: rows of 3 whole chunks and 14 single pixels, nmi_grid_kernel_rows; 9 x 9 on 27 workgroups, three candidates each."""
+    """Width 62: rows of 3 whole chunks and 14 single pixels, nmi_grid_kernel<GridRows, ..>; 9 x 9 on 27 workgroups, three candidates each."""
     rs, ws = stacks(9, 9, h=48, w=62, seed=8)
     N = nmi.NmiContext
     check(nmi, "rows", rs, ws, {N.OPT_WORKGROUPS: 27})
@@ -154,7 +154,7 @@ def test_rows_unit(nmi):
 
 def test_gated_unit_behind_the_few_levels_kernels(nmi):
     """NMI_OPT_CONTENT_PATH 1 sends the search to the few-levels kernels, whose probe finds 256 x 155 levels and hands it back on
-    the device: nmi_grid_kernel_gated scores it, on the tile order (this launch's table is the few-levels kernels')."""
+    the device: nmi_grid_kernel<GridGated, ..> scores it, on the tile order (this launch's table is the few-levels kernels')."""
     rs, ws = stacks(27, 27)
     N = nmi.NmiContext
     info = check(nmi, "27x27", rs, ws, {N.OPT_WORKGROUPS: 243, N.OPT_CONTENT_PATH: 1})

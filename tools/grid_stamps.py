@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where nmi_grid_kernel's time goes on a grid of S x Wn candidates (one workgroup per candidate): wall_clock64 stamps
 (100 MHz) at the phase boundaries of one candidate of every workgroup -- its k-th, the first by default (NMI_OPT_STAMPS,
-NMI_OPT_STAMP_CANDIDATE -> nmi_grid_kernel_stamped) -- and the moment each of the 16 wavefronts added its last pixel.
+NMI_OPT_STAMP_CANDIDATE -> nmi_grid_kernel<GridStamped, ..>, csrc/nmi_kernels_stamped.hip) -- and the moment each of the 16 wavefronts added its last pixel.
 python tools/grid_stamps.py [S Wn] [--noise] [--k K] [--shares FILE] [--calibrate N] [--out FILE]
   --k K          stamp every workgroup's K-th candidate (0 or 1 on a 27 x 27 grid: wavefront 0 scores the previous candidate
                  before it starts on the K-th's pixels when K > 0)

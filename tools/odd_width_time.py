@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The cost of frame widths that are not multiples of 16 (the histogram phase's 16-byte loads need width % 16 == 0; other widths
-take the byte path, nmi_kernels.hip): 729 candidates at 640x480 against 641x480 / 648x480, and KITTI's 1241x376 against
+take the byte path, launch_grid in nmi_kernels.hip; the rows form is nmi_kernels_rows.hip): 729 candidates at 640x480 against 641x480 / 648x480, and KITTI's 1241x376 against
 1248x376.  python tools/odd_width_time.py"""
 import os, sys
 import numpy as np

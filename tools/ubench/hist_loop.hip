@@ -11,7 +11,7 @@ constexpr int kWordsLds = 32768;
 template <int J>
 __device__ __forceinline__ void addr_val(uint32_t r, uint32_t w, uint32_t &addr, uint32_t &val)
 {
-    // the kernel's five instructions (nmi_kernels.hip, add_chunk)
+    // the kernel's five instructions (nmi_grid_device.h, add_chunk)
     uint32_t a1, a2, hi;
     const uint32_t nine = 9;
     if (J == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(a1) : "v"(nine), "v"(r));
